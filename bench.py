@@ -14,6 +14,13 @@ of the pooled fingerprints and the all-reduce of the loss statistics (RCCL); the
 `--config5`: BASELINE.json configs[4] as worded - the full training step (fwd + bwd + Adam) at atom_dim 128, 6 steps,
 data-parallel over the ranks, the gradient all-reduce inside every timed step (a line of its own: another metric).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can
+carry, each from untimed runs of its own after the timed steps: the encoder kernel alone on the chip (`roofline`), one
+stream, the whole model forward, the cost of the prepared weights, the other encoder modes, `other_configs` and the
+CPU baseline (`--no-cpu-baseline` / `--no-other-configs` drop the last two from a full run).
+`--dump-outputs DIR`: after the timed steps, rank 0 writes what its last timed step returned as DIR/<name>.npy
+(forward: the two ions' GlobalSumPool outputs; `--config5`: the loss and the trainable parameters after the step).
 """
 from __future__ import annotations
 
@@ -39,6 +46,22 @@ import torch  # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3    # MI355X_MICROARCH.md: dense f32 MFMA peak (16x16x4 / 4x4x1 f32: 256 flop/clk/CU)
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak
 PEAK_HBM_GBS = 8000.0           # HBM3E spec
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: tensor or array} -> out_dir/<name>.npy in float32 (float64 stays float64).  Beyond DUMP_LIMIT_BYTES in
+    all, every array keeps the same share of its rows: a fixed, seeded sample, in row order."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def algorithmic_flops_per_pair(N, E, D, S):
@@ -346,6 +369,10 @@ def run_config5(args, rank, world, dev, rehearsal, ndev):
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {
+            "loss": np.array([loss], dtype=np.float64),
+            "parameters": torch.cat([t.detach().reshape(-1).float() for _, t in m.trainable_variables()])})
     rows, edges = executed_counts(inp)
     fwd = S * (12 * D * D * rows + 2 * D * D * edges)
     ms = elapsed / args.steps * 1e3
@@ -389,9 +416,15 @@ def main():
                     help="BASELINE.json configs[4] as worded: the full training step (fwd + bwd + Adam) at atom_dim 128, 6 steps, "
                          "data-parallel over the ranks with the gradient all-reduce inside every timed step (default batch 4096 "
                          "pairs per rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: roofline (the encoder "
+                         "kernel alone), one stream, whole model forward, prepared weights, other encoder modes, "
+                         "other_configs and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the labelled extras for BASELINE.json configs[2] and configs[4]")
+                    help="--full without the labelled extras for BASELINE.json configs[2] and configs[4]")
     ap.add_argument("--schedule", choices=["fused", "layered"], default="fused")
     ap.add_argument("--pipeline", action="store_true",
                     help="enqueue the plan kernels of step i+1 on a side stream before the encoder of step i "
@@ -413,6 +446,8 @@ def main():
                          "faster of the two in this run (VERDICT r2, ruling on mode f32x3), else f32t's.  f16x2 (narrower "
                          "products) on request only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from ionic_mpnn_amd import _lib, dist as idist, model, ops, synthetic, weights
 
@@ -516,7 +551,7 @@ def main():
         for _ in range(args.warmup):
             pc, pa = step()
         torch.cuda.synchronize()
-        if fused:
+        if fused and args.full:  # HIP events around every encoder launch: roofline's `overlapped` figure
             _lib.check(lib.impnn_profile_enable(args.steps))
         if world > 1:
             dist.barrier()
@@ -532,7 +567,7 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
         overlapped_ms = None
-        if fused:
+        if fused and args.full:
             buf = (C.c_float * args.steps)()
             n = C.c_int32(0)
             _lib.check(lib.impnn_profile_collect(buf, args.steps, C.byref(n)))
@@ -562,6 +597,8 @@ def main():
     mode_used = min(runs, key=lambda k: runs[k]["elapsed"]) if len(runs) > 1 else candidates[0]
     main_run = runs[mode_used]
     elapsed, pc, pa = main_run["elapsed"], main_run["pc"], main_run["pa"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pooled_cation": pc, "pooled_anion": pa})
     no_coll = None
     if args.config4:  # the same K steps without the collectives, beside it
         no_coll = run_mode(mode_used, False, 30.0)["elapsed"]
@@ -575,7 +612,7 @@ def main():
         local_sum = t
     total_pairs = float(local_sum[1].item())
 
-    # ---- everything below is outside the timed region ----------------------------------------------------------
+    # ---- everything below is outside the timed region; what it measures is --full's --------------------------------
     def events_ms(fn, n):
         """mean HIP-event duration (ms) of the encoder kernel over n calls of fn on the current stream: the events
         are recorded by libimpnn around that launch alone, on the stream it is launched on"""
@@ -633,7 +670,7 @@ def main():
         return _gpu_timed(lambda: m.encode_pooled(d_in, fused=True), args.steps, warm=5)
 
     kernel_ms, single_ms, full_ms, extras, other_configs, prep_us = {}, {}, None, {}, None, None
-    if fused and rank == 0:
+    if fused and rank == 0 and args.full:
         for mode in runs:
             kernel_ms[mode] = kernel_alone_ms(mode)
             single_ms[mode] = single_stream_ms(mode)
@@ -808,7 +845,7 @@ def main():
                                        "neighbouring batches' kernels share the chip - not a roofline figure"}
         return r
 
-    rf = roofline_of(mode_used) if fused else None
+    rf = roofline_of(mode_used) if fused and args.full else None
     if rf:
         rf["whole_step"] = {"achieved": flops_launch / (ms_per_step * 1e-3) / 1e12,
                             "frac": flops_launch / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS,
@@ -817,7 +854,7 @@ def main():
         for other in runs:
             if other != mode_used:
                 out[f"roofline_{other}"] = roofline_of(other)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(inputs, w, gpu_pooled=(pc, pa))
     print(json.dumps(out), flush=True)
     if world > 1:

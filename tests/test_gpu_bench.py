@@ -33,7 +33,7 @@ def _run(cmd, timeout=420):
 
 def test_bench_line_contract_one_gpu():
     out = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--ramp-ms", "20", "--batch", "512",
-                "--no-cpu-baseline", "--no-other-configs"])
+                "--full", "--no-cpu-baseline", "--no-other-configs"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out, k
@@ -46,6 +46,32 @@ def test_bench_line_contract_one_gpu():
     assert "prepared_weights" in out["config"] and out["config"]["prepared_weights"]["us_per_weight_version"] > 0
     r = out["roofline"]
     assert r["bound"] == "mfma" and 0 < r["frac"] and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes the last timed step's pooled outputs,
+    which match the fp64 CPU port on the same seeded batch."""
+    import torch
+    from ionic_mpnn_amd import synthetic, weights
+    from oracle import torch_ref as TR
+    B, steps = 512, 7
+    out = _run([sys.executable, "bench.py", "--steps", str(steps), "--warmup", "2", "--ramp-ms", "20", "--batch", str(B),
+                "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == steps and out["value"] > 0 and out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - B) < 1e-6 * B   # value and ms_per_step: the same K steps
+    assert set(out["config"]["modes_timed"]) == {"f32t", "f32x3"}
+    for k in ("roofline", "cpu_baseline"):
+        assert k not in out, k
+    for k in ("other_configs", "other_modes", "single_stream", "full_model_forward"):
+        assert k not in out["config"], k
+    got = [np.load(tmp_path / f"pooled_{ion}.npy") for ion in ("cation", "anion")]
+    inp = synthetic.make_batch(B, max_atoms=40, max_edges=80, seed=0)
+    w = weights.init_weights("viscosity", synthetic.DEFAULT_VA, synthetic.DEFAULT_VB, atom_dim=32, bond_dim=8,
+                             num_steps=3, seed=1)
+    ref = [t.numpy() for t in TR.pooled_pair(w, {k: v[:32] for k, v in inp.items()}, torch.float64)]
+    for g, r in zip(got, ref):
+        assert g.dtype == np.float32 and g.shape == (B, 32)
+        assert np.max(np.abs(g[:32] - r)) <= 1e-5 * np.max(np.abs(r))
 
 
 @pytest.mark.parametrize("extra", [[], ["--config4"]])
