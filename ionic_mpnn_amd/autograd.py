@@ -4,52 +4,17 @@ the reference layer, each backward the matching ``impnn_*_bwd`` entry (csrc/trai
 the calls are the plain forward entries.  torch.autograd only keeps the graph - no torch op computes here.
 A model's training pass uses the larger nodes at the end of this file (a batch-32 step is bound by the number of
 launches): BondTypeMatricesAll (every layer's type matrices), MessagePassingStep (message -> Reduce -> GatedUpdate)
-and ModelHeadLoss (head + mse + l2 penalties); the per-layer nodes serve the drop-in layers called one by one."""
+and ModelHeadLoss (head + mse + l2 penalties); the per-layer nodes serve the drop-in layers called one by one.
+The message nodes take the ion's ``ops.IonGraph`` of the pass: their forwards and backwards share its edge sort by
+bond type and its message buffer, which live as long as the autograd graph that holds them."""
 from __future__ import annotations
 
 import ctypes as C
-import itertools
-import threading
 
 import torch
 
 from . import _lib, ops
 from ._lib import check, f32c, i32c, ptr, stream_ptr
-
-
-class _PassState(threading.local):  # one scope stack per host thread
-    def __init__(self):
-        self.d = {"id": None}
-
-    def __getitem__(self, k):
-        return self.d[k]
-
-    def __setitem__(self, k, v):
-        self.d[k] = v
-
-
-_pass = _PassState()
-_pass_ids = itertools.count(1)  # ids are unique across threads (next() is atomic under the GIL)
-
-
-class training_pass:
-    """Scope of ONE differentiable forward pass (MPNNModel.__call__(training=True) opens it).  Work that depends on
-    the batch's graph tensors only - the edge sort by bond type of the message backward - is shared by the nodes
-    created inside one scope and never across scopes (the tensors may be refilled in place by kernels that torch's
-    version counters do not see)."""
-
-    def __enter__(self):
-        self.prev = _pass["id"]
-        _pass["id"] = next(_pass_ids)
-        return self
-
-    def __exit__(self, *exc):
-        _pass["id"] = self.prev
-        return False
-
-
-def current_pass():
-    return _pass["id"]
 
 
 def _sink(param):
@@ -115,7 +80,9 @@ class BondTypeMatrices(torch.autograd.Function):
 
 class BondTypeMatricesAll(torch.autograd.Function):
     """The type matrices of all message layers (both ions, every step) as one node: one forward launch, two backward
-    launches (impnn_bond_type_matrices_multi[_bwd]) instead of three per layer."""
+    launches (impnn_bond_type_matrices_multi[_bwd]) instead of three per layer.  Returns the n matrices and, as a
+    non-differentiable last output, their gradient pool (n,Vb,D,D), zeroed for all layers at once (None without grad):
+    MessagePassingStep adds each layer's type-matrix gradient into its slice and hands that slice back here."""
 
     @staticmethod
     def forward(ctx, bond_table, *Ws):
@@ -128,11 +95,12 @@ class BondTypeMatricesAll(torch.autograd.Function):
         ot = (C.c_void_p * len(Ws))(*[o.data_ptr() for o in outs])
         _lib_call(bond_table.device, _lib.load().impnn_bond_type_matrices_multi, ptr(bond_table), wt, ot, len(Ws), Vb, K, D)
         ctx.save_for_backward(bond_table, *Ws)
+        pool = None
         if any(W.requires_grad for W in Ws) or bond_table.requires_grad:
             pool = torch.zeros(len(Ws), Vb, D, D, dtype=torch.float32, device=bond_table.device)  # one fill per step
-            for p, o in enumerate(outs):
-                o._impnn_dmats = pool[p]
-        return outs
+            ctx.mark_non_differentiable(pool)
+        ctx.set_materialize_grads(False)  # (no zero fill for the pool's gradient; a missing dmats is filled below)
+        return (*outs, pool)
 
     @staticmethod
     def backward(ctx, *dmats):
@@ -140,7 +108,7 @@ class BondTypeMatricesAll(torch.autograd.Function):
         Vb, K = bond_table.shape
         D = Ws[0].shape[-1]
         dmats = [f32c(d) if d is not None else torch.zeros(Vb, D, D, dtype=torch.float32, device=bond_table.device)
-                 for d in dmats]
+                 for d in dmats[:-1]]
         sinks = [_sink(W) for W in Ws]
         st = _sink(bond_table)
         use_sinks = st is not None and all(sk is not None for sk in sinks)
@@ -160,36 +128,35 @@ class BondTypeMatricesAll(torch.autograd.Function):
         return (dtb, *dWs)
 
 
+def _message_adjoint(entry, graph, h, bond_ids, conn, mats, grad, dh, dmats, scratch=None):
+    """One message-adjoint launch (``entry``: an impnn_*_bwd name) that ADDS into dh and dmats, on the edge sort of
+    the ion's graph - sorted by an earlier message call of the pass, or by this one."""
+    B, N, D = h.shape
+    E, Vb = conn.shape[1], mats.shape[0]
+    ws, ready = (graph or ops.IonGraph(None, bond_ids, conn, Vb)).edge_sort()
+    _lib_call(h.device, getattr(_lib.load(), entry), ptr(h), ptr(bond_ids), ptr(conn), ptr(mats), ptr(grad), ptr(dh),
+              ptr(dmats), ptr(ws), ws.numel(), *(() if scratch is None else (ptr(scratch),)), B, N, E, D, Vb,
+              1 if ready else 0)
+
+
 class BmmMessageTyped(torch.autograd.Function):
     """BondMatrixMessage.call in the per-bond-type schedule (models/layers.py:100-117)."""
 
     @staticmethod
-    def forward(ctx, h, bond_ids, conn, type_mats):
+    def forward(ctx, h, bond_ids, conn, type_mats, graph=None):
         h, type_mats, bond_ids, conn = f32c(h), f32c(type_mats), i32c(bond_ids), i32c(conn)
         ctx.save_for_backward(h, bond_ids, conn, type_mats)
-        ctx.graph_key = (conn, bond_ids, _pass["id"])  # the tensor OBJECTS (the S layers of one ion share them)
-        return ops.bmm_message_typed(h, bond_ids, conn, type_mats)
+        ctx.graph = graph
+        return ops.bmm_message_typed(h, bond_ids, conn, type_mats, graph)
 
     @staticmethod
     def backward(ctx, dm):
         h, bond_ids, conn, mats = ctx.saved_tensors
-        B, N, D = h.shape
-        E, Vb = conn.shape[1], mats.shape[0]
         dm = f32c(dm)
         both = torch.zeros(h.numel() + mats.numel(), dtype=torch.float32, device=h.device)  # one fill for both sums
         dh, dmats = both[:h.numel()].view_as(h), both[h.numel():].view_as(mats)
-        lib = _lib.load()
-        # the edge sort by bond type depends on (conn, bond_ids) only: shared inside a training pass
-        holder, bond_obj, pass_id = ctx.graph_key  # the objects the forward saw (saved tensors may be re-wrapped)
-        prev = _pass["id"]
-        _pass["id"] = pass_id                       # backward runs outside the with-block: re-enter its pass
-        try:
-            ws, ready = ops.edge_sort_workspace(holder, bond_obj, B, E, Vb)
-        finally:
-            _pass["id"] = prev
-        _lib_call(h.device, lib.impnn_bmm_message_typed_bwd, ptr(h), ptr(bond_ids), ptr(conn), ptr(mats),
-                  ptr(dm), ptr(dh), ptr(dmats), ptr(ws), ws.numel(), B, N, E, D, Vb, 1 if ready else 0)
-        return dh, None, None, dmats
+        _message_adjoint("impnn_bmm_message_typed_bwd", ctx.graph, h, bond_ids, conn, mats, dm, dh, dmats)
+        return dh, None, None, dmats, None
 
 
 class MessageReduceTyped(torch.autograd.Function):
@@ -198,31 +165,21 @@ class MessageReduceTyped(torch.autograd.Function):
     (impnn_message_reduce_typed_bwd), so neither the (B,E,D) messages nor their gradient outlive the forward."""
 
     @staticmethod
-    def forward(ctx, h, bond_ids, conn, type_mats):
+    def forward(ctx, h, bond_ids, conn, type_mats, graph=None):
         h, type_mats, bond_ids, conn = f32c(h), f32c(type_mats), i32c(bond_ids), i32c(conn)
         ctx.save_for_backward(h, bond_ids, conn, type_mats)
-        ctx.graph_key = (conn, bond_ids, _pass["id"])
-        m = ops.bmm_message_typed(h, bond_ids, conn, type_mats)
+        ctx.graph = graph
+        m = ops.bmm_message_typed(h, bond_ids, conn, type_mats, graph)
         return ops.reduce_scatter_add(m, conn[:, :, 1], h.shape[1])
 
     @staticmethod
     def backward(ctx, dagg):
         h, bond_ids, conn, mats = ctx.saved_tensors
-        B, N, D = h.shape
-        E, Vb = conn.shape[1], mats.shape[0]
         dagg = f32c(dagg)
         both = torch.zeros(h.numel() + mats.numel(), dtype=torch.float32, device=h.device)
         dh, dmats = both[:h.numel()].view_as(h), both[h.numel():].view_as(mats)
-        holder, bond_obj, pass_id = ctx.graph_key
-        prev = _pass["id"]
-        _pass["id"] = pass_id
-        try:
-            ws, ready = ops.edge_sort_workspace(holder, bond_obj, B, E, Vb)
-        finally:
-            _pass["id"] = prev
-        _lib_call(h.device, _lib.load().impnn_message_reduce_typed_bwd, ptr(h), ptr(bond_ids), ptr(conn), ptr(mats),
-                  ptr(dagg), ptr(dh), ptr(dmats), ptr(ws), ws.numel(), B, N, E, D, Vb, 1 if ready else 0)
-        return dh, None, None, dmats
+        _message_adjoint("impnn_message_reduce_typed_bwd", ctx.graph, h, bond_ids, conn, mats, dagg, dh, dmats)
+        return dh, None, None, dmats, None
 
 
 class ReduceScatterAdd(torch.autograd.Function):
@@ -327,12 +284,13 @@ MESSAGE_BWD_EDGE_BUFFER_MIN_SLOTS = 8192
 class MessagePassingStep(torch.autograd.Function):
     """One message-passing step as one node (train_viscosity.py:179-186: BondMatrixMessage -> Reduce -> GatedUpdate).
     Backward: impnn_gated_update_bwd writes dh and dagg, then impnn_message_reduce_typed_bwd ADDS the message path's
-    share into the same dh - no separate sum of the two consumers of h, no zero fill of dh; the type-matrix gradient
-    goes into a buffer BondTypeMatricesAll zeroed for all layers at once (``type_mats._impnn_dmats``) when there is one."""
+    share into the same dh - no separate sum of the two consumers of h, no zero fill of dh.  ``graph``: the ion's
+    ops.IonGraph of this pass (edge sort and message buffer shared with the ion's other steps); ``dmats``: this
+    layer's slice of BondTypeMatricesAll's gradient pool, where the type-matrix gradient goes when there is one."""
 
     @staticmethod
-    def forward(ctx, h, bond_ids, conn, type_mats, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, row_index=None,
-                n_rows=None, inner=False):
+    def forward(ctx, h, bond_ids, conn, type_mats, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, graph, dmats=None,
+                row_index=None, n_rows=None, inner=False):
         """row_index / n_rows (ops.kept_row_index; atom_dim 64 / 128): GatedUpdate forward and backward on the kept rows
         only - padding atoms reach neither a message nor the pool, so their rows of the output are left undefined
         and their gradient is zero (include/impnn.h, impnn_gated_update_rows[_bwd])."""
@@ -341,14 +299,10 @@ class MessagePassingStep(torch.autograd.Function):
         # inner (with a row list): this step's input is the output of another MessagePassingStep on the SAME list - that
         # node reads its incoming gradient at the listed rows only, so the rows outside the list need no zero fill here
         ctx.inner = bool(inner) and row_index is not None
-        if h.shape[-1] != 32:
-            # one message buffer per ion and pass (the Reduce behind each layer consumes it at once; at atom_dim 64 / 128
-            # the message adjoint writes its per-edge vectors there)
-            buf, reused = ops.message_scratch(conn, bond_ids, h.shape[0], conn.shape[1], h.shape[-1])
-            m = ops.bmm_message_typed(h, bond_ids, conn, type_mats, out=buf, out_reused=reused)
-            del buf
-        else:
-            m = ops.bmm_message_typed(h, bond_ids, conn, type_mats)
+        # one message buffer per ion and pass (the Reduce behind each layer consumes it at once; at atom_dim 64 / 128
+        # the message adjoint writes its per-edge vectors there)
+        buf = graph.message_buffer(h.shape[-1]) if h.shape[-1] != 32 else None
+        m = ops.bmm_message_typed(h, bond_ids, conn, type_mats, graph, out=buf)
         agg = ops.reduce_scatter_add(m, conn[:, :, 1], h.shape[1])
         del m
         ctx.row_list = (row_index, n_rows) if row_index is not None else None
@@ -361,8 +315,7 @@ class MessagePassingStep(torch.autograd.Function):
             out = ops.gated_update(h, agg, *gu, beta, eps, rows=ctx.row_list)
         ctx.save_for_backward(h, agg, *gu, beta, bond_ids, conn, type_mats)
         ctx.eps = float(eps)
-        ctx.graph_key = (conn, bond_ids, _pass["id"])
-        ctx.dmats_buf = getattr(type_mats, "_impnn_dmats", None)
+        ctx.graph, ctx.dmats = graph, dmats
         return out
 
     @staticmethod
@@ -378,29 +331,16 @@ class MessagePassingStep(torch.autograd.Function):
         dh, dagg, *dparams = _gated_update_backward(saved[:10], ctx.eps, dout, ctx.row_list, kept, ctx.inner)
         del kept
         B, N, D = h.shape
-        E, Vb = conn.shape[1], mats.shape[0]
-        dmats = ctx.dmats_buf if ctx.dmats_buf is not None else torch.zeros_like(mats)
-        holder, bond_obj, pass_id = ctx.graph_key
-        prev = _pass["id"]
-        _pass["id"] = pass_id
-        scratch, kept_zero = None, False
-        try:
-            ws, ready = ops.edge_sort_workspace(holder, bond_obj, B, E, Vb)
-            # (atom_dim 32: measured slower that way - 1.71 -> 1.88 ms per step at batch 4096 - the rows are a quarter as
-            #  long, the atomics a quarter as many, and the buffer's round trip through HBM costs the same launch)
-            if D in (64, 128) and B * E >= MESSAGE_BWD_EDGE_BUFFER_MIN_SLOTS:
-                # the forward's message buffer of this ion and pass: zero rows at masked edges, free since the Reduce
-                scratch, kept_zero = ops.message_scratch(holder, bond_obj, B, E, D)
-        finally:
-            _pass["id"] = prev
-        if scratch is not None and kept_zero:
-            _lib_call(h.device, _lib.load().impnn_message_reduce_typed_bwd_scratch, ptr(h), ptr(bond_ids), ptr(conn),
-                      ptr(mats), ptr(dagg), ptr(dh), ptr(dmats), ptr(ws), ws.numel(), ptr(scratch), B, N, E, D, Vb,
-                      1 if ready else 0)
-        else:
-            _lib_call(h.device, _lib.load().impnn_message_reduce_typed_bwd, ptr(h), ptr(bond_ids), ptr(conn), ptr(mats),
-                      ptr(dagg), ptr(dh), ptr(dmats), ptr(ws), ws.numel(), B, N, E, D, Vb, 1 if ready else 0)
-        return (dh, None, None, dmats, *dparams, None, None, None)
+        dmats = ctx.dmats if ctx.dmats is not None else torch.zeros_like(mats)
+        scratch = None
+        # (atom_dim 32: measured slower that way - 1.71 -> 1.88 ms per step at batch 4096 - the rows are a quarter as
+        #  long, the atomics a quarter as many, and the buffer's round trip through HBM costs the same launch)
+        if D in (64, 128) and B * conn.shape[1] >= MESSAGE_BWD_EDGE_BUFFER_MIN_SLOTS:
+            # the forward's message buffer of this ion and pass: zero rows at masked edges, free since the Reduce
+            scratch = ctx.graph.written_message_buffer(D)
+        entry = "impnn_message_reduce_typed_bwd" if scratch is None else "impnn_message_reduce_typed_bwd_scratch"
+        _message_adjoint(entry, ctx.graph, h, bond_ids, conn, mats, dagg, dh, dmats, scratch)
+        return (dh, None, None, dmats, *dparams) + (None,) * 5
 
 
 class GlobalSumPool(torch.autograd.Function):

@@ -294,18 +294,20 @@ class MPNNModel:
 
     def _all_type_matrices(self):
         """Training: the type matrices of every message layer from one node (3 launches per step instead of 3 per
-        layer); None where the per-layer entries are the better fit (bond_dim >= 64 is GEMM-shaped)."""
+        layer) as {(ion, step): (matrices, their slice of the node's gradient pool)}; None where the per-layer entries
+        are the better fit (bond_dim >= 64 is GEMM-shaped)."""
         if self.bond_dim >= 64 or self.num_steps == 0 or not self._builds_graph():
             return None
         from . import autograd
         keys = [(p, i) for p in ("cat", "an") for i in range(self.num_steps)]
-        mats = autograd.BondTypeMatricesAll.apply(self.bond_emb.embeddings,
-                                                  *[self.branches[p]["bmm"][i].bond_transform for p, i in keys])
-        return dict(zip(keys, mats))
+        *mats, pool = autograd.BondTypeMatricesAll.apply(
+            self.bond_emb.embeddings, *[self.branches[p]["bmm"][i].bond_transform for p, i in keys])
+        return {k: (mats[j], None if pool is None else pool[j]) for j, k in enumerate(keys)}
 
     def encode_layered(self, prefix, atom_ids, bond_ids, conn, trace=None, typed=True, type_mats=None):
-        """encode() layer at a time (train_viscosity.py:171-187) -> pooled (B,D)."""
+        """encode() layer at a time (train_viscosity.py:171-187) -> pooled (B,D); type_mats: _all_type_matrices()."""
         br = self.branches[prefix]
+        graph = ops.IonGraph(atom_ids, bond_ids, conn, self.bond_vocab_size)  # the message calls of all layers share it
         h = self.atom_emb(atom_ids)
         bond = self.bond_emb(bond_ids)
         if not typed:
@@ -326,14 +328,17 @@ class MPNNModel:
         for i in range(self.num_steps):
             if one_node:
                 from . import autograd
-                mats = type_mats[(prefix, i)] if type_mats else br["bmm"][i]._type_matrices(bond.table)
+                mats, dmats = type_mats[(prefix, i)] if type_mats else (br["bmm"][i]._type_matrices(bond.table), None)
                 u, w = br["update"][i], br["update"][i]._weights
                 h = autograd.MessagePassingStep.apply(
                     h, bond.ids, conn, mats, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
-                    w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta, u.epsilon,
+                    w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta, u.epsilon, graph, dmats,
                     *(rows if rows is not None else (None, None)), i > 0)
                 continue
-            m = br["bmm"][i]([h, bond, conn])
+            if typed:  # (the layer's own call would sort the edges again)
+                m = ops.bmm_message_typed(h, bond.ids, conn, br["bmm"][i]._type_matrices(bond.table), graph)
+            else:
+                m = br["bmm"][i]([h, bond, conn])
             agg = br["reduce"][i]([m, conn[:, :, 1], h])
             if rows is not None:
                 u, w = br["update"][i], br["update"][i]._weights
@@ -418,12 +423,11 @@ class MPNNModel:
             quiet = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
             if quiet is not None:
                 quiet(False)
-        for (p, _), mats in (tm or {}).items():
+        for (p, _), (mats, dmats) in (tm or {}).items():
             if p == "an":
                 mats.record_stream(side)
-                pool = getattr(mats, "_impnn_dmats", None)
-                if pool is not None:
-                    pool.record_stream(side)
+                if dmats is not None:
+                    dmats.record_stream(side)
         for t in an:
             t.record_stream(side)
         side.wait_stream(cur)
@@ -478,12 +482,9 @@ class MPNNModel:
         head as one autograd node over impnn_model_head_tensors / impnn_model_head_bwd."""
         inputs = self._to_device(inputs)
         if training:
-            from . import autograd
-            with autograd.training_pass():
-                pc, pa = self.encode_pooled(inputs, fused=False)
-                return self.head(pc, pa, inputs.get("temperature"), differentiable=True)
-        from . import autograd
-        with torch.no_grad(), autograd.training_pass():  # (the scope also lets the layers of an ion share graph work)
+            pc, pa = self.encode_pooled(inputs, fused=False)
+            return self.head(pc, pa, inputs.get("temperature"), differentiable=True)
+        with torch.no_grad():
             pc, pa = self.encode_pooled(inputs, fused=fused, trace=trace)
             return self.head(pc, pa, inputs.get("temperature"), trace=trace)
 
@@ -528,12 +529,11 @@ class MPNNModel:
             ws = getattr(self, "_loss_ws", None)
             if ws is None or ws.numel() < need:
                 ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
-            with autograd.training_pass():
-                pc, pa = self.encode_pooled(inputs, fused=False)
-                T = inputs.get("temperature") if self.kind == "viscosity" else None
-                return autograd.ModelHeadLoss.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
-                                                    self.mixing_size, self._head_l2(), ws, pc, pa, T, y,
-                                                    *self._head_tensors())
+            pc, pa = self.encode_pooled(inputs, fused=False)
+            T = inputs.get("temperature") if self.kind == "viscosity" else None
+            return autograd.ModelHeadLoss.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
+                                                self.mixing_size, self._head_l2(), ws, pc, pa, T, y,
+                                                *self._head_tensors())
         pred = self(inputs, training=True) if training else self(inputs)
         if training:
             return train.mse(y, pred) + self.regularization_loss()

@@ -136,67 +136,73 @@ def bond_type_matrices(bond_table, W):
     return out
 
 
-def message_scratch(conn, bond_ids, B, E, D):
-    """(buffer, reuse) - the (B,E,D) message buffer of this (conn, bond_ids) inside an ``autograd.training_pass``: the
-    layers of an ion write their messages into the same buffer one after the other (each is consumed by the Reduce right
-    behind it), so the zero rows of masked edges are written by the first layer only.  Outside a pass: (None, False)."""
-    from . import autograd
-    pass_id = autograd.current_pass()
-    if pass_id is None:
-        return None, False
-    key = (pass_id, conn._version, bond_ids.data_ptr(), bond_ids._version, B, E, D)
-    cached = getattr(conn, "_impnn_msg_scratch", None)
-    if cached is not None and cached[0] == key:
-        return cached[1], True
-    m = torch.empty(B, E, D, dtype=torch.float32, device=conn.device)
-    conn._impnn_msg_scratch = (key, m)
-    return m, False
+class IonGraph:
+    """atom_ids (B,N), bond_ids (B,E), conn (B,E,2) of one ion for one encode pass, and the device work that depends on
+    them alone, shared by the message calls of all layers of the ion, forward and backward.  Kernels may refill these
+    tensors in place without torch seeing it (the graphed training step's gather_rows): whoever does makes a new
+    IonGraph."""
+
+    def __init__(self, atom_ids, bond_ids, conn, bond_vocab_size):
+        self.atom_ids, self.bond_ids, self.conn = atom_ids, bond_ids, conn
+        self.bond_vocab_size = int(bond_vocab_size)
+        self._sort = None
+        self._messages = None
+
+    def edge_sort(self):
+        """(workspace, sorted_ready) of the edge sort by bond type.  The first call allocates the workspace and returns
+        False: the message kernel it is handed to sorts into it.  Later calls return it with True."""
+        if self._sort is not None:
+            return self._sort, True
+        B, E = self.conn.shape[0], self.conn.shape[1]
+        wsb = int(_lib.load().impnn_bmm_message_typed_bwd_workspace_bytes(B, E, self.bond_vocab_size))
+        self._sort = torch.empty(max(wsb, 4), dtype=torch.uint8, device=self.conn.device)
+        return self._sort, False
+
+    def message_buffer(self, D):
+        """(buffer, zero_rows_written) of the (B,E,D) messages: the layers of the ion write theirs into one buffer, one
+        after the other (each is consumed by the Reduce right behind it).  The first call allocates it and returns
+        False: the message kernel it is handed to writes the zero rows of masked edges.  Later calls return True."""
+        if self._messages is not None and self._messages.shape[-1] == D:
+            return self._messages, True
+        B, E = self.conn.shape[0], self.conn.shape[1]
+        self._messages = torch.empty(B, E, D, dtype=torch.float32, device=self.conn.device)
+        return self._messages, False
+
+    def written_message_buffer(self, D):
+        """The message buffer if a forward already wrote its zero rows, else None (never allocates)."""
+        m = self._messages
+        return m if m is not None and m.shape[-1] == D else None
 
 
-def bmm_message_typed(h, bond_ids, conn, type_mats, out=None, out_reused=False):
-    """``out`` / ``out_reused``: ops.message_scratch's pair (model-internal: the training loop's message buffer)."""
+def bmm_message_typed(h, bond_ids, conn, type_mats, graph=None, out=None):
+    """BondMatrixMessage.call in the per-bond-type schedule (models/layers.py:100-117) -> messages (B,E,D).
+    ``graph``: the IonGraph of (bond_ids, conn) in this pass, whose edge sort the call shares; without one the call
+    sorts on its own.  ``out``: graph.message_buffer's pair (model-internal: the training step's message buffer)."""
     if _wants_grad(h, type_mats):
         from . import autograd
-        return autograd.BmmMessageTyped.apply(h, bond_ids, conn, type_mats)
+        return autograd.BmmMessageTyped.apply(h, bond_ids, conn, type_mats, graph)
     require_gpu(h, bond_ids, conn, type_mats)
     _check_bmm_shapes(h, conn)
     h, type_mats, conn, bond_ids = f32c(h), f32c(type_mats), i32c(conn), i32c(bond_ids)
     B, N, D = h.shape
     E, Vb = conn.shape[1], type_mats.shape[0]
+    if graph is not None and graph.bond_vocab_size != Vb:
+        raise ValueError(f"type matrices for {Vb} bond types, the ion graph has {graph.bond_vocab_size}")
     if DEBUG_VALIDATE:
         validate_indices(conn=conn, bond_ids=bond_ids, N=N, Vb=Vb)
-    m = out if out is not None else torch.empty(B, E, D, dtype=torch.float32, device=h.device)
+    m, zero_rows = out if out is not None else (torch.empty(B, E, D, dtype=torch.float32, device=h.device), False)
     lib = _lib.load()
     with torch.cuda.device(h.device):
         if D != 32 and D <= 128 and E > 0 and B > 0:
             # any other width: type-sorted segments with A[type] in LDS (the D = 32 kernel sorts inside its workgroups)
-            ws, ready = edge_sort_workspace(conn, bond_ids, B, E, Vb)
-            flags = (1 if ready else 0) | (2 if out is not None and out_reused else 0)
+            ws, ready = (graph or IonGraph(None, bond_ids, conn, Vb)).edge_sort()
+            flags = (1 if ready else 0) | (2 if zero_rows else 0)
             check(lib.impnn_bmm_message_typed_sorted(ptr(h), ptr(bond_ids), ptr(conn), ptr(type_mats), ptr(m), ptr(ws),
                                                      ws.numel(), B, N, E, D, Vb, flags, stream_ptr()))
         else:
             check(lib.impnn_bmm_message_typed(ptr(h), ptr(bond_ids), ptr(conn), ptr(type_mats), ptr(m), B, N,
                                               E, D, Vb, stream_ptr()))
     return m
-
-
-def edge_sort_workspace(conn, bond_ids, B, E, Vb):
-    """Workspace of the by-bond-type edge sort for (conn, bond_ids) and whether it already holds that sort.
-    Inside an ``autograd.training_pass`` the workspace is kept on the connectivity tensor object, so the forward and
-    backward message kernels of all layers of one ion sort once; outside, every call gets a fresh workspace."""
-    from . import autograd
-    lib = _lib.load()
-    wsb = int(lib.impnn_bmm_message_typed_bwd_workspace_bytes(B, E, Vb))
-    pass_id = autograd.current_pass()
-    if pass_id is None:
-        return torch.empty(max(wsb, 4), dtype=torch.uint8, device=conn.device), False
-    key = (pass_id, conn._version, bond_ids.data_ptr(), bond_ids._version, Vb, wsb)
-    cached = getattr(conn, "_impnn_edge_sort", None)
-    if cached is not None and cached[0] == key:
-        return cached[1], True
-    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=conn.device)
-    conn._impnn_edge_sort = (key, ws)
-    return ws, False
 
 
 def reduce_scatter_add(messages, tgt_idx, num_atoms):

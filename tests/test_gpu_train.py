@@ -62,6 +62,13 @@ def test_message_reduce_backward(D, K, B, E):
     close(hf.grad, ho.grad, what="dh (one node)")
     close(Wf.grad, Wo.grad, what="dW (one node)")
     close(tbf.grad, tbo.grad, what="dbond_table (one node)")
+    # an ion graph allocates its edge sort and message buffer on the first call (False) and hands them out after (True)
+    g = ops.IonGraph(None, bg, cg, Vb)
+    assert g.written_message_buffer(D) is None
+    for get in (g.edge_sort, lambda: g.message_buffer(D)):
+        (t0, r0), (t1, r1) = get(), get()
+        assert t1 is t0 and (r0, r1) == (False, True)
+    assert g.written_message_buffer(D) is t0
 
 
 @pytest.mark.parametrize("D,Vb,from_agg,B", [(128, 12, True, 700), (64, 72, True, 700), (128, 3, False, 700), (128, 72, True, 32), (64, 9, True, 200)])
@@ -369,6 +376,39 @@ def test_wide_state_model_gradients_match_the_oracle(B, N):
     close(loss, lo, 1e-5, "loss")
     for name, t in m.trainable_variables():
         close(t.grad, wo[name].grad, 2e-4, f"grad {name}")
+
+
+def test_interleaved_training_passes_keep_their_own_graph_work():
+    """Two differentiable passes over the SAME input tensors with interleaved backwards (forward A, forward B, backward B,
+    backward A) at atom_dim 128, where the layers of an ion share the edge sort by bond type and the message buffer
+    (ops.IonGraph; B * E above the edge-buffer threshold, B * N above the row-list one): each pass gets the loss and the
+    gradients of a pass run alone, and no input tensor carries anything of the library afterwards."""
+    from ionic_mpnn_amd import autograd
+    Va, Vb, D, K, S, B = 13, 6, 128, 4, 2, 120
+    w = weights.init_weights("viscosity", Va, Vb, atom_dim=D, bond_dim=K, fp_size=12, mixing_size=10, num_steps=S, seed=21,
+                             perturb=True)
+    m = MM.build_model(Va, Vb, atom_dim=D, bond_dim=K, fp_size=12, mixing_size=10, num_steps=S, device=DEV)
+    m.load_weights(w)
+    d = m._to_device(synthetic.make_batch(B, max_atoms=36, max_edges=72, atom_vocab_size=Va, bond_vocab_size=Vb,
+                                          min_atoms=3, seed=21))
+    assert B * d["cat_connectivity"].shape[1] >= autograd.MESSAGE_BWD_EDGE_BUFFER_MIN_SLOTS
+    assert B * d["cat_atom"].shape[1] >= MM.TRAIN_ROW_LIST_MIN_ROWS
+    ys = [np.random.default_rng(s).normal(1.0, 0.5, size=B).astype(np.float32) for s in (1, 2)]
+    params = [t.requires_grad_(True) for _, t in m.trainable_variables()]  # no .grad buffers: autograd.grad returns all
+    alone = []
+    for y in ys:
+        loss = m._loss(d, y, training=True)
+        alone.append((loss.detach(), torch.autograd.grad(loss, params)))
+    loss_a = m._loss(d, ys[0], training=True)
+    loss_b = m._loss(d, ys[1], training=True)
+    got_b = torch.autograd.grad(loss_b, params)
+    got_a = torch.autograd.grad(loss_a, params)
+    for what, loss, got, (loss0, want) in (("A", loss_a, got_a, alone[0]), ("B", loss_b, got_b, alone[1])):
+        assert torch.equal(loss.detach(), loss0), what
+        for (name, _), g, g0 in zip(m.trainable_variables(), got, want):
+            close(g, g0, 2e-4, f"pass {what}: grad {name}")
+    for k, t in d.items():
+        assert not vars(t), f"{k} carries {sorted(vars(t))}"
 
 
 @pytest.mark.parametrize("D,B", [(64, 6), (32, 5)])
