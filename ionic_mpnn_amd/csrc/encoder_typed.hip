@@ -167,7 +167,9 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
   int* const run_ctr = reinterpret_cast<int*>(recl + kTRecCounts + 8);  // next dynamically assigned type run
   const uint4* const r_grp = reinterpret_cast<const uint4*>(recl + kTRecGrp);
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  // (readfirstlane: uniform to the compiler too, so the run loop's conditions stay scalar - and no register spills)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int a = lane & 15, q = lane >> 4;
   // diagnostics build only (impnn_debug_set_stamp_buffer): the stamp bookkeeping costs ~10 VGPRs
   unsigned long long* stamp = STAMPS && p.stamps ? p.stamps + (size_t)blockIdx.x * 32 : nullptr;
@@ -224,7 +226,8 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       if (m < M && part == 0) st4(out_g + (int64_t)(m0 + m) * kD + 4 * f4, acc);
     }
   };
-  // h0 = atom_table[atom id of the placed row]: 4 threads per row, 2 x 16 B each; slack rows: zeros
+  // h0 = atom_table[atom id of the placed row]: 4 threads per row, 2 x 16 B each; slack rows: zeros.  From the LDS copy of
+  // the table when there is one: step 0 then reads h like every other step (no per-group branch, a compile-time stride).
   auto fill_h0 = [&]() {
     const int row = tid >> 2, sub = tid & 3;
     const int id = r_rowatom[row];
@@ -272,7 +275,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
   const int acol = 16 * kh + 2 * ((lane >> 2) & 7);  // first of the two h columns this lane feeds (see Grp)
 
   for (int c = c_begin; c < c_end; ++c) {
-    // ---- chunk prologue: descriptor, record -> LDS, h0 = atom_table[atom ids] (only without the LDS table)
+    // ---- chunk prologue: descriptor, record -> LDS, h0 = atom_table[atom ids]
     const int4 dsc = dsc_next;
     const int m0 = __builtin_amdgcn_readfirstlane(dsc.x), M = __builtin_amdgcn_readfirstlane(dsc.y);
     const int rg = __builtin_amdgcn_readfirstlane(dsc.w);
@@ -290,7 +293,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       dsc_next = reinterpret_cast<const int4*>(p.desc)[cn];
     }
     lds_barrier();
-    if (!p.atab_lds) fill_h0();
+    fill_h0();
     if (tid == 0) *run_ctr = 2 * kWaves;  // runs 0 .. 2 kWaves - 1 are assigned statically (two per wave)
     lds_barrier();
     if (stamp && tid == 0) {
@@ -337,7 +340,6 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     if (kRunsEarly >= 1) fetch_P(0);
     if (kRunsEarly >= 2) fetch_Q(0);
     for (int s = 0; s < p.S; ++s) {
-      const bool g0 = p.atab_lds && s == 0;  // step 0 reads h0 = atom_table[id] straight from the LDS table
       const float* tm_s = tmat_g + (size_t)s * p.Vb * kTMatFloats;
       // ---- message phase: m_e = A[type_e] h[src_e], one group of <= 4 edges of one bond type per 16 MFMAs.
       // v_mfma_f32_4x4x1_16b: 16 independent 4x4 blocks.  Block b < 8 accumulates, for feature quad b, the k < 16
@@ -353,16 +355,11 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       // lanes point at a dump slot, so the stores are unconditional) and the loop body is branch-free.
       __builtin_amdgcn_s_setprio(2);
       {
-        const float* const abase = (g0 ? atab : hbuf) + acol;
-        const int astride = g0 ? kTAS : HS;
+        const float* const abase = hbuf + acol;
         auto load_group = [&](int e, Grp& G) {
           G.ge = r_grp[e];
-          int src = __builtin_amdgcn_ubfe(G.ge.y, ysh, 8);
-          if (g0) {
-            const int id = r_rowatom[src];
-            src = (unsigned)id < (unsigned)p.Va ? id : p.Va;
-          }
-          G.aq = *reinterpret_cast<const f32x2v*>(abase + src * astride);
+          const int src = __builtin_amdgcn_ubfe(G.ge.y, ysh, 8);
+          G.aq = *reinterpret_cast<const f32x2v*>(abase + src * HS);
         };
         auto compute = [&](const Grp& G, const f32x4 (&bq)[4]) {
           f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
@@ -389,13 +386,14 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
           acc0[0] = G.aq[0] + bq[0][0] + bq[3][3];
           acc1[1] = G.aq[1] + bq[1][1] + bq[2][2];
 #endif
-          acc0 += acc1;
+          // acc0 + acc1 as four v_add_f32: as a vector add the compiler emits two v_pk_add_f32, which beside MFMAs cost
+          // more issue time than the four scalar adds (the same IEEE sums either way)
+          float x0 = acc0[0] + acc1[0], x1 = acc0[1] + acc1[1], x2 = acc0[2] + acc1[2], x3 = acc0[3] + acc1[3];
           // element i of lane l: edge i, feature l & 31, k-half l >> 5.
           // v_permlane32_swap x, y: lanes 32-63 of x <-> lanes 0-31 of y.  Afterwards x = {x.lo, y.lo},
           // y = {x.hi, y.hi}, so x + y is edge 0 (2) complete in lanes 0-31 and edge 1 (3) in lanes 32-63.
           // (Inline asm: the compiler's builtin for this gfx950 instruction folded its two operands into one here.
           //  The s_nop covers the VALU-write -> permlane-read wait states the assembler does not insert.)
-          float x0 = acc0[0], x1 = acc0[1], x2 = acc0[2], x3 = acc0[3];
           asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3"
                        : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
           msg[__builtin_amdgcn_ubfe(G.ge.z, zsh, 16) ^ f] = x0 + x1;
@@ -552,14 +550,8 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
           if (kRunsEarly >= 1) fetch_P(s + 1);
           if (kRunsEarly >= 2) fetch_Q(s + 1);
         }
-        int own = row * HS + (int)(hbuf - smem);
-        if (g0) {
-          const int id = r_rowatom[row];
-          own = ((unsigned)id < (unsigned)p.Va ? id : p.Va) * kTAS + (int)(atab - smem);
-        }
-        own += 4 * q;
-        const f32x4 h0 = ld4(smem + own);
-        const f32x4 h1 = ld4(smem + own + 16);
+        const f32x4 h0 = ld4(hbuf + row * HS + 4 * q);
+        const f32x4 h1 = ld4(hbuf + row * HS + 16 + 4 * q);
 
         // ---- gates z, r (models/layers.py:144-147) and candidate (:150-151): out^T = W^T [h | agg]^T
         f32x4 z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
