@@ -443,6 +443,55 @@ int impnn_gated_update_rows_bwd_saved(const float* h, const float* agg, const fl
                                       const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
                                       int32_t accumulate, float* saved, impnn_stream_t stream);
 
+/*  GatedUpdate dropout in training (models/layers.py:156: Dropout(rate)(LN(n) + h, training=True)), fused into the
+ *  GatedUpdate kernels.  The mask is not stored: element (row, column) of the (rows, D) output, row = the flat row of
+ *  h (for row-list calls the row the list names, so both forms draw the same mask), draws word column % 4 of
+ *      Philox4x32-10(counter = (column / 4, row, layer_word, lo32(*step)),
+ *                    key     = (lo32(seed), hi32(seed) ^ hi32(*step)))
+ *  and is kept iff (word >> 8) * 2^-24 >= rate; kept: out * (1.0f / (1.0f - rate)) (one f32 multiply), dropped: +0.
+ *  layer_word = layer_id | (rank << 16).  `step` is a DEVICE int64 (a snapshot slot of impnn_dropout_step): the kernels
+ *  read it when they run, so a captured step draws a fresh mask on every replay.  0 <= rate < 1, else IMPNN_E_BADARG.
+ *  Each entry below is the entry without the suffix plus (rate, seed, step, layer_word); the forwards apply the mask on
+ *  the final store (after the residual; `saved` keeps the pre-dropout gates, candidate and r * h), the backwards read
+ *  dout through the same mask and scale.  rate == 0 gives the plain entry's results bit for bit (it is called). */
+int impnn_gated_update_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                               const float* br, const float* Wh, const float* bh, const float* gamma,
+                               const float* beta, float ln_eps, float* out, int64_t rows, int32_t D, float rate,
+                               uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream);
+/* row_index / n_rows: both or neither (NULL: all max_rows rows); saved: NULL, or as impnn_gated_update_rows_train */
+int impnn_gated_update_rows_train_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                          const float* Wr, const float* br, const float* Wh, const float* bh,
+                                          const float* gamma, const float* beta, float ln_eps, float* out,
+                                          const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                          float* saved, float rate, uint64_t seed, const int64_t* step,
+                                          int32_t layer_word, impnn_stream_t stream);
+int impnn_gated_update_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                                   const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                                   const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                                   int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate, float rate,
+                                   uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream);
+int impnn_gated_update_rows_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                        const float* Wr, const float* br, const float* Wh, const float* bh,
+                                        const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
+                                        float* dparams, float* workspace, int64_t workspace_floats,
+                                        const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                        int32_t accumulate, float rate, uint64_t seed, const int64_t* step,
+                                        int32_t layer_word, impnn_stream_t stream);
+int impnn_gated_update_rows_bwd_saved_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                              const float* Wr, const float* br, const float* Wh, const float* bh,
+                                              const float* gamma, float ln_eps, const float* dout, float* dh,
+                                              float* dagg, float* dparams, float* workspace, int64_t workspace_floats,
+                                              const int32_t* row_index, const int32_t* n_rows, int64_t max_rows,
+                                              int32_t D, int32_t accumulate, float* saved, float rate, uint64_t seed,
+                                              const int64_t* step, int32_t layer_word, impnn_stream_t stream);
+/* One launch: *snapshot = *counter; *counter += 1 (both DEVICE int64).  A training pass takes its step this way, so
+ * the step never passes through the host and a captured pass advances it on every replay. */
+int impnn_dropout_step(int64_t* counter, int64_t* snapshot, impnn_stream_t stream);
+/* The mask itself (tests, diagnostics): out[row * D + c] = scale or 0 for the rows row_index[0 .. *n_rows) (both NULL:
+ * rows 0 .. max_rows), as the entries above draw it; other rows of out are not written. */
+int impnn_dropout_mask(uint64_t seed, const int64_t* step, int32_t layer_word, float rate, const int32_t* row_index,
+                       const int32_t* n_rows, int64_t max_rows, int32_t D, float* out, impnn_stream_t stream);
+
 /*  Optimizer step, one launch for all variables (train_viscosity.py:227-230):
  *      g <- g * clipnorm / max(||g||_2, clipnorm)      per variable (tf.clip_by_norm); clipnorm <= 0: off
  *      m <- b1 m + (1-b1) g;   v <- b2 v + (1-b2) g^2

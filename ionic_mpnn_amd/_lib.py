@@ -15,7 +15,7 @@ _LIB_PATH = Path(os.environ.get("IMPNN_LIB") or Path(__file__).resolve().parent 
 _lock = threading.Lock()
 _lib = None
 
-i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
+i32, i64, u64, f32, vp, sz = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p, C.c_size_t
 PP = C.POINTER(vp)
 
 # name -> (restype, argtypes); mirrors include/impnn.h one to one
@@ -79,6 +79,15 @@ SIGNATURES = {
     "impnn_gated_update_rows_saved_floats": (i64, [i64, i32]),
     "impnn_gated_update_rows_train": (C.c_int, [vp] * 10 + [f32, vp, vp, vp, i64, i32, vp, vp]),
     "impnn_gated_update_rows_bwd_saved": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, vp, vp]),
+    "impnn_gated_update_dropout": (C.c_int, [vp] * 10 + [f32, vp, i64, i32, f32, u64, vp, i32, vp]),
+    "impnn_gated_update_rows_train_dropout": (C.c_int, [vp] * 10 + [f32, vp, vp, vp, i64, i32, vp, f32, u64, vp, i32, vp]),
+    "impnn_gated_update_bwd_dropout": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, i64, i32, i32, f32, u64, vp, i32, vp]),
+    "impnn_gated_update_rows_bwd_dropout": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, f32, u64, vp,
+                                                                                 i32, vp]),
+    "impnn_gated_update_rows_bwd_saved_dropout": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, vp, f32,
+                                                                                       u64, vp, i32, vp]),
+    "impnn_dropout_step": (C.c_int, [vp, vp, vp]),
+    "impnn_dropout_mask": (C.c_int, [u64, vp, i32, f32, vp, vp, i64, i32, vp, vp]),
     "impnn_adam_clipnorm_step": (C.c_int, [vp, vp, i32, i64, f32, f32, f32, f32, f32, vp]),
     "impnn_adam_clipnorm_step_counted": (C.c_int, [vp, vp, i32, vp, f32, f32, f32, f32, f32, vp]),
     "impnn_batch_assemble": (C.c_int, [i32, vp, i32, i32, PP, PP, PP, PP, PP, i32, i32, i32, PP, PP, PP, vp, vp, vp]),

@@ -204,26 +204,29 @@ class ReduceScatterAdd(torch.autograd.Function):
 
 
 class GatedUpdate(torch.autograd.Function):
-    """GatedUpdate.call (models/layers.py:142-156)."""
+    """GatedUpdate.call (models/layers.py:142-156); ``dropout``: an ops.Dropout whose mask the backward regenerates."""
 
     @staticmethod
-    def forward(ctx, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps):
+    def forward(ctx, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, *dropout):
         ts = [f32c(t) for t in (h, agg, Wz, bz, Wr, br, Wh, bh, gamma)]
         ctx.save_for_backward(*ts, beta)
         ctx.eps = float(eps)
-        return ops.gated_update(*ts, beta, eps)
+        ctx.extra = len(dropout)  # (0 or 1: the node's inputs, so its gradients, end with eps or with the dropout)
+        ctx.dropout = dropout[0] if dropout else None
+        return ops.gated_update(*ts, beta, eps, dropout=ctx.dropout)
 
     @staticmethod
     def backward(ctx, dout):
-        return _gated_update_backward(ctx.saved_tensors, ctx.eps, dout)
+        return _gated_update_backward(ctx.saved_tensors, ctx.eps, dout, dropout=ctx.dropout) + (None,) * ctx.extra
 
 
-def _gated_update_backward(saved, eps, dout, row_list=None, kept=None, unlisted_undefined=False):
+def _gated_update_backward(saved, eps, dout, row_list=None, kept=None, unlisted_undefined=False, dropout=None):
     """(dh, dagg, 8 parameter gradients or None where the kernel added into the sink, None for eps).
     row_list = (row_index, n_rows) of ops.kept_row_index: gradients of those rows only (impnn_gated_update_rows_bwd);
     dh is zero elsewhere (padding atoms carry no gradient), dagg is undefined there and never read.
     kept: the buffer the training forward filled (ops.gated_update(.., save=True)) - the backward then skips its
-    recompute passes (impnn_gated_update_rows_bwd_saved) and overwrites the buffer."""
+    recompute passes (impnn_gated_update_rows_bwd_saved) and overwrites the buffer.
+    dropout: the forward's ops.Dropout (rate > 0) - the *_dropout entries read dout through its mask."""
     h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta = saved
     D = h.shape[-1]
     rows = h.numel() // D
@@ -238,17 +241,21 @@ def _gated_update_backward(saved, eps, dout, row_list=None, kept=None, unlisted_
         wsn = int(lib.impnn_gated_update_bwd_workspace_floats(rows, D))
     ws = torch.empty(max(wsn, 1), dtype=torch.float32, device=h.device)
 
+    drop = dropout is not None and dropout.rate > 0.0
+    sfx, dargs = ("_dropout", dropout.args()) if drop else ("", ())
+
     def call(dparams, accumulate):
         common = (ptr(h), ptr(agg), ptr(Wz), ptr(bz), ptr(Wr), ptr(br), ptr(Wh), ptr(bh), ptr(gamma), eps, ptr(dout),
                   ptr(dh), ptr(dagg), ptr(dparams), ptr(ws), wsn)
         if kept is not None:
             ri, rn = (ptr(row_list[0]), ptr(row_list[1])) if row_list is not None else (None, None)
-            _lib_call(h.device, lib.impnn_gated_update_rows_bwd_saved, *common, ri, rn, rows, D, accumulate, ptr(kept))
+            _lib_call(h.device, getattr(lib, "impnn_gated_update_rows_bwd_saved" + sfx), *common, ri, rn, rows, D,
+                      accumulate, ptr(kept), *dargs)
         elif row_list is not None:
-            _lib_call(h.device, lib.impnn_gated_update_rows_bwd, *common, ptr(row_list[0]), ptr(row_list[1]), rows, D,
-                      accumulate)
+            _lib_call(h.device, getattr(lib, "impnn_gated_update_rows_bwd" + sfx), *common, ptr(row_list[0]),
+                      ptr(row_list[1]), rows, D, accumulate, *dargs)
         else:
-            _lib_call(h.device, lib.impnn_gated_update_bwd, *common, rows, D, accumulate)
+            _lib_call(h.device, getattr(lib, "impnn_gated_update_bwd" + sfx), *common, rows, D, accumulate, *dargs)
     # the eight parameter gradients leave the kernel as one block in the canonical order; when the existing
     # .grad buffers form exactly that block (train.Adam's flat buffer does), the kernel adds into it directly
     params = (Wz, bz, Wr, br, Wh, bh, gamma, beta)
@@ -290,10 +297,11 @@ class MessagePassingStep(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, bond_ids, conn, type_mats, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, graph, dmats=None,
-                row_index=None, n_rows=None, inner=False):
+                row_index=None, n_rows=None, inner=False, dropout=None):
         """row_index / n_rows (ops.kept_row_index; atom_dim 64 / 128): GatedUpdate forward and backward on the kept rows
         only - padding atoms reach neither a message nor the pool, so their rows of the output are left undefined
-        and their gradient is zero (include/impnn.h, impnn_gated_update_rows[_bwd])."""
+        and their gradient is zero (include/impnn.h, impnn_gated_update_rows[_bwd]).
+        dropout: an ops.Dropout of this layer and pass (training) - fused into the GatedUpdate forward and backward."""
         h, type_mats, bond_ids, conn = f32c(h), f32c(type_mats), i32c(bond_ids), i32c(conn)
         gu = [f32c(t) for t in (Wz, bz, Wr, br, Wh, bh, gamma)]
         # inner (with a row list): this step's input is the output of another MessagePassingStep on the SAME list - that
@@ -310,9 +318,10 @@ class MessagePassingStep(torch.autograd.Function):
         if h.shape[-1] in (64, 128) or (h.shape[-1] == 32 and ctx.row_list is None):
             # the gates, the candidate and r * h of the (kept) rows stay for the backward (4 D floats per row and step)
             # instead of being recomputed there with half of its matrix work
-            out, ctx.kept = ops.gated_update(h, agg, *gu, beta, eps, rows=ctx.row_list, save=True)
+            out, ctx.kept = ops.gated_update(h, agg, *gu, beta, eps, rows=ctx.row_list, save=True, dropout=dropout)
         else:
-            out = ops.gated_update(h, agg, *gu, beta, eps, rows=ctx.row_list)
+            out = ops.gated_update(h, agg, *gu, beta, eps, rows=ctx.row_list, dropout=dropout)
+        ctx.dropout = dropout
         ctx.save_for_backward(h, agg, *gu, beta, bond_ids, conn, type_mats)
         ctx.eps = float(eps)
         ctx.graph, ctx.dmats = graph, dmats
@@ -328,7 +337,8 @@ class MessagePassingStep(torch.autograd.Function):
                 raise RuntimeError("MessagePassingStep: the kept activations were consumed by an earlier backward "
                                    "(run the forward again instead of retain_graph)")
             ctx.kept = False
-        dh, dagg, *dparams = _gated_update_backward(saved[:10], ctx.eps, dout, ctx.row_list, kept, ctx.inner)
+        dh, dagg, *dparams = _gated_update_backward(saved[:10], ctx.eps, dout, ctx.row_list, kept, ctx.inner,
+                                                    ctx.dropout)
         del kept
         B, N, D = h.shape
         dmats = ctx.dmats if ctx.dmats is not None else torch.zeros_like(mats)
@@ -340,7 +350,7 @@ class MessagePassingStep(torch.autograd.Function):
             scratch = ctx.graph.written_message_buffer(D)
         entry = "impnn_message_reduce_typed_bwd" if scratch is None else "impnn_message_reduce_typed_bwd_scratch"
         _message_adjoint(entry, ctx.graph, h, bond_ids, conn, mats, dagg, dh, dmats, scratch)
-        return (dh, None, None, dmats, *dparams) + (None,) * 5
+        return (dh, None, None, dmats, *dparams) + (None,) * 6
 
 
 class GlobalSumPool(torch.autograd.Function):

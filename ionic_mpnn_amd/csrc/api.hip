@@ -681,6 +681,140 @@ int impnn_gated_update_rows_bwd_saved(const float* h, const float* agg, const fl
                                  max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows, saved);
 }
 
+#define DROPOUT_ARGS(d_)                                                                                    \
+  DropoutArgs d_;                                                                                           \
+  REQUIRE(step != nullptr, "null step pointer");                                                           \
+  if (!dropout_args(rate, seed, step, layer_word, &d_)) return fail(IMPNN_E_BADARG, "dropout rate %g is not in [0, 1)", \
+                                                                    (double)rate)
+
+int impnn_gated_update_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                               const float* br, const float* Wh, const float* bh, const float* gamma,
+                               const float* beta, float ln_eps, float* out, int64_t rows, int32_t D, float rate,
+                               uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream) {
+  DROPOUT_ARGS(d);
+  if (rate == 0.f) return impnn_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, rows, D, stream);
+  REQUIRE(rows >= 0 && D > 0, "bad shape");
+  if (rows == 0) return IMPNN_OK;
+  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out, "null pointer");
+  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
+  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, rows, D, as_stream(stream),
+                             nullptr, nullptr, nullptr, &d);
+}
+
+int impnn_gated_update_rows_train_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                          const float* Wr, const float* br, const float* Wh, const float* bh,
+                                          const float* gamma, const float* beta, float ln_eps, float* out,
+                                          const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                          float* saved, float rate, uint64_t seed, const int64_t* step,
+                                          int32_t layer_word, impnn_stream_t stream) {
+  DROPOUT_ARGS(d);
+  if (rate == 0.f) {
+    if (saved)
+      return impnn_gated_update_rows_train(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows,
+                                           max_rows, D, saved, stream);
+    if (row_index)
+      return impnn_gated_update_rows(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows,
+                                     max_rows, D, stream);
+    return impnn_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, max_rows, D, stream);
+  }
+  REQUIRE(max_rows >= 0 && D > 0, "bad shape");
+  if (saved && D != 32 && D != 64 && D != 128)
+    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_train: atom_dim %d (the saving forward covers 32, 64 and 128)", D);
+  if (max_rows == 0) return IMPNN_OK;
+  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out, "null pointer");
+  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
+  REQUIRE(!saved || (reinterpret_cast<uintptr_t>(saved) & 15u) == 0, "saved must be 16-byte aligned");
+  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
+  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, max_rows, D, as_stream(stream),
+                             row_index, n_rows, saved, &d);
+}
+
+int impnn_gated_update_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                                   const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                                   const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                                   int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate, float rate,
+                                   uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream) {
+  DROPOUT_ARGS(d);
+  if (rate == 0.f)
+    return impnn_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
+                                  workspace_floats, rows, D, accumulate, stream);
+  REQUIRE(rows >= 0 && D > 0 && D <= 256 && 256 % D == 0, "atom_dim must divide 256");
+  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace,
+          "null pointer");
+  if (workspace_floats < impnn_gated_update_bwd_workspace_floats(rows, D))
+    return fail(IMPNN_E_WORKSPACE, "gated_update_bwd: workspace of %lld floats is too small", (long long)workspace_floats);
+  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
+                                 rows, D, accumulate != 0, as_stream(stream), nullptr, nullptr, nullptr, &d);
+}
+
+int impnn_gated_update_rows_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                        const float* Wr, const float* br, const float* Wh, const float* bh,
+                                        const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
+                                        float* dparams, float* workspace, int64_t workspace_floats,
+                                        const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                        int32_t accumulate, float rate, uint64_t seed, const int64_t* step,
+                                        int32_t layer_word, impnn_stream_t stream) {
+  DROPOUT_ARGS(d);
+  if (rate == 0.f)
+    return impnn_gated_update_rows_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
+                                       workspace_floats, row_index, n_rows, max_rows, D, accumulate, stream);
+  REQUIRE(max_rows >= 0, "bad shape");
+  if (D != 64 && D != 128)
+    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd: atom_dim %d (the row-list form covers 64 and 128)", D);
+  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace &&
+          row_index && n_rows, "null pointer");
+  if (workspace_floats < impnn_gated_update_rows_bwd_workspace_floats(max_rows, D))
+    return fail(IMPNN_E_WORKSPACE, "gated_update_rows_bwd: workspace of %lld floats is too small", (long long)workspace_floats);
+  if (max_rows == 0) return IMPNN_OK;
+  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
+                                 max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows, nullptr, &d);
+}
+
+int impnn_gated_update_rows_bwd_saved_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                              const float* Wr, const float* br, const float* Wh, const float* bh,
+                                              const float* gamma, float ln_eps, const float* dout, float* dh,
+                                              float* dagg, float* dparams, float* workspace, int64_t workspace_floats,
+                                              const int32_t* row_index, const int32_t* n_rows, int64_t max_rows,
+                                              int32_t D, int32_t accumulate, float* saved, float rate, uint64_t seed,
+                                              const int64_t* step, int32_t layer_word, impnn_stream_t stream) {
+  DROPOUT_ARGS(d);
+  if (rate == 0.f)
+    return impnn_gated_update_rows_bwd_saved(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams,
+                                             workspace, workspace_floats, row_index, n_rows, max_rows, D, accumulate,
+                                             saved, stream);
+  REQUIRE(max_rows >= 0, "bad shape");
+  if (D != 32 && D != 64 && D != 128)
+    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim %d (covers 32, 64 and 128)", D);
+  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace && saved,
+          "null pointer");
+  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
+  if (D == 32 && row_index)
+    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim 32 takes no row list");
+  if (workspace_floats < (D == 32 ? impnn_gated_update_bwd_workspace_floats(max_rows, D)
+                                  : impnn_gated_update_rows_bwd_workspace_floats(max_rows, D)))
+    return fail(IMPNN_E_WORKSPACE, "gated_update_rows_bwd_saved: workspace of %lld floats is too small",
+                (long long)workspace_floats);
+  if (max_rows == 0) return IMPNN_OK;
+  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
+                                 max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows, saved, &d);
+}
+
+int impnn_dropout_step(int64_t* counter, int64_t* snapshot, impnn_stream_t stream) {
+  REQUIRE(counter && snapshot, "null pointer");
+  return launch_dropout_step(counter, snapshot, as_stream(stream));
+}
+
+int impnn_dropout_mask(uint64_t seed, const int64_t* step, int32_t layer_word, float rate, const int32_t* row_index,
+                       const int32_t* n_rows, int64_t max_rows, int32_t D, float* out, impnn_stream_t stream) {
+  DROPOUT_ARGS(d);
+  REQUIRE(max_rows >= 0 && D > 0, "bad shape");
+  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
+  if (max_rows == 0) return IMPNN_OK;
+  REQUIRE(out, "null pointer");
+  return launch_dropout_mask(d, row_index, n_rows, max_rows, D, out, as_stream(stream));
+}
+#undef DROPOUT_ARGS
+
 int impnn_adam_clipnorm_step(const void* var_table, const int64_t* sizes, int32_t n_vars, int64_t step, float lr,
                              float beta1, float beta2, float eps, float clipnorm, impnn_stream_t stream) {
   REQUIRE(n_vars >= 0 && step >= 1, "bad arguments (step counts from 1)");

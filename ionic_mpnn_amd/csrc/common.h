@@ -27,6 +27,103 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 constexpr int kWave = 64;  // CDNA wavefront
 
+// ---- GatedUpdate dropout.  Philox4x32-10 (Salmon et al., SC'11), the counter-based generator of
+// Random123: one call gives four 32-bit words.  Element (row, column) of a (rows, D) GatedUpdate output draws word
+// column % 4 of philox(counter = (column / 4, row, layer_word, lo32(step)), key = (lo32(seed), hi32(seed) ^
+// hi32(step))); it is kept iff (word >> 8) * 2^-24 >= rate, i.e. iff (word >> 8) >= thr = ceil(rate * 2^24), and a
+// kept element is out * scale with scale = 1 / (1 - rate), a dropped one +0.  The backward regenerates the mask.
+struct Philox4 {
+  uint32_t v[4];
+};
+
+__device__ __host__ inline uint32_t philox_mulhi(uint32_t a, uint32_t b) {
+  return (uint32_t)(((uint64_t)a * b) >> 32);
+}
+
+__device__ __host__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                 uint32_t k1) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    if (i > 0) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint32_t hi0 = philox_mulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = philox_mulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// What a dropout kernel instantiation receives (by value).  `step` points at a device int64 step (a snapshot slot of
+// impnn_dropout_step); the kernels read it once and never take the step from the host.
+struct DropoutArgs {
+  float scale;          // 1 / (1 - rate), rounded to float
+  uint32_t thr;         // ceil(rate * 2^24): keep iff (word >> 8) >= thr
+  uint32_t k0, k1;      // lo32(seed), hi32(seed)
+  uint32_t layer_word;  // layer_id | (rank << 16)
+  const int64_t* step;
+};
+
+// rate in [0, 1) -> false otherwise (NaN included)
+inline bool dropout_args(float rate, uint64_t seed, const int64_t* step, int32_t layer_word, DropoutArgs* d) {
+  if (!(rate >= 0.f && rate < 1.f)) return false;
+  d->scale = 1.0f / (1.0f - rate);
+  d->thr = (uint32_t)ceilf(rate * 16777216.0f);  // exact: a power-of-two scaling of a float below 1
+  d->k0 = (uint32_t)seed;
+  d->k1 = (uint32_t)(seed >> 32);
+  d->layer_word = (uint32_t)layer_word;
+  d->step = step;
+  return true;
+}
+
+// The per-launch part of the key and counter: x2 = layer word, x3 = lo32(step), k1 ^= hi32(step).
+struct DropoutKey {
+  uint32_t k0, k1, x2, x3, thr;
+  float scale;
+};
+
+__device__ __forceinline__ DropoutKey dropout_key(const DropoutArgs& d) {
+  const int64_t st = *d.step;
+  return DropoutKey{d.k0, d.k1 ^ (uint32_t)((uint64_t)st >> 32), d.layer_word, (uint32_t)st, d.thr, d.scale};
+}
+
+__device__ __forceinline__ Philox4 dropout_bits(const DropoutKey& k, int64_t row, int col4) {
+  return philox4x32_10((uint32_t)col4, (uint32_t)row, k.x2, k.x3, k.k0, k.k1);
+}
+
+__device__ __forceinline__ float dropout_apply(const DropoutKey& k, uint32_t word, float v) {
+  return (word >> 8) >= k.thr ? v * k.scale : 0.0f;
+}
+
+// Kernels take the dropout arguments as an optional trailing parameter pack (`class... Drop`): the instantiation
+// without them has exactly the parameters, and so the code, of the kernel before dropout existed.
+__device__ __forceinline__ DropoutArgs dropout_of() { return DropoutArgs{}; }
+__device__ __forceinline__ DropoutArgs dropout_of(const DropoutArgs& d) { return d; }
+
+__device__ __forceinline__ uint32_t philox_word(const Philox4& p, int i) {
+  return i == 0 ? p.v[0] : i == 1 ? p.v[1] : i == 2 ? p.v[2] : p.v[3];
+}
+
+// The MFMA tile layout of the wide GatedUpdate kernels: lane j = lane & 3 of a quad of lanes owns column 4 * col4 + j
+// of the quad's four rows g = 0..3 (row_j: the row with g == j).  One Philox call per lane, for row_j; a 4 x 4
+// transpose across the quad then hands lane j word j of every row: w[g].  All four lanes of the quad must be active.
+__device__ __forceinline__ void dropout_quad_words(const DropoutKey& k, int64_t row_j, int col4, int j, uint32_t w[4]) {
+  const Philox4 p = dropout_bits(k, row_j, col4);
+  uint32_t got[4];  // got[s]: word j of the row of lane j ^ s
+  got[0] = philox_word(p, j);
+#pragma unroll
+  for (int s = 1; s < 4; ++s) got[s] = (uint32_t)__shfl_xor((int)philox_word(p, j ^ s), s);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int s = g ^ j;
+    w[g] = s == 0 ? got[0] : s == 1 ? got[1] : s == 2 ? got[2] : got[3];
+  }
+}
+
 // ---- layer-at-a-time launches (layer_kernels.hip)
 int launch_embed_gather(const int32_t* ids, const float* table, float* out, int64_t rows, int vocab,
                         int dim, hipStream_t s);
@@ -43,7 +140,7 @@ int launch_gated_update(const float* h, const float* agg, const float* Wz, const
                         const float* Wr, const float* br, const float* Wh, const float* bh,
                         const float* gamma, const float* beta, float eps, float* out, int64_t rows,
                         int D, hipStream_t s, const int32_t* ridx = nullptr, const int32_t* nrows_dev = nullptr,
-                        float* save = nullptr);
+                        float* save = nullptr, const DropoutArgs* drop = nullptr);
 int launch_kept_rows(const int32_t* atom_ids, const int32_t* bond_ids, const int32_t* conn, int32_t* rows_out, int B,
                      int N, int E, int Vb, hipStream_t s);
 int launch_row_index_fill(const int32_t* r, const int32_t* incl, int32_t* idx, int32_t* count, int B, int N,
@@ -95,7 +192,11 @@ int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, c
                             const float* br, const float* Wh, const float* bh, const float* gamma, float eps,
                             const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
                             int64_t rows, int D, int accumulate, hipStream_t s, const int32_t* ridx = nullptr,
-                            const int32_t* nrows_dev = nullptr, float* saved = nullptr);
+                            const int32_t* nrows_dev = nullptr, float* saved = nullptr,
+                            const DropoutArgs* drop = nullptr);
+int launch_dropout_step(int64_t* counter, int64_t* snapshot, hipStream_t s);
+int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t* nrows_dev, int64_t max_rows, int D,
+                        float* out, hipStream_t s);
 int launch_adam_clipnorm(const void* table, const void* sizes, int n_vars, int64_t step, int64_t* step_dev, float lr,
                          float b1, float b2, float eps, float clipnorm, hipStream_t s);
 

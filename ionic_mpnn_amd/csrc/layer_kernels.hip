@@ -452,13 +452,14 @@ __global__ void reduce_scatter_kernel(const float* __restrict__ m, const int32_t
 // ---------------------------------------------------------------------------------------
 // Thread (row group rg, column i) owns column i of RB rows (rg, rg + G, ...; G = blockDim / D row groups): every
 // weight element it loads from L2 is used for RB rows, so a pass over the 3 x 2D x D kernels serves RB * G rows.
-template <int RB>
+// Drop (empty, or one DropoutArgs): the dropout form (common.h) - the mask goes on the final store.
+template <int RB, class... Drop>
 __global__ void gated_update_kernel(const float* __restrict__ h, const float* __restrict__ agg,
                                     const float* __restrict__ Wz, const float* __restrict__ bz,
                                     const float* __restrict__ Wr, const float* __restrict__ br,
                                     const float* __restrict__ Wh, const float* __restrict__ bh,
                                     const float* __restrict__ gamma, const float* __restrict__ beta,
-                                    float eps, float* __restrict__ out, int64_t rows, int D, int R) {
+                                    float eps, float* __restrict__ out, int64_t rows, int D, int R, Drop... drop) {
   extern __shared__ __align__(16) float smem[];
   float* hs = smem;            // R*D
   float* as = hs + R * D;      // R*D
@@ -546,6 +547,21 @@ __global__ void gated_update_kernel(const float* __restrict__ h, const float* __
     st[2 * r + 1] = 1.0f / sqrtf(var + eps);
   }
   __syncthreads();
+  if constexpr (sizeof...(Drop) > 0) {  // one Philox call per quad of columns: a thread walks (row, column quad)
+    const DropoutKey dk = dropout_key(dropout_of(drop...));
+    const int Q = (D + 3) / 4;
+    for (int t4 = threadIdx.x; t4 < nr * Q; t4 += blockDim.x) {
+      const int r = t4 / Q, c4 = t4 - r * Q;
+      const Philox4 bits = dropout_bits(dk, row0 + r, c4);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int c = 4 * c4 + u, t = r * D + c;
+        if (c < D)
+          out[row0 * D + t] = dropout_apply(dk, bits.v[u], (ns[t] - st[2 * r]) * st[2 * r + 1] * gamma[c] + beta[c] + hs[t]);
+      }
+    }
+    return;
+  }
   for (int t = threadIdx.x; t < nr * D; t += blockDim.x) {
     const int r = t / D, c = t - r * D;
     out[row0 * D + t] = (ns[t] - st[2 * r]) * st[2 * r + 1] * gamma[c] + beta[c] + hs[t];
@@ -560,12 +576,13 @@ __global__ void gated_update_kernel(const float* __restrict__ h, const float* __
 // ---------------------------------------------------------------------------------------
 constexpr int kGuRS = 68;  // LDS row stride of the transposed gate kernels
 
+template <class... Drop>  // Drop: as gated_update_kernel
 __global__ __launch_bounds__(256) void gated_update_d32_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
     const float* __restrict__ bz, const float* __restrict__ Wr, const float* __restrict__ br,
     const float* __restrict__ Wh, const float* __restrict__ bh, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, float* __restrict__ out, int64_t rows,
-    const int32_t* __restrict__ ridx, const int32_t* __restrict__ nrows_dev, float* __restrict__ save) {
+    const int32_t* __restrict__ ridx, const int32_t* __restrict__ nrows_dev, float* __restrict__ save, Drop... drop) {
   // save (optional; impnn_gated_update_rows_train): [z | r | tanh(t)] per row by list position, then r * h from float
   // 3 D max_rows on - see gated_update_wide16_kernel
   constexpr int D = 32;
@@ -592,6 +609,8 @@ __global__ __launch_bounds__(256) void gated_update_d32_kernel(
   const int64_t ntiles = (rows + 15) >> 4;
   const int64_t wave_id = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  [[maybe_unused]] DropoutKey dk{};
+  if constexpr (sizeof...(Drop) > 0) dk = dropout_key(dropout_of(drop...));
   for (int64_t tile = wave_id; tile < ntiles; tile += nwaves) {
     const int64_t row = tile * 16 + a;
     int64_t rl = row < rows ? row : rows - 1;  // clamped load address; the store is masked
@@ -692,6 +711,14 @@ __global__ __launch_bounds__(256) void gated_update_d32_kernel(
       o0[i] = n0[i] * inv * g0[i] + b0[i] + h0[i];
       o1[i] = n1[i] * inv * g1[i] + b1[i] + h1[i];
     }
+    if constexpr (sizeof...(Drop) > 0) {  // the mask of row rl (the listed row), columns 4q.. and 16 + 4q..
+      const Philox4 m0 = dropout_bits(dk, rl, q), m1 = dropout_bits(dk, rl, 4 + q);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        o0[i] = dropout_apply(dk, m0.v[i], o0[i]);
+        o1[i] = dropout_apply(dk, m1.v[i], o1[i]);
+      }
+    }
     if (row < rows) {  // (rl is the row itself, or its entry of the row list)
       *reinterpret_cast<f32x4_t*>(out + rl * D + 4 * q) = o0;
       *reinterpret_cast<f32x4_t*>(out + rl * D + 16 + 4 * q) = o1;
@@ -715,12 +742,12 @@ __device__ __forceinline__ float row16_sum_f(float v) {
   return v;
 }
 
-template <int NT>  // NT = D / 16 feature tiles
+template <int NT, class... Drop>  // NT = D / 16 feature tiles; Drop: as gated_update_kernel
 __global__ __launch_bounds__(256) void gated_update_wide_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
     const float* __restrict__ bz, const float* __restrict__ Wr, const float* __restrict__ br,
     const float* __restrict__ Wh, const float* __restrict__ bh, const float* __restrict__ gamma,
-    const float* __restrict__ beta, float eps, float* __restrict__ out, int64_t rows) {
+    const float* __restrict__ beta, float eps, float* __restrict__ out, int64_t rows, Drop... drop) {
   constexpr int D = 16 * NT, LDC = 2 * D + 4, LDR = D + 4;
   constexpr int LDW = 2 * D;  // slice layout: element (input row 4*qq + r, column c) at ((qq * LDW + c) * 4 + r)
   extern __shared__ __align__(16) float smem[];
@@ -851,29 +878,35 @@ __global__ __launch_bounds__(256) void gated_update_wide_kernel(
     }
 #pragma unroll
   for (int g = 0; g < 4; ++g) inv[g] = 1.0f / sqrtf(row16_sum_f(var[g]) * (1.0f / D) + eps);
+  [[maybe_unused]] DropoutKey dk{};
+  if constexpr (sizeof...(Drop) > 0) dk = dropout_key(dropout_of(drop...));
 #pragma unroll
   for (int T = 0; T < NT; ++T) {
     const int f = 16 * T + a;
     const float gm = gamma[f], bt = beta[f];
+    uint32_t mw[4];
+    if constexpr (sizeof...(Drop) > 0)  // (all lanes active: the quad transpose)
+      dropout_quad_words(dk, row0 + 16 * wave + 4 * q + (a & 3), f >> 2, a & 3, mw);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int rl = 16 * wave + 4 * q + g;
-      if (row0 + rl < rows)
-        out[(row0 + rl) * D + f] = (tt[T][g] - mean[g]) * inv[g] * gm + bt + cs[rl * LDC + f];
+      float v = (tt[T][g] - mean[g]) * inv[g] * gm + bt + cs[rl * LDC + f];
+      if constexpr (sizeof...(Drop) > 0) v = dropout_apply(dk, mw[g], v);
+      if (row0 + rl < rows) out[(row0 + rl) * D + f] = v;
     }
   }
 }
 
 // The same with 16 waves (4 per SIMD, so LDS / MFMA latencies overlap): wave (row tile w & 3, feature group w >> 2)
 // owns NT/4 feature tiles of 16 rows; LayerNorm's row sums are completed across the 4 feature groups through LDS.
-template <int NT>  // NT = D / 16 feature tiles, NT % 4 == 0
+template <int NT, class... Drop>  // NT = D / 16 feature tiles, NT % 4 == 0; Drop: as gated_update_kernel
 __global__ __launch_bounds__(1024) void gated_update_wide16_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
     const float* __restrict__ bz, const float* __restrict__ Wr, const float* __restrict__ br,
     const float* __restrict__ Wh, const float* __restrict__ bh, const float* __restrict__ gamma,
     const float* __restrict__ beta, float eps, float* __restrict__ out, int64_t rows,
     const int32_t* __restrict__ ridx, const int32_t* __restrict__ nrows_dev, int tile_rows,
-    float* __restrict__ save) {
+    float* __restrict__ save, Drop... drop) {
   // save (optional; the training forward, impnn_gated_update_rows_train): what the backward would otherwise recompute
   // with two of its four GEMM passes, by LIST POSITION - [z | r | tanh(t)] in 3 D floats per row, and from float
   // 3 D max_rows on r * h (the layout gated_update_bwd_wide16_kernel keeps its pre-activation gradients in).
@@ -1128,17 +1161,31 @@ __global__ __launch_bounds__(1024) void gated_update_wide16_kernel(
     const int rl = 256 + 16 * wave + 4 * q + g;
     inv[g] = 1.0f / sqrtf(((part[rl] + part[64 + rl]) + (part[128 + rl] + part[192 + rl])) * (1.0f / D) + eps);
   }
+  [[maybe_unused]] int64_t mrow = 0;  // dropout: the row (of h / out) of this lane's row g == (a & 3) of the quad
+  [[maybe_unused]] DropoutKey dk{};
+  if constexpr (sizeof...(Drop) > 0) {
+    dk = dropout_key(dropout_of(drop...));
+    const int rl = 16 * wave + 4 * q + (a & 3);
+    if (row0 + rl < rows) {
+      mrow = ridx ? (int64_t)ridx[row0 + rl] : row0 + rl;
+      mrow = mrow < 0 ? 0 : (mrow < max_rows ? mrow : max_rows - 1);
+    }
+  }
 #pragma unroll
   for (int TL = 0; TL < NL; ++TL) {
     const int f = 16 * (fg * NL + TL) + a;
     const float gm = gamma[f], bt = beta[f];
+    uint32_t mw[4];
+    if constexpr (sizeof...(Drop) > 0) dropout_quad_words(dk, mrow, f >> 2, a & 3, mw);
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int rl = 16 * wave + 4 * q + g;
       if (row0 + rl < rows) {
         int64_t dst = ridx ? (int64_t)ridx[row0 + rl] : row0 + rl;
         dst = dst < 0 ? 0 : (dst < max_rows ? dst : max_rows - 1);
-        out[dst * D + f] = (tt[TL][g] - mean[g]) * inv[g] * gm + bt + cs[rl * LDC + f];
+        float v = (tt[TL][g] - mean[g]) * inv[g] * gm + bt + cs[rl * LDC + f];
+        if constexpr (sizeof...(Drop) > 0) v = dropout_apply(dk, mw[g], v);
+        out[dst * D + f] = v;
       }
     }
   }
@@ -1520,11 +1567,12 @@ int launch_row_index_fill(const int32_t* r, const int32_t* incl, int32_t* idx, i
   return check_launch("row_index_fill");
 }
 
-int launch_gated_update(const float* h, const float* agg, const float* Wz, const float* bz,
-                        const float* Wr, const float* br, const float* Wh, const float* bh,
-                        const float* gamma, const float* beta, float eps, float* out, int64_t rows,
-                        int D, hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* save) {
-  if (rows == 0) return IMPNN_OK;
+template <class... Drop>
+static int launch_gated_update_impl(const float* h, const float* agg, const float* Wz, const float* bz,
+                                    const float* Wr, const float* br, const float* Wh, const float* bh,
+                                    const float* gamma, const float* beta, float eps, float* out, int64_t rows, int D,
+                                    hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* save,
+                                    Drop... drop) {
   if (save && !(D == 32 || D == 64 || D == 128))
     return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_train: atom_dim %d (the saving forward covers 32, 64 and 128)", D);
   if (save && D == 32 && !(aligned16(h) && aligned16(agg) && aligned16(out) && aligned16(save)))
@@ -1537,8 +1585,8 @@ int launch_gated_update(const float* h, const float* agg, const float* Wz, const
     const int64_t tiles = (rows + 15) / 16;
     int64_t blocks = (tiles + 3) / 4;
     if (blocks > 256 * 4) blocks = 256 * 4;  // grid-stride: the weight transpose is paid once per workgroup
-    gated_update_d32_kernel<<<(unsigned)blocks, 256, 0, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, rows,
-                                                             ridx, nrows_dev, save);
+    gated_update_d32_kernel<Drop...><<<(unsigned)blocks, 256, 0, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps,
+                                                                      out, rows, ridx, nrows_dev, save, drop...);
     return check_launch("gated_update_d32");
   }
   if (D % 16 == 0 && D >= 48 && D <= 128) {  // matrix cores; the kernels stream through LDS in 16-row slices
@@ -1550,19 +1598,21 @@ int launch_gated_update(const float* h, const float* agg, const float* Wz, const
 #define WIDE(NT_)                                                                                                  \
     do {                                                                                                            \
       if (lw > 48 * 1024)                                                                                           \
-        (void)hipFuncSetAttribute((const void*)gated_update_wide_kernel<NT_>,                                       \
+        (void)hipFuncSetAttribute((const void*)gated_update_wide_kernel<NT_, Drop...>,                              \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lw);                             \
-      gated_update_wide_kernel<NT_><<<blocks, 256, lw, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, rows); \
+      gated_update_wide_kernel<NT_, Drop...><<<blocks, 256, lw, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, \
+                                                                     out, rows, drop...);                           \
       return check_launch("gated_update_wide");                                                                     \
     } while (0)
     if (D % 64 == 0) {  // 16 waves per workgroup: 4 per SIMD
       const size_t l16 = lw + sizeof(float) * (512 + 16 * 2 * D);  // a third slice buffer + the LayerNorm partials
 #define WIDE16(NT_)                                                                                                \
       do {                                                                                                          \
-        (void)hipFuncSetAttribute((const void*)gated_update_wide16_kernel<NT_>,                                     \
+        (void)hipFuncSetAttribute((const void*)gated_update_wide16_kernel<NT_, Drop...>,                            \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)l16);                            \
-        gated_update_wide16_kernel<NT_><<<blocks16, 1024, l16, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, \
-                                                                   rows, ridx, nrows_dev, tile_rows, save);         \
+        gated_update_wide16_kernel<NT_, Drop...><<<blocks16, 1024, l16, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, \
+                                                                            eps, out, rows, ridx, nrows_dev, tile_rows, \
+                                                                            save, drop...);                         \
         return check_launch("gated_update_wide16");                                                                 \
       } while (0)
       if (D == 64) WIDE16(4);
@@ -1588,16 +1638,33 @@ int launch_gated_update(const float* h, const float* agg, const float* Wz, const
   const int64_t blocks = (rows + R - 1) / R;
   if (big) {
     if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gated_update_kernel<8><<<(unsigned)blocks, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out,
-                                                                rows, D, R);
+      (void)hipFuncSetAttribute((const void*)gated_update_kernel<8, Drop...>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+    gated_update_kernel<8, Drop...><<<(unsigned)blocks, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps,
+                                                                         out, rows, D, R, drop...);
   } else {
     if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gated_update_kernel<4><<<(unsigned)blocks, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out,
-                                                                rows, D, R);
+      (void)hipFuncSetAttribute((const void*)gated_update_kernel<4, Drop...>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+    gated_update_kernel<4, Drop...><<<(unsigned)blocks, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps,
+                                                                         out, rows, D, R, drop...);
   }
   return check_launch("gated_update");
+}
+
+int launch_gated_update(const float* h, const float* agg, const float* Wz, const float* bz,
+                        const float* Wr, const float* br, const float* Wh, const float* bh,
+                        const float* gamma, const float* beta, float eps, float* out, int64_t rows,
+                        int D, hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* save,
+                        const DropoutArgs* drop) {
+  if (rows == 0) return IMPNN_OK;
+  if (drop) {  // the dropout instantiations: same shapes and dispatch, the mask on the final store
+    const DropoutArgs d = *drop;
+    return launch_gated_update_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, rows, D, s, ridx, nrows_dev,
+                                    save, d);
+  }
+  return launch_gated_update_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, rows, D, s, ridx, nrows_dev,
+                                  save);
 }
 
 int launch_global_sum_pool(const float* h, const int32_t* ids, float* out, int B, int N, int D,

@@ -974,13 +974,16 @@ __global__ void bond_type_matrices_t_sum_kernel(const float* __restrict__ part, 
 // WLDS: the three gate kernels staged in LDS (row stride D+1: both access directions conflict-free).
 // BS: workgroup size = rows per tile x D; large D uses 1024 threads so that one pass over the (L2-resident)
 // kernels serves 4x more rows.
-template <bool WLDS, int BS>
+// Drop (empty, or one DropoutArgs; common.h): the dropout form - dout is read through the forward's mask and scale.
+template <bool WLDS, int BS, class... Drop>
 __global__ __launch_bounds__(BS) void gated_update_bwd_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
     const float* __restrict__ bz, const float* __restrict__ Wr, const float* __restrict__ br,
     const float* __restrict__ Wh, const float* __restrict__ bh, const float* __restrict__ gamma, float eps,
     const float* __restrict__ dout, float* __restrict__ dh, float* __restrict__ dagg, float* __restrict__ dpre,
-    float* __restrict__ rh_out, float* __restrict__ small, const float* __restrict__ WT, int64_t rows, int D, int R) {
+    float* __restrict__ rh_out, float* __restrict__ small, const float* __restrict__ WT, int64_t rows, int D, int R,
+    Drop... drop) {
+  constexpr bool kDrop = sizeof...(Drop) > 0;
   extern __shared__ __align__(16) float smem[];
   float* hs = smem;            // R*D each
   float* as = hs + R * D;
@@ -1016,6 +1019,8 @@ __global__ __launch_bounds__(BS) void gated_update_bwd_kernel(
       wh_s[rw * LD + c] = Wh[t];
     }
   }
+  [[maybe_unused]] DropoutKey dk{};
+  if constexpr (kDrop) dk = dropout_key(dropout_of(drop...));
   const int64_t ntile = (rows + R - 1) / R;
   for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const int64_t row0 = tile * R;
@@ -1070,6 +1075,26 @@ __global__ __launch_bounds__(BS) void gated_update_bwd_kernel(
       st[4 * r + 1] = 1.0f / sqrtf(var / (float)D + eps);
     }
     __syncthreads();
+    if constexpr (kDrop) {  // one Philox call per (row, column quad); the masked dout waits in g3 (dtp's slot)
+      const int Q = (D + 3) / 4;
+      for (int t4 = tid; t4 < nr * Q; t4 += BS) {
+        const int r = t4 / Q, c4 = t4 - r * Q;
+        const Philox4 bits = dropout_bits(dk, row0 + r, c4);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i = 4 * c4 + u, t = r * D + i;
+          if (i < D) {
+            const float xh = (xs[t] - st[4 * r]) * st[4 * r + 1];
+            xs[t] = xh;
+            const float dy = dropout_apply(dk, bits.v[u], dout[row0 * D + t]);
+            g3[t] = dy;
+            const float dxh = dy * gamma[i];
+            g1[t] = dxh;
+            g2[t] = dxh * xh;
+          }
+        }
+      }
+    } else {
     for (int t = tid; t < nr * D; t += BS) {
       const int r = t / D, i = t - r * D;
       const float xh = (xs[t] - st[4 * r]) * st[4 * r + 1];
@@ -1078,6 +1103,7 @@ __global__ __launch_bounds__(BS) void gated_update_bwd_kernel(
       const float dxh = dy * gamma[i];
       g1[t] = dxh;
       g2[t] = dxh * xh;
+    }
     }
     __syncthreads();
     for (int r = tid; r < nr; r += BS) {
@@ -1093,7 +1119,7 @@ __global__ __launch_bounds__(BS) void gated_update_bwd_kernel(
     // dn -> (dzp, dtp), first part of dh; column sums for dgamma / dbeta
     for (int t = tid; t < nr * D; t += BS) {
       const int r = t / D;
-      const float dy = dout[row0 * D + t];
+      const float dy = kDrop ? g3[t] : dout[row0 * D + t];
       const float xh = xs[t];
       const float dn = st[4 * r + 1] * (g1[t] - st[4 * r + 2] - xh * st[4 * r + 3]);
       const float z = zs[t], tt = ts[t];
@@ -1191,13 +1217,14 @@ constexpr int kBwN = 36;  // stride of the natural kernels (rows: gate*64 + in, 
 
 // SAVED: dpre / rh_out arrive holding the training forward's z, r, tanh(t) / r * h (gated_update_d32_kernel's `save`):
 // no recompute, no transposed kernels in LDS - 24 of the kernel's 48 MFMAs per 16 rows.
-template <bool SAVED>
+// Drop: as gated_update_bwd_kernel.
+template <bool SAVED, class... Drop>
 __global__ __launch_bounds__(kBlock, SAVED ? 2 : 1) void gated_update_bwd_d32_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
     const float* __restrict__ bz, const float* __restrict__ Wr, const float* __restrict__ br,
     const float* __restrict__ Wh, const float* __restrict__ bh, const float* __restrict__ gamma, float eps,
     const float* __restrict__ dout, float* __restrict__ dh, float* __restrict__ dagg, float* __restrict__ dpre,
-    float* __restrict__ rh_out, float* __restrict__ small, int64_t rows) {
+    float* __restrict__ rh_out, float* __restrict__ small, int64_t rows, Drop... drop) {
   constexpr int D = 32;
   extern __shared__ __align__(16) float smem[];
   float* wt = smem;                       // 3*D rows x kBwT (not with SAVED)
@@ -1225,16 +1252,32 @@ __global__ __launch_bounds__(kBlock, SAVED ? 2 : 1) void gated_update_bwd_d32_ke
   f32x4_t s_bz[2] = {zero4, zero4}, s_br[2] = {zero4, zero4}, s_bh[2] = {zero4, zero4};
   f32x4_t s_dg[2] = {zero4, zero4}, s_db[2] = {zero4, zero4};
   const f32x4_t gm0 = ldv4(wvec + 3 * D + 4 * q), gm1 = ldv4(wvec + 3 * D + 16 + 4 * q);
+  [[maybe_unused]] DropoutKey dk{};
+  if constexpr (sizeof...(Drop) > 0) dk = dropout_key(dropout_of(drop...));
   for (int64_t tile = wave_id; tile < ntiles; tile += nwaves) {
     const int64_t row = tile * 16 + a;
     const bool live = row < rows;
     const int64_t rl = live ? row : rows - 1;  // clamped load address; stores and sums are masked through dy = 0
+    [[maybe_unused]] uint32_t keep = 0;  // dropout: the forward's keep bits of columns 4q + i (bit i), 16 + 4q + i (4 + i)
+    if constexpr (sizeof...(Drop) > 0) {
+      const Philox4 m0 = dropout_bits(dk, rl, q), m1 = dropout_bits(dk, rl, 4 + q);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        keep |= (uint32_t)((m0.v[i] >> 8) >= dk.thr) << i | (uint32_t)((m1.v[i] >> 8) >= dk.thr) << (4 + i);
+    }
     const f32x4_t h0 = ldv4(h + rl * D + 4 * q), h1 = ldv4(h + rl * D + 16 + 4 * q);
     const f32x4_t a0 = ldv4(agg + rl * D + 4 * q), a1 = ldv4(agg + rl * D + 16 + 4 * q);
     f32x4_t dy0 = ldv4(dout + rl * D + 4 * q), dy1 = ldv4(dout + rl * D + 16 + 4 * q);
     if (!live) {
       dy0 = zero4;
       dy1 = zero4;
+    }
+    if constexpr (sizeof...(Drop) > 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        dy0[i] = (keep >> i) & 1u ? dy0[i] * dk.scale : 0.0f;
+        dy1[i] = (keep >> (4 + i)) & 1u ? dy1[i] * dk.scale : 0.0f;
+      }
     }
     // ---- forward recompute (as gated_update_d32_kernel), or what that kernel kept
     f32x4_t z0, z1, r0, r1, t0, t1;
@@ -1446,7 +1489,7 @@ __global__ __launch_bounds__(kBlock, SAVED ? 2 : 1) void gated_update_bwd_d32_ke
 // ---------------------------------------------------------------------------------------
 // SAVED: dpre / rh_out arrive holding what the training forward kept (gated_update_wide16_kernel's `save`: z, r, tanh(t)
 // in the slots that receive dzp, drp, dtp; r * h) - the recompute passes P1 and P2, half of the kernel's MFMAs, go.
-template <int NT, bool SAVED>
+template <int NT, bool SAVED, class... Drop>  // Drop: as gated_update_bwd_kernel
 __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
     const float* __restrict__ bz, const float* __restrict__ Wr, const float* __restrict__ br,
@@ -1454,7 +1497,7 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
     const float* __restrict__ dout, float* __restrict__ dh, float* __restrict__ dagg, float* __restrict__ dpre,
     float* __restrict__ rh_out, float* __restrict__ small, int64_t rows, const int32_t* __restrict__ ridx,
     const int32_t* __restrict__ nrows_dev, float* __restrict__ hc, float* __restrict__ aggc, int tile_rows,
-    const float* __restrict__ wt) {
+    const float* __restrict__ wt, Drop... drop) {
   // wt = [Wz^T | Wr^T | Wh^T], each D x 2D (transpose3_kernel, once per call): the slices of P3 / P4 are then rows of
   // 2D consecutive floats - fetched and parked like the forward's (coalesced 4-byte loads two slices ahead, one
   // conflict-free 16-byte LDS store, a ring of three buffers) instead of 64-byte pieces and 4-way conflicting stores.
@@ -1517,6 +1560,8 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
     }
   };
   float s_bz[NL] = {}, s_br[NL] = {}, s_bh[NL] = {}, s_dg[NL] = {}, s_db[NL] = {};
+  [[maybe_unused]] DropoutKey dk{};
+  if constexpr (sizeof...(Drop) > 0) dk = dropout_key(dropout_of(drop...));
   const int64_t ntile = (rows + tile_rows - 1) / tile_rows;
   for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const int64_t row0 = tile * tile_rows;
@@ -1530,6 +1575,17 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
       grow_s[tid] = (int32_t)(gr < 0 ? 0 : (gr < max_rows ? gr : max_rows - 1));
     }
     __syncthreads();
+    // dropout: the forward's keep bits of this lane's 4 x NL elements (bit 4 TL + g), drawn while few registers are live
+    [[maybe_unused]] uint32_t keep = 0;
+    if constexpr (sizeof...(Drop) > 0) {
+#pragma unroll
+      for (int TL = 0; TL < NL; ++TL) {
+        uint32_t mw[4];
+        dropout_quad_words(dk, grow_s[16 * rt + 4 * q + (a & 3)], (16 * (fg * NL + TL) + a) >> 2, a & 3, mw);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) keep |= (uint32_t)((mw[g] >> 8) >= dk.thr) << (4 * TL + g);
+      }
+    }
     for (int t = tid; t < 64 * D; t += 1024) {
       const int r = t / D, c = t - r * D;
       const bool in = r < nrt;
@@ -1703,6 +1759,7 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
       for (int g = 0; g < 4; ++g) {
         const int rl = 16 * rt + 4 * q + g;
         dy[TL][g] = rl < nrt ? dout[(int64_t)grow_s[rl] * D + 16 * (fg * NL + TL) + a] : 0.f;
+        if constexpr (sizeof...(Drop) > 0) dy[TL][g] = (keep >> (4 * TL + g)) & 1u ? dy[TL][g] * dk.scale : 0.0f;
         xh[TL][g] *= inv[g];
         dxh[TL][g] = dy[TL][g] * gm;
         m1[g] += dxh[TL][g];
@@ -2868,11 +2925,13 @@ int64_t gated_update_bwd_workspace(int64_t rows, int D, bool row_list) {
          (int64_t)3 * 2 * D * D + (row_list ? rows * 2 * D : 0);
 }
 
-int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                            const float* br, const float* Wh, const float* bh, const float* gamma, float eps,
-                            const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                            int64_t rows, int D, int accumulate, hipStream_t s, const int32_t* ridx,
-                            const int32_t* nrows_dev, float* saved) {
+template <class... Drop>
+static int launch_gated_update_bwd_impl(const float* h, const float* agg, const float* Wz, const float* bz,
+                                        const float* Wr, const float* br, const float* Wh, const float* bh,
+                                        const float* gamma, float eps, const float* dout, float* dh, float* dagg,
+                                        float* dparams, float* workspace, int64_t rows, int D, int accumulate,
+                                        hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* saved,
+                                        Drop... drop) {
   if (D > kBlock || kBlock % D != 0)
     return fail(IMPNN_E_UNSUPPORTED, "gated_update_bwd: atom_dim %d must divide %d", D, kBlock);
   if (ridx && D != 64 && D != 128)
@@ -2910,11 +2969,12 @@ int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, c
     nsmall = nb;                                            // (zeros when the row list ends before its tiles)
 #define BWD16(NT_, SV_)                                                                                              \
     do {                                                                                                              \
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_wide16_kernel<NT_, SV_>,                                \
+      (void)hipFuncSetAttribute((const void*)gated_update_bwd_wide16_kernel<NT_, SV_, Drop...>,                       \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lw);                                 \
-      gated_update_bwd_wide16_kernel<NT_, SV_><<<nb, 1024, lw, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, \
-                                                                   dagg, dpre, rh, small, rows, ridx, nrows_dev, hc,  \
-                                                                   aggc, tile_rows, wt);                              \
+      gated_update_bwd_wide16_kernel<NT_, SV_, Drop...><<<nb, 1024, lw, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, \
+                                                                            dout, dh, dagg, dpre, rh, small, rows,    \
+                                                                            ridx, nrows_dev, hc, aggc, tile_rows, wt, \
+                                                                            drop...);                                 \
     } while (0)
     if (D == 64) {
       if (saved) BWD16(4, true); else BWD16(4, false);
@@ -2925,35 +2985,36 @@ int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, c
   } else if (D == 32 && al16) {
     const size_t l32 = sizeof(float) * ((size_t)3 * 32 * kBwT + 3 * 64 * kBwN + 4 * 32 + 4 * 5 * 32);
     if (l32 > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_d32_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)l32);
+      (void)hipFuncSetAttribute((const void*)gated_update_bwd_d32_kernel<false, Drop...>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)l32);
     if (saved) {
       const size_t l32s = l32 - sizeof(float) * 3 * 32 * kBwT;  // no transposed kernels
-      gated_update_bwd_d32_kernel<true><<<nblk, kBlock, l32s, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, dagg,
-                                                                 dpre, rh, small, rows);
+      gated_update_bwd_d32_kernel<true, Drop...><<<nblk, kBlock, l32s, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout,
+                                                                          dh, dagg, dpre, rh, small, rows, drop...);
     } else {
-      gated_update_bwd_d32_kernel<false><<<nblk, kBlock, l32, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, dagg,
-                                                                  dpre, rh, small, rows);
+      gated_update_bwd_d32_kernel<false, Drop...><<<nblk, kBlock, l32, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout,
+                                                                           dh, dagg, dpre, rh, small, rows, drop...);
     }
   } else if (lds + wlds <= 120 * 1024) {
     lds += wlds;
     if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_kernel<true, kBlock>,
+      (void)hipFuncSetAttribute((const void*)gated_update_bwd_kernel<true, kBlock, Drop...>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gated_update_bwd_kernel<true, kBlock><<<nblk, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh,
-                                                                    dagg, dpre, rh, small, nullptr, rows, D, R);
+    gated_update_bwd_kernel<true, kBlock, Drop...><<<nblk, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout,
+                                                                             dh, dagg, dpre, rh, small, nullptr, rows, D, R,
+                                                                             drop...);
   } else {
     constexpr int kBig = 1024;
     const int Rb = kBig / D;
     size_t lb = sizeof(float) * ((size_t)10 * Rb * D + 4 * Rb);
     if (lb < sizeof(float) * 5 * kBig) lb = sizeof(float) * 5 * kBig;
     if (lb > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_kernel<false, kBig>,
+      (void)hipFuncSetAttribute((const void*)gated_update_bwd_kernel<false, kBig, Drop...>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
     transpose3_kernel<<<dim3((D + 31) / 32, (2 * D + 31) / 32, 3), dim3(32, 8), 0, s>>>(Wz, Wr, Wh, wt, D);
     if (int rc = check_launch("transpose3")) return rc;
-    gated_update_bwd_kernel<false, kBig><<<nblk, kBig, lb, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh,
-                                                                dagg, dpre, rh, small, wt, rows, D, Rb);
+    gated_update_bwd_kernel<false, kBig, Drop...><<<nblk, kBig, lb, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh,
+                                                                         dagg, dpre, rh, small, wt, rows, D, Rb, drop...);
   }
   if (int rc = check_launch("gated_update_bwd")) return rc;
   int tiles_n = 1;
@@ -2980,6 +3041,65 @@ int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, c
   gated_update_reduce_kernel<<<wblocks + vblocks, kBlock, 0, s>>>(small, gpart, dparams, nsmall, nchunk, D, accumulate,
                                                                  wblocks);
   return check_launch("gated_update_reduce");
+}
+
+int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                            const float* br, const float* Wh, const float* bh, const float* gamma, float eps,
+                            const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                            int64_t rows, int D, int accumulate, hipStream_t s, const int32_t* ridx,
+                            const int32_t* nrows_dev, float* saved, const DropoutArgs* drop) {
+  if (drop) {  // the dropout instantiations of the main kernel; the GEMMs and the reduction behind it are the same
+    const DropoutArgs d = *drop;
+    return launch_gated_update_bwd_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, dagg, dparams, workspace,
+                                        rows, D, accumulate, s, ridx, nrows_dev, saved, d);
+  }
+  return launch_gated_update_bwd_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, dagg, dparams, workspace,
+                                      rows, D, accumulate, s, ridx, nrows_dev, saved);
+}
+
+// impnn_dropout_step: snapshot <- counter; counter += 1 (one thread; a captured step replays it)
+__global__ void dropout_step_kernel(long long* __restrict__ counter, long long* __restrict__ snapshot) {
+  const long long v = *counter;
+  *snapshot = v;
+  *counter = v + 1;
+}
+
+int launch_dropout_step(int64_t* counter, int64_t* snapshot, hipStream_t s) {
+  dropout_step_kernel<<<1, 1, 0, s>>>(reinterpret_cast<long long*>(counter), reinterpret_cast<long long*>(snapshot));
+  return check_launch("dropout_step");
+}
+
+// impnn_dropout_mask: out[row, c] = scale or 0, the mask the GatedUpdate kernels apply (one thread per column quad)
+__global__ void dropout_mask_kernel(DropoutArgs d, const int32_t* __restrict__ ridx, const int32_t* __restrict__ nrows_dev,
+                                    int64_t max_rows, int D, float* __restrict__ out) {
+  int64_t rows = max_rows;
+  if (nrows_dev) {
+    const int64_t n = *nrows_dev;
+    rows = n < 0 ? 0 : (n < max_rows ? n : max_rows);
+  }
+  const DropoutKey dk = dropout_key(d);
+  const int Q = (D + 3) / 4;
+  const int64_t n = rows * Q;
+  for (int64_t t4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t4 < n; t4 += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t4 / Q;
+    const int c4 = (int)(t4 - i * Q);
+    int64_t row = ridx ? (int64_t)ridx[i] : i;
+    if (row < 0 || row >= max_rows) continue;  // (indices are never trusted)
+    const Philox4 bits = dropout_bits(dk, row, c4);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (4 * c4 + u < D) out[row * D + 4 * c4 + u] = dropout_apply(dk, bits.v[u], 1.0f);
+  }
+}
+
+int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t* nrows_dev, int64_t max_rows, int D,
+                        float* out, hipStream_t s) {
+  const int64_t n = max_rows * ((D + 3) / 4);
+  int64_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  dropout_mask_kernel<<<(unsigned)blocks, 256, 0, s>>>(d, ridx, nrows_dev, max_rows, D, out);
+  return check_launch("dropout_mask");
 }
 
 int launch_adam_clipnorm(const void* table, const void* sizes, int n_vars, int64_t step, int64_t* step_dev, float lr,

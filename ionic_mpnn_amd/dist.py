@@ -130,3 +130,9 @@ class ShardedForward:
     def __call__(self, global_inputs, gather=True):
         out = self.fn(self.local_inputs(global_inputs))
         return all_gather_fingerprints(out) if gather else out
+
+
+def dropout_rank():
+    """The rank that goes into the dropout layer word (ops.dropout_layer_word): this process's rank under
+    torch.distributed, else 0 - so the ranks of a data-parallel step draw different masks."""
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0

@@ -275,14 +275,32 @@ class _DenseVars:
 class GatedUpdate(Layer):
     """models/layers.py:128-156: GRU-style gate + LayerNormalization + residual + Dropout.
 
+    ``call(..., training=True)`` with ``dropout_rate > 0`` applies Keras' Dropout to the output (after the residual):
+    the mask is drawn inside the GatedUpdate kernels from a counter-based generator keyed on the layer's seed and a
+    device step counter that every training call advances, and the backward regenerates it.  The
+    seed is ``dropout_seed`` or, when that is None, one draw from torch's CPU generator at construction (so
+    ``torch.manual_seed`` makes runs reproducible).  Inference (``training`` false) never applies it.
+
     The reference has no get_config() override here, so its atom_dim is lost on save
     (SURVEY.md 8b); this class serialises it."""
 
-    def __init__(self, atom_dim, dropout_rate=0.0, **kwargs):
+    def __init__(self, atom_dim, dropout_rate=0.0, dropout_seed=None, **kwargs):
         super().__init__(**kwargs)
         self.atom_dim = int(atom_dim)
-        self.dropout_rate = float(dropout_rate)
+        self.dropout_rate = ops.check_dropout_rate(dropout_rate)
+        if dropout_seed is None and self.dropout_rate > 0.0:
+            dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        self._dropout_counter = None  # device int64, created by the first training call
         self.epsilon = ops.LN_EPS
+
+    def dropout_counter(self):
+        """The layer's device step counter (None at rate 0); each training call snapshots and advances it."""
+        if self.dropout_rate == 0.0:
+            return None
+        if self._dropout_counter is None:
+            self._dropout_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self._dropout_counter
 
     def build(self, input_shape):
         D = self.atom_dim
@@ -295,18 +313,19 @@ class GatedUpdate(Layer):
 
     def call(self, inputs, training=None):
         atom_state, agg = inputs
+        dropout = None
         if training and self.dropout_rate > 0.0:
-            raise NotImplementedError("Dropout with rate > 0 in training mode is outside the forward path; "
-                                      "the reference always builds GatedUpdate with rate 0.0 "
-                                      "(train_viscosity.py:184)")
+            from . import dist as idist
+            dropout = ops.Dropout(self.dropout_rate, self.dropout_seed, ops.dropout_layer_word(0, idist.dropout_rank()),
+                                  ops.dropout_step(self.dropout_counter()))
         w = self._weights
         return ops.gated_update(atom_state, agg, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
                                 w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], self.gamma, self.beta,
-                                self.epsilon)
+                                self.epsilon, dropout=dropout)
 
     def get_config(self):
         cfg = super().get_config()
-        cfg.update({"atom_dim": self.atom_dim, "dropout_rate": self.dropout_rate})
+        cfg.update({"atom_dim": self.atom_dim, "dropout_rate": self.dropout_rate, "dropout_seed": self.dropout_seed})
         return cfg
 
 

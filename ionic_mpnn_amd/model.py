@@ -35,13 +35,21 @@ TRAIN_ROW_LIST_MIN_ROWS = int(os.environ.get("IMPNN_TRAIN_ROW_LIST_MIN_ROWS", 40
 
 class MPNNModel:
     def __init__(self, kind, atom_vocab_size, bond_vocab_size, atom_dim, bond_dim, fp_size, mixing_size,
-                 num_steps, fp_l2, device=None, name=None):
+                 num_steps, fp_l2, device=None, name=None, dropout_rate=0.0, dropout_seed=None):
+        """dropout_rate / dropout_seed: GatedUpdate's Dropout in every message-passing step of both ions, applied by
+        training passes only (fit, train_on_batch, __call__(training=True)); the seed defaults to one draw from
+        torch's CPU generator."""
         self.kind = kind
         self.name = name or ("MeltingPoint_MPNN" if kind == "melting_point" else "model")
         self.atom_vocab_size, self.bond_vocab_size = int(atom_vocab_size), int(bond_vocab_size)
         self.atom_dim, self.bond_dim = int(atom_dim), int(bond_dim)
         self.fp_size, self.mixing_size, self.num_steps = int(fp_size), int(mixing_size), int(num_steps)
         self.fp_l2 = float(fp_l2)
+        self.dropout_rate = ops.check_dropout_rate(dropout_rate)
+        if dropout_seed is None and self.dropout_rate > 0.0:
+            dropout_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        self._dropout_counter = None
         self.device = device or L.default_device()
         dev = dict(device=self.device)
         D, K, S = self.atom_dim, self.bond_dim, self.num_steps
@@ -54,7 +62,7 @@ class MPNNModel:
             for i in range(S):
                 br["bmm"].append(L.BondMatrixMessage(D, K, name=f"{p}_bmm_{i}", **dev))
                 br["reduce"].append(L.Reduce(name=f"{p}_reduce_{i}", **dev))
-                br["update"].append(L.GatedUpdate(D, **dev))
+                br["update"].append(L.GatedUpdate(D, dropout_rate=self.dropout_rate, dropout_seed=self.dropout_seed, **dev))
             br["pool"] = L.GlobalSumPool(**dev)
             br["fp"] = L.Dense(fp_size, activation="relu", kernel_regularizer=("l2", fp_l2), **dev)
             self.branches[p] = br
@@ -165,7 +173,7 @@ class MPNNModel:
         return {"name": self.name, "kind": self.kind, "atom_vocab_size": self.atom_vocab_size,
                 "bond_vocab_size": self.bond_vocab_size, "atom_dim": self.atom_dim, "bond_dim": self.bond_dim,
                 "fp_size": self.fp_size, "mixing_size": self.mixing_size, "num_steps": self.num_steps,
-                "fp_l2": self.fp_l2,
+                "fp_l2": self.fp_l2, "dropout_rate": self.dropout_rate, "dropout_seed": self.dropout_seed,
                 "layers": [{"class_name": type(l).__name__, "config": l.get_config()} for l in self.layers]}
 
     @classmethod
@@ -173,7 +181,8 @@ class MPNNModel:
         L.reset_uids()  # keras auto-names (gated_update_3, ...) restart with a new model graph
         return cls(config["kind"], config["atom_vocab_size"], config["bond_vocab_size"], config["atom_dim"],
                    config["bond_dim"], config["fp_size"], config["mixing_size"], config["num_steps"],
-                   config.get("fp_l2", 1e-4), device=device, name=config.get("name"))
+                   config.get("fp_l2", 1e-4), device=device, name=config.get("name"),
+                   dropout_rate=config.get("dropout_rate", 0.0), dropout_seed=config.get("dropout_seed"))
 
     def save_weights(self, path):
         """All variables under their Keras-style names (ionic_mpnn_amd.weights) plus the config, as one .npz."""
@@ -304,8 +313,25 @@ class MPNNModel:
             self.bond_emb.embeddings, *[self.branches[p]["bmm"][i].bond_transform for p, i in keys])
         return {k: (mats[j], None if pool is None else pool[j]) for j, k in enumerate(keys)}
 
-    def encode_layered(self, prefix, atom_ids, bond_ids, conn, trace=None, typed=True, type_mats=None):
-        """encode() layer at a time (train_viscosity.py:171-187) -> pooled (B,D); type_mats: _all_type_matrices()."""
+    def dropout_counter(self):
+        """The model's device dropout step counter (None at rate 0): every training pass snapshots and advances it once
+        (ops.dropout_step), before the two ions fork, and both ions' layers draw their masks from that snapshot."""
+        if self.dropout_rate == 0.0:
+            return None
+        if self._dropout_counter is None:
+            self._dropout_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
+        return self._dropout_counter
+
+    def _layer_dropout(self, prefix, i, step):
+        """ops.Dropout of step i of an ion in the pass whose snapshot is ``step`` (layer id: cation i, anion S + i)."""
+        from . import dist as idist
+        lid = i + (self.num_steps if prefix == "an" else 0)
+        return ops.Dropout(self.dropout_rate, self.dropout_seed, ops.dropout_layer_word(lid, idist.dropout_rank()), step)
+
+    def encode_layered(self, prefix, atom_ids, bond_ids, conn, trace=None, typed=True, type_mats=None,
+                       dropout_step=None):
+        """encode() layer at a time (train_viscosity.py:171-187) -> pooled (B,D); type_mats: _all_type_matrices().
+        dropout_step: the pass's dropout snapshot (a training pass of a model with dropout_rate > 0), else None."""
         br = self.branches[prefix]
         graph = ops.IonGraph(atom_ids, bond_ids, conn, self.bond_vocab_size)  # the message calls of all layers share it
         h = self.atom_emb(atom_ids)
@@ -326,6 +352,7 @@ class MPNNModel:
             #  step is bound by its launch count and the list's own launches cost more than the skipped rows save)
             rows = ops.kept_row_index(atom_ids, bond_ids, conn, self.bond_vocab_size)
         for i in range(self.num_steps):
+            drop = self._layer_dropout(prefix, i, dropout_step) if dropout_step is not None else None
             if one_node:
                 from . import autograd
                 mats, dmats = type_mats[(prefix, i)] if type_mats else (br["bmm"][i]._type_matrices(bond.table), None)
@@ -333,18 +360,18 @@ class MPNNModel:
                 h = autograd.MessagePassingStep.apply(
                     h, bond.ids, conn, mats, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
                     w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta, u.epsilon, graph, dmats,
-                    *(rows if rows is not None else (None, None)), i > 0)
+                    *(rows if rows is not None else (None, None)), i > 0, drop)
                 continue
             if typed:  # (the layer's own call would sort the edges again)
                 m = ops.bmm_message_typed(h, bond.ids, conn, br["bmm"][i]._type_matrices(bond.table), graph)
             else:
                 m = br["bmm"][i]([h, bond, conn])
             agg = br["reduce"][i]([m, conn[:, :, 1], h])
-            if rows is not None:
+            if rows is not None or drop is not None:
                 u, w = br["update"][i], br["update"][i]._weights
                 h = ops.gated_update(h, agg, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
                                      w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta,
-                                     u.epsilon, rows=rows)
+                                     u.epsilon, rows=rows, dropout=drop)
             else:
                 h = br["update"][i]([h, agg])
             if trace is not None:
@@ -368,8 +395,9 @@ class MPNNModel:
         return self._pipeline.plan(ions, self.atom_dim, self.bond_dim, self.num_steps, self.atom_vocab_size,
                                    self.bond_vocab_size, mode=mode, workgroups=self.encoder_workgroups)
 
-    def encode_pooled(self, inputs, fused=None, trace=None, plan=None):
-        """Both ions' GlobalSumPool outputs: the hot path."""
+    def encode_pooled(self, inputs, fused=None, trace=None, plan=None, training=False):
+        """Both ions' GlobalSumPool outputs: the hot path.  ``training`` (layer at a time only):
+        a training pass - GatedUpdate's dropout applies when the model has a rate above 0."""
         if plan is not None:
             mode = plan.mode
             pc, pa = self._pipeline.run(plan, self.atom_emb.embeddings, self.bond_emb.embeddings,
@@ -399,14 +427,19 @@ class MPNNModel:
             if trace is not None:
                 trace["cat/pooled"], trace["an/pooled"] = pc, pa
             return pc, pa
+        if training and fused:
+            raise ValueError("a training pass runs layer at a time (fused=False)")
+        # dropout: one snapshot of the step counter per pass, taken before the ions fork; it lives with the pass
+        # (the autograd nodes of both ions hold it), so interleaved passes keep their own masks in the backward
+        ds = ops.dropout_step(self.dropout_counter()) if training and self.dropout_rate > 0.0 else None
         tm = self._all_type_matrices() if trace is None else None
         if trace is None and getattr(self, "two_streams", True) and ca.is_cuda \
                 and ca.shape[0] <= int(os.environ.get("IMPNN_TWO_STREAM_MAX_BATCH", TWO_STREAM_MAX_BATCH)):
-            return self._encode_two_streams((ca, cb, cc), (aa, ab, ac), tm)
-        return (self.encode_layered("cat", ca, cb, cc, trace, type_mats=tm),
-                self.encode_layered("an", aa, ab, ac, trace, type_mats=tm))
+            return self._encode_two_streams((ca, cb, cc), (aa, ab, ac), tm, ds)
+        return (self.encode_layered("cat", ca, cb, cc, trace, type_mats=tm, dropout_step=ds),
+                self.encode_layered("an", aa, ab, ac, trace, type_mats=tm, dropout_step=ds))
 
-    def _encode_two_streams(self, cat, an, tm):
+    def _encode_two_streams(self, cat, an, tm, dropout_step=None):
         """Layer-at-a-time path: the two ions' chains are independent until the head, and most of their kernels
         leave part of the chip idle (a batch-32 kernel nearly all of it) - the anion chain runs on a second HIP stream
         (in training: a parallel branch of the captured hipGraph; autograd replays each node's backward on the stream
@@ -430,10 +463,12 @@ class MPNNModel:
                     dmats.record_stream(side)
         for t in an:
             t.record_stream(side)
+        if dropout_step is not None:
+            dropout_step.record_stream(side)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            pa = self.encode_layered("an", *an, None, type_mats=tm)
-        pc = self.encode_layered("cat", *cat, None, type_mats=tm)
+            pa = self.encode_layered("an", *an, None, type_mats=tm, dropout_step=dropout_step)
+        pc = self.encode_layered("cat", *cat, None, type_mats=tm, dropout_step=dropout_step)
         cur.wait_stream(side)
         pa.record_stream(cur)
         self._side_stream_used = True
@@ -482,7 +517,7 @@ class MPNNModel:
         head as one autograd node over impnn_model_head_tensors / impnn_model_head_bwd."""
         inputs = self._to_device(inputs)
         if training:
-            pc, pa = self.encode_pooled(inputs, fused=False)
+            pc, pa = self.encode_pooled(inputs, fused=False, training=True)
             return self.head(pc, pa, inputs.get("temperature"), differentiable=True)
         with torch.no_grad():
             pc, pa = self.encode_pooled(inputs, fused=fused, trace=trace)
@@ -529,7 +564,7 @@ class MPNNModel:
             ws = getattr(self, "_loss_ws", None)
             if ws is None or ws.numel() < need:
                 ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
-            pc, pa = self.encode_pooled(inputs, fused=False)
+            pc, pa = self.encode_pooled(inputs, fused=False, training=True)
             T = inputs.get("temperature") if self.kind == "viscosity" else None
             return autograd.ModelHeadLoss.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
                                                 self.mixing_size, self._head_l2(), ws, pc, pa, T, y,
@@ -714,17 +749,19 @@ class MPNNModel:
 
 
 def build_model(atom_vocab_size, bond_vocab_size, atom_dim=32, bond_dim=8, fp_size=32, mixing_size=20,
-                num_steps=4, device=None):
-    """train_viscosity.py:139-231 (same positional/keyword signature and defaults)."""
+                num_steps=4, device=None, dropout_rate=0.0, dropout_seed=None):
+    """train_viscosity.py:139-231 (same positional/keyword signature and defaults; dropout_rate / dropout_seed:
+    GatedUpdate's Dropout in training, MPNNModel)."""
     return MPNNModel("viscosity", atom_vocab_size, bond_vocab_size, atom_dim, bond_dim, fp_size, mixing_size,
-                     num_steps, fp_l2=1e-4, device=device)
+                     num_steps, fp_l2=1e-4, device=device, dropout_rate=dropout_rate, dropout_seed=dropout_seed)
 
 
 def build_melting_point_model(atom_vocab_size, bond_vocab_size, atom_dim=32, fp_size=32, mixing_size=20,
-                              num_steps=4, device=None):
+                              num_steps=4, device=None, dropout_rate=0.0, dropout_seed=None):
     """train_melting_point.py:137-215: bond embedding width = atom_dim**2 (:146)."""
     return MPNNModel("melting_point", atom_vocab_size, bond_vocab_size, atom_dim, atom_dim * atom_dim, fp_size,
-                     mixing_size, num_steps, fp_l2=1e-5, device=device)
+                     mixing_size, num_steps, fp_l2=1e-5, device=device, dropout_rate=dropout_rate,
+                     dropout_seed=dropout_seed)
 
 
 def load_model(path, custom_objects=None, device=None):

@@ -273,13 +273,76 @@ def kept_row_index(atom_ids, bond_ids, conn, Vb):
     return idx, cnt
 
 
-def gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps=LN_EPS, rows=None, save=False):
+def check_dropout_rate(rate):
+    """-> rate as a float; ValueError unless 0 <= rate < 1 (also after rounding to float32, as the kernels see it)."""
+    r = float(rate)
+    if not (0.0 <= r < 1.0) or not float(torch.tensor(r, dtype=torch.float32)) < 1.0:
+        raise ValueError(f"dropout rate must satisfy 0 <= rate < 1, got {rate!r}")
+    return r
+
+
+def dropout_layer_word(layer_id, rank=0):
+    """The mask's layer counter word: layer_id | (rank << 16) (a model's cation step i is layer i, anion step i S + i)."""
+    layer_id, rank = int(layer_id), int(rank)
+    if not (0 <= layer_id < 1 << 16 and 0 <= rank < 1 << 15):
+        raise ValueError(f"dropout layer id {layer_id} / rank {rank} out of range")
+    return layer_id | (rank << 16)
+
+
+class Dropout:
+    """GatedUpdate's dropout in one training pass (include/impnn.h, impnn_*_dropout): rate, the 64-bit seed, the layer
+    word and ``step`` - a device int64 tensor of one element, the pass's snapshot of a dropout counter
+    (dropout_step).  The backward regenerates the mask from the same four values."""
+
+    __slots__ = ("rate", "seed", "layer_word", "step")
+
+    def __init__(self, rate, seed, layer_word, step):
+        self.rate = check_dropout_rate(rate)
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.layer_word = int(layer_word)
+        if not isinstance(step, torch.Tensor) or step.dtype != torch.int64 or step.numel() != 1:
+            raise TypeError("Dropout.step must be a one-element int64 device tensor (ops.dropout_step)")
+        self.step = step
+
+    def args(self):
+        return (float(self.rate), C.c_uint64(self.seed), ptr(self.step), int(self.layer_word))
+
+
+def dropout_step(counter):
+    """One launch: a fresh snapshot slot <- *counter, *counter += 1 (both device int64).  Returns the snapshot."""
+    require_gpu(counter)
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise TypeError("the dropout counter must be a one-element int64 tensor")
+    snap = torch.empty(1, dtype=torch.int64, device=counter.device)
+    with torch.cuda.device(counter.device):
+        check(_lib.load().impnn_dropout_step(ptr(counter), ptr(snap), stream_ptr()))
+    return snap
+
+
+def dropout_mask(dropout, rows, D, row_list=None):
+    """The (rows, D) float32 mask the GatedUpdate kernels apply for ``dropout`` (impnn_dropout_mask): scale where kept,
+    0 where dropped; with ``row_list`` = (row_index, n_rows) only the listed rows (zeros elsewhere)."""
+    out = torch.zeros(int(rows), int(D), dtype=torch.float32, device=dropout.step.device)
+    ri, rn = (ptr(row_list[0]), ptr(row_list[1])) if row_list is not None else (None, None)
+    rate, seed, step, lw = dropout.args()
+    with torch.cuda.device(out.device):
+        check(_lib.load().impnn_dropout_mask(seed, step, lw, rate, ri, rn, int(rows), int(D), ptr(out), stream_ptr()))
+    return out
+
+
+def gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps=LN_EPS, rows=None, save=False, dropout=None):
     """GatedUpdate.call, models/layers.py:142-156.  ``rows`` = (row_index, n_rows) of kept_row_index: only those rows
     of the output are computed (model-internal use: padding atoms; the rest of ``out`` is undefined).
     ``save`` (atom_dim 32 / 64 / 128; the training forward): returns (out, saved) - the gates, the candidate
-    and r * h of the listed rows for impnn_gated_update_rows_bwd_saved."""
+    and r * h of the listed rows for impnn_gated_update_rows_bwd_saved.
+    ``dropout`` (an ops.Dropout; training): the output goes through its mask, fused into the kernel's final store.
+    None or rate 0 is the plain forward, bit for bit."""
+    if dropout is not None and dropout.rate == 0.0:
+        dropout = None
     if _wants_grad(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta):
         from . import autograd
+        if dropout is not None:
+            return autograd.GatedUpdate.apply(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, dropout)
         return autograd.GatedUpdate.apply(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps)
     require_gpu(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta)
     if h.shape != agg.shape:
@@ -292,6 +355,21 @@ def gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps=LN_EPS, rows=N
     out = torch.empty_like(ts[0])
     nrows = ts[0].numel() // D
     with torch.cuda.device(h.device):
+        if dropout is not None:
+            lib = _lib.load()
+            saved = None
+            if save:
+                saved = torch.empty(int(lib.impnn_gated_update_rows_saved_floats(nrows, D)), dtype=torch.float32,
+                                    device=h.device)
+            if save or rows is not None:
+                ri, rn = (ptr(rows[0]), ptr(rows[1])) if rows is not None else (None, None)
+                check(lib.impnn_gated_update_rows_train_dropout(*[ptr(t) for t in ts], float(eps), ptr(out), ri, rn, nrows,
+                                                                D, ptr(saved) if saved is not None else None,
+                                                                *dropout.args(), stream_ptr()))
+            else:
+                check(lib.impnn_gated_update_dropout(*[ptr(t) for t in ts], float(eps), ptr(out), nrows, D,
+                                                     *dropout.args(), stream_ptr()))
+            return (out, saved) if save else out
         if save:
             lib = _lib.load()
             saved = torch.empty(int(lib.impnn_gated_update_rows_saved_floats(nrows, D)), dtype=torch.float32,

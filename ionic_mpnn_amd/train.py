@@ -96,7 +96,7 @@ class GraphedTrainStep:
     (torch.cuda.CUDAGraph) and replayed per mini-batch: the reference trains with batches of 32
     (train_viscosity.py:332), where a step is ~150 small launches and the host, not the GPU, sets the pace.
     Inputs are copied into static buffers; every kernel argument that changes between steps lives in device
-    memory (the Adam step counter)."""
+    memory (the Adam step counter, the dropout step counter that the captured snapshot launch advances)."""
 
     def __init__(self, model, inputs, y, resident=None):
         """``resident=(x, y_dev)``: the whole padded training set lives on the device; the captured step then starts
@@ -120,6 +120,8 @@ class GraphedTrainStep:
         opt = model.optimizer
         saved_w = [t.detach().clone() for _, t in model.trainable_variables()]
         saved_o = opt.state()
+        ctr = model.dropout_counter()  # the dropout step counter: the warm-up steps advance it, like the Adam state
+        saved_c = ctr.clone() if ctr is not None else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):  # warm-up off the default stream, as graph capture requires
@@ -133,6 +135,8 @@ class GraphedTrainStep:
             for (_, t), w0 in zip(model.trainable_variables(), saved_w):
                 t.copy_(w0)
         opt.load_state(saved_o)
+        if ctr is not None:
+            ctr.copy_(saved_c)
         opt.zero_grad()
         model.invalidate_packed_weights()
 
