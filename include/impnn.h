@@ -89,26 +89,126 @@ int impnn_bmm_fused(const float* h, const float* bond_state, const int32_t* conn
                     float* agg, int32_t B, int32_t N, int32_t E, int32_t D, int32_t K,
                     impnn_stream_t stream);
 
-/* ---- a7: GatedUpdate.call (models/layers.py:142-156) over `rows` = B*N atom rows (padding rows
- *      included, as the reference computes them).  Wz/Wr/Wh are keras Dense kernels (2D,D)
- *      (input-major), b* (D,), LayerNormalization gamma/beta (D,), eps = 1e-3 by keras default. */
+/* ---- a7: GatedUpdate (models/layers.py:142-156), forward and backward, one family of entries.
+ *  Forward: GatedUpdate.call on `rows` = B*N atom rows (padding rows included, as the reference computes them).
+ *  Wz/Wr/Wh are keras Dense kernels (2D,D) (input-major), b* (D,), LayerNormalization gamma/beta (D,), eps = 1e-3 by
+ *  keras default.  Backward: dh, dagg (rows,D) and dparams, as "Backward" below describes.
+ *
+ *  entry (impnn_gated_update..)  rows         atom_dim              extra buffers              workspace query
+ *  (forward)                     all          any                   -                          -
+ *  _rows                         the list     32, 64, 128           row list                   -
+ *  _rows_train                   list or all  32, 64, 128           row list or none, saved    -
+ *  _dropout                      all          any                   dropout                    -
+ *  _rows_train_dropout           list or all  any; with saved:      row list or none, saved    -
+ *                                             32, 64, 128           or none, dropout
+ *  _bwd                          all          divides 256           -                          _bwd_workspace_floats
+ *  _rows_bwd                     the list     64, 128               row list                   _rows_bwd_workspace_floats
+ *  _rows_bwd_saved               list or all  32 (all rows), 64,    row list or none, saved    _rows_bwd_...; at 32
+ *                                             128                                              _bwd_workspace_floats
+ *  _bwd_dropout, _rows_bwd_dropout, _rows_bwd_saved_dropout: the entry without the suffix, + dropout
+ *
+ *  Row list (row_index, n_rows): only rows row_index[0 .. *n_rows) of h / agg / out (dh / dagg) are read and written;
+ *    the others are left untouched, and the parameter gradients are sums over the listed rows.  *n_rows lives on the
+ *    device (no host round trip, capturable); the launch is sized for max_rows.  Padding atoms reach neither a message
+ *    nor the pool (no valid edge names them), so a caller that owns the whole encode() loop may skip them:
+ *    impnn_kept_rows and impnn_row_index_fill below build that list.  "row list or none": both NULL = all max_rows.
+ *  saved (impnn_gated_update_rows_saved_floats(max_rows, D) = 4 D max_rows floats, 16-byte aligned): the training
+ *    forward writes, per listed row (by list position), the gates z, r, the candidate tanh(.) and r * h of
+ *    models/layers.py:145-152; the saving backward uses them instead of its two recompute GEMM passes (half of its
+ *    matrix work) and CONSUMES the buffer (it comes back holding the pre-activation gradients; a second backward over
+ *    it needs a second forward).
+ *  dropout (rate, seed, step, layer_word) - Dropout(rate)(LN(n) + h, training=True) of models/layers.py:156, fused
+ *    into the kernels.  The mask is not stored: element (row, column) of the (rows, D) output, row = the flat row of h
+ *    (for row-list calls the row the list names, so both forms draw the same mask), draws word column % 4 of
+ *        Philox4x32-10(counter = (column / 4, row, layer_word, lo32(*step)),
+ *                      key     = (lo32(seed), hi32(seed) ^ hi32(*step)))
+ *    and is kept iff (word >> 8) * 2^-24 >= rate; kept: out * (1.0f / (1.0f - rate)) (one f32 multiply), dropped: +0.
+ *    layer_word = layer_id | (rank << 16).  `step` is a DEVICE int64 (a snapshot slot of impnn_dropout_step): the
+ *    kernels read it when they run, so a captured step draws a fresh mask on every replay.  The forwards apply the
+ *    mask on the final store (after the residual; `saved` keeps the pre-dropout values), the backwards read dout
+ *    through the same mask and scale.
+ *
+ *  Rules shared by the family, checked in this order:
+ *    1. dropout: step != NULL, then 0 <= rate < 1 (IMPNN_E_BADARG).  rate == 0 is the plain entry's call, results and
+ *       status bit for bit (_rows_train_dropout: _rows_train with saved, else _rows with a row list, else the forward).
+ *    2. rows >= 0 (IMPNN_E_BADARG); an atom_dim outside "any" (> 0) or "divides 256" is IMPNN_E_BADARG, outside a
+ *       fixed set IMPNN_E_UNSUPPORTED, as is a saved buffer at an atom_dim other than 32, 64 and 128.
+ *    3. the forwards: rows == 0 returns 0 before any pointer is read.
+ *    4. a null tensor, or a row list with only one of row_index / n_rows: IMPNN_E_BADARG.
+ *    5. then the forwards: saved 16-byte aligned, ln_eps >= 0 (IMPNN_E_BADARG); a row list at an atom_dim other
+ *       than 32, 64 and 128 is IMPNN_E_UNSUPPORTED; at atom_dim 32 a row list or a saved buffer needs h, agg and out
+ *       16-byte aligned (IMPNN_E_BADARG).
+ *    6. then the backwards: a row list at an atom_dim other than 64 and 128 is IMPNN_E_UNSUPPORTED; workspace_floats
+ *       below the form's query is IMPNN_E_WORKSPACE; rows == 0 then returns 0 for the row-list and saving forms (the
+ *       plain backward still runs and writes dparams); the row-list and saving forms need h, agg, dout, dh, dagg,
+ *       workspace and saved 16-byte aligned (IMPNN_E_BADARG).  The backwards do not check ln_eps. */
 int impnn_gated_update(const float* h, const float* agg, const float* Wz, const float* bz,
                        const float* Wr, const float* br, const float* Wh, const float* bh,
                        const float* gamma, const float* beta, float ln_eps, float* out,
                        int64_t rows, int32_t D, impnn_stream_t stream);
-
-/* ---- a7 on a row list: the same arithmetic on rows row_index[0 .. *n_rows) of h / agg / out only (all other rows of
- *      `out` are left untouched).  The reference computes GatedUpdate on padding atoms too; their values can reach
- *      neither a message (no valid edge names them) nor the pool, so a caller that owns the whole encode() loop may
- *      skip them: impnn_kept_rows gives, per molecule, r_b = 1 + max(last n with atom_ids[b,n] > 0, largest atom
- *      index on a valid edge) (the kept rows are closed under "is a source of": skipping is exact), and
- *      impnn_row_index_fill turns r and its inclusive prefix sum into the flat list b*N + [0, r_b) and its length
- *      (*n_rows, device memory - no host round trip; the launch is sized for max_rows = B*N).  atom_dim 32 / 64 / 128. */
 int impnn_gated_update_rows(const float* h, const float* agg, const float* Wz, const float* bz,
                             const float* Wr, const float* br, const float* Wh, const float* bh,
                             const float* gamma, const float* beta, float ln_eps, float* out,
                             const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
                             impnn_stream_t stream);
+int64_t impnn_gated_update_rows_saved_floats(int64_t max_rows, int32_t D);
+int impnn_gated_update_rows_train(const float* h, const float* agg, const float* Wz, const float* bz,
+                                  const float* Wr, const float* br, const float* Wh, const float* bh,
+                                  const float* gamma, const float* beta, float ln_eps, float* out,
+                                  const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                  float* saved, impnn_stream_t stream);
+int impnn_gated_update_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                               const float* br, const float* Wh, const float* bh, const float* gamma,
+                               const float* beta, float ln_eps, float* out, int64_t rows, int32_t D, float rate,
+                               uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream);
+int impnn_gated_update_rows_train_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                          const float* Wr, const float* br, const float* Wh, const float* bh,
+                                          const float* gamma, const float* beta, float ln_eps, float* out,
+                                          const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                          float* saved, float rate, uint64_t seed, const int64_t* step,
+                                          int32_t layer_word, impnn_stream_t stream);
+int64_t impnn_gated_update_param_floats(int32_t D);
+int64_t impnn_gated_update_bwd_workspace_floats(int64_t rows, int32_t D);
+int impnn_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                           const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                           const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                           int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate,
+                           impnn_stream_t stream);
+int64_t impnn_gated_update_rows_bwd_workspace_floats(int64_t max_rows, int32_t D);
+int impnn_gated_update_rows_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                                const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                                const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                                int64_t workspace_floats, const int32_t* row_index, const int32_t* n_rows,
+                                int64_t max_rows, int32_t D, int32_t accumulate, impnn_stream_t stream);
+int impnn_gated_update_rows_bwd_saved(const float* h, const float* agg, const float* Wz, const float* bz,
+                                      const float* Wr, const float* br, const float* Wh, const float* bh,
+                                      const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
+                                      float* dparams, float* workspace, int64_t workspace_floats,
+                                      const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                      int32_t accumulate, float* saved, impnn_stream_t stream);
+int impnn_gated_update_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                                   const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                                   const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                                   int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate, float rate,
+                                   uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream);
+int impnn_gated_update_rows_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                        const float* Wr, const float* br, const float* Wh, const float* bh,
+                                        const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
+                                        float* dparams, float* workspace, int64_t workspace_floats,
+                                        const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                        int32_t accumulate, float rate, uint64_t seed, const int64_t* step,
+                                        int32_t layer_word, impnn_stream_t stream);
+int impnn_gated_update_rows_bwd_saved_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
+                                              const float* Wr, const float* br, const float* Wh, const float* bh,
+                                              const float* gamma, float ln_eps, const float* dout, float* dh,
+                                              float* dagg, float* dparams, float* workspace, int64_t workspace_floats,
+                                              const int32_t* row_index, const int32_t* n_rows, int64_t max_rows,
+                                              int32_t D, int32_t accumulate, float* saved, float rate, uint64_t seed,
+                                              const int64_t* step, int32_t layer_word, impnn_stream_t stream);
+/* The row list of an encode() loop: impnn_kept_rows gives, per molecule, r_b = 1 + max(last n with atom_ids[b,n] > 0,
+ * largest atom index on a valid edge) (the kept rows are closed under "is a source of": skipping is exact), and
+ * impnn_row_index_fill turns r and its inclusive prefix sum into the flat list b*N + [0, r_b) and its length (*n_rows,
+ * device memory; the GatedUpdate launches are sized for max_rows = B*N). */
 int impnn_kept_rows(const int32_t* atom_ids, const int32_t* bond_ids, const int32_t* conn, int32_t* rows_out,
                     int32_t B, int32_t N, int32_t E, int32_t Vb, impnn_stream_t stream);
 int impnn_row_index_fill(const int32_t* kept_rows, const int32_t* kept_rows_inclusive_prefix,
@@ -403,87 +503,6 @@ int impnn_bond_type_matrices_multi_bwd_ws(const float* bond_table, const float* 
                                           const float* const* dtype_mats, float* const* dW, float* dbond_table,
                                           int32_t n, int32_t Vb, int32_t K, int32_t D, int32_t accumulate,
                                           float* workspace, int64_t workspace_floats, impnn_stream_t stream);
-int64_t impnn_gated_update_param_floats(int32_t D);
-int64_t impnn_gated_update_bwd_workspace_floats(int64_t rows, int32_t D);
-int impnn_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                           const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
-                           const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                           int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate,
-                           impnn_stream_t stream);
-/* a7 backward on a row list (the adjoint of impnn_gated_update_rows; atom_dim 64 / 128): gradients of the rows
- * row_index[0 .. *n_rows) only - dh / dagg rows outside the list are left untouched (a caller that reads them zeroes
- * them first), the parameter gradients are sums over the listed rows.  Padding atoms of an encode() loop carry no
- * gradient (nothing they compute reaches a message or the pool), so this is exact for impnn_kept_rows' list.
- * The launch is sized for max_rows; *n_rows lives on the device (no host round trip, capturable). */
-int64_t impnn_gated_update_rows_bwd_workspace_floats(int64_t max_rows, int32_t D);
-int impnn_gated_update_rows_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                                const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
-                                const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                                int64_t workspace_floats, const int32_t* row_index, const int32_t* n_rows,
-                                int64_t max_rows, int32_t D, int32_t accumulate, impnn_stream_t stream);
-/* The same pair for a training loop that keeps activations instead of recomputing them (atom_dim 64 / 128, and 32
- * without a row list - workspace of impnn_gated_update_bwd_workspace_floats there):
- * impnn_gated_update_rows_train is impnn_gated_update_rows that also writes, per LISTED row (by list position), the
- * gates z, r, the candidate tanh(.) and r * h of models/layers.py:145-152 into `saved`
- * (impnn_gated_update_rows_saved_floats(max_rows, D) = 4 D max_rows floats, 16-byte aligned);
- * impnn_gated_update_rows_bwd_saved is impnn_gated_update_rows_bwd without its two recompute GEMM passes (half of its
- * matrix work): same arguments, same workspace size, plus that buffer - which it CONSUMES (it comes back holding the
- * pre-activation gradients; a second backward over it needs a second forward).  Both take row_index = n_rows = NULL
- * for "all max_rows rows" (the small batches a training loop does not build a list for). */
-int64_t impnn_gated_update_rows_saved_floats(int64_t max_rows, int32_t D);
-int impnn_gated_update_rows_train(const float* h, const float* agg, const float* Wz, const float* bz,
-                                  const float* Wr, const float* br, const float* Wh, const float* bh,
-                                  const float* gamma, const float* beta, float ln_eps, float* out,
-                                  const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
-                                  float* saved, impnn_stream_t stream);
-int impnn_gated_update_rows_bwd_saved(const float* h, const float* agg, const float* Wz, const float* bz,
-                                      const float* Wr, const float* br, const float* Wh, const float* bh,
-                                      const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
-                                      float* dparams, float* workspace, int64_t workspace_floats,
-                                      const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
-                                      int32_t accumulate, float* saved, impnn_stream_t stream);
-
-/*  GatedUpdate dropout in training (models/layers.py:156: Dropout(rate)(LN(n) + h, training=True)), fused into the
- *  GatedUpdate kernels.  The mask is not stored: element (row, column) of the (rows, D) output, row = the flat row of
- *  h (for row-list calls the row the list names, so both forms draw the same mask), draws word column % 4 of
- *      Philox4x32-10(counter = (column / 4, row, layer_word, lo32(*step)),
- *                    key     = (lo32(seed), hi32(seed) ^ hi32(*step)))
- *  and is kept iff (word >> 8) * 2^-24 >= rate; kept: out * (1.0f / (1.0f - rate)) (one f32 multiply), dropped: +0.
- *  layer_word = layer_id | (rank << 16).  `step` is a DEVICE int64 (a snapshot slot of impnn_dropout_step): the kernels
- *  read it when they run, so a captured step draws a fresh mask on every replay.  0 <= rate < 1, else IMPNN_E_BADARG.
- *  Each entry below is the entry without the suffix plus (rate, seed, step, layer_word); the forwards apply the mask on
- *  the final store (after the residual; `saved` keeps the pre-dropout gates, candidate and r * h), the backwards read
- *  dout through the same mask and scale.  rate == 0 gives the plain entry's results bit for bit (it is called). */
-int impnn_gated_update_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                               const float* br, const float* Wh, const float* bh, const float* gamma,
-                               const float* beta, float ln_eps, float* out, int64_t rows, int32_t D, float rate,
-                               uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream);
-/* row_index / n_rows: both or neither (NULL: all max_rows rows); saved: NULL, or as impnn_gated_update_rows_train */
-int impnn_gated_update_rows_train_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
-                                          const float* Wr, const float* br, const float* Wh, const float* bh,
-                                          const float* gamma, const float* beta, float ln_eps, float* out,
-                                          const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
-                                          float* saved, float rate, uint64_t seed, const int64_t* step,
-                                          int32_t layer_word, impnn_stream_t stream);
-int impnn_gated_update_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                                   const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
-                                   const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                                   int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate, float rate,
-                                   uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream);
-int impnn_gated_update_rows_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
-                                        const float* Wr, const float* br, const float* Wh, const float* bh,
-                                        const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
-                                        float* dparams, float* workspace, int64_t workspace_floats,
-                                        const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
-                                        int32_t accumulate, float rate, uint64_t seed, const int64_t* step,
-                                        int32_t layer_word, impnn_stream_t stream);
-int impnn_gated_update_rows_bwd_saved_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
-                                              const float* Wr, const float* br, const float* Wh, const float* bh,
-                                              const float* gamma, float ln_eps, const float* dout, float* dh,
-                                              float* dagg, float* dparams, float* workspace, int64_t workspace_floats,
-                                              const int32_t* row_index, const int32_t* n_rows, int64_t max_rows,
-                                              int32_t D, int32_t accumulate, float* saved, float rate, uint64_t seed,
-                                              const int64_t* step, int32_t layer_word, impnn_stream_t stream);
 /* One launch: *snapshot = *counter; *counter += 1 (both DEVICE int64).  A training pass takes its step this way, so
  * the step never passes through the host and a captured pass advances it on every replay. */
 int impnn_dropout_step(int64_t* counter, int64_t* snapshot, impnn_stream_t stream);

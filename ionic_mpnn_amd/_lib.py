@@ -18,6 +18,13 @@ _lib = None
 i32, i64, u64, f32, vp, sz = C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_void_p, C.c_size_t
 PP = C.POINTER(vp)
 
+# argument groups of the GatedUpdate entries: the forward's h .. out, the backward's h .. workspace_floats, a row list,
+# the dropout tail
+_GU_FWD = [vp] * 10 + [f32, vp]
+_GU_BWD = [vp] * 9 + [f32] + [vp] * 5 + [i64]
+_ROWS = [vp, vp]
+_DROP = [f32, u64, vp, i32]
+
 # name -> (restype, argtypes); mirrors include/impnn.h one to one
 SIGNATURES = {
     "impnn_abi_version": (C.c_int, []),
@@ -29,8 +36,8 @@ SIGNATURES = {
     "impnn_bmm_message_typed": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "impnn_reduce_scatter_add": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_bmm_fused": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "impnn_gated_update": (C.c_int, [vp] * 10 + [f32, vp, i64, i32, vp]),
-    "impnn_gated_update_rows": (C.c_int, [vp] * 10 + [f32, vp, vp, vp, i64, i32, vp]),
+    "impnn_gated_update": (C.c_int, _GU_FWD + [i64, i32, vp]),
+    "impnn_gated_update_rows": (C.c_int, _GU_FWD + _ROWS + [i64, i32, vp]),
     "impnn_kept_rows": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "impnn_row_index_fill": (C.c_int, [vp, vp, vp, vp, i32, i32, vp]),
     "impnn_global_sum_pool": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
@@ -73,19 +80,17 @@ SIGNATURES = {
     "impnn_bond_type_matrices_multi_bwd_ws": (C.c_int, [vp, PP, PP, PP, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
     "impnn_gated_update_param_floats": (i64, [i32]),
     "impnn_gated_update_bwd_workspace_floats": (i64, [i64, i32]),
-    "impnn_gated_update_bwd": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, i64, i32, i32, vp]),
+    "impnn_gated_update_bwd": (C.c_int, _GU_BWD + [i64, i32, i32, vp]),
     "impnn_gated_update_rows_bwd_workspace_floats": (i64, [i64, i32]),
-    "impnn_gated_update_rows_bwd": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, vp]),
+    "impnn_gated_update_rows_bwd": (C.c_int, _GU_BWD + _ROWS + [i64, i32, i32, vp]),
     "impnn_gated_update_rows_saved_floats": (i64, [i64, i32]),
-    "impnn_gated_update_rows_train": (C.c_int, [vp] * 10 + [f32, vp, vp, vp, i64, i32, vp, vp]),
-    "impnn_gated_update_rows_bwd_saved": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, vp, vp]),
-    "impnn_gated_update_dropout": (C.c_int, [vp] * 10 + [f32, vp, i64, i32, f32, u64, vp, i32, vp]),
-    "impnn_gated_update_rows_train_dropout": (C.c_int, [vp] * 10 + [f32, vp, vp, vp, i64, i32, vp, f32, u64, vp, i32, vp]),
-    "impnn_gated_update_bwd_dropout": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, i64, i32, i32, f32, u64, vp, i32, vp]),
-    "impnn_gated_update_rows_bwd_dropout": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, f32, u64, vp,
-                                                                                 i32, vp]),
-    "impnn_gated_update_rows_bwd_saved_dropout": (C.c_int, [vp] * 9 + [f32] + [vp] * 5 + [i64, vp, vp, i64, i32, i32, vp, f32,
-                                                                                       u64, vp, i32, vp]),
+    "impnn_gated_update_rows_train": (C.c_int, _GU_FWD + _ROWS + [i64, i32, vp, vp]),
+    "impnn_gated_update_rows_bwd_saved": (C.c_int, _GU_BWD + _ROWS + [i64, i32, i32, vp, vp]),
+    "impnn_gated_update_dropout": (C.c_int, _GU_FWD + [i64, i32] + _DROP + [vp]),
+    "impnn_gated_update_rows_train_dropout": (C.c_int, _GU_FWD + _ROWS + [i64, i32, vp] + _DROP + [vp]),
+    "impnn_gated_update_bwd_dropout": (C.c_int, _GU_BWD + [i64, i32, i32] + _DROP + [vp]),
+    "impnn_gated_update_rows_bwd_dropout": (C.c_int, _GU_BWD + _ROWS + [i64, i32, i32] + _DROP + [vp]),
+    "impnn_gated_update_rows_bwd_saved_dropout": (C.c_int, _GU_BWD + _ROWS + [i64, i32, i32, vp] + _DROP + [vp]),
     "impnn_dropout_step": (C.c_int, [vp, vp, vp]),
     "impnn_dropout_mask": (C.c_int, [u64, vp, i32, f32, vp, vp, i64, i32, vp, vp]),
     "impnn_adam_clipnorm_step": (C.c_int, [vp, vp, i32, i64, f32, f32, f32, f32, f32, vp]),

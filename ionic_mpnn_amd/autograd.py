@@ -241,21 +241,11 @@ def _gated_update_backward(saved, eps, dout, row_list=None, kept=None, unlisted_
         wsn = int(lib.impnn_gated_update_bwd_workspace_floats(rows, D))
     ws = torch.empty(max(wsn, 1), dtype=torch.float32, device=h.device)
 
-    drop = dropout is not None and dropout.rate > 0.0
-    sfx, dargs = ("_dropout", dropout.args()) if drop else ("", ())
 
     def call(dparams, accumulate):
-        common = (ptr(h), ptr(agg), ptr(Wz), ptr(bz), ptr(Wr), ptr(br), ptr(Wh), ptr(bh), ptr(gamma), eps, ptr(dout),
-                  ptr(dh), ptr(dagg), ptr(dparams), ptr(ws), wsn)
-        if kept is not None:
-            ri, rn = (ptr(row_list[0]), ptr(row_list[1])) if row_list is not None else (None, None)
-            _lib_call(h.device, getattr(lib, "impnn_gated_update_rows_bwd_saved" + sfx), *common, ri, rn, rows, D,
-                      accumulate, ptr(kept), *dargs)
-        elif row_list is not None:
-            _lib_call(h.device, getattr(lib, "impnn_gated_update_rows_bwd" + sfx), *common, ptr(row_list[0]),
-                      ptr(row_list[1]), rows, D, accumulate, *dargs)
-        else:
-            _lib_call(h.device, getattr(lib, "impnn_gated_update_bwd" + sfx), *common, rows, D, accumulate, *dargs)
+        entry, tail = _gated_update_bwd_entry(lib, row_list, kept, dropout, rows, D, accumulate)
+        _lib_call(h.device, entry, ptr(h), ptr(agg), ptr(Wz), ptr(bz), ptr(Wr), ptr(br), ptr(Wh), ptr(bh), ptr(gamma),
+                  eps, ptr(dout), ptr(dh), ptr(dagg), ptr(dparams), ptr(ws), wsn, *tail)
     # the eight parameter gradients leave the kernel as one block in the canonical order; when the existing
     # .grad buffers form exactly that block (train.Adam's flat buffer does), the kernel adds into it directly
     params = (Wz, bz, Wr, br, Wh, bh, gamma, beta)
@@ -280,6 +270,20 @@ def _gated_update_backward(saved, eps, dout, row_list=None, kept=None, unlisted_
     grads.append(dparams[o:o + D])
     grads.append(dparams[o + D:o + 2 * D])
     return (dh, dagg, *grads, None)
+
+
+def _gated_update_bwd_entry(lib, row_list, kept, dropout, max_rows, D, accumulate):
+    """(row list?, kept?, dropout?) -> the backward entry and its arguments between the workspace size and the stream.
+    A ``dropout`` of rate 0 takes the plain entry."""
+    ri, rn = (ptr(row_list[0]), ptr(row_list[1])) if row_list is not None else (None, None)
+    d = dropout.args() if dropout is not None and dropout.rate > 0.0 else ()
+    if kept is not None:
+        entry = lib.impnn_gated_update_rows_bwd_saved_dropout if d else lib.impnn_gated_update_rows_bwd_saved
+        return entry, (ri, rn, max_rows, D, accumulate, ptr(kept), *d)
+    if row_list is not None:
+        entry = lib.impnn_gated_update_rows_bwd_dropout if d else lib.impnn_gated_update_rows_bwd
+        return entry, (ri, rn, max_rows, D, accumulate, *d)
+    return (lib.impnn_gated_update_bwd_dropout if d else lib.impnn_gated_update_bwd), (max_rows, D, accumulate, *d)
 
 
 # edge slots per ion from which the message adjoint writes per-edge vectors and sums them in slot order instead of adding

@@ -65,6 +65,135 @@ using namespace impnn;
     if (!(cond)) return fail(IMPNN_E_BADARG, "%s: %s", __func__, what); \
   } while (0)
 
+// ---- the GatedUpdate family (include/impnn.h).  Each entry fills a GatedUpdateCall with its form; one check per
+// direction applies the family's rules in a fixed order and launches.
+namespace {
+
+constexpr GuArg kNo = GuArg::kAbsent, kOpt = GuArg::kOptional, kReq = GuArg::kRequired;
+// impnn_gated_update(_dropout), _rows, _rows_train, _rows_train_dropout (rate > 0); a forward row list's atom_dims
+// (32, 64, 128) are checked after its arguments
+constexpr GatedUpdateForm kFwd{kNo, kNo, GuDims::kAny}, kFwdRows{kReq, kNo, GuDims::kAny},
+    kFwdTrain{kOpt, kReq, GuDims::k32_64_128}, kFwdTrainDropout{kOpt, kOpt, GuDims::kAny};
+// impnn_gated_update_bwd, _rows_bwd, _rows_bwd_saved, each with its _dropout twin
+constexpr GatedUpdateForm kBwd{kNo, kNo, GuDims::kDivide256}, kBwdRows{kReq, kNo, GuDims::k64_128},
+    kBwdSaved{kOpt, kReq, GuDims::k32_64_128};
+
+bool covers(GuDims dims, int D) {
+  switch (dims) {
+    case GuDims::kAny: return D > 0;
+    case GuDims::kDivide256: return D > 0 && D <= 256 && 256 % D == 0;
+    case GuDims::k32_64_128: return D == 32 || D == 64 || D == 128;
+    case GuDims::k64_128: return D == 64 || D == 128;
+  }
+  return false;
+}
+
+int uncovered(const GatedUpdateCall& c, const char* what) {
+  return fail(IMPNN_E_UNSUPPORTED, "%s: atom_dim %d (%s)", c.entry, c.D, what);
+}
+
+#define CHECK(cond, what)                                                  \
+  do {                                                                     \
+    if (!(cond)) return fail(IMPNN_E_BADARG, "%s: %s", c.entry, what);   \
+  } while (0)
+
+// rows >= 0 and the form's atom_dims: an open rule (any, divides 256) is part of the shape, a fixed set is coverage
+int check_shape(const GatedUpdateCall& c) {
+  const GuDims dims = c.form.dims;
+  const bool open = dims == GuDims::kAny || dims == GuDims::kDivide256;
+  CHECK(c.rows >= 0 && (!open || covers(dims, c.D)), dims == GuDims::kDivide256 ? "atom_dim must divide 256" : "bad shape");
+  if (!covers(dims, c.D))
+    return uncovered(c, dims == GuDims::k64_128 ? "the row-list form covers 64 and 128" : "the saving form covers 32, 64 and 128");
+  return IMPNN_OK;
+}
+
+// a form without a row list or a saved buffer leaves those pointers null
+void clear_absent(GatedUpdateCall& c) {
+  if (c.form.row_list == kNo) c.row_index = c.n_rows = nullptr;
+  if (c.form.saved == kNo) c.saved = nullptr;
+}
+
+int gated_update_checked(GatedUpdateCall c) {
+  clear_absent(c);
+  if (int rc = check_shape(c)) return rc;
+  if (c.saved && !covers(GuDims::k32_64_128, c.D)) return uncovered(c, "the saving forward covers 32, 64 and 128");
+  if (c.rows == 0) return IMPNN_OK;
+  CHECK(c.h && c.agg && c.Wz && c.bz && c.Wr && c.br && c.Wh && c.bh && c.gamma && c.beta && c.out &&
+            (c.form.row_list != kReq || (c.row_index && c.n_rows)) && (c.form.saved != kReq || c.saved),
+        "null pointer");
+  CHECK((c.row_index != nullptr) == (c.n_rows != nullptr), "row_index and n_rows: both or neither");
+  CHECK(!c.saved || aligned16(c.saved), "saved must be 16-byte aligned");
+  CHECK(c.eps >= 0.f, "ln_eps must be >= 0");
+  if (c.row_index && !covers(GuDims::k32_64_128, c.D)) return uncovered(c, "a row list covers 32, 64 and 128");
+  CHECK(c.D != 32 || !(c.row_index || c.saved) || (aligned16(c.h) && aligned16(c.agg) && aligned16(c.out)),
+        "a row list or saved buffer at atom_dim 32 needs 16-byte aligned tensors");
+  return launch_gated_update(c);
+}
+
+int gated_update_bwd_checked(GatedUpdateCall c) {
+  clear_absent(c);
+  if (int rc = check_shape(c)) return rc;
+  CHECK(c.h && c.agg && c.Wz && c.bz && c.Wr && c.br && c.Wh && c.bh && c.gamma && c.dout && c.dh && c.dagg &&
+            c.dparams && c.workspace && (c.form.row_list != kReq || (c.row_index && c.n_rows)) &&
+            (c.form.saved != kReq || c.saved),
+        "null pointer");
+  CHECK((c.row_index != nullptr) == (c.n_rows != nullptr), "row_index and n_rows: both or neither");
+  if (c.row_index && !covers(GuDims::k64_128, c.D)) return uncovered(c, "a row list covers 64 and 128");
+  // the forms that take a row list size their workspace for one (impnn_gated_update_rows_bwd_workspace_floats) where
+  // it exists, at atom_dim 64 / 128, list or not
+  const bool list_ws = c.form.row_list != kNo && covers(GuDims::k64_128, c.D);
+  if (c.workspace_floats < gated_update_bwd_workspace(c.rows, c.D, list_ws))
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", c.entry, (long long)c.workspace_floats);
+  // zero rows: the plain form still writes dparams (zeros, or nothing added)
+  if (c.rows == 0 && (c.form.row_list != kNo || c.form.saved != kNo)) return IMPNN_OK;
+  CHECK(!(c.row_index || c.saved) || (aligned16(c.h) && aligned16(c.agg) && aligned16(c.dout) && aligned16(c.dh) &&
+                                      aligned16(c.dagg) && aligned16(c.workspace) && (!c.saved || aligned16(c.saved))),
+        "the row-list and saving forms need 16-byte aligned tensors");
+  return launch_gated_update_bwd(c);
+}
+#undef CHECK
+
+int check_dropout(const char* entry, float rate, uint64_t seed, const int64_t* step, int32_t layer_word,
+                  DropoutArgs* d) {
+  if (!step) return fail(IMPNN_E_BADARG, "%s: null step pointer", entry);
+  if (!dropout_args(rate, seed, step, layer_word, d))
+    return fail(IMPNN_E_BADARG, "%s: dropout rate %g is not in [0, 1)", entry, (double)rate);
+  return IMPNN_OK;
+}
+
+// a *_dropout entry's tail, checked before everything else; rate 0 is the plain entry's call
+int add_dropout(GatedUpdateCall& c, float rate, uint64_t seed, const int64_t* step, int32_t layer_word) {
+  c.dropout = rate != 0.f;
+  return check_dropout(c.entry, rate, seed, step, layer_word, &c.drop);
+}
+
+GatedUpdateCall gu_forward(const char* entry, GatedUpdateForm form, const float* h, const float* agg, const float* Wz,
+                           const float* bz, const float* Wr, const float* br, const float* Wh, const float* bh,
+                           const float* gamma, const float* beta, float eps, float* out, const int32_t* row_index,
+                           const int32_t* n_rows, int64_t rows, int32_t D, float* saved, impnn_stream_t stream) {
+  GatedUpdateCall c{};
+  c.entry = entry, c.form = form, c.h = h, c.agg = agg, c.Wz = Wz, c.bz = bz, c.Wr = Wr, c.br = br, c.Wh = Wh;
+  c.bh = bh, c.gamma = gamma, c.beta = beta, c.eps = eps, c.out = out;
+  c.row_index = row_index, c.n_rows = n_rows, c.rows = rows, c.D = D, c.saved = saved, c.stream = as_stream(stream);
+  return c;
+}
+
+GatedUpdateCall gu_backward(const char* entry, GatedUpdateForm form, const float* h, const float* agg,
+                            const float* Wz, const float* bz, const float* Wr, const float* br, const float* Wh,
+                            const float* bh, const float* gamma, float eps, const float* dout, float* dh, float* dagg,
+                            float* dparams, float* workspace, int64_t workspace_floats, const int32_t* row_index,
+                            const int32_t* n_rows, int64_t rows, int32_t D, int32_t accumulate, float* saved,
+                            impnn_stream_t stream) {
+  GatedUpdateCall c{};
+  c.entry = entry, c.form = form, c.h = h, c.agg = agg, c.Wz = Wz, c.bz = bz, c.Wr = Wr, c.br = br, c.Wh = Wh;
+  c.bh = bh, c.gamma = gamma, c.eps = eps, c.dout = dout, c.dh = dh, c.dagg = dagg, c.dparams = dparams;
+  c.workspace = workspace, c.workspace_floats = workspace_floats, c.accumulate = accumulate != 0;
+  c.row_index = row_index, c.n_rows = n_rows, c.rows = rows, c.D = D, c.saved = saved, c.stream = as_stream(stream);
+  return c;
+}
+
+}  // namespace
+
 extern "C" {
 
 int impnn_abi_version(void) { return IMPNN_ABI_VERSION; }
@@ -118,30 +247,6 @@ int impnn_bmm_fused(const float* h, const float* bond_state, const int32_t* conn
   if (B == 0) return IMPNN_OK;
   REQUIRE(h && bond_state && conn && W && agg, "null pointer");
   return launch_bmm_message(h, bond_state, conn, W, nullptr, agg, B, N, E, D, K, as_stream(stream));
-}
-
-int impnn_gated_update(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                       const float* br, const float* Wh, const float* bh, const float* gamma,
-                       const float* beta, float ln_eps, float* out, int64_t rows, int32_t D,
-                       impnn_stream_t stream) {
-  REQUIRE(rows >= 0 && D > 0, "bad shape");
-  if (rows == 0) return IMPNN_OK;
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out, "null pointer");
-  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
-  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, rows, D,
-                             as_stream(stream));
-}
-
-int impnn_gated_update_rows(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                            const float* br, const float* Wh, const float* bh, const float* gamma,
-                            const float* beta, float ln_eps, float* out, const int32_t* row_index,
-                            const int32_t* n_rows, int64_t max_rows, int32_t D, impnn_stream_t stream) {
-  REQUIRE(max_rows >= 0 && D > 0, "bad shape");
-  if (max_rows == 0) return IMPNN_OK;
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out && row_index && n_rows, "null pointer");
-  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
-  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, max_rows, D, as_stream(stream),
-                             row_index, n_rows);
 }
 
 int impnn_kept_rows(const int32_t* atom_ids, const int32_t* bond_ids, const int32_t* conn, int32_t* rows_out,
@@ -600,40 +705,9 @@ int64_t impnn_gated_update_bwd_workspace_floats(int64_t rows, int32_t D) {
   return gated_update_bwd_workspace(rows, D);
 }
 
-int impnn_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                           const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
-                           const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                           int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate,
-                           impnn_stream_t stream) {
-  REQUIRE(rows >= 0 && D > 0 && D <= 256 && 256 % D == 0, "atom_dim must divide 256");
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace,
-          "null pointer");
-  if (workspace_floats < impnn_gated_update_bwd_workspace_floats(rows, D))
-    return fail(IMPNN_E_WORKSPACE, "gated_update_bwd: workspace of %lld floats is too small", (long long)workspace_floats);
-  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                 rows, D, accumulate != 0, as_stream(stream));
-}
-
 int64_t impnn_gated_update_rows_bwd_workspace_floats(int64_t max_rows, int32_t D) {
   if (max_rows < 0 || (D != 64 && D != 128)) return 0;
   return gated_update_bwd_workspace(max_rows, D, true);
-}
-
-int impnn_gated_update_rows_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                                const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
-                                const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                                int64_t workspace_floats, const int32_t* row_index, const int32_t* n_rows,
-                                int64_t max_rows, int32_t D, int32_t accumulate, impnn_stream_t stream) {
-  REQUIRE(max_rows >= 0, "bad shape");
-  if (D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd: atom_dim %d (the row-list form covers 64 and 128)", D);
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace &&
-          row_index && n_rows, "null pointer");
-  if (workspace_floats < impnn_gated_update_rows_bwd_workspace_floats(max_rows, D))
-    return fail(IMPNN_E_WORKSPACE, "gated_update_rows_bwd: workspace of %lld floats is too small", (long long)workspace_floats);
-  if (max_rows == 0) return IMPNN_OK;
-  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                 max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows);
 }
 
 int64_t impnn_gated_update_rows_saved_floats(int64_t max_rows, int32_t D) {
@@ -641,64 +715,37 @@ int64_t impnn_gated_update_rows_saved_floats(int64_t max_rows, int32_t D) {
   return max_rows * 4 * D;
 }
 
+int impnn_gated_update(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                       const float* br, const float* Wh, const float* bh, const float* gamma,
+                       const float* beta, float ln_eps, float* out, int64_t rows, int32_t D,
+                       impnn_stream_t stream) {
+  return gated_update_checked(gu_forward(__func__, kFwd, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, nullptr, nullptr, rows, D, nullptr, stream));
+}
+
+int impnn_gated_update_rows(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                            const float* br, const float* Wh, const float* bh, const float* gamma,
+                            const float* beta, float ln_eps, float* out, const int32_t* row_index,
+                            const int32_t* n_rows, int64_t max_rows, int32_t D, impnn_stream_t stream) {
+  return gated_update_checked(
+      gu_forward(__func__, kFwdRows, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows, max_rows, D, nullptr, stream));
+}
+
 int impnn_gated_update_rows_train(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
                                   const float* br, const float* Wh, const float* bh, const float* gamma,
                                   const float* beta, float ln_eps, float* out, const int32_t* row_index,
                                   const int32_t* n_rows, int64_t max_rows, int32_t D, float* saved,
                                   impnn_stream_t stream) {
-  REQUIRE(max_rows >= 0, "bad shape");
-  if (D != 32 && D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_train: atom_dim %d (the saving forward covers 32, 64 and 128)", D);
-  if (max_rows == 0) return IMPNN_OK;
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out && saved, "null pointer");
-  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
-  REQUIRE((reinterpret_cast<uintptr_t>(saved) & 15u) == 0, "saved must be 16-byte aligned");
-  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
-  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, max_rows, D, as_stream(stream),
-                             row_index, n_rows, saved);
+  return gated_update_checked(
+      gu_forward(__func__, kFwdTrain, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows, max_rows, D, saved, stream));
 }
-
-int impnn_gated_update_rows_bwd_saved(const float* h, const float* agg, const float* Wz, const float* bz,
-                                      const float* Wr, const float* br, const float* Wh, const float* bh,
-                                      const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
-                                      float* dparams, float* workspace, int64_t workspace_floats,
-                                      const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
-                                      int32_t accumulate, float* saved, impnn_stream_t stream) {
-  REQUIRE(max_rows >= 0, "bad shape");
-  if (D != 32 && D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim %d (covers 32, 64 and 128)", D);
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace && saved,
-          "null pointer");
-  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
-  if (D == 32 && row_index)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim 32 takes no row list");
-  if (workspace_floats < (D == 32 ? impnn_gated_update_bwd_workspace_floats(max_rows, D)
-                                  : impnn_gated_update_rows_bwd_workspace_floats(max_rows, D)))
-    return fail(IMPNN_E_WORKSPACE, "gated_update_rows_bwd_saved: workspace of %lld floats is too small",
-                (long long)workspace_floats);
-  if (max_rows == 0) return IMPNN_OK;
-  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                 max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows, saved);
-}
-
-#define DROPOUT_ARGS(d_)                                                                                    \
-  DropoutArgs d_;                                                                                           \
-  REQUIRE(step != nullptr, "null step pointer");                                                           \
-  if (!dropout_args(rate, seed, step, layer_word, &d_)) return fail(IMPNN_E_BADARG, "dropout rate %g is not in [0, 1)", \
-                                                                    (double)rate)
 
 int impnn_gated_update_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
                                const float* br, const float* Wh, const float* bh, const float* gamma,
                                const float* beta, float ln_eps, float* out, int64_t rows, int32_t D, float rate,
                                uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream) {
-  DROPOUT_ARGS(d);
-  if (rate == 0.f) return impnn_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, rows, D, stream);
-  REQUIRE(rows >= 0 && D > 0, "bad shape");
-  if (rows == 0) return IMPNN_OK;
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out, "null pointer");
-  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
-  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, rows, D, as_stream(stream),
-                             nullptr, nullptr, nullptr, &d);
+  GatedUpdateCall c = gu_forward(__func__, kFwd, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, nullptr, nullptr, rows, D, nullptr, stream);
+  if (int rc = add_dropout(c, rate, seed, step, layer_word)) return rc;
+  return gated_update_checked(c);
 }
 
 int impnn_gated_update_rows_train_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
@@ -707,26 +754,39 @@ int impnn_gated_update_rows_train_dropout(const float* h, const float* agg, cons
                                           const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
                                           float* saved, float rate, uint64_t seed, const int64_t* step,
                                           int32_t layer_word, impnn_stream_t stream) {
-  DROPOUT_ARGS(d);
-  if (rate == 0.f) {
-    if (saved)
-      return impnn_gated_update_rows_train(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows,
-                                           max_rows, D, saved, stream);
-    if (row_index)
-      return impnn_gated_update_rows(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows,
-                                     max_rows, D, stream);
-    return impnn_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, max_rows, D, stream);
-  }
-  REQUIRE(max_rows >= 0 && D > 0, "bad shape");
-  if (saved && D != 32 && D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_train: atom_dim %d (the saving forward covers 32, 64 and 128)", D);
-  if (max_rows == 0) return IMPNN_OK;
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && beta && out, "null pointer");
-  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
-  REQUIRE(!saved || (reinterpret_cast<uintptr_t>(saved) & 15u) == 0, "saved must be 16-byte aligned");
-  REQUIRE(ln_eps >= 0.f, "ln_eps must be >= 0");
-  return launch_gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, max_rows, D, as_stream(stream),
-                             row_index, n_rows, saved, &d);
+  // rate 0 is the plain entry these arguments name: the saving forward, the row list, or every row
+  const GatedUpdateForm form = rate != 0.f ? kFwdTrainDropout : saved ? kFwdTrain : row_index ? kFwdRows : kFwd;
+  GatedUpdateCall c = gu_forward(__func__, form, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, ln_eps, out, row_index, n_rows, max_rows, D, saved, stream);
+  if (int rc = add_dropout(c, rate, seed, step, layer_word)) return rc;
+  return gated_update_checked(c);
+}
+
+int impnn_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                           const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                           const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                           int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate,
+                           impnn_stream_t stream) {
+  return gated_update_bwd_checked(
+      gu_backward(__func__, kBwd, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace, workspace_floats, nullptr, nullptr, rows, D, accumulate, nullptr, stream));
+}
+
+int impnn_gated_update_rows_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
+                                const float* br, const float* Wh, const float* bh, const float* gamma, float ln_eps,
+                                const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
+                                int64_t workspace_floats, const int32_t* row_index, const int32_t* n_rows,
+                                int64_t max_rows, int32_t D, int32_t accumulate, impnn_stream_t stream) {
+  return gated_update_bwd_checked(
+      gu_backward(__func__, kBwdRows, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace, workspace_floats, row_index, n_rows, max_rows, D, accumulate, nullptr, stream));
+}
+
+int impnn_gated_update_rows_bwd_saved(const float* h, const float* agg, const float* Wz, const float* bz,
+                                      const float* Wr, const float* br, const float* Wh, const float* bh,
+                                      const float* gamma, float ln_eps, const float* dout, float* dh, float* dagg,
+                                      float* dparams, float* workspace, int64_t workspace_floats,
+                                      const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
+                                      int32_t accumulate, float* saved, impnn_stream_t stream) {
+  return gated_update_bwd_checked(
+      gu_backward(__func__, kBwdSaved, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace, workspace_floats, row_index, n_rows, max_rows, D, accumulate, saved, stream));
 }
 
 int impnn_gated_update_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
@@ -734,17 +794,9 @@ int impnn_gated_update_bwd_dropout(const float* h, const float* agg, const float
                                    const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
                                    int64_t workspace_floats, int64_t rows, int32_t D, int32_t accumulate, float rate,
                                    uint64_t seed, const int64_t* step, int32_t layer_word, impnn_stream_t stream) {
-  DROPOUT_ARGS(d);
-  if (rate == 0.f)
-    return impnn_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                  workspace_floats, rows, D, accumulate, stream);
-  REQUIRE(rows >= 0 && D > 0 && D <= 256 && 256 % D == 0, "atom_dim must divide 256");
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace,
-          "null pointer");
-  if (workspace_floats < impnn_gated_update_bwd_workspace_floats(rows, D))
-    return fail(IMPNN_E_WORKSPACE, "gated_update_bwd: workspace of %lld floats is too small", (long long)workspace_floats);
-  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                 rows, D, accumulate != 0, as_stream(stream), nullptr, nullptr, nullptr, &d);
+  GatedUpdateCall c = gu_backward(__func__, kBwd, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace, workspace_floats, nullptr, nullptr, rows, D, accumulate, nullptr, stream);
+  if (int rc = add_dropout(c, rate, seed, step, layer_word)) return rc;
+  return gated_update_bwd_checked(c);
 }
 
 int impnn_gated_update_rows_bwd_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
@@ -754,20 +806,10 @@ int impnn_gated_update_rows_bwd_dropout(const float* h, const float* agg, const 
                                         const int32_t* row_index, const int32_t* n_rows, int64_t max_rows, int32_t D,
                                         int32_t accumulate, float rate, uint64_t seed, const int64_t* step,
                                         int32_t layer_word, impnn_stream_t stream) {
-  DROPOUT_ARGS(d);
-  if (rate == 0.f)
-    return impnn_gated_update_rows_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                       workspace_floats, row_index, n_rows, max_rows, D, accumulate, stream);
-  REQUIRE(max_rows >= 0, "bad shape");
-  if (D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd: atom_dim %d (the row-list form covers 64 and 128)", D);
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace &&
-          row_index && n_rows, "null pointer");
-  if (workspace_floats < impnn_gated_update_rows_bwd_workspace_floats(max_rows, D))
-    return fail(IMPNN_E_WORKSPACE, "gated_update_rows_bwd: workspace of %lld floats is too small", (long long)workspace_floats);
-  if (max_rows == 0) return IMPNN_OK;
-  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                 max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows, nullptr, &d);
+  GatedUpdateCall c =
+      gu_backward(__func__, kBwdRows, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace, workspace_floats, row_index, n_rows, max_rows, D, accumulate, nullptr, stream);
+  if (int rc = add_dropout(c, rate, seed, step, layer_word)) return rc;
+  return gated_update_bwd_checked(c);
 }
 
 int impnn_gated_update_rows_bwd_saved_dropout(const float* h, const float* agg, const float* Wz, const float* bz,
@@ -777,26 +819,10 @@ int impnn_gated_update_rows_bwd_saved_dropout(const float* h, const float* agg, 
                                               const int32_t* row_index, const int32_t* n_rows, int64_t max_rows,
                                               int32_t D, int32_t accumulate, float* saved, float rate, uint64_t seed,
                                               const int64_t* step, int32_t layer_word, impnn_stream_t stream) {
-  DROPOUT_ARGS(d);
-  if (rate == 0.f)
-    return impnn_gated_update_rows_bwd_saved(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams,
-                                             workspace, workspace_floats, row_index, n_rows, max_rows, D, accumulate,
-                                             saved, stream);
-  REQUIRE(max_rows >= 0, "bad shape");
-  if (D != 32 && D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim %d (covers 32, 64 and 128)", D);
-  REQUIRE(h && agg && Wz && bz && Wr && br && Wh && bh && gamma && dout && dh && dagg && dparams && workspace && saved,
-          "null pointer");
-  REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
-  if (D == 32 && row_index)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim 32 takes no row list");
-  if (workspace_floats < (D == 32 ? impnn_gated_update_bwd_workspace_floats(max_rows, D)
-                                  : impnn_gated_update_rows_bwd_workspace_floats(max_rows, D)))
-    return fail(IMPNN_E_WORKSPACE, "gated_update_rows_bwd_saved: workspace of %lld floats is too small",
-                (long long)workspace_floats);
-  if (max_rows == 0) return IMPNN_OK;
-  return launch_gated_update_bwd(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace,
-                                 max_rows, D, accumulate != 0, as_stream(stream), row_index, n_rows, saved, &d);
+  GatedUpdateCall c =
+      gu_backward(__func__, kBwdSaved, h, agg, Wz, bz, Wr, br, Wh, bh, gamma, ln_eps, dout, dh, dagg, dparams, workspace, workspace_floats, row_index, n_rows, max_rows, D, accumulate, saved, stream);
+  if (int rc = add_dropout(c, rate, seed, step, layer_word)) return rc;
+  return gated_update_bwd_checked(c);
 }
 
 int impnn_dropout_step(int64_t* counter, int64_t* snapshot, impnn_stream_t stream) {
@@ -806,14 +832,14 @@ int impnn_dropout_step(int64_t* counter, int64_t* snapshot, impnn_stream_t strea
 
 int impnn_dropout_mask(uint64_t seed, const int64_t* step, int32_t layer_word, float rate, const int32_t* row_index,
                        const int32_t* n_rows, int64_t max_rows, int32_t D, float* out, impnn_stream_t stream) {
-  DROPOUT_ARGS(d);
+  DropoutArgs d;
+  if (int rc = check_dropout(__func__, rate, seed, step, layer_word, &d)) return rc;
   REQUIRE(max_rows >= 0 && D > 0, "bad shape");
   REQUIRE((row_index != nullptr) == (n_rows != nullptr), "row_index and n_rows: both or neither");
   if (max_rows == 0) return IMPNN_OK;
   REQUIRE(out, "null pointer");
   return launch_dropout_mask(d, row_index, n_rows, max_rows, D, out, as_stream(stream));
 }
-#undef DROPOUT_ARGS
 
 int impnn_adam_clipnorm_step(const void* var_table, const int64_t* sizes, int32_t n_vars, int64_t step, float lr,
                              float beta1, float beta2, float eps, float clipnorm, impnn_stream_t stream) {

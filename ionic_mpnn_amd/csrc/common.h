@@ -124,6 +124,42 @@ __device__ __forceinline__ void dropout_quad_words(const DropoutKey& k, int64_t 
   }
 }
 
+// ---- one GatedUpdate call (include/impnn.h, the GatedUpdate family).  api.hip fills it from the entry's arguments
+// and checks it once per direction; the launchers read it.  The form is what the entry takes and covers: whether it
+// has a row list and a `saved` buffer (a form without one leaves those pointers null), and its atom_dims.
+enum class GuArg : uint8_t { kAbsent, kOptional, kRequired };
+enum class GuDims : uint8_t { kAny, kDivide256, k32_64_128, k64_128 };
+struct GatedUpdateForm {
+  GuArg row_list, saved;
+  GuDims dims;
+};
+
+struct GatedUpdateCall {
+  const char* entry;  // the exported entry, named by the error text
+  GatedUpdateForm form;
+  const float *h, *agg, *Wz, *bz, *Wr, *br, *Wh, *bh, *gamma;
+  const float* beta;  // forward
+  float eps;
+  float* out;          // forward
+  const float* dout;   // backward: dout .. accumulate
+  float *dh, *dagg, *dparams, *workspace;
+  int64_t workspace_floats;
+  bool accumulate;
+  const int32_t *row_index, *n_rows;  // the row list (device), or both null
+  int64_t rows;                       // max_rows with a row list
+  int D;
+  float* saved;
+  bool dropout;  // rate > 0: `drop` holds the mask's arguments
+  DropoutArgs drop;
+  hipStream_t stream;
+};
+
+// f() or f(drop): the kernels' optional trailing dropout pack (Drop... = nothing, or one DropoutArgs)
+template <class F>
+int with_dropout_pack(const GatedUpdateCall& c, F&& f) {
+  return c.dropout ? f(c.drop) : f();
+}
+
 // ---- layer-at-a-time launches (layer_kernels.hip)
 int launch_embed_gather(const int32_t* ids, const float* table, float* out, int64_t rows, int vocab,
                         int dim, hipStream_t s);
@@ -136,11 +172,7 @@ int launch_bmm_message_typed(const float* h, const int32_t* bond_ids, const int3
                              hipStream_t s);
 int launch_reduce_scatter_add(const float* m, const int32_t* tgt, int tgt_stride, float* agg, int B,
                               int N, int E, int D, hipStream_t s, int accumulate = 0);
-int launch_gated_update(const float* h, const float* agg, const float* Wz, const float* bz,
-                        const float* Wr, const float* br, const float* Wh, const float* bh,
-                        const float* gamma, const float* beta, float eps, float* out, int64_t rows,
-                        int D, hipStream_t s, const int32_t* ridx = nullptr, const int32_t* nrows_dev = nullptr,
-                        float* save = nullptr, const DropoutArgs* drop = nullptr);
+int launch_gated_update(const GatedUpdateCall& c);  // a checked call (api.hip)
 int launch_kept_rows(const int32_t* atom_ids, const int32_t* bond_ids, const int32_t* conn, int32_t* rows_out, int B,
                      int N, int E, int Vb, hipStream_t s);
 int launch_row_index_fill(const int32_t* r, const int32_t* incl, int32_t* idx, int32_t* count, int B, int N,
@@ -188,12 +220,7 @@ int launch_bond_type_matrices_bwd(const float* tb, const float* W, const float* 
 int gated_update_bwd_blocks(int64_t rows, int D);
 int64_t gated_update_param_floats(int D);
 int64_t gated_update_bwd_workspace(int64_t rows, int D, bool row_list = false);
-int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                            const float* br, const float* Wh, const float* bh, const float* gamma, float eps,
-                            const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                            int64_t rows, int D, int accumulate, hipStream_t s, const int32_t* ridx = nullptr,
-                            const int32_t* nrows_dev = nullptr, float* saved = nullptr,
-                            const DropoutArgs* drop = nullptr);
+int launch_gated_update_bwd(const GatedUpdateCall& c);  // a checked call (api.hip)
 int launch_dropout_step(int64_t* counter, int64_t* snapshot, hipStream_t s);
 int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t* nrows_dev, int64_t max_rows, int D,
                         float* out, hipStream_t s);

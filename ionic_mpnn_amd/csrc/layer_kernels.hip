@@ -1567,20 +1567,17 @@ int launch_row_index_fill(const int32_t* r, const int32_t* incl, int32_t* idx, i
   return check_launch("row_index_fill");
 }
 
+// (api.hip has checked the call: a row list or a `saved` buffer comes with an atom_dim and alignment it covers)
 template <class... Drop>
-static int launch_gated_update_impl(const float* h, const float* agg, const float* Wz, const float* bz,
-                                    const float* Wr, const float* br, const float* Wh, const float* bh,
-                                    const float* gamma, const float* beta, float eps, float* out, int64_t rows, int D,
-                                    hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* save,
-                                    Drop... drop) {
-  if (save && !(D == 32 || D == 64 || D == 128))
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_train: atom_dim %d (the saving forward covers 32, 64 and 128)", D);
-  if (save && D == 32 && !(aligned16(h) && aligned16(agg) && aligned16(out) && aligned16(save)))
-    return fail(IMPNN_E_BADARG, "gated_update_rows_train: needs 16-byte aligned tensors");
-  if (ridx && !(D == 32 || (D % 64 == 0 && D <= 128)))
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update: a row list is supported for atom_dim 32, 64 and 128 only");
-  if (ridx && D == 32 && !(aligned16(h) && aligned16(agg) && aligned16(out)))
-    return fail(IMPNN_E_BADARG, "gated_update: row-list variant needs 16-byte aligned tensors");
+static int launch_gated_update_impl(const GatedUpdateCall& c, Drop... drop) {
+  const float *h = c.h, *agg = c.agg, *Wz = c.Wz, *bz = c.bz, *Wr = c.Wr, *br = c.br, *Wh = c.Wh, *bh = c.bh;
+  const float *gamma = c.gamma, *beta = c.beta;
+  const float eps = c.eps;
+  float *out = c.out, *save = c.saved;
+  const int32_t *ridx = c.row_index, *nrows_dev = c.n_rows;
+  const int64_t rows = c.rows;
+  const int D = c.D;
+  const hipStream_t s = c.stream;
   if (D == 32 && aligned16(h) && aligned16(agg) && aligned16(out)) {
     const int64_t tiles = (rows + 15) / 16;
     int64_t blocks = (tiles + 3) / 4;
@@ -1652,19 +1649,9 @@ static int launch_gated_update_impl(const float* h, const float* agg, const floa
   return check_launch("gated_update");
 }
 
-int launch_gated_update(const float* h, const float* agg, const float* Wz, const float* bz,
-                        const float* Wr, const float* br, const float* Wh, const float* bh,
-                        const float* gamma, const float* beta, float eps, float* out, int64_t rows,
-                        int D, hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* save,
-                        const DropoutArgs* drop) {
-  if (rows == 0) return IMPNN_OK;
-  if (drop) {  // the dropout instantiations: same shapes and dispatch, the mask on the final store
-    const DropoutArgs d = *drop;
-    return launch_gated_update_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, rows, D, s, ridx, nrows_dev,
-                                    save, d);
-  }
-  return launch_gated_update_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps, out, rows, D, s, ridx, nrows_dev,
-                                  save);
+int launch_gated_update(const GatedUpdateCall& c) {
+  // the dropout instantiations: same shapes and dispatch, the mask on the final store
+  return with_dropout_pack(c, [&](auto... drop) { return launch_gated_update_impl(c, drop...); });
 }
 
 int launch_global_sum_pool(const float* h, const int32_t* ids, float* out, int B, int N, int D,

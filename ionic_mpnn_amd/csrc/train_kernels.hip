@@ -2925,24 +2925,21 @@ int64_t gated_update_bwd_workspace(int64_t rows, int D, bool row_list) {
          (int64_t)3 * 2 * D * D + (row_list ? rows * 2 * D : 0);
 }
 
+// (api.hip has checked the call: atom_dim divides 256, and a row list or a `saved` buffer comes with an atom_dim and
+// alignment it covers)
 template <class... Drop>
-static int launch_gated_update_bwd_impl(const float* h, const float* agg, const float* Wz, const float* bz,
-                                        const float* Wr, const float* br, const float* Wh, const float* bh,
-                                        const float* gamma, float eps, const float* dout, float* dh, float* dagg,
-                                        float* dparams, float* workspace, int64_t rows, int D, int accumulate,
-                                        hipStream_t s, const int32_t* ridx, const int32_t* nrows_dev, float* saved,
-                                        Drop... drop) {
-  if (D > kBlock || kBlock % D != 0)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_bwd: atom_dim %d must divide %d", D, kBlock);
-  if (ridx && D != 64 && D != 128)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd: atom_dim %d (the row-list form covers 64 and 128)", D);
+static int launch_gated_update_bwd_impl(const GatedUpdateCall& c, Drop... drop) {
+  const float *h = c.h, *agg = c.agg, *Wz = c.Wz, *bz = c.bz, *Wr = c.Wr, *br = c.br, *Wh = c.Wh, *bh = c.bh;
+  const float *gamma = c.gamma, *dout = c.dout;
+  const float eps = c.eps;
+  float *dh = c.dh, *dagg = c.dagg, *dparams = c.dparams, *workspace = c.workspace, *saved = c.saved;
+  const int32_t *ridx = c.row_index, *nrows_dev = c.n_rows;
+  const int64_t rows = c.rows;
+  const int D = c.D, accumulate = c.accumulate;
+  const hipStream_t s = c.stream;
   const int R = kBlock / D;
   const int nblk = gu_main_blocks(rows, D), nchunk = gu_chunks(rows, D);
   int nsmall = nblk;  // slices of `small` the reduction reads
-  if (saved && !(D == 32 || D == 64 || D == 128))
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim %d (covers 32, 64 and 128)", D);
-  if (saved && D == 32 && ridx)
-    return fail(IMPNN_E_UNSUPPORTED, "gated_update_rows_bwd_saved: atom_dim 32 takes no row list");
   // saved (impnn_gated_update_rows_train's buffer, [z | r | tanh(t)] then r * h): used in place of the workspace's
   // first two regions and CONSUMED - it leaves holding the pre-activation gradients
   float* dpre = saved ? saved : workspace;
@@ -2958,7 +2955,6 @@ static int launch_gated_update_bwd_impl(const float* h, const float* agg, const 
   const bool al16 = ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(agg) | reinterpret_cast<uintptr_t>(dout) |
                       reinterpret_cast<uintptr_t>(dh) | reinterpret_cast<uintptr_t>(dagg) |
                       reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(dpre)) & 15u) == 0;
-  if ((ridx || saved) && !al16) return fail(IMPNN_E_BADARG, "gated_update_rows_bwd: tensors must be 16B aligned");
   if ((D == 64 || D == 128) && al16) {
     const size_t lw = sizeof(float) * ((size_t)64 * (2 * D + 4) + 64 * (D + 4) + 3 * 16 * 2 * D + 4 * 256) + 64 * sizeof(int32_t);
     const int tile_rows = gu_wide_tile_rows(rows);  // (as the forward kernel: 16-row tiles below ~8 K rows)
@@ -3043,18 +3039,9 @@ static int launch_gated_update_bwd_impl(const float* h, const float* agg, const 
   return check_launch("gated_update_reduce");
 }
 
-int launch_gated_update_bwd(const float* h, const float* agg, const float* Wz, const float* bz, const float* Wr,
-                            const float* br, const float* Wh, const float* bh, const float* gamma, float eps,
-                            const float* dout, float* dh, float* dagg, float* dparams, float* workspace,
-                            int64_t rows, int D, int accumulate, hipStream_t s, const int32_t* ridx,
-                            const int32_t* nrows_dev, float* saved, const DropoutArgs* drop) {
-  if (drop) {  // the dropout instantiations of the main kernel; the GEMMs and the reduction behind it are the same
-    const DropoutArgs d = *drop;
-    return launch_gated_update_bwd_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, dagg, dparams, workspace,
-                                        rows, D, accumulate, s, ridx, nrows_dev, saved, d);
-  }
-  return launch_gated_update_bwd_impl(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh, dagg, dparams, workspace,
-                                      rows, D, accumulate, s, ridx, nrows_dev, saved);
+int launch_gated_update_bwd(const GatedUpdateCall& c) {
+  // the dropout instantiations of the main kernel; the GEMMs and the reduction behind it are the same
+  return with_dropout_pack(c, [&](auto... drop) { return launch_gated_update_bwd_impl(c, drop...); });
 }
 
 // impnn_dropout_step: snapshot <- counter; counter += 1 (one thread; a captured step replays it)

@@ -354,36 +354,33 @@ def gated_update(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta, eps=LN_EPS, rows=N
     ts = [f32c(t) for t in (h, agg, Wz, bz, Wr, br, Wh, bh, gamma, beta)]
     out = torch.empty_like(ts[0])
     nrows = ts[0].numel() // D
+    if rows is not None and not save and dropout is None and D not in (32, 64, 128):
+        rows = None  # the plain forward has no row list at other widths: every row is computed
     with torch.cuda.device(h.device):
-        if dropout is not None:
-            lib = _lib.load()
-            saved = None
-            if save:
-                saved = torch.empty(int(lib.impnn_gated_update_rows_saved_floats(nrows, D)), dtype=torch.float32,
-                                    device=h.device)
-            if save or rows is not None:
-                ri, rn = (ptr(rows[0]), ptr(rows[1])) if rows is not None else (None, None)
-                check(lib.impnn_gated_update_rows_train_dropout(*[ptr(t) for t in ts], float(eps), ptr(out), ri, rn, nrows,
-                                                                D, ptr(saved) if saved is not None else None,
-                                                                *dropout.args(), stream_ptr()))
-            else:
-                check(lib.impnn_gated_update_dropout(*[ptr(t) for t in ts], float(eps), ptr(out), nrows, D,
-                                                     *dropout.args(), stream_ptr()))
-            return (out, saved) if save else out
+        lib = _lib.load()
+        saved = None
         if save:
-            lib = _lib.load()
             saved = torch.empty(int(lib.impnn_gated_update_rows_saved_floats(nrows, D)), dtype=torch.float32,
                                 device=h.device)
-            ri, rn = (ptr(rows[0]), ptr(rows[1])) if rows is not None else (None, None)
-            check(lib.impnn_gated_update_rows_train(*[ptr(t) for t in ts], float(eps), ptr(out), ri, rn, nrows, D,
-                                                    ptr(saved), stream_ptr()))
-            return out, saved
-        if rows is not None and D in (32, 64, 128):
-            check(_lib.load().impnn_gated_update_rows(*[ptr(t) for t in ts], float(eps), ptr(out), ptr(rows[0]),
-                                                      ptr(rows[1]), nrows, D, stream_ptr()))
-        else:
-            check(_lib.load().impnn_gated_update(*[ptr(t) for t in ts], float(eps), ptr(out), nrows, D, stream_ptr()))
-    return out
+        entry, tail = _gated_update_entry(lib, rows, saved, dropout, nrows, D)
+        check(entry(*[ptr(t) for t in ts], float(eps), ptr(out), *tail, stream_ptr()))
+    return (out, saved) if save else out
+
+
+def _gated_update_entry(lib, rows, saved, dropout, max_rows, D):
+    """(row list?, saved?, dropout?) -> the forward entry and its arguments between ``out`` and the stream.
+    ``dropout``: rate > 0; with it, a row list or a saved buffer takes impnn_gated_update_rows_train_dropout."""
+    ri, rn = (ptr(rows[0]), ptr(rows[1])) if rows is not None else (None, None)
+    sv = ptr(saved) if saved is not None else None
+    if dropout is not None:
+        if rows is None and saved is None:
+            return lib.impnn_gated_update_dropout, (max_rows, D, *dropout.args())
+        return lib.impnn_gated_update_rows_train_dropout, (ri, rn, max_rows, D, sv, *dropout.args())
+    if saved is not None:
+        return lib.impnn_gated_update_rows_train, (ri, rn, max_rows, D, sv)
+    if rows is not None:
+        return lib.impnn_gated_update_rows, (ri, rn, max_rows, D)
+    return lib.impnn_gated_update, (max_rows, D)
 
 
 def global_sum_pool(h, atom_ids):

@@ -167,3 +167,191 @@ def test_row_list_backward_reports_its_coverage():
     assert rc == -2 and b"row-list" in lib.impnn_last_error_string()
     rc = lib.impnn_gated_update_rows_bwd(*([null] * 9), 1e-3, *([null] * 5), 0, null, null, 1000, 128, 0, null)
     assert rc == -1  # null pointers
+
+
+# ---- the GatedUpdate family's argument rules, pinned entry by entry.  Every row is refused, or is a zero-row no-op,
+# before anything is launched: the pointers are stand-ins that are never dereferenced.
+_A = 0x100000  # a 16-byte aligned stand-in
+_M = 0x100004  # a misaligned one
+_GU_FWD = ["h", "agg", "Wz", "bz", "Wr", "br", "Wh", "bh", "gamma", "beta", "eps", "out"]
+_GU_BWD = ["h", "agg", "Wz", "bz", "Wr", "br", "Wh", "bh", "gamma", "eps", "dout", "dh", "dagg", "dparams", "workspace",
+           "workspace_floats"]
+_ROWS = ["row_index", "n_rows"]
+_DROP = ["rate", "seed", "step", "layer_word"]
+_GU_PARAMS = {
+    "impnn_gated_update": _GU_FWD + ["rows", "D"],
+    "impnn_gated_update_rows": _GU_FWD + _ROWS + ["rows", "D"],
+    "impnn_gated_update_rows_train": _GU_FWD + _ROWS + ["rows", "D", "saved"],
+    "impnn_gated_update_dropout": _GU_FWD + ["rows", "D"] + _DROP,
+    "impnn_gated_update_rows_train_dropout": _GU_FWD + _ROWS + ["rows", "D", "saved"] + _DROP,
+    "impnn_gated_update_bwd": _GU_BWD + ["rows", "D", "accumulate"],
+    "impnn_gated_update_rows_bwd": _GU_BWD + _ROWS + ["rows", "D", "accumulate"],
+    "impnn_gated_update_rows_bwd_saved": _GU_BWD + _ROWS + ["rows", "D", "accumulate", "saved"],
+    "impnn_gated_update_bwd_dropout": _GU_BWD + ["rows", "D", "accumulate"] + _DROP,
+    "impnn_gated_update_rows_bwd_dropout": _GU_BWD + _ROWS + ["rows", "D", "accumulate"] + _DROP,
+    "impnn_gated_update_rows_bwd_saved_dropout": _GU_BWD + _ROWS + ["rows", "D", "accumulate", "saved"] + _DROP,
+}
+_NULLS = {k: None for k in ("h", "agg", "Wz", "bz", "Wr", "br", "Wh", "bh", "gamma", "beta", "out", "dout", "dh", "dagg",
+                            "dparams", "workspace")}
+_BAD, _UNS, _WS = -1, -2, -4
+_WS_PLAIN, _WS_ROWS = "impnn_gated_update_bwd_workspace_floats", "impnn_gated_update_rows_bwd_workspace_floats"
+# (entry, arguments that differ from the defaults, expected status, substring of the error text or None)
+_GU_CASES = [
+    # null tensors; zero rows return before the null check in the forwards and the list / saving backwards only
+    ("impnn_gated_update", dict(_NULLS), _BAD, b"null"),
+    ("impnn_gated_update", dict(_NULLS, rows=0), 0, None),
+    ("impnn_gated_update", dict(out=None), _BAD, b"null"),
+    ("impnn_gated_update_rows", dict(gamma=None), _BAD, b"null"),
+    ("impnn_gated_update_rows", dict(_NULLS, rows=0), 0, None),
+    ("impnn_gated_update_rows_train", dict(saved=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_train", dict(_NULLS, saved=None, rows=0), 0, None),
+    ("impnn_gated_update_dropout", dict(beta=None), _BAD, b"null"),
+    ("impnn_gated_update_dropout", dict(_NULLS, rows=0), 0, None),
+    ("impnn_gated_update_dropout", dict(_NULLS, rows=0, rate=0.0), 0, None),
+    ("impnn_gated_update_rows_train_dropout", dict(h=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_train_dropout", dict(h=None, rate=0.0), _BAD, b"null"),
+    ("impnn_gated_update_rows_train_dropout", dict(h=None, saved=None, rate=0.0), _BAD, b"null"),
+    ("impnn_gated_update_rows_train_dropout", dict(_NULLS, rows=0), 0, None),
+    ("impnn_gated_update_bwd", dict(dparams=None), _BAD, b"null"),
+    ("impnn_gated_update_bwd", dict(_NULLS, rows=0), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd", dict(workspace=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd", dict(rows=0), 0, None),
+    ("impnn_gated_update_rows_bwd", dict(_NULLS, rows=0), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd_saved", dict(saved=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd_saved", dict(rows=0), 0, None),
+    ("impnn_gated_update_rows_bwd_saved", dict(rows=0, D=32, row_index=None, n_rows=None), 0, None),
+    ("impnn_gated_update_bwd_dropout", dict(dh=None), _BAD, b"null"),
+    ("impnn_gated_update_bwd_dropout", dict(_NULLS, rows=0), _BAD, b"null"),
+    ("impnn_gated_update_bwd_dropout", dict(_NULLS, rows=0, rate=0.0), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd_dropout", dict(dagg=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd_dropout", dict(rows=0), 0, None),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(dout=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(rows=0), 0, None),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(rows=0, rate=0.0), 0, None),
+    # a row list needs both row_index and n_rows
+    ("impnn_gated_update_rows", dict(n_rows=None), _BAD, b"null"),
+    ("impnn_gated_update_rows", dict(row_index=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_train", dict(n_rows=None), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_train", dict(row_index=None), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_train_dropout", dict(n_rows=None), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_train_dropout", dict(row_index=None, saved=None), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_train_dropout", dict(n_rows=None, saved=None, rate=0.0), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd", dict(n_rows=None), _BAD, b"null"),
+    ("impnn_gated_update_rows_bwd_saved", dict(row_index=None), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(n_rows=None), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(n_rows=None, rate=0.0), _BAD, b"both or neither"),
+    ("impnn_gated_update_rows_bwd_dropout", dict(row_index=None), _BAD, b"null"),
+    # atom_dim coverage per form
+    ("impnn_gated_update", dict(D=0), _BAD, None),
+    ("impnn_gated_update", dict(D=512), _UNS, None),
+    ("impnn_gated_update_rows", dict(D=48), _UNS, None),
+    ("impnn_gated_update_rows", dict(D=0), _BAD, None),
+    ("impnn_gated_update_rows_train", dict(D=256), _UNS, None),
+    ("impnn_gated_update_rows_train", dict(D=0), _UNS, None),
+    ("impnn_gated_update_rows_train", dict(D=48, saved=None), _UNS, None),
+    ("impnn_gated_update_rows_train", dict(D=48, rows=0), _UNS, None),
+    ("impnn_gated_update_dropout", dict(D=0), _BAD, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=256), _UNS, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=256, rows=0), _UNS, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=0), _BAD, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=48, saved=None), _UNS, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=48, saved=None, rows=0), 0, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=256, rate=0.0), _UNS, None),
+    ("impnn_gated_update_rows_train_dropout", dict(D=48, saved=None, rate=0.0), _UNS, None),
+    ("impnn_gated_update_bwd", dict(D=48), _BAD, None),
+    ("impnn_gated_update_bwd", dict(D=512), _BAD, None),
+    ("impnn_gated_update_rows_bwd", dict(D=48), _UNS, b"row-list"),
+    ("impnn_gated_update_rows_bwd", dict(D=32, rows=0), _UNS, b"row-list"),
+    ("impnn_gated_update_rows_bwd", dict(_NULLS, D=256), _UNS, b"row-list"),
+    ("impnn_gated_update_rows_bwd_saved", dict(D=256), _UNS, None),
+    ("impnn_gated_update_rows_bwd_saved", dict(_NULLS, D=48), _UNS, None),
+    ("impnn_gated_update_rows_bwd_saved", dict(D=32), _UNS, b"row list"),
+    ("impnn_gated_update_rows_bwd_saved", dict(D=32, rows=0), _UNS, b"row list"),
+    ("impnn_gated_update_bwd_dropout", dict(D=96), _BAD, None),
+    ("impnn_gated_update_rows_bwd_dropout", dict(D=48), _UNS, b"row-list"),
+    ("impnn_gated_update_rows_bwd_dropout", dict(D=48, rate=0.0), _UNS, b"row-list"),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(D=256), _UNS, None),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(D=32), _UNS, b"row list"),
+    # 16-byte alignment of the row-list and saving forms
+    ("impnn_gated_update_rows", dict(D=32, h=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_train", dict(saved=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_train", dict(D=32, out=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_train", dict(D=32, agg=_M, row_index=None, n_rows=None), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_train_dropout", dict(saved=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_train_dropout", dict(D=32, h=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_train_dropout", dict(D=32, h=_M, saved=None), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd", dict(h=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd", dict(workspace=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd_saved", dict(saved=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd_saved", dict(D=32, dout=_M, row_index=None, n_rows=None), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd_saved", dict(dh=_M, row_index=None, n_rows=None), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd_dropout", dict(dagg=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(saved=_M), _BAD, b"aligned"),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(saved=_M, rate=0.0), _BAD, b"aligned"),
+    # workspace one float too small (the saving backward takes the row-list size at 64 / 128, list or not)
+    ("impnn_gated_update_bwd", dict(workspace_floats=(_WS_PLAIN, -1)), _WS, b"workspace"),
+    ("impnn_gated_update_rows_bwd", dict(workspace_floats=(_WS_ROWS, -1)), _WS, b"workspace"),
+    ("impnn_gated_update_rows_bwd", dict(workspace_floats=(_WS_ROWS, -1), rows=0), _WS, b"workspace"),
+    ("impnn_gated_update_rows_bwd_saved", dict(workspace_floats=(_WS_ROWS, -1)), _WS, b"workspace"),
+    ("impnn_gated_update_rows_bwd_saved", dict(workspace_floats=(_WS_ROWS, -1), row_index=None, n_rows=None), _WS, None),
+    ("impnn_gated_update_rows_bwd_saved", dict(workspace_floats=(_WS_PLAIN, 0), D=128, row_index=None, n_rows=None),
+     _WS, None),
+    ("impnn_gated_update_rows_bwd_saved", dict(workspace_floats=(_WS_PLAIN, -1), D=32, row_index=None, n_rows=None),
+     _WS, None),
+    ("impnn_gated_update_bwd_dropout", dict(workspace_floats=(_WS_PLAIN, -1)), _WS, None),
+    ("impnn_gated_update_bwd_dropout", dict(workspace_floats=(_WS_PLAIN, -1), rate=0.0), _WS, None),
+    ("impnn_gated_update_rows_bwd_dropout", dict(workspace_floats=(_WS_ROWS, -1)), _WS, None),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(workspace_floats=(_WS_ROWS, -1)), _WS, None),
+    # rows < 0
+    ("impnn_gated_update", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_rows", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_rows_train", dict(rows=-1, D=48), _BAD, None),
+    ("impnn_gated_update_dropout", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_rows_train_dropout", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_bwd", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_rows_bwd", dict(rows=-1, D=48), _BAD, None),
+    ("impnn_gated_update_rows_bwd_saved", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_bwd_dropout", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_rows_bwd_dropout", dict(rows=-1), _BAD, None),
+    ("impnn_gated_update_rows_bwd_saved_dropout", dict(rows=-1), _BAD, None),
+    # eps < 0 (the forwards check it; the backwards do not)
+    ("impnn_gated_update", dict(eps=-1.0), _BAD, b"ln_eps"),
+    ("impnn_gated_update_rows", dict(eps=-1.0), _BAD, b"ln_eps"),
+    ("impnn_gated_update_rows_train", dict(eps=-1.0), _BAD, b"ln_eps"),
+    ("impnn_gated_update_dropout", dict(eps=-1.0), _BAD, b"ln_eps"),
+    ("impnn_gated_update_rows_train_dropout", dict(eps=-1.0), _BAD, b"ln_eps"),
+    ("impnn_gated_update_rows_train_dropout", dict(eps=-1.0, rate=0.0, saved=None, row_index=None), _BAD, b"ln_eps"),
+] + [
+    # the dropout tail: a null step, then the rate, come before everything else
+    (entry, dict(_NULLS, rows=-1, **kw), _BAD, what)
+    for entry in [e for e in _GU_PARAMS if e.endswith("_dropout")]
+    for kw, what in ((dict(step=None), b"step"), (dict(rate=-0.1), b"rate"), (dict(rate=1.0), b"rate"),
+                     (dict(rate=float("nan")), b"rate"), (dict(step=None, rate=0.0), b"step"))
+]
+
+
+def _gu_args(lib, entry, kw):
+    args = dict(eps=1e-3, rows=1000, D=64, accumulate=0, rate=0.5, seed=7, layer_word=3, step=_A,
+                workspace_floats=1 << 40)
+    args.update(kw)
+    q = args["workspace_floats"]
+    if isinstance(q, tuple):  # (size query, offset)
+        args["workspace_floats"] = getattr(lib, q[0])(max(args["rows"], 0), args["D"]) + q[1]
+    names = _GU_PARAMS[entry]
+    return [args.get(n, _A) for n in names] + [None]
+
+
+def test_gated_update_status_codes_are_pinned():
+    """The status code of every GatedUpdate entry for each class of refusal (recorded on the entries as they were
+    before their checks were shared).  Nothing here reaches a launch."""
+    lib = _lib.load()
+    assert set(_GU_PARAMS) == {n for n in _lib.SIGNATURES if n.startswith("impnn_gated_update") and
+                               not n.endswith("_floats")}
+    assert {c[0] for c in _GU_CASES} == set(_GU_PARAMS)
+    for entry, kw, want, what in _GU_CASES:
+        fn = getattr(lib, entry)
+        args = _gu_args(lib, entry, kw)
+        assert len(args) == len(fn.argtypes), entry
+        assert fn(*args) == want, (entry, kw)
+        if what is not None:
+            assert what in lib.impnn_last_error_string(), (entry, kw)
