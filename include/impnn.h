@@ -411,6 +411,52 @@ int impnn_batch_assemble(int32_t n_ions, const int32_t* sample_idx, int32_t B, i
                          int32_t* const* atom_ids, int32_t* const* bond_ids, int32_t* const* conn,
                          const float* t_flat, float* t_out, impnn_stream_t stream);
 
+/* ---- the transfer head (train_melting_point_transfer.py:95-103): everything behind GlobalSumPool of the transfer model,
+ *        pooled_cat, pooled_an -> fp Dense relu (per ion) -> proj Dense relu (per ion) -> add
+ *          -> Dense 256 relu -> BatchNormalization -> Dense 128 relu -> Dropout -> Dense 64 relu -> Dense 1
+ *      `weights` / `dweights`: HOST arrays of 18 device pointers (keras shapes, kernels (in,out)):
+ *        Wfp_cat bfp_cat Wfp_an bfp_an Wp_cat bp_cat Wp_an bp_an W1 b1 gamma beta W2 b2 W3 b3 Wo bo
+ *      moving_mean / moving_var (256): BatchNormalization's moving statistics.  D <= 128, F, Mx <= 64, any B >= 1.
+ *      impnn_transfer_head: inference (moving statistics, no dropout), one launch, out (B,1).
+ *      impnn_transfer_head_loss: loss = mean_b L(pred_b - y_b) + sum_t l2[t] * sum(W_t^2), L = e^2 (loss_kind 0) or
+ *      Huber(delta) (loss_kind 1: e^2 / 2 for |e| <= delta, else delta (|e| - delta / 2)); `l2` a HOST array of 18
+ *      lambdas.  bn_batch != 0 (a training pass of a trainable BatchNormalization): normalises with the batch mean and
+ *      the biased batch variance and moves the moving statistics, moving -= (moving - batch) * (1 - bn_momentum), in
+ *      device memory; three launches (the statistics sit between the two halves).  bn_batch == 0: the moving
+ *      statistics, one launch.  rate > 0: Dropout behind the 128-wide Dense with the Philox mask of the
+ *      GatedUpdate *_dropout entries on (row = sample, column = unit); rate == 0 ignores seed / step / layer_word.
+ *      `saved` (impnn_transfer_head_saved_floats, may be null when bn_batch == 0): what the backward reads.
+ *      `workspace`: impnn_transfer_head_loss_workspace_floats(B) floats, the first 4 bytes ZERO before the first call
+ *      (every call leaves them zero).  `pred` (B) may be null.  All sums run in a fixed order: the same inputs give the
+ *      same bits.
+ *      impnn_transfer_head_loss_bwd: the same arguments as the forward of the pass plus `dloss` (device scalar);
+ *      ADDS the parameter gradients to dweights[t] where that pointer is not null (a null entry is a frozen tensor:
+ *      nothing is computed for it), 2 l2[t] W_t dloss included, and writes dpooled_cat / dpooled_an (B,D) unless both
+ *      are null (a frozen encoder).  `workspace`: impnn_transfer_head_bwd_workspace_floats floats.  Three launches, four
+ *      with bn_batch.
+ *      Status codes: dropout first (rate > 0: step != NULL and rate < 1, IMPNN_E_BADARG), then shape, loss_kind and
+ *      null pointers (IMPNN_E_BADARG), then the buffer sizes (IMPNN_E_WORKSPACE), then the widths
+ *      (IMPNN_E_UNSUPPORTED). */
+int64_t impnn_transfer_head_saved_floats(int32_t B, int32_t F, int32_t Mx);
+int64_t impnn_transfer_head_bwd_workspace_floats(int32_t B, int32_t F, int32_t Mx);
+int64_t impnn_transfer_head_loss_workspace_floats(int32_t B);
+int impnn_transfer_head(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                        const float* moving_mean, const float* moving_var, float bn_eps, float* out, int32_t B,
+                        int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_head_loss(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                             const float* l2, float* moving_mean, float* moving_var, float bn_momentum, float bn_eps,
+                             int32_t bn_batch, const float* y, int32_t loss_kind, float delta, float rate,
+                             uint64_t seed, const int64_t* step, int32_t layer_word, float* saved,
+                             int64_t saved_floats, float* pred, float* loss, float* workspace,
+                             int64_t workspace_floats, int32_t B, int32_t D, int32_t F, int32_t Mx,
+                             impnn_stream_t stream);
+int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                                 float* const* dweights, const float* l2, int32_t bn_batch, const float* y,
+                                 int32_t loss_kind, float delta, const float* dloss, float rate, uint64_t seed,
+                                 const int64_t* step, int32_t layer_word, const float* saved, int64_t saved_floats,
+                                 float* workspace, int64_t workspace_floats, float* dpooled_cat, float* dpooled_an,
+                                 int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

@@ -64,6 +64,14 @@ SIGNATURES = {
     "impnn_model_head_loss": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "impnn_model_head_loss_bwd": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, PP, i32, i32, i32, i32,
                                             vp]),
+    "impnn_transfer_head_saved_floats": (i64, [i32, i32, i32]),
+    "impnn_transfer_head_bwd_workspace_floats": (i64, [i32, i32, i32]),
+    "impnn_transfer_head_loss_workspace_floats": (i64, [i32]),
+    "impnn_transfer_head": (C.c_int, [vp, vp, PP, vp, vp, f32, vp, i32, i32, i32, i32, vp]),
+    "impnn_transfer_head_loss": (C.c_int, [vp, vp, PP, C.POINTER(f32), vp, vp, f32, f32, i32, vp, i32, f32] + _DROP
+                                 + [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "impnn_transfer_head_loss_bwd": (C.c_int, [vp, vp, PP, PP, C.POINTER(f32), i32, vp, i32, f32, vp] + _DROP
+                                     + [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

@@ -111,9 +111,12 @@ class BondTypeMatricesAll(torch.autograd.Function):
                  for d in dmats[:-1]]
         sinks = [_sink(W) for W in Ws]
         st = _sink(bond_table)
-        use_sinks = st is not None and all(sk is not None for sk in sinks)
+        # a frozen bond embedding (no gradient asked for): the kernel's table gradient goes to a scratch buffer and
+        # the layers' dW still go straight into their sinks
+        frozen_table = not ctx.needs_input_grad[0]
+        use_sinks = (st is not None or frozen_table) and all(sk is not None for sk in sinks)
         dWs = sinks if use_sinks else [torch.empty_like(W) for W in Ws]
-        dtb = st if use_sinks else torch.empty_like(bond_table)
+        dtb = st if use_sinks and st is not None else torch.empty_like(bond_table)
         n = len(Ws)
         wt = (C.c_void_p * n)(*[W.data_ptr() for W in Ws])
         dt = (C.c_void_p * n)(*[d.data_ptr() for d in dmats])
@@ -125,7 +128,7 @@ class BondTypeMatricesAll(torch.autograd.Function):
                   n, Vb, K, D, 1 if use_sinks else 0, ptr(ws), wsn)
         if use_sinks:
             return (None,) * (n + 1)
-        return (dtb, *dWs)
+        return (None if frozen_table else dtb, *dWs)
 
 
 def _message_adjoint(entry, graph, h, bond_ids, conn, mats, grad, dh, dmats, scratch=None):
@@ -345,6 +348,9 @@ class MessagePassingStep(torch.autograd.Function):
                                                     ctx.dropout)
         del kept
         B, N, D = h.shape
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]):
+            # the lowest trained step with a frozen message layer: neither h nor the type matrices take a gradient
+            return (None, None, None, None, *dparams) + (None,) * 6
         dmats = ctx.dmats if ctx.dmats is not None else torch.zeros_like(mats)
         scratch = None
         # (atom_dim 32: measured slower that way - 1.71 -> 1.88 ms per step at batch 4096 - the rows are a quarter as
@@ -462,3 +468,62 @@ class ModelHeadLoss(torch.autograd.Function):
                   ptr(T) if T is not None else None, wt, lam, ptr(y), ptr(dloss), ptr(dpc), ptr(dpa), gt, B, D, F, Mx)
         return (None, None, None, None, None, dpc, dpa, None, None) + tuple(
             None if s is not None else g for s, g in zip(sinks, grads))
+
+
+
+class TransferHeadLoss(torch.autograd.Function):
+    """The transfer model's head + Huber / squared error + l2 penalties as one node -> the scalar loss
+    (impnn_transfer_head_loss[_bwd]).  ``cfg``: MPNNModel._transfer_cfg (widths, l2, the moving statistics, which
+    the forward moves in place when cfg["bn_batch"], the pass's ops.Dropout or None, the loss); ``workspace``: a
+    persistent float tensor whose first word is zero.  The backward adds the gradients of the tensors that ask for one
+    into their sinks and leaves the frozen ones alone; it writes the pooled vectors' gradients only when they ask."""
+
+    @staticmethod
+    def forward(ctx, cfg, workspace, pooled_cat, pooled_an, y, *weights):
+        pooled_cat, pooled_an, y = f32c(pooled_cat), f32c(pooled_an), f32c(y).reshape(-1)
+        weights = tuple(f32c(w) for w in weights)
+        B, D = pooled_cat.shape
+        if y.numel() != B:
+            raise ValueError("y must hold one value per sample")
+        lib = _lib.load()
+        F, Mx = cfg["fp_size"], cfg["mixing_size"]
+        keep = any(ctx.needs_input_grad) or cfg["bn_batch"]
+        n_saved = int(lib.impnn_transfer_head_saved_floats(B, F, Mx)) if keep else 0
+        saved = torch.empty(n_saved, dtype=torch.float32, device=pooled_cat.device) if keep else None
+        loss = torch.empty((), dtype=torch.float32, device=pooled_cat.device)
+        lam = (C.c_float * len(weights))(*[float(v) for v in cfg["l2"]])
+        table = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
+        drop = cfg["dropout"]
+        dargs = drop.args() if drop is not None and drop.rate > 0.0 else (0.0, C.c_uint64(0), None, 0)
+        _lib_call(pooled_cat.device, lib.impnn_transfer_head_loss, ptr(pooled_cat), ptr(pooled_an), table, lam,
+                  ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]), cfg["momentum"], cfg["epsilon"],
+                  1 if cfg["bn_batch"] else 0, ptr(y), cfg["loss_kind"], cfg["delta"], *dargs,
+                  ptr(saved) if keep else None, n_saved, None, ptr(loss), ptr(workspace), workspace.numel(), B, D, F, Mx)
+        ctx.save_for_backward(pooled_cat, pooled_an, y, *weights)
+        ctx.meta = (cfg, saved, dargs, weights)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        cfg, saved, dargs, params = ctx.meta
+        pooled_cat, pooled_an, y, *weights = ctx.saved_tensors
+        B, D = pooled_cat.shape
+        F, Mx = cfg["fp_size"], cfg["mixing_size"]
+        dloss = f32c(dloss).reshape(1)
+        lib = _lib.load()
+        wants = ctx.needs_input_grad[5:]
+        sinks = [_sink(p) if w else None for p, w in zip(params, wants)]
+        grads = [None if not w else (s if s is not None else torch.zeros_like(t))
+                 for w, s, t in zip(wants, sinks, weights)]
+        pooled = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        dpc = torch.empty_like(pooled_cat) if pooled else None
+        dpa = torch.empty_like(pooled_an) if pooled else None
+        wsn = int(lib.impnn_transfer_head_bwd_workspace_floats(B, F, Mx))
+        ws = torch.empty(wsn, dtype=torch.float32, device=dloss.device)
+        lam = (C.c_float * len(weights))(*[float(v) for v in cfg["l2"]])
+        wt = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
+        gt = (C.c_void_p * len(weights))(*[g.data_ptr() if g is not None else None for g in grads])
+        _lib_call(dloss.device, lib.impnn_transfer_head_loss_bwd, ptr(pooled_cat), ptr(pooled_an), wt, gt, lam,
+                  1 if cfg["bn_batch"] else 0, ptr(y), cfg["loss_kind"], cfg["delta"], ptr(dloss), *dargs, ptr(saved),
+                  saved.numel(), ptr(ws), wsn, ptr(dpc) if pooled else None, ptr(dpa) if pooled else None, B, D, F, Mx)
+        return (None, None, dpc, dpa, None) + tuple(None if s is not None else g for s, g in zip(sinks, grads))

@@ -506,6 +506,86 @@ int impnn_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float
                                dweights, B, D, F, Mx, as_stream(stream), l2, y, dloss);
 }
 
+// ---- the transfer head (include/impnn.h; transfer_head.hip)
+int64_t impnn_transfer_head_saved_floats(int32_t B, int32_t F, int32_t Mx) {
+  return B > 0 && F > 0 && Mx > 0 ? transfer_head_saved_floats(B, F, Mx) : -1;
+}
+int64_t impnn_transfer_head_bwd_workspace_floats(int32_t B, int32_t F, int32_t Mx) {
+  return B > 0 && F > 0 && Mx > 0 ? transfer_head_bwd_workspace_floats(B, F, Mx) : -1;
+}
+int64_t impnn_transfer_head_loss_workspace_floats(int32_t B) {
+  return B > 0 ? transfer_head_loss_workspace_floats(B) : 4;
+}
+
+int impnn_transfer_head(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                        const float* moving_mean, const float* moving_var, float bn_eps, float* out, int32_t B,
+                        int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  REQUIRE(B >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE(bn_eps >= 0.f, "bn_eps must not be negative");
+  if (B == 0) return IMPNN_OK;
+  REQUIRE(pooled_cat && pooled_an && weights && moving_mean && moving_var && out, "null pointer");
+  TransferHeadCall c{};
+  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.bn_eps = bn_eps, c.out = out;
+  c.moving_mean = const_cast<float*>(moving_mean), c.moving_var = const_cast<float*>(moving_var);  // read only here
+  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
+  return launch_transfer_head(c);
+}
+
+int impnn_transfer_head_loss(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                             const float* l2, float* moving_mean, float* moving_var, float bn_momentum, float bn_eps,
+                             int32_t bn_batch, const float* y, int32_t loss_kind, float delta, float rate,
+                             uint64_t seed, const int64_t* step, int32_t layer_word, float* saved,
+                             int64_t saved_floats, float* pred, float* loss, float* workspace,
+                             int64_t workspace_floats, int32_t B, int32_t D, int32_t F, int32_t Mx,
+                             impnn_stream_t stream) {
+  TransferHeadCall c{};
+  c.dropout = rate != 0.f;
+  if (c.dropout) {
+    if (int rc = check_dropout(__func__, rate, seed, step, layer_word, &c.drop)) return rc;
+  }
+  REQUIRE(B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE(loss_kind == 0 || (loss_kind == 1 && delta > 0.f), "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
+  REQUIRE(bn_eps >= 0.f && bn_momentum >= 0.f && bn_momentum <= 1.f, "bn_eps >= 0 and 0 <= bn_momentum <= 1 required");
+  REQUIRE(pooled_cat && pooled_an && weights && l2 && moving_mean && moving_var && y && loss && workspace,
+          "null pointer");
+  REQUIRE(saved || !bn_batch, "the batch statistics need the saved buffer");
+  if (saved && saved_floats < transfer_head_saved_floats(B, F, Mx))
+    return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", __func__, (long long)saved_floats);
+  if (workspace_floats < impnn_transfer_head_loss_workspace_floats(B))
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", __func__, (long long)workspace_floats);
+  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.l2 = l2, c.moving_mean = moving_mean;
+  c.moving_var = moving_var, c.bn_momentum = bn_momentum, c.bn_eps = bn_eps, c.bn_batch = bn_batch != 0, c.y = y;
+  c.loss_kind = loss_kind, c.delta = delta, c.saved = saved, c.out = pred, c.loss = loss, c.workspace = workspace;
+  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
+  return launch_transfer_head(c);
+}
+
+int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                                 float* const* dweights, const float* l2, int32_t bn_batch, const float* y,
+                                 int32_t loss_kind, float delta, const float* dloss, float rate, uint64_t seed,
+                                 const int64_t* step, int32_t layer_word, const float* saved, int64_t saved_floats,
+                                 float* workspace, int64_t workspace_floats, float* dpooled_cat, float* dpooled_an,
+                                 int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  TransferHeadCall c{};
+  c.dropout = rate != 0.f;
+  if (c.dropout) {
+    if (int rc = check_dropout(__func__, rate, seed, step, layer_word, &c.drop)) return rc;
+  }
+  REQUIRE(B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE(loss_kind == 0 || (loss_kind == 1 && delta > 0.f), "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
+  REQUIRE(pooled_cat && pooled_an && weights && dweights && l2 && y && dloss && saved && workspace, "null pointer");
+  REQUIRE((dpooled_cat != nullptr) == (dpooled_an != nullptr), "dpooled_cat and dpooled_an: both or neither");
+  if (saved_floats < transfer_head_saved_floats(B, F, Mx))
+    return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", __func__, (long long)saved_floats);
+  if (workspace_floats < transfer_head_bwd_workspace_floats(B, F, Mx))
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", __func__, (long long)workspace_floats);
+  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.dweights = dweights, c.l2 = l2;
+  c.bn_batch = bn_batch != 0, c.y = y, c.loss_kind = loss_kind, c.delta = delta, c.dloss = dloss;
+  c.saved = const_cast<float*>(saved), c.workspace = workspace, c.dpc = dpooled_cat, c.dpa = dpooled_an;
+  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
+  return launch_transfer_head_bwd(c);
+}
+
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,
                       const int64_t* rows, int32_t n_rows, impnn_stream_t stream) {
   REQUIRE(n_tensors >= 0 && n_rows >= 0, "bad shape");

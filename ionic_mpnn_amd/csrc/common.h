@@ -187,6 +187,33 @@ int launch_model_head_bwd(int kind, const float* pc, const float* pa, const floa
                           const float* dout, float* dpc, float* dpa, float* const* grads, int B, int D, int F, int Mx,
                           hipStream_t s, const float* l2 = nullptr, const float* y = nullptr,
                           const float* dloss = nullptr);
+// ---- the transfer head (transfer_head.hip; include/impnn.h, impnn_transfer_head*).  api.hip fills and checks it.
+constexpr int kThTensors = 18;
+struct TransferHeadCall {
+  const float *pc, *pa;
+  const float* const* weights;  // kThTensors device pointers
+  float* const* dweights;       // backward: kThTensors device pointers, null where a tensor is frozen
+  const float* l2;              // host, kThTensors lambdas
+  float *moving_mean, *moving_var;
+  float bn_momentum, bn_eps;
+  bool bn_batch;  // normalise with the batch statistics and move the moving ones (else: the moving statistics)
+  const float* y;
+  int loss_kind;  // 0 squared error, 1 Huber(delta)
+  float delta;
+  const float* dloss;
+  bool dropout;
+  DropoutArgs drop;
+  float* saved;
+  float *out, *loss, *workspace;
+  float *dpc, *dpa;
+  int B, D, F, Mx;
+  hipStream_t stream;
+};
+int64_t transfer_head_saved_floats(int B, int F, int Mx);
+int64_t transfer_head_bwd_workspace_floats(int B, int F, int Mx);
+int64_t transfer_head_loss_workspace_floats(int B);
+int launch_transfer_head(const TransferHeadCall& c);
+int launch_transfer_head_bwd(const TransferHeadCall& c);
 int launch_gather_rows(int n, const void* const* src, void* const* dst, const int64_t* row_bytes, const int64_t* rows,
                        int n_rows, hipStream_t s);
 int launch_model_head(int kind, const float* pc, const float* pa, const float* T, const float* w, float* out, int B,

@@ -365,6 +365,83 @@ class Dense(Layer):
         return cfg
 
 
+class BatchNormalization(Layer):
+    """keras.layers.BatchNormalization(momentum=0.99, epsilon=1e-3) on a rank-2 input, as the transfer head uses it
+    (train_melting_point_transfer.py:99).  Variables: gamma, beta (trainable), moving_mean, moving_variance (state).
+    ``training``: normalise with the batch mean and the biased batch variance and move the moving statistics,
+    moving -= (moving - batch) * (1 - momentum); otherwise the moving statistics.  As in tf.keras 2 a layer with
+    ``trainable = False`` runs in inference mode whatever ``training`` says.  The model's hot path is the fused head
+    (impnn_transfer_head*); this call serves the layer used on its own."""
+
+    def __init__(self, momentum=0.99, epsilon=1e-3, **kwargs):
+        super().__init__(**kwargs)
+        self.momentum, self.epsilon = float(momentum), float(epsilon)
+
+    def build(self, input_shape):
+        n = int(input_shape[-1])
+        self.gamma = self.add_weight((n,), "ones", name="gamma")
+        self.beta = self.add_weight((n,), "zeros", name="beta")
+        self.moving_mean = self.add_weight((n,), "zeros", name="moving_mean")
+        self.moving_variance = self.add_weight((n,), "ones", name="moving_variance")
+
+    @property
+    def trainable_weights(self):
+        return [self.gamma, self.beta] if self.trainable else []
+
+    @property
+    def non_trainable_weights(self):
+        return [self.moving_mean, self.moving_variance] + ([] if self.trainable else [self.gamma, self.beta])
+
+    def call(self, x, training=None):
+        if training and self.trainable:
+            mean, var = x.mean(0), x.var(0, unbiased=False)
+            with torch.no_grad():
+                self.moving_mean.sub_((self.moving_mean - mean) * (1.0 - self.momentum))
+                self.moving_variance.sub_((self.moving_variance - var) * (1.0 - self.momentum))
+        else:
+            mean, var = self.moving_mean, self.moving_variance
+        return (x - mean) * torch.rsqrt(var + self.epsilon) * self.gamma + self.beta
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.update({"momentum": self.momentum, "epsilon": self.epsilon})
+        return cfg
+
+
+class Dropout(Layer):
+    """keras.layers.Dropout(rate) (train_melting_point_transfer.py:101): in training a kept unit is scaled by
+    1 / (1 - rate), inference is the identity.  The mask is the Philox mask of GatedUpdate's dropout
+    on (row = sample, column = unit) with the layer word LAYER_ID, which no GatedUpdate of a model uses; ``seed``
+    defaults to one draw from torch's CPU generator."""
+
+    LAYER_ID = 0xFFFF  # (a model's GatedUpdates count up from 0)
+
+    def __init__(self, rate, seed=None, **kwargs):
+        super().__init__(**kwargs)
+        self.rate = ops.check_dropout_rate(rate)
+        if seed is None and self.rate > 0.0:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        self.seed = None if seed is None else int(seed)
+        self._counter = None
+
+    def call(self, x, training=None, counter=None):
+        if not training or self.rate == 0.0:
+            return x
+        if counter is None:
+            if self._counter is None:
+                self._counter = torch.zeros(1, dtype=torch.int64, device=x.device)
+            counter = self._counter
+        from . import dist as idist
+        d = ops.Dropout(self.rate, self.seed, ops.dropout_layer_word(self.LAYER_ID, idist.dropout_rank()),
+                        ops.dropout_step(counter))
+        return x * ops.dropout_mask(d, x.shape[0], x.shape[1])
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.update({"rate": self.rate, "seed": self.seed})
+        return cfg
+
+
 # ---- viscosity head helpers (models/layers.py:10-49); elementwise torch, ~1e2 flop/sample
 @register_keras_serializable()
 class ComputeLogEta(Layer):

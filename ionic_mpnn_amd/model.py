@@ -35,12 +35,15 @@ TRAIN_ROW_LIST_MIN_ROWS = int(os.environ.get("IMPNN_TRAIN_ROW_LIST_MIN_ROWS", 40
 
 class MPNNModel:
     def __init__(self, kind, atom_vocab_size, bond_vocab_size, atom_dim, bond_dim, fp_size, mixing_size,
-                 num_steps, fp_l2, device=None, name=None, dropout_rate=0.0, dropout_seed=None):
+                 num_steps, fp_l2, device=None, name=None, dropout_rate=0.0, dropout_seed=None,
+                 head_dropout_rate=0.3, head_dropout_seed=None):
         """dropout_rate / dropout_seed: GatedUpdate's Dropout in every message-passing step of both ions, applied by
         training passes only (fit, train_on_batch, __call__(training=True)); the seed defaults to one draw from
-        torch's CPU generator."""
+        torch's CPU generator.  head_dropout_rate / head_dropout_seed (kind "transfer" only): the head's Dropout."""
+        if kind not in ("viscosity", "melting_point", "transfer"):
+            raise ValueError(f"unknown model kind {kind!r}")
         self.kind = kind
-        self.name = name or ("MeltingPoint_MPNN" if kind == "melting_point" else "model")
+        self.name = name or {"melting_point": "MeltingPoint_MPNN", "transfer": "MeltingPoint_Transfer"}.get(kind, "model")
         self.atom_vocab_size, self.bond_vocab_size = int(atom_vocab_size), int(bond_vocab_size)
         self.atom_dim, self.bond_dim = int(atom_dim), int(bond_dim)
         self.fp_size, self.mixing_size, self.num_steps = int(fp_size), int(mixing_size), int(num_steps)
@@ -68,7 +71,15 @@ class MPNNModel:
             self.branches[p] = br
         self.cat_proj = L.Dense(mixing_size, activation="relu", **dev)  # :197
         self.an_proj = L.Dense(mixing_size, activation="relu", **dev)   # :198
-        if kind == "viscosity":
+        if kind == "transfer":  # train_melting_point_transfer.py:95-103 on the viscosity model cut at mix_cat_an
+            self.mix = L.AddTwoTensors(name="mix_cat_an", **dev)
+            self.mp_dense_1 = L.Dense(256, activation="relu", name="mp_dense_1", **dev)
+            self.mp_bn_1 = L.BatchNormalization(name="mp_bn_1", **dev)
+            self.mp_dense_2 = L.Dense(128, activation="relu", name="mp_dense_2", **dev)
+            self.mp_dropout = L.Dropout(head_dropout_rate, seed=head_dropout_seed, name="mp_dropout", **dev)
+            self.mp_dense_3 = L.Dense(64, activation="relu", name="mp_dense_3", **dev)
+            self.melting_point = L.Dense(1, name="melting_point", **dev)
+        elif kind == "viscosity":
             self.mix = L.AddTwoTensors(name="mix_cat_an", **dev)        # :201
             self.visc_params = L.Dense(3, **dev)                        # :204
             self.param_A = L.SliceParamA(name="param_A", **dev)
@@ -102,7 +113,12 @@ class MPNNModel:
             br["fp"].build((None, D)); br["fp"].built = True
         for lyr in (self.cat_proj, self.an_proj):
             lyr.build((None, self.fp_size)); lyr.built = True
-        if self.kind == "viscosity":
+        if self.kind == "transfer":
+            width = self.mixing_size
+            for lyr in self._transfer_head_layers():
+                lyr.build((None, width)); lyr.built = True
+                width = getattr(lyr, "units", width)
+        elif self.kind == "viscosity":
             self.visc_params.build((None, self.mixing_size)); self.visc_params.built = True
         else:
             self.mp_hidden.build((None, self.mixing_size)); self.mp_hidden.built = True
@@ -117,11 +133,16 @@ class MPNNModel:
                 out += [br["bmm"][i], br["reduce"][i], br["update"][i]]
             out += [br["pool"], br["fp"]]
         out += [self.cat_proj, self.an_proj, self.mix]
-        if self.kind == "viscosity":
+        if self.kind == "transfer":
+            out += self._transfer_head_layers()
+        elif self.kind == "viscosity":
             out += [self.visc_params, self.param_A, self.param_B, self.param_C, self.scale_T, self.log_eta]
         else:
             out += [self.mp_hidden, self.mp_out]
         return out
+
+    def _transfer_head_layers(self):
+        return [self.mp_dense_1, self.mp_bn_1, self.mp_dense_2, self.mp_dropout, self.mp_dense_3, self.melting_point]
 
     def get_layer(self, name):
         for lyr in self.layers:
@@ -130,32 +151,52 @@ class MPNNModel:
         raise ValueError(f"No such layer: {name}")
 
     # ------------------------------------------------------------------ weights
-    def _named_tensors(self):
-        t = {"atom_embedding": self.atom_emb.embeddings, "bond_embedding": self.bond_emb.embeddings}
+    def _owned_tensors(self):
+        """[(name, tensor, owning layer)] of every weight, in the fixed order of the weight files."""
+        t = [("atom_embedding", self.atom_emb.embeddings, self.atom_emb),
+             ("bond_embedding", self.bond_emb.embeddings, self.bond_emb)]
+        dense = lambda prefix, lyr: [(f"{prefix}/kernel", lyr.kernel, lyr), (f"{prefix}/bias", lyr.bias, lyr)]
         for p in ("cat", "an"):
             br = self.branches[p]
             for i in range(self.num_steps):
-                t[f"{p}_bmm_{i}/bond_transform"] = br["bmm"][i].bond_transform
+                t.append((f"{p}_bmm_{i}/bond_transform", br["bmm"][i].bond_transform, br["bmm"][i]))
                 for wn, w in br["update"][i]._weights.items():
-                    t[f"{p}_gu_{i}/{wn}"] = w
-            t[f"{p}_fp/kernel"], t[f"{p}_fp/bias"] = br["fp"].kernel, br["fp"].bias
-        t["cat_proj/kernel"], t["cat_proj/bias"] = self.cat_proj.kernel, self.cat_proj.bias
-        t["an_proj/kernel"], t["an_proj/bias"] = self.an_proj.kernel, self.an_proj.bias
-        if self.kind == "viscosity":
-            t["visc_params/kernel"], t["visc_params/bias"] = self.visc_params.kernel, self.visc_params.bias
+                    t.append((f"{p}_gu_{i}/{wn}", w, br["update"][i]))
+            t += dense(f"{p}_fp", br["fp"])
+        t += dense("cat_proj", self.cat_proj) + dense("an_proj", self.an_proj)
+        if self.kind == "transfer":
+            bn = self.mp_bn_1
+            t += dense("mp_dense_1", self.mp_dense_1) + [("mp_bn_1/gamma", bn.gamma, bn), ("mp_bn_1/beta", bn.beta, bn)]
+            t += dense("mp_dense_2", self.mp_dense_2) + dense("mp_dense_3", self.mp_dense_3)
+            t += dense("melting_point", self.melting_point)
+        elif self.kind == "viscosity":
+            t += dense("visc_params", self.visc_params)
         else:
-            t["mp_hidden/kernel"], t["mp_hidden/bias"] = self.mp_hidden.kernel, self.mp_hidden.bias
-            t["mp_out/kernel"], t["mp_out/bias"] = self.mp_out.kernel, self.mp_out.bias
+            t += dense("mp_hidden", self.mp_hidden) + dense("mp_out", self.mp_out)
         return t
 
+    def _named_tensors(self):
+        return {n: w for n, w, _ in self._owned_tensors()}
+
+    def _named_state(self):
+        """What a training run changes besides the weights: BatchNormalization's moving statistics."""
+        if self.kind != "transfer":
+            return {}
+        return {"mp_bn_1/moving_mean": self.mp_bn_1.moving_mean, "mp_bn_1/moving_variance": self.mp_bn_1.moving_variance}
+
+    def variables(self):
+        """[(name, tensor)] of everything a training run changes or a file must hold: all weights, trainable or
+        frozen, then the moving statistics."""
+        return list(self._named_tensors().items()) + list(self._named_state().items())
+
     def state_dict(self):
-        return {k: v.detach().cpu().numpy().copy() for k, v in self._named_tensors().items()}
+        return {k: v.detach().cpu().numpy().copy() for k, v in self.variables()}
 
     def load_weights(self, weights):
         """weights: dict name -> array in the naming of ionic_mpnn_amd.weights, or the path of a save_weights file."""
         if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
             weights = self.load_weight_file(weights)[1]
-        named = self._named_tensors()
+        named = dict(self.variables())
         missing = sorted(set(named) - set(weights))
         if missing:
             raise KeyError(f"missing weights: {missing[:5]}{'...' if len(missing) > 5 else ''}")
@@ -174,21 +215,30 @@ class MPNNModel:
                 "bond_vocab_size": self.bond_vocab_size, "atom_dim": self.atom_dim, "bond_dim": self.bond_dim,
                 "fp_size": self.fp_size, "mixing_size": self.mixing_size, "num_steps": self.num_steps,
                 "fp_l2": self.fp_l2, "dropout_rate": self.dropout_rate, "dropout_seed": self.dropout_seed,
+                **({"head_dropout_rate": self.mp_dropout.rate, "head_dropout_seed": self.mp_dropout.seed}
+                   if self.kind == "transfer" else {}),
+                "layer_trainable": {l.name: bool(l.trainable) for l in self.layers},
                 "layers": [{"class_name": type(l).__name__, "config": l.get_config()} for l in self.layers]}
 
     @classmethod
     def from_config(cls, config, device=None):
         L.reset_uids()  # keras auto-names (gated_update_3, ...) restart with a new model graph
-        return cls(config["kind"], config["atom_vocab_size"], config["bond_vocab_size"], config["atom_dim"],
-                   config["bond_dim"], config["fp_size"], config["mixing_size"], config["num_steps"],
-                   config.get("fp_l2", 1e-4), device=device, name=config.get("name"),
-                   dropout_rate=config.get("dropout_rate", 0.0), dropout_seed=config.get("dropout_seed"))
+        m = cls(config["kind"], config["atom_vocab_size"], config["bond_vocab_size"], config["atom_dim"],
+                config["bond_dim"], config["fp_size"], config["mixing_size"], config["num_steps"],
+                config.get("fp_l2", 1e-4), device=device, name=config.get("name"),
+                dropout_rate=config.get("dropout_rate", 0.0), dropout_seed=config.get("dropout_seed"),
+                head_dropout_rate=config.get("head_dropout_rate", 0.3),
+                head_dropout_seed=config.get("head_dropout_seed"))
+        flags = config.get("layer_trainable") or {}  # (absent in files written before layers could be frozen)
+        for lyr in m.layers:
+            lyr.trainable = bool(flags.get(lyr.name, True))
+        return m
 
     def save_weights(self, path):
         """All variables under their Keras-style names (ionic_mpnn_amd.weights) plus the config, as one .npz."""
         import json
-        arrays = self.state_dict()
-        cfg = {k: v for k, v in self.get_config().items() if k != "layers"}
+        arrays = self.state_dict()  # every variable, frozen or not, and the moving statistics
+        cfg = {k: v for k, v in self.get_config().items() if k != "layers"}  # (keeps each layer's trainable flag)
         # through a file handle: np.savez(path, ...) appends ".npz" to any other suffix, and the reference flow saves
         # to "models/viscosity_final.keras" and loads that very name (train_melting_point_transfer.py:78)
         with open(path, "wb") as f:
@@ -220,13 +270,38 @@ class MPNNModel:
             for lyr in self.branches[p]["bmm"]:
                 lyr.invalidate_cache()
 
+    def weights_updated(self):
+        """After an optimizer step: drops the caches that hold copies of variables the step changed.  The packed
+        encoder weights and a frozen message layer's type matrices stay when nothing they were built from trains - a
+        captured training step reads them on every replay."""
+        self._head_packed = None
+        enc = [t for n, t in self._named_tensors().items()
+               if n.endswith("_embedding") or "_bmm_" in n or "_gu_" in n]
+        if any(t.requires_grad for t in enc):
+            self._packed, self._prepared, self._split_deg_limit = None, {}, None
+        table = self.bond_emb.embeddings.requires_grad
+        for p in ("cat", "an"):
+            for lyr in self.branches[p]["bmm"]:
+                if table or lyr.bond_transform.requires_grad:
+                    lyr.invalidate_cache()
+
+    def _cache_refs(self):
+        """The cached tensors a captured step may read (kept alive by train.GraphedTrainStep)."""
+        return [dict(self._prepared), self._packed] + [getattr(l, "_mats_cache", None)
+                                                       for p in ("cat", "an") for l in self.branches[p]["bmm"]]
+
     def _head_tensors(self):
         """Head weight tensors in the order of impnn_model_head's packed layout (include/impnn.h)."""
         parts = []
         for p in ("cat", "an"):
             parts += [self.branches[p]["fp"].kernel, self.branches[p]["fp"].bias]
         parts += [self.cat_proj.kernel, self.cat_proj.bias, self.an_proj.kernel, self.an_proj.bias]
-        if self.kind == "viscosity":
+        if self.kind == "transfer":  # the order of impnn_transfer_head's `weights`
+            bn = self.mp_bn_1
+            parts += [self.mp_dense_1.kernel, self.mp_dense_1.bias, bn.gamma, bn.beta, self.mp_dense_2.kernel,
+                      self.mp_dense_2.bias, self.mp_dense_3.kernel, self.mp_dense_3.bias, self.melting_point.kernel,
+                      self.melting_point.bias]
+        elif self.kind == "viscosity":
             parts += [self.visc_params.kernel, self.visc_params.bias]
         else:
             parts += [self.mp_hidden.kernel, self.mp_hidden.bias, self.mp_out.kernel, self.mp_out.bias]
@@ -299,16 +374,40 @@ class MPNNModel:
 
     def _builds_graph(self):
         """True when this call is differentiated: grad mode on and some variable asks for a gradient."""
-        return torch.is_grad_enabled() and any(t.requires_grad for _, t in self.trainable_variables())
+        return torch.is_grad_enabled() and any(t.requires_grad for t in self._named_tensors().values())
+
+    def _first_trained_step(self, prefix):
+        """The lowest message-passing step of an ion below which a differentiated pass keeps nothing: the first whose
+        BondMatrixMessage or GatedUpdate asks for a gradient; 0 when an embedding does (the atom embedding feeds step
+        0, the bond embedding every step's type matrices); None when nothing in the ion's encoder does."""
+        if not torch.is_grad_enabled():
+            return None
+        if self.atom_emb.embeddings.requires_grad or self.bond_emb.embeddings.requires_grad:
+            return 0
+        br = self.branches[prefix]
+        for i in range(self.num_steps):
+            if br["bmm"][i].bond_transform.requires_grad or any(w.requires_grad for w in br["update"][i].weights):
+                return i
+        return None
+
+    def _encoder_trains(self):
+        """True when a differentiated pass has to keep an encoder graph (some embedding or step asks for a gradient)."""
+        return any(self._first_trained_step(p) is not None for p in ("cat", "an"))
 
     def _all_type_matrices(self):
         """Training: the type matrices of every message layer from one node (3 launches per step instead of 3 per
         layer) as {(ion, step): (matrices, their slice of the node's gradient pool)}; None where the per-layer entries
         are the better fit (bond_dim >= 64 is GEMM-shaped)."""
-        if self.bond_dim >= 64 or self.num_steps == 0 or not self._builds_graph():
+        if self.bond_dim >= 64 or self.num_steps == 0 or not self._encoder_trains():
             return None
         from . import autograd
-        keys = [(p, i) for p in ("cat", "an") for i in range(self.num_steps)]
+        # (a frozen layer's matrices come from its cache and get no gradient; a trainable bond embedding needs every
+        #  layer's)
+        table = self.bond_emb.embeddings.requires_grad
+        keys = [(p, i) for p in ("cat", "an") for i in range(self.num_steps)
+                if table or self.branches[p]["bmm"][i].bond_transform.requires_grad]
+        if not keys:
+            return None
         *mats, pool = autograd.BondTypeMatricesAll.apply(
             self.bond_emb.embeddings, *[self.branches[p]["bmm"][i].bond_transform for p, i in keys])
         return {k: (mats[j], None if pool is None else pool[j]) for j, k in enumerate(keys)}
@@ -316,7 +415,7 @@ class MPNNModel:
     def dropout_counter(self):
         """The model's device dropout step counter (None at rate 0): every training pass snapshots and advances it once
         (ops.dropout_step), before the two ions fork, and both ions' layers draw their masks from that snapshot."""
-        if self.dropout_rate == 0.0:
+        if self.dropout_rate == 0.0 and self.kind != "transfer":  # (the transfer head's Dropout always owns one)
             return None
         if self._dropout_counter is None:
             self._dropout_counter = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -338,7 +437,8 @@ class MPNNModel:
         bond = self.bond_emb(bond_ids)
         if not typed:
             bond = bond.dense()
-        one_node = typed and trace is None and self._builds_graph()  # training: a whole step as one autograd node
+        s0 = self._first_trained_step(prefix)
+        one_node = typed and trace is None and s0 is not None  # training: a whole step as one autograd node
         # inference through the layered path (what serves atom_dim 64 / 128): GatedUpdate only on the rows an
         # encode() loop has to carry - padding atoms can reach neither a message nor the pool (include/impnn.h,
         # impnn_gated_update_rows); their rows of h are left undefined and are never read
@@ -346,34 +446,36 @@ class MPNNModel:
         # (atom_dim 32 has the entry too, but there the three small launches that build the list cost what the skipped
         #  rows save: measured 8.1 vs 8.5 M pairs/s at batch 4096)
         if typed and trace is None and self.atom_dim in (64, 128) and self.num_steps > 0 and (
-                not self._builds_graph() or atom_ids.numel() >= TRAIN_ROW_LIST_MIN_ROWS):
+                s0 is None or atom_ids.numel() >= TRAIN_ROW_LIST_MIN_ROWS):
             # (training too, from TRAIN_ROW_LIST_MIN_ROWS atom rows per ion: the one-node step runs GatedUpdate forward
             #  AND backward on the list, impnn_gated_update_rows_bwd - padding atoms carry no gradient; below that a
             #  step is bound by its launch count and the list's own launches cost more than the skipped rows save)
             rows = ops.kept_row_index(atom_ids, bond_ids, conn, self.bond_vocab_size)
         for i in range(self.num_steps):
             drop = self._layer_dropout(prefix, i, dropout_step) if dropout_step is not None else None
-            if one_node:
+            if one_node and i >= s0:
                 from . import autograd
-                mats, dmats = type_mats[(prefix, i)] if type_mats else (br["bmm"][i]._type_matrices(bond.table), None)
+                mats, dmats = (type_mats[(prefix, i)] if type_mats and (prefix, i) in type_mats
+                               else (br["bmm"][i]._type_matrices(bond.table), None))
                 u, w = br["update"][i], br["update"][i]._weights
                 h = autograd.MessagePassingStep.apply(
                     h, bond.ids, conn, mats, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
                     w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta, u.epsilon, graph, dmats,
-                    *(rows if rows is not None else (None, None)), i > 0, drop)
+                    *(rows if rows is not None else (None, None)), i > s0, drop)
                 continue
-            if typed:  # (the layer's own call would sort the edges again)
-                m = ops.bmm_message_typed(h, bond.ids, conn, br["bmm"][i]._type_matrices(bond.table), graph)
-            else:
-                m = br["bmm"][i]([h, bond, conn])
-            agg = br["reduce"][i]([m, conn[:, :, 1], h])
-            if rows is not None or drop is not None:
-                u, w = br["update"][i], br["update"][i]._weights
-                h = ops.gated_update(h, agg, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
-                                     w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta,
-                                     u.epsilon, rows=rows, dropout=drop)
-            else:
-                h = br["update"][i]([h, agg])
+            with torch.set_grad_enabled(torch.is_grad_enabled() and not one_node):  # (one_node: a step below s0)
+                if typed:  # (the layer's own call would sort the edges again)
+                    m = ops.bmm_message_typed(h, bond.ids, conn, br["bmm"][i]._type_matrices(bond.table), graph)
+                else:
+                    m = br["bmm"][i]([h, bond, conn])
+                agg = br["reduce"][i]([m, conn[:, :, 1], h])
+                if rows is not None or drop is not None:
+                    u, w = br["update"][i], br["update"][i]._weights
+                    h = ops.gated_update(h, agg, w["dense_z/kernel"], w["dense_z/bias"], w["dense_r/kernel"],
+                                         w["dense_r/bias"], w["dense_h/kernel"], w["dense_h/bias"], u.gamma, u.beta,
+                                         u.epsilon, rows=rows, dropout=drop)
+                else:
+                    h = br["update"][i]([h, agg])
             if trace is not None:
                 trace[f"{prefix}/m{i}"], trace[f"{prefix}/agg{i}"], trace[f"{prefix}/h{i + 1}"] = m, agg, h
         pooled = br["pool"]([h, atom_ids])
@@ -395,7 +497,7 @@ class MPNNModel:
         return self._pipeline.plan(ions, self.atom_dim, self.bond_dim, self.num_steps, self.atom_vocab_size,
                                    self.bond_vocab_size, mode=mode, workgroups=self.encoder_workgroups)
 
-    def encode_pooled(self, inputs, fused=None, trace=None, plan=None, training=False):
+    def encode_pooled(self, inputs, fused=None, trace=None, plan=None, training=False, dropout_step=None):
         """Both ions' GlobalSumPool outputs: the hot path.  ``training`` (layer at a time only):
         a training pass - GatedUpdate's dropout applies when the model has a rate above 0."""
         if plan is not None:
@@ -431,7 +533,10 @@ class MPNNModel:
             raise ValueError("a training pass runs layer at a time (fused=False)")
         # dropout: one snapshot of the step counter per pass, taken before the ions fork; it lives with the pass
         # (the autograd nodes of both ions hold it), so interleaved passes keep their own masks in the backward
-        ds = ops.dropout_step(self.dropout_counter()) if training and self.dropout_rate > 0.0 else None
+        # (dropout_step: the caller took the pass's snapshot already - the transfer model, whose head shares it)
+        ds = None
+        if training and self.dropout_rate > 0.0:
+            ds = dropout_step if dropout_step is not None else ops.dropout_step(self.dropout_counter())
         tm = self._all_type_matrices() if trace is None else None
         if trace is None and getattr(self, "two_streams", True) and ca.is_cuda \
                 and ca.shape[0] <= int(os.environ.get("IMPNN_TWO_STREAM_MAX_BATCH", TWO_STREAM_MAX_BATCH)):
@@ -488,7 +593,39 @@ class MPNNModel:
             torch.cuda.current_stream(self.device).wait_stream(self._side_stream)
             self._side_stream_used = False
 
-    def head(self, pooled_cat, pooled_an, temperature=None, trace=None, differentiable=False):
+    def _transfer_cfg(self, training, dropout_step=None):
+        """The per-pass settings of the transfer head kernels (autograd.TransferHeadLoss, ops.transfer_head)."""
+        from . import dist as idist
+        bn, dp = self.mp_bn_1, self.mp_dropout
+        drop = None
+        if training and dp.rate > 0.0:
+            drop = ops.Dropout(dp.rate, dp.seed, ops.dropout_layer_word(L.Dropout.LAYER_ID, idist.dropout_rank()),
+                               dropout_step)
+        # keras 2: a BatchNormalization frozen at compile() runs in inference mode inside a training pass
+        return {"fp_size": self.fp_size, "mixing_size": self.mixing_size, "l2": self._head_l2(),
+                "moving_mean": bn.moving_mean, "moving_variance": bn.moving_variance, "momentum": bn.momentum,
+                "epsilon": bn.epsilon, "bn_batch": bool(training and getattr(self, "_bn_training", bn.trainable)),
+                "dropout": drop, "loss_kind": 0 if self._loss_name() == "mse" else 1, "delta": self._loss_delta()}
+
+    def _loss_name(self):
+        return getattr(self, "loss", "mse") if isinstance(getattr(self, "loss", "mse"), str) else "huber"
+
+    def _loss_delta(self):
+        loss = getattr(self, "loss", "mse")
+        return 1.0 if isinstance(loss, str) else float(loss.delta)
+
+    def head(self, pooled_cat, pooled_an, temperature=None, trace=None, differentiable=False, training=False):
+        if self.kind == "transfer":
+            if trace is None and not differentiable and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64:
+                return ops.transfer_head(pooled_cat, pooled_an, self._head_tensors(), self._transfer_cfg(False))
+            # layer by layer (traces, model(x, training=True), widths the kernels do not cover)
+            fp_cat, fp_an = self.branches["cat"]["fp"](pooled_cat), self.branches["an"]["fp"](pooled_an)
+            x = self.mix([self.cat_proj(fp_cat), self.an_proj(fp_an)])
+            if trace is not None:
+                trace["cat/fp"], trace["an/fp"], trace["mixed"] = fp_cat, fp_an, x
+            x = self.mp_bn_1(self.mp_dense_1(x), training=training and getattr(self, "_bn_training", True))
+            x = self.mp_dropout(self.mp_dense_2(x), training=training, counter=self.dropout_counter())
+            return self.melting_point(self.mp_dense_3(x))
         if trace is None and not differentiable and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64:
             return ops.model_head(self.kind, pooled_cat, pooled_an, temperature, self._packed_head(), self.fp_size,
                                   self.mixing_size)  # one launch (SURVEY.md 8 f1)
@@ -518,45 +655,62 @@ class MPNNModel:
         inputs = self._to_device(inputs)
         if training:
             pc, pa = self.encode_pooled(inputs, fused=False, training=True)
-            return self.head(pc, pa, inputs.get("temperature"), differentiable=True)
+            return self.head(pc, pa, inputs.get("temperature"), differentiable=True, training=True)
         with torch.no_grad():
             pc, pa = self.encode_pooled(inputs, fused=fused, trace=trace)
             return self.head(pc, pa, inputs.get("temperature"), trace=trace)
 
     # ------------------------------------------------------------------ training (SURVEY.md 8 f4)
     def trainable_variables(self):
-        """[(name, tensor)] in a fixed order; every variable of the reference model is trainable."""
-        return list(self._named_tensors().items())
+        """[(name, tensor)] of the weights whose layer is trainable (``layer.trainable``, all by default), in the
+        fixed order of ``variables()``."""
+        return [(n, w) for n, w, lyr in self._owned_tensors() if lyr.trainable]
 
     def compile(self, optimizer=None, loss="mse"):
-        """model.compile(optimizer=Adam(1e-3, clipnorm=1.0), loss="mse") (train_viscosity.py:227-230)."""
+        """model.compile(optimizer=Adam(1e-3, clipnorm=1.0), loss="mse") (train_viscosity.py:227-230) or
+        loss=Huber(delta=1.0) / "huber" (train_melting_point_transfer.py:193-196).  Reads every ``layer.trainable``
+        as Keras does: the optimizer (a fresh state per compile) holds the trainable variables only, the frozen ones
+        ask for no gradient and no training step changes them; a flag changed later counts from the next compile."""
         from . import train
-        if loss != "mse":
-            raise ValueError("the reference trainers use loss='mse'")
+        if not (loss in ("mse", "huber") or isinstance(loss, train.Huber)):
+            raise ValueError("loss must be 'mse', 'huber' or a train.Huber object")
+        tv = self.trainable_variables()
+        if not tv:
+            raise ValueError("no trainable variable: every layer of the model is frozen")
+        self.loss = loss
         self.optimizer = optimizer if optimizer is not None else train.Adam(1e-3, clipnorm=1.0)
-        for _, t in self.trainable_variables():
-            t.requires_grad_(True)
-        self.optimizer.build([t for _, t in self.trainable_variables()])
+        names = {n for n, _ in tv}
+        for n, t in self._named_tensors().items():
+            t.requires_grad_(n in names)
+            if n not in names:
+                t.grad = None
+        if self.kind == "transfer":
+            self._bn_training = bool(self.mp_bn_1.trainable)
+        self.optimizer.build([t for _, t in tv])
         return self
 
     def regularization_loss(self):
         """keras l2(fp_l2) on the fingerprint Dense kernels (train_viscosity.py:189) and, for the melting-point
         model, on the hidden Dense (train_melting_point.py:173,197): fp_l2 * sum(w^2)."""
         ks = [self.branches["cat"]["fp"].kernel, self.branches["an"]["fp"].kernel]
-        if self.kind != "viscosity":
+        if self.kind == "melting_point":
             ks.append(self.mp_hidden.kernel)
         return self.fp_l2 * sum((k * k).sum() for k in ks)
 
     def _head_l2(self):
         """keras l2 lambda per head tensor, in the order of _head_tensors() (see regularization_loss)."""
         lam = [self.fp_l2, 0.0, self.fp_l2, 0.0, 0.0, 0.0, 0.0, 0.0]
+        if self.kind == "transfer":
+            return lam + [0.0] * 10
         return lam + ([0.0, 0.0] if self.kind == "viscosity" else [self.fp_l2, 0.0, 0.0, 0.0])
 
     def _loss(self, inputs, y, training):
         from . import train
         y = torch.as_tensor(y, dtype=torch.float32).to(self.device).reshape(-1, 1)
-        if training and torch.is_grad_enabled() and y.shape[0] > 0 \
-                and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64:
+        covered = y.shape[0] > 0 and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
+        if self.kind == "transfer" and covered:
+            return self._transfer_loss(self._to_device(inputs), y, training)
+        if training and torch.is_grad_enabled() and covered and self._loss_name() == "mse":
             # head, mse and the l2 penalties as ONE node (impnn_model_head_loss): ~25 launches fewer per step
             from . import autograd
             inputs = self._to_device(inputs)
@@ -570,10 +724,44 @@ class MPNNModel:
                                                 self.mixing_size, self._head_l2(), ws, pc, pa, T, y,
                                                 *self._head_tensors())
         pred = self(inputs, training=True) if training else self(inputs)
+        fn = train.mse if self._loss_name() == "mse" else train.Huber(self._loss_delta())
         if training:
-            return train.mse(y, pred) + self.regularization_loss()
+            return fn(y, pred) + self.regularization_loss()
         with torch.no_grad():
-            return train.mse(y, pred) + self.regularization_loss()
+            return fn(y, pred) + self.regularization_loss()
+
+    def _overflow_check(self, inputs):
+        """True where the fused encoder would end with its host-side overflow check (N > 256 or E > 255: a molecule
+        may exceed a chunk) - a synchronisation a captured training step cannot contain, so training passes of such
+        shapes run layer at a time, eager and captured alike."""
+        N, E = inputs["cat_atom"].shape[1], inputs["cat_bond"].shape[1]
+        mode = self.resolve_encoder_mode(N, E)
+        return mode is not None and ops.encoder_overflow_possible(N, E, self.atom_dim, mode)
+
+    def _transfer_loss(self, inputs, y, training):
+        """The transfer model's loss as one node (impnn_transfer_head_loss[_bwd]).  An encoder with nothing to train
+        computes the pooled vectors as inference does - fused encoder where the shape allows, no graph, nothing saved -
+        unless its GatedUpdate dropout has to apply; otherwise the layered pass keeps a graph from the first trained
+        step up (_first_trained_step)."""
+        from . import autograd
+        B = int(y.shape[0])
+        need = int(ops._lib.load().impnn_transfer_head_loss_workspace_floats(B))
+        ws = getattr(self, "_loss_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
+        # one snapshot of the step counter per training pass, shared by the encoder's GatedUpdates and the head
+        ds = ops.dropout_step(self.dropout_counter()) if training else None
+        if training and self._encoder_trains():
+            pc, pa = self.encode_pooled(inputs, fused=False, training=True, dropout_step=ds)
+        else:
+            with torch.no_grad():
+                if training and self.dropout_rate > 0.0:
+                    pc, pa = self.encode_pooled(inputs, fused=False, training=True, dropout_step=ds)
+                else:
+                    pc, pa = self.encode_pooled(inputs, fused=False if training and self._overflow_check(inputs) else None)
+        with torch.set_grad_enabled(training and torch.is_grad_enabled()):
+            return autograd.TransferHeadLoss.apply(self._transfer_cfg(training, ds), ws, pc, pa, y,
+                                                   *self._head_tensors())
 
     def train_on_batch(self, inputs, y, group=None, n_global=None):
         """One optimizer step on one mini-batch -> the batch loss (MSE + penalties) as a 0-d tensor.
@@ -601,7 +789,7 @@ class MPNNModel:
             self.join_training_streams()
         opt.apply_gradients()   # clips, updates, and leaves the gradients in place ...
         opt.zero_grad()         # ... so clear them for the next accumulation
-        self.invalidate_packed_weights()
+        self.weights_updated()
         return loss.detach() if loss is not None else torch.zeros((), device=opt.flat_grad.device)
 
     def evaluate(self, inputs, y, batch_size=32):
@@ -762,6 +950,25 @@ def build_melting_point_model(atom_vocab_size, bond_vocab_size, atom_dim=32, fp_
     return MPNNModel("melting_point", atom_vocab_size, bond_vocab_size, atom_dim, atom_dim * atom_dim, fp_size,
                      mixing_size, num_steps, fp_l2=1e-5, device=device, dropout_rate=dropout_rate,
                      dropout_seed=dropout_seed)
+
+
+def build_transfer_model(viscosity_model_path, device=None, dropout_seed=None):
+    """train_melting_point_transfer.py:73-106: the viscosity model of a file written by ``MPNNModel.save`` cut at
+    ``mix_cat_an`` (layers, names and weights kept: cat_bmm_2, gated_update_6, ...), and on it the head Dense 256 relu
+    "mp_dense_1", BatchNormalization "mp_bn_1", Dense 128 relu "mp_dense_2", Dropout 0.3 "mp_dropout", Dense 64 relu
+    "mp_dense_3", Dense 1 "melting_point".  Inputs: the six graph tensors (a "temperature" key is ignored).
+    dropout_seed: the seed of the head's Dropout mask (default: one draw from torch's CPU generator)."""
+    cfg, w = MPNNModel.load_weight_file(viscosity_model_path)
+    if cfg.get("kind") != "viscosity":
+        raise ValueError(f"{viscosity_model_path}: a viscosity model is needed, this file holds kind {cfg.get('kind')!r}")
+    L.reset_uids()
+    m = MPNNModel("transfer", cfg["atom_vocab_size"], cfg["bond_vocab_size"], cfg["atom_dim"], cfg["bond_dim"],
+                  cfg["fp_size"], cfg["mixing_size"], cfg["num_steps"], cfg.get("fp_l2", 1e-4), device=device,
+                  dropout_rate=cfg.get("dropout_rate", 0.0), dropout_seed=cfg.get("dropout_seed"),
+                  head_dropout_seed=dropout_seed)
+    head = {n for lyr in m._transfer_head_layers() for n, _, o in m._owned_tensors() if o is lyr} | set(m._named_state())
+    m.load_weights({**{n: t.detach().cpu().numpy() for n, t in m.variables() if n in head}, **w})
+    return m
 
 
 def load_model(path, custom_objects=None, device=None):

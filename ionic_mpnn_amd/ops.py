@@ -700,3 +700,19 @@ def model_head(kind, pooled_cat, pooled_an, temperature, head_weights, fp_size, 
         check(lib.impnn_model_head(k, ptr(pooled_cat), ptr(pooled_an), ptr(T) if T is not None else None,
                                    ptr(head_weights), ptr(out), B, D, fp_size, mixing_size, stream_ptr()))
     return out
+
+
+def transfer_head(pooled_cat, pooled_an, weights, cfg):
+    """The transfer model's head in inference, one launch (impnn_transfer_head): ``weights`` the 18 tensors in the
+    order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg -> (B,1)."""
+    require_gpu(pooled_cat, pooled_an, *weights)
+    pooled_cat, pooled_an = f32c(pooled_cat), f32c(pooled_an)
+    weights = [f32c(w) for w in weights]
+    B, D = pooled_cat.shape
+    out = torch.empty(B, 1, dtype=torch.float32, device=pooled_cat.device)
+    table = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
+    with torch.cuda.device(pooled_cat.device):
+        check(_lib.load().impnn_transfer_head(ptr(pooled_cat), ptr(pooled_an), table, ptr(cfg["moving_mean"]),
+                                              ptr(cfg["moving_variance"]), cfg["epsilon"], ptr(out), B, D,
+                                              cfg["fp_size"], cfg["mixing_size"], stream_ptr()))
+    return out

@@ -118,7 +118,7 @@ class GraphedTrainStep:
                 self.resident = ([x[k] for k in keys] + [y_dev], [self.static_in[k] for k in keys] + [self.static_y])
                 self.static_rows = torch.zeros(self.batch, dtype=torch.int64, device=dev)
         opt = model.optimizer
-        saved_w = [t.detach().clone() for _, t in model.trainable_variables()]
+        saved_w = [t.detach().clone() for _, t in model.variables()]  # (with BatchNormalization's moving statistics)
         saved_o = opt.state()
         ctr = model.dropout_counter()  # the dropout step counter: the warm-up steps advance it, like the Adam state
         saved_c = ctr.clone() if ctr is not None else None
@@ -132,13 +132,14 @@ class GraphedTrainStep:
         with torch.cuda.graph(self.graph):
             self.static_loss = self._step()
         with torch.no_grad():  # the warm-up steps were real updates: undo them
-            for (_, t), w0 in zip(model.trainable_variables(), saved_w):
+            for (_, t), w0 in zip(model.variables(), saved_w):
                 t.copy_(w0)
         opt.load_state(saved_o)
         if ctr is not None:
             ctr.copy_(saved_c)
         opt.zero_grad()
-        model.invalidate_packed_weights()
+        self._cache_refs = model._cache_refs()  # frozen layers' cached tensors the captured kernels read
+        model.weights_updated()
 
     def _step(self):
         m = self.model
@@ -166,7 +167,7 @@ class GraphedTrainStep:
                 torch.index_select(x[k], 0, rows, out=v)
             torch.index_select(y_dev, 0, rows, out=self.static_y)
         self.graph.replay()
-        self.model.invalidate_packed_weights()
+        self.model.weights_updated()
         return self.static_loss
 
     def __call__(self, inputs, y):
@@ -174,7 +175,7 @@ class GraphedTrainStep:
             v.copy_(inputs[k], non_blocking=True)
         self.static_y.copy_(torch.as_tensor(np.asarray(y, np.float32)).reshape(-1, 1), non_blocking=True)
         self.graph.replay()
-        self.model.invalidate_packed_weights()
+        self.model.weights_updated()
         return self.static_loss
 
 
@@ -242,6 +243,25 @@ class EarlyStopping(Callback):
     def on_train_end(self, logs=None):
         if self.restore_best_weights and self.best_weights is not None:
             self.model.load_weights(self.best_weights)
+
+
+class Huber:
+    """keras.losses.Huber(delta): per sample e^2 / 2 where |e| <= delta, else delta * (|e| - delta / 2); mean over
+    the batch (train_melting_point_transfer.py:195).  ``model.compile(loss=Huber(1.0))``; the transfer model computes
+    it inside its head kernels, the other models through this call."""
+
+    def __init__(self, delta=1.0):
+        self.delta = float(delta)
+        if not self.delta > 0.0:
+            raise ValueError("Huber delta must be positive")
+
+    def get_config(self):
+        return {"name": "huber_loss", "delta": self.delta}
+
+    def __call__(self, y_true, y_pred):
+        e = y_pred.reshape(y_true.shape[0], -1) - y_true.reshape(y_true.shape[0], -1)
+        a = e.abs()
+        return torch.mean(torch.where(a <= self.delta, 0.5 * e * e, self.delta * (a - 0.5 * self.delta)))
 
 
 def mse(y_true, y_pred):
