@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """One-off extension of the committed fuzz tests (tests/test_gpu_encoder.py, tests/test_gpu_wide.py): the same random
 dense multigraph cases for further seeds, every exact-f32 form the shape allows, against the fp64 oracle.
-python tools/extended_fuzz.py [--first 24] [--count 150]      (GPU box; test infrastructure, uses oracle/)"""
+python tools/extended_fuzz.py [--first 24] [--count 150]      (GPU box; test infrastructure, uses oracle/)
+python tools/extended_fuzz.py --train [--first 32] [--count 64]: the whole-model gradient fuzz of
+tests/test_gpu_train_fuzz.py (run_model_case) for further seeds instead."""
 import argparse
 import sys
 from pathlib import Path
@@ -21,8 +23,21 @@ from oracle import mpnn_oracle as O  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--first", type=int, default=24)
 ap.add_argument("--count", type=int, default=150)
+ap.add_argument("--train", action="store_true")
 args = ap.parse_args()
 bad, ran = [], 0
+if args.train:
+    import test_gpu_train_fuzz as TF  # noqa: E402
+    for seed in range(args.first, args.first + args.count):
+        try:
+            TF.run_model_case(seed)
+            ran += 1
+        except AssertionError as e:  # a gradient outside its bound; anything else (a HIP error) ends the run
+            bad.append(("train", seed, str(e)[:300]))
+    print(f"{ran} training passes over seeds {args.first} .. {args.first + args.count - 1}: {len(bad)} failures")
+    for b in bad:
+        print(b)
+    sys.exit(1 if bad else 0)
 for seed in range(args.first, args.first + args.count):
     rng = np.random.default_rng(1000 + seed)
     N, E, K, S, B, Va, Vb, inp = TE._random_dense_case(rng)
