@@ -1,5 +1,6 @@
 """Autograd nodes of the layer-at-a-time path: each forward is the libimpnn entry of
-the reference layer, each backward the matching ``impnn_*_bwd`` entry (csrc/train_kernels.hip).
+the reference layer, each backward the matching ``impnn_*_bwd`` entry (csrc/train_kernels.hip; the message
+adjoint and its edge sort: csrc/message_typed.hip).
 ``ops.*`` routes through these nodes whenever an input requires grad and grad mode is on; with no grad
 the calls are the plain forward entries.  torch.autograd only keeps the graph - no torch op computes here.
 A model's training pass uses the larger nodes at the end of this file (a batch-32 step is bound by the number of
@@ -142,6 +143,15 @@ def _message_adjoint(entry, graph, h, bond_ids, conn, mats, grad, dh, dmats, scr
               1 if ready else 0)
 
 
+def _message_node_backward(entry, ctx, grad):
+    """The backward of the two message nodes below: (dh, dmats) of ``entry`` for the node's five inputs."""
+    h, bond_ids, conn, mats = ctx.saved_tensors
+    both = torch.zeros(h.numel() + mats.numel(), dtype=torch.float32, device=h.device)  # one fill for both sums
+    dh, dmats = both[:h.numel()].view_as(h), both[h.numel():].view_as(mats)
+    _message_adjoint(entry, ctx.graph, h, bond_ids, conn, mats, f32c(grad), dh, dmats)
+    return dh, None, None, dmats, None
+
+
 class BmmMessageTyped(torch.autograd.Function):
     """BondMatrixMessage.call in the per-bond-type schedule (models/layers.py:100-117)."""
 
@@ -154,12 +164,7 @@ class BmmMessageTyped(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dm):
-        h, bond_ids, conn, mats = ctx.saved_tensors
-        dm = f32c(dm)
-        both = torch.zeros(h.numel() + mats.numel(), dtype=torch.float32, device=h.device)  # one fill for both sums
-        dh, dmats = both[:h.numel()].view_as(h), both[h.numel():].view_as(mats)
-        _message_adjoint("impnn_bmm_message_typed_bwd", ctx.graph, h, bond_ids, conn, mats, dm, dh, dmats)
-        return dh, None, None, dmats, None
+        return _message_node_backward("impnn_bmm_message_typed_bwd", ctx, dm)
 
 
 class MessageReduceTyped(torch.autograd.Function):
@@ -177,12 +182,7 @@ class MessageReduceTyped(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dagg):
-        h, bond_ids, conn, mats = ctx.saved_tensors
-        dagg = f32c(dagg)
-        both = torch.zeros(h.numel() + mats.numel(), dtype=torch.float32, device=h.device)
-        dh, dmats = both[:h.numel()].view_as(h), both[h.numel():].view_as(mats)
-        _message_adjoint("impnn_message_reduce_typed_bwd", ctx.graph, h, bond_ids, conn, mats, dagg, dh, dmats)
-        return dh, None, None, dmats, None
+        return _message_node_backward("impnn_message_reduce_typed_bwd", ctx, dagg)
 
 
 class ReduceScatterAdd(torch.autograd.Function):

@@ -192,6 +192,32 @@ GatedUpdateCall gu_backward(const char* entry, GatedUpdateForm form, const float
   return c;
 }
 
+// ---- the typed-message family (include/impnn.h; message_typed.hip).  Each entry fills a TypedMessageCall; one check
+// applies the family's rules in a fixed order and launches.
+TypedMessageCall typed_message(const char* entry, const float* h, const int32_t* bond_ids, const int32_t* conn,
+                               const float* type_mats, void* workspace, int64_t workspace_bytes, int32_t B, int32_t N,
+                               int32_t E, int32_t D, int32_t Vb, int32_t sort_ready, impnn_stream_t stream) {
+  TypedMessageCall c{};
+  c.entry = entry, c.h = h, c.bond_ids = bond_ids, c.conn = conn, c.type_mats = type_mats, c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes, c.B = B, c.N = N, c.E = E, c.D = D, c.Vb = Vb, c.sort_ready = sort_ready != 0;
+  c.stream = as_stream(stream);
+  return c;
+}
+
+// The family's rules in their order: shape, zero work, null pointers (`tensors`: the entry's own are non-null), workspace
+// size, coverage - then the launch (the adjoint's refuses a misaligned edge buffer before it launches anything).
+int typed_message_checked(const TypedMessageCall& c, bool tensors, int (*launch)(const TypedMessageCall&)) {
+  if (!(c.B >= 0 && c.N > 0 && c.E >= 0 && c.D > 0 && c.Vb > 0)) return fail(IMPNN_E_BADARG, "%s: bad shape", c.entry);
+  if (c.B == 0 || c.E == 0) return IMPNN_OK;
+  if (!(c.h && c.bond_ids && c.conn && c.type_mats && c.workspace && tensors))
+    return fail(IMPNN_E_BADARG, "%s: null pointer", c.entry);
+  if (c.workspace_bytes < 4 * bmm_message_typed_bwd_workspace_ints(c.B, c.E, c.Vb))
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld bytes is too small", c.entry, (long long)c.workspace_bytes);
+  if (c.Vb > kMaxTypes) return fail(IMPNN_E_UNSUPPORTED, "%s: Vb=%d too large", c.entry, c.Vb);
+  if (c.D > 128) return fail(IMPNN_E_UNSUPPORTED, "%s: D=%d > 128", c.entry, c.D);
+  return launch(c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -677,43 +703,30 @@ int impnn_bmm_message_typed_sorted(const float* h, const int32_t* bond_ids, cons
                                    const float* type_mats, float* messages, void* workspace, int64_t workspace_bytes,
                                    int32_t B, int32_t N, int32_t E, int32_t D, int32_t Vb, int32_t sorted_ready,
                                    impnn_stream_t stream) {
-  REQUIRE(B >= 0 && N > 0 && E >= 0 && D > 0 && Vb > 0, "bad shape");
-  if (B == 0 || E == 0) return IMPNN_OK;
-  REQUIRE(h && bond_ids && conn && type_mats && messages && workspace, "null pointer");
-  if (workspace_bytes < impnn_bmm_message_typed_bwd_workspace_bytes(B, E, Vb))
-    return fail(IMPNN_E_WORKSPACE, "bmm_message_typed_sorted: workspace of %lld bytes is too small",
-                (long long)workspace_bytes);
-  return launch_bmm_message_typed_sorted(h, bond_ids, conn, type_mats, messages, static_cast<int32_t*>(workspace), B,
-                                         N, E, D, Vb, sorted_ready & 3, as_stream(stream));
+  TypedMessageCall c = typed_message(__func__, h, bond_ids, conn, type_mats, workspace, workspace_bytes, B, N, E, D, Vb,
+                                     sorted_ready & 1, stream);
+  c.messages = messages, c.zero_rows_ready = (sorted_ready & 2) != 0;
+  return typed_message_checked(c, messages != nullptr, launch_bmm_message_typed_sorted);
 }
 
 int impnn_bmm_message_typed_bwd(const float* h, const int32_t* bond_ids, const int32_t* conn,
                                 const float* type_mats, const float* dmessages, float* dh, float* dtype_mats,
                                 void* workspace, int64_t workspace_bytes, int32_t B, int32_t N, int32_t E, int32_t D,
                                 int32_t Vb, int32_t sorted_ready, impnn_stream_t stream) {
-  REQUIRE(B >= 0 && N > 0 && E >= 0 && D > 0 && Vb > 0, "bad shape");
-  if (B == 0 || E == 0) return IMPNN_OK;
-  REQUIRE(h && bond_ids && conn && type_mats && dmessages && dh && dtype_mats && workspace, "null pointer");
-  if (workspace_bytes < impnn_bmm_message_typed_bwd_workspace_bytes(B, E, Vb))
-    return fail(IMPNN_E_WORKSPACE, "bmm_message_typed_bwd: workspace of %lld bytes is too small", (long long)workspace_bytes);
-  return launch_bmm_message_typed_bwd(h, bond_ids, conn, type_mats, dmessages, dh, dtype_mats,
-                                      static_cast<int32_t*>(workspace), B, N, E, D, Vb, sorted_ready != 0, 0,
-                                      as_stream(stream));
+  TypedMessageCall c = typed_message(__func__, h, bond_ids, conn, type_mats, workspace, workspace_bytes, B, N, E, D, Vb,
+                                     sorted_ready, stream);
+  c.grad = dmessages, c.dh = dh, c.dtype_mats = dtype_mats;
+  return typed_message_checked(c, dmessages && dh && dtype_mats, launch_bmm_message_typed_bwd);
 }
 
 int impnn_message_reduce_typed_bwd(const float* h, const int32_t* bond_ids, const int32_t* conn,
                                    const float* type_mats, const float* dagg, float* dh, float* dtype_mats,
                                    void* workspace, int64_t workspace_bytes, int32_t B, int32_t N, int32_t E, int32_t D,
                                    int32_t Vb, int32_t sorted_ready, impnn_stream_t stream) {
-  REQUIRE(B >= 0 && N > 0 && E >= 0 && D > 0 && Vb > 0, "bad shape");
-  if (B == 0 || E == 0) return IMPNN_OK;
-  REQUIRE(h && bond_ids && conn && type_mats && dagg && dh && dtype_mats && workspace, "null pointer");
-  if (workspace_bytes < impnn_bmm_message_typed_bwd_workspace_bytes(B, E, Vb))
-    return fail(IMPNN_E_WORKSPACE, "message_reduce_typed_bwd: workspace of %lld bytes is too small",
-                (long long)workspace_bytes);
-  return launch_bmm_message_typed_bwd(h, bond_ids, conn, type_mats, dagg, dh, dtype_mats,
-                                      static_cast<int32_t*>(workspace), B, N, E, D, Vb, sorted_ready != 0, 1,
-                                      as_stream(stream));
+  TypedMessageCall c = typed_message(__func__, h, bond_ids, conn, type_mats, workspace, workspace_bytes, B, N, E, D, Vb,
+                                     sorted_ready, stream);
+  c.grad = dagg, c.dh = dh, c.dtype_mats = dtype_mats, c.from_agg = true;
+  return typed_message_checked(c, dagg && dh && dtype_mats, launch_bmm_message_typed_bwd);
 }
 
 int impnn_message_reduce_typed_bwd_scratch(const float* h, const int32_t* bond_ids, const int32_t* conn,
@@ -721,15 +734,10 @@ int impnn_message_reduce_typed_bwd_scratch(const float* h, const int32_t* bond_i
                                            void* workspace, int64_t workspace_bytes, float* edge_scratch, int32_t B,
                                            int32_t N, int32_t E, int32_t D, int32_t Vb, int32_t sorted_ready,
                                            impnn_stream_t stream) {
-  REQUIRE(B >= 0 && N > 0 && E >= 0 && D > 0 && Vb > 0, "bad shape");
-  if (B == 0 || E == 0) return IMPNN_OK;
-  REQUIRE(h && bond_ids && conn && type_mats && dagg && dh && dtype_mats && workspace && edge_scratch, "null pointer");
-  if (workspace_bytes < impnn_bmm_message_typed_bwd_workspace_bytes(B, E, Vb))
-    return fail(IMPNN_E_WORKSPACE, "message_reduce_typed_bwd_scratch: workspace of %lld bytes is too small",
-                (long long)workspace_bytes);
-  return launch_bmm_message_typed_bwd(h, bond_ids, conn, type_mats, dagg, dh, dtype_mats,
-                                      static_cast<int32_t*>(workspace), B, N, E, D, Vb, sorted_ready != 0, 1,
-                                      as_stream(stream), edge_scratch);
+  TypedMessageCall c = typed_message(__func__, h, bond_ids, conn, type_mats, workspace, workspace_bytes, B, N, E, D, Vb,
+                                     sorted_ready, stream);
+  c.grad = dagg, c.dh = dh, c.dtype_mats = dtype_mats, c.from_agg = true, c.edge_scratch = edge_scratch;
+  return typed_message_checked(c, dagg && dh && dtype_mats && edge_scratch, launch_bmm_message_typed_bwd);
 }
 
 int impnn_bond_type_matrices_bwd(const float* bond_table, const float* W, const float* dtype_mats, float* dW,

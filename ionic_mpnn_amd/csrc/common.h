@@ -160,6 +160,37 @@ int with_dropout_pack(const GatedUpdateCall& c, F&& f) {
   return c.dropout ? f(c.drop) : f();
 }
 
+// ---- one typed-message call (include/impnn.h: impnn_bmm_message_typed_sorted, impnn_bmm_message_typed_bwd,
+// impnn_message_reduce_typed_bwd[_scratch]).  api.hip fills it from the entry's arguments and checks it; the
+// launchers (message_typed.hip) read it.
+constexpr int kMaxTypes = 4096;  // bond types the family's kernels cover (their LDS histograms); also D <= 128
+struct TypedMessageCall {
+  const char* entry;  // the exported entry, named by the error text
+  const float* h;
+  const int32_t *bond_ids, *conn;
+  const float* type_mats;
+  float* messages;            // forward
+  const float* grad;          // backward: of the messages (B,E,D), or with from_agg of Reduce's output (B,N,D)
+  float *dh, *dtype_mats;     // backward: added into
+  float* edge_scratch;        // backward, optional (B,E,D): per-edge vectors summed into dh in slot order, no atomics on dh
+  void* workspace;            // the edge sort (EdgeSortView)
+  int64_t workspace_bytes;
+  int B, N, E, D, Vb;
+  bool sort_ready;       // the workspace holds this batch's sort (an earlier call of the pass made it)
+  bool zero_rows_ready;  // forward: `messages` still holds the zero rows of an earlier call on this batch
+  bool from_agg;         // backward: `grad` is read at every edge's target row
+  hipStream_t stream;
+};
+
+// The sort workspace (int32): cnt Vb+1 | start Vb+1 | cursor Vb+1 | segbase Vb+1 | order B*E
+// (bmm_message_typed_bwd_workspace_ints).
+struct EdgeSortView {
+  int32_t *cnt, *start, *cursor, *segbase, *order;
+  EdgeSortView(void* workspace, int Vb)
+      : cnt(static_cast<int32_t*>(workspace)), start(cnt + Vb + 1), cursor(start + Vb + 1), segbase(cursor + Vb + 1),
+        order(segbase + Vb + 1) {}
+};
+
 // ---- layer-at-a-time launches (layer_kernels.hip)
 int launch_embed_gather(const int32_t* ids, const float* table, float* out, int64_t rows, int vocab,
                         int dim, hipStream_t s);
@@ -221,19 +252,18 @@ int launch_model_head(int kind, const float* pc, const float* pa, const float* T
 int launch_validate_indices(const int32_t* conn, const int32_t* atom_ids, const int32_t* bond_ids,
                             int32_t* counts, int B, int N, int E, int Va, int Vb, hipStream_t s);
 
-// ---- backward + optimizer (train_kernels.hip)
+// ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
+int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
+int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)
+int launch_bmm_message_typed_bwd(const TypedMessageCall& c);     // a checked call (api.hip)
+
+// ---- backward + optimizer (train_kernels.hip): embedding / pool / Reduce adjoints, bond-table gradient, GatedUpdate
+// backward, dropout step, Adam, model head
 int launch_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable, int64_t rows, int vocab, int dim,
                             hipStream_t s);
 int launch_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int tgt_stride, float* dm, int B, int N, int E,
                               int D, hipStream_t s);
 int launch_global_sum_pool_bwd(const float* dp, const int32_t* ids, float* dh, int B, int N, int D, hipStream_t s);
-int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
-int launch_bmm_message_typed_sorted(const float* h, const int32_t* bond_ids, const int32_t* conn, const float* A,
-                                    float* m, int32_t* workspace, int B, int N, int E, int D, int Vb, int sorted_ready,
-                                    hipStream_t s);
-int launch_bmm_message_typed_bwd(const float* h, const int32_t* bond_ids, const int32_t* conn, const float* A,
-                                 const float* dm, float* dh, float* dA, int32_t* workspace, int B, int N, int E,
-                                 int D, int Vb, int sorted_ready, int from_agg, hipStream_t s, float* du = nullptr);
 int launch_strided_gemm(const float* A, const float* B, float* out, int64_t rows, int M, int N, int64_t a_rs,
                         int64_t a_cs, int64_t b_rs, int64_t b_cs, hipStream_t s);
 int launch_bond_type_matrices_multi(const float* tb, const float* const* W, float* const* out, int n, int Vb, int K,

@@ -355,3 +355,69 @@ def test_gated_update_status_codes_are_pinned():
         assert fn(*args) == want, (entry, kw)
         if what is not None:
             assert what in lib.impnn_last_error_string(), (entry, kw)
+
+
+# ---- the typed-message family's argument rules, pinned entry by entry (recorded on the entries as they were before
+# their checks were shared).  Every call returns before any device call: pointers that must not be null are addresses
+# inside a host buffer, and no case lets them be dereferenced.
+_TM_GRAD = ["h", "bond_ids", "conn", "type_mats", "grad", "dh", "dtype_mats", "workspace", "workspace_bytes"]
+_TM_SHAPE = ["B", "N", "E", "D", "Vb", "sorted_ready"]
+_TM_PARAMS = {
+    "impnn_bmm_message_typed_sorted": ["h", "bond_ids", "conn", "type_mats", "messages", "workspace", "workspace_bytes"]
+                                      + _TM_SHAPE,
+    "impnn_bmm_message_typed_bwd": _TM_GRAD + _TM_SHAPE,
+    "impnn_message_reduce_typed_bwd": _TM_GRAD + _TM_SHAPE,
+    "impnn_message_reduce_typed_bwd_scratch": _TM_GRAD + ["edge_scratch"] + _TM_SHAPE,
+}
+_TM_POINTERS = ("h", "bond_ids", "conn", "type_mats", "messages", "grad", "dh", "dtype_mats", "workspace", "edge_scratch")
+
+
+def test_typed_message_status_codes_are_pinned():
+    """Status code and error text of the four typed-message entries for each class of refusal, in the order the rules
+    apply: shape, zero work, null pointers, workspace size, coverage (Vb, then D)."""
+    lib = _lib.load()
+    host = (C.c_char * 256)()
+    at = C.addressof(host)  # 16-byte steps inside the buffer: distinct, never dereferenced
+    ptrs = {n: at + 16 * (i + 1) for i, n in enumerate(_TM_POINTERS)}
+    nulls = {n: None for n in _TM_POINTERS}
+    need = lib.impnn_bmm_message_typed_bwd_workspace_bytes
+
+    def call(entry, **kw):
+        args = dict(ptrs, B=3, N=7, E=11, D=64, Vb=5, sorted_ready=0)
+        args.update(kw)
+        args.setdefault("workspace_bytes", 1 << 40)
+        fn = getattr(lib, entry)
+        row = [args[n] for n in _TM_PARAMS[entry]] + [None]
+        assert len(row) == len(fn.argtypes), entry
+        return fn(*row), lib.impnn_last_error_string()
+
+    assert set(_TM_PARAMS) == {n for n in _lib.SIGNATURES if "message" in n and "typed_" in n and not n.endswith("_bytes")}
+    for entry, names in _TM_PARAMS.items():
+        short = entry[len("impnn_"):].encode()
+        # 1. shape, before everything else
+        for kw in (dict(N=0), dict(N=0, B=0, **nulls), dict(B=-1), dict(E=-1), dict(D=0), dict(Vb=0)):
+            rc, msg = call(entry, **kw)
+            assert rc == _BAD and b"bad shape" in msg and short in msg, (entry, kw, msg)
+        # 2. zero work is a success with no pointer looked at
+        for kw in (dict(B=0), dict(E=0), dict(B=0, E=0)):
+            assert call(entry, workspace_bytes=0, **nulls, **kw)[0] == 0, (entry, kw)
+        # 3. null pointers: all of them, each one alone, and before the workspace size
+        for kw in [dict(nulls), dict(nulls, workspace_bytes=0)] + [{n: None} for n in names if n in _TM_POINTERS]:
+            rc, msg = call(entry, **kw)
+            assert rc == _BAD and b"null pointer" in msg and short in msg, (entry, kw, msg)
+        # 4. a workspace one byte short, before the coverage rules
+        for kw in (dict(), dict(Vb=4097), dict(D=129), dict(B=1, E=1, Vb=1)):
+            args = dict(B=3, E=11, Vb=5)
+            args.update(kw)
+            size = need(args["B"], args["E"], args["Vb"])
+            assert size == 4 * (4 * (args["Vb"] + 1) + args["B"] * args["E"])
+            rc, msg = call(entry, workspace_bytes=size - 1, **kw)
+            assert rc == _WS and b"too small" in msg and short in msg, (entry, kw, msg)
+        # 5. coverage: more than 4096 bond types, then atom_dim above 128 (the claimed workspace is large enough)
+        for kw, what in ((dict(Vb=4097), b"Vb=4097"), (dict(D=129), b"D=129"), (dict(Vb=4097, D=129), b"Vb=4097")):
+            rc, msg = call(entry, **kw)
+            assert rc == _UNS and what in msg, (entry, kw, msg)
+            rc, msg = call(entry, workspace_bytes=need(3, 11, kw.get("Vb", 5)), **kw)  # exactly enough
+            assert rc == _UNS and what in msg, (entry, kw, msg)
+    rc, msg = call("impnn_message_reduce_typed_bwd_scratch", edge_scratch=None)
+    assert rc == _BAD and b"null pointer" in msg

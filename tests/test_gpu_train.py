@@ -73,7 +73,7 @@ def test_message_reduce_backward(D, K, B, E):
 
 @pytest.mark.parametrize("D,Vb,from_agg,B", [(128, 12, True, 700), (64, 72, True, 700), (128, 3, False, 700), (128, 72, True, 32), (64, 9, True, 200)])
 def test_message_backward_on_the_matrix_cores_equals_the_valu_kernel(D, Vb, from_agg, B):
-    """Wide states take bmm_message_typed_bwd_mfma_kernel (csrc/train_kernels.hip): same gradients as the VALU kernel
+    """Wide states take bmm_message_typed_bwd_mfma_kernel (csrc/message_typed.hip): same gradients as the VALU kernel
     (IMPNN_MESSAGE_BWD=valu) on a batch whose type runs span several segments and several workgroup ranges - types
     change inside a workgroup's range, last segments of a type are partial.  (Both kernels add into dh / dA with
     float atomics: equal up to the order of f32 additions.)"""

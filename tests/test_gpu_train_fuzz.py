@@ -9,7 +9,7 @@ fp32 to the same bounds against grad_ref in fp64: the bounds are attainable by a
 these inputs.
 
 How a case is mapped to a branch: the tables below name, per case, the branch it is meant for; ``message_branch``
-restates the dispatch of launch_edge_type_sort / launch_bmm_message_typed_bwd (csrc/train_kernels.hip) from the
+restates the dispatch of launch_edge_type_sort / launch_bmm_message_typed_bwd (csrc/message_typed.hip) from the
 shape, with the constants named, and every case asserts that the restatement gives the branch its row claims.  Whole
 model seeds 0-7 sit exactly on the two thresholds of the training pass (autograd.MESSAGE_BWD_EDGE_BUFFER_MIN_SLOTS,
 model.TRAIN_ROW_LIST_MIN_ROWS), one side per ion."""
