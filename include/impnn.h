@@ -322,6 +322,28 @@ int impnn_model_head(int32_t kind, const float* pooled_cat, const float* pooled_
                      const float* temperature, const float* head_weights, float* out, int32_t B,
                      int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
 
+/* ---- f1 over a Cartesian product: C cations x A anions (x nT temperatures) from C + A encoder rows.  An ion's branch
+ *      meets its partner only at AddTwoTensors / Add, so the head splits in two (replaces train_viscosity.py:189,197-214
+ *      and train_melting_point.py:173,191-198 evaluated on every pair of a screen).  Both entries read the packed
+ *      head_weights of impnn_model_head (impnn_model_head_floats); D <= 128, F, Mx <= 64.
+ *      impnn_head_ion_mix: ion 0 = cation, 1 = anion; pooled (M,D) ->
+ *        mix[m,:] = relu(relu(pooled[m] Wfp_g + bfp_g) Wp_g + bp_g)   (M,Mx), the per-ion half of impnn_model_head.
+ *      impnn_head_grid: mixed = mix_cat[i] + mix_an[j] (the cation term first), then the tail of impnn_model_head.
+ *        kind 0: temperatures (nT) in kelvin, 1 <= nT <= 4096; out (C,A,nT) row-major; params NULL or (C,A,3), which
+ *                receives the VFT parameters (A, B, C) of every pair (the reference's SliceParamA/B/C outputs).
+ *        kind 1: out (C,A); temperatures and params NULL, nT 0.
+ *      Element (i,j,t) has the bits impnn_model_head returns for the single sample (pooled_cat[i], pooled_an[j],
+ *      T[t]): the same fmaf chains (bias first, inputs ascending), no atomics.  One difference, on non-finite input
+ *      only: relu here keeps a NaN (as keras does), so a NaN pooled row gives NaN in exactly its row / column of the
+ *      grid, where impnn_model_head's fmaxf turns it into 0.
+ *      Checks in order: shape (sizes, limits, nT, kind, ion); zero work (M == 0, C == 0 or A == 0: IMPNN_OK, nothing
+ *      touched); null pointers.  C * A * nT may exceed 2^31. */
+int impnn_head_ion_mix(int32_t kind, int32_t ion, const float* pooled, const float* head_weights, float* mix,
+                       int32_t M, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_head_grid(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                    const float* head_weights, float* out, float* params, int32_t C, int32_t A, int32_t nT,
+                    int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+
 /* ---- f1 for training (f4): the same head read from the INDIVIDUAL weight tensors - `weights` is a host array of
  *      device pointers in the order of impnn_model_head's packed layout (10 tensors for kind 0, 12 for kind 1), so a
  *      training step does not re-pack the head after every optimizer update - and its backward in one launch.

@@ -58,6 +58,8 @@ SIGNATURES = {
                                     i32, i32, i32, i32, f32, vp, vp, sz, vp]),
     "impnn_model_head_floats": (i64, [i32, i32, i32, i32]),
     "impnn_model_head": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "impnn_head_ion_mix": (C.c_int, [i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "impnn_head_grid": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "impnn_model_head_tensors": (C.c_int, [i32, vp, vp, vp, PP, vp, i32, i32, i32, i32, vp]),
     "impnn_model_head_bwd": (C.c_int, [i32, vp, vp, vp, PP, vp, vp, vp, PP, i32, i32, i32, i32, vp]),
     "impnn_model_head_loss_workspace_floats": (i64, [i32]),

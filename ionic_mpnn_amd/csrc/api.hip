@@ -532,6 +532,44 @@ int impnn_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float
                                dweights, B, D, F, Mx, as_stream(stream), l2, y, dloss);
 }
 
+// ---- the head over a cation x anion grid (include/impnn.h; head_grid.hip).  The family's order: shape, zero work,
+// null pointers.
+namespace {
+int head_grid_dims(const char* entry, int D, int F, int Mx) {
+  if (D > 128 || F > 64 || Mx > 64)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= 128) F=%d Mx=%d (<= 64)", entry, D, F, Mx);
+  return IMPNN_OK;
+}
+}  // namespace
+
+int impnn_head_ion_mix(int32_t kind, int32_t ion, const float* pooled, const float* head_weights, float* mix, int32_t M,
+                       int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
+  REQUIRE(ion == 0 || ion == 1, "ion must be 0 (cation) or 1 (anion)");
+  REQUIRE(M >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  if (int rc = head_grid_dims(__func__, D, F, Mx)) return rc;
+  if (M == 0) return IMPNN_OK;
+  REQUIRE(pooled && head_weights && mix, "null pointer");
+  return launch_head_ion_mix(kind, ion, pooled, head_weights, mix, M, D, F, Mx, as_stream(stream));
+}
+
+int impnn_head_grid(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                    const float* head_weights, float* out, float* params, int32_t C, int32_t A, int32_t nT, int32_t D,
+                    int32_t F, int32_t Mx, impnn_stream_t stream) {
+  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
+  REQUIRE(C >= 0 && A >= 0 && nT >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE(kind == 1 || nT >= 1, "the viscosity grid needs nT >= 1 temperatures");
+  REQUIRE(kind == 0 || nT == 0, "the melting-point grid takes no temperatures: nT must be 0");
+  if (int rc = head_grid_dims(__func__, D, F, Mx)) return rc;
+  if (nT > head_grid_max_temperatures())
+    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", __func__, nT, head_grid_max_temperatures());
+  if (C == 0 || A == 0) return IMPNN_OK;
+  REQUIRE(mix_cat && mix_an && head_weights && out && (kind == 1 || temperatures), "null pointer");
+  REQUIRE(kind == 0 || (!temperatures && !params), "the melting-point grid takes neither temperatures nor params");
+  return launch_head_grid(kind, mix_cat, mix_an, temperatures, head_weights, out, params, C, A, nT, D, F, Mx,
+                          as_stream(stream));
+}
+
 // ---- the transfer head (include/impnn.h; transfer_head.hip)
 int64_t impnn_transfer_head_saved_floats(int32_t B, int32_t F, int32_t Mx) {
   return B > 0 && F > 0 && Mx > 0 ? transfer_head_saved_floats(B, F, Mx) : -1;

@@ -252,6 +252,14 @@ int launch_model_head(int kind, const float* pc, const float* pa, const float* T
 int launch_validate_indices(const int32_t* conn, const int32_t* atom_ids, const int32_t* bond_ids,
                             int32_t* counts, int B, int N, int E, int Va, int Vb, hipStream_t s);
 
+// ---- the head over a cation x anion grid (head_grid.hip; include/impnn.h, impnn_head_ion_mix / impnn_head_grid).
+// api.hip checks the arguments; `w` is the packed head of impnn_model_head.
+int launch_head_ion_mix(int kind, int ion, const float* pooled, const float* w, float* mix, int M, int D, int F, int Mx,
+                        hipStream_t s);
+int head_grid_max_temperatures();
+int launch_head_grid(int kind, const float* mix_cat, const float* mix_an, const float* T, const float* w, float* out,
+                     float* params, int C, int A, int nT, int D, int F, int Mx, hipStream_t s);
+
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)

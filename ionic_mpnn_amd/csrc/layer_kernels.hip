@@ -7,6 +7,7 @@
 //
 // Reference lines each kernel follows are cited at the kernel.
 #include "common.h"
+#include "head_device.h"
 
 namespace impnn {
 
@@ -1249,8 +1250,6 @@ __global__ void validate_indices_kernel(const int32_t* conn, const int32_t* atom
 constexpr int kHeadMaxDim = 64;   // fp_size, mixing_size
 constexpr int kHeadMaxX = 128;    // pooled width (atom_dim 128: train_viscosity.py with a wider encoder)
 
-__device__ __forceinline__ float softplus_exact(float x) { return x > 20.f ? x + log1pf(expf(-x)) : log1pf(expf(x)); }
-
 // 8 samples per 256-thread workgroup, 32 threads per sample: thread (s, jj) owns outputs jj, jj+32 of
 // every layer; the sample's vectors and all weights sit in LDS (13.6 KB of weights at the defaults).
 constexpr int kHeadSPB = 8;
@@ -1305,9 +1304,7 @@ __global__ __launch_bounds__(256) void model_head_kernel(int kind, const float* 
     __syncthreads();
     if (jj == 0 && live) {
       const float* vp = hid + sl * kHeadMaxDim;
-      const float Bc = fminf(fmaxf(softplus_exact(vp[1]), 0.f), 20.f);
-      const float Cc = fminf(fmaxf(softplus_exact(vp[2]), 0.1f), 50.f);
-      out[b] = vp[0] + Bc / (T[b] / 100.0f + Cc + 1e-6f);
+      out[b] = head_vft_eval(head_vft_params(vp[0], vp[1], vp[2]), head_scaled_t(T[b]));  // head_device.h
     }
   } else {
     const float* Wh = wt;

@@ -33,6 +33,66 @@ TWO_STREAM_MAX_BATCH = 4096
 TRAIN_ROW_LIST_MIN_ROWS = int(os.environ.get("IMPNN_TRAIN_ROW_LIST_MIN_ROWS", 4096))
 
 
+ION_KEYS = ("atom", "bond", "connectivity")
+# predict_grid: elements of `out` one launch may write (1 GiB of float32); above it the cation axis is tiled on the host
+GRID_OUTPUT_BUDGET = 1 << 28
+GRID_MAX_TEMPERATURES = 4096   # temperatures per impnn_head_grid launch (include/impnn.h)
+GRID_GATHER_PAIRS = 1 << 18    # pairs per tile of the gathered path (widths above 64, the transfer head)
+
+
+def _ion_numpy(ion, what):
+    """One species dict {"atom" (M,N), "bond" (M,E), "connectivity" (M,E,2)} as int32 numpy arrays."""
+    if not isinstance(ion, dict) or any(k not in ion for k in ION_KEYS):
+        raise KeyError(f"{what} must be a dict with the keys {ION_KEYS}")
+    out = []
+    for k in ION_KEYS:
+        v = ion[k]
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        out.append(np.ascontiguousarray(np.asarray(v), dtype=np.int32))
+    a, b, c = out
+    if a.ndim != 2 or b.ndim != 2 or c.ndim != 3 or c.shape[2] != 2 or len({len(a), len(b), len(c)}) != 1 \
+            or b.shape[1] != c.shape[1]:
+        raise ValueError(f"{what}: atom (M,N), bond (M,E), connectivity (M,E,2) expected, got {a.shape}, {b.shape}, "
+                         f"{c.shape}")
+    return a, b, c
+
+
+def ion_pair_batches(cations=None, anions=None, batch_size=4096):
+    """The pair batches ``MPNNModel.encode_ions`` feeds to ``encode_pooled``: species lists -> (batches, C, A).
+
+    Both sides are zero-padded to a common (N, E) - atom id 0, bond id 0 and [0, 0] edges are padding everywhere in
+    the model - and to R = max(C, A) rows; the shorter or absent side is filled with all-padding molecules.  Row r of
+    the batches holds cation r (r < C) and anion r (r < A); ``batches`` is a list of model input dicts (numpy int32,
+    no temperature) of at most ``batch_size`` rows, in row order."""
+    if cations is None and anions is None:
+        raise ValueError("encode_ions needs cations, anions or both")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    sides = [None if x is None else _ion_numpy(x, w) for x, w in ((cations, "cations"), (anions, "anions"))]
+    given = [s for s in sides if s is not None]
+    N = max(s[0].shape[1] for s in given)
+    E = max(s[1].shape[1] for s in given)
+    counts = [0 if s is None else len(s[0]) for s in sides]
+    R = max(counts)
+    padded = []
+    for s in sides:
+        atom, bond, conn = np.zeros((R, N), np.int32), np.zeros((R, E), np.int32), np.zeros((R, E, 2), np.int32)
+        if s is not None:
+            m = len(s[0])
+            atom[:m, :s[0].shape[1]], bond[:m, :s[1].shape[1]], conn[:m, :s[2].shape[1]] = s
+        padded.append((atom, bond, conn))
+    batches = []
+    for lo in range(0, R, batch_size):
+        b = {}
+        for p, arrs in zip(("cat", "an"), padded):
+            for k, arr in zip(ION_KEYS, arrs):
+                b[f"{p}_{k}"] = arr[lo:lo + batch_size]
+        batches.append(b)
+    return batches, counts[0], counts[1]
+
+
 class MPNNModel:
     def __init__(self, kind, atom_vocab_size, bond_vocab_size, atom_dim, bond_dim, fp_size, mixing_size,
                  num_steps, fp_l2, device=None, name=None, dropout_rate=0.0, dropout_seed=None,
@@ -922,6 +982,106 @@ class MPNNModel:
         for o in outs:
             o.record_stream(cur)
         return torch.cat(outs, dim=0).cpu().numpy()
+
+    # ------------------------------------------------------------------ screening: one encoder row per ion species
+    def encode_ions(self, cations=None, anions=None, batch_size=4096):
+        """GlobalSumPool rows of ion species on their own: ``cations`` / ``anions`` are dicts {"atom" (M,N), "bond"
+        (M,E), "connectivity" (M,E,2)} of numpy arrays or torch tensors, or None -> (pooled_cat (C,D) | None,
+        pooled_an (A,D) | None) on the model's device.  Goes through ``encode_pooled`` on the pair batches of
+        ``ion_pair_batches`` (so: the resolved encoder mode, prepared weights, the overflow fallback, the wide and
+        layered paths), ``batch_size`` rows at a time; the padding rows are dropped.  Inference only: no graph, no
+        dropout."""
+        batches, C, A = ion_pair_batches(cations, anions, batch_size)
+        parts = []
+        with torch.no_grad():
+            for b in batches:
+                inp = {k: torch.from_numpy(v).to(self.device, non_blocking=True) for k, v in b.items()}
+                parts.append(self.encode_pooled(inp))
+        out = []
+        for g, (given, n) in enumerate(((cations, C), (anions, A))):
+            if given is None:
+                out.append(None)
+            elif not parts:
+                out.append(torch.zeros(0, self.atom_dim, dtype=torch.float32, device=self.device))
+            else:
+                out.append(torch.cat([p[g] for p in parts], dim=0)[:n].contiguous())
+        return out[0], out[1]
+
+    def _grid_kernels_cover(self):
+        return self.kind != "transfer" and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
+
+    def predict_grid(self, cations, anions, temperatures=None, return_params=False, max_pairs_per_launch=None,
+                     batch_size=4096):
+        """Every cation x anion pair (x temperature) of a screen from C + A encoder rows: ``encode_ions``, the
+        per-ion half of the head once per species (impnn_head_ion_mix), then one impnn_head_grid launch over the
+        product.  Viscosity: ``temperatures`` (nT) in kelvin -> numpy (C,A,nT), with ``return_params`` also the VFT
+        parameters (C,A,3) = (A, B, C) of every pair; melting point and transfer: numpy (C,A).  Element [i,j,t] has
+        the bits ``predict`` gives for the pair (cation i, anion j, T[t]) from the same pooled rows.
+        ``max_pairs_per_launch`` tiles the cation axis on the host; the default keeps one launch's output within
+        GRID_OUTPUT_BUDGET elements (1 GiB of float32); ``batch_size``: rows per encoder launch.  Widths the head kernels do not cover (fp_size or mixing_size
+        above 64) and the transfer model evaluate ``self.head`` on gathered tiles of pairs instead."""
+        if self.kind == "viscosity" and temperatures is None:
+            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
+        if return_params and self.kind != "viscosity":
+            raise ValueError(f"return_params: the {self.kind} model has no VFT parameters")
+        if cations is None or anions is None:
+            raise ValueError("predict_grid needs both cations and anions")
+        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
+            raise ValueError("max_pairs_per_launch must be >= 1")
+        visc = self.kind == "viscosity"
+        T = None
+        if visc:
+            T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
+            T = T.to(torch.float32).reshape(-1)
+            if T.numel() == 0:
+                raise ValueError("temperatures must hold at least one value")
+        pc, pa = self.encode_ions(cations, anions, batch_size)
+        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
+        out = np.empty((C, A, nT) if visc else (C, A), np.float32)
+        params = np.empty((C, A, 3), np.float32) if return_params else None
+        if C == 0 or A == 0:
+            return (out, params) if return_params else out
+        covered = self._grid_kernels_cover()
+        if max_pairs_per_launch is None:
+            max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
+            if not covered:
+                max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
+        rows = max(1, int(max_pairs_per_launch) // A)
+        with torch.no_grad():
+            if visc:
+                T = T.to(self.device)
+            if covered:
+                w = self._packed_head()
+                mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
+                ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
+            for lo in range(0, C, rows):
+                hi = min(C, lo + rows)
+                if not covered:
+                    out[lo:hi] = self._grid_gathered(pc[lo:hi], pa, T).cpu().numpy()
+                elif not visc:
+                    out[lo:hi] = ops.head_grid(self.kind, mc[lo:hi], ma, None, w, self.fp_size,
+                                               self.mixing_size).cpu().numpy()
+                else:
+                    for t0 in range(0, nT, GRID_MAX_TEMPERATURES):
+                        t1 = min(nT, t0 + GRID_MAX_TEMPERATURES)
+                        got = ops.head_grid(self.kind, mc[lo:hi], ma, T[t0:t1], w, self.fp_size, self.mixing_size,
+                                            return_params=return_params and t0 == 0)
+                        if return_params and t0 == 0:
+                            got, pr = got
+                            params[lo:hi] = pr.cpu().numpy()
+                        out[lo:hi, :, t0:t1] = got.cpu().numpy()
+        return (out, params) if return_params else out
+
+    def _grid_gathered(self, pc, pa, T):
+        """``self.head`` on the explicit pairs of a tile of cations x all anions (x T) -> (c, A[, nT])."""
+        c, A, nT = int(pc.shape[0]), int(pa.shape[0]), (int(T.numel()) if T is not None else 1)
+        D = pc.shape[1]
+        pcg = pc[:, None, None, :].expand(c, A, nT, D).reshape(-1, D).contiguous()
+        pag = pa[None, :, None, :].expand(c, A, nT, D).reshape(-1, D).contiguous()
+        if T is None:
+            return self.head(pcg, pag).reshape(c, A)
+        return self.head(pcg, pag, T[None, None, :].expand(c, A, nT).reshape(-1, 1).contiguous()).reshape(c, A, nT)
 
     def _to_device(self, inputs):
         out = {}

@@ -702,6 +702,70 @@ def model_head(kind, pooled_cat, pooled_an, temperature, head_weights, fp_size, 
     return out
 
 
+HEAD_KINDS = {"viscosity": 0, "melting_point": 1}
+
+
+def head_ion_mix(kind, ion, pooled, head_weights, fp_size, mixing_size):
+    """The per-ion half of the head (impnn_head_ion_mix): ``ion`` "cat" / 0 or "an" / 1, pooled (M,D) ->
+    relu(relu(pooled Wfp + bfp) Wp + bp) (M,Mx), from the packed head weights of ``model_head``."""
+    require_gpu(pooled, head_weights)
+    pooled, head_weights = f32c(pooled), f32c(head_weights)
+    if pooled.dim() != 2:
+        raise ValueError(f"pooled must be (M,D), got {tuple(pooled.shape)}")
+    M, D = pooled.shape
+    k = HEAD_KINDS[kind]
+    g = {"cat": 0, "an": 1, 0: 0, 1: 1}[ion]
+    lib = _lib.load()
+    if head_weights.numel() != lib.impnn_model_head_floats(k, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+    mix = torch.empty(M, mixing_size, dtype=torch.float32, device=pooled.device)
+    with torch.cuda.device(pooled.device):
+        check(lib.impnn_head_ion_mix(k, g, ptr(pooled), ptr(head_weights), ptr(mix), M, D, fp_size, mixing_size,
+                                     stream_ptr()))
+    return mix
+
+
+def head_grid(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, return_params=False):
+    """The head on every cation x anion pair in one launch (impnn_head_grid), from ``head_ion_mix`` rows.
+    "viscosity": temperatures (nT) in kelvin -> (C,A,nT), with return_params also the VFT parameters (C,A,3);
+    "melting_point": temperatures None -> (C,A).  Element (i,j,t) has the bits of ``model_head`` on that sample."""
+    require_gpu(mix_cat, mix_an, head_weights)
+    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
+    k = HEAD_KINDS[kind]
+    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
+        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
+                         f"and {tuple(mix_an.shape)}")
+    if return_params and k != 0:
+        raise ValueError("return_params: only the viscosity head has VFT parameters")
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    lib = _lib.load()
+    # the packed length depends on D through the per-ion part only: recover D from it
+    per_d = 2 * fp_size
+    rest = lib.impnn_model_head_floats(k, 1, fp_size, mixing_size) - per_d
+    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
+    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(k, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+    dev = mix_cat.device
+    T, nT = None, 0
+    if k == 0:
+        if temperatures is None:
+            raise ValueError("the viscosity grid needs temperatures")
+        require_gpu(temperatures)
+        T = f32c(temperatures).reshape(-1)
+        nT = int(T.numel())
+        out = torch.empty(C_, A_, nT, dtype=torch.float32, device=dev)
+    else:
+        if temperatures is not None:
+            raise ValueError("the melting-point grid takes no temperatures")
+        out = torch.empty(C_, A_, dtype=torch.float32, device=dev)
+    params = torch.empty(C_, A_, 3, dtype=torch.float32, device=dev) if return_params else None
+    with torch.cuda.device(dev):
+        check(lib.impnn_head_grid(k, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None, ptr(head_weights),
+                                  ptr(out), ptr(params) if params is not None else None, C_, A_, nT, D, fp_size,
+                                  mixing_size, stream_ptr()))
+    return (out, params) if return_params else out
+
+
 def transfer_head(pooled_cat, pooled_an, weights, cfg):
     """The transfer model's head in inference, one launch (impnn_transfer_head): ``weights`` the 18 tensors in the
     order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg -> (B,1)."""
