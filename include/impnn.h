@@ -479,6 +479,33 @@ int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an
                                  float* workspace, int64_t workspace_floats, float* dpooled_cat, float* dpooled_an,
                                  int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
 
+/* ---- the transfer head over a Cartesian product: C cations x A anions from C + A encoder rows, on the matrix cores.
+ *      mix = relu(proj_cat) + relu(proj_an) is a sum and mp_dense_1 is linear in it before its relu, so
+ *        a1[i,j] = relu(u_cat[i] + u_an[j]),  u_cat = mix_cat W1 (C,256),  u_an = mix_an W1 + b1 (A,256)
+ *      (replaces train_melting_point_transfer.py:95-103 evaluated on every pair of a screen).  Inference semantics as
+ *      impnn_transfer_head: moving statistics, no Dropout.  `weights`: the HOST array of 18 device pointers above.
+ *      impnn_transfer_grid_prepare: W2, W3 in the operand order of v_mfma_f32_32x32x2_f32, BatchNormalization as
+ *        scale = gamma / sqrt(moving_var + bn_eps), shift = beta - moving_mean * scale, then b2, b3, Wo, bo -> `image`
+ *        (impnn_transfer_grid_image_floats() floats, 16B aligned).  Once per weight version; one small launch.
+ *      impnn_transfer_ion_half: ion 0 = cation, 1 = anion; pooled (M,D) ->
+ *        u[m,:] = relu(relu(pooled[m] Wfp_g + bfp_g) Wp_g + bp_g) W1 (+ b1 for the anion: the bias enters once)  (M,256).
+ *      impnn_transfer_head_grid: out[i,j] = Dense1(relu(Dense64(relu(Dense128(bn(relu(u_cat[i] + u_an[j])))))))  (C,A)
+ *        row-major; u_cat (C,256), u_an (A,256) and the image 16B aligned, `out` at any 4-byte alignment.  Exact f32
+ *        products (a k-ordered fmaf chain per output); against impnn_transfer_head only the order of the sums and the
+ *        factored first layer differ.  Element (i,j) depends on u_cat[i], u_an[j] and the image only - not on C, A, the
+ *        position in the grid or the launch - and is reproducible bit for bit; no atomics.  relu keeps a NaN (as keras
+ *        does), so a NaN u row gives NaN in exactly its row / column of the grid.
+ *      Checks in order: shape (ion, sizes >= 0, widths > 0, bn_eps >= 0; IMPNN_E_BADARG); zero work (M == 0, C == 0 or
+ *      A == 0: IMPNN_OK, nothing touched); null pointers, then alignment (IMPNN_E_BADARG) and image_floats below the
+ *      query (IMPNN_E_WORKSPACE); the ranges D <= 128, F, Mx <= 64 (IMPNN_E_UNSUPPORTED).  C * A may exceed 2^31. */
+int64_t impnn_transfer_grid_image_floats(void);
+int impnn_transfer_grid_prepare(const float* const* weights, const float* moving_mean, const float* moving_var,
+                                float bn_eps, float* image, int64_t image_floats, impnn_stream_t stream);
+int impnn_transfer_ion_half(int32_t ion, const float* pooled, const float* const* weights, float* u, int32_t M,
+                            int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                             float* out, int32_t C, int32_t A, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

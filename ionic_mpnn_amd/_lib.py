@@ -74,6 +74,10 @@ SIGNATURES = {
                                  + [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "impnn_transfer_head_loss_bwd": (C.c_int, [vp, vp, PP, PP, C.POINTER(f32), i32, vp, i32, f32, vp] + _DROP
                                      + [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),
+    "impnn_transfer_grid_image_floats": (i64, []),
+    "impnn_transfer_grid_prepare": (C.c_int, [PP, vp, vp, f32, vp, i64, vp]),
+    "impnn_transfer_ion_half": (C.c_int, [i32, vp, PP, vp, i32, i32, i32, i32, vp]),
+    "impnn_transfer_head_grid": (C.c_int, [vp, vp, vp, i64, vp, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

@@ -650,6 +650,76 @@ int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an
   return launch_transfer_head_bwd(c);
 }
 
+// ---- the transfer head over a cation x anion grid (include/impnn.h; transfer_grid.hip).  One place applies the
+// family's rules in their fixed order: shape, zero work, null pointers (then alignment and the image size), ranges.
+namespace {
+struct TransferGridCheck {
+  const char* entry;
+  bool shape_ok;
+  bool zero_work;
+  bool pointers_ok;
+  bool weights_needed;            // the 18-pointer table is read
+  const float* const* weights;
+  bool aligned_ok;
+  int64_t image_floats;           // < 0: the entry takes no image
+  int D, F, Mx;                   // D == 0: the entry takes no widths
+};
+// IMPNN_OK with *launch == false: success with nothing to do
+int transfer_grid_check(const TransferGridCheck& c, bool* launch) {
+  *launch = false;
+  if (!c.shape_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", c.entry);
+  if (c.zero_work) return IMPNN_OK;
+  if (!c.pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", c.entry);
+  if (c.weights_needed)
+    for (int t = 0; t < kThTensors; ++t)
+      if (!c.weights[t]) return fail(IMPNN_E_BADARG, "%s: null weight tensor %d", c.entry, t);
+  if (!c.aligned_ok) return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", c.entry);
+  if (c.image_floats >= 0 && c.image_floats < transfer_grid_image_floats())
+    return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", c.entry, (long long)c.image_floats,
+                (long long)transfer_grid_image_floats());
+  if (c.D > 128 || c.F > 64 || c.Mx > 64)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= 128) F=%d Mx=%d (<= 64)", c.entry, c.D, c.F, c.Mx);
+  *launch = true;
+  return IMPNN_OK;
+}
+}  // namespace
+
+int64_t impnn_transfer_grid_image_floats(void) { return transfer_grid_image_floats(); }
+
+int impnn_transfer_grid_prepare(const float* const* weights, const float* moving_mean, const float* moving_var,
+                                float bn_eps, float* image, int64_t image_floats, impnn_stream_t stream) {
+  TransferGridCheck c{};
+  c.entry = __func__, c.shape_ok = bn_eps >= 0.f && image_floats >= 0;
+  c.pointers_ok = weights && moving_mean && moving_var && image;
+  c.weights_needed = true, c.weights = weights, c.aligned_ok = aligned16(image), c.image_floats = image_floats;
+  bool launch;
+  if (int rc = transfer_grid_check(c, &launch)) return rc;
+  return launch ? launch_transfer_grid_prepare(weights, moving_mean, moving_var, bn_eps, image, as_stream(stream)) : IMPNN_OK;
+}
+
+int impnn_transfer_ion_half(int32_t ion, const float* pooled, const float* const* weights, float* u, int32_t M,
+                            int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  TransferGridCheck c{};
+  c.entry = __func__, c.shape_ok = (ion == 0 || ion == 1) && M >= 0 && D > 0 && F > 0 && Mx > 0;
+  c.zero_work = M == 0, c.pointers_ok = pooled && weights && u;
+  c.weights_needed = true, c.weights = weights, c.aligned_ok = true, c.image_floats = -1;
+  c.D = D, c.F = F, c.Mx = Mx;
+  bool launch;
+  if (int rc = transfer_grid_check(c, &launch)) return rc;
+  return launch ? launch_transfer_ion_half(ion, pooled, weights, u, M, D, F, Mx, as_stream(stream)) : IMPNN_OK;
+}
+
+int impnn_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                             float* out, int32_t C, int32_t A, impnn_stream_t stream) {
+  TransferGridCheck c{};
+  c.entry = __func__, c.shape_ok = C >= 0 && A >= 0 && image_floats >= 0;
+  c.zero_work = C == 0 || A == 0, c.pointers_ok = u_cat && u_an && image && out;
+  c.aligned_ok = aligned16(u_cat) && aligned16(u_an) && aligned16(image), c.image_floats = image_floats;
+  bool launch;
+  if (int rc = transfer_grid_check(c, &launch)) return rc;
+  return launch ? launch_transfer_head_grid(u_cat, u_an, image, out, C, A, as_stream(stream)) : IMPNN_OK;
+}
+
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,
                       const int64_t* rows, int32_t n_rows, impnn_stream_t stream) {
   REQUIRE(n_tensors >= 0 && n_rows >= 0, "bad shape");

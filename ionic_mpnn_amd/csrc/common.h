@@ -260,6 +260,16 @@ int head_grid_max_temperatures();
 int launch_head_grid(int kind, const float* mix_cat, const float* mix_an, const float* T, const float* w, float* out,
                      float* params, int C, int A, int nT, int D, int F, int Mx, hipStream_t s);
 
+// ---- the transfer head over a cation x anion grid (transfer_grid.hip; include/impnn.h, impnn_transfer_grid_prepare /
+// impnn_transfer_ion_half / impnn_transfer_head_grid).  api.hip checks the arguments; `weights`: kThTensors pointers.
+int64_t transfer_grid_image_floats();
+int launch_transfer_grid_prepare(const float* const* weights, const float* moving_mean, const float* moving_var,
+                                 float bn_eps, float* image, hipStream_t s);
+int launch_transfer_ion_half(int ion, const float* pooled, const float* const* weights, float* u, int M, int D, int F,
+                             int Mx, hipStream_t s);
+int launch_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, float* out, int C, int A,
+                              hipStream_t s);
+
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)

@@ -157,6 +157,8 @@ class MPNNModel:
         self._split_deg_limit = None
         self.encoder_mode = "auto"  # "auto" | "f32t" | "f32x3" | "f32" | "f16x2" (ops.encoder_fused)
         self.encoder_workgroups = 0  # persistent workgroups per encoder launch (0: library default, one per CU)
+        self._transfer_grid_image = None
+        self.grid_head_mode = "auto"  # "auto" | "gathered": predict_grid's head for the transfer model
 
     # ------------------------------------------------------------------ construction
     def _build_all(self):
@@ -320,8 +322,24 @@ class MPNNModel:
             cfg = json.loads(bytes(z["__config__"].tobytes()).decode())
             return cfg, {k: z[k] for k in z.files if k != "__config__"}
 
+    GRID_HEAD_MODES = ("auto", "gathered")
+
+    @property
+    def grid_head_mode(self):
+        """How ``predict_grid`` evaluates the transfer head: "auto" takes the matrix-core grid kernel
+        (impnn_transfer_head_grid) where it covers the model, "gathered" always runs ``self.head`` on gathered tiles of
+        pairs.  The viscosity and melting-point models ignore it."""
+        return self._grid_head_mode
+
+    @grid_head_mode.setter
+    def grid_head_mode(self, mode):
+        if mode not in self.GRID_HEAD_MODES:
+            raise ValueError(f"grid_head_mode must be one of {self.GRID_HEAD_MODES}, got {mode!r}")
+        self._grid_head_mode = mode
+
     def invalidate_packed_weights(self):
         """Call after mutating layer weights in place; the fused encoder caches a packed copy."""
+        self._transfer_grid_image = None
         self._packed = None
         self._prepared = {}
         self._split_deg_limit = None
@@ -335,6 +353,9 @@ class MPNNModel:
         encoder weights and a frozen message layer's type matrices stay when nothing they were built from trains - a
         captured training step reads them on every replay."""
         self._head_packed = None
+        if self.kind == "transfer" and (getattr(self, "_bn_training", self.mp_bn_1.trainable)
+                                        or any(t.requires_grad for t in self._head_tensors()[10:])):
+            self._transfer_grid_image = None  # (a frozen tail keeps its image, as a frozen encoder its prepared weights)
         enc = [t for n, t in self._named_tensors().items()
                if n.endswith("_embedding") or "_bmm_" in n or "_gu_" in n]
         if any(t.requires_grad for t in enc):
@@ -373,6 +394,13 @@ class MPNNModel:
             with torch.no_grad():
                 self._head_packed = torch.cat([t.reshape(-1) for t in self._head_tensors()]).contiguous()
         return self._head_packed
+
+    def _transfer_image(self):
+        """The weight image of impnn_transfer_head_grid (ops.transfer_grid_prepare), cached per weight version."""
+        if self._transfer_grid_image is None:
+            with torch.no_grad():
+                self._transfer_grid_image = ops.transfer_grid_prepare(self._head_tensors(), self._transfer_cfg(False))
+        return self._transfer_grid_image
 
     def _prepared_weights(self, mode):
         """Kernel-side weight images (one per ion), built once per weight version and mode."""
@@ -1010,16 +1038,25 @@ class MPNNModel:
     def _grid_kernels_cover(self):
         return self.kind != "transfer" and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
 
+    def _transfer_grid_covers(self):
+        """The matrix-core grid of the transfer head (impnn_transfer_ion_half / impnn_transfer_head_grid) covers it."""
+        return self.kind == "transfer" and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
+
     def predict_grid(self, cations, anions, temperatures=None, return_params=False, max_pairs_per_launch=None,
                      batch_size=4096):
         """Every cation x anion pair (x temperature) of a screen from C + A encoder rows: ``encode_ions``, the
         per-ion half of the head once per species (impnn_head_ion_mix), then one impnn_head_grid launch over the
         product.  Viscosity: ``temperatures`` (nT) in kelvin -> numpy (C,A,nT), with ``return_params`` also the VFT
-        parameters (C,A,3) = (A, B, C) of every pair; melting point and transfer: numpy (C,A).  Element [i,j,t] has
-        the bits ``predict`` gives for the pair (cation i, anion j, T[t]) from the same pooled rows.
+        parameters (C,A,3) = (A, B, C) of every pair; melting point and transfer: numpy (C,A).  For the viscosity and
+        melting-point models, and for the transfer model with ``grid_head_mode = "gathered"``, element [i,j,t] has the
+        bits ``predict`` gives for the pair (cation i, anion j, T[t]) from the same pooled rows.  The transfer model in
+        "auto" runs its head on the matrix cores from one ``impnn_transfer_ion_half`` row per species
+        (impnn_transfer_head_grid): the order of the sums and the factored first layer differ from ``predict``'s
+        kernel, the values agree within the project's 1e-5 bound, and an element's bits do not depend on the grid's
+        size or the host tiling.
         ``max_pairs_per_launch`` tiles the cation axis on the host; the default keeps one launch's output within
         GRID_OUTPUT_BUDGET elements (1 GiB of float32); ``batch_size``: rows per encoder launch.  Widths the head kernels do not cover (fp_size or mixing_size
-        above 64) and the transfer model evaluate ``self.head`` on gathered tiles of pairs instead."""
+        above 64) and the transfer model in "gathered" mode evaluate ``self.head`` on gathered tiles of pairs instead."""
         if self.kind == "viscosity" and temperatures is None:
             raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
         if return_params and self.kind != "viscosity":
@@ -1042,7 +1079,8 @@ class MPNNModel:
         params = np.empty((C, A, 3), np.float32) if return_params else None
         if C == 0 or A == 0:
             return (out, params) if return_params else out
-        covered = self._grid_kernels_cover()
+        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
+        covered = self._grid_kernels_cover() or mfma
         if max_pairs_per_launch is None:
             max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
             if not covered:
@@ -1051,7 +1089,11 @@ class MPNNModel:
         with torch.no_grad():
             if visc:
                 T = T.to(self.device)
-            if covered:
+            if mfma:
+                tensors, image = self._head_tensors(), self._transfer_image()
+                mc = ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size)
+                ma = ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size)
+            elif covered:
                 w = self._packed_head()
                 mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
                 ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
@@ -1059,6 +1101,8 @@ class MPNNModel:
                 hi = min(C, lo + rows)
                 if not covered:
                     out[lo:hi] = self._grid_gathered(pc[lo:hi], pa, T).cpu().numpy()
+                elif mfma:
+                    out[lo:hi] = ops.transfer_head_grid(mc[lo:hi], ma, image).cpu().numpy()
                 elif not visc:
                     out[lo:hi] = ops.head_grid(self.kind, mc[lo:hi], ma, None, w, self.fp_size,
                                                self.mixing_size).cpu().numpy()

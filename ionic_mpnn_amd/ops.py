@@ -766,6 +766,73 @@ def head_grid(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing
     return (out, params) if return_params else out
 
 
+TRANSFER_GRID_WIDTH = 256  # mp_dense_1's units: the width of a ``transfer_ion_half`` row
+
+
+def _transfer_weight_table(weights):
+    if len(weights) != 18:
+        raise ValueError(f"the transfer head has 18 weight tensors, got {len(weights)}")
+    require_gpu(*weights)
+    weights = [f32c(w) for w in weights]
+    return weights, (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
+
+
+def transfer_grid_prepare(weights, cfg):
+    """The weight image of ``transfer_head_grid`` (impnn_transfer_grid_prepare): mp_dense_2 / mp_dense_3 in MFMA operand
+    order, BatchNormalization's moving statistics as scale and shift, the last biases and kernel.  ``weights`` the 18
+    tensors in the order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg.  Build it once per weight version."""
+    weights, table = _transfer_weight_table(weights)
+    mean, var = cfg["moving_mean"], cfg["moving_variance"]
+    require_gpu(mean, var)
+    mean, var = f32c(mean), f32c(var)
+    if weights[12].shape != (256, 128) or weights[14].shape != (128, 64) or mean.numel() != 256 or var.numel() != 256:
+        raise ValueError("transfer_grid_prepare: the head is Dense 256 - BatchNormalization - Dense 128 - Dense 64 - Dense 1")
+    lib = _lib.load()
+    n = lib.impnn_transfer_grid_image_floats()
+    image = torch.empty(n, dtype=torch.float32, device=mean.device)
+    with torch.cuda.device(mean.device):
+        check(lib.impnn_transfer_grid_prepare(table, ptr(mean), ptr(var), cfg["epsilon"], ptr(image), n, stream_ptr()))
+    return image
+
+
+def transfer_ion_half(ion, pooled, weights, fp_size, mixing_size):
+    """The per-ion half of the transfer head (impnn_transfer_ion_half): ``ion`` "cat" / 0 or "an" / 1, pooled (M,D) ->
+    relu(relu(pooled Wfp + bfp) Wp + bp) W1 (+ b1 for the anion) (M,256), from the 18 weight tensors."""
+    require_gpu(pooled)
+    pooled = f32c(pooled)
+    if pooled.dim() != 2:
+        raise ValueError(f"pooled must be (M,D), got {tuple(pooled.shape)}")
+    weights, table = _transfer_weight_table(weights)
+    M, D = pooled.shape
+    g = {"cat": 0, "an": 1, 0: 0, 1: 1}[ion]
+    if weights[2 * g].shape != (D, fp_size) or weights[4 + 2 * g].shape != (fp_size, mixing_size) \
+            or weights[8].shape != (mixing_size, TRANSFER_GRID_WIDTH):
+        raise ValueError(f"transfer_ion_half: weight shapes do not match D={D}, fp_size={fp_size}, mixing_size={mixing_size}")
+    u = torch.empty(M, TRANSFER_GRID_WIDTH, dtype=torch.float32, device=pooled.device)
+    with torch.cuda.device(pooled.device):
+        check(_lib.load().impnn_transfer_ion_half(g, ptr(pooled), table, ptr(u), M, D, fp_size, mixing_size, stream_ptr()))
+    return u
+
+
+def transfer_head_grid(u_cat, u_an, image):
+    """The transfer head on every cation x anion pair in one launch (impnn_transfer_head_grid), on the matrix cores in
+    exact f32: ``transfer_ion_half`` rows (C,256) and (A,256), the image of ``transfer_grid_prepare`` -> (C,A)."""
+    require_gpu(u_cat, u_an, image)
+    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
+    W = TRANSFER_GRID_WIDTH
+    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
+        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
+    lib = _lib.load()
+    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
+        raise ValueError("the prepared image has the wrong length")
+    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
+    out = torch.empty(C_, A_, dtype=torch.float32, device=u_cat.device)
+    with torch.cuda.device(u_cat.device):
+        check(lib.impnn_transfer_head_grid(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), ptr(out), C_, A_,
+                                           stream_ptr()))
+    return out
+
+
 def transfer_head(pooled_cat, pooled_an, weights, cfg):
     """The transfer model's head in inference, one launch (impnn_transfer_head): ``weights`` the 18 tensors in the
     order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg -> (B,1)."""

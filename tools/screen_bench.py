@@ -1,7 +1,9 @@
 """Cation x anion screening: MPNNModel.predict_grid against MPNNModel.predict on the explicitly expanded pair list
-(the only inference entry before the grid existed), plus the grid kernel alone against the HBM write rate.
+(the only inference entry before the grid existed), plus the grid kernel alone against the HBM write rate.  For the
+transfer model: predict_grid with grid_head_mode "gathered" (self.head on gathered tiles of pairs) against "auto" (the
+matrix-core grid, impnn_transfer_head_grid), plus that kernel alone against the f32 MFMA peak.
 
-python tools/screen_bench.py [--quick]      -> one JSON line per configuration, appended to profiles/screen_bench.jsonl
+python tools/screen_bench.py [--quick] [--only viscosity|transfer]      -> one JSON line per configuration, appended to profiles/screen_bench.jsonl
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -22,6 +24,7 @@ from ionic_mpnn_amd import model as MM, ops, synthetic, weights  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="the first configuration only")
+ap.add_argument("--only", choices=("viscosity", "transfer"), help="one family of configurations")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -47,7 +50,7 @@ def species(n, seed):
 
 
 lines = []
-for name, D, S, C, A, nT, bs in CONFIGS[:1] if args.quick else CONFIGS:
+for name, D, S, C, A, nT, bs in [] if args.only == "transfer" else CONFIGS[:1] if args.quick else CONFIGS:
     m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
     m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
     cat, _ = species(C, 1)
@@ -86,6 +89,62 @@ for name, D, S, C, A, nT, bs in CONFIGS[:1] if args.quick else CONFIGS:
     print(json.dumps(line), flush=True)
     lines.append(line)
     del exp, m
+    torch.cuda.empty_cache()
+
+# ---- the transfer model: "gathered" against "auto", then the matrix-core grid kernel alone
+# (name, atom_dim, steps, C, A)
+TRANSFER_CONFIGS = [("transfer 256x256", 32, 3, 256, 256),
+                    ("transfer 1024x1024", 32, 3, 1024, 1024),
+                    ("transfer D128 S6 256x256", 128, 6, 256, 256)]
+PAIR_FLOP = 2 * (256 * 128 + 128 * 64 + 64)  # executed per pair by the grid kernel
+MFMA_F32_PEAK = 157.3e12
+
+
+def build_transfer(D, S):
+    import tempfile
+    v = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
+    v.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
+    with tempfile.TemporaryDirectory() as d:
+        path = str(Path(d) / "viscosity_final.keras")
+        v.save(path)
+        return MM.build_transfer_model(path, device=dev)
+
+
+for name, D, S, C, A in [] if args.only == "viscosity" else TRANSFER_CONFIGS[:1] if args.quick else TRANSFER_CONFIGS:
+    t = build_transfer(D, S)
+    cat, _ = species(C, 1)
+    _, an = species(A, 2)
+
+    def run(mode):
+        t.grid_head_mode = mode
+        return t.predict_grid(cat, an)
+
+    _, y_g = timed(lambda: run("gathered"))
+    _, y_a = timed(lambda: run("auto"))
+    err = float(np.max(np.abs(y_g - y_a)) / np.max(np.abs(y_g)))
+    t_g, t_a = [], []
+    for _ in range(3):
+        t_g.append(timed(lambda: run("gathered"))[0])
+        t_a.append(timed(lambda: run("auto"))[0])
+    with torch.no_grad():
+        pc, pa = t.encode_ions(cat, an)
+        tensors, image = t._head_tensors(), t._transfer_image()
+        uc = ops.transfer_ion_half("cat", pc, tensors, t.fp_size, t.mixing_size)
+        ua = ops.transfer_ion_half("an", pa, tensors, t.fp_size, t.mixing_size)
+        launch = lambda: [ops.transfer_head_grid(uc, ua, image) for _ in range(20)]
+        timed(launch)
+        k_ms = statistics.median(timed(launch)[0] for _ in range(3)) / 20
+    ms_g, ms_a = statistics.median(t_g), statistics.median(t_a)
+    flops = C * A * PAIR_FLOP / (k_ms * 1e-3)
+    line = {"config": name, "atom_dim": D, "steps": S, "C": C, "A": A, "pairs": C * A,
+            "predict_grid_gathered_ms": round(ms_g, 3), "predict_grid_auto_ms": round(ms_a, 3),
+            "speedup": round(ms_g / ms_a, 2), "rounds_gathered_ms": [round(x, 3) for x in t_g],
+            "rounds_auto_ms": [round(x, 3) for x in t_a], "gathered_spread_ms": round(max(t_g) - min(t_g), 3),
+            "grid_kernel_us": round(k_ms * 1e3, 2), "grid_kernel_GFLOPs": round(flops / 1e9, 1),
+            "grid_kernel_of_f32_mfma_peak": round(flops / MFMA_F32_PEAK, 3), "max_rel_diff": err}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+    del t
     torch.cuda.empty_cache()
 Path(args.out).parent.mkdir(parents=True, exist_ok=True)
 with open(args.out, "a") as f:
