@@ -218,6 +218,36 @@ int typed_message_checked(const TypedMessageCall& c, bool tensors, int (*launch)
   return launch(c);
 }
 
+// ---- the model head family (include/impnn.h; model_head.hip).  Each entry fills a ModelHeadCall; one check applies the
+// family's rules in a fixed order and launches.
+ModelHeadCall model_head(const char* entry, int32_t kind, const float* pooled_cat, const float* pooled_an,
+                         const float* temperature, int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  ModelHeadCall c{};
+  c.entry = entry, c.kind = kind, c.pc = pooled_cat, c.pa = pooled_an, c.T = temperature;
+  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
+  return c;
+}
+
+struct ModelHeadForm {
+  bool empty_batch, tensors;  // B == 0 is a success (not for the loss entries); the entry's own pointers are non-null
+  int (*launch)(const ModelHeadCall&);
+};
+
+// The family's rules in their order: kind, shape, zero work, null pointers (the temperature is kind 0's alone), workspace
+// size (the loss forward is the one entry with a workspace) - then the launcher: widths, null weight / gradient tensor
+// i, LDS fit.
+int model_head_checked(const ModelHeadCall& c, ModelHeadForm form) {
+  if (!(c.kind == 0 || c.kind == 1))
+    return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", c.entry);
+  if (!(c.B >= (form.empty_batch ? 0 : 1) && c.D > 0 && c.F > 0 && c.Mx > 0))
+    return fail(IMPNN_E_BADARG, "%s: bad shape", c.entry);
+  if (c.B == 0) return IMPNN_OK;
+  if (!(c.pc && c.pa && form.tensors && (c.kind == 1 || c.T))) return fail(IMPNN_E_BADARG, "%s: null pointer", c.entry);
+  if (c.workspace && c.workspace_floats < impnn_model_head_loss_workspace_floats(c.B))
+    return fail(IMPNN_E_WORKSPACE, "model_head_loss: workspace of %lld floats is too small", (long long)c.workspace_floats);
+  return form.launch(c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -472,35 +502,25 @@ int64_t impnn_model_head_floats(int32_t kind, int32_t D, int32_t F, int32_t Mx) 
 int impnn_model_head(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,
                      const float* head_weights, float* out, int32_t B, int32_t D, int32_t F, int32_t Mx,
                      impnn_stream_t stream) {
-  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
-  REQUIRE(B >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  if (B == 0) return IMPNN_OK;
-  REQUIRE(pooled_cat && pooled_an && head_weights && out && (kind == 1 || temperature), "null pointer");
-  return launch_model_head(kind, pooled_cat, pooled_an, temperature, head_weights, out, B, D, F, Mx, as_stream(stream));
+  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.w = head_weights, c.out = out;
+  return model_head_checked(c, {true, head_weights && out, launch_model_head});
 }
 
 int impnn_model_head_tensors(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,
                              const float* const* weights, float* out, int32_t B, int32_t D, int32_t F, int32_t Mx,
                              impnn_stream_t stream) {
-  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
-  REQUIRE(B >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  if (B == 0) return IMPNN_OK;
-  REQUIRE(pooled_cat && pooled_an && weights && out && (kind == 1 || temperature), "null pointer");
-  return launch_model_head_tensors(kind, pooled_cat, pooled_an, temperature, weights, out, B, D, F, Mx,
-                                   as_stream(stream));
+  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.weights = weights, c.out = out;
+  return model_head_checked(c, {true, weights && out, launch_model_head_tensors});
 }
 
 int impnn_model_head_bwd(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,
                          const float* const* weights, const float* dout, float* dpooled_cat, float* dpooled_an,
                          float* const* dweights, int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
-  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
-  REQUIRE(B >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  if (B == 0) return IMPNN_OK;
-  REQUIRE(pooled_cat && pooled_an && weights && dout && dpooled_cat && dpooled_an && dweights &&
-              (kind == 1 || temperature),
-          "null pointer");
-  return launch_model_head_bwd(kind, pooled_cat, pooled_an, temperature, weights, dout, dpooled_cat, dpooled_an,
-                               dweights, B, D, F, Mx, as_stream(stream));
+  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.weights = weights, c.dout = dout, c.dpc = dpooled_cat, c.dpa = dpooled_an, c.dweights = dweights;
+  return model_head_checked(c, {true, weights && dout && dpooled_cat && dpooled_an && dweights, launch_model_head_bwd});
 }
 
 int64_t impnn_model_head_loss_workspace_floats(int32_t B) { return B > 0 ? model_head_loss_workspace_floats(B) : 4; }
@@ -509,45 +529,30 @@ int impnn_model_head_loss(int32_t kind, const float* pooled_cat, const float* po
                           const float* const* weights, const float* l2, const float* y, float* pred, float* loss,
                           float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F, int32_t Mx,
                           impnn_stream_t stream) {
-  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
-  REQUIRE(B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  REQUIRE(pooled_cat && pooled_an && weights && l2 && y && loss && workspace && (kind == 1 || temperature),
-          "null pointer");
-  if (workspace_floats < impnn_model_head_loss_workspace_floats(B))
-    return fail(IMPNN_E_WORKSPACE, "model_head_loss: workspace of %lld floats is too small", (long long)workspace_floats);
-  return launch_model_head_tensors(kind, pooled_cat, pooled_an, temperature, weights, pred, B, D, F, Mx,
-                                   as_stream(stream), l2, y, loss, workspace);
+  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.weights = weights, c.l2 = l2, c.y = y, c.out = pred, c.loss = loss, c.workspace = workspace;
+  c.workspace_floats = workspace_floats;
+  return model_head_checked(c, {false, weights && l2 && y && loss && workspace, launch_model_head_tensors});
 }
 
 int impnn_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,
                               const float* const* weights, const float* l2, const float* y, const float* dloss,
                               float* dpooled_cat, float* dpooled_an, float* const* dweights, int32_t B, int32_t D,
                               int32_t F, int32_t Mx, impnn_stream_t stream) {
-  REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
-  REQUIRE(B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  REQUIRE(pooled_cat && pooled_an && weights && l2 && y && dloss && dpooled_cat && dpooled_an && dweights &&
-              (kind == 1 || temperature),
-          "null pointer");
-  return launch_model_head_bwd(kind, pooled_cat, pooled_an, temperature, weights, nullptr, dpooled_cat, dpooled_an,
-                               dweights, B, D, F, Mx, as_stream(stream), l2, y, dloss);
+  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.weights = weights, c.l2 = l2, c.y = y, c.dloss = dloss, c.dpc = dpooled_cat, c.dpa = dpooled_an, c.dweights = dweights;
+  return model_head_checked(c, {false, weights && l2 && y && dloss && dpooled_cat && dpooled_an && dweights,
+                                launch_model_head_bwd});
 }
 
 // ---- the head over a cation x anion grid (include/impnn.h; head_grid.hip).  The family's order: shape, zero work,
 // null pointers.
-namespace {
-int head_grid_dims(const char* entry, int D, int F, int Mx) {
-  if (D > 128 || F > 64 || Mx > 64)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= 128) F=%d Mx=%d (<= 64)", entry, D, F, Mx);
-  return IMPNN_OK;
-}
-}  // namespace
-
 int impnn_head_ion_mix(int32_t kind, int32_t ion, const float* pooled, const float* head_weights, float* mix, int32_t M,
                        int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
   REQUIRE(kind == 0 || kind == 1, "kind must be 0 (viscosity) or 1 (melting point)");
   REQUIRE(ion == 0 || ion == 1, "ion must be 0 (cation) or 1 (anion)");
   REQUIRE(M >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  if (int rc = head_grid_dims(__func__, D, F, Mx)) return rc;
+  if (int rc = head_widths_covered(__func__, D, F, Mx)) return rc;
   if (M == 0) return IMPNN_OK;
   REQUIRE(pooled && head_weights && mix, "null pointer");
   return launch_head_ion_mix(kind, ion, pooled, head_weights, mix, M, D, F, Mx, as_stream(stream));
@@ -560,7 +565,7 @@ int impnn_head_grid(int32_t kind, const float* mix_cat, const float* mix_an, con
   REQUIRE(C >= 0 && A >= 0 && nT >= 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
   REQUIRE(kind == 1 || nT >= 1, "the viscosity grid needs nT >= 1 temperatures");
   REQUIRE(kind == 0 || nT == 0, "the melting-point grid takes no temperatures: nT must be 0");
-  if (int rc = head_grid_dims(__func__, D, F, Mx)) return rc;
+  if (int rc = head_widths_covered(__func__, D, F, Mx)) return rc;
   if (nT > head_grid_max_temperatures())
     return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", __func__, nT, head_grid_max_temperatures());
   if (C == 0 || A == 0) return IMPNN_OK;
@@ -677,8 +682,7 @@ int transfer_grid_check(const TransferGridCheck& c, bool* launch) {
   if (c.image_floats >= 0 && c.image_floats < transfer_grid_image_floats())
     return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", c.entry, (long long)c.image_floats,
                 (long long)transfer_grid_image_floats());
-  if (c.D > 128 || c.F > 64 || c.Mx > 64)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= 128) F=%d Mx=%d (<= 64)", c.entry, c.D, c.F, c.Mx);
+  if (int rc = head_widths_covered(c.entry, c.D, c.F, c.Mx)) return rc;
   *launch = true;
   return IMPNN_OK;
 }

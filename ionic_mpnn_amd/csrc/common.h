@@ -191,6 +191,40 @@ struct EdgeSortView {
         order(segbase + Vb + 1) {}
 };
 
+// ---- the widths every head kernel covers (model_head.hip, head_grid.hip, transfer_head.hip, transfer_grid.hip): LDS row
+// strides as well as the limits api.hip and the launchers refuse above; ops.py mirrors them (HEAD_MAX_X, HEAD_MAX_DIM)
+constexpr int kHeadMaxX = 128;   // pooled width (atom_dim)
+constexpr int kHeadMaxDim = 64;  // fp_size, mixing_size
+// the refusal of a width above them, in the name of an entry (api.hip: the grid families) or of a launcher (model_head.hip)
+inline int head_widths_covered(const char* what, int D, int F, int Mx) {
+  if (D > kHeadMaxX || F > kHeadMaxDim || Mx > kHeadMaxDim)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= %d) F=%d Mx=%d (<= %d)", what, D, kHeadMaxX, F, Mx, kHeadMaxDim);
+  return IMPNN_OK;
+}
+
+// ---- one model head call (include/impnn.h: impnn_model_head, _tensors, _bwd, _loss, _loss_bwd).  api.hip fills it from
+// the entry's arguments and checks it (model_head_checked); the launchers (model_head.hip) read it.  Pointers an entry
+// does not take stay null; `y` is what makes a call a loss call.
+struct ModelHeadCall {
+  const char* entry;  // the exported entry, named by the error text
+  int kind;           // 0 viscosity, 1 melting point
+  const float *pc, *pa, *T;
+  const float* w;               // impnn_model_head: the packed head; every other entry:
+  const float* const* weights;  // 10 / 12 device pointers in the packed order (a host table)
+  float* const* dweights;       // backward: the gradients, added into
+  const float* dout;            // backward, plain
+  float *out, *dpc, *dpa;       // forward (optional in the loss forward); backward
+  const float *l2, *y, *dloss;  // loss entries: host lambdas per tensor, targets; backward: device scalar
+  float *loss, *workspace;      // loss forward: device scalar; model_head_loss_workspace_floats
+  int64_t workspace_floats;
+  int B, D, F, Mx;
+  hipStream_t stream;
+};
+int64_t model_head_loss_workspace_floats(int B);
+int launch_model_head(const ModelHeadCall& c);          // a checked call (api.hip)
+int launch_model_head_tensors(const ModelHeadCall& c);  // a checked call (api.hip)
+int launch_model_head_bwd(const ModelHeadCall& c);      // a checked call (api.hip)
+
 // ---- layer-at-a-time launches (layer_kernels.hip)
 int launch_embed_gather(const int32_t* ids, const float* table, float* out, int64_t rows, int vocab,
                         int dim, hipStream_t s);
@@ -210,14 +244,6 @@ int launch_row_index_fill(const int32_t* r, const int32_t* incl, int32_t* idx, i
                           hipStream_t s);
 int launch_global_sum_pool(const float* h, const int32_t* ids, float* out, int B, int N, int D,
                            hipStream_t s);
-int64_t model_head_loss_workspace_floats(int B);
-int launch_model_head_tensors(int kind, const float* pc, const float* pa, const float* T, const float* const* weights,
-                              float* out, int B, int D, int F, int Mx, hipStream_t s, const float* l2 = nullptr,
-                              const float* y = nullptr, float* loss_out = nullptr, float* workspace = nullptr);
-int launch_model_head_bwd(int kind, const float* pc, const float* pa, const float* T, const float* const* weights,
-                          const float* dout, float* dpc, float* dpa, float* const* grads, int B, int D, int F, int Mx,
-                          hipStream_t s, const float* l2 = nullptr, const float* y = nullptr,
-                          const float* dloss = nullptr);
 // ---- the transfer head (transfer_head.hip; include/impnn.h, impnn_transfer_head*).  api.hip fills and checks it.
 constexpr int kThTensors = 18;
 struct TransferHeadCall {
@@ -247,8 +273,6 @@ int launch_transfer_head(const TransferHeadCall& c);
 int launch_transfer_head_bwd(const TransferHeadCall& c);
 int launch_gather_rows(int n, const void* const* src, void* const* dst, const int64_t* row_bytes, const int64_t* rows,
                        int n_rows, hipStream_t s);
-int launch_model_head(int kind, const float* pc, const float* pa, const float* T, const float* w, float* out, int B,
-                      int D, int F, int Mx, hipStream_t s);
 int launch_validate_indices(const int32_t* conn, const int32_t* atom_ids, const int32_t* bond_ids,
                             int32_t* counts, int B, int N, int E, int Va, int Vb, hipStream_t s);
 
@@ -276,7 +300,7 @@ int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked ca
 int launch_bmm_message_typed_bwd(const TypedMessageCall& c);     // a checked call (api.hip)
 
 // ---- backward + optimizer (train_kernels.hip): embedding / pool / Reduce adjoints, bond-table gradient, GatedUpdate
-// backward, dropout step, Adam, model head
+// backward, dropout step, Adam
 int launch_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable, int64_t rows, int vocab, int dim,
                             hipStream_t s);
 int launch_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int tgt_stride, float* dm, int B, int N, int E,

@@ -1,13 +1,18 @@
-// Device arithmetic of the model head after GlobalSumPool (f1), shared by model_head_kernel (layer_kernels.hip: one
-// launch per pair list) and the grid kernels (head_grid.hip: per-ion mixing rows, then every cation x anion pair).
-// One definition of every rounding step, so a pair gives the same bits whichever kernel evaluates it.
+// Device arithmetic of the model head after GlobalSumPool (f1), shared by the kernels of model_head.hip (one launch
+// per pair list: the inference forward, the training forward and the backward) and the grid kernels (head_grid.hip:
+// per-ion mixing rows, then every cation x anion pair; transfer_grid.hip).  One definition of every rounding step, so a
+// pair gives the same bits whichever kernel evaluates it.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 namespace impnn {
 
+// Two softplus forms that round differently, so neither may stand in for the other.  _exact: the inference head
+// (impnn_model_head) and the grid (impnn_head_grid), bit-equal to each other.  _stable: the tensor-table forward
+// (impnn_model_head_tensors, _loss) and the backward (impnn_model_head_bwd, _loss_bwd), which recomputes that forward.
 __device__ __forceinline__ float softplus_exact(float x) { return x > 20.f ? x + log1pf(expf(-x)) : log1pf(expf(x)); }
+__device__ __forceinline__ float softplus_stable(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
 // A Dense output: the bias first, then the inputs in ascending order, one fmaf each.  w[i * stride] is the kernel
 // entry of input i for this output.

@@ -14,8 +14,6 @@ namespace impnn {
 
 namespace {
 
-constexpr int kMaxDim = 64;   // fp_size, mixing_size
-constexpr int kMaxX = 128;    // pooled width
 constexpr int kMixRows = 8;   // ion rows per 256-thread workgroup, 32 threads per row (as model_head_kernel)
 
 __global__ __launch_bounds__(256) void head_ion_mix_kernel(const float* __restrict__ pooled,
@@ -26,21 +24,21 @@ __global__ __launch_bounds__(256) void head_ion_mix_kernel(const float* __restri
   const int nfp = D * F + F, np = F * Mx + Mx;
   float* Wfp = sm;                          // Wfp_g D*F | bfp_g F
   float* Wp = Wfp + ((nfp + 3) & ~3);       // Wp_g F*Mx | bp_g Mx
-  float* xs = Wp + ((np + 3) & ~3);         // [kMixRows][kMaxX]
-  float* fp = xs + kMixRows * kMaxX;        // [kMixRows][kMaxDim]
+  float* xs = Wp + ((np + 3) & ~3);         // [kMixRows][kHeadMaxX]
+  float* fp = xs + kMixRows * kHeadMaxX;        // [kMixRows][kHeadMaxDim]
   const int tid = threadIdx.x, sl = tid >> 5, jj = tid & 31;
   const int64_t m = (int64_t)blockIdx.x * kMixRows + sl;
   const bool live = m < M;
   for (int t = tid; t < nfp; t += blockDim.x) Wfp[t] = wfp_g[t];
   for (int t = tid; t < np; t += blockDim.x) Wp[t] = wp_g[t];
-  for (int i = jj; i < D; i += 32) xs[sl * kMaxX + i] = live ? pooled[m * D + i] : 0.f;
+  for (int i = jj; i < D; i += 32) xs[sl * kHeadMaxX + i] = live ? pooled[m * D + i] : 0.f;
   __syncthreads();
   for (int j = jj; j < F; j += 32)
-    fp[sl * kMaxDim + j] = head_relu(head_chain(xs + sl * kMaxX, Wfp + j, F, D, Wfp[D * F + j]));
+    fp[sl * kHeadMaxDim + j] = head_relu(head_chain(xs + sl * kHeadMaxX, Wfp + j, F, D, Wfp[D * F + j]));
   __syncthreads();
   if (live)
     for (int j = jj; j < Mx; j += 32)
-      mix[m * Mx + j] = head_relu(head_chain(fp + sl * kMaxDim, Wp + j, Mx, F, Wp[F * Mx + j]));
+      mix[m * Mx + j] = head_relu(head_chain(fp + sl * kHeadMaxDim, Wp + j, Mx, F, Wp[F * Mx + j]));
 }
 
 // ---- the grid.  One workgroup owns kTileC cations x kTileA anions; lane = anion, a wave walks the tile's cations.
@@ -220,7 +218,7 @@ int launch_head_ion_mix(int kind, int ion, const float* pooled, const float* w, 
                         hipStream_t s) {
   (void)kind;  // both kinds share the per-ion layout
   const int nfp = D * F + F, np = F * Mx + Mx;
-  const size_t lds = sizeof(float) * (align4(nfp) + align4(np) + (size_t)kMixRows * (kMaxX + kMaxDim));  // <= 54.3 KiB
+  const size_t lds = sizeof(float) * (align4(nfp) + align4(np) + (size_t)kMixRows * (kHeadMaxX + kHeadMaxDim));  // <= 54.3 KiB
   head_ion_mix_kernel<<<(int)(((int64_t)M + kMixRows - 1) / kMixRows), 256, lds, s>>>(pooled, w + (size_t)ion * nfp,
                                                                       w + 2 * (size_t)nfp + (size_t)ion * np, mix, M, D, F, Mx);
   return check_launch("head_ion_mix");

@@ -7,7 +7,6 @@
 //
 // Reference lines each kernel follows are cited at the kernel.
 #include "common.h"
-#include "head_device.h"
 
 namespace impnn {
 
@@ -1238,92 +1237,6 @@ __global__ void validate_indices_kernel(const int32_t* conn, const int32_t* atom
   if (c2) atomicAdd(&counts[2], c2);
 }
 
-// ---------------------------------------------------------------------------------------
-// f1  model head after GlobalSumPool, one launch (train_viscosity.py:189,197-214 + models/layers.py:10-49;
-// train_melting_point.py:173,191-198).
-//   fp_g  = relu(pooled_g @ Wfp_g + bfp_g)         (D -> F)     g in {cat, an}
-//   mixed = relu(fp_cat @ Wp_cat + bp_cat) + relu(fp_an @ Wp_an + bp_an)      (F -> Mx)
-//   kind 0: vp = mixed @ Wv + bv (Mx -> 3); A = vp0; Bc = clip(softplus(vp1), 0, 20);
-//           Cc = clip(softplus(vp2), 0.1, 50); out = A + Bc / (T/100 + Cc + 1e-6)
-//   kind 1: out = relu(mixed @ Wh + bh) @ Wo + bo   (Mx -> F -> 1)
-// ---------------------------------------------------------------------------------------
-constexpr int kHeadMaxDim = 64;   // fp_size, mixing_size
-constexpr int kHeadMaxX = 128;    // pooled width (atom_dim 128: train_viscosity.py with a wider encoder)
-
-// 8 samples per 256-thread workgroup, 32 threads per sample: thread (s, jj) owns outputs jj, jj+32 of
-// every layer; the sample's vectors and all weights sit in LDS (13.6 KB of weights at the defaults).
-constexpr int kHeadSPB = 8;
-
-__global__ __launch_bounds__(256) void model_head_kernel(int kind, const float* __restrict__ pc,
-                                                         const float* __restrict__ pa, const float* __restrict__ T,
-                                                         const float* __restrict__ w, float* __restrict__ out, int B, int D,
-                                                         int F, int Mx, int wfloats) {
-  extern __shared__ __align__(16) float hsm[];
-  float* ws = hsm;                                   // all head weights
-  float* xs = ws + ((wfloats + 3) & ~3);             // [kHeadSPB][2][kHeadMaxX] pooled rows
-  float* fp = xs + kHeadSPB * 2 * kHeadMaxX;         // [kHeadSPB][2][kHeadMaxDim]
-  float* mix = fp + kHeadSPB * 2 * kHeadMaxDim;      // [kHeadSPB][kHeadMaxDim]
-  float* hid = mix + kHeadSPB * kHeadMaxDim;         // [kHeadSPB][kHeadMaxDim]
-  const int tid = threadIdx.x, sl = tid >> 5, jj = tid & 31;
-  const int b = blockIdx.x * kHeadSPB + sl;
-  const bool live = b < B;
-  for (int t = tid; t < wfloats; t += blockDim.x) ws[t] = w[t];
-  for (int g = 0; g < 2; ++g)
-    for (int i = jj; i < D; i += 32) xs[(sl * 2 + g) * kHeadMaxX + i] = live ? (g == 0 ? pc : pa)[(int64_t)b * D + i] : 0.f;
-  __syncthreads();
-  const float* Wfp[2] = {ws, ws + D * F + F};
-  const float* wp = ws + 2 * (D * F + F);
-  const float* Wp[2] = {wp, wp + F * Mx + Mx};
-  const float* wt = wp + 2 * (F * Mx + Mx);
-  for (int g = 0; g < 2; ++g)
-    for (int j = jj; j < F; j += 32) {
-      float acc = Wfp[g][D * F + j];
-      const float* x = xs + (sl * 2 + g) * kHeadMaxX;
-      for (int i = 0; i < D; ++i) acc = fmaf(x[i], Wfp[g][i * F + j], acc);
-      fp[(sl * 2 + g) * kHeadMaxDim + j] = fmaxf(acc, 0.f);
-    }
-  __syncthreads();
-  for (int j = jj; j < Mx; j += 32) {
-    float m = 0.f;
-    for (int g = 0; g < 2; ++g) {
-      float acc = Wp[g][F * Mx + j];
-      const float* x = fp + (sl * 2 + g) * kHeadMaxDim;
-      for (int i = 0; i < F; ++i) acc = fmaf(x[i], Wp[g][i * Mx + j], acc);
-      m += fmaxf(acc, 0.f);  // AddTwoTensors / keras Add
-    }
-    mix[sl * kHeadMaxDim + j] = m;
-  }
-  __syncthreads();
-  const float* mx = mix + sl * kHeadMaxDim;
-  if (kind == 0) {
-    if (jj < 3) {
-      float acc = wt[Mx * 3 + jj];
-      for (int i = 0; i < Mx; ++i) acc = fmaf(mx[i], wt[i * 3 + jj], acc);
-      hid[sl * kHeadMaxDim + jj] = acc;
-    }
-    __syncthreads();
-    if (jj == 0 && live) {
-      const float* vp = hid + sl * kHeadMaxDim;
-      out[b] = head_vft_eval(head_vft_params(vp[0], vp[1], vp[2]), head_scaled_t(T[b]));  // head_device.h
-    }
-  } else {
-    const float* Wh = wt;
-    const float* bh = Wh + Mx * F;
-    const float* Wo = bh + F;
-    for (int j = jj; j < F; j += 32) {
-      float acc = bh[j];
-      for (int i = 0; i < Mx; ++i) acc = fmaf(mx[i], Wh[i * F + j], acc);
-      hid[sl * kHeadMaxDim + j] = fmaxf(acc, 0.f);
-    }
-    __syncthreads();
-    if (jj == 0 && live) {
-      float acc = Wo[F];
-      for (int j = 0; j < F; ++j) acc = fmaf(hid[sl * kHeadMaxDim + j], Wo[j], acc);
-      out[b] = acc;
-    }
-  }
-}
-
 inline int grid_for(int64_t items, int block = kBlock, int cap = 256 * 8) {
   int64_t g = (items + block - 1) / block;
   if (g < 1) g = 1;
@@ -1656,21 +1569,6 @@ int launch_global_sum_pool(const float* h, const int32_t* ids, float* out, int B
   if (B == 0) return IMPNN_OK;
   global_sum_pool_kernel<<<grid_for((int64_t)B * D), kBlock, 0, s>>>(h, ids, out, B, N, D);
   return check_launch("global_sum_pool");
-}
-
-int launch_model_head(int kind, const float* pc, const float* pa, const float* T, const float* w, float* out, int B,
-                      int D, int F, int Mx, hipStream_t s) {
-  if (B == 0) return IMPNN_OK;
-  if (D > kHeadMaxX || F > kHeadMaxDim || Mx > kHeadMaxDim)
-    return fail(IMPNN_E_UNSUPPORTED, "model_head: dims D=%d (<= %d) F=%d Mx=%d (<= %d)", D, kHeadMaxX, F, Mx, kHeadMaxDim);
-  const int wfloats = (int)impnn_model_head_floats(kind, D, F, Mx);
-  const size_t lds = sizeof(float) * (((size_t)wfloats + 3) / 4 * 4 + (size_t)kHeadSPB * (2 * kHeadMaxX + 4 * kHeadMaxDim));
-  // every (D <= 128, F <= 64, Mx <= 64) fits the 160 KB of a gfx950 CU: 29 057 weight floats + 16 KB of sample scratch
-  if (lds > 160 * 1024) return fail(IMPNN_E_UNSUPPORTED, "model_head: weights do not fit LDS");
-  if (lds > 64 * 1024)
-    if (int rc = ensure_lds_limit((const void*)model_head_kernel, 8)) return rc;
-  model_head_kernel<<<(B + kHeadSPB - 1) / kHeadSPB, 256, lds, s>>>(kind, pc, pa, T, w, out, B, D, F, Mx, wfloats);
-  return check_launch("model_head");
 }
 
 int launch_validate_indices(const int32_t* conn, const int32_t* atom_ids, const int32_t* bond_ids,

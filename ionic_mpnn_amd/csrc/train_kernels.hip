@@ -4,8 +4,8 @@
 // in layer_kernels.hip with the same masks (models/layers.py:114-115, :70 tgt > 0) and the same
 // "out-of-range index == padding" rule.  Written for any D (VALU, f32); the parameter-gradient sums run
 // over per-workgroup partial buffers that a second kernel adds in a fixed order, except where noted.
-// Holds the embedding, pool and Reduce adjoints, the bond-table gradient, the GatedUpdate backward, Adam and the
-// model head; the message adjoint (a4) and its edge sort are in message_typed.hip.
+// Holds the embedding, pool and Reduce adjoints, the bond-table gradient, the GatedUpdate backward and Adam; the message
+// adjoint (a4) and its edge sort are in message_typed.hip, the model head's backward in model_head.hip.
 #include "kernel_device.h"
 
 namespace impnn {
@@ -1656,406 +1656,6 @@ __global__ __launch_bounds__(1024) void adam_clipnorm_kernel(const unsigned long
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// f1 for training: everything after GlobalSumPool, forward from the individual weight tensors (no packing) and
-// its backward, one launch each (train_viscosity.py:189,197-214 + models/layers.py:10-49;
-// train_melting_point.py:173,191-198).  Tensor order = the packed order of impnn_model_head:
-//   Wfp_cat | bfp_cat | Wfp_an | bfp_an | Wp_cat | bp_cat | Wp_an | bp_an | kind 0: Wv | bv ; kind 1: Wh | bh | Wo | bo
-// Backward: 8 samples per workgroup, 32 threads per sample; the forward is recomputed; parameter gradients are
-// summed in LDS per workgroup and ADDED to the individual gradient buffers with float atomics.
-// ---------------------------------------------------------------------------------------
-constexpr int kHdMax = 64, kHdSPB = 8, kHdTensors = 12;
-constexpr int kHdXMax = 128;  // widest pooled state (config 5: atom_dim 128); fp_size and mixing_size stay <= kHdMax
-struct HeadTensors {
-  const float* w[kHdTensors];
-  float* g[kHdTensors];
-  int off[kHdTensors + 1];
-  int n;
-  float l2[kHdTensors];  // keras l2(lambda) per tensor (0: none); used by the loss entries only
-};
-// loss = mean_b (pred_b - y_b)^2 + sum_t l2_t * sum(W_t^2)   (keras "mse" + kernel_regularizer, train_viscosity.py:189,229)
-struct HeadLoss {
-  const float* y;        // (B); null: the kernels behave as the plain head entries
-  const float* dloss;    // backward: device scalar, the gradient of the loss value
-  float* loss_out;       // forward: device scalar
-  float* partial;        // forward: one squared-error sum per workgroup
-  unsigned int* counter; // forward: arrival ticket, zero before the first call, left at zero by every call
-  float inv_B;
-};
-__device__ __forceinline__ float head_l2(const HeadTensors& ht, int sgm) {
-  float v = ht.l2[0];
-#pragma unroll
-  for (int q = 1; q < kHdTensors; ++q) v = sgm == q ? ht.l2[q] : v;
-  return v;
-}
-// deterministic workgroup sum of one value per thread (256 threads); result valid in every thread
-__device__ __forceinline__ float head_block_sum(float v, float* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float softplus_stable(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
-__device__ __forceinline__ int head_total(const HeadTensors& ht) {
-  int tot = ht.off[1];
-#pragma unroll
-  for (int q = 2; q <= kHdTensors; ++q) tot = ht.n == q ? ht.off[q] : tot;
-  return tot;
-}
-// segment of packed index t.  Constant indices only: the table is a kernel argument, a dynamic index into it would
-// be a dependent load from the kernarg segment per probe.
-__device__ __forceinline__ int head_segment(const HeadTensors& ht, int t, int* base) {
-  int sgm = 0, b = 0;
-#pragma unroll
-  for (int q = 1; q < kHdTensors; ++q)
-    if (q < ht.n && t >= ht.off[q]) sgm = q, b = ht.off[q];
-  *base = b;
-  return sgm;
-}
-__device__ __forceinline__ const float* head_wptr(const HeadTensors& ht, int sgm) {
-  const float* p = ht.w[0];
-#pragma unroll
-  for (int q = 1; q < kHdTensors; ++q) p = sgm == q ? ht.w[q] : p;
-  return p;
-}
-__device__ __forceinline__ float* head_gptr(const HeadTensors& ht, int sgm) {
-  float* p = ht.g[0];
-#pragma unroll
-  for (int q = 1; q < kHdTensors; ++q) p = sgm == q ? ht.g[q] : p;
-  return p;
-}
-
-__device__ __forceinline__ void head_load_weights(const HeadTensors& ht, float* ws) {
-  const int total = head_total(ht);
-  constexpr int kU = 8;  // independent loads in flight per thread
-  for (int t0 = threadIdx.x; t0 < total; t0 += blockDim.x * kU) {
-    float v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int t = t0 + u * blockDim.x;
-      int base;
-      const int sgm = head_segment(ht, t, &base);
-      v[u] = t < total ? head_wptr(ht, sgm)[t - base] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int t = t0 + u * blockDim.x;
-      if (t < total) ws[t] = v[u];
-    }
-  }
-}
-
-// forward up to the mixed vector; returns through LDS: fpre (pre-activation of the fingerprint Dense), fp, ppre, mix
-__device__ __forceinline__ void head_forward_mix(const float* ws, const float* xs, float* fpre, float* ppre, float* mix,
-                                                 int sl, int jj, int D, int F, int Mx) {
-  const float* Wfp[2] = {ws, ws + D * F + F};
-  const float* wp = ws + 2 * (D * F + F);
-  const float* Wp[2] = {wp, wp + F * Mx + Mx};
-  for (int g = 0; g < 2; ++g)
-    for (int j = jj; j < F; j += 32) {
-      float acc = Wfp[g][D * F + j];
-      const float* x = xs + (sl * 2 + g) * kHdXMax;
-      for (int i = 0; i < D; ++i) acc = fmaf(x[i], Wfp[g][i * F + j], acc);
-      fpre[(sl * 2 + g) * kHdMax + j] = acc;
-    }
-  __syncthreads();
-  for (int j = jj; j < Mx; j += 32) {
-    float m = 0.f;
-    for (int g = 0; g < 2; ++g) {
-      float acc = Wp[g][F * Mx + j];
-      const float* x = fpre + (sl * 2 + g) * kHdMax;
-      for (int i = 0; i < F; ++i) acc = fmaf(fmaxf(x[i], 0.f), Wp[g][i * Mx + j], acc);
-      ppre[(sl * 2 + g) * kHdMax + j] = acc;
-      m += fmaxf(acc, 0.f);
-    }
-    mix[sl * kHdMax + j] = m;
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void model_head_tensors_kernel(int kind, const float* __restrict__ pc,
-                                                                 const float* __restrict__ pa,
-                                                                 const float* __restrict__ T, HeadTensors ht,
-                                                                 float* __restrict__ out, int B, int D, int F, int Mx,
-                                                                 HeadLoss hl) {
-  extern __shared__ __align__(16) float hsm[];
-  __shared__ float red[256];
-  __shared__ float sq[kHdSPB];
-  __shared__ int is_last;
-  const int total = head_total(ht);
-  float* ws = hsm;
-  float* xs = ws + ((total + 3) & ~3);
-  float* fpre = xs + kHdSPB * 2 * kHdXMax;
-  float* ppre = fpre + kHdSPB * 2 * kHdMax;
-  float* mix = ppre + kHdSPB * 2 * kHdMax;
-  float* hid = mix + kHdSPB * kHdMax;
-  const int tid = threadIdx.x, sl = tid >> 5, jj = tid & 31;
-  const int b = blockIdx.x * kHdSPB + sl;
-  const bool live = b < B;
-  head_load_weights(ht, ws);
-  for (int g = 0; g < 2; ++g)
-    for (int i = jj; i < D; i += 32) xs[(sl * 2 + g) * kHdXMax + i] = live ? (g == 0 ? pc : pa)[(int64_t)b * D + i] : 0.f;
-  __syncthreads();
-  head_forward_mix(ws, xs, fpre, ppre, mix, sl, jj, D, F, Mx);
-  const float* wt = ws + 2 * (D * F + F) + 2 * (F * Mx + Mx);
-  const float* mx = mix + sl * kHdMax;
-  if (kind == 0) {
-    if (jj < 3) {
-      float acc = wt[Mx * 3 + jj];
-      for (int i = 0; i < Mx; ++i) acc = fmaf(mx[i], wt[i * 3 + jj], acc);
-      hid[sl * kHdMax + jj] = acc;
-    }
-    __syncthreads();
-    if (jj == 0) {
-      float pred = 0.f;
-      if (live) {
-        const float* vp = hid + sl * kHdMax;
-        const float Bc = fminf(fmaxf(softplus_stable(vp[1]), 0.f), 20.f);
-        const float Cc = fminf(fmaxf(softplus_stable(vp[2]), 0.1f), 50.f);
-        pred = vp[0] + Bc / (T[b] / 100.0f + Cc + 1e-6f);
-        if (out) out[b] = pred;
-      }
-      if (hl.y) sq[sl] = live ? (pred - hl.y[b]) * (pred - hl.y[b]) : 0.f;
-    }
-  } else {
-    const float* Wh = wt;
-    const float* bh = Wh + Mx * F;
-    const float* Wo = bh + F;
-    for (int j = jj; j < F; j += 32) {
-      float acc = bh[j];
-      for (int i = 0; i < Mx; ++i) acc = fmaf(mx[i], Wh[i * F + j], acc);
-      hid[sl * kHdMax + j] = fmaxf(acc, 0.f);
-    }
-    __syncthreads();
-    if (jj == 0) {
-      float acc = Wo[F];
-      for (int j = 0; j < F; ++j) acc = fmaf(hid[sl * kHdMax + j], Wo[j], acc);
-      if (live && out) out[b] = acc;
-      if (hl.y) sq[sl] = live ? (acc - hl.y[b]) * (acc - hl.y[b]) : 0.f;
-    }
-  }
-  if (!hl.y) return;
-  // ---- loss: workgroup sums in sample order, then the LAST workgroup to arrive adds them in workgroup order
-  __syncthreads();
-  if (tid == 0) {
-    float sum = 0.f;
-    for (int q = 0; q < kHdSPB; ++q) sum += sq[q];
-    __hip_atomic_store(&hl.partial[blockIdx.x], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    const unsigned int ticket = atomicAdd(hl.counter, 1u);
-    is_last = ticket == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
-  float v = 0.f;
-  for (int i = tid; i < (int)gridDim.x; i += 256)
-    v += __hip_atomic_load(&hl.partial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const float se = head_block_sum(v, red);
-  float reg = 0.f;
-  for (int t = tid; t < total; t += 256) {
-    int base;
-    const float lam = head_l2(ht, head_segment(ht, t, &base));
-    reg = fmaf(lam * ws[t], ws[t], reg);
-  }
-  reg = head_block_sum(reg, red);
-  if (tid == 0) {
-    hl.loss_out[0] = se * hl.inv_B + reg;
-    *hl.counter = 0u;
-  }
-}
-
-// per-sample vectors of the backward, kHdMax floats each, in LDS: the parameter gradients are outer products of these
-enum { kVX0, kVX1, kVFp0, kVFp1, kVDfp0, kVDfp1, kVDpr0, kVDpr1, kVMix, kVTop, kVHid, kVOne, kHdVecs };
-constexpr int kHdVecStride = 2 * kHdXMax + (kHdVecs - 2) * kHdMax;
-__device__ __forceinline__ int head_vec_off(int which) {
-  return which < 2 ? which * kHdXMax : 2 * kHdXMax + (which - 2) * kHdMax;
-}
-
-// 1024 threads: the first 256 walk the samples (8 samples x 32 lanes, as the forward kernel), all of them stage the
-// weights, form the parameter gradients' outer products and flush them - the three phases that scale with the packed
-// weight count (25 K floats at atom_dim 128) and made the kernel ~96 us at every batch below 2048, alone on the stream
-// between the two halves of a training step.
-__global__ __launch_bounds__(1024) void model_head_bwd_kernel(int kind, const float* __restrict__ pc,
-                                                             const float* __restrict__ pa, const float* __restrict__ T,
-                                                             HeadTensors ht, const float* __restrict__ dout,
-                                                             float* __restrict__ dpc, float* __restrict__ dpa, int B,
-                                                             int D, int F, int Mx, HeadLoss hl) {
-  extern __shared__ __align__(16) float hsm[];
-  const int total = head_total(ht);
-  const int tpad = (total + 3) & ~3;
-  float* ws = hsm;
-  float* dws = ws + tpad;  // parameter-gradient sums of this workgroup; element t is owned by thread t % 256
-  float* vec = dws + tpad;  // [kHdSPB][kHdVecStride]: the two pooled states (kHdXMax each), then 10 vectors of kHdMax
-  float* fpre = vec + kHdSPB * kHdVecStride;
-  float* ppre = fpre + kHdSPB * 2 * kHdMax;
-  const int tid = threadIdx.x;
-  const bool worker = tid < 32 * kHdSPB;                     // a lane of a sample; the others skip the per-sample loops
-  const int sl = worker ? tid >> 5 : 0, jj = worker ? (tid & 31) : (1 << 30);
-  float* my = vec + sl * kHdVecStride;
-  auto V = [&](int which) { return my + head_vec_off(which); };
-  head_load_weights(ht, ws);
-  for (int t = tid; t < tpad; t += blockDim.x) dws[t] = 0.f;
-  const int o_fp[2] = {0, D * F + F};
-  const int o_p0 = 2 * (D * F + F);
-  const int o_p[2] = {o_p0, o_p0 + F * Mx + Mx};
-  const int o_t = o_p0 + 2 * (F * Mx + Mx);
-
-  for (int b0 = blockIdx.x * kHdSPB; b0 < B; b0 += gridDim.x * kHdSPB) {
-    const int b = b0 + sl;
-    const bool live = worker && b < B;
-    __syncthreads();  // the previous group's outer products are done with vec
-    // xs of head_forward_mix = vectors kVX0,kVX1 (contiguous)
-    for (int g = 0; g < 2; ++g)
-      for (int i = jj; i < D; i += 32) V(kVX0 + g)[i] = live ? (g == 0 ? pc : pa)[(int64_t)b * D + i] : 0.f;
-    __syncthreads();
-    {  // forward (same arithmetic as head_forward_mix, on this kernel's vector layout)
-      for (int g = 0; g < 2; ++g)
-        for (int j = jj; j < F; j += 32) {
-          float acc = ws[o_fp[g] + D * F + j];
-          const float* x = V(kVX0 + g);
-          for (int i = 0; i < D; ++i) acc = fmaf(x[i], ws[o_fp[g] + i * F + j], acc);
-          fpre[(sl * 2 + g) * kHdMax + j] = acc;
-          V(kVFp0 + g)[j] = fmaxf(acc, 0.f);
-        }
-      __syncthreads();
-      for (int j = jj; j < Mx; j += 32) {
-        float m = 0.f;
-        for (int g = 0; g < 2; ++g) {
-          float acc = ws[o_p[g] + F * Mx + j];
-          const float* x = V(kVFp0 + g);
-          for (int i = 0; i < F; ++i) acc = fmaf(x[i], ws[o_p[g] + i * Mx + j], acc);
-          ppre[(sl * 2 + g) * kHdMax + j] = acc;
-          m += fmaxf(acc, 0.f);
-        }
-        V(kVMix)[j] = m;
-      }
-      __syncthreads();
-    }
-    const float* mx = V(kVMix);
-    // gradient of the prediction: given (plain head), or 2 (pred - y) / B * dloss once pred is known (loss entries)
-    const float gscale = hl.y ? 2.0f * hl.inv_B * hl.dloss[0] : 0.f;
-    float d = (live && !hl.y) ? dout[b] : 0.f;
-    float* top = V(kVTop);
-    // ---- top of the head: kVTop = gradient of [A,b,c] (kind 0) / of the hidden pre-activation (kind 1)
-    if (kind == 0) {
-      if (jj < 3) {
-        float acc = ws[o_t + Mx * 3 + jj];
-        for (int i = 0; i < Mx; ++i) acc = fmaf(mx[i], ws[o_t + i * 3 + jj], acc);
-        V(kVHid)[jj] = acc;
-      }
-      __syncthreads();
-      const float* vp = V(kVHid);
-      const float sp1 = softplus_stable(vp[1]), sp2 = softplus_stable(vp[2]);
-      const float Bc = fminf(fmaxf(sp1, 0.f), 20.f), Cc = fminf(fmaxf(sp2, 0.1f), 50.f);
-      const float den = (live ? T[b] : 300.f) / 100.0f + Cc + 1e-6f;
-      if (hl.y && live) d = gscale * (vp[0] + Bc / den - hl.y[b]);
-      if (jj == 0) V(kVOne)[0] = d;
-      float dvp[3];
-      dvp[0] = d;
-      dvp[1] = (sp1 >= 0.f && sp1 <= 20.f) ? d / den / (1.0f + expf(-vp[1])) : 0.f;  // clamp passes inside [min,max]
-      dvp[2] = (sp2 >= 0.1f && sp2 <= 50.f) ? -d * Bc / (den * den) / (1.0f + expf(-vp[2])) : 0.f;
-      if (jj < 3) top[jj] = jj == 0 ? dvp[0] : (jj == 1 ? dvp[1] : dvp[2]);
-      for (int i = jj; i < Mx; i += 32) {
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc = fmaf(ws[o_t + i * 3 + c], dvp[c], acc);
-        V(kVDpr0)[i] = ppre[(sl * 2 + 0) * kHdMax + i] > 0.f ? acc : 0.f;
-        V(kVDpr1)[i] = ppre[(sl * 2 + 1) * kHdMax + i] > 0.f ? acc : 0.f;
-      }
-    } else {
-      const int o_bh = o_t + Mx * F, o_wo = o_bh + F;
-      for (int j = jj; j < F; j += 32) {
-        float acc = ws[o_bh + j];
-        for (int i = 0; i < Mx; ++i) acc = fmaf(mx[i], ws[o_t + i * F + j], acc);
-        V(kVHid)[j] = fmaxf(acc, 0.f);
-      }
-      __syncthreads();
-      if (hl.y && live) {
-        float pred = ws[o_wo + F];
-        for (int j = 0; j < F; ++j) pred = fmaf(V(kVHid)[j], ws[o_wo + j], pred);  // as the forward kernel
-        d = gscale * (pred - hl.y[b]);
-      }
-      if (jj == 0) V(kVOne)[0] = d;
-      for (int j = jj; j < F; j += 32) top[j] = V(kVHid)[j] > 0.f ? ws[o_wo + j] * d : 0.f;
-      __syncthreads();
-      for (int i = jj; i < Mx; i += 32) {
-        float acc = 0.f;
-        for (int j = 0; j < F; ++j) acc = fmaf(ws[o_t + i * F + j], top[j], acc);
-        V(kVDpr0)[i] = ppre[(sl * 2 + 0) * kHdMax + i] > 0.f ? acc : 0.f;
-        V(kVDpr1)[i] = ppre[(sl * 2 + 1) * kHdMax + i] > 0.f ? acc : 0.f;
-      }
-    }
-    __syncthreads();
-    // ---- projections (relu) -> fingerprints (relu) -> pooled
-    for (int g = 0; g < 2; ++g) {
-      const float* dpr = V(kVDpr0 + g);
-      for (int i = jj; i < F; i += 32) {
-        float acc = 0.f;
-        for (int j = 0; j < Mx; ++j) acc = fmaf(ws[o_p[g] + i * Mx + j], dpr[j], acc);
-        V(kVDfp0 + g)[i] = fpre[(sl * 2 + g) * kHdMax + i] > 0.f ? acc : 0.f;
-      }
-    }
-    __syncthreads();
-    for (int g = 0; g < 2; ++g) {
-      const float* dfg = V(kVDfp0 + g);
-      float* dx = g == 0 ? dpc : dpa;
-      for (int i = jj; i < D; i += 32) {
-        float acc = 0.f;
-        for (int j = 0; j < F; ++j) acc = fmaf(ws[o_fp[g] + i * F + j], dfg[j], acc);
-        if (live) dx[(int64_t)b * D + i] = acc;
-      }
-    }
-    // ---- parameter gradients: element t of the packed layout = sum over the samples of a[i] * b[j]
-    for (int t = tid; t < total; t += blockDim.x) {
-      int base;
-      const int sgm = head_segment(ht, t, &base);
-      const int loc = t - base;
-      int va, vb, ncols;  // va < 0: a bias (sum of b[j])
-      switch (sgm) {
-        case 0: va = kVX0, vb = kVDfp0, ncols = F; break;
-        case 1: va = -1, vb = kVDfp0, ncols = F; break;
-        case 2: va = kVX1, vb = kVDfp1, ncols = F; break;
-        case 3: va = -1, vb = kVDfp1, ncols = F; break;
-        case 4: va = kVFp0, vb = kVDpr0, ncols = Mx; break;
-        case 5: va = -1, vb = kVDpr0, ncols = Mx; break;
-        case 6: va = kVFp1, vb = kVDpr1, ncols = Mx; break;
-        case 7: va = -1, vb = kVDpr1, ncols = Mx; break;
-        case 8: va = kVMix, vb = kVTop, ncols = kind == 0 ? 3 : F; break;
-        case 9: va = -1, vb = kVTop, ncols = kind == 0 ? 3 : F; break;
-        case 10: va = kVHid, vb = kVOne, ncols = 1; break;  // Wo (F,1): hidden * dout
-        default: va = -1, vb = kVOne, ncols = 1; break;     // bo
-      }
-      const int i = loc / ncols, j = loc - i * ncols;
-      float acc = 0.f;
-      if (va < 0) {
-#pragma unroll
-        for (int q = 0; q < kHdSPB; ++q) acc += vec[q * kHdVecStride + head_vec_off(vb) + j];
-      } else {
-#pragma unroll
-        for (int q = 0; q < kHdSPB; ++q)
-          acc = fmaf(vec[q * kHdVecStride + head_vec_off(va) + i], vec[q * kHdVecStride + head_vec_off(vb) + j], acc);
-      }
-      dws[t] += acc;
-    }
-  }
-  __syncthreads();
-  const float reg_scale = (hl.y && blockIdx.x == 0) ? 2.0f * hl.dloss[0] : 0.f;  // d/dW of l2 * sum(W^2), added once
-  for (int t = tid; t < total; t += blockDim.x) {
-    int base;
-    const int sgm = head_segment(ht, t, &base);
-    const float v = dws[t] + reg_scale * head_l2(ht, sgm) * ws[t];
-    if (v != 0.f) atomicAdd(head_gptr(ht, sgm) + (t - base), v);
-  }
-}
-
 }  // namespace
 
 int launch_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable, int64_t rows, int vocab, int dim,
@@ -2321,74 +1921,6 @@ int launch_adam_clipnorm(const void* table, const void* sizes, int n_vars, int64
                                                static_cast<const long long*>(sizes), lr, b1, b2, eps, clipnorm,
                                                corr1, corr2, reinterpret_cast<const long long*>(step_dev));
   return check_launch("adam_clipnorm");
-}
-
-static int head_tensor_table(int kind, const float* const* weights, float* const* grads, int D, int F, int Mx,
-                             HeadTensors* ht, const float* l2 = nullptr) {
-  const int sizes0[10] = {D * F, F, D * F, F, F * Mx, Mx, F * Mx, Mx, Mx * 3, 3};
-  const int sizes1[12] = {D * F, F, D * F, F, F * Mx, Mx, F * Mx, Mx, Mx * F, F, F, 1};
-  ht->n = kind == 0 ? 10 : 12;
-  int off = 0;
-  for (int i = 0; i < ht->n; ++i) {
-    if (!weights[i]) return fail(IMPNN_E_BADARG, "model_head: null weight tensor %d", i);
-    ht->w[i] = weights[i];
-    ht->g[i] = grads ? grads[i] : nullptr;
-    if (grads && !grads[i]) return fail(IMPNN_E_BADARG, "model_head_bwd: null gradient tensor %d", i);
-    ht->off[i] = off;
-    ht->l2[i] = l2 ? l2[i] : 0.f;
-    off += kind == 0 ? sizes0[i] : sizes1[i];
-  }
-  ht->off[ht->n] = off;
-  return IMPNN_OK;
-}
-
-int64_t model_head_loss_workspace_floats(int B) { return (B + kHdSPB - 1) / kHdSPB + 4; }
-
-int launch_model_head_tensors(int kind, const float* pc, const float* pa, const float* T, const float* const* weights,
-                              float* out, int B, int D, int F, int Mx, hipStream_t s, const float* l2, const float* y,
-                              float* loss_out, float* workspace) {
-  if (D > kHdXMax || F > kHdMax || Mx > kHdMax)
-    return fail(IMPNN_E_UNSUPPORTED, "model_head: dims D=%d (<= %d) F=%d Mx=%d (<= %d)", D, kHdXMax, F, Mx, kHdMax);
-  HeadTensors ht{};
-  if (int rc = head_tensor_table(kind, weights, nullptr, D, F, Mx, &ht, l2)) return rc;
-  HeadLoss hl{};
-  if (y) {  // workspace: [0] arrival counter (zero between calls) | [4...] one partial per workgroup
-    hl.y = y;
-    hl.loss_out = loss_out;
-    hl.counter = reinterpret_cast<unsigned int*>(workspace);
-    hl.partial = workspace + 4;
-    hl.inv_B = 1.0f / (float)B;
-  }
-  const size_t lds =
-      sizeof(float) * (((size_t)ht.off[ht.n] + 3) / 4 * 4 + (size_t)kHdSPB * (2 * kHdXMax + 6 * kHdMax));
-  if (lds > 156 * 1024) return fail(IMPNN_E_UNSUPPORTED, "model_head: weights do not fit LDS");
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)model_head_tensors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  model_head_tensors_kernel<<<(B + kHdSPB - 1) / kHdSPB, 256, lds, s>>>(kind, pc, pa, T, ht, out, B, D, F, Mx, hl);
-  return check_launch("model_head_tensors");
-}
-
-int launch_model_head_bwd(int kind, const float* pc, const float* pa, const float* T, const float* const* weights,
-                          const float* dout, float* dpc, float* dpa, float* const* grads, int B, int D, int F, int Mx,
-                          hipStream_t s, const float* l2, const float* y, const float* dloss) {
-  if (D > kHdXMax || F > kHdMax || Mx > kHdMax)
-    return fail(IMPNN_E_UNSUPPORTED, "model_head_bwd: dims D=%d (<= %d) F=%d Mx=%d (<= %d)", D, kHdXMax, F, Mx, kHdMax);
-  HeadTensors ht{};
-  if (int rc = head_tensor_table(kind, weights, grads, D, F, Mx, &ht, l2)) return rc;
-  HeadLoss hl{};
-  if (y) {
-    hl.y = y;
-    hl.dloss = dloss;
-    hl.inv_B = 1.0f / (float)B;
-  }
-  const size_t lds =
-      sizeof(float) * (2 * (((size_t)ht.off[ht.n] + 3) / 4 * 4) + (size_t)kHdSPB * (kHdVecStride + 4 * kHdMax));
-  if (lds > 156 * 1024) return fail(IMPNN_E_UNSUPPORTED, "model_head_bwd: weights do not fit LDS");
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)model_head_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int groups = (B + kHdSPB - 1) / kHdSPB;  // bounded grid: every workgroup flushes ~|weights| atomics once
-  model_head_bwd_kernel<<<groups < 512 ? groups : 512, 1024, lds, s>>>(kind, pc, pa, T, ht, dout, dpc, dpa, B, D, F, Mx, hl);
-  return check_launch("model_head_bwd");
 }
 
 int launch_bond_type_matrices_multi(const float* tb, const float* const* W, float* const* out, int n, int Vb, int K,

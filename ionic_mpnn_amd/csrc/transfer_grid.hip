@@ -22,8 +22,6 @@ namespace impnn {
 namespace {
 
 constexpr int kH1 = 256, kH2 = 128, kH3 = 64;
-constexpr int kMaxDim = 64;   // fp_size, mixing_size
-constexpr int kMaxX = 128;    // pooled width
 constexpr int kHalfRows = 8;  // ion rows per 256-thread workgroup, 32 threads per row (as head_ion_mix_kernel)
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -89,11 +87,11 @@ __global__ __launch_bounds__(256) void transfer_ion_half_kernel(const float* __r
   const int nfp = D * F, np = F * Mx;
   float* Wfp = sm;                                 // Wfp_g D*F
   float* bfp = Wfp + ((nfp + 3) & ~3);             // bfp_g F
-  float* Wp = bfp + kMaxDim;                       // Wp_g F*Mx
+  float* Wp = bfp + kHeadMaxDim;                       // Wp_g F*Mx
   float* bp = Wp + ((np + 3) & ~3);                // bp_g Mx
-  float* xs = bp + kMaxDim;                        // [kHalfRows][kMaxX]
-  float* fp = xs + kHalfRows * kMaxX;              // [kHalfRows][kMaxDim]
-  float* mix = fp + kHalfRows * kMaxDim;           // [kHalfRows][kMaxDim]
+  float* xs = bp + kHeadMaxDim;                        // [kHalfRows][kHeadMaxX]
+  float* fp = xs + kHalfRows * kHeadMaxX;              // [kHalfRows][kHeadMaxDim]
+  float* mix = fp + kHalfRows * kHeadMaxDim;           // [kHalfRows][kHeadMaxDim]
   const int tid = threadIdx.x, sl = tid >> 5, jj = tid & 31;
   const int64_t m = (int64_t)blockIdx.x * kHalfRows + sl;
   const bool live = m < M;
@@ -101,15 +99,15 @@ __global__ __launch_bounds__(256) void transfer_ion_half_kernel(const float* __r
   for (int t = tid; t < np; t += blockDim.x) Wp[t] = wp_g[t];
   for (int t = tid; t < F; t += blockDim.x) bfp[t] = bfp_g[t];
   for (int t = tid; t < Mx; t += blockDim.x) bp[t] = bp_g[t];
-  for (int i = jj; i < D; i += 32) xs[sl * kMaxX + i] = live ? pooled[m * D + i] : 0.f;
+  for (int i = jj; i < D; i += 32) xs[sl * kHeadMaxX + i] = live ? pooled[m * D + i] : 0.f;
   __syncthreads();
-  for (int j = jj; j < F; j += 32) fp[sl * kMaxDim + j] = head_relu(head_chain(xs + sl * kMaxX, Wfp + j, F, D, bfp[j]));
+  for (int j = jj; j < F; j += 32) fp[sl * kHeadMaxDim + j] = head_relu(head_chain(xs + sl * kHeadMaxX, Wfp + j, F, D, bfp[j]));
   __syncthreads();
-  for (int j = jj; j < Mx; j += 32) mix[sl * kMaxDim + j] = head_relu(head_chain(fp + sl * kMaxDim, Wp + j, Mx, F, bp[j]));
+  for (int j = jj; j < Mx; j += 32) mix[sl * kHeadMaxDim + j] = head_relu(head_chain(fp + sl * kHeadMaxDim, Wp + j, Mx, F, bp[j]));
   __syncthreads();
   if (live)
     for (int j = jj; j < kH1; j += 32)  // W1 from L2: 32 consecutive columns per row of threads
-      u[m * kH1 + j] = head_chain(mix + sl * kMaxDim, w1 + j, kH1, Mx, b1 ? b1[j] : 0.f);
+      u[m * kH1 + j] = head_chain(mix + sl * kHeadMaxDim, w1 + j, kH1, Mx, b1 ? b1[j] : 0.f);
 }
 
 // ---- the grid.  One workgroup owns kTgTileC cations x kTgTileA anions; a wave owns two cations of the tile, i.e. two
@@ -309,8 +307,8 @@ int launch_transfer_grid_prepare(const float* const* weights, const float* movin
 
 int launch_transfer_ion_half(int ion, const float* pooled, const float* const* weights, float* u, int M, int D, int F,
                              int Mx, hipStream_t s) {
-  const size_t lds = sizeof(float) * (align4((size_t)D * F) + align4((size_t)F * Mx) + 2 * kMaxDim +
-                                      (size_t)kHalfRows * (kMaxX + 2 * kMaxDim));  // <= 56.5 KiB
+  const size_t lds = sizeof(float) * (align4((size_t)D * F) + align4((size_t)F * Mx) + 2 * kHeadMaxDim +
+                                      (size_t)kHalfRows * (kHeadMaxX + 2 * kHeadMaxDim));  // <= 56.5 KiB
   transfer_ion_half_kernel<<<(int)(((int64_t)M + kHalfRows - 1) / kHalfRows), 256, lds, s>>>(
       pooled, weights[2 * ion], weights[2 * ion + 1], weights[4 + 2 * ion], weights[5 + 2 * ion], weights[8],
       ion == 1 ? weights[9] : nullptr, u, M, D, F, Mx);

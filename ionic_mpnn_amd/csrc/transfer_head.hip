@@ -19,7 +19,6 @@ namespace {
 
 constexpr int kThSPB = 8, kThThreads = 256;
 constexpr int kThH1 = 256, kThH2 = 128, kThH3 = 64;
-constexpr int kThXMax = 128, kThMax = 64;  // widest pooled state; widest fp_size / mixing_size
 constexpr int kThStatLanes = 16;  // sample lanes per feature in the statistics kernels
 
 struct ThTensors {
@@ -99,10 +98,10 @@ __device__ __forceinline__ float th_loss_grad(int kind, float delta, float e) {
 }
 
 struct ThSmem {
-  float x[kThSPB * 2 * kThXMax];
-  float fp[kThSPB * 2 * kThMax];
-  float pr[kThSPB * 2 * kThMax];
-  float mix[kThSPB * kThMax];
+  float x[kThSPB * 2 * kHeadMaxX];
+  float fp[kThSPB * 2 * kHeadMaxDim];
+  float pr[kThSPB * 2 * kHeadMaxDim];
+  float mix[kThSPB * kHeadMaxDim];
   float a1[kThSPB * kThH1];
   float bn[kThSPB * kThH1];
   float a2[kThSPB * kThH2];
@@ -190,31 +189,31 @@ __global__ __launch_bounds__(kThThreads) void th_forward(const float* __restrict
   if (flags & kThPre) {
     for (int idx = tid; idx < kThSPB * 2 * D; idx += kThThreads) {
       const int s = idx / (2 * D), r = idx - s * 2 * D, g = r / D, i = r - g * D;
-      sm.x[(s * 2 + g) * kThXMax + i] = b0 + s < B ? (g == 0 ? pc : pa)[(int64_t)(b0 + s) * D + i] : 0.f;
+      sm.x[(s * 2 + g) * kHeadMaxX + i] = b0 + s < B ? (g == 0 ? pc : pa)[(int64_t)(b0 + s) * D + i] : 0.f;
     }
     __syncthreads();
     for (int g = 0; g < 2; ++g)
-      th_dense(sm.x + g * kThXMax, 2 * kThXMax, D, ht.w[2 * g], F, 1, ht.w[2 * g + 1], F, sm.fp + g * kThMax,
-               2 * kThMax, true, sm.part);
+      th_dense(sm.x + g * kHeadMaxX, 2 * kHeadMaxX, D, ht.w[2 * g], F, 1, ht.w[2 * g + 1], F, sm.fp + g * kHeadMaxDim,
+               2 * kHeadMaxDim, true, sm.part);
     for (int g = 0; g < 2; ++g)
-      th_dense(sm.fp + g * kThMax, 2 * kThMax, F, ht.w[4 + 2 * g], Mx, 1, ht.w[5 + 2 * g], Mx, sm.pr + g * kThMax,
-               2 * kThMax, true, sm.part);
+      th_dense(sm.fp + g * kHeadMaxDim, 2 * kHeadMaxDim, F, ht.w[4 + 2 * g], Mx, 1, ht.w[5 + 2 * g], Mx, sm.pr + g * kHeadMaxDim,
+               2 * kHeadMaxDim, true, sm.part);
     for (int idx = tid; idx < kThSPB * Mx; idx += kThThreads) {
       const int s = idx / Mx, j = idx - s * Mx;
-      sm.mix[s * kThMax + j] = sm.pr[(s * 2) * kThMax + j] + sm.pr[(s * 2 + 1) * kThMax + j];
+      sm.mix[s * kHeadMaxDim + j] = sm.pr[(s * 2) * kHeadMaxDim + j] + sm.pr[(s * 2 + 1) * kHeadMaxDim + j];
     }
     __syncthreads();
-    th_dense(sm.mix, kThMax, Mx, ht.w[8], kThH1, 1, ht.w[9], kThH1, sm.a1, kThH1, true, sm.part);
+    th_dense(sm.mix, kHeadMaxDim, Mx, ht.w[8], kThH1, 1, ht.w[9], kThH1, sm.a1, kThH1, true, sm.part);
     if (saved) {
       for (int idx = tid; idx < kThSPB * 2 * F; idx += kThThreads) {
         const int s = idx / (2 * F), r = idx - s * 2 * F, g = r / F, j = r - g * F;
-        if (b0 + s < B) saved[so.fp + (int64_t)(b0 + s) * 2 * F + r] = sm.fp[(s * 2 + g) * kThMax + j];
+        if (b0 + s < B) saved[so.fp + (int64_t)(b0 + s) * 2 * F + r] = sm.fp[(s * 2 + g) * kHeadMaxDim + j];
       }
       for (int idx = tid; idx < kThSPB * 2 * Mx; idx += kThThreads) {
         const int s = idx / (2 * Mx), r = idx - s * 2 * Mx, g = r / Mx, j = r - g * Mx;
-        if (b0 + s < B) saved[so.pr + (int64_t)(b0 + s) * 2 * Mx + r] = sm.pr[(s * 2 + g) * kThMax + j];
+        if (b0 + s < B) saved[so.pr + (int64_t)(b0 + s) * 2 * Mx + r] = sm.pr[(s * 2 + g) * kHeadMaxDim + j];
       }
-      th_store_tile(sm.mix, kThMax, saved + so.mix, Mx, b0, B);
+      th_store_tile(sm.mix, kHeadMaxDim, saved + so.mix, Mx, b0, B);
       th_store_tile(sm.a1, kThH1, saved + so.a1, kThH1, b0, B);
     }
   }
@@ -439,30 +438,30 @@ __global__ __launch_bounds__(kThThreads) void th_bwd_pre(ThTensors ht, const flo
     __syncthreads();
   }
   if (!(flags & kThNeedBase)) return;
-  th_dense(sm.a1, kThH1, kThH1, ht.w[8], 1, kThH1, nullptr, Mx, sm.mix, kThMax, false, sm.part);  // dmix
+  th_dense(sm.a1, kThH1, kThH1, ht.w[8], 1, kThH1, nullptr, Mx, sm.mix, kHeadMaxDim, false, sm.part);  // dmix
   for (int idx = tid; idx < kThSPB * 2 * Mx; idx += kThThreads) {
     const int s = idx / (2 * Mx), r = idx - s * 2 * Mx, g = r / Mx, j = r - g * Mx;
     const bool live = b0 + s < B;
-    const float v = live && saved[so.pr + (int64_t)(b0 + s) * 2 * Mx + r] > 0.f ? sm.mix[s * kThMax + j] : 0.f;
-    sm.pr[(s * 2 + g) * kThMax + j] = v;
+    const float v = live && saved[so.pr + (int64_t)(b0 + s) * 2 * Mx + r] > 0.f ? sm.mix[s * kHeadMaxDim + j] : 0.f;
+    sm.pr[(s * 2 + g) * kHeadMaxDim + j] = v;
     if (live) work[wo.dpr + (int64_t)(b0 + s) * 2 * Mx + r] = v;
   }
   __syncthreads();
   for (int g = 0; g < 2; ++g)
-    th_dense(sm.pr + g * kThMax, 2 * kThMax, Mx, ht.w[4 + 2 * g], 1, Mx, nullptr, F, sm.fp + g * kThMax, 2 * kThMax,
+    th_dense(sm.pr + g * kHeadMaxDim, 2 * kHeadMaxDim, Mx, ht.w[4 + 2 * g], 1, Mx, nullptr, F, sm.fp + g * kHeadMaxDim, 2 * kHeadMaxDim,
              false, sm.part);
   for (int idx = tid; idx < kThSPB * 2 * F; idx += kThThreads) {
     const int s = idx / (2 * F), r = idx - s * 2 * F, g = r / F, j = r - g * F;
     const bool live = b0 + s < B;
-    const float v = live && saved[so.fp + (int64_t)(b0 + s) * 2 * F + r] > 0.f ? sm.fp[(s * 2 + g) * kThMax + j] : 0.f;
-    sm.fp[(s * 2 + g) * kThMax + j] = v;
+    const float v = live && saved[so.fp + (int64_t)(b0 + s) * 2 * F + r] > 0.f ? sm.fp[(s * 2 + g) * kHeadMaxDim + j] : 0.f;
+    sm.fp[(s * 2 + g) * kHeadMaxDim + j] = v;
     if (live) work[wo.dfp + (int64_t)(b0 + s) * 2 * F + r] = v;
   }
   __syncthreads();
   if (!(flags & kThNeedPooled)) return;
   for (int g = 0; g < 2; ++g) {
-    th_dense(sm.fp + g * kThMax, 2 * kThMax, F, ht.w[2 * g], 1, F, nullptr, D, sm.x, kThXMax, false, sm.part);
-    th_store_tile(sm.x, kThXMax, g == 0 ? dpc : dpa, D, b0, B);
+    th_dense(sm.fp + g * kHeadMaxDim, 2 * kHeadMaxDim, F, ht.w[2 * g], 1, F, nullptr, D, sm.x, kHeadMaxX, false, sm.part);
+    th_store_tile(sm.x, kHeadMaxX, g == 0 ? dpc : dpa, D, b0, B);
     __syncthreads();
   }
 }
@@ -505,8 +504,8 @@ __global__ __launch_bounds__(kThThreads) void th_param_grads(ThJobs jobs, const 
 }
 
 int th_check_dims(const char* what, int D, int F, int Mx) {
-  if (D > kThXMax || F > kThMax || Mx > kThMax)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= %d) F=%d Mx=%d (<= %d)", what, D, kThXMax, F, Mx, kThMax);
+  if (D > kHeadMaxX || F > kHeadMaxDim || Mx > kHeadMaxDim)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: dims D=%d (<= %d) F=%d Mx=%d (<= %d)", what, D, kHeadMaxX, F, Mx, kHeadMaxDim);
   return IMPNN_OK;
 }
 

@@ -704,7 +704,7 @@ class MPNNModel:
 
     def head(self, pooled_cat, pooled_an, temperature=None, trace=None, differentiable=False, training=False):
         if self.kind == "transfer":
-            if trace is None and not differentiable and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64:
+            if trace is None and not differentiable and self._head_kernels_cover():
                 return ops.transfer_head(pooled_cat, pooled_an, self._head_tensors(), self._transfer_cfg(False))
             # layer by layer (traces, model(x, training=True), widths the kernels do not cover)
             fp_cat, fp_an = self.branches["cat"]["fp"](pooled_cat), self.branches["an"]["fp"](pooled_an)
@@ -714,11 +714,10 @@ class MPNNModel:
             x = self.mp_bn_1(self.mp_dense_1(x), training=training and getattr(self, "_bn_training", True))
             x = self.mp_dropout(self.mp_dense_2(x), training=training, counter=self.dropout_counter())
             return self.melting_point(self.mp_dense_3(x))
-        if trace is None and not differentiable and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64:
+        if trace is None and not differentiable and self._head_kernels_cover():
             return ops.model_head(self.kind, pooled_cat, pooled_an, temperature, self._packed_head(), self.fp_size,
                                   self.mixing_size)  # one launch
-        if trace is None and differentiable and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64 \
-                and torch.is_grad_enabled():
+        if trace is None and differentiable and self._head_kernels_cover() and torch.is_grad_enabled():
             from . import autograd
             T = temperature if self.kind == "viscosity" else None
             return autograd.ModelHead.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
@@ -795,7 +794,7 @@ class MPNNModel:
     def _loss(self, inputs, y, training):
         from . import train
         y = torch.as_tensor(y, dtype=torch.float32).to(self.device).reshape(-1, 1)
-        covered = y.shape[0] > 0 and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
+        covered = y.shape[0] > 0 and self._head_kernels_cover()
         if self.kind == "transfer" and covered:
             return self._transfer_loss(self._to_device(inputs), y, training)
         if training and torch.is_grad_enabled() and covered and self._loss_name() == "mse":
@@ -1035,12 +1034,16 @@ class MPNNModel:
                 out.append(torch.cat([p[g] for p in parts], dim=0)[:n].contiguous())
         return out[0], out[1]
 
+    def _head_kernels_cover(self):
+        """The head kernels (model head, transfer head and their grids) cover the model's widths."""
+        return self.atom_dim <= ops.HEAD_MAX_X and max(self.fp_size, self.mixing_size) <= ops.HEAD_MAX_DIM
+
     def _grid_kernels_cover(self):
-        return self.kind != "transfer" and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
+        return self.kind != "transfer" and self._head_kernels_cover()
 
     def _transfer_grid_covers(self):
         """The matrix-core grid of the transfer head (impnn_transfer_ion_half / impnn_transfer_head_grid) covers it."""
-        return self.kind == "transfer" and self.atom_dim <= 128 and max(self.fp_size, self.mixing_size) <= 64
+        return self.kind == "transfer" and self._head_kernels_cover()
 
     def predict_grid(self, cations, anions, temperatures=None, return_params=False, max_pairs_per_launch=None,
                      batch_size=4096):

@@ -680,6 +680,11 @@ def gather_rows(srcs, dsts, rows):
         check(_lib.load().impnn_gather_rows(n, st, dt, bt, ptr(rows), n_rows, stream_ptr()))
 
 
+# the widths every head kernel covers: kHeadMaxX / kHeadMaxDim of csrc/common.h (tests/test_cabi.py holds them equal)
+HEAD_MAX_X = 128    # pooled width (atom_dim)
+HEAD_MAX_DIM = 64   # fp_size, mixing_size
+
+
 def model_head(kind, pooled_cat, pooled_an, temperature, head_weights, fp_size, mixing_size):
     """Everything after GlobalSumPool in one launch (impnn_model_head): kind "viscosity" or "melting_point"."""
     require_gpu(pooled_cat, pooled_an, head_weights)

@@ -421,3 +421,147 @@ def test_typed_message_status_codes_are_pinned():
             assert rc == _UNS and what in msg, (entry, kw, msg)
     rc, msg = call("impnn_message_reduce_typed_bwd_scratch", edge_scratch=None)
     assert rc == _BAD and b"null pointer" in msg
+
+
+# ---- the model head family's argument rules, pinned entry by entry (recorded on the entries as they were before their
+# checks were shared).  Every call returns before any device call: pointers that must not be null are addresses inside
+# a host buffer that nothing dereferences, the two pointer tables and l2 are real host arrays, and a case that has to
+# show that a check passed carries a width above the limit, so that it ends as unsupported.
+_MH_SHAPE = ["B", "D", "F", "Mx"]
+_MH_PARAMS = {
+    "impnn_model_head": ["kind", "pc", "pa", "T", "w", "out"] + _MH_SHAPE,
+    "impnn_model_head_tensors": ["kind", "pc", "pa", "T", "weights", "out"] + _MH_SHAPE,
+    "impnn_model_head_bwd": ["kind", "pc", "pa", "T", "weights", "dout", "dpc", "dpa", "dweights"] + _MH_SHAPE,
+    "impnn_model_head_loss": ["kind", "pc", "pa", "T", "weights", "l2", "y", "pred", "loss", "workspace",
+                              "workspace_floats"] + _MH_SHAPE,
+    "impnn_model_head_loss_bwd": ["kind", "pc", "pa", "T", "weights", "l2", "y", "dloss", "dpc", "dpa", "dweights"]
+                                 + _MH_SHAPE,
+}
+_MH_POINTERS = ("pc", "pa", "T", "w", "out", "weights", "dout", "dpc", "dpa", "dweights", "l2", "y", "pred", "loss",
+                "dloss", "workspace")
+_MH_OPTIONAL = ("T", "pred")  # T: kind 1 takes none; pred: the loss forward may drop the predictions
+_MH_KIND = b"kind must be 0 (viscosity) or 1 (melting point)"
+
+
+def test_model_head_status_codes_are_pinned():
+    """Status code and error text of the five model head entries for each class of refusal, in the order the rules
+    apply: kind, shape, zero work, null pointers, workspace size (loss forward), then in the launcher widths, null
+    weight / gradient tensor i, LDS fit."""
+    lib = _lib.load()
+    host = (C.c_char * 512)()
+    at = C.addressof(host)
+    n_t = {0: 10, 1: 12}
+
+    def table(null_at=()):
+        t = (C.c_void_p * 12)(*[at + 16 * (i + 1) for i in range(12)])
+        for i in null_at:
+            t[i] = None
+        return C.cast(t, _lib.PP)
+
+    ptrs = {n: at + 16 * (i + 1) for i, n in enumerate(_MH_POINTERS)}
+    ptrs.update(weights=table(), dweights=table(), l2=(C.c_float * 12)())
+    nulls = {n: None for n in _MH_POINTERS}
+    need = lib.impnn_model_head_loss_workspace_floats
+
+    def call(entry, **kw):
+        args = dict(ptrs, kind=0, B=9, D=32, F=32, Mx=20)
+        args.update(kw)
+        args.setdefault("workspace_floats", 1 << 40)
+        fn = getattr(lib, entry)
+        row = [args[n] for n in _MH_PARAMS[entry]] + [None]
+        assert len(row) == len(fn.argtypes), entry
+        return fn(*row), lib.impnn_last_error_string()
+
+    assert set(_MH_PARAMS) == {n for n in _lib.SIGNATURES if n.startswith("impnn_model_head") and
+                               not n.endswith("_floats")}
+    assert [need(b) for b in (-1, 0, 1, 8, 9)] == [4, 4, 5, 5, 6]
+    for entry, names in _MH_PARAMS.items():
+        short = entry.encode()
+        loss = "_loss" in entry
+        bwd = entry.endswith("_bwd")
+        packed = entry == "impnn_model_head"
+        launcher = b"model_head_bwd: " if bwd else b"model_head: "
+        required = [n for n in names if n in _MH_POINTERS and n not in _MH_OPTIONAL]
+        # 1. kind, before everything else
+        for kw in (dict(kind=2), dict(kind=-1), dict(kind=2, B=-1, **nulls), dict(kind=2, B=0, D=0)):
+            rc, msg = call(entry, **kw)
+            assert rc == _BAD and msg == short + b": " + _MH_KIND, (entry, kw, msg)
+        # 2. shape
+        for kw in (dict(B=-1), dict(D=0), dict(F=0), dict(Mx=0), dict(B=-1, **nulls), dict(B=0, D=0, **nulls),
+                   dict(D=-1, F=65)):
+            rc, msg = call(entry, **kw)
+            assert rc == _BAD and msg == short + b": bad shape", (entry, kw, msg)
+        # 3. zero work: a success with no pointer looked at and no width judged (the plain entries); the loss entries
+        # have no empty batch
+        for kw in (dict(), dict(D=129), dict(F=65, Mx=65), dict(kind=1, D=129)):
+            rc, msg = call(entry, B=0, workspace_floats=0, **nulls, **kw)
+            if loss:
+                assert rc == _BAD and msg == short + b": bad shape", (entry, kw, msg)
+            else:
+                assert rc == 0, (entry, kw, msg)
+        # 4. null pointers: all of them, each required one alone, before the workspace size and the widths
+        cases = [dict(nulls), dict(nulls, workspace_floats=0), dict(nulls, D=129)] + [{n: None} for n in required]
+        cases += [dict(c, kind=1) for c in cases] + [dict(T=None), dict(T=None, D=129)]
+        for kw in cases:
+            rc, msg = call(entry, **kw)
+            assert rc == _BAD and msg == short + b": null pointer", (entry, kw, msg)
+        # the temperature is kind 0's alone, and the loss forward's predictions are optional: the call goes on to the
+        # widths
+        for kw in [dict(kind=1, T=None)] + ([dict(pred=None), dict(kind=1, pred=None, T=None)] if "pred" in names else []):
+            rc, msg = call(entry, D=129, **kw)
+            assert rc == _UNS and msg.startswith(launcher + b"dims D=129"), (entry, kw, msg)
+        # 5. the loss forward's workspace one float short, before the widths; exactly enough passes
+        if "workspace_floats" in names:
+            for kw in (dict(), dict(D=129), dict(B=1), dict(B=8), dict(B=17, F=65), dict(kind=1, T=None)):
+                size = need(kw.get("B", 9))
+                rc, msg = call(entry, workspace_floats=size - 1, **kw)
+                assert rc == _WS and msg == b"model_head_loss: workspace of %d floats is too small" % (size - 1), (entry, kw, msg)
+            rc, msg = call(entry, workspace_floats=need(9), D=129)
+            assert rc == _UNS, (entry, msg)
+        # 6. widths, judged by the launcher, before the pointer tables are read
+        for kw, dims in ((dict(D=129), (129, 32, 20)), (dict(F=65), (32, 65, 20)), (dict(Mx=65), (32, 32, 65)),
+                         (dict(D=129, F=65, Mx=65), (129, 65, 65)), (dict(kind=1, D=4096), (4096, 32, 20))):
+            for tables in (dict(), dict(weights=table(range(12)), dweights=table(range(12)))):
+                rc, msg = call(entry, **kw, **tables)
+                assert rc == _UNS and msg == launcher + b"dims D=%d (<= 128) F=%d Mx=%d (<= 64)" % dims, (entry, kw, msg)
+        if packed:
+            continue  # no table, and every width within the limits fits its LDS: the next step is the launch
+        # 7. tensor i of a table is null: weight i, then gradient i, tensor by tensor; only the kind's own tensors count
+        for kind in (0, 1):
+            for i in range(n_t[kind]):
+                rc, msg = call(entry, kind=kind, weights=table([i]), dweights=table([i]))
+                assert rc == _BAD and msg == b"model_head: null weight tensor %d" % i, (entry, kind, i, msg)
+                if not bwd:
+                    continue
+                rc, msg = call(entry, kind=kind, dweights=table([i]))
+                assert rc == _BAD and msg == b"model_head_bwd: null gradient tensor %d" % i, (entry, kind, i, msg)
+                if i + 1 < n_t[kind]:
+                    rc, msg = call(entry, kind=kind, weights=table([i + 1]), dweights=table([i]))
+                    assert rc == _BAD and msg == b"model_head_bwd: null gradient tensor %d" % i, (entry, kind, i, msg)
+        if bwd:
+            # a null past kind 0's ten tensors is not looked at: the call goes on to the LDS fit
+            rc, msg = call(entry, kind=0, D=128, F=64, Mx=64, weights=table([10, 11]), dweights=table([10, 11]))
+            assert rc == _UNS and msg == b"model_head_bwd: weights do not fit LDS", (entry, msg)
+            # 8. LDS fit, after the tables: the backward keeps the weights and their gradient sums in LDS, 2 * padded
+            # weight floats + 9216 floats of sample vectors against 156 KB, so 15 360 weight floats fit and 15 420 do not
+            for kw in (dict(kind=0, D=128, F=64, Mx=64), dict(kind=1, D=128, F=64, Mx=64), dict(kind=0, D=128, F=48, Mx=30)):
+                rc, msg = call(entry, **kw)
+                assert rc == _UNS and msg == b"model_head_bwd: weights do not fit LDS", (entry, kw, msg)
+                rc, msg = call(entry, dweights=table([3]), **kw)
+                assert rc == _BAD and msg == b"model_head_bwd: null gradient tensor 3", (entry, kw, msg)
+    assert lib.impnn_model_head_floats(0, 128, 48, 30) == 15417
+
+
+def test_head_width_limits_match_the_library():
+    """ops.HEAD_MAX_X / HEAD_MAX_DIM, which decide in model.py whether a head kernel is called, are the library's
+    kHeadMaxX / kHeadMaxDim: impnn_head_ion_mix judges the widths before it finds that M = 0 leaves nothing to do."""
+    from ionic_mpnn_amd import ops
+    lib = _lib.load()
+    X, Dm = ops.HEAD_MAX_X, ops.HEAD_MAX_DIM
+    assert (X, Dm) == (128, 64)
+    for kind in (0, 1):
+        assert lib.impnn_head_ion_mix(kind, 0, None, None, None, 0, X, Dm, Dm, None) == 0
+        for D, F, Mx in ((X + 1, Dm, Dm), (X, Dm + 1, Dm), (X, Dm, Dm + 1), (X + 1, Dm + 1, Dm + 1)):
+            assert lib.impnn_head_ion_mix(kind, 0, None, None, None, 0, D, F, Mx, None) == _UNS, (D, F, Mx)
+            assert lib.impnn_last_error_string() == b"impnn_head_ion_mix: dims D=%d (<= %d) F=%d Mx=%d (<= %d)" % (
+                D, X, F, Mx, Dm)
