@@ -506,6 +506,39 @@ int impnn_transfer_ion_half(int32_t ion, const float* pooled, const float* const
 int impnn_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
                              float* out, int32_t C, int32_t A, impnn_stream_t stream);
 
+/* ---- the k best pairs of a screen, selected on the GPU: the grids above without their (C,A[,nT]) output.  The
+ *      selecting kernels run the tile arithmetic of impnn_head_grid / impnn_transfer_head_grid (a selected value has the
+ *      bits those entries write for the pair) in persistent workgroups and keep a running top k per temperature in LDS;
+ *      a second small launch merges the workgroups' lists.  No C x A buffer, no float atomics, no global atomics.
+ *      Order: a pair's entry is (key << 32) | (i * A + j), compared as an unsigned 64-bit integer.  key is the
+ *      order-preserving integer image of the float (-0.0 < +0.0), complemented when `largest` != 0; every NaN has the
+ *      key 0xFFFFFFFF in both directions.  So: by value, ties by cation then anion index, NaN last (by index), and
+ *      the result is the exact top k under that order - independent of `workgroups` and of any schedule.
+ *      Outputs, sorted: values (nT,k) float (a NaN comes back as the quiet NaN 0x7FC00000), cation (nT,k) and anion
+ *      (nT,k) int32; the melting-point and transfer grids have one row (nT = 0 in the call).  With C * A < k only the
+ *      first C * A slots of a row are pairs; the rest hold NaN / -1 / -1.
+ *      Limits of one call: 1 <= k <= 1024; kind 0: 1 <= nT <= impnn_grid_topk_max_temperatures() (4; split longer
+ *      sweeps, a row does not depend on the others); C * A < 2^32; the widths of impnn_head_grid.
+ *      workgroups: 0 = the default (two per compute unit, at most one per tile); otherwise that many, at most one per
+ *      tile.  workspace: impnn_grid_topk_workspace_bytes bytes for the same (family, C, A, nT, k, workgroups), 8-byte
+ *      aligned, family 0 = impnn_head_grid_topk, 1 = impnn_transfer_head_grid_topk; it holds [workgroups][nT][k]
+ *      entries between the two launches and carries nothing from call to call.
+ *      impnn_transfer_head_grid_topk: u rows and image as impnn_transfer_head_grid (16B aligned).
+ *      Checks in order: shape (kind, sizes, nT, k, the limits, C * A, workgroups >= 0; IMPNN_E_BADARG, a limit
+ *      IMPNN_E_UNSUPPORTED); zero work (C == 0 or A == 0: IMPNN_OK, nothing touched); null pointers, then alignment and
+ *      the image size; the workspace size (IMPNN_E_WORKSPACE).  No allocation, no synchronisation, no state. */
+int32_t impnn_grid_topk_max_temperatures(void);
+int impnn_grid_topk_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t k, int32_t workgroups,
+                                    size_t* need);
+int impnn_head_grid_topk(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                         const float* head_weights, int32_t k, int32_t largest, float* values, int32_t* cation,
+                         int32_t* anion, void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT,
+                         int32_t D, int32_t F, int32_t Mx, int32_t workgroups, impnn_stream_t stream);
+int impnn_transfer_head_grid_topk(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                  int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
+                                  void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
+                                  impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

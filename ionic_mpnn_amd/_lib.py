@@ -78,6 +78,10 @@ SIGNATURES = {
     "impnn_transfer_grid_prepare": (C.c_int, [PP, vp, vp, f32, vp, i64, vp]),
     "impnn_transfer_ion_half": (C.c_int, [i32, vp, PP, vp, i32, i32, i32, i32, vp]),
     "impnn_transfer_head_grid": (C.c_int, [vp, vp, vp, i64, vp, i32, i32, vp]),
+    "impnn_grid_topk_max_temperatures": (i32, []),
+    "impnn_grid_topk_workspace_bytes": (C.c_int, [i32] * 6 + [C.POINTER(sz)]),
+    "impnn_head_grid_topk": (C.c_int, [i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz] + [i32] * 7 + [vp]),
+    "impnn_transfer_head_grid_topk": (C.c_int, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, sz, i32, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

@@ -724,6 +724,87 @@ int impnn_transfer_head_grid(const float* u_cat, const float* u_an, const float*
   return launch ? launch_transfer_head_grid(u_cat, u_an, image, out, C, A, as_stream(stream)) : IMPNN_OK;
 }
 
+// ---- top-k selection over a cation x anion grid (include/impnn.h; grid_select.hip).  One place applies the family's
+// rules in their fixed order: shape, zero work, null pointers, workspace size.
+namespace {
+// shape only: what the workspace query and the two entries share
+int grid_topk_shape(const char* entry, int family, int C, int A, int nT, int k, int workgroups) {
+  if (family != 0 && family != 1) return fail(IMPNN_E_BADARG, "%s: family must be 0 (head grid) or 1 (transfer grid)", entry);
+  if (C < 0 || A < 0 || nT < 0 || workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (k < 1) return fail(IMPNN_E_BADARG, "%s: k=%d must be at least 1", entry, k);
+  if (k > kSelectMaxK) return fail(IMPNN_E_UNSUPPORTED, "%s: k=%d entries (<= %d per call)", entry, k, kSelectMaxK);
+  if (nT > kSelectMaxT)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
+  if ((int64_t)C * A >= (int64_t)1 << 32)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (< 2^32 per call); split the cation axis", entry,
+                (long long)((int64_t)C * A));
+  return IMPNN_OK;
+}
+
+int grid_topk_checked(const char* entry, const GridTopkCall& c, bool widths_ok, bool pointers_ok, int64_t image_floats,
+                      size_t workspace_bytes) {
+  if (c.family == 0) {
+    if (c.kind != 0 && c.kind != 1) return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", entry);
+    if (!widths_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+    if (c.kind == 0 && c.nT < 1 && c.nT >= 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
+    if (c.kind == 1 && c.nT > 0)
+      return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", entry);
+  } else if (image_floats < 0) {
+    return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  }
+  if (int rc = grid_topk_shape(entry, c.family, c.C, c.A, c.nT, c.k, c.workgroups)) return rc;
+  if (c.family == 0)
+    if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
+  if (c.C == 0 || c.A == 0) return IMPNN_OK;
+  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
+  if ((reinterpret_cast<uintptr_t>(c.workspace) & 7u) != 0) return fail(IMPNN_E_BADARG, "%s: the workspace must be 8-byte aligned", entry);
+  if (c.family == 1) {
+    if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
+      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
+    if (image_floats < transfer_grid_image_floats())
+      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
+                  (long long)transfer_grid_image_floats());
+  }
+  const size_t need = grid_topk_workspace_bytes(c.family, c.C, c.A, c.nT, c.k, c.workgroups);
+  if (workspace_bytes < need)
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", entry, workspace_bytes, need);
+  return launch_grid_topk(c);
+}
+}  // namespace
+
+int32_t impnn_grid_topk_max_temperatures(void) { return kSelectMaxT; }
+
+int impnn_grid_topk_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t k, int32_t workgroups,
+                                    size_t* need) {
+  if (int rc = grid_topk_shape(__func__, family, C, A, nT, k, workgroups)) return rc;
+  REQUIRE(need, "null pointer");
+  *need = grid_topk_workspace_bytes(family, C, A, nT, k, workgroups);
+  return IMPNN_OK;
+}
+
+int impnn_head_grid_topk(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                         const float* head_weights, int32_t k, int32_t largest, float* values, int32_t* cation,
+                         int32_t* anion, void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT,
+                         int32_t D, int32_t F, int32_t Mx, int32_t workgroups, impnn_stream_t stream) {
+  const GridTopkCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, k, largest, values, cation, anion, workspace,
+                       C, A, nT, D, F, Mx, workgroups, as_stream(stream)};
+  return grid_topk_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
+                           mix_cat && mix_an && head_weights && values && cation && anion && workspace &&
+                               (kind == 1 || temperatures),
+                           0, workspace_bytes);
+}
+
+int impnn_transfer_head_grid_topk(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                  int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
+                                  void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
+                                  impnn_stream_t stream) {
+  const GridTopkCall c{1, 1, u_cat, u_an, nullptr, image, k, largest, values, cation, anion, workspace,
+                       C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
+  return grid_topk_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && workspace,
+                           image_floats, workspace_bytes);
+}
+
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,
                       const int64_t* rows, int32_t n_rows, impnn_stream_t stream) {
   REQUIRE(n_tensors >= 0 && n_rows >= 0, "bad shape");

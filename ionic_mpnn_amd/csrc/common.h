@@ -294,6 +294,26 @@ int launch_transfer_ion_half(int ion, const float* pooled, const float* const* w
 int launch_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, float* out, int C, int A,
                               hipStream_t s);
 
+// ---- top-k selection over a cation x anion grid (grid_select.hip; include/impnn.h, impnn_head_grid_topk /
+// impnn_transfer_head_grid_topk).  The limits of one selecting launch (ops.py mirrors them):
+constexpr int kSelectMaxK = 1024;  // entries kept per temperature: one head_grid tile's worth
+constexpr int kSelectMaxT = 4;     // temperatures: 16 KiB of LDS each beside the tile's regions
+// One selecting launch.  family 0: the head grid (`kind`, mixing rows, T, the packed head `w`); family 1: the transfer
+// grid (u rows in mix_cat / mix_an, the image in w).  api.hip checks the arguments.
+struct GridTopkCall {
+  int family, kind;
+  const float *mix_cat, *mix_an, *T, *w;
+  int k, largest;
+  float* values;
+  int32_t *cation, *anion;
+  void* workspace;
+  int C, A, nT, D, F, Mx, workgroups;
+  hipStream_t stream;
+};
+int grid_topk_workgroups(int family, int C, int A, int workgroups);  // 0: the default; capped by the tile count
+size_t grid_topk_workspace_bytes(int family, int C, int A, int nT, int k, int workgroups);
+int launch_grid_topk(const GridTopkCall& c);
+
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)

@@ -1,0 +1,569 @@
+// Device code the grid kernels share: the tile bodies of head_grid.hip and transfer_grid.hip, which the materialising
+// kernels (impnn_head_grid, impnn_transfer_head_grid) and the selecting kernels (grid_select.hip: impnn_head_grid_topk,
+// impnn_transfer_head_grid_topk) both run, and the keys and the running top-k of the selection.  One definition of a
+// tile's arithmetic, so a selected value has the bits the materialised grid holds for that pair.
+#pragma once
+
+#include "common.h"
+#include "head_device.h"
+
+namespace impnn {
+
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef float f32x16_t __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f32x4_t ld4(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
+
+__host__ __device__ inline size_t align4(size_t n) { return (n + 3) & ~(size_t)3; }
+
+// ================================================================ selection (grid_select.hip)
+// An entry is (key << 32) | pair index.  The key is the order-preserving integer image of the float's bits (sign bit
+// flipped for non-negatives, all bits flipped for negatives: -0.0 < +0.0), complemented for `largest`; any NaN has the
+// key 0xFFFFFFFF in both directions, which no other value has (it would be the image of a NaN's bits).  Entries are
+// unique, compared as unsigned 64-bit integers: the total order (value, cation index, anion index), NaN last.
+constexpr unsigned long long kSelectNone = ~0ull;  // no entry: pair indices stay below 2^32 - 1
+
+__device__ __forceinline__ uint32_t select_key(float v, bool largest) {
+  const uint32_t u = __float_as_uint(v);
+  const uint32_t key = (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
+  return v != v ? 0xFFFFFFFFu : (largest ? ~key : key);
+}
+
+__device__ __forceinline__ float select_value(uint32_t key, bool largest) {
+  if (key == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);  // the canonical quiet NaN
+  if (largest) key = ~key;
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+// The running selection of one temperature, in LDS: buf[0 .. count) are the entries kept so far, in no order after
+// the first `kept`; `bound` is the k-th smallest entry at the last compaction, or kSelectNone before k entries were
+// seen.  An entry at or above the bound cannot be among the k smallest.
+struct SelectList {
+  unsigned long long* buf;    // [cap], cap a power of two >= k + the entries one round can offer
+  unsigned long long* bound;  // [1]
+  int* count;                 // [1]
+};
+
+// Sorts buf[0 .. count) ascending and keeps the first k: a bitonic network over the next power of two, the tail padded
+// with kSelectNone.  Every thread of the workgroup calls it with the same arguments, between barriers of its own.
+__device__ __forceinline__ int select_compact(const SelectList& s, int count, int k) {
+  const int tid = threadIdx.x;
+  int P = 2;
+  while (P < count) P <<= 1;
+  for (int i = count + tid; i < P; i += blockDim.x) s.buf[i] = kSelectNone;
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < (P >> 1); i += blockDim.x) {
+        const int lo = 2 * i - (i & (stride - 1)), hi = lo + stride;
+        const unsigned long long a = s.buf[lo], b = s.buf[hi];
+        if ((a > b) == ((lo & size) == 0)) s.buf[lo] = b, s.buf[hi] = a;
+      }
+      __syncthreads();
+    }
+  const int kept = min(count, k);
+  if (tid == 0) {
+    *s.count = kept;
+    *s.bound = kept == k ? s.buf[k - 1] : kSelectNone;
+  }
+  __syncthreads();
+  return kept;
+}
+
+// Before a round that offers at most `round` entries: compacts when the list could not take them, or as soon as k
+// entries have been seen and there is no bound yet.  Block-uniform; the offers of the last round are behind a barrier.
+__device__ __forceinline__ void select_make_room(const SelectList& s, int k, int cap, int round) {
+  const int count = *s.count;
+  const bool unbounded = *s.bound == kSelectNone;
+  __syncthreads();  // (every thread has read count and bound before thread 0 of select_compact rewrites them)
+  if (count + round > cap || (unbounded && count >= k)) select_compact(s, count, k);
+}
+
+// A wave offers one entry per lane (`live` lanes): the survivors of the bound are appended with one ballot, one
+// popcount and one integer LDS atomic per wave.
+__device__ __forceinline__ void select_offer(const SelectList& s, unsigned long long bound, bool live,
+                                             unsigned long long entry) {
+  const bool pass = live && entry < bound;
+  const unsigned long long mask = __ballot(pass);
+  if (mask == 0) return;
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) base = atomicAdd(s.count, __popcll(mask));
+  base = __shfl(base, 0);
+  if (pass) s.buf[base + __popcll(mask & ((1ull << lane) - 1))] = entry;
+}
+
+__host__ __device__ inline int select_capacity(int k, int round) {
+  int cap = 2;
+  while (cap < k + round) cap <<= 1;
+  return cap;
+}
+
+// carves nT lists of `cap` entries from 8-byte aligned LDS at `base`; list t is out[t]
+__device__ __forceinline__ SelectList select_list(void* base, int nT, int cap, int t) {
+  unsigned long long* bufs = reinterpret_cast<unsigned long long*>(base);
+  unsigned long long* bounds = bufs + (size_t)nT * cap;
+  int* counts = reinterpret_cast<int*>(bounds + nT);
+  return SelectList{bufs + (size_t)t * cap, bounds + t, counts + t};
+}
+inline size_t select_lds_bytes(int nT, int cap) { return (size_t)nT * ((size_t)cap * 8 + 8 + 8); }
+
+// What a selecting launch adds to a grid kernel's arguments: the trailing pack of head_grid_kernel and
+// transfer_grid_kernel.  With it a workgroup is persistent: it walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
+// and, where the materialising form stores a tile, offers the tile's values to its lists; at the end it writes its k
+// kept entries per temperature, sorted, to ws [gridDim.x][nT][k] (unused slots kSelectNone).
+struct GridSelect {
+  unsigned long long* ws;
+  int k, cap, largest;
+  unsigned tiles;
+};
+
+// (the barriers between a kernel's loads and its first select_tile publish the empty lists)
+__device__ __forceinline__ void select_init(const GridSelect& g, float* lds, int nT) {
+  if ((int)threadIdx.x < nT) {
+    const SelectList s = select_list(lds, nT, g.cap, threadIdx.x);
+    *s.count = 0;
+    *s.bound = kSelectNone;
+  }
+}
+
+// A tile's `round` values (a multiple of the 256 threads; behind a barrier) against the lists:
+// value(q, t, &live, &pair) is thread tid's q-th value at temperature t, whether it is a pair of the grid, and its index.
+template <class Fn>
+__device__ __forceinline__ void select_tile(const GridSelect& g, float* lds, int nT, int round, Fn value) {
+  for (int t = 0; t < nT; ++t) select_make_room(select_list(lds, nT, g.cap, t), g.k, g.cap, round);
+  for (int q = 0; q < round / 256; ++q)
+    for (int t = 0; t < nT; ++t) {
+      bool live;
+      uint32_t pair;
+      const float v = value(q, t, &live, &pair);
+      const SelectList s = select_list(lds, nT, g.cap, t);
+      select_offer(s, *s.bound, live, ((unsigned long long)select_key(v, g.largest != 0) << 32) | pair);
+    }
+  __syncthreads();  // the tile's regions are free for the next tile, the offers are in the lists
+}
+
+__device__ __forceinline__ bool select_next_tile(unsigned*) { return false; }
+__device__ __forceinline__ bool select_next_tile(unsigned* tile, const GridSelect& g) {
+  *tile += gridDim.x;
+  return *tile < g.tiles;
+}
+
+__device__ __forceinline__ void select_finish(const GridSelect& g, float* lds, int nT) {
+  for (int t = 0; t < nT; ++t) {
+    const SelectList s = select_list(lds, nT, g.cap, t);
+    const int kept = select_compact(s, *s.count, g.k);
+    unsigned long long* dst = g.ws + ((size_t)blockIdx.x * nT + t) * g.k;
+    for (int i = threadIdx.x; i < g.k; i += blockDim.x) dst[i] = i < kept ? s.buf[i] : kSelectNone;
+  }
+}
+
+// ================================================================ the head grid (head_grid.hip; grid_select.hip)
+// One workgroup owns kTileC cations x kTileA anions; lane = anion, a wave walks the tile's cations.
+constexpr int kTileC = 16, kTileA = 64, kTilePairs = kTileC * kTileA;
+
+// Row stride (floats) of the mixing rows in LDS.  A lane reads its anion's row 16 bytes at a time (ds_read_b128: 16
+// lanes per LDS cycle, 64 banks), so the 16 lanes of a group must start 4 banks apart: stride = 4 * odd.  Mx = 64
+// unpadded would put all 64 lanes on one bank quad; the default Mx = 20 is 4 * 5 already.
+__host__ __device__ inline int mix_row_stride(int Mx) {
+  const int s = (Mx + 3) & ~3;
+  return ((s >> 2) & 1) ? s : s + 4;
+}
+
+__host__ __device__ inline size_t grid_lds_floats(int kind, int nT, int F, int Mx) {
+  const size_t rows = (size_t)(kTileA + kTileC) * mix_row_stride(Mx);
+  if (kind == 0) return rows + align4((size_t)Mx * 3 + 3) + 3 * (size_t)kTilePairs + align4((size_t)nT);
+  return rows + (size_t)F * align4(Mx) + align4(F) + align4((size_t)F + 1) + kTilePairs;
+}
+
+
+// Writes `rows` row spans of `span` floats each (row r starts at out + first + r * pitch) with 16-byte stores on
+// every naturally aligned quad that lies inside the span and 4-byte stores on the ragged ends.  Element e of a span
+// is value(r, e / per, e % per).  Consecutive threads take consecutive quads of a row: coalesced along the span.
+template <class Fn>
+__device__ __forceinline__ void store_rows(float* __restrict__ out, int64_t first, int64_t pitch, int rows, int span,
+                                           int per, Fn value) {
+  const int64_t po = (int64_t)((reinterpret_cast<uintptr_t>(out) >> 2) & 3);
+  const int quads = (span + 3) / 4 + 1;  // quads a span can touch at any alignment
+  for (int item = threadIdx.x; item < rows * quads; item += blockDim.x) {
+    const int r = item / quads, q = item - r * quads;
+    const int64_t g0 = first + (int64_t)r * pitch;
+    const int e0 = 4 * q - (int)((g0 + po) & 3);  // out + g0 + e0 is 16-byte aligned
+    if (e0 >= span) continue;
+    const int e = e0 < 0 ? 0 : e0;
+    int a = e / per, t = e - a * per;
+    float v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      v[u] = 0.f;
+      if (e0 + u >= 0 && e0 + u < span) {
+        v[u] = value(r, a, t);
+        if (++t == per) t = 0, ++a;
+      }
+    }
+    float* p = out + g0 + e0;
+    if (e0 >= 0 && e0 + 3 < span) {
+      // written once and not read again by the launch: a streaming (nontemporal) global_store_dwordx4
+      __builtin_nontemporal_store(f32x4_t{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4_t*>(p));
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (e0 + u >= 0 && e0 + u < span) p[u] = v[u];
+    }
+  }
+}
+
+// KIND 0: MXR unused (0).  KIND 1: MXR = 32 or 64 registers hold a pair's mixed vector.
+template <int KIND, int MXR, class... Sel>
+__global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict__ mix_cat,
+                                                        const float* __restrict__ mix_an,
+                                                        const float* __restrict__ T, const float* __restrict__ tail,
+                                                        float* __restrict__ out, float* __restrict__ params, int C,
+                                                        int A, int nT, int F, int Mx, int tiles_a, Sel... sel) {
+  extern __shared__ __align__(16) float sm[];
+  const int S = mix_row_stride(Mx);
+  float* man = sm;                     // [kTileA][S]
+  float* mcat = man + kTileA * S;      // [kTileC][S]
+  float* wts = mcat + kTileC * S;      // the tail weights
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  constexpr bool kSelect = sizeof...(Sel) > 0;
+  unsigned tile = blockIdx.x;
+  if constexpr (kSelect) select_init(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
+  do {
+  const int c0 = (tile / tiles_a) * kTileC, a0 = (tile % tiles_a) * kTileA;
+  const int nc = min(kTileC, C - c0), na = min(kTileA, A - a0);
+
+  // the tile's mixing rows: contiguous in global memory, padded rows in LDS (the pads are never used)
+  for (int idx = tid; idx < na * Mx; idx += blockDim.x) {
+    const int r = idx / Mx;
+    man[r * S + (idx - r * Mx)] = mix_an[(int64_t)a0 * Mx + idx];
+  }
+  for (int idx = tid; idx < nc * Mx; idx += blockDim.x) {
+    const int r = idx / Mx;
+    mcat[r * S + (idx - r * Mx)] = mix_cat[(int64_t)c0 * Mx + idx];
+  }
+
+  if constexpr (KIND == 0) {
+    const int nw = Mx * 3 + 3;         // Wv Mx*3 | bv 3
+    float* resA = wts + ((nw + 3) & ~3);
+    float* resB = resA + kTilePairs;
+    float* resC = resB + kTilePairs;
+    float* t100 = resC + kTilePairs;   // [nT]
+    for (int t = tid; t < nw; t += blockDim.x) wts[t] = tail[t];
+    for (int t = tid; t < nT; t += blockDim.x) t100[t] = head_scaled_t(T[t]);
+    __syncthreads();
+    for (int ci = wave; ci < nc; ci += 4) {
+      if (lane < na) {
+        const float4* pc = reinterpret_cast<const float4*>(mcat + ci * S);
+        const float4* pa = reinterpret_cast<const float4*>(man + lane * S);
+        float v0 = wts[Mx * 3], v1 = wts[Mx * 3 + 1], v2 = wts[Mx * 3 + 2];
+        for (int k4 = 0; k4 < Mx; k4 += 4) {
+          const float4 c = pc[k4 >> 2], a = pa[k4 >> 2];
+          const float m[4] = {c.x + a.x, c.y + a.y, c.z + a.z, c.w + a.w};  // AddTwoTensors, the cation term first
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (k4 + u < Mx) {
+              const float* w = wts + (k4 + u) * 3;
+              v0 = fmaf(m[u], w[0], v0);
+              v1 = fmaf(m[u], w[1], v1);
+              v2 = fmaf(m[u], w[2], v2);
+            }
+        }
+        const VftParams p = head_vft_params(v0, v1, v2);
+        resA[ci * kTileA + lane] = p.A;
+        resB[ci * kTileA + lane] = p.Bc;
+        resC[ci * kTileA + lane] = p.Cc;
+      }
+    }
+    __syncthreads();
+    if constexpr (kSelect) {
+      select_tile(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, kTilePairs, [&](int q, int t, bool* live, uint32_t* pair) {
+        const int e = q * 256 + tid, r = e >> 6, a = e & 63;
+        *live = r < nc && a < na;
+        *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a);
+        return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]);
+      });
+    } else {
+    store_rows(out, ((int64_t)c0 * A + a0) * nT, (int64_t)A * nT, nc, na * nT, nT, [&](int r, int a, int t) {
+      return head_vft_eval(VftParams{resA[r * kTileA + a], resB[r * kTileA + a], resC[r * kTileA + a]}, t100[t]);
+    });
+    if (params)
+      store_rows(params, ((int64_t)c0 * A + a0) * 3, (int64_t)A * 3, nc, na * 3, 3, [&](int r, int a, int t) {
+        return (t == 0 ? resA : t == 1 ? resB : resC)[r * kTileA + a];
+      });
+    }
+  } else {
+    const int S2 = (Mx + 3) & ~3;
+    float* whT = wts;                         // [F][S2]: Wh transposed, a hidden unit's kernel column contiguous
+    float* bh = whT + F * S2;                 // [F]
+    float* wo = bh + ((F + 3) & ~3);          // Wo F | bo 1
+    float* res = wo + ((F + 4) & ~3);         // [kTilePairs]
+    for (int idx = tid; idx < Mx * F; idx += blockDim.x) {
+      const int i = idx / F;
+      whT[(idx - i * F) * S2 + i] = tail[idx];
+    }
+    for (int t = tid; t < F; t += blockDim.x) bh[t] = tail[Mx * F + t];
+    for (int t = tid; t < F + 1; t += blockDim.x) wo[t] = tail[Mx * F + F + t];
+    __syncthreads();
+    for (int ci = wave; ci < nc; ci += 4) {
+      if (lane < na) {
+        const float4* pc = reinterpret_cast<const float4*>(mcat + ci * S);
+        const float4* pa = reinterpret_cast<const float4*>(man + lane * S);
+        float mixed[MXR];
+#pragma unroll
+        for (int k4 = 0; k4 < MXR; k4 += 4)
+          if (k4 < Mx) {
+            const float4 c = pc[k4 >> 2], a = pa[k4 >> 2];
+            mixed[k4] = c.x + a.x, mixed[k4 + 1] = c.y + a.y, mixed[k4 + 2] = c.z + a.z, mixed[k4 + 3] = c.w + a.w;
+          }
+        float acc2 = wo[F];
+        for (int j = 0; j < F; ++j) {
+          const float4* w = reinterpret_cast<const float4*>(whT + j * S2);
+          float acc = bh[j];
+#pragma unroll
+          for (int k4 = 0; k4 < MXR; k4 += 4)
+            if (k4 < Mx) {
+              const float4 ww = w[k4 >> 2];
+              acc = fmaf(mixed[k4], ww.x, acc);
+              if (k4 + 1 < Mx) acc = fmaf(mixed[k4 + 1], ww.y, acc);
+              if (k4 + 2 < Mx) acc = fmaf(mixed[k4 + 2], ww.z, acc);
+              if (k4 + 3 < Mx) acc = fmaf(mixed[k4 + 3], ww.w, acc);
+            }
+          acc2 = fmaf(head_relu(acc), wo[j], acc2);
+        }
+        res[ci * kTileA + lane] = acc2;
+      }
+    }
+    __syncthreads();
+    if constexpr (kSelect) {
+      select_tile(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, kTilePairs, [&](int q, int, bool* live, uint32_t* pair) {
+        const int e = q * 256 + tid, r = e >> 6, a = e & 63;
+        *live = r < nc && a < na;
+        *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a);
+        return res[e];
+      });
+    } else {
+    store_rows(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, 1, [&](int r, int a, int) { return res[r * kTileA + a]; });
+    }
+  }
+  } while (select_next_tile(&tile, sel...));  // (the materialising form: one tile per workgroup)
+  if constexpr (kSelect) select_finish(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
+}
+
+
+// ================================================================ the transfer grid (transfer_grid.hip; grid_select.hip)
+constexpr int kH1 = 256, kH2 = 128, kH3 = 64;
+
+// ---- the prepared image, in floats.  W2 / W3 blocks are 64 lanes x 4 floats in A-operand order: lane l (row a = l & 31,
+// half h = l >> 5), element b of block (g, mb) holds the kernel entry [input 8 g + 4 h + b][output 32 mb + a], so a
+// lane's A operands of four consecutive k steps are one 16-byte load and a wave's load is 1 KB, contiguous.
+constexpr int kImgW2 = 0;                          // [g 0..31][mb 0..3][64][4]
+constexpr int kImgW3 = kImgW2 + kH1 * kH2;         // [kb 0..3][g 0..3][mb 0..1][64][4], input 32 kb + 8 g + 4 h + b
+constexpr int kImgScale = kImgW3 + kH2 * kH3;      // gamma / sqrt(moving_var + eps)          [256]
+constexpr int kImgShift = kImgScale + kH1;         // beta - moving_mean * scale              [256]
+constexpr int kImgB2 = kImgShift + kH1;            // [128]
+constexpr int kImgB3 = kImgB2 + kH2;               // [64]
+constexpr int kImgWo = kImgB3 + kH3;               // [64]
+constexpr int kImgBo = kImgWo + kH3;               // [1] + 3 pad
+constexpr int kImgFloats = kImgBo + 4;             // 41 732 floats, 163.0 KiB
+
+// One workgroup owns kTgTileC cations x kTgTileA anions; a wave owns two cations of the tile, i.e. two
+// MFMA column blocks of 32 pairs (lane & 31 = anion), and fetches every weight once for its 64 pairs.
+constexpr int kTgTileC = 8, kTgTileA = 32;
+// Row stride (floats) of the anion u rows in LDS.  A lane reads its anion's row 16 bytes at a time (ds_read_b128: 16
+// lanes per LDS cycle, 64 banks), so the 16 lanes of a group must start 4 banks apart: stride = 4 * odd.  256 unpadded
+// would put every lane on one bank quad; 260 = 4 * 65.  The cation rows, scale and shift are read at one address per
+// lane half (a broadcast), so they stay unpadded.
+constexpr int kTgAnStride = kH1 + 4;
+constexpr int kTgLdsFloats = kTgTileA * kTgAnStride + kTgTileC * kH1 + 2 * kH1 + kTgTileC * kTgTileA;  // 43.5 KiB
+
+__device__ __forceinline__ f32x16_t mfma32(float a, float b, f32x16_t c) {
+  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// Writes `rows` spans of `span` floats (row r starts at out + first + r * pitch, its values at res + r * rs) with
+// 16-byte stores on every naturally aligned quad inside the span and 4-byte stores on the ragged ends (the scheme of
+// head_grid.hip's store_rows, one value per pair).
+__device__ __forceinline__ void store_spans(float* __restrict__ out, int64_t first, int64_t pitch, int rows, int span,
+                                            const float* res, int rs) {
+  const int64_t po = (int64_t)((reinterpret_cast<uintptr_t>(out) >> 2) & 3);
+  const int quads = (span + 3) / 4 + 1;  // quads a span can touch at any alignment
+  for (int item = threadIdx.x; item < rows * quads; item += blockDim.x) {
+    const int r = item / quads, q = item - r * quads;
+    const int64_t g0 = first + (int64_t)r * pitch;
+    const int e0 = 4 * q - (int)((g0 + po) & 3);  // out + g0 + e0 is 16-byte aligned
+    if (e0 >= span) continue;
+    const float* v = res + r * rs + e0;
+    if (e0 >= 0 && e0 + 3 < span) {
+      // written once and not read again by the launch: a streaming (nontemporal) global_store_dwordx4
+      __builtin_nontemporal_store(f32x4_t{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4_t*>(out + g0 + e0));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (e0 + k >= 0 && e0 + k < span) out[g0 + e0 + k] = v[k];
+    }
+  }
+}
+
+// One k group (8 input features: 4 per lane half) of Dense 128 for a wave's two column blocks: the operand
+// bn(relu(u_cat + u_an)) is formed in registers, then 4 k steps x 4 row blocks x 2 column blocks of MFMA.
+__device__ __forceinline__ void dense128_group(f32x16_t (&acc)[4][2], const f32x4_t (&w)[4], const float* ua_row,
+                                               const float* uc_row, const float* bn_half, int g) {
+  const f32x4_t ua = ld4(ua_row + 8 * g), sc = ld4(bn_half + 8 * g), sh = ld4(bn_half + kH1 + 8 * g);
+  const f32x4_t uc0 = ld4(uc_row + 8 * g), uc1 = ld4(uc_row + kH1 + 8 * g);
+  float x[2][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {  // relu(mp_dense_1), then BatchNormalization's affine, per feature
+    x[0][b] = fmaf(head_relu(uc0[b] + ua[b]), sc[b], sh[b]);
+    x[1][b] = fmaf(head_relu(uc1[b] + ua[b]), sc[b], sh[b]);
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) acc[mb][nb] = mfma32(w[mb][b], x[nb][b], acc[mb][nb]);
+}
+
+// One k group of Dense 64: registers 4 g .. 4 g + 3 of the input block's accumulators, relu applied on the way.
+__device__ __forceinline__ void dense64_group(f32x16_t (&acc)[2][2], const f32x16_t (&in)[2], const f32x4_t (&w)[2],
+                                              int g) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+      const float a2 = head_relu(in[nb][4 * g + b]);
+      acc[0][nb] = mfma32(w[0][b], a2, acc[0][nb]);
+      acc[1][nb] = mfma32(w[1][b], a2, acc[1][nb]);
+    }
+}
+
+template <class... Sel>
+__global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restrict__ u_cat,
+                                                            const float* __restrict__ u_an,
+                                                            const float* __restrict__ img, float* __restrict__ out,
+                                                            int C, int A, int tiles_a, Sel... sel) {
+  extern __shared__ __align__(16) float sm[];
+  float* uan = sm;                            // [kTgTileA][kTgAnStride]
+  float* ucat = uan + kTgTileA * kTgAnStride; // [kTgTileC][kH1]
+  float* bnv = ucat + kTgTileC * kH1;         // scale kH1 | shift kH1
+  float* res = bnv + 2 * kH1;                 // [kTgTileC][kTgTileA]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, p = lane & 31, h = lane >> 5;
+  constexpr bool kSelect = sizeof...(Sel) > 0;
+  unsigned tile = blockIdx.x;
+  if constexpr (kSelect) select_init(sel..., sm + kTgLdsFloats, 1);
+  do {
+  const int c0 = (tile / tiles_a) * kTgTileC, a0 = (tile % tiles_a) * kTgTileA;
+  const int nc = min(kTgTileC, C - c0), na = min(kTgTileA, A - a0);
+
+  // the tile's u rows; the rows of a ragged tile's padding pairs are zero (computed, not stored)
+  const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  for (int idx = tid; idx < kTgTileA * (kH1 / 4); idx += blockDim.x) {
+    const int r = idx >> 6, q = idx & 63;
+    *reinterpret_cast<f32x4_t*>(uan + r * kTgAnStride + 4 * q) = r < na ? ld4(u_an + (int64_t)(a0 + r) * kH1 + 4 * q) : zero4;
+  }
+  for (int idx = tid; idx < kTgTileC * (kH1 / 4); idx += blockDim.x) {
+    const int r = idx >> 6, q = idx & 63;
+    *reinterpret_cast<f32x4_t*>(ucat + r * kH1 + 4 * q) = r < nc ? ld4(u_cat + (int64_t)(c0 + r) * kH1 + 4 * q) : zero4;
+  }
+  for (int idx = tid; idx < 2 * kH1 / 4; idx += blockDim.x)
+    *reinterpret_cast<f32x4_t*>(bnv + 4 * idx) = ld4(img + kImgScale + 4 * idx);
+  __syncthreads();
+
+  if (2 * wave < nc) {  // (wave-uniform; no barrier inside)
+    const float* ua_row = uan + p * kTgAnStride + 4 * h;
+    const float* uc_row = ucat + (2 * wave) * kH1 + 4 * h;
+    const f32x4_t* w2 = reinterpret_cast<const f32x4_t*>(img + kImgW2) + lane;
+    const f32x4_t* w3 = reinterpret_cast<const f32x4_t*>(img + kImgW3) + lane;
+
+    // Dense 128: the accumulators start at the bias (bias first, as every Dense of this project)
+    f32x16_t acc2[4][2];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4_t bb = ld4(img + kImgB2 + 32 * mb + 8 * q + 4 * h);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc2[mb][0][4 * q + b] = acc2[mb][1][4 * q + b] = bb[b];
+      }
+    // The A operands of k group g + 1 travel while the 32 MFMAs of group g run: two register sets in turn, and
+    // scheduling fences, without which the compiler sinks the loads to just before their use (one L2 latency exposed
+    // per group).
+    f32x4_t wa[4], wb[4];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) wa[mb] = w2[mb * 64];
+#pragma unroll 1
+    for (int g = 0; g < kH1 / 8; g += 2) {
+#pragma unroll
+      for (int mb = 0; mb < 4; ++mb) wb[mb] = w2[((g + 1) * 4 + mb) * 64];
+      __builtin_amdgcn_sched_barrier(0);
+      dense128_group(acc2, wa, ua_row, uc_row, bnv + 4 * h, g);
+      __builtin_amdgcn_sched_barrier(0);
+      const int gn = min(g + 2, kH1 / 8 - 1);  // (the last turn reloads group 31: in bounds, unused)
+#pragma unroll
+      for (int mb = 0; mb < 4; ++mb) wa[mb] = w2[(gn * 4 + mb) * 64];
+      __builtin_amdgcn_sched_barrier(0);
+      dense128_group(acc2, wb, ua_row, uc_row, bnv + 4 * h, g + 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+
+    // Dense 64: the B operand of k step 4 g + b of input block kb is register 4 g + b of acc2[kb]
+    f32x16_t acc3[2][2];
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4_t bb = ld4(img + kImgB3 + 32 * mb + 8 * q + 4 * h);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc3[mb][0][4 * q + b] = acc3[mb][1][4 * q + b] = bb[b];
+      }
+    f32x4_t va[2], vb[2];
+    va[0] = w3[0], va[1] = w3[64];
+#pragma unroll
+    for (int s = 0; s < 16; s += 2) {  // s = 4 kb + g
+      vb[0] = w3[((s + 1) * 2 + 0) * 64], vb[1] = w3[((s + 1) * 2 + 1) * 64];
+      __builtin_amdgcn_sched_barrier(0);
+      dense64_group(acc3, acc2[s >> 2], va, s & 3);
+      __builtin_amdgcn_sched_barrier(0);
+      const int sn = s + 2 < 16 ? s + 2 : 15;
+      va[0] = w3[(sn * 2 + 0) * 64], va[1] = w3[(sn * 2 + 1) * 64];
+      __builtin_amdgcn_sched_barrier(0);
+      dense64_group(acc3, acc2[(s + 1) >> 2], vb, (s + 1) & 3);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+
+    // Dense 1: a lane sums its 32 features in ascending order, the two lane halves meet (half 0 first), then the bias
+    float part[2] = {0.f, 0.f};
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4_t wo = ld4(img + kImgWo + 32 * mb + 8 * q + 4 * h);
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) part[nb] = fmaf(head_relu(acc3[mb][nb][4 * q + b]), wo[b], part[nb]);
+      }
+    const float bo = img[kImgBo];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+      const float other = __shfl_xor(part[nb], 32);
+      if (h == 0) res[(2 * wave + nb) * kTgTileA + p] = (part[nb] + other) + bo;
+    }
+  }
+  __syncthreads();
+  if constexpr (kSelect) {
+    select_tile(sel..., sm + kTgLdsFloats, 1, kTgTileC * kTgTileA, [&](int, int, bool* live, uint32_t* pair) {
+      const int r = tid >> 5;
+      *live = r < nc && p < na;
+      *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + p);
+      return res[tid];
+    });
+  } else {
+  store_spans(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, res, kTgTileA);
+  }
+  } while (select_next_tile(&tile, sel...));  // (the materialising form: one tile per workgroup)
+  if constexpr (kSelect) select_finish(sel..., sm + kTgLdsFloats, 1);
+}
+
+
+}  // namespace impnn

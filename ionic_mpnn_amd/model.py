@@ -19,6 +19,7 @@ import os
 import numpy as np
 import torch
 
+from . import data
 from . import layers as L
 from . import ops
 
@@ -38,6 +39,8 @@ ION_KEYS = ("atom", "bond", "connectivity")
 GRID_OUTPUT_BUDGET = 1 << 28
 GRID_MAX_TEMPERATURES = 4096   # temperatures per impnn_head_grid launch (include/impnn.h)
 GRID_GATHER_PAIRS = 1 << 18    # pairs per tile of the gathered path (widths above 64, the transfer head)
+SCREEN_MAX_K = ops.SELECT_MAX_K       # screen_top_k: the largest k the selecting kernels keep (above it: the fallback)
+SCREEN_MAX_PAIRS = (1 << 32) - 1      # pairs of one selecting launch: a pair's index has 32 bits
 
 
 def _ion_numpy(ion, what):
@@ -1119,6 +1122,107 @@ class MPNNModel:
                             params[lo:hi] = pr.cpu().numpy()
                         out[lo:hi, :, t0:t1] = got.cpu().numpy()
         return (out, params) if return_params else out
+
+    def screen_top_k(self, cations, anions, temperatures=None, k=100, largest=False, max_pairs_per_launch=None,
+                     batch_size=4096):
+        """The k pairs of a screen with the smallest (``largest``: largest) prediction, selected on the GPU: what
+        ``data.grid_top_k(self.predict_grid(...), k, largest)`` returns, without the grid.  ``encode_ions`` and the
+        per-ion halves are ``predict_grid``'s; the selecting kernels (impnn_head_grid_topk,
+        impnn_transfer_head_grid_topk) evaluate every pair with the grid kernels' arithmetic and keep a running top k
+        on the chip.  -> ``data.TopK`` of numpy ``values`` float32, ``cation``, ``anion`` int64 (positions in the lists
+        given), sorted, of shape (nT, min(k, C*A)) for viscosity - a row per temperature - and (min(k, C*A),)
+        otherwise.  Order: by value, ties by cation then anion index, NaN last.
+        The cation axis is tiled on the host so that a launch has fewer than 2^32 pairs (``max_pairs_per_launch``
+        overrides it), temperatures are split at ops.SELECT_MAX_T per launch, and the launches' results are merged
+        under the same order.  Widths the head kernels do not cover, the transfer model with ``grid_head_mode =
+        "gathered"`` and k above SCREEN_MAX_K walk ``predict_grid``'s tiles instead and select per tile: never more than
+        one tile and k entries are held."""
+        if self.kind == "viscosity" and temperatures is None:
+            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
+        if cations is None or anions is None:
+            raise ValueError("screen_top_k needs both cations and anions")
+        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
+            raise ValueError("max_pairs_per_launch must be >= 1")
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        visc = self.kind == "viscosity"
+        T = None
+        if visc:
+            T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
+            T = T.to(torch.float32).reshape(-1)
+            if T.numel() == 0:
+                raise ValueError("temperatures must hold at least one value")
+        pc, pa = self.encode_ions(cations, anions, batch_size)
+        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
+        n_rows = nT if visc else 1
+        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
+        covered = self._grid_kernels_cover() or mfma
+        select = covered and k <= SCREEN_MAX_K
+        # the running best of every row: (values, flat index i * A + j as int64), at most k each
+        best = [(np.empty(0, np.float32), np.empty(0, np.int64)) for _ in range(n_rows)]
+
+        def offer(row, values, flat):
+            v, f = np.concatenate([best[row][0], values]), np.concatenate([best[row][1], flat])
+            order = data.top_k_order(v, f, k, largest)
+            best[row] = (v[order], f[order])
+
+        if C > 0 and A > 0:
+            if max_pairs_per_launch is None:
+                max_pairs_per_launch = SCREEN_MAX_PAIRS if select else max(
+                    1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
+                if not covered:
+                    max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
+            step = max(1, min(int(max_pairs_per_launch), SCREEN_MAX_PAIRS if select else 1 << 62) // A)
+            t_step = ops.SELECT_MAX_T if select else GRID_MAX_TEMPERATURES
+            with torch.no_grad():
+                if visc:
+                    T = T.to(self.device)
+                if mfma:
+                    tensors, image = self._head_tensors(), self._transfer_image()
+                    mc = ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size)
+                    ma = ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size)
+                elif covered:
+                    w = self._packed_head()
+                    mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
+                    ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
+                for lo in range(0, C, step):
+                    hi = min(C, lo + step)
+                    for t0 in range(0, n_rows, t_step):
+                        t1 = min(n_rows, t0 + t_step)
+                        Tt = T[t0:t1] if visc else None
+                        if select:
+                            if mfma:
+                                got = ops.transfer_head_grid_topk(mc[lo:hi], ma, image, k, largest)
+                            else:
+                                got = ops.head_grid_topk(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size,
+                                                         self.mixing_size, k, largest)
+                            v, ci, ai = (x.cpu().numpy() for x in got)
+                            for r in range(t1 - t0):
+                                used = ci[r] >= 0
+                                offer(t0 + r, v[r][used], (ci[r][used].astype(np.int64) + lo) * A + ai[r][used])
+                        else:
+                            if not covered:
+                                tile = self._grid_gathered(pc[lo:hi], pa, Tt)
+                            elif mfma:
+                                tile = ops.transfer_head_grid(mc[lo:hi], ma, image)
+                            else:
+                                tile = ops.head_grid(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size, self.mixing_size)
+                            tile = tile.cpu().numpy().reshape((hi - lo) * A, -1)
+                            flat = np.arange(lo * A, hi * A, dtype=np.int64)
+                            for r in range(t1 - t0):
+                                order = data.top_k_order(tile[:, r], flat, k, largest)
+                                offer(t0 + r, tile[order, r], flat[order])
+        m = min(k, C * A)
+        values = np.empty((n_rows, m), np.float32)
+        cation, anion = np.empty((n_rows, m), np.int64), np.empty((n_rows, m), np.int64)
+        for r, (v, f) in enumerate(best):
+            values[r], cation[r], anion[r] = v, f // max(A, 1), f % max(A, 1)
+        values[np.isnan(values)] = data.QUIET_NAN
+        if not visc:
+            values, cation, anion = values[0], cation[0], anion[0]
+        return data.TopK(values, cation, anion)
 
     def _grid_gathered(self, pc, pa, T):
         """``self.head`` on the explicit pairs of a tile of cations x all anions (x T) -> (c, A[, nT])."""

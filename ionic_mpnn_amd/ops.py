@@ -838,6 +838,83 @@ def transfer_head_grid(u_cat, u_an, image):
     return out
 
 
+# the limits of one selecting launch: kSelectMaxK / kSelectMaxT of csrc/common.h (tests/test_screen_host.py holds them equal)
+SELECT_MAX_K = 1024
+SELECT_MAX_T = 4
+
+
+def _grid_topk_outputs(lib, family, C_, A_, nT, k, workgroups, dev):
+    rows = max(nT, 1)
+    need = C.c_size_t(0)
+    check(lib.impnn_grid_topk_workspace_bytes(family, C_, A_, nT, k, workgroups, C.byref(need)))
+    values = torch.empty(rows, k, dtype=torch.float32, device=dev)
+    cation = torch.empty(rows, k, dtype=torch.int32, device=dev)
+    anion = torch.empty(rows, k, dtype=torch.int32, device=dev)
+    if C_ == 0 or A_ == 0:  # zero work touches nothing: no pair in any slot
+        values.fill_(float("nan")), cation.fill_(-1), anion.fill_(-1)
+    return values, cation, anion, _workspace(dev, need.value), need.value
+
+
+def head_grid_topk(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, k, largest=False,
+                   workgroups=0):
+    """The k best pairs of ``head_grid``'s product without the product (impnn_head_grid_topk): the same arguments, ->
+    values (nT,k) float32, cation (nT,k), anion (nT,k) int32 on the device, a row per temperature (one row for
+    "melting_point"), sorted under the order of ``data.grid_top_k``; slots past C*A hold NaN / -1.  A value has the
+    bits ``head_grid`` gives for its pair.  k <= SELECT_MAX_K, at most SELECT_MAX_T temperatures, C*A < 2^32."""
+    require_gpu(mix_cat, mix_an, head_weights)
+    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
+    kd = HEAD_KINDS[kind]
+    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
+        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
+                         f"and {tuple(mix_an.shape)}")
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    lib = _lib.load()
+    per_d = 2 * fp_size
+    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
+    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
+    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+    T, nT = None, 0
+    if kd == 0:
+        if temperatures is None:
+            raise ValueError("the viscosity grid needs temperatures")
+        require_gpu(temperatures)
+        T = f32c(temperatures).reshape(-1)
+        nT = int(T.numel())
+    elif temperatures is not None:
+        raise ValueError("the melting-point grid takes no temperatures")
+    dev = mix_cat.device
+    k, workgroups = int(k), int(workgroups)
+    with torch.cuda.device(dev):
+        values, cation, anion, ws, nbytes = _grid_topk_outputs(lib, 0, C_, A_, nT, k, workgroups, dev)
+        check(lib.impnn_head_grid_topk(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
+                                       ptr(head_weights), k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion),
+                                       ptr(ws), nbytes, C_, A_, nT, D, fp_size, mixing_size, workgroups, stream_ptr()))
+    return values, cation, anion
+
+
+def transfer_head_grid_topk(u_cat, u_an, image, k, largest=False, workgroups=0):
+    """The k best pairs of ``transfer_head_grid``'s product without the product (impnn_transfer_head_grid_topk) ->
+    values (1,k) float32, cation (1,k), anion (1,k) int32 on the device, as ``head_grid_topk``."""
+    require_gpu(u_cat, u_an, image)
+    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
+    W = TRANSFER_GRID_WIDTH
+    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
+        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
+    lib = _lib.load()
+    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
+        raise ValueError("the prepared image has the wrong length")
+    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
+    dev = u_cat.device
+    k, workgroups = int(k), int(workgroups)
+    with torch.cuda.device(dev):
+        values, cation, anion, ws, nbytes = _grid_topk_outputs(lib, 1, C_, A_, 0, k, workgroups, dev)
+        check(lib.impnn_transfer_head_grid_topk(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), k, int(bool(largest)),
+                                                ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, C_, A_, workgroups,
+                                                stream_ptr()))
+    return values, cation, anion
+
+
 def transfer_head(pooled_cat, pooled_an, weights, cfg):
     """The transfer model's head in inference, one launch (impnn_transfer_head): ``weights`` the 18 tensors in the
     order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg -> (B,1)."""

@@ -4,15 +4,24 @@ transfer model: predict_grid with grid_head_mode "gathered" (self.head on gather
 matrix-core grid, impnn_transfer_head_grid), plus that kernel alone against the f32 MFMA peak.
 
 python tools/screen_bench.py [--quick] [--only viscosity|transfer]      -> one JSON line per configuration, appended to profiles/screen_bench.jsonl
+python tools/screen_bench.py --select [--quick] [--only ...]            -> the top-k selection instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
 The expanded inputs are built once and stay on the device, so the baseline pays no host-to-device copy; predict_grid
-gets host arrays of C + A molecules, as a caller would hand them over."""
+gets host arrays of C + A molecules, as a caller would hand them over.
+
+--select: MPNNModel.screen_top_k(k = 100) against the way to the same answer without it, predict_grid followed by
+data.grid_top_k on the host, at the configurations above and at two larger ones (C * A * nT in the 10^7 range); the
+same three alternating rounds, wall time around each side (the host sort is part of the old way).  Plus the selecting
+launches alone (impnn_head_grid_topk / impnn_transfer_head_grid_topk with their merge; a viscosity sweep above
+ops.SELECT_MAX_T temperatures takes several) against the materialising launch of the same C x A x nT, 10 calls
+between two HIP events."""
 import argparse
 import json
 import statistics
 import sys
+import time
 from pathlib import Path
 
 import numpy as np
@@ -20,11 +29,12 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-from ionic_mpnn_amd import model as MM, ops, synthetic, weights  # noqa: E402
+from ionic_mpnn_amd import data, model as MM, ops, synthetic, weights  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="the first configuration only")
 ap.add_argument("--only", choices=("viscosity", "transfer"), help="one family of configurations")
+ap.add_argument("--select", action="store_true", help="time screen_top_k against predict_grid + host selection")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -50,7 +60,7 @@ def species(n, seed):
 
 
 lines = []
-for name, D, S, C, A, nT, bs in [] if args.only == "transfer" else CONFIGS[:1] if args.quick else CONFIGS:
+for name, D, S, C, A, nT, bs in [] if args.only == "transfer" or args.select else CONFIGS[:1] if args.quick else CONFIGS:
     m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
     m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
     cat, _ = species(C, 1)
@@ -110,7 +120,7 @@ def build_transfer(D, S):
         return MM.build_transfer_model(path, device=dev)
 
 
-for name, D, S, C, A in [] if args.only == "viscosity" else TRANSFER_CONFIGS[:1] if args.quick else TRANSFER_CONFIGS:
+for name, D, S, C, A in [] if args.only == "viscosity" or args.select else TRANSFER_CONFIGS[:1] if args.quick else TRANSFER_CONFIGS:
     t = build_transfer(D, S)
     cat, _ = species(C, 1)
     _, an = species(A, 2)
@@ -146,6 +156,81 @@ for name, D, S, C, A in [] if args.only == "viscosity" else TRANSFER_CONFIGS[:1]
     lines.append(line)
     del t
     torch.cuda.empty_cache()
+
+# ---- --select: screen_top_k against predict_grid + data.grid_top_k, then the launches alone
+SELECT_K = 100
+SELECT_CONFIGS = [("viscosity",) + c[:6] for c in CONFIGS] + [("viscosity", "config2 2048x2048x4", 32, 3, 2048, 2048, 4)] \
+    + [("transfer",) + c + (0,) for c in TRANSFER_CONFIGS] + [("transfer", "transfer 4096x4096", 32, 3, 4096, 4096, 0)]
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def same_top(a, b):
+    return all(np.array_equal(np.asarray(x).view(np.uint32) if x.dtype == np.float32 else x, np.asarray(y).view(np.uint32)
+                              if y.dtype == np.float32 else y) for x, y in zip(a, b))
+
+
+if args.select:
+    todo = [c for c in SELECT_CONFIGS if args.only in (None, c[0])]
+    for kind, name, D, S, C, A, nT in todo[:1] if args.quick else todo:
+        if kind == "viscosity":
+            m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
+            m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
+            T = np.linspace(263.15, 393.15, nT).astype(np.float32)
+        else:
+            m, T = build_transfer(D, S), None
+        cat, _ = species(C, 1)
+        _, an = species(A, 2)
+        old_way = lambda: data.grid_top_k(m.predict_grid(cat, an, T), SELECT_K)
+        new_way = lambda: m.screen_top_k(cat, an, T, k=SELECT_K)
+        _, top_old = wall(old_way)
+        _, top_new = wall(new_way)
+        t_old, t_new = [], []
+        for _ in range(3):
+            t_old.append(wall(old_way)[0])
+            t_new.append(wall(new_way)[0])
+        with torch.no_grad():
+            pc, pa = m.encode_ions(cat, an)
+            if kind == "viscosity":
+                w = m._packed_head()
+                mc = ops.head_ion_mix(kind, "cat", pc, w, m.fp_size, m.mixing_size)
+                ma = ops.head_ion_mix(kind, "an", pa, w, m.fp_size, m.mixing_size)
+                Td = torch.from_numpy(T).to(dev)
+                store = lambda: [ops.head_grid(kind, mc, ma, Td, w, m.fp_size, m.mixing_size) for _ in range(10)]
+                select = lambda: [ops.head_grid_topk(kind, mc, ma, Td[t0:t0 + ops.SELECT_MAX_T], w, m.fp_size, m.mixing_size,
+                                                     SELECT_K) for _ in range(10) for t0 in range(0, nT, ops.SELECT_MAX_T)]
+            else:
+                tensors, image = m._head_tensors(), m._transfer_image()
+                uc = ops.transfer_ion_half("cat", pc, tensors, m.fp_size, m.mixing_size)
+                ua = ops.transfer_ion_half("an", pa, tensors, m.fp_size, m.mixing_size)
+                store = lambda: [ops.transfer_head_grid(uc, ua, image) for _ in range(10)]
+                select = lambda: [ops.transfer_head_grid_topk(uc, ua, image, SELECT_K) for _ in range(10)]
+            timed(store), timed(select)
+            k_store, k_select = [], []
+            for _ in range(3):
+                k_store.append(timed(store)[0] / 10)
+                k_select.append(timed(select)[0] / 10)
+        ms_old, ms_new = statistics.median(t_old), statistics.median(t_new)
+        us_store, us_select = statistics.median(k_store) * 1e3, statistics.median(k_select) * 1e3
+        line = {"config": "select " + name, "kind": kind, "atom_dim": D, "steps": S, "C": C, "A": A, "nT": nT, "k": SELECT_K,
+                "values": C * A * max(nT, 1), "predict_grid_plus_host_top_k_ms": round(ms_old, 3),
+                "screen_top_k_ms": round(ms_new, 3), "speedup": round(ms_old / ms_new, 2),
+                "rounds_old_ms": [round(x, 3) for x in t_old], "rounds_new_ms": [round(x, 3) for x in t_new],
+                "materialising_launch_us": round(us_store, 2), "selecting_launches_us": round(us_select, 2),
+                "selecting_over_materialising": round(us_select / us_store, 3),
+                "rounds_materialising_us": [round(x * 1e3, 2) for x in k_store],
+                "rounds_selecting_us": [round(x * 1e3, 2) for x in k_select], "same_answer": same_top(top_old, top_new)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del m
+        torch.cuda.empty_cache()
+
 Path(args.out).parent.mkdir(parents=True, exist_ok=True)
 with open(args.out, "a") as f:
     for line in lines:
