@@ -539,6 +539,43 @@ int impnn_transfer_head_grid_topk(const float* u_cat, const float* u_an, const f
                                   void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
                                   impnn_stream_t stream);
 
+/* ---- a screen under a constraint: packed pair masks.  A mask over C cations x A anions is uint32_t words[C][W] with
+ *      W = impnn_grid_mask_row_words(A) = ceil(A / 32); pair (i,j) is bit (j & 31) of words[i][j >> 5]; the pad bits
+ *      (j >= A) are always 0.  Rows are word-aligned, and both grid kernels start a tile on a word boundary (64 and 32
+ *      anions), so every word has one writer: no atomics, no pre-zeroing - a mask-writing call writes EVERY word of its
+ *      output.  A viscosity mask is [nT][C][W], one plane per temperature.
+ *      impnn_head_grid_mask / impnn_transfer_head_grid_mask: the arguments of impnn_head_grid (without params) /
+ *        impnn_transfer_head_grid with (lo, hi, words) for `out`: bit (i,j[,t]) = lo <= v && v <= hi, where v has the
+ *        bits the materialising entry writes for that element (the same tile arithmetic).  A NaN prediction fails both
+ *        comparisons; lo = -inf or hi = +inf mean "no limit" on that side.  kind 0: 1 <= nT <= 4096; kind 1: nT 0 and
+ *        temperatures NULL.  words 4-byte aligned.  No C x A float buffer exists.
+ *        Checks in order: shape (kind, sizes, nT, widths > 0, image_floats >= 0, a NaN bound; IMPNN_E_BADARG); zero
+ *        work (C == 0 or A == 0: IMPNN_OK, nothing touched); null pointers; alignment (IMPNN_E_BADARG) and the image
+ *        size (IMPNN_E_WORKSPACE); the limits D <= 128, F, Mx <= 64, nT <= 4096 (IMPNN_E_UNSUPPORTED).  C * A may
+ *        exceed 2^31.
+ *      impnn_head_grid_topk_where / impnn_transfer_head_grid_topk_where: the plain entries above plus `where`, a
+ *        (C,W) mask, 4-byte aligned, NULL is IMPNN_E_BADARG (a null-pointer rule); for viscosity the one mask applies to
+ *        every temperature row.  The result is the exact top k, under the same 64-bit entry order, of the pairs whose
+ *        bit is set; with fewer than k such pairs the remaining slots hold NaN / -1 / -1.  Limits, workspace
+ *        (impnn_grid_topk_workspace_bytes serves both forms) and checks are the plain entries'.  A persistent workgroup
+ *        passes over a tile (16 x 64, 8 x 32 pairs) none of whose bits is set before it loads a row, so a selective
+ *        constraint costs about the tiles it leaves. */
+int64_t impnn_grid_mask_row_words(int32_t A);
+int impnn_head_grid_mask(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                         const float* head_weights, float lo, float hi, uint32_t* words, int32_t C, int32_t A,
+                         int32_t nT, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_head_grid_mask(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                  float lo, float hi, uint32_t* words, int32_t C, int32_t A, impnn_stream_t stream);
+int impnn_head_grid_topk_where(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                               const float* head_weights, const uint32_t* where, int32_t k, int32_t largest,
+                               float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                               int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F, int32_t Mx, int32_t workgroups,
+                               impnn_stream_t stream);
+int impnn_transfer_head_grid_topk_where(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                        const uint32_t* where, int32_t k, int32_t largest, float* values,
+                                        int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                                        int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

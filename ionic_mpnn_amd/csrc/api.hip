@@ -756,9 +756,10 @@ int grid_topk_checked(const char* entry, const GridTopkCall& c, bool widths_ok, 
   if (c.family == 0)
     if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
   if (c.C == 0 || c.A == 0) return IMPNN_OK;
-  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (!pointers_ok || (c.masked && !c.where)) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
   if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
   if ((reinterpret_cast<uintptr_t>(c.workspace) & 7u) != 0) return fail(IMPNN_E_BADARG, "%s: the workspace must be 8-byte aligned", entry);
+  if ((reinterpret_cast<uintptr_t>(c.where) & 3u) != 0) return fail(IMPNN_E_BADARG, "%s: the mask must be 4-byte aligned", entry);
   if (c.family == 1) {
     if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
       return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
@@ -803,6 +804,78 @@ int impnn_transfer_head_grid_topk(const float* u_cat, const float* u_an, const f
                        C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
   return grid_topk_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && workspace,
                            image_floats, workspace_bytes);
+}
+
+int impnn_head_grid_topk_where(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                               const float* head_weights, const uint32_t* where, int32_t k, int32_t largest,
+                               float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                               int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F, int32_t Mx, int32_t workgroups,
+                               impnn_stream_t stream) {
+  GridTopkCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, k, largest, values, cation, anion, workspace,
+                 C, A, nT, D, F, Mx, workgroups, as_stream(stream)};
+  c.masked = true, c.where = where;
+  return grid_topk_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
+                           mix_cat && mix_an && head_weights && values && cation && anion && workspace &&
+                               (kind == 1 || temperatures),
+                           0, workspace_bytes);
+}
+
+int impnn_transfer_head_grid_topk_where(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                        const uint32_t* where, int32_t k, int32_t largest, float* values,
+                                        int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                                        int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream) {
+  GridTopkCall c{1, 1, u_cat, u_an, nullptr, image, k, largest, values, cation, anion, workspace,
+                 C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
+  c.masked = true, c.where = where;
+  return grid_topk_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && workspace,
+                           image_floats, workspace_bytes);
+}
+
+// ---- pair masks (include/impnn.h; grid_mask.hip).  One place applies the family's rules in their fixed order: shape
+// (a NaN bound included), zero work, null pointers, alignment and the image size, the limits of one launch.
+namespace {
+int grid_mask_checked(const char* entry, const GridMaskCall& c, bool shape_ok, bool pointers_ok, int64_t image_floats) {
+  if (c.family == 0 && c.kind != 0 && c.kind != 1)
+    return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", entry);
+  if (!shape_ok || c.C < 0 || c.A < 0 || c.nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (c.family == 0 && c.kind == 0 && c.nT < 1) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
+  if (c.family == 0 && c.kind == 1 && c.nT > 0)
+    return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", entry);
+  if (c.lo != c.lo || c.hi != c.hi) return fail(IMPNN_E_BADARG, "%s: a bound is NaN (an infinity means no limit)", entry);
+  if (c.C == 0 || c.A == 0) return IMPNN_OK;
+  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
+  if ((reinterpret_cast<uintptr_t>(c.words) & 3u) != 0) return fail(IMPNN_E_BADARG, "%s: the mask must be 4-byte aligned", entry);
+  if (c.family == 1) {
+    if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
+      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
+    if (image_floats < transfer_grid_image_floats())
+      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
+                  (long long)transfer_grid_image_floats());
+  } else {
+    if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
+    if (c.nT > head_grid_max_temperatures())
+      return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, c.nT, head_grid_max_temperatures());
+  }
+  return launch_grid_mask(c);
+}
+}  // namespace
+
+int64_t impnn_grid_mask_row_words(int32_t A) { return grid_mask_row_words(A); }
+
+int impnn_head_grid_mask(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                         const float* head_weights, float lo, float hi, uint32_t* words, int32_t C, int32_t A,
+                         int32_t nT, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  const GridMaskCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, lo, hi, words, C, A, nT, D, F, Mx,
+                       as_stream(stream)};
+  return grid_mask_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
+                           mix_cat && mix_an && head_weights && words && (kind == 1 || temperatures), 0);
+}
+
+int impnn_transfer_head_grid_mask(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                  float lo, float hi, uint32_t* words, int32_t C, int32_t A, impnn_stream_t stream) {
+  const GridMaskCall c{1, 1, u_cat, u_an, nullptr, image, lo, hi, words, C, A, 0, 0, 0, 0, as_stream(stream)};
+  return grid_mask_checked(__func__, c, image_floats >= 0, u_cat && u_an && image && words, image_floats);
 }
 
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,

@@ -309,10 +309,25 @@ struct GridTopkCall {
   void* workspace;
   int C, A, nT, D, F, Mx, workgroups;
   hipStream_t stream;
+  bool masked = false;              // the _where entries: only pairs whose bit of `where` is set compete
+  const uint32_t* where = nullptr;  // (C, ceil(A / 32)) words
 };
 int grid_topk_workgroups(int family, int C, int A, int workgroups);  // 0: the default; capped by the tile count
 size_t grid_topk_workspace_bytes(int family, int C, int A, int nT, int k, int workgroups);
 int launch_grid_topk(const GridTopkCall& c);
+
+// ---- pair masks (grid_mask.hip; include/impnn.h, impnn_head_grid_mask / impnn_transfer_head_grid_mask).  One
+// mask-writing launch: family and operands as GridTopkCall; bit (i, j) = lo <= prediction <= hi.  api.hip checks it.
+struct GridMaskCall {
+  int family, kind;
+  const float *mix_cat, *mix_an, *T, *w;
+  float lo, hi;
+  uint32_t* words;  // (C, W), viscosity (nT, C, W); W = grid_mask_row_words(A)
+  int C, A, nT, D, F, Mx;
+  hipStream_t stream;
+};
+int64_t grid_mask_row_words(int A);
+int launch_grid_mask(const GridMaskCall& c);
 
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);

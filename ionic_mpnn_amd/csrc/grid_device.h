@@ -1,7 +1,9 @@
 // Device code the grid kernels share: the tile bodies of head_grid.hip and transfer_grid.hip, which the materialising
-// kernels (impnn_head_grid, impnn_transfer_head_grid) and the selecting kernels (grid_select.hip: impnn_head_grid_topk,
-// impnn_transfer_head_grid_topk) both run, and the keys and the running top-k of the selection.  One definition of a
-// tile's arithmetic, so a selected value has the bits the materialised grid holds for that pair.
+// kernels (impnn_head_grid, impnn_transfer_head_grid), the selecting kernels (grid_select.hip: impnn_head_grid_topk,
+// impnn_transfer_head_grid_topk and their _where forms) and the mask-writing kernels (grid_mask.hip:
+// impnn_head_grid_mask, impnn_transfer_head_grid_mask) all run, and the keys and the running top-k of the selection.
+// One definition of a tile's arithmetic, so a selected or tested value has the bits the materialised grid holds for
+// that pair.
 #pragma once
 
 #include "common.h"
@@ -105,7 +107,7 @@ __device__ __forceinline__ SelectList select_list(void* base, int nT, int cap, i
   int* counts = reinterpret_cast<int*>(bounds + nT);
   return SelectList{bufs + (size_t)t * cap, bounds + t, counts + t};
 }
-inline size_t select_lds_bytes(int nT, int cap) { return (size_t)nT * ((size_t)cap * 8 + 8 + 8); }
+__host__ __device__ inline size_t select_lds_bytes(int nT, int cap) { return (size_t)nT * ((size_t)cap * 8 + 8 + 8); }
 
 // What a selecting launch adds to a grid kernel's arguments: the trailing pack of head_grid_kernel and
 // transfer_grid_kernel.  With it a workgroup is persistent: it walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ...
@@ -155,6 +157,87 @@ __device__ __forceinline__ void select_finish(const GridSelect& g, float* lds, i
     unsigned long long* dst = g.ws + ((size_t)blockIdx.x * nT + t) * g.k;
     for (int i = threadIdx.x; i < g.k; i += blockDim.x) dst[i] = i < kept ? s.buf[i] : kSelectNone;
   }
+}
+
+// ================================================================ pair masks (grid_mask.hip; grid_select.hip)
+// The packed pair mask of include/impnn.h: words[C][W], W = ceil(A / 32), pair (i, j) is bit j & 31 of
+// words[i][j >> 5], pad bits 0.  Both tile shapes start a tile on a word boundary (64 and 32 anions), so a word
+// belongs to one workgroup.
+__host__ __device__ inline int mask_row_words(int A) { return (int)(((int64_t)A + 31) >> 5); }
+
+// A selecting launch over a masked grid: GridSelect plus the mask.  Only pairs whose bit is set compete, and a
+// workgroup passes over a tile none of whose bits is set before it loads a row.  The tile's words sit in LDS behind
+// the lists ([kWhereTileWords]).
+constexpr int kWhereTileWords = 32;  // the larger tile: 16 cations x 2 words
+struct GridSelectWhere : GridSelect {
+  const uint32_t* where;  // [C][W]
+  int W;
+};
+
+// What a mask-writing launch adds: where the materialising form stores a tile, this one tests lo <= v && v <= hi (a NaN
+// fails both), ballots, and one lane per 32-pair span writes the word.  A viscosity mask is [nT][C][W].
+struct GridMask {
+  uint32_t* words;
+  float lo, hi;
+  int W;
+};
+
+// which form of a grid kernel its trailing pack makes
+template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false; };
+template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false; };
+template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false; };
+template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true; };
+
+__device__ __forceinline__ bool select_next_tile(unsigned*, const GridMask&) { return false; }
+
+__device__ __forceinline__ uint32_t* where_tile_words(const GridSelectWhere& g, float* lists, int nT) {
+  return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lists) + select_lds_bytes(nT, g.cap));
+}
+
+// Loads the words of the tile's rows c0 .. c0 + nc, `wpr` words per row from anion word w0, into LDS (word r * wpr + w;
+// 0 where the grid has no such word) and returns whether any bit is set.  Block-uniform: every thread of the workgroup
+// calls it, and it is a barrier (the last tile's readers of these words are behind select_tile's).
+__device__ __forceinline__ bool where_tile_any(const GridSelectWhere& g, float* lists, int nT, int c0, int nc, int w0,
+                                               int wpr) {
+  const int tid = threadIdx.x;
+  uint32_t word = 0;
+  if (tid < kWhereTileWords) {
+    const int r = tid / wpr, w = w0 + tid % wpr;
+    if (r < nc && w < g.W) word = g.where[(int64_t)(c0 + r) * g.W + w];
+    where_tile_words(g, lists, nT)[tid] = word;
+  }
+  return __syncthreads_or(word != 0) != 0;
+}
+
+// the bit of the tile's pair (row r, anion a of the tile), after where_tile_any
+__device__ __forceinline__ bool where_bit(const GridSelectWhere& g, float* lists, int nT, int r, int a, int wpr) {
+  return (where_tile_words(g, lists, nT)[r * wpr + (a >> 5)] >> (a & 31)) & 1u;
+}
+
+// A wave's ballot of `pass` as the mask words of its 64 lanes: lane 0 writes the low word to lo_word, lane 32 the high
+// word to hi_word (null: no such word in the grid).  Ordinary vector stores.
+__device__ __forceinline__ void mask_store_ballot(bool pass, uint32_t* lo_word, uint32_t* hi_word) {
+  const unsigned long long b = __ballot(pass);
+  const int lane = threadIdx.x & 63;
+  if (lane == 0 && lo_word) *lo_word = (uint32_t)b;
+  if (lane == 32 && hi_word) *hi_word = (uint32_t)(b >> 32);
+}
+
+__device__ __forceinline__ uint32_t* mask_word(const GridMask& g, int64_t row, int w) { return g.words + (int64_t)row * g.W + w; }
+__device__ __forceinline__ bool mask_passes(const GridMask& g, float v) { return g.lo <= v && v <= g.hi; }
+
+// The head grid's tile as mask words: value(e, t) is pair e = r * kTileA + a of the tile at temperature t.  A wave's
+// 64 lanes are the 64 anions of one tile row, i.e. that row's two words.
+template <class Fn>
+__device__ __forceinline__ void mask_head_tile(const GridMask& g, int C, int c0, int a0, int nc, int na, int nT, Fn value) {
+  for (int t = 0; t < nT; ++t)
+    for (int q = 0; q < 4; ++q) {  // kTilePairs / 256 threads
+      const int e = q * 256 + (int)threadIdx.x, r = e >> 6, a = e & 63;
+      const float v = value(e, t);
+      uint32_t* row = mask_word(g, t * (int64_t)C + c0 + r, a0 >> 5);
+      mask_store_ballot(r < nc && a < na && mask_passes(g, v), r < nc ? row : nullptr,
+                        r < nc && (a0 >> 5) + 1 < g.W ? row + 1 : nullptr);
+    }
 }
 
 // ================================================================ the head grid (head_grid.hip; grid_select.hip)
@@ -225,12 +308,17 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
   float* mcat = man + kTileA * S;      // [kTileC][S]
   float* wts = mcat + kTileC * S;      // the tail weights
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  constexpr bool kSelect = sizeof...(Sel) > 0;
+  using Form = GridForm<Sel...>;
+  constexpr bool kSelect = Form::select;
   unsigned tile = blockIdx.x;
   if constexpr (kSelect) select_init(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
   do {
   const int c0 = (tile / tiles_a) * kTileC, a0 = (tile % tiles_a) * kTileA;
   const int nc = min(kTileC, C - c0), na = min(kTileA, A - a0);
+  if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
+    if (!where_tile_any(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1, c0, nc, a0 >> 5, kTileA / 32))
+      continue;
+  }
 
   // the tile's mixing rows: contiguous in global memory, padded rows in LDS (the pads are never used)
   for (int idx = tid; idx < na * Mx; idx += blockDim.x) {
@@ -279,7 +367,12 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       select_tile(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, kTilePairs, [&](int q, int t, bool* live, uint32_t* pair) {
         const int e = q * 256 + tid, r = e >> 6, a = e & 63;
         *live = r < nc && a < na;
+        if constexpr (Form::where) *live = *live && where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
         *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a);
+        return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]);
+      });
+    } else if constexpr (Form::mask) {
+      mask_head_tile(sel..., C, c0, a0, nc, na, nT, [&](int e, int t) {
         return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]);
       });
     } else {
@@ -338,9 +431,12 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       select_tile(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, kTilePairs, [&](int q, int, bool* live, uint32_t* pair) {
         const int e = q * 256 + tid, r = e >> 6, a = e & 63;
         *live = r < nc && a < na;
+        if constexpr (Form::where) *live = *live && where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
         *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a);
         return res[e];
       });
+    } else if constexpr (Form::mask) {
+      mask_head_tile(sel..., C, c0, a0, nc, na, 1, [&](int e, int) { return res[e]; });
     } else {
     store_rows(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, 1, [&](int r, int a, int) { return res[r * kTileA + a]; });
     }
@@ -448,12 +544,16 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
   float* bnv = ucat + kTgTileC * kH1;         // scale kH1 | shift kH1
   float* res = bnv + 2 * kH1;                 // [kTgTileC][kTgTileA]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, p = lane & 31, h = lane >> 5;
-  constexpr bool kSelect = sizeof...(Sel) > 0;
+  using Form = GridForm<Sel...>;
+  constexpr bool kSelect = Form::select;
   unsigned tile = blockIdx.x;
   if constexpr (kSelect) select_init(sel..., sm + kTgLdsFloats, 1);
   do {
   const int c0 = (tile / tiles_a) * kTgTileC, a0 = (tile % tiles_a) * kTgTileA;
   const int nc = min(kTgTileC, C - c0), na = min(kTgTileA, A - a0);
+  if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
+    if (!where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) continue;
+  }
 
   // the tile's u rows; the rows of a ragged tile's padding pairs are zero (computed, not stored)
   const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -555,9 +655,16 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
     select_tile(sel..., sm + kTgLdsFloats, 1, kTgTileC * kTgTileA, [&](int, int, bool* live, uint32_t* pair) {
       const int r = tid >> 5;
       *live = r < nc && p < na;
+      if constexpr (Form::where) *live = *live && where_bit(sel..., sm + kTgLdsFloats, 1, r, p, kTgTileA / 32);
       *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + p);
       return res[tid];
     });
+  } else if constexpr (Form::mask) {
+    // a wave's lanes are two tile rows of 32 anions: lane 0 and lane 32 each write the word of their own row
+    const int r = tid >> 5;
+    const float v = res[tid];
+    uint32_t* word = mask_word(sel..., c0 + r, a0 >> 5);
+    mask_store_ballot(r < nc && p < na && mask_passes(sel..., v), r < nc ? word : nullptr, r < nc ? word : nullptr);
   } else {
   store_spans(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, res, kTgTileA);
   }

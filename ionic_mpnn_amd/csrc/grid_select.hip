@@ -9,6 +9,11 @@
 // temperature in the workspace; grid_select_merge_kernel, one workgroup per temperature, runs the same filter and sort
 // over those G * k candidates and writes values and indices.  Entries are unique and totally ordered, so the result is
 // the exact top k whatever the schedule.  No float atomics, no global atomics, no C x A buffer.
+//
+// The _where entries run the same kernels with the GridSelectWhere pack: a pair competes only where its bit of the
+// packed mask is set (the bit joins `live`), and a persistent workgroup first loads its tile's mask words (at most 32)
+// and passes over a tile without a set bit before it loads a row - a block-uniform decision (__syncthreads_or), so a
+// selective constraint costs about the tiles it leaves.  The plain entries keep their own instantiations.
 #include "grid_device.h"
 
 namespace impnn {
@@ -82,15 +87,26 @@ int launch_grid_topk(const GridTopkCall& c) {
   const int cap = select_capacity(c.k, c.family == 0 ? kTilePairs : kTgTileC * kTgTileA);
   unsigned long long* ws = static_cast<unsigned long long*>(c.workspace);
   const GridSelect sel{ws, c.k, cap, c.largest, (unsigned)tiles};
-  const size_t sel_lds = select_lds_bytes(nT, cap);  // <= 64.1 KiB (4 temperatures, k = 1024)
+  GridSelectWhere selw;
+  static_cast<GridSelect&>(selw) = sel;
+  selw.where = c.where, selw.W = mask_row_words(c.A);
+  const size_t where_lds = c.masked ? sizeof(uint32_t) * kWhereTileWords : 0;  // the tile's mask words, behind the lists
+  const size_t sel_lds = select_lds_bytes(nT, cap) + where_lds;  // <= 64.2 KiB (4 temperatures, k = 1024)
   if (c.family == 0) {
     const float* tail = c.w + 2 * ((size_t)c.D * c.F + c.F) + 2 * ((size_t)c.F * c.Mx + c.Mx);
-    const size_t lds = sizeof(float) * grid_lds_floats(c.kind, c.nT, c.F, c.Mx) + sel_lds;  // <= 98.1 KiB
+    const size_t lds = sizeof(float) * grid_lds_floats(c.kind, c.nT, c.F, c.Mx) + sel_lds;  // <= 98.2 KiB
+#define IMPNN_SELECT_AS(KIND, MXR, PACK, pack)                                                                        \
+  do {                                                                                                                \
+    raise_lds_limit(head_grid_kernel<KIND, MXR, PACK>, lds);                                                          \
+    head_grid_kernel<KIND, MXR, PACK><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr,    \
+                                                                 c.C, c.A, c.nT, c.F, c.Mx, tiles_a, pack);           \
+  } while (0)
 #define IMPNN_SELECT(KIND, MXR)                                                                                       \
   do {                                                                                                                \
-    raise_lds_limit(head_grid_kernel<KIND, MXR, GridSelect>, lds);                                                    \
-    head_grid_kernel<KIND, MXR, GridSelect><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr, \
-                                                                       c.C, c.A, c.nT, c.F, c.Mx, tiles_a, sel);      \
+    if (c.masked)                                                                                                     \
+      IMPNN_SELECT_AS(KIND, MXR, GridSelectWhere, selw);                                                              \
+    else                                                                                                              \
+      IMPNN_SELECT_AS(KIND, MXR, GridSelect, sel);                                                                    \
   } while (0)
     if (c.kind == 0)
       IMPNN_SELECT(0, 0);
@@ -99,10 +115,16 @@ int launch_grid_topk(const GridTopkCall& c) {
     else
       IMPNN_SELECT(1, 64);
 #undef IMPNN_SELECT
+#undef IMPNN_SELECT_AS
   } else {
     const size_t lds = sizeof(float) * kTgLdsFloats + sel_lds;  // <= 59.5 KiB
-    raise_lds_limit(transfer_grid_kernel<GridSelect>, lds);
-    transfer_grid_kernel<GridSelect><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, sel);
+    if (c.masked) {
+      raise_lds_limit(transfer_grid_kernel<GridSelectWhere>, lds);
+      transfer_grid_kernel<GridSelectWhere><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, selw);
+    } else {
+      raise_lds_limit(transfer_grid_kernel<GridSelect>, lds);
+      transfer_grid_kernel<GridSelect><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, sel);
+    }
   }
   if (int rc = check_launch(c.family == 0 ? "head_grid_topk" : "transfer_head_grid_topk")) return rc;
   const int mcap = select_capacity(c.k, kMergeRound);

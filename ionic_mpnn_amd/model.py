@@ -1123,8 +1123,94 @@ class MPNNModel:
                         out[lo:hi, :, t0:t1] = got.cpu().numpy()
         return (out, params) if return_params else out
 
+    def screen_mask(self, cations, anions, temperatures=None, at_least=None, at_most=None, max_pairs_per_launch=None,
+                    batch_size=4096):
+        """A screen's constraint as a packed pair mask, written on the GPU: bit (i, j[, t]) is set where
+        ``at_least <= prediction <= at_most`` for the value ``predict_grid`` gives that element -> ``data.PairMask`` of
+        shape (C,A), viscosity (C,A,nT), its words on the model's device.  At least one bound is needed; a missing one is
+        -inf / +inf; bounds are compared as float32, a NaN prediction fails.  ``encode_ions``, the per-ion halves and
+        the host tiling of the cation axis are ``predict_grid``'s; the mask-writing kernels (impnn_head_grid_mask,
+        impnn_transfer_head_grid_mask; the transfer model in "auto" on the matrix cores) evaluate every pair with the
+        grid kernels' arithmetic, and no C x A float buffer exists.  Widths the head kernels do not cover and the
+        transfer model with ``grid_head_mode = "gathered"`` evaluate ``predict_grid``'s tiles, compare and pack
+        instead; more temperatures than one launch takes are split.  The result is the same.
+        Masks compose (``&``, ``|``, ``~``) and constrain ``screen_top_k``: "of the pairs the melting-point model puts
+        below a limit and nobody has made yet, the 100 least viscous at 298 K" is
+
+            liquid = mp_model.screen_mask(cat, an, at_most=limit_scaled)
+            known  = data.PairMask.from_bool(already_made, device=liquid.words.device)
+            best   = visc_model.screen_top_k(cat, an, [298.15], k=100, where=liquid & ~known)
+
+        (the melting-point model predicts the standardised target: convert a kelvin limit with the training set's
+        ``y_mean`` / ``y_std`` first)."""
+        if at_least is None and at_most is None:
+            raise ValueError("screen_mask needs a bound: at_least, at_most or both")
+        lo = np.float32(-np.inf if at_least is None else at_least)
+        hi = np.float32(np.inf if at_most is None else at_most)
+        if np.isnan(lo) or np.isnan(hi):
+            raise ValueError("a screen_mask bound is NaN")
+        if self.kind == "viscosity" and temperatures is None:
+            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
+        if cations is None or anions is None:
+            raise ValueError("screen_mask needs both cations and anions")
+        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
+            raise ValueError("max_pairs_per_launch must be >= 1")
+        visc = self.kind == "viscosity"
+        T = None
+        if visc:
+            T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
+            T = T.to(torch.float32).reshape(-1)
+            if T.numel() == 0:
+                raise ValueError("temperatures must hold at least one value")
+        pc, pa = self.encode_ions(cations, anions, batch_size)
+        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
+        W = data.mask_row_words(A)
+        words = torch.zeros((nT, C, W) if visc else (C, W), dtype=torch.int32, device=self.device)
+        mask = data.PairMask(words, (C, A, nT) if visc else (C, A))
+        if C == 0 or A == 0:
+            return mask
+        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
+        covered = self._grid_kernels_cover() or mfma
+        if max_pairs_per_launch is None:
+            max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
+            if not covered:
+                max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
+        rows = max(1, int(max_pairs_per_launch) // A)
+        with torch.no_grad():
+            if visc:
+                T = T.to(self.device)
+            if mfma:
+                tensors, image = self._head_tensors(), self._transfer_image()
+                mc = ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size)
+                ma = ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size)
+            elif covered:
+                w = self._packed_head()
+                mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
+                ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
+            for c0 in range(0, C, rows):
+                c1 = min(C, c0 + rows)
+                if not covered:
+                    tile = self._grid_gathered(pc[c0:c1], pa, T).cpu().numpy()
+                    got = data.PairMask.from_bool((tile >= lo) & (tile <= hi), device=self.device).words
+                    if visc:
+                        words[:, c0:c1] = got
+                    else:
+                        words[c0:c1] = got
+                elif mfma:
+                    words[c0:c1] = ops.transfer_head_grid_mask(mc[c0:c1], ma, image, lo, hi)
+                elif not visc:
+                    words[c0:c1] = ops.head_grid_mask(self.kind, mc[c0:c1], ma, None, w, self.fp_size, self.mixing_size,
+                                                      lo, hi)
+                else:
+                    for t0 in range(0, nT, GRID_MAX_TEMPERATURES):
+                        t1 = min(nT, t0 + GRID_MAX_TEMPERATURES)
+                        words[t0:t1, c0:c1] = ops.head_grid_mask(self.kind, mc[c0:c1], ma, T[t0:t1], w, self.fp_size,
+                                                                 self.mixing_size, lo, hi)
+        return mask
+
     def screen_top_k(self, cations, anions, temperatures=None, k=100, largest=False, max_pairs_per_launch=None,
-                     batch_size=4096):
+                     batch_size=4096, where=None):
         """The k pairs of a screen with the smallest (``largest``: largest) prediction, selected on the GPU: what
         ``data.grid_top_k(self.predict_grid(...), k, largest)`` returns, without the grid.  ``encode_ions`` and the
         per-ion halves are ``predict_grid``'s; the selecting kernels (impnn_head_grid_topk,
@@ -1136,11 +1222,26 @@ class MPNNModel:
         overrides it), temperatures are split at ops.SELECT_MAX_T per launch, and the launches' results are merged
         under the same order.  Widths the head kernels do not cover, the transfer model with ``grid_head_mode =
         "gathered"`` and k above SCREEN_MAX_K walk ``predict_grid``'s tiles instead and select per tile: never more than
-        one tile and k entries are held."""
+        one tile and k entries are held.
+        ``where``: a 2-D ``data.PairMask`` of shape (C,A) (``screen_mask``, ``PairMask.from_bool``, and their ``&``,
+        ``|``, ``~``); only its pairs compete, in every temperature row (for one plane of a viscosity mask take
+        ``temperature(t)`` and call per row), and a row has min(k, where.count()) entries.  The selecting kernels read
+        the mask (impnn_head_grid_topk_where, impnn_transfer_head_grid_topk_where) and pass over tiles without a set
+        bit; it is tiled with the cation axis and honoured by every fallback too.  See ``screen_mask`` for the
+        intended use."""
         if self.kind == "viscosity" and temperatures is None:
             raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
         if cations is None or anions is None:
             raise ValueError("screen_top_k needs both cations and anions")
+        if where is not None:
+            if not isinstance(where, data.PairMask):
+                raise TypeError(f"where must be a data.PairMask, got {type(where).__name__}")
+            if len(where.shape) != 2:
+                raise ValueError("where must be a 2-D mask over (cation, anion): take temperature(t) of a viscosity mask "
+                                 "and call per temperature")
+            given = (len(cations["atom"]), len(anions["atom"]))
+            if where.shape != given:
+                raise ValueError(f"where has shape {where.shape}, the screen is {given[0]} cations x {given[1]} anions")
         if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
             raise ValueError("max_pairs_per_launch must be >= 1")
         k = int(k)
@@ -1157,6 +1258,8 @@ class MPNNModel:
         pc, pa = self.encode_ions(cations, anions, batch_size)
         C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
         n_rows = nT if visc else 1
+        if where is not None and where.words.device != pc.device:
+            where = data.PairMask(where.words.to(pc.device), where.shape)
         mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
         covered = self._grid_kernels_cover() or mfma
         select = covered and k <= SCREEN_MAX_K
@@ -1193,11 +1296,12 @@ class MPNNModel:
                         t1 = min(n_rows, t0 + t_step)
                         Tt = T[t0:t1] if visc else None
                         if select:
+                            wh = where.rows(lo, hi).words if where is not None else None
                             if mfma:
-                                got = ops.transfer_head_grid_topk(mc[lo:hi], ma, image, k, largest)
+                                got = ops.transfer_head_grid_topk(mc[lo:hi], ma, image, k, largest, where=wh)
                             else:
                                 got = ops.head_grid_topk(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size,
-                                                         self.mixing_size, k, largest)
+                                                         self.mixing_size, k, largest, where=wh)
                             v, ci, ai = (x.cpu().numpy() for x in got)
                             for r in range(t1 - t0):
                                 used = ci[r] >= 0
@@ -1211,10 +1315,13 @@ class MPNNModel:
                                 tile = ops.head_grid(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size, self.mixing_size)
                             tile = tile.cpu().numpy().reshape((hi - lo) * A, -1)
                             flat = np.arange(lo * A, hi * A, dtype=np.int64)
+                            if where is not None:  # only the mask's pairs reach the order
+                                keep = np.flatnonzero(where.rows(lo, hi).to_bool().reshape(-1))
+                                tile, flat = tile[keep], flat[keep]
                             for r in range(t1 - t0):
                                 order = data.top_k_order(tile[:, r], flat, k, largest)
                                 offer(t0 + r, tile[order, r], flat[order])
-        m = min(k, C * A)
+        m = min(k, C * A if where is None else where.count())
         values = np.empty((n_rows, m), np.float32)
         cation, anion = np.empty((n_rows, m), np.int64), np.empty((n_rows, m), np.int64)
         for r, (v, f) in enumerate(best):

@@ -855,12 +855,25 @@ def _grid_topk_outputs(lib, family, C_, A_, nT, k, workgroups, dev):
     return values, cation, anion, _workspace(dev, need.value), need.value
 
 
+def _mask_words(where, C_, A_, dev):
+    """``where`` of the top-k wrappers: a (C,W) int32 tensor of mask words, or an object with such ``words``."""
+    where = getattr(where, "words", where)
+    require_gpu(where)
+    want = (C_, (A_ + 31) // 32)
+    if where.dtype != torch.int32 or tuple(where.shape) != want or where.device != dev:
+        raise ValueError(f"where must be int32 mask words of shape {want} on {dev}, got {where.dtype} "
+                         f"{tuple(where.shape)} on {where.device}")
+    return where.contiguous()
+
+
 def head_grid_topk(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, k, largest=False,
-                   workgroups=0):
+                   workgroups=0, where=None):
     """The k best pairs of ``head_grid``'s product without the product (impnn_head_grid_topk): the same arguments, ->
     values (nT,k) float32, cation (nT,k), anion (nT,k) int32 on the device, a row per temperature (one row for
     "melting_point"), sorted under the order of ``data.grid_top_k``; slots past C*A hold NaN / -1.  A value has the
-    bits ``head_grid`` gives for its pair.  k <= SELECT_MAX_K, at most SELECT_MAX_T temperatures, C*A < 2^32."""
+    bits ``head_grid`` gives for its pair.  k <= SELECT_MAX_K, at most SELECT_MAX_T temperatures, C*A < 2^32.
+    ``where``: the (C,W) words of a pair mask (``head_grid_mask``, ``data.PairMask``): only its pairs compete
+    (impnn_head_grid_topk_where), slots past their count hold NaN / -1."""
     require_gpu(mix_cat, mix_an, head_weights)
     mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
     kd = HEAD_KINDS[kind]
@@ -885,17 +898,26 @@ def head_grid_topk(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, m
         raise ValueError("the melting-point grid takes no temperatures")
     dev = mix_cat.device
     k, workgroups = int(k), int(workgroups)
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
     with torch.cuda.device(dev):
         values, cation, anion, ws, nbytes = _grid_topk_outputs(lib, 0, C_, A_, nT, k, workgroups, dev)
-        check(lib.impnn_head_grid_topk(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
-                                       ptr(head_weights), k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion),
-                                       ptr(ws), nbytes, C_, A_, nT, D, fp_size, mixing_size, workgroups, stream_ptr()))
+        if where is None:
+            check(lib.impnn_head_grid_topk(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
+                                           ptr(head_weights), k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion),
+                                           ptr(ws), nbytes, C_, A_, nT, D, fp_size, mixing_size, workgroups, stream_ptr()))
+        else:
+            check(lib.impnn_head_grid_topk_where(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
+                                                 ptr(head_weights), ptr(where), k, int(bool(largest)), ptr(values),
+                                                 ptr(cation), ptr(anion), ptr(ws), nbytes, C_, A_, nT, D, fp_size,
+                                                 mixing_size, workgroups, stream_ptr()))
     return values, cation, anion
 
 
-def transfer_head_grid_topk(u_cat, u_an, image, k, largest=False, workgroups=0):
+def transfer_head_grid_topk(u_cat, u_an, image, k, largest=False, workgroups=0, where=None):
     """The k best pairs of ``transfer_head_grid``'s product without the product (impnn_transfer_head_grid_topk) ->
-    values (1,k) float32, cation (1,k), anion (1,k) int32 on the device, as ``head_grid_topk``."""
+    values (1,k) float32, cation (1,k), anion (1,k) int32 on the device, as ``head_grid_topk``; ``where`` as there
+    (impnn_transfer_head_grid_topk_where)."""
     require_gpu(u_cat, u_an, image)
     u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
     W = TRANSFER_GRID_WIDTH
@@ -907,12 +929,84 @@ def transfer_head_grid_topk(u_cat, u_an, image, k, largest=False, workgroups=0):
     C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
     dev = u_cat.device
     k, workgroups = int(k), int(workgroups)
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
     with torch.cuda.device(dev):
         values, cation, anion, ws, nbytes = _grid_topk_outputs(lib, 1, C_, A_, 0, k, workgroups, dev)
-        check(lib.impnn_transfer_head_grid_topk(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), k, int(bool(largest)),
-                                                ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, C_, A_, workgroups,
-                                                stream_ptr()))
+        if where is None:
+            check(lib.impnn_transfer_head_grid_topk(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), k, int(bool(largest)),
+                                                    ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, C_, A_, workgroups,
+                                                    stream_ptr()))
+        else:
+            check(lib.impnn_transfer_head_grid_topk_where(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), ptr(where), k,
+                                                          int(bool(largest)), ptr(values), ptr(cation), ptr(anion), ptr(ws),
+                                                          nbytes, C_, A_, workgroups, stream_ptr()))
     return values, cation, anion
+
+
+def _mask_bounds(lo, hi):
+    lo, hi = C.c_float(lo).value, C.c_float(hi).value  # as the kernels see them: float32
+    if lo != lo or hi != hi:
+        raise ValueError("a mask bound is NaN (an infinity means no limit)")
+    return lo, hi
+
+
+def head_grid_mask(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, lo, hi):
+    """``head_grid``'s product as a packed pair mask (impnn_head_grid_mask): bit (i,j[,t]) = lo <= v <= hi for the value
+    v ``head_grid`` gives that element (a NaN fails; +-inf: no limit) -> int32 words (C,W), "viscosity" (nT,C,W), W =
+    ceil(A / 32), pad bits 0: the ``words`` of a ``data.PairMask`` of shape (C,A) / (C,A,nT).  No (C,A) floats exist."""
+    require_gpu(mix_cat, mix_an, head_weights)
+    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
+    kd = HEAD_KINDS[kind]
+    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
+        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
+                         f"and {tuple(mix_an.shape)}")
+    lo, hi = _mask_bounds(lo, hi)
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    lib = _lib.load()
+    per_d = 2 * fp_size
+    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
+    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
+    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+    dev = mix_cat.device
+    W = int(lib.impnn_grid_mask_row_words(A_))
+    T, nT = None, 0
+    if kd == 0:
+        if temperatures is None:
+            raise ValueError("the viscosity grid needs temperatures")
+        require_gpu(temperatures)
+        T = f32c(temperatures).reshape(-1)
+        nT = int(T.numel())
+        words = torch.empty(nT, C_, W, dtype=torch.int32, device=dev)
+    else:
+        if temperatures is not None:
+            raise ValueError("the melting-point grid takes no temperatures")
+        words = torch.empty(C_, W, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.impnn_head_grid_mask(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None, ptr(head_weights),
+                                       lo, hi, ptr(words), C_, A_, nT, D, fp_size, mixing_size, stream_ptr()))
+    return words
+
+
+def transfer_head_grid_mask(u_cat, u_an, image, lo, hi):
+    """``transfer_head_grid``'s product as a packed pair mask (impnn_transfer_head_grid_mask) -> int32 words (C,W), as
+    ``head_grid_mask``."""
+    require_gpu(u_cat, u_an, image)
+    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
+    Wd = TRANSFER_GRID_WIDTH
+    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != Wd or u_an.shape[1] != Wd:
+        raise ValueError(f"u rows must be (C,{Wd}) and (A,{Wd}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
+    lo, hi = _mask_bounds(lo, hi)
+    lib = _lib.load()
+    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
+        raise ValueError("the prepared image has the wrong length")
+    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
+    words = torch.empty(C_, int(lib.impnn_grid_mask_row_words(A_)), dtype=torch.int32, device=u_cat.device)
+    with torch.cuda.device(u_cat.device):
+        check(lib.impnn_transfer_head_grid_mask(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), lo, hi, ptr(words), C_, A_,
+                                                stream_ptr()))
+    return words
 
 
 def transfer_head(pooled_cat, pooled_an, weights, cfg):

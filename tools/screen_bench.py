@@ -5,6 +5,7 @@ matrix-core grid, impnn_transfer_head_grid), plus that kernel alone against the 
 
 python tools/screen_bench.py [--quick] [--only viscosity|transfer]      -> one JSON line per configuration, appended to profiles/screen_bench.jsonl
 python tools/screen_bench.py --select [--quick] [--only ...]            -> the top-k selection instead (see below)
+python tools/screen_bench.py --select --where FRACTION [--quick]        -> the constrained screen instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -16,7 +17,15 @@ data.grid_top_k on the host, at the configurations above and at two larger ones 
 same three alternating rounds, wall time around each side (the host sort is part of the old way).  Plus the selecting
 launches alone (impnn_head_grid_topk / impnn_transfer_head_grid_topk with their merge; a viscosity sweep above
 ops.SELECT_MAX_T temperatures takes several) against the materialising launch of the same C x A x nT, 10 calls
-between two HIP events."""
+between two HIP events.
+
+--select --where F: the constrained screen "of the pairs the melting-point model puts below a limit, the k least viscous
+at 298.15 K", the limit being the F quantile of the melting-point grid.  Three alternating rounds after a warm-up, wall
+time, of (a) mp.screen_mask + visc.screen_top_k(where=) against (b) the way to the same answer without them: two
+predict_grid calls and data.grid_top_k(where=) on the host; screen_mask and screen_top_k(where=) also on their own.  Then
+the selecting launches alone, 10 calls between two HIP events, five rounds each in turn: plain, an all-ones mask, a
+random mask of density F, and a block-structured mask of the same density (whole tiles of the kernel set or clear), for
+the head grid and the transfer grid; and the mask-writing launch against the materialising one."""
 import argparse
 import json
 import statistics
@@ -35,6 +44,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="the first configuration only")
 ap.add_argument("--only", choices=("viscosity", "transfer"), help="one family of configurations")
 ap.add_argument("--select", action="store_true", help="time screen_top_k against predict_grid + host selection")
+ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: the constrained screen at this mask density")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -176,7 +186,90 @@ def same_top(a, b):
                               if y.dtype == np.float32 else y) for x, y in zip(a, b))
 
 
-if args.select:
+# ---- --select --where F: the constrained screen
+# (name, atom_dim, steps, C, A)
+WHERE_CONFIGS = [("where 1024x1024", 32, 3, 1024, 1024), ("where 4096x4096", 32, 3, 4096, 4096)]
+T_ROOM = np.array([298.15], np.float32)
+
+
+def block_mask(C, A, tile, fraction, rng):
+    """Whole tiles of tile = (rows, anions) set with probability `fraction`: the density of a random mask, in blocks."""
+    tc, ta = tile
+    on = rng.random(((C + tc - 1) // tc, (A + ta - 1) // ta)) < fraction
+    return np.repeat(np.repeat(on, tc, axis=0), ta, axis=1)[:C, :A]
+
+
+def spread(xs):
+    return {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+
+
+if args.select and args.where is not None:
+    F = float(args.where)
+    for name, D, S, C, A in WHERE_CONFIGS[:1] if args.quick else WHERE_CONFIGS:
+        m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
+        m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
+        mp = MM.build_melting_point_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
+        mp.load_weights(weights.init_weights("melting_point", Va, Vb, atom_dim=D, bond_dim=D * D, num_steps=S, seed=2, perturb=True))
+        t = build_transfer(D, S)
+        cat, _ = species(C, 1)
+        _, an = species(A, 2)
+        limit = np.float32(np.quantile(mp.predict_grid(cat, an), F))
+        new_mask = lambda: mp.screen_mask(cat, an, at_most=limit)
+        new_way = lambda: m.screen_top_k(cat, an, T_ROOM, k=SELECT_K, where=new_mask())
+        old_way = lambda: data.grid_top_k(m.predict_grid(cat, an, T_ROOM), SELECT_K, where=mp.predict_grid(cat, an) <= limit)
+        _, liquid = wall(new_mask)
+        new_top = lambda: m.screen_top_k(cat, an, T_ROOM, k=SELECT_K, where=liquid)
+        _, top_old = wall(old_way)
+        _, top_new = wall(new_way)
+        wall(new_top)
+        t_old, t_new, t_mask, t_top = [], [], [], []
+        for _ in range(3):
+            t_old.append(wall(old_way)[0])
+            t_new.append(wall(new_way)[0])
+            t_mask.append(wall(new_mask)[0])
+            t_top.append(wall(new_top)[0])
+        line = {"config": name + " F=%g" % F, "atom_dim": D, "steps": S, "C": C, "A": A, "k": SELECT_K, "fraction": F,
+                "mask_density": round(liquid.count() / (C * A), 4),
+                "two_grids_plus_host_top_k_ms": spread(t_old), "screen_mask_plus_top_k_where_ms": spread(t_new),
+                "speedup": round(statistics.median(t_old) / statistics.median(t_new), 2),
+                "screen_mask_ms": spread(t_mask), "screen_top_k_where_ms": spread(t_top), "same_answer": same_top(top_old, top_new)}
+        # the launches alone
+        rng = np.random.default_rng(5)
+        with torch.no_grad():
+            pc, pa = m.encode_ions(cat, an)
+            w = m._packed_head()
+            mc = ops.head_ion_mix("viscosity", "cat", pc, w, m.fp_size, m.mixing_size)
+            ma = ops.head_ion_mix("viscosity", "an", pa, w, m.fp_size, m.mixing_size)
+            Td = torch.from_numpy(T_ROOM).to(dev)
+            tensors, image = t._head_tensors(), t._transfer_image()
+            tpc, tpa = t.encode_ions(cat, an)
+            uc = ops.transfer_ion_half("cat", tpc, tensors, t.fp_size, t.mixing_size)
+            ua = ops.transfer_ion_half("an", tpa, tensors, t.fp_size, t.mixing_size)
+            for fam, tile, topk, grid, mask in (
+                    ("head", (16, 64), lambda wh: ops.head_grid_topk("viscosity", mc, ma, Td, w, m.fp_size, m.mixing_size, SELECT_K, where=wh),
+                     lambda: ops.head_grid("viscosity", mc, ma, Td, w, m.fp_size, m.mixing_size),
+                     lambda: ops.head_grid_mask("viscosity", mc, ma, Td, w, m.fp_size, m.mixing_size, -np.inf, 0.0)),
+                    ("transfer", (8, 32), lambda wh: ops.transfer_head_grid_topk(uc, ua, image, SELECT_K, where=wh),
+                     lambda: ops.transfer_head_grid(uc, ua, image), lambda: ops.transfer_head_grid_mask(uc, ua, image, -np.inf, 0.0))):
+                masks = {"plain": None, "ones": data.PairMask.from_bool(np.ones((C, A), bool), device=dev).words,
+                         "random": data.PairMask.from_bool(rng.random((C, A)) < F, device=dev).words,
+                         "block": data.PairMask.from_bool(block_mask(C, A, tile, F, rng), device=dev).words}
+                runs = {n: (lambda wh=wh: [topk(wh) for _ in range(10)]) for n, wh in masks.items()}
+                runs["materialise"] = lambda: [grid() for _ in range(10)]
+                runs["mask"] = lambda: [mask() for _ in range(10)]
+                got = {n: [] for n in runs}
+                for fn in runs.values():
+                    timed(fn)
+                for _ in range(5):
+                    for n, fn in runs.items():
+                        got[n].append(timed(fn)[0] / 10 * 1e3)
+                line[fam + "_launch_us"] = {n: spread(x) for n, x in got.items()}
+                line[fam + "_block_density"] = round(data.PairMask(masks["block"], (C, A)).count() / (C * A), 4)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del m, mp, t
+        torch.cuda.empty_cache()
+elif args.select:
     todo = [c for c in SELECT_CONFIGS if args.only in (None, c[0])]
     for kind, name, D, S, C, A, nT in todo[:1] if args.quick else todo:
         if kind == "viscosity":
