@@ -576,6 +576,42 @@ int impnn_transfer_head_grid_topk_where(const float* u_cat, const float* u_an, c
                                         int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
                                         int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream);
 
+/* ---- each ion's best partners, selected on the GPU: for every cation its m best anions and for every anion its m
+ *      best cations, from ONE launch over the grid and without its (C,A[,nT]) output.  The partner-selecting kernels run
+ *      the tile arithmetic of impnn_head_grid / impnn_transfer_head_grid (a selected value has the bits those entries
+ *      write for the pair), one tile (16 x 64, 8 x 32 pairs) per workgroup, and select from the tile's values on the
+ *      chip: a tile row by m rounds of a 64-bit minimum across a wave's lanes, a tile column by one thread that keeps m
+ *      entries in registers; a second small launch, one thread per (temperature, ion), merges the tiles' candidates.
+ *      No C x A buffer, no atomics, no pre-zeroed memory.
+ *      Order: the entry of impnn_head_grid_topk, (key << 32) | (i * A + j), compared as an unsigned 64-bit integer.  For
+ *      a fixed cation that is: by value, ties by anion index, NaN last; for a fixed anion: by value, ties by cation
+ *      index, NaN last.  The result is exact and independent of tiles, launches and schedule.
+ *      where: NULL, or a (C,W) pair mask (see below), 4-byte aligned: only pairs whose bit is set compete, the one mask
+ *      for every temperature; a workgroup passes over a tile none of whose bits is set before it loads a row.
+ *      Outputs: cat_values float / cat_partner int32 [max(nT,1)][C][m], the anion index of cation i's s-th best in
+ *      slot [t][i][s]; an_values / an_partner [max(nT,1)][A][m], cation indices.  Ascending under the order; a NaN
+ *      value comes back as the quiet NaN 0x7FC00000; slots past the number of competing partners of that ion hold
+ *      NaN / -1.  The melting-point and transfer grids have one plane (nT = 0 in the call).
+ *      Limits of one call: 1 <= m <= 8; kind 0: 1 <= nT <= 4 (split longer sweeps, a plane does not depend on the
+ *      others); C * A < 2^32; the widths of impnn_head_grid.
+ *      workspace: impnn_grid_partners_workspace_bytes bytes for the same (family, C, A, nT, m), 8-byte aligned, family
+ *      0 = impnn_head_grid_partners, 1 = impnn_transfer_head_grid_partners; it holds [nT][tiles_a][C][m] and
+ *      [nT][tiles_c][A][m] entries between the two launches, every one written by the first, and carries nothing from
+ *      call to call.
+ *      Checks in order, as impnn_head_grid_topk: shape (kind, sizes, nT, m, the limits, C * A; IMPNN_E_BADARG, a limit
+ *      IMPNN_E_UNSUPPORTED); zero work (C == 0 or A == 0: IMPNN_OK, nothing touched); null pointers, then alignment and
+ *      the image size; the workspace size (IMPNN_E_WORKSPACE).  No allocation, no synchronisation, no state. */
+int impnn_grid_partners_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t m, size_t* need);
+int impnn_head_grid_partners(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                             const float* head_weights, const uint32_t* where, int32_t m, int32_t largest,
+                             float* cat_values, int32_t* cat_partner, float* an_values, int32_t* an_partner,
+                             void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t D,
+                             int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_head_grid_partners(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                      const uint32_t* where, int32_t m, int32_t largest, float* cat_values,
+                                      int32_t* cat_partner, float* an_values, int32_t* an_partner, void* workspace,
+                                      size_t workspace_bytes, int32_t C, int32_t A, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

@@ -741,36 +741,95 @@ int grid_topk_shape(const char* entry, int family, int C, int A, int nT, int k, 
   return IMPNN_OK;
 }
 
-int grid_topk_checked(const char* entry, const GridTopkCall& c, bool widths_ok, bool pointers_ok, int64_t image_floats,
-                      size_t workspace_bytes) {
-  if (c.family == 0) {
-    if (c.kind != 0 && c.kind != 1) return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", entry);
-    if (!widths_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
-    if (c.kind == 0 && c.nT < 1 && c.nT >= 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
-    if (c.kind == 1 && c.nT > 0)
-      return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", entry);
+// What the selecting entries (top-k, best partners) share of a request: the operands and the buffers between launches.
+struct GridRequest {
+  const char* entry;
+  int family, kind;
+  const float *mix_cat, *mix_an, *T, *w;
+  const void* workspace;
+  const uint32_t* where;
+  bool where_needed;  // a _where entry: a null mask is a null pointer
+  int C, A, nT, D, F, Mx;
+};
+
+// before the entry's own shape rule: the kind, the widths' signs and the temperature count of the kind
+int grid_request_kind(const GridRequest& r, bool widths_ok, int64_t image_floats) {
+  if (r.family == 0) {
+    if (r.kind != 0 && r.kind != 1) return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", r.entry);
+    if (!widths_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", r.entry);
+    if (r.kind == 0 && r.nT < 1 && r.nT >= 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", r.entry);
+    if (r.kind == 1 && r.nT > 0)
+      return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", r.entry);
   } else if (image_floats < 0) {
-    return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+    return fail(IMPNN_E_BADARG, "%s: bad shape", r.entry);
   }
-  if (int rc = grid_topk_shape(entry, c.family, c.C, c.A, c.nT, c.k, c.workgroups)) return rc;
-  if (c.family == 0)
-    if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
-  if (c.C == 0 || c.A == 0) return IMPNN_OK;
-  if (!pointers_ok || (c.masked && !c.where)) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
-  if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
-  if ((reinterpret_cast<uintptr_t>(c.workspace) & 7u) != 0) return fail(IMPNN_E_BADARG, "%s: the workspace must be 8-byte aligned", entry);
-  if ((reinterpret_cast<uintptr_t>(c.where) & 3u) != 0) return fail(IMPNN_E_BADARG, "%s: the mask must be 4-byte aligned", entry);
-  if (c.family == 1) {
-    if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
-      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
+  return IMPNN_OK;
+}
+
+// after it: the widths' limits, zero work (IMPNN_OK with *launch == false), null pointers, alignment and the image
+// size, the workspace size (`need`: the entry's query for the request's shape)
+int grid_request_operands(const GridRequest& r, bool pointers_ok, int64_t image_floats, size_t need, size_t workspace_bytes,
+                          bool* launch) {
+  *launch = false;
+  if (r.family == 0)
+    if (int rc = head_widths_covered(r.entry, r.D, r.F, r.Mx)) return rc;
+  if (r.C == 0 || r.A == 0) return IMPNN_OK;
+  if (!pointers_ok || (r.where_needed && !r.where)) return fail(IMPNN_E_BADARG, "%s: null pointer", r.entry);
+  if (r.family == 0 && r.kind == 1 && r.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", r.entry);
+  if ((reinterpret_cast<uintptr_t>(r.workspace) & 7u) != 0) return fail(IMPNN_E_BADARG, "%s: the workspace must be 8-byte aligned", r.entry);
+  if ((reinterpret_cast<uintptr_t>(r.where) & 3u) != 0) return fail(IMPNN_E_BADARG, "%s: the mask must be 4-byte aligned", r.entry);
+  if (r.family == 1) {
+    if (!(aligned16(r.mix_cat) && aligned16(r.mix_an) && aligned16(r.w)))
+      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", r.entry);
     if (image_floats < transfer_grid_image_floats())
-      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
+      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", r.entry, (long long)image_floats,
                   (long long)transfer_grid_image_floats());
   }
-  const size_t need = grid_topk_workspace_bytes(c.family, c.C, c.A, c.nT, c.k, c.workgroups);
   if (workspace_bytes < need)
-    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", entry, workspace_bytes, need);
-  return launch_grid_topk(c);
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", r.entry, workspace_bytes, need);
+  *launch = true;
+  return IMPNN_OK;
+}
+
+int grid_topk_checked(const char* entry, const GridTopkCall& c, bool widths_ok, bool pointers_ok, int64_t image_floats,
+                      size_t workspace_bytes) {
+  const GridRequest r{entry, c.family, c.kind, c.mix_cat, c.mix_an, c.T, c.w, c.workspace, c.where, c.masked,
+                      c.C, c.A, c.nT, c.D, c.F, c.Mx};
+  if (int rc = grid_request_kind(r, widths_ok, image_floats)) return rc;
+  if (int rc = grid_topk_shape(entry, c.family, c.C, c.A, c.nT, c.k, c.workgroups)) return rc;
+  bool launch;
+  if (int rc = grid_request_operands(r, pointers_ok, image_floats,
+                                     grid_topk_workspace_bytes(c.family, c.C, c.A, c.nT, c.k, c.workgroups), workspace_bytes,
+                                     &launch))
+    return rc;
+  return launch ? launch_grid_topk(c) : IMPNN_OK;
+}
+
+// ---- each ion's best partners (include/impnn.h; grid_partners.hip): the same request, its own shape rule
+int grid_partners_shape(const char* entry, int family, int C, int A, int nT, int m) {
+  if (family != 0 && family != 1) return fail(IMPNN_E_BADARG, "%s: family must be 0 (head grid) or 1 (transfer grid)", entry);
+  if (C < 0 || A < 0 || nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (m < 1) return fail(IMPNN_E_BADARG, "%s: m=%d must be at least 1", entry, m);
+  if (m > kPartnersMaxM) return fail(IMPNN_E_UNSUPPORTED, "%s: m=%d partners (<= %d per call)", entry, m, kPartnersMaxM);
+  if (nT > kSelectMaxT)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
+  if ((int64_t)C * A >= (int64_t)1 << 32)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (< 2^32 per call); split the cation axis", entry,
+                (long long)((int64_t)C * A));
+  return IMPNN_OK;
+}
+
+int grid_partners_checked(const char* entry, const GridPartnersCall& c, bool widths_ok, bool pointers_ok,
+                          int64_t image_floats, size_t workspace_bytes) {
+  const GridRequest r{entry, c.family, c.kind, c.mix_cat, c.mix_an, c.T, c.w, c.workspace, c.where, false,
+                      c.C, c.A, c.nT, c.D, c.F, c.Mx};
+  if (int rc = grid_request_kind(r, widths_ok, image_floats)) return rc;
+  if (int rc = grid_partners_shape(entry, c.family, c.C, c.A, c.nT, c.m)) return rc;
+  bool launch;
+  if (int rc = grid_request_operands(r, pointers_ok, image_floats,
+                                     grid_partners_workspace_bytes(c.family, c.C, c.A, c.nT, c.m), workspace_bytes, &launch))
+    return rc;
+  return launch ? launch_grid_partners(c) : IMPNN_OK;
 }
 }  // namespace
 
@@ -829,6 +888,37 @@ int impnn_transfer_head_grid_topk_where(const float* u_cat, const float* u_an, c
   c.masked = true, c.where = where;
   return grid_topk_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && workspace,
                            image_floats, workspace_bytes);
+}
+
+int impnn_grid_partners_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t m, size_t* need) {
+  if (int rc = grid_partners_shape(__func__, family, C, A, nT, m)) return rc;
+  REQUIRE(need, "null pointer");
+  *need = grid_partners_workspace_bytes(family, C, A, nT, m);
+  return IMPNN_OK;
+}
+
+int impnn_head_grid_partners(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                             const float* head_weights, const uint32_t* where, int32_t m, int32_t largest,
+                             float* cat_values, int32_t* cat_partner, float* an_values, int32_t* an_partner,
+                             void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t D,
+                             int32_t F, int32_t Mx, impnn_stream_t stream) {
+  const GridPartnersCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, where, m, largest, cat_values, cat_partner,
+                           an_values, an_partner, workspace, C, A, nT, D, F, Mx, as_stream(stream)};
+  return grid_partners_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
+                               mix_cat && mix_an && head_weights && cat_values && cat_partner && an_values && an_partner &&
+                                   workspace && (kind == 1 || temperatures),
+                               0, workspace_bytes);
+}
+
+int impnn_transfer_head_grid_partners(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                      const uint32_t* where, int32_t m, int32_t largest, float* cat_values,
+                                      int32_t* cat_partner, float* an_values, int32_t* an_partner, void* workspace,
+                                      size_t workspace_bytes, int32_t C, int32_t A, impnn_stream_t stream) {
+  const GridPartnersCall c{1, 1, u_cat, u_an, nullptr, image, where, m, largest, cat_values, cat_partner, an_values,
+                           an_partner, workspace, C, A, 0, 0, 0, 0, as_stream(stream)};
+  return grid_partners_checked(__func__, c, true,
+                               u_cat && u_an && image && cat_values && cat_partner && an_values && an_partner && workspace,
+                               image_floats, workspace_bytes);
 }
 
 // ---- pair masks (include/impnn.h; grid_mask.hip).  One place applies the family's rules in their fixed order: shape

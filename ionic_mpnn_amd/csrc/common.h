@@ -329,6 +329,27 @@ struct GridMaskCall {
 int64_t grid_mask_row_words(int A);
 int launch_grid_mask(const GridMaskCall& c);
 
+// ---- each ion's best partners over a cation x anion grid (grid_partners.hip; include/impnn.h,
+// impnn_head_grid_partners / impnn_transfer_head_grid_partners).  The limits of one launch (ops.py mirrors them): m, at
+// most kSelectMaxT temperatures, C * A < 2^32.
+constexpr int kPartnersMaxM = 8;  // partners kept per ion: a tile column's running best lives in registers
+// One partner-selecting launch: family and operands as GridTopkCall; `where` may be null.  api.hip checks it.
+struct GridPartnersCall {
+  int family, kind;
+  const float *mix_cat, *mix_an, *T, *w;
+  const uint32_t* where;  // (C, ceil(A / 32)) words, or null: every pair competes
+  int m, largest;
+  float* cat_values;     // [max(nT,1)][C][m]
+  int32_t* cat_partner;  // anion indices
+  float* an_values;      // [max(nT,1)][A][m]
+  int32_t* an_partner;   // cation indices
+  void* workspace;
+  int C, A, nT, D, F, Mx;
+  hipStream_t stream;
+};
+size_t grid_partners_workspace_bytes(int family, int C, int A, int nT, int m);
+int launch_grid_partners(const GridPartnersCall& c);
+
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)

@@ -1,7 +1,8 @@
 // Device code the grid kernels share: the tile bodies of head_grid.hip and transfer_grid.hip, which the materialising
 // kernels (impnn_head_grid, impnn_transfer_head_grid), the selecting kernels (grid_select.hip: impnn_head_grid_topk,
 // impnn_transfer_head_grid_topk and their _where forms) and the mask-writing kernels (grid_mask.hip:
-// impnn_head_grid_mask, impnn_transfer_head_grid_mask) all run, and the keys and the running top-k of the selection.
+// impnn_head_grid_mask, impnn_transfer_head_grid_mask) and the partner-selecting kernels (grid_partners.hip:
+// impnn_head_grid_partners, impnn_transfer_head_grid_partners) all run, and the keys and the running top-k of the selection.
 // One definition of a tile's arithmetic, so a selected or tested value has the bits the materialised grid holds for
 // that pair.
 #pragma once
@@ -182,23 +183,46 @@ struct GridMask {
   int W;
 };
 
+// What a partner-selecting launch adds (grid_partners.hip): where the materialising form stores a tile, this one selects
+// from the tile's values in LDS the m first entries of every tile row (a cation's anions) and of every tile column (an
+// anion's cations) under the selection's order, and writes them, ascending, to rows [nT][tiles_a][C][m] and cols
+// [nT][tiles_c][A][m] (kSelectNone where a row or column has fewer).  One tile per workgroup and one writing workgroup
+// per slot: no pre-zeroing, no atomics.
+struct GridPartners {
+  unsigned long long *rows, *cols;
+  int m, largest;
+};
+// ... over a masked grid: only pairs whose bit is set compete.  The tile's words sit in LDS behind the tile's regions
+// ([kWhereTileWords]); a tile without a set bit is passed over before a row is loaded, its slots written kSelectNone.
+struct GridPartnersWhere : GridPartners {
+  const uint32_t* where;  // [C][W]
+  int W;
+};
+
 // which form of a grid kernel its trailing pack makes
-template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false; };
-template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false; };
-template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false; };
-template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true; };
+template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false, partners = false; };
+template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false, partners = false; };
+template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false, partners = false; };
+template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true, partners = false; };
+template <> struct GridForm<GridPartners> { static constexpr bool select = false, where = false, mask = false, partners = true; };
+template <> struct GridForm<GridPartnersWhere> { static constexpr bool select = false, where = true, mask = false, partners = true; };
 
 __device__ __forceinline__ bool select_next_tile(unsigned*, const GridMask&) { return false; }
+__device__ __forceinline__ bool select_next_tile(unsigned*, const GridPartners&) { return false; }
 
+// the tile's mask words in LDS; `lists` is the LDS behind the tile's regions
 __device__ __forceinline__ uint32_t* where_tile_words(const GridSelectWhere& g, float* lists, int nT) {
   return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lists) + select_lds_bytes(nT, g.cap));
+}
+__device__ __forceinline__ uint32_t* where_tile_words(const GridPartnersWhere&, float* lists, int) {
+  return reinterpret_cast<uint32_t*>(lists);
 }
 
 // Loads the words of the tile's rows c0 .. c0 + nc, `wpr` words per row from anion word w0, into LDS (word r * wpr + w;
 // 0 where the grid has no such word) and returns whether any bit is set.  Block-uniform: every thread of the workgroup
 // calls it, and it is a barrier (the last tile's readers of these words are behind select_tile's).
-__device__ __forceinline__ bool where_tile_any(const GridSelectWhere& g, float* lists, int nT, int c0, int nc, int w0,
-                                               int wpr) {
+template <class Where>
+__device__ __forceinline__ bool where_tile_any(const Where& g, float* lists, int nT, int c0, int nc, int w0, int wpr) {
   const int tid = threadIdx.x;
   uint32_t word = 0;
   if (tid < kWhereTileWords) {
@@ -210,7 +234,8 @@ __device__ __forceinline__ bool where_tile_any(const GridSelectWhere& g, float* 
 }
 
 // the bit of the tile's pair (row r, anion a of the tile), after where_tile_any
-__device__ __forceinline__ bool where_bit(const GridSelectWhere& g, float* lists, int nT, int r, int a, int wpr) {
+template <class Where>
+__device__ __forceinline__ bool where_bit(const Where& g, float* lists, int nT, int r, int a, int wpr) {
   return (where_tile_words(g, lists, nT)[r * wpr + (a >> 5)] >> (a & 31)) & 1u;
 }
 
@@ -240,7 +265,86 @@ __device__ __forceinline__ void mask_head_tile(const GridMask& g, int C, int c0,
     }
 }
 
-// ================================================================ the head grid (head_grid.hip; grid_select.hip)
+// ================================================================ best partners (grid_partners.hip)
+// The entry of a tile's pair, or kSelectNone for a lane that is no pair of the grid or whose mask bit is clear.
+__device__ __forceinline__ unsigned long long partners_entry(const GridPartners& g, bool live, float v, uint32_t pair) {
+  return live ? ((unsigned long long)select_key(v, g.largest != 0) << 32) | pair : kSelectNone;
+}
+
+// x of the lane a DPP control names (a permutation inside a row of 16 lanes; every lane of the wave is active)
+template <int CTRL>
+__device__ __forceinline__ unsigned long long partners_dpp(unsigned long long x) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, CTRL, 0xF, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), CTRL, 0xF, 0xF, false);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long partners_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+// The unsigned 64-bit minimum over a row of WIDTH = 64 or 32 lanes, in every lane of the row: four DPP steps inside
+// the 16-lane rows (lane ^ 1, lane ^ 2, the mirrors of 8 and 16), then lane ^ 16 (and lane ^ 32) by shuffle.
+template <int WIDTH>
+__device__ __forceinline__ unsigned long long partners_row_min(unsigned long long x) {
+  x = partners_min(x, partners_dpp<0xB1>(x));   // quad_perm [1,0,3,2]
+  x = partners_min(x, partners_dpp<0x4E>(x));   // quad_perm [2,3,0,1]
+  x = partners_min(x, partners_dpp<0x141>(x));  // row_half_mirror
+  x = partners_min(x, partners_dpp<0x140>(x));  // row_mirror
+  x = partners_min(x, __shfl_xor(x, 16));
+  if (WIDTH == 64) x = partners_min(x, __shfl_xor(x, 32));
+  return x;
+}
+
+// A tile row, one entry per lane of a row of WIDTH lanes: m rounds of the minimum, the winner retires after each
+// (entries are unique), lane i of the row keeps round i's and the first m lanes write dst[0 .. m) (null: the grid has
+// no such row).  Wave-uniform control flow.
+template <int WIDTH>
+__device__ __forceinline__ void partners_row(const GridPartners& g, unsigned long long entry, unsigned long long* dst) {
+  const int l = threadIdx.x & (WIDTH - 1);
+  unsigned long long mine = kSelectNone;
+  for (int i = 0; i < g.m; ++i) {
+    const unsigned long long mn = partners_row_min<WIDTH>(entry);
+    if (l == i) mine = mn;
+    if (entry == mn) entry = kSelectNone;
+  }
+  if (dst && l < g.m) dst[l] = mine;
+}
+
+// A tile column, one thread: the kPartnersMaxM smallest entries offered so far, ascending, in registers (every index
+// is a constant after unrolling).
+struct PartnersBest {
+  unsigned long long e[kPartnersMaxM];
+  __device__ __forceinline__ PartnersBest() {
+#pragma unroll
+    for (int i = 0; i < kPartnersMaxM; ++i) e[i] = kSelectNone;
+  }
+  __device__ __forceinline__ void offer(unsigned long long cand) {
+#pragma unroll
+    for (int i = 0; i < kPartnersMaxM; ++i) {
+      const unsigned long long b = e[i];
+      const bool first = cand < b;
+      e[i] = first ? cand : b;
+      cand = first ? b : cand;
+    }
+  }
+  __device__ __forceinline__ void store(unsigned long long* dst, int m) const {
+#pragma unroll
+    for (int i = 0; i < kPartnersMaxM; ++i)
+      if (i < m) dst[i] = e[i];
+  }
+};
+
+// The slots of a tile the mask lets the workgroup pass over: rows c0 .. c0 + nc of anion tile ta and columns a0 .. a0 + na
+// of cation tile tc, every plane, all kSelectNone (each run of slots is contiguous).
+__device__ __forceinline__ void partners_skip_tile(const GridPartners& g, int C, int A, int c0, int a0, int nc, int na,
+                                                   int tiles_a, int ta, int tiles_c, int tc, int planes) {
+  for (int t = 0; t < planes; ++t) {
+    unsigned long long* rows = g.rows + (((size_t)t * tiles_a + ta) * C + c0) * g.m;
+    unsigned long long* cols = g.cols + (((size_t)t * tiles_c + tc) * A + a0) * g.m;
+    for (int i = threadIdx.x; i < nc * g.m; i += blockDim.x) rows[i] = kSelectNone;
+    for (int i = threadIdx.x; i < na * g.m; i += blockDim.x) cols[i] = kSelectNone;
+  }
+}
+
+// ================================================================ the head grid (head_grid.hip; grid_select.hip; grid_mask.hip; grid_partners.hip)
 // One workgroup owns kTileC cations x kTileA anions; lane = anion, a wave walks the tile's cations.
 constexpr int kTileC = 16, kTileA = 64, kTilePairs = kTileC * kTileA;
 
@@ -258,6 +362,32 @@ __host__ __device__ inline size_t grid_lds_floats(int kind, int nT, int F, int M
   return rows + (size_t)F * align4(Mx) + align4(F) + align4((size_t)F + 1) + kTilePairs;
 }
 
+
+// The head grid's tile as partners: value(e, t) is pair e = r * kTileA + a of the tile at plane t, live(r, a) its mask
+// bit.  A wave's 64 lanes are the 64 anions of one tile row; then one thread per (plane, tile column) walks the
+// column's rows in LDS.
+template <class Fn, class Live>
+__device__ __forceinline__ void partners_head_tile(const GridPartners& g, int C, int A, int c0, int a0, int nc, int na,
+                                                   int tiles_a, int planes, Fn value, Live live) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ta = a0 / kTileA, tc = c0 / kTileC, tiles_c = (C + kTileC - 1) / kTileC;
+  for (int t = 0; t < planes; ++t)
+    for (int q = 0; q < kTilePairs / 256; ++q) {
+      const int e = q * 256 + tid, r = e >> 6;
+      const bool ok = r < nc && lane < na && live(r, lane);
+      const unsigned long long entry =
+          partners_entry(g, ok, value(e, t), (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + lane));
+      partners_row<kTileA>(g, entry, r < nc ? g.rows + (((size_t)t * tiles_a + ta) * C + c0 + r) * g.m : nullptr);
+    }
+  for (int item = tid; item < planes * kTileA; item += 256) {
+    const int t = item >> 6, a = item & 63;
+    if (a >= na) continue;
+    PartnersBest best;
+    for (int r = 0; r < nc; ++r)
+      best.offer(partners_entry(g, live(r, a), value(r * kTileA + a, t), (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a)));
+    best.store(g.cols + (((size_t)t * tiles_c + tc) * A + a0 + a) * g.m, g.m);
+  }
+}
 
 // Writes `rows` row spans of `span` floats each (row r starts at out + first + r * pitch) with 16-byte stores on
 // every naturally aligned quad that lies inside the span and 4-byte stores on the ragged ends.  Element e of a span
@@ -316,8 +446,12 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
   const int c0 = (tile / tiles_a) * kTileC, a0 = (tile % tiles_a) * kTileA;
   const int nc = min(kTileC, C - c0), na = min(kTileA, A - a0);
   if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
-    if (!where_tile_any(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1, c0, nc, a0 >> 5, kTileA / 32))
+    if (!where_tile_any(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1, c0, nc, a0 >> 5, kTileA / 32)) {
+      if constexpr (Form::partners)  // (its slots have no other writer)
+        partners_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTileA, (C + kTileC - 1) / kTileC, c0 / kTileC,
+                           KIND == 0 ? nT : 1);
       continue;
+    }
   }
 
   // the tile's mixing rows: contiguous in global memory, padded rows in LDS (the pads are never used)
@@ -375,6 +509,13 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       mask_head_tile(sel..., C, c0, a0, nc, na, nT, [&](int e, int t) {
         return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]);
       });
+    } else if constexpr (Form::partners) {
+      partners_head_tile(sel..., C, A, c0, a0, nc, na, tiles_a, nT,
+                         [&](int e, int t) { return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]); },
+                         [&](int r, int a) {
+                           if constexpr (Form::where) return where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
+                           return true;
+                         });
     } else {
     store_rows(out, ((int64_t)c0 * A + a0) * nT, (int64_t)A * nT, nc, na * nT, nT, [&](int r, int a, int t) {
       return head_vft_eval(VftParams{resA[r * kTileA + a], resB[r * kTileA + a], resC[r * kTileA + a]}, t100[t]);
@@ -437,6 +578,11 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       });
     } else if constexpr (Form::mask) {
       mask_head_tile(sel..., C, c0, a0, nc, na, 1, [&](int e, int) { return res[e]; });
+    } else if constexpr (Form::partners) {
+      partners_head_tile(sel..., C, A, c0, a0, nc, na, tiles_a, 1, [&](int e, int) { return res[e]; }, [&](int r, int a) {
+        if constexpr (Form::where) return where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
+        return true;
+      });
     } else {
     store_rows(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, 1, [&](int r, int a, int) { return res[r * kTileA + a]; });
     }
@@ -471,6 +617,24 @@ constexpr int kTgTileC = 8, kTgTileA = 32;
 // lane half (a broadcast), so they stay unpadded.
 constexpr int kTgAnStride = kH1 + 4;
 constexpr int kTgLdsFloats = kTgTileA * kTgAnStride + kTgTileC * kH1 + 2 * kH1 + kTgTileC * kTgTileA;  // 43.5 KiB
+
+// The transfer grid's tile as partners: a 32-lane half of a wave is one tile row of `res`; then one thread per tile
+// column walks its rows.
+template <class Live>
+__device__ __forceinline__ void partners_transfer_tile(const GridPartners& g, const float* res, int C, int A, int c0,
+                                                       int a0, int nc, int na, int tiles_a, Live live) {
+  const int tid = threadIdx.x, r = tid >> 5, p = tid & 31;
+  const int ta = a0 / kTgTileA, tc = c0 / kTgTileC;
+  const bool ok = r < nc && p < na && live(r, p);
+  const unsigned long long entry = partners_entry(g, ok, res[tid], (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + p));
+  partners_row<kTgTileA>(g, entry, r < nc ? g.rows + ((size_t)ta * C + c0 + r) * g.m : nullptr);
+  if (tid < na) {
+    PartnersBest best;
+    for (int rr = 0; rr < nc; ++rr)
+      best.offer(partners_entry(g, live(rr, tid), res[rr * kTgTileA + tid], (uint32_t)(c0 + rr) * (uint32_t)A + (uint32_t)(a0 + tid)));
+    best.store(g.cols + ((size_t)tc * A + a0 + tid) * g.m, g.m);
+  }
+}
 
 __device__ __forceinline__ f32x16_t mfma32(float a, float b, f32x16_t c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
@@ -552,7 +716,11 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
   const int c0 = (tile / tiles_a) * kTgTileC, a0 = (tile % tiles_a) * kTgTileA;
   const int nc = min(kTgTileC, C - c0), na = min(kTgTileA, A - a0);
   if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
-    if (!where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) continue;
+    if (!where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) {
+      if constexpr (Form::partners)  // (its slots have no other writer)
+        partners_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTgTileA, (C + kTgTileC - 1) / kTgTileC, c0 / kTgTileC, 1);
+      continue;
+    }
   }
 
   // the tile's u rows; the rows of a ragged tile's padding pairs are zero (computed, not stored)
@@ -665,6 +833,11 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
     const float v = res[tid];
     uint32_t* word = mask_word(sel..., c0 + r, a0 >> 5);
     mask_store_ballot(r < nc && p < na && mask_passes(sel..., v), r < nc ? word : nullptr, r < nc ? word : nullptr);
+  } else if constexpr (Form::partners) {
+    partners_transfer_tile(sel..., res, C, A, c0, a0, nc, na, tiles_a, [&](int r, int a) {
+      if constexpr (Form::where) return where_bit(sel..., sm + kTgLdsFloats, 1, r, a, kTgTileA / 32);
+      return true;
+    });
   } else {
   store_spans(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, res, kTgTileA);
   }

@@ -1209,6 +1209,45 @@ class MPNNModel:
                                                                  self.mixing_size, lo, hi)
         return mask
 
+    def _screen_request(self, what, cations, anions, temperatures, where, max_pairs_per_launch):
+        """The argument rules the selecting screens share (``screen_top_k``, ``screen_best_partners``) -> the
+        temperatures as a float32 host tensor (nT), or None for a model without them."""
+        if self.kind == "viscosity" and temperatures is None:
+            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
+        if cations is None or anions is None:
+            raise ValueError(f"{what} needs both cations and anions")
+        if where is not None:
+            if not isinstance(where, data.PairMask):
+                raise TypeError(f"where must be a data.PairMask, got {type(where).__name__}")
+            if len(where.shape) != 2:
+                raise ValueError("where must be a 2-D mask over (cation, anion): take temperature(t) of a viscosity mask "
+                                 "and call per temperature")
+            given = (len(cations["atom"]), len(anions["atom"]))
+            if where.shape != given:
+                raise ValueError(f"where has shape {where.shape}, the screen is {given[0]} cations x {given[1]} anions")
+        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
+            raise ValueError("max_pairs_per_launch must be >= 1")
+        if self.kind != "viscosity":
+            return None
+        T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
+        T = T.to(torch.float32).reshape(-1)
+        if T.numel() == 0:
+            raise ValueError("temperatures must hold at least one value")
+        return T
+
+    def _ion_halves(self, pc, pa, mfma):
+        """The per-ion halves of the covered grid kernels -> (cation rows, anion rows, the head's weights as those
+        kernels take them): ``impnn_transfer_ion_half`` rows and the prepared image on the matrix-core path, else
+        ``impnn_head_ion_mix`` rows and the packed head."""
+        if mfma:
+            tensors, image = self._head_tensors(), self._transfer_image()
+            return (ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size),
+                    ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size), image)
+        w = self._packed_head()
+        return (ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size),
+                ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size), w)
+
     def screen_top_k(self, cations, anions, temperatures=None, k=100, largest=False, max_pairs_per_launch=None,
                      batch_size=4096, where=None):
         """The k pairs of a screen with the smallest (``largest``: largest) prediction, selected on the GPU: what
@@ -1229,32 +1268,11 @@ class MPNNModel:
         the mask (impnn_head_grid_topk_where, impnn_transfer_head_grid_topk_where) and pass over tiles without a set
         bit; it is tiled with the cation axis and honoured by every fallback too.  See ``screen_mask`` for the
         intended use."""
-        if self.kind == "viscosity" and temperatures is None:
-            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
-        if cations is None or anions is None:
-            raise ValueError("screen_top_k needs both cations and anions")
-        if where is not None:
-            if not isinstance(where, data.PairMask):
-                raise TypeError(f"where must be a data.PairMask, got {type(where).__name__}")
-            if len(where.shape) != 2:
-                raise ValueError("where must be a 2-D mask over (cation, anion): take temperature(t) of a viscosity mask "
-                                 "and call per temperature")
-            given = (len(cations["atom"]), len(anions["atom"]))
-            if where.shape != given:
-                raise ValueError(f"where has shape {where.shape}, the screen is {given[0]} cations x {given[1]} anions")
-        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
-            raise ValueError("max_pairs_per_launch must be >= 1")
+        T = self._screen_request("screen_top_k", cations, anions, temperatures, where, max_pairs_per_launch)
         k = int(k)
         if k < 1:
             raise ValueError("k must be >= 1")
         visc = self.kind == "viscosity"
-        T = None
-        if visc:
-            T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
-                np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
-            T = T.to(torch.float32).reshape(-1)
-            if T.numel() == 0:
-                raise ValueError("temperatures must hold at least one value")
         pc, pa = self.encode_ions(cations, anions, batch_size)
         C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
         n_rows = nT if visc else 1
@@ -1282,14 +1300,9 @@ class MPNNModel:
             with torch.no_grad():
                 if visc:
                     T = T.to(self.device)
-                if mfma:
-                    tensors, image = self._head_tensors(), self._transfer_image()
-                    mc = ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size)
-                    ma = ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size)
-                elif covered:
-                    w = self._packed_head()
-                    mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
-                    ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
+                if covered:
+                    mc, ma, w = self._ion_halves(pc, pa, mfma)
+                    image = w
                 for lo in range(0, C, step):
                     hi = min(C, lo + step)
                     for t0 in range(0, n_rows, t_step):
@@ -1330,6 +1343,95 @@ class MPNNModel:
         if not visc:
             values, cation, anion = values[0], cation[0], anion[0]
         return data.TopK(values, cation, anion)
+
+    def _grid_tile(self, pc, pa, T, halves, mfma):
+        """One host tile of the materialised grid, on the device: rows ``pc`` x all anions (x ``T``); ``halves`` the
+        ``_ion_halves`` of the same rows, or None where the head kernels do not cover the model."""
+        if halves is None:
+            return self._grid_gathered(pc, pa, T)
+        mc, ma, w = halves
+        if mfma:
+            return ops.transfer_head_grid(mc, ma, w)
+        return ops.head_grid(self.kind, mc, ma, T, w, self.fp_size, self.mixing_size)
+
+    def screen_best_partners(self, cations, anions, temperatures=None, m=1, largest=False, where=None,
+                             max_pairs_per_launch=None, batch_size=4096):
+        """For every cation of a screen its ``m`` best anions, and for every anion its ``m`` best cations, selected on
+        the GPU: what ``data.grid_best_partners(self.predict_grid(...), m, largest, where)`` returns, without the grid.
+        ``encode_ions``, the per-ion halves, the argument rules and the host tiling are ``screen_top_k``'s; the
+        partner-selecting kernels (impnn_head_grid_partners, impnn_transfer_head_grid_partners) evaluate every pair
+        with the grid kernels' arithmetic and answer both axes from one launch.  -> ``data.BestPartners(by_cation,
+        by_anion)`` of ``data.Partners(values, partner)``, numpy float32 / int64 (positions in the lists given):
+        (nT,C,m) and (nT,A,m) for viscosity - a plane per temperature - and (C,m), (A,m) otherwise.  An ion's partners
+        are in order: by value, ties by the partner's index, NaN last; slots past the number of its competing partners
+        hold NaN / -1.
+        The cation axis is tiled on the host (``max_pairs_per_launch`` overrides the default, which bounds a launch's
+        workspace): per-cation results are concatenated, per-anion results merged under the same order; temperatures
+        are split at ops.SELECT_MAX_T per launch.  Widths the head kernels do not cover, the transfer model with
+        ``grid_head_mode = "gathered"`` and m above ops.PARTNERS_MAX_M walk ``predict_grid``'s tiles instead and apply
+        ``data.grid_best_partners`` per tile.  The result is the same.
+        ``where``: a 2-D ``data.PairMask`` of shape (C,A), as in ``screen_top_k``; only its pairs compete."""
+        T = self._screen_request("screen_best_partners", cations, anions, temperatures, where, max_pairs_per_launch)
+        m = int(m)
+        if m < 1:
+            raise ValueError("m must be >= 1")
+        visc = self.kind == "viscosity"
+        pc, pa = self.encode_ions(cations, anions, batch_size)
+        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
+        n_rows = nT if visc else 1
+        if where is not None and where.words.device != pc.device:
+            where = data.PairMask(where.words.to(pc.device), where.shape)
+        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
+        covered = self._grid_kernels_cover() or mfma
+        select = covered and m <= ops.PARTNERS_MAX_M
+        cat_v, cat_p = np.full((n_rows, C, m), data.QUIET_NAN, np.float32), np.full((n_rows, C, m), -1, np.int64)
+        an_v, an_p = np.full((n_rows, A, m), data.QUIET_NAN, np.float32), np.full((n_rows, A, m), -1, np.int64)
+        if C > 0 and A > 0:
+            t_step = ops.SELECT_MAX_T if select else GRID_MAX_TEMPERATURES
+            if max_pairs_per_launch is None:
+                if select:  # a launch's workspace: m entries per plane for every tile row and tile column
+                    tc, ta = ops.PARTNERS_TILE[1 if mfma else 0]
+                    per_pair = 8 * m * min(n_rows, t_step) * (1.0 / tc + 1.0 / ta)
+                    max_pairs_per_launch = min(SCREEN_MAX_PAIRS, max(1, int(4 * GRID_OUTPUT_BUDGET / per_pair)))
+                else:
+                    max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
+                    if not covered:
+                        max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
+            step = max(1, min(int(max_pairs_per_launch), SCREEN_MAX_PAIRS if select else 1 << 62) // A)
+            with torch.no_grad():
+                if visc:
+                    T = T.to(self.device)
+                halves = self._ion_halves(pc, pa, mfma) if covered else None
+                for lo in range(0, C, step):
+                    hi = min(C, lo + step)
+                    wh = where.rows(lo, hi) if where is not None else None
+                    for t0 in range(0, n_rows, t_step):
+                        t1 = min(n_rows, t0 + t_step)
+                        Tt = T[t0:t1] if visc else None
+                        if select:
+                            mc, ma, w = halves
+                            words = wh.words if wh is not None else None
+                            if mfma:
+                                got = ops.transfer_head_grid_partners(mc[lo:hi], ma, w, m, largest, where=words)
+                            else:
+                                got = ops.head_grid_partners(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size,
+                                                             self.mixing_size, m, largest, where=words)
+                            cv, cp, av, ap = (x.cpu().numpy() for x in got)
+                            cp, ap = cp.astype(np.int64), ap.astype(np.int64)
+                        else:
+                            tile = self._grid_tile(pc[lo:hi], pa, Tt, (halves[0][lo:hi],) + halves[1:] if covered else None,
+                                                   mfma).cpu().numpy()
+                            got = data.grid_best_partners(tile, m, largest, where=wh)
+                            (cv, cp), (av, ap) = ((x.reshape((t1 - t0, -1, m)) for x in side) for side in got)
+                        cat_v[t0:t1, lo:hi], cat_p[t0:t1, lo:hi] = cv, cp
+                        ap = np.where(ap >= 0, ap + lo, -1)      # the tile's cations are lo .. hi of the screen
+                        for r in range(t1 - t0):                 # an anion's best so far against this tile's, same order
+                            an_v[t0 + r], an_p[t0 + r] = data.best_of(np.concatenate([an_v[t0 + r], av[r]], axis=1),
+                                                                      np.concatenate([an_p[t0 + r], ap[r]], axis=1), m, largest)
+        by_cation, by_anion = data.Partners(cat_v, cat_p), data.Partners(an_v, an_p)
+        if not visc:
+            by_cation, by_anion = data.Partners(cat_v[0], cat_p[0]), data.Partners(an_v[0], an_p[0])
+        return data.BestPartners(by_cation, by_anion)
 
     def _grid_gathered(self, pc, pa, T):
         """``self.head`` on the explicit pairs of a tile of cations x all anions (x T) -> (c, A[, nT])."""

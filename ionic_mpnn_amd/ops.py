@@ -944,6 +944,90 @@ def transfer_head_grid_topk(u_cat, u_an, image, k, largest=False, workgroups=0, 
     return values, cation, anion
 
 
+# the limit of one partner-selecting launch: kPartnersMaxM of csrc/common.h (tests/test_partners_host.py holds them equal)
+PARTNERS_MAX_M = 8
+PARTNERS_TILE = {0: (16, 64), 1: (8, 32)}  # (cations, anions) of a kernel tile: head grid, transfer grid
+
+
+def _grid_partners_outputs(lib, family, C_, A_, nT, m, dev):
+    rows = max(nT, 1)
+    need = C.c_size_t(0)
+    check(lib.impnn_grid_partners_workspace_bytes(family, C_, A_, nT, m, C.byref(need)))
+    out = [torch.empty(rows, n, m, dtype=dt, device=dev) for n in (C_, A_) for dt in (torch.float32, torch.int32)]
+    if C_ == 0 or A_ == 0:  # zero work touches nothing: no ion has a partner
+        for o in out:
+            o.fill_(float("nan") if o.dtype == torch.float32 else -1)
+    return out, _workspace(dev, need.value), need.value
+
+
+def head_grid_partners(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, m=1, largest=False,
+                       where=None):
+    """Each ion's m best partners over ``head_grid``'s product without the product (impnn_head_grid_partners): the same
+    arguments -> (cat_values (nT,C,m) float32, cat_partner (nT,C,m) int32 of anion indices, an_values (nT,A,m),
+    an_partner (nT,A,m) of cation indices) on the device, a plane per temperature (one for "melting_point"), ascending
+    under the order of ``data.grid_best_partners``; slots past an ion's competing partners hold NaN / -1.  A value has
+    the bits ``head_grid`` gives for its pair.  m <= PARTNERS_MAX_M, at most SELECT_MAX_T temperatures, C*A < 2^32.
+    ``where``: the (C,W) words of a pair mask (``head_grid_mask``, ``data.PairMask``): only its pairs compete."""
+    require_gpu(mix_cat, mix_an, head_weights)
+    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
+    kd = HEAD_KINDS[kind]
+    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
+        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
+                         f"and {tuple(mix_an.shape)}")
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    lib = _lib.load()
+    per_d = 2 * fp_size
+    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
+    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
+    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+    T, nT = None, 0
+    if kd == 0:
+        if temperatures is None:
+            raise ValueError("the viscosity grid needs temperatures")
+        require_gpu(temperatures)
+        T = f32c(temperatures).reshape(-1)
+        nT = int(T.numel())
+    elif temperatures is not None:
+        raise ValueError("the melting-point grid takes no temperatures")
+    dev = mix_cat.device
+    m = int(m)
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
+    with torch.cuda.device(dev):
+        out, ws, nbytes = _grid_partners_outputs(lib, 0, C_, A_, nT, m, dev)
+        check(lib.impnn_head_grid_partners(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
+                                           ptr(head_weights), ptr(where) if where is not None else None, m,
+                                           int(bool(largest)), *[ptr(o) for o in out], ptr(ws), nbytes, C_, A_, nT, D,
+                                           fp_size, mixing_size, stream_ptr()))
+    return tuple(out)
+
+
+def transfer_head_grid_partners(u_cat, u_an, image, m=1, largest=False, where=None):
+    """Each ion's m best partners over ``transfer_head_grid``'s product without the product
+    (impnn_transfer_head_grid_partners) -> (cat_values (1,C,m), cat_partner, an_values (1,A,m), an_partner) on the
+    device, as ``head_grid_partners``; ``where`` as there."""
+    require_gpu(u_cat, u_an, image)
+    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
+    W = TRANSFER_GRID_WIDTH
+    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
+        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
+    lib = _lib.load()
+    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
+        raise ValueError("the prepared image has the wrong length")
+    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
+    dev = u_cat.device
+    m = int(m)
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
+    with torch.cuda.device(dev):
+        out, ws, nbytes = _grid_partners_outputs(lib, 1, C_, A_, 0, m, dev)
+        check(lib.impnn_transfer_head_grid_partners(ptr(u_cat), ptr(u_an), ptr(image), image.numel(),
+                                                    ptr(where) if where is not None else None, m, int(bool(largest)),
+                                                    *[ptr(o) for o in out], ptr(ws), nbytes, C_, A_, stream_ptr()))
+    return tuple(out)
+
+
 def _mask_bounds(lo, hi):
     lo, hi = C.c_float(lo).value, C.c_float(hi).value  # as the kernels see them: float32
     if lo != lo or hi != hi:

@@ -6,6 +6,7 @@ matrix-core grid, impnn_transfer_head_grid), plus that kernel alone against the 
 python tools/screen_bench.py [--quick] [--only viscosity|transfer]      -> one JSON line per configuration, appended to profiles/screen_bench.jsonl
 python tools/screen_bench.py --select [--quick] [--only ...]            -> the top-k selection instead (see below)
 python tools/screen_bench.py --select --where FRACTION [--quick]        -> the constrained screen instead (see below)
+python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each ion's best partners instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -25,7 +26,14 @@ time, of (a) mp.screen_mask + visc.screen_top_k(where=) against (b) the way to t
 predict_grid calls and data.grid_top_k(where=) on the host; screen_mask and screen_top_k(where=) also on their own.  Then
 the selecting launches alone, 10 calls between two HIP events, five rounds each in turn: plain, an all-ones mask, a
 random mask of density F, and a block-structured mask of the same density (whole tiles of the kernel set or clear), for
-the head grid and the transfer grid; and the mask-writing launch against the materialising one."""
+the head grid and the transfer grid; and the mask-writing launch against the materialising one.
+
+--partners: MPNNModel.screen_best_partners(m = 3) against predict_grid followed by data.grid_best_partners on the host,
+at the configurations of --select: three alternating rounds after a warm-up of each, wall time, median and spread; the
+two ways must return the same bits.  Plus the partner-selecting launches alone (impnn_head_grid_partners /
+impnn_transfer_head_grid_partners with their merge; a sweep above ops.SELECT_MAX_T temperatures takes several) against
+the materialising launch of the same C x A x nT, 10 calls between two HIP events, three rounds each in turn.  With
+--where F both ways run under one random pair mask of density F."""
 import argparse
 import json
 import statistics
@@ -44,9 +52,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="the first configuration only")
 ap.add_argument("--only", choices=("viscosity", "transfer"), help="one family of configurations")
 ap.add_argument("--select", action="store_true", help="time screen_top_k against predict_grid + host selection")
-ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: the constrained screen at this mask density")
+ap.add_argument("--partners", action="store_true", help="time screen_best_partners against predict_grid + host reference")
+ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: the constrained screen at this mask density; "
+                "with --partners: a random mask of this density")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
+other = args.select or args.partners  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -70,7 +81,7 @@ def species(n, seed):
 
 
 lines = []
-for name, D, S, C, A, nT, bs in [] if args.only == "transfer" or args.select else CONFIGS[:1] if args.quick else CONFIGS:
+for name, D, S, C, A, nT, bs in [] if args.only == "transfer" or other else CONFIGS[:1] if args.quick else CONFIGS:
     m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
     m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
     cat, _ = species(C, 1)
@@ -130,7 +141,7 @@ def build_transfer(D, S):
         return MM.build_transfer_model(path, device=dev)
 
 
-for name, D, S, C, A in [] if args.only == "viscosity" or args.select else TRANSFER_CONFIGS[:1] if args.quick else TRANSFER_CONFIGS:
+for name, D, S, C, A in [] if args.only == "viscosity" or other else TRANSFER_CONFIGS[:1] if args.quick else TRANSFER_CONFIGS:
     t = build_transfer(D, S)
     cat, _ = species(C, 1)
     _, an = species(A, 2)
@@ -203,7 +214,71 @@ def spread(xs):
     return {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
 
 
-if args.select and args.where is not None:
+PARTNERS_M = 3
+
+
+def same_partners(a, b):
+    return all(np.array_equal(np.asarray(x).view(np.uint32) if x.dtype == np.float32 else x, np.asarray(y).view(np.uint32)
+                              if y.dtype == np.float32 else y) for sa, sb in zip(a, b) for x, y in zip(sa, sb))
+
+
+if args.partners:
+    todo = [c for c in SELECT_CONFIGS if args.only in (None, c[0])]
+    for kind, name, D, S, C, A, nT in todo[:1] if args.quick else todo:
+        if kind == "viscosity":
+            m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
+            m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
+            T = np.linspace(263.15, 393.15, nT).astype(np.float32)
+        else:
+            m, T = build_transfer(D, S), None
+        cat, _ = species(C, 1)
+        _, an = species(A, 2)
+        where_b = None if args.where is None else np.random.default_rng(5).random((C, A)) < float(args.where)
+        where = None if where_b is None else data.PairMask.from_bool(where_b, device=dev)
+        old_way = lambda: data.grid_best_partners(m.predict_grid(cat, an, T), PARTNERS_M, where=where_b)
+        new_way = lambda: m.screen_best_partners(cat, an, T, m=PARTNERS_M, where=where)
+        _, best_old = wall(old_way)
+        _, best_new = wall(new_way)
+        t_old, t_new = [], []
+        for _ in range(3):
+            t_old.append(wall(old_way)[0])
+            t_new.append(wall(new_way)[0])
+        words = None if where is None else where.words
+        with torch.no_grad():
+            pc, pa = m.encode_ions(cat, an)
+            if kind == "viscosity":
+                w = m._packed_head()
+                mc = ops.head_ion_mix(kind, "cat", pc, w, m.fp_size, m.mixing_size)
+                ma = ops.head_ion_mix(kind, "an", pa, w, m.fp_size, m.mixing_size)
+                Td = torch.from_numpy(T).to(dev)
+                store = lambda: [ops.head_grid(kind, mc, ma, Td, w, m.fp_size, m.mixing_size) for _ in range(10)]
+                select = lambda: [ops.head_grid_partners(kind, mc, ma, Td[t0:t0 + ops.SELECT_MAX_T], w, m.fp_size, m.mixing_size,
+                                                         PARTNERS_M, where=words)
+                                  for _ in range(10) for t0 in range(0, nT, ops.SELECT_MAX_T)]
+            else:
+                tensors, image = m._head_tensors(), m._transfer_image()
+                uc = ops.transfer_ion_half("cat", pc, tensors, m.fp_size, m.mixing_size)
+                ua = ops.transfer_ion_half("an", pa, tensors, m.fp_size, m.mixing_size)
+                store = lambda: [ops.transfer_head_grid(uc, ua, image) for _ in range(10)]
+                select = lambda: [ops.transfer_head_grid_partners(uc, ua, image, PARTNERS_M, where=words) for _ in range(10)]
+            timed(store), timed(select)
+            k_store, k_select = [], []
+            for _ in range(3):
+                k_store.append(timed(store)[0] / 10 * 1e3)
+                k_select.append(timed(select)[0] / 10 * 1e3)
+        line = {"config": "partners " + name + ("" if args.where is None else " F=%g" % args.where), "kind": kind, "atom_dim": D,
+                "steps": S, "C": C, "A": A, "nT": nT, "m": PARTNERS_M, "values": C * A * max(nT, 1),
+                "mask_density": None if where is None else round(where.count() / (C * A), 4),
+                "predict_grid_plus_host_best_partners_ms": spread(t_old), "screen_best_partners_ms": spread(t_new),
+                "speedup": round(statistics.median(t_old) / statistics.median(t_new), 2),
+                "materialising_launch_us": spread(k_store), "partner_launches_us": spread(k_select),
+                "partners_over_materialising": round(statistics.median(k_select) / statistics.median(k_store), 3),
+                "same_answer": same_partners(best_old, best_new)}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del m
+        torch.cuda.empty_cache()
+elif args.select and args.where is not None:
     F = float(args.where)
     for name, D, S, C, A in WHERE_CONFIGS[:1] if args.quick else WHERE_CONFIGS:
         m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
