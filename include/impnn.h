@@ -612,6 +612,44 @@ int impnn_transfer_head_grid_partners(const float* u_cat, const float* u_an, con
                                       int32_t* cat_partner, float* an_values, int32_t* an_partner, void* workspace,
                                       size_t workspace_bytes, int32_t C, int32_t A, impnn_stream_t stream);
 
+/* ---- the rank cut and the best-k pair mask, by radix select on the GPU: for every temperature plane the k-th entry
+ *      (1-based) of the order of impnn_head_grid_topk - (key << 32) | (i * A + j), compared as an unsigned 64-bit
+ *      integer: by value, ties by cation then anion index, NaN last, `largest` complementing the key - and, optionally,
+ *      the pairs at or before it as a packed pair mask.  k is not limited by on-chip memory: the k-th entry is found one
+ *      8-bit digit a pass (impnn_grid_rank_digit_bits), most significant first, four passes over the key and one per
+ *      byte that C * A - 1 needs (impnn_grid_rank_passes: 4 .. 8).  A pass runs the tile arithmetic of impnn_head_grid /
+ *      impnn_transfer_head_grid (an entry has the bits those entries write for its pair) in persistent workgroups,
+ *      counts the entries that share the digits found so far by their next digit in LDS, and a one-workgroup-per-plane
+ *      step launch takes the digit; the state stays in the workspace, and a call enqueues every launch without a host
+ *      round trip.  No C x A buffer, no global atomics, no float atomics, no pre-zeroed memory; the result is exact and
+ *      does not depend on `workgroups` or the schedule.
+ *      where: NULL, or a (C,W) pair mask, 4-byte aligned: only pairs whose bit is set compete, the one mask for every
+ *      plane; a workgroup passes over a tile none of whose bits is set before it loads a row.
+ *      Outputs, [max(nT,1)] each: values float, cation / anion int32 of the k-th entry (a NaN value comes back as the
+ *      quiet NaN 0x7FC00000), count int64 (8-byte aligned) the number of competing pairs.  k > count: NaN / -1 / -1.
+ *      mask_words: NULL, or (C,W) words, kind 0 (nT,C,W), 4-byte aligned, every one written: bit (i, j[, t]) is set
+ *      for exactly the first min(k, count) competing pairs of plane t (a run of equal values that straddles k is cut by
+ *      index), pad bits 0.
+ *      Limits of one call: C * A <= 2^32 - 2; kind 0: 1 <= nT <= 4; the widths of impnn_head_grid.  workgroups: 0 for the
+ *      default (one per compute unit), capped by the tile count.
+ *      workspace: impnn_grid_rank_workspace_bytes bytes for the same (family, C, A, nT, workgroups), 8-byte aligned,
+ *      family 0 = impnn_head_grid_rank, 1 = impnn_transfer_head_grid_rank; it carries nothing from call to call.
+ *      Checks in order, one text each: kind; shape; zero work (C == 0 or A == 0: IMPNN_OK, nothing touched); null
+ *      pointers, then alignment and the image size; k < 1; the pair count; nT; the workspace size (IMPNN_E_WORKSPACE);
+ *      the widths (IMPNN_E_UNSUPPORTED, as the limits).  No allocation, no synchronisation, no state. */
+int32_t impnn_grid_rank_digit_bits(void);
+int32_t impnn_grid_rank_passes(int32_t C, int32_t A);
+int impnn_grid_rank_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t workgroups, size_t* need);
+int impnn_head_grid_rank(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                         const float* head_weights, int64_t k, int32_t largest, const uint32_t* where, float* values,
+                         int32_t* cation, int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
+                         size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F, int32_t Mx,
+                         int32_t workgroups, impnn_stream_t stream);
+int impnn_transfer_head_grid_rank(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                  int64_t k, int32_t largest, const uint32_t* where, float* values, int32_t* cation,
+                                  int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
+                                  size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

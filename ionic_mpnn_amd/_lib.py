@@ -85,6 +85,11 @@ SIGNATURES = {
     "impnn_grid_partners_workspace_bytes": (C.c_int, [i32] * 5 + [C.POINTER(sz)]),
     "impnn_head_grid_partners": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz] + [i32] * 6 + [vp]),
     "impnn_transfer_head_grid_partners": (C.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp]),
+    "impnn_grid_rank_digit_bits": (i32, []),
+    "impnn_grid_rank_passes": (i32, [i32, i32]),
+    "impnn_grid_rank_workspace_bytes": (C.c_int, [i32] * 5 + [C.POINTER(sz)]),
+    "impnn_head_grid_rank": (C.c_int, [i32, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, sz] + [i32] * 7 + [vp]),
+    "impnn_transfer_head_grid_rank": (C.c_int, [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, vp]),
     "impnn_grid_mask_row_words": (i64, [i32]),
     "impnn_head_grid_mask": (C.c_int, [i32, vp, vp, vp, vp, f32, f32, vp] + [i32] * 6 + [vp]),
     "impnn_transfer_head_grid_mask": (C.c_int, [vp, vp, vp, i64, f32, f32, vp, i32, i32, vp]),

@@ -921,6 +921,85 @@ int impnn_transfer_head_grid_partners(const float* u_cat, const float* u_an, con
                                image_floats, workspace_bytes);
 }
 
+// ---- the rank cut and the best-k pair mask (include/impnn.h; grid_rank.hip).  One place applies the family's rules in
+// their fixed order, one error text each: kind, shape, zero work, null pointers (then alignment and the image size),
+// k < 1, the pair-count limit, the nT limit, the workspace size, the widths.  Nothing is launched before the last.
+namespace {
+int grid_rank_limits(const char* entry, int C, int A, int nT) {
+  if ((int64_t)C * A > kRankMaxPairs)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (<= 2^32 - 2 per call)", entry, (long long)((int64_t)C * A));
+  if (nT > kSelectMaxT)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
+  return IMPNN_OK;
+}
+
+int grid_rank_checked(const char* entry, const GridRankCall& c, bool widths_ok, bool pointers_ok, int64_t image_floats,
+                      size_t workspace_bytes) {
+  const GridRequest r{entry, c.family, c.kind, c.mix_cat, c.mix_an, c.T, c.w, c.workspace, c.where, false,
+                      c.C, c.A, c.nT, c.D, c.F, c.Mx};
+  if (int rc = grid_request_kind(r, widths_ok, image_floats)) return rc;
+  if (c.C < 0 || c.A < 0 || c.nT < 0 || c.workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (c.C == 0 || c.A == 0) return IMPNN_OK;
+  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
+  if ((reinterpret_cast<uintptr_t>(c.workspace) & 7u) != 0 || (reinterpret_cast<uintptr_t>(c.count) & 7u) != 0)
+    return fail(IMPNN_E_BADARG, "%s: the workspace and the counts must be 8-byte aligned", entry);
+  if (((reinterpret_cast<uintptr_t>(c.where) | reinterpret_cast<uintptr_t>(c.mask_words)) & 3u) != 0)
+    return fail(IMPNN_E_BADARG, "%s: the masks must be 4-byte aligned", entry);
+  if (c.family == 1) {
+    if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
+      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
+    if (image_floats < transfer_grid_image_floats())
+      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
+                  (long long)transfer_grid_image_floats());
+  }
+  if (c.k < 1) return fail(IMPNN_E_BADARG, "%s: k=%lld must be at least 1", entry, (long long)c.k);
+  if (int rc = grid_rank_limits(entry, c.C, c.A, c.nT)) return rc;
+  const size_t need = grid_rank_workspace_bytes(c.family, c.C, c.A, c.nT, c.workgroups);
+  if (workspace_bytes < need)
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", entry, workspace_bytes, need);
+  if (c.family == 0)
+    if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
+  return launch_grid_rank(c);
+}
+}  // namespace
+
+int32_t impnn_grid_rank_digit_bits(void) { return kRankDigitBits; }
+
+int32_t impnn_grid_rank_passes(int32_t C, int32_t A) { return C < 0 || A < 0 ? 0 : grid_rank_passes((int64_t)C * A); }
+
+int impnn_grid_rank_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t workgroups, size_t* need) {
+  if (family != 0 && family != 1) return fail(IMPNN_E_BADARG, "%s: family must be 0 (head grid) or 1 (transfer grid)", __func__);
+  if (C < 0 || A < 0 || nT < 0 || workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", __func__);
+  REQUIRE(need, "null pointer");
+  if (int rc = grid_rank_limits(__func__, C, A, nT)) return rc;
+  *need = grid_rank_workspace_bytes(family, C, A, nT, workgroups);
+  return IMPNN_OK;
+}
+
+int impnn_head_grid_rank(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                         const float* head_weights, int64_t k, int32_t largest, const uint32_t* where, float* values,
+                         int32_t* cation, int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
+                         size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F, int32_t Mx,
+                         int32_t workgroups, impnn_stream_t stream) {
+  const GridRankCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, k, largest, where, values, cation, anion,
+                       count, mask_words, workspace, C, A, nT, D, F, Mx, workgroups, as_stream(stream)};
+  return grid_rank_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
+                           mix_cat && mix_an && head_weights && values && cation && anion && count && workspace &&
+                               (kind == 1 || temperatures),
+                           0, workspace_bytes);
+}
+
+int impnn_transfer_head_grid_rank(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                  int64_t k, int32_t largest, const uint32_t* where, float* values, int32_t* cation,
+                                  int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
+                                  size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream) {
+  const GridRankCall c{1, 1, u_cat, u_an, nullptr, image, k, largest, where, values, cation, anion, count, mask_words,
+                       workspace, C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
+  return grid_rank_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && count && workspace,
+                           image_floats, workspace_bytes);
+}
+
 // ---- pair masks (include/impnn.h; grid_mask.hip).  One place applies the family's rules in their fixed order: shape
 // (a NaN bound included), zero work, null pointers, alignment and the image size, the limits of one launch.
 namespace {

@@ -350,6 +350,32 @@ struct GridPartnersCall {
 size_t grid_partners_workspace_bytes(int family, int C, int A, int nT, int m);
 int launch_grid_partners(const GridPartnersCall& c);
 
+// ---- the rank cut and the best-k pair mask over a cation x anion grid (grid_rank.hip; include/impnn.h,
+// impnn_head_grid_rank / impnn_transfer_head_grid_rank): a radix select over the selection's 64-bit entries, most
+// significant digit first, the grid evaluated once per digit (ops.py mirrors the digit width: RANK_DIGIT_BITS).
+constexpr int kRankDigitBits = 8;
+constexpr int kRankBins = 1 << kRankDigitBits;
+constexpr int64_t kRankMaxPairs = ((int64_t)1 << 32) - 2;  // the entry format: a pair index stays below 2^32 - 1
+// One call: family and operands as GridTopkCall; `where` and `mask_words` may be null.  api.hip checks it.
+struct GridRankCall {
+  int family, kind;
+  const float *mix_cat, *mix_an, *T, *w;
+  int64_t k;
+  int largest;
+  const uint32_t* where;  // (C, ceil(A / 32)) words, or null: every pair competes
+  float* values;          // [max(nT,1)]
+  int32_t *cation, *anion;
+  int64_t* count;
+  uint32_t* mask_words;   // (C, W), viscosity (nT, C, W), or null: the rank cut alone
+  void* workspace;
+  int C, A, nT, D, F, Mx, workgroups;
+  hipStream_t stream;
+};
+int grid_rank_passes(int64_t pairs);  // 4 key digits + the digits that hold pairs - 1
+int grid_rank_workgroups(int family, int C, int A, int workgroups);  // 0: the default; capped by the tile count
+size_t grid_rank_workspace_bytes(int family, int C, int A, int nT, int workgroups);
+int launch_grid_rank(const GridRankCall& c);
+
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)

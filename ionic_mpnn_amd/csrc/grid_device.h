@@ -2,7 +2,8 @@
 // kernels (impnn_head_grid, impnn_transfer_head_grid), the selecting kernels (grid_select.hip: impnn_head_grid_topk,
 // impnn_transfer_head_grid_topk and their _where forms) and the mask-writing kernels (grid_mask.hip:
 // impnn_head_grid_mask, impnn_transfer_head_grid_mask) and the partner-selecting kernels (grid_partners.hip:
-// impnn_head_grid_partners, impnn_transfer_head_grid_partners) all run, and the keys and the running top-k of the selection.
+// impnn_head_grid_partners, impnn_transfer_head_grid_partners) and the rank-cut kernels (grid_rank.hip:
+// impnn_head_grid_rank, impnn_transfer_head_grid_rank) all run, and the keys and the running top-k of the selection.
 // One definition of a tile's arithmetic, so a selected or tested value has the bits the materialised grid holds for
 // that pair.
 #pragma once
@@ -199,22 +200,64 @@ struct GridPartnersWhere : GridPartners {
   int W;
 };
 
+// What the rank cut adds (grid_rank.hip): the k-th entry of the selection's order by a most-significant-digit radix select
+// over the 64-bit entries, kRankDigitBits bits a pass.  The state of one plane between the launches of a call, in the
+// workspace: the digits found so far (the bits of `prefix` above the current digit), the rank that remains inside the
+// entries that share them, and after the last pass the k-th entry itself, `bound` (kSelectNone, latched by `none`, when
+// fewer than k pairs compete).
+struct RankState {
+  unsigned long long prefix, rank, bound;
+  uint32_t count, none;
+};
+// The counting form.  With it a workgroup is persistent, as with GridSelect, and where the materialising form stores a
+// tile it counts the tile's entries whose bits above `shift + kRankDigitBits` equal the plane's prefix by their digit
+// at `shift`, into an LDS histogram [planes][kRankBins] behind the tile's regions (integer LDS atomics); at the end it
+// writes all of its counters to hist [gridDim.x][planes][kRankBins].  `where` may be null: every pair competes.
+struct GridRank {
+  const RankState* state;  // [planes]; not read by the first pass (shift + kRankDigitBits == 64)
+  uint32_t* hist;
+  const uint32_t* where;   // [C][W], or null
+  int W, shift, largest;
+  unsigned tiles;
+};
+// The mask form: one tile per workgroup, as GridMask; the bit of a pair is in-grid && where bit && entry <= bound of
+// its plane.  A viscosity mask is [nT][C][W].
+struct GridMaskRank {
+  uint32_t* words;
+  const RankState* state;  // [planes]
+  const uint32_t* where;   // [C][W], or null
+  int W, largest;
+};
+
 // which form of a grid kernel its trailing pack makes
-template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false, partners = false; };
-template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false, partners = false; };
-template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false, partners = false; };
-template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true, partners = false; };
-template <> struct GridForm<GridPartners> { static constexpr bool select = false, where = false, mask = false, partners = true; };
-template <> struct GridForm<GridPartnersWhere> { static constexpr bool select = false, where = true, mask = false, partners = true; };
+template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = false; };
+template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false, partners = false, rank_count = false, rank_mask = false; };
+template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false, partners = false, rank_count = false, rank_mask = false; };
+template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true, partners = false, rank_count = false, rank_mask = false; };
+template <> struct GridForm<GridPartners> { static constexpr bool select = false, where = false, mask = false, partners = true, rank_count = false, rank_mask = false; };
+template <> struct GridForm<GridPartnersWhere> { static constexpr bool select = false, where = true, mask = false, partners = true, rank_count = false, rank_mask = false; };
+template <> struct GridForm<GridRank> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = true, rank_mask = false; };
+template <> struct GridForm<GridMaskRank> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = true; };
 
 __device__ __forceinline__ bool select_next_tile(unsigned*, const GridMask&) { return false; }
 __device__ __forceinline__ bool select_next_tile(unsigned*, const GridPartners&) { return false; }
+__device__ __forceinline__ bool select_next_tile(unsigned*, const GridMaskRank&) { return false; }
+__device__ __forceinline__ bool select_next_tile(unsigned* tile, const GridRank& g) {
+  *tile += gridDim.x;
+  return *tile < g.tiles;
+}
 
 // the tile's mask words in LDS; `lists` is the LDS behind the tile's regions
 __device__ __forceinline__ uint32_t* where_tile_words(const GridSelectWhere& g, float* lists, int nT) {
   return reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lists) + select_lds_bytes(nT, g.cap));
 }
 __device__ __forceinline__ uint32_t* where_tile_words(const GridPartnersWhere&, float* lists, int) {
+  return reinterpret_cast<uint32_t*>(lists);
+}
+__device__ __forceinline__ uint32_t* where_tile_words(const GridRank&, float* lists, int nT) {  // behind the histogram
+  return reinterpret_cast<uint32_t*>(lists) + (size_t)nT * kRankBins;
+}
+__device__ __forceinline__ uint32_t* where_tile_words(const GridMaskRank&, float* lists, int) {
   return reinterpret_cast<uint32_t*>(lists);
 }
 
@@ -344,6 +387,69 @@ __device__ __forceinline__ void partners_skip_tile(const GridPartners& g, int C,
   }
 }
 
+// ================================================================ rank cut (grid_rank.hip)
+__host__ __device__ inline size_t rank_lds_bytes(int planes) { return sizeof(uint32_t) * (size_t)planes * kRankBins; }
+
+// whether the launch has a mask (block-uniform: a kernel argument)
+__device__ __forceinline__ bool rank_masked(const GridRank& g) { return g.where != nullptr; }
+__device__ __forceinline__ bool rank_masked(const GridMaskRank& g) { return g.where != nullptr; }
+
+__device__ __forceinline__ unsigned long long rank_entry(float v, int largest, uint32_t pair) {
+  return ((unsigned long long)select_key(v, largest != 0) << 32) | pair;
+}
+
+// (the barriers between a kernel's loads and its first rank_count publish the zeros)
+__device__ __forceinline__ void rank_init(const GridRank&, float* lists, int planes) {
+  uint32_t* hist = reinterpret_cast<uint32_t*>(lists);
+  for (int i = threadIdx.x; i < planes * kRankBins; i += blockDim.x) hist[i] = 0;
+}
+
+// the plane's digits so far; the first pass has none and does not read the state
+__device__ __forceinline__ unsigned long long rank_prefix(const GridRank& g, int t) {
+  return g.shift + kRankDigitBits < 64 ? g.state[t].prefix : 0ull;
+}
+
+// A wave counts one entry per lane (`live` lanes) into hist[kRankBins] of its plane.  Entries of a tile crowd a few
+// bins (the sign and exponent of the first pass; one bin per pass on a grid of equal values), so the wave's leading
+// digit values are peeled first: the first pending lane's digit, a ballot of the lanes that share it, one atomic with
+// their number; at most kRankPeel rounds, then one atomic per lane that is left.  Wave-uniform control flow.
+constexpr int kRankPeel = 2;
+__device__ __forceinline__ void rank_count(const GridRank& g, uint32_t* hist, unsigned long long prefix, bool live,
+                                           unsigned long long entry) {
+  const int hi = g.shift + kRankDigitBits;
+  const bool match = live && (hi >= 64 || (entry >> hi) == (prefix >> hi));
+  const uint32_t digit = (uint32_t)(entry >> g.shift) & (kRankBins - 1);
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(match);
+  for (int round = 0; round < kRankPeel && todo != 0; ++round) {
+    const int leader = __ffsll(todo) - 1;
+    const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)digit, leader);
+    const unsigned long long same = __ballot(match && digit == d);  // (a peeled lane has another digit)
+    if (lane == leader) atomicAdd(hist + d, (uint32_t)__popcll(same));
+    todo &= ~same;
+  }
+  if ((todo >> lane) & 1ull) atomicAdd(hist + digit, 1u);
+}
+
+// all of the workgroup's counters, zeros included: every slot of hist has one writer and needs no zeroing
+__device__ __forceinline__ void rank_finish(const GridRank& g, float* lists, int planes) {
+  __syncthreads();
+  const uint32_t* hist = reinterpret_cast<const uint32_t*>(lists);
+  uint32_t* dst = g.hist + (size_t)blockIdx.x * planes * kRankBins;
+  for (int i = threadIdx.x; i < planes * kRankBins; i += blockDim.x) dst[i] = hist[i];
+}
+
+// The words of a tile the mask lets the workgroup pass over (rows c0 .. c0 + nc, `wpr` words from word w0, every
+// plane): the counting form owes nothing, the mask form is their only writer and writes them 0.
+__device__ __forceinline__ void rank_skip_tile(const GridRank&, int, int, int, int, int, int) {}
+__device__ __forceinline__ void rank_skip_tile(const GridMaskRank& g, int C, int c0, int nc, int w0, int wpr, int planes) {
+  const int nw = min(wpr, g.W - w0);
+  for (int i = threadIdx.x; i < planes * nc * nw; i += blockDim.x) {
+    const int t = i / (nc * nw), r = (i / nw) % nc, w = i % nw;
+    g.words[((int64_t)t * C + c0 + r) * g.W + w0 + w] = 0u;
+  }
+}
+
 // ================================================================ the head grid (head_grid.hip; grid_select.hip; grid_mask.hip; grid_partners.hip)
 // One workgroup owns kTileC cations x kTileA anions; lane = anion, a wave walks the tile's cations.
 constexpr int kTileC = 16, kTileA = 64, kTilePairs = kTileC * kTileA;
@@ -386,6 +492,39 @@ __device__ __forceinline__ void partners_head_tile(const GridPartners& g, int C,
     for (int r = 0; r < nc; ++r)
       best.offer(partners_entry(g, live(r, a), value(r * kTileA + a, t), (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a)));
     best.store(g.cols + (((size_t)t * tiles_c + tc) * A + a0 + a) * g.m, g.m);
+  }
+}
+
+// The head grid's tile counted and as best-k mask words: value(e, t) is pair e = r * kTileA + a of the tile at plane t,
+// live(r, a) its mask bit.  A wave's 64 lanes are the 64 anions of one tile row, i.e. that row's two words.
+template <class Fn, class Live>
+__device__ __forceinline__ void rank_head_tile(const GridRank& g, float* lists, int A, int c0, int a0, int nc, int na,
+                                               int planes, Fn value, Live live) {
+  uint32_t* hist = reinterpret_cast<uint32_t*>(lists);
+  for (int t = 0; t < planes; ++t) {
+    const unsigned long long prefix = rank_prefix(g, t);
+    for (int q = 0; q < kTilePairs / 256; ++q) {
+      const int e = q * 256 + (int)threadIdx.x, r = e >> 6, a = e & 63;
+      const bool ok = r < nc && a < na && live(r, a);
+      rank_count(g, hist + t * kRankBins, prefix, ok,
+                 rank_entry(value(e, t), g.largest, (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a)));
+    }
+  }
+  __syncthreads();  // the tile's regions and mask words are free for the next tile
+}
+
+template <class Fn, class Live>
+__device__ __forceinline__ void rank_mask_head_tile(const GridMaskRank& g, int C, int A, int c0, int a0, int nc, int na,
+                                                    int planes, Fn value, Live live) {
+  for (int t = 0; t < planes; ++t) {
+    const unsigned long long bound = g.state[t].bound;
+    for (int q = 0; q < kTilePairs / 256; ++q) {
+      const int e = q * 256 + (int)threadIdx.x, r = e >> 6, a = e & 63;
+      const bool ok = r < nc && a < na && live(r, a);
+      const unsigned long long entry = rank_entry(value(e, t), g.largest, (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a));
+      uint32_t* row = g.words + ((int64_t)t * C + c0 + r) * g.W + (a0 >> 5);
+      mask_store_ballot(ok && entry <= bound, r < nc ? row : nullptr, r < nc && (a0 >> 5) + 1 < g.W ? row + 1 : nullptr);
+    }
   }
 }
 
@@ -442,6 +581,7 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
   constexpr bool kSelect = Form::select;
   unsigned tile = blockIdx.x;
   if constexpr (kSelect) select_init(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
+  if constexpr (Form::rank_count) rank_init(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
   do {
   const int c0 = (tile / tiles_a) * kTileC, a0 = (tile % tiles_a) * kTileA;
   const int nc = min(kTileC, C - c0), na = min(kTileA, A - a0);
@@ -450,6 +590,13 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       if constexpr (Form::partners)  // (its slots have no other writer)
         partners_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTileA, (C + kTileC - 1) / kTileC, c0 / kTileC,
                            KIND == 0 ? nT : 1);
+      continue;
+    }
+  }
+  if constexpr (Form::rank_count || Form::rank_mask) {  // the rank forms' mask may be null: the same pass, when there is one
+    if (rank_masked(sel...) &&
+        !where_tile_any(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1, c0, nc, a0 >> 5, kTileA / 32)) {
+      rank_skip_tile(sel..., C, c0, nc, a0 >> 5, kTileA / 32, KIND == 0 ? nT : 1);  // (its words have no other writer)
       continue;
     }
   }
@@ -516,6 +663,18 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
                            if constexpr (Form::where) return where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
                            return true;
                          });
+    } else if constexpr (Form::rank_count) {
+      rank_head_tile(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), A, c0, a0, nc, na, nT,
+                     [&](int e, int t) { return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]); },
+                     [&](int r, int a) {
+                       return !rank_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
+                     });
+    } else if constexpr (Form::rank_mask) {
+      rank_mask_head_tile(sel..., C, A, c0, a0, nc, na, nT,
+                          [&](int e, int t) { return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]); },
+                          [&](int r, int a) {
+                            return !rank_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
+                          });
     } else {
     store_rows(out, ((int64_t)c0 * A + a0) * nT, (int64_t)A * nT, nc, na * nT, nT, [&](int r, int a, int t) {
       return head_vft_eval(VftParams{resA[r * kTileA + a], resB[r * kTileA + a], resC[r * kTileA + a]}, t100[t]);
@@ -583,12 +742,22 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
         if constexpr (Form::where) return where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
         return true;
       });
+    } else if constexpr (Form::rank_count) {
+      rank_head_tile(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), A, c0, a0, nc, na, 1, [&](int e, int) { return res[e]; },
+                     [&](int r, int a) {
+                       return !rank_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
+                     });
+    } else if constexpr (Form::rank_mask) {
+      rank_mask_head_tile(sel..., C, A, c0, a0, nc, na, 1, [&](int e, int) { return res[e]; }, [&](int r, int a) {
+        return !rank_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
+      });
     } else {
     store_rows(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, 1, [&](int r, int a, int) { return res[r * kTileA + a]; });
     }
   }
   } while (select_next_tile(&tile, sel...));  // (the materialising form: one tile per workgroup)
   if constexpr (kSelect) select_finish(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
+  if constexpr (Form::rank_count) rank_finish(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
 }
 
 
@@ -634,6 +803,27 @@ __device__ __forceinline__ void partners_transfer_tile(const GridPartners& g, co
       best.offer(partners_entry(g, live(rr, tid), res[rr * kTgTileA + tid], (uint32_t)(c0 + rr) * (uint32_t)A + (uint32_t)(a0 + tid)));
     best.store(g.cols + ((size_t)tc * A + a0 + tid) * g.m, g.m);
   }
+}
+
+// The transfer grid's tile counted and as best-k mask words: thread tid holds pair (tid >> 5, tid & 31) of `res`; a wave's
+// lanes are two tile rows of 32 anions, lane 0 and lane 32 each write the word of their own row.
+template <class Live>
+__device__ __forceinline__ void rank_transfer_tile(const GridRank& g, float* lists, const float* res, int, int A, int c0,
+                                                   int a0, int nc, int na, Live live) {
+  const int tid = threadIdx.x, r = tid >> 5, p = tid & 31;
+  const bool ok = r < nc && p < na && live(r, p);
+  rank_count(g, reinterpret_cast<uint32_t*>(lists), rank_prefix(g, 0), ok,
+             rank_entry(res[tid], g.largest, (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + p)));
+  __syncthreads();  // the tile's regions and mask words are free for the next tile
+}
+template <class Live>
+__device__ __forceinline__ void rank_transfer_tile(const GridMaskRank& g, float*, const float* res, int, int A, int c0,
+                                                   int a0, int nc, int na, Live live) {
+  const int tid = threadIdx.x, r = tid >> 5, p = tid & 31;
+  const bool ok = r < nc && p < na && live(r, p);
+  const unsigned long long entry = rank_entry(res[tid], g.largest, (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + p));
+  uint32_t* word = g.words + (int64_t)(c0 + r) * g.W + (a0 >> 5);
+  mask_store_ballot(ok && entry <= g.state[0].bound, r < nc ? word : nullptr, r < nc ? word : nullptr);
 }
 
 __device__ __forceinline__ f32x16_t mfma32(float a, float b, f32x16_t c) {
@@ -712,6 +902,7 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
   constexpr bool kSelect = Form::select;
   unsigned tile = blockIdx.x;
   if constexpr (kSelect) select_init(sel..., sm + kTgLdsFloats, 1);
+  if constexpr (Form::rank_count) rank_init(sel..., sm + kTgLdsFloats, 1);
   do {
   const int c0 = (tile / tiles_a) * kTgTileC, a0 = (tile % tiles_a) * kTgTileA;
   const int nc = min(kTgTileC, C - c0), na = min(kTgTileA, A - a0);
@@ -719,6 +910,12 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
     if (!where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) {
       if constexpr (Form::partners)  // (its slots have no other writer)
         partners_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTgTileA, (C + kTgTileC - 1) / kTgTileC, c0 / kTgTileC, 1);
+      continue;
+    }
+  }
+  if constexpr (Form::rank_count || Form::rank_mask) {  // the rank forms' mask may be null: the same pass, when there is one
+    if (rank_masked(sel...) && !where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) {
+      rank_skip_tile(sel..., C, c0, nc, a0 >> 5, kTgTileA / 32, 1);  // (its words have no other writer)
       continue;
     }
   }
@@ -838,11 +1035,16 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
       if constexpr (Form::where) return where_bit(sel..., sm + kTgLdsFloats, 1, r, a, kTgTileA / 32);
       return true;
     });
+  } else if constexpr (Form::rank_count || Form::rank_mask) {
+    rank_transfer_tile(sel..., sm + kTgLdsFloats, res, C, A, c0, a0, nc, na, [&](int r, int a) {
+      return !rank_masked(sel...) || where_bit(sel..., sm + kTgLdsFloats, 1, r, a, kTgTileA / 32);
+    });
   } else {
   store_spans(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, res, kTgTileA);
   }
   } while (select_next_tile(&tile, sel...));  // (the materialising form: one tile per workgroup)
   if constexpr (kSelect) select_finish(sel..., sm + kTgLdsFloats, 1);
+  if constexpr (Form::rank_count) rank_finish(sel..., sm + kTgLdsFloats, 1);
 }
 
 

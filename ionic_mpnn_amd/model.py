@@ -1210,8 +1210,8 @@ class MPNNModel:
         return mask
 
     def _screen_request(self, what, cations, anions, temperatures, where, max_pairs_per_launch):
-        """The argument rules the selecting screens share (``screen_top_k``, ``screen_best_partners``) -> the
-        temperatures as a float32 host tensor (nT), or None for a model without them."""
+        """The argument rules the selecting screens share (``screen_top_k``, ``screen_best_partners``, ``screen_rank``,
+        ``screen_best_mask``) -> the temperatures as a float32 host tensor (nT), or None for a model without them."""
         if self.kind == "viscosity" and temperatures is None:
             raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
         if cations is None or anions is None:
@@ -1432,6 +1432,87 @@ class MPNNModel:
         if not visc:
             by_cation, by_anion = data.Partners(cat_v[0], cat_p[0]), data.Partners(an_v[0], an_p[0])
         return data.BestPartners(by_cation, by_anion)
+
+    def _screen_rank(self, what, cations, anions, temperatures, k, largest, where, batch_size, mask):
+        """``screen_rank`` and ``screen_best_mask``: the rank cut of every plane and, with ``mask``, the best-k mask ->
+        (data.RankCut of arrays (planes,), int32 words (planes,C,W) on the model's device or None)."""
+        T = self._screen_request(what, cations, anions, temperatures, where, None)
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        if len(cations["atom"]) * len(anions["atom"]) > ops.RANK_MAX_PAIRS:
+            raise ValueError(f"{what}: {len(cations['atom']) * len(anions['atom'])} pairs, a rank cut takes at most 2^32 - 2")
+        visc = self.kind == "viscosity"
+        pc, pa = self.encode_ions(cations, anions, batch_size)
+        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
+        planes = nT if visc else 1
+        if where is not None and where.words.device != pc.device:
+            where = data.PairMask(where.words.to(pc.device), where.shape)
+        values, count = np.full(planes, data.QUIET_NAN, np.float32), np.zeros(planes, np.int64)
+        cation, anion = np.full(planes, -1, np.int64), np.full(planes, -1, np.int64)
+        words = torch.zeros((planes, C, data.mask_row_words(A)), dtype=torch.int32, device=self.device) if mask else None
+        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
+        if C > 0 and A > 0 and (self._grid_kernels_cover() or mfma):
+            with torch.no_grad():
+                mc, ma, w = self._ion_halves(pc, pa, mfma)
+                wh = where.words if where is not None else None
+                for t0 in range(0, planes, ops.SELECT_MAX_T):
+                    t1 = min(planes, t0 + ops.SELECT_MAX_T)
+                    if mfma:
+                        got = ops.transfer_head_grid_rank(mc, ma, w, k, largest, where=wh, mask=mask)
+                    else:
+                        got = ops.head_grid_rank(self.kind, mc, ma, T[t0:t1].to(self.device) if visc else None, w,
+                                                 self.fp_size, self.mixing_size, k, largest, where=wh, mask=mask)
+                    values[t0:t1], cation[t0:t1], anion[t0:t1], count[t0:t1] = (x.cpu().numpy() for x in got[:4])
+                    if mask:
+                        words[t0:t1] = got[4].reshape(t1 - t0, C, -1)
+        elif C > 0 and A > 0:  # the host references on the grid itself
+            tk = {"temperatures": T} if visc else {}
+            grid = self.predict_grid(cations, anions, batch_size=batch_size, **tk)
+            values[:], cation[:], anion[:], count[:] = data.grid_rank(grid, k, largest, where)
+            if mask:
+                best = data.grid_best_mask(grid, k, largest, where)
+                words = data.PairMask.from_bool(best, device=self.device).words.reshape(planes, C, -1)
+        return data.RankCut(values, cation, anion, count), words
+
+    def screen_rank(self, cations, anions, temperatures=None, k=100, largest=False, where=None, batch_size=4096):
+        """The rank cut of a screen: the ``k``-th pair (1-based) with the smallest (``largest``: largest) prediction,
+        found on the GPU - what ``data.grid_rank(self.predict_grid(...), k, largest, where)`` returns, without the grid,
+        for any k: "the value below which the best 1 % of the pairs lie".  ``encode_ions``, the per-ion halves and the
+        argument rules are ``screen_top_k``'s; the rank-cut kernels (impnn_head_grid_rank,
+        impnn_transfer_head_grid_rank) evaluate the grid once per 8-bit digit of the selection's 64-bit entry
+        (``ops.rank_passes``) and keep only a histogram.  -> ``data.RankCut`` of numpy ``values`` float32, ``cation``,
+        ``anion`` int64 (positions in the lists given) and ``count`` int64, the number of competing pairs: arrays (nT,)
+        for viscosity, scalars otherwise.  Order: by value, ties by cation then anion index, NaN last; more than
+        ``count`` asked for gives NaN / -1 / -1.  Temperatures are split at ops.SELECT_MAX_T per launch; the cation axis
+        is not tiled: more than 2^32 - 2 pairs raise ValueError.  ``where``: a 2-D ``data.PairMask`` of shape (C,A), as
+        in ``screen_top_k``; only its pairs compete.
+        Widths the head kernels do not cover and the transfer model with ``grid_head_mode = "gathered"`` apply
+        ``data.grid_rank`` to ``predict_grid``: that path holds the grid."""
+        cut, _ = self._screen_rank("screen_rank", cations, anions, temperatures, k, largest, where, batch_size, False)
+        return cut if self.kind == "viscosity" else data.RankCut(*[x[0] for x in cut])
+
+    def screen_best_mask(self, cations, anions, temperatures=None, k=100, largest=False, where=None, batch_size=4096):
+        """The ``k`` best pairs of a screen as a set to go on working with: a ``data.PairMask`` whose set bits are exactly
+        the first min(k, competing) pairs under ``screen_top_k``'s order - ``PairMask.from_bool(data.grid_best_mask(
+        self.predict_grid(...), k, largest, where))`` without the grid, for any k - of shape (C,A,nT) for viscosity, a
+        plane per temperature, and (C,A) otherwise, its words on the model's device.  A run of equal predictions that
+        straddles k is cut by index: a plane never holds more than k bits.  The rank cut of ``screen_rank`` gives the
+        k-th entry, then one more launch over the grid sets every pair at or before it (impnn_head_grid_rank,
+        impnn_transfer_head_grid_rank with mask words).  ``where`` and the limits as in ``screen_rank``.  "The best 1 %
+        of the pairs that are liquid, then each cation's three best anions among them":
+
+            liquid = mp_model.screen_mask(cat, an, at_most=limit_scaled)
+            top1pc = visc_model.screen_best_mask(cat, an, [298.15], k=liquid.count() // 100, where=liquid).temperature(0)
+            per_cation = visc_model.screen_best_partners(cat, an, [298.15], m=3, where=top1pc)
+
+        Widths the head kernels do not cover and the transfer model with ``grid_head_mode = "gathered"`` apply
+        ``data.grid_best_mask`` to ``predict_grid``: that path holds the grid."""
+        _, words = self._screen_rank("screen_best_mask", cations, anions, temperatures, k, largest, where, batch_size, True)
+        C, A = int(words.shape[1]), len(anions["atom"])
+        if self.kind == "viscosity":
+            return data.PairMask(words, (C, A, int(words.shape[0])))
+        return data.PairMask(words[0], (C, A))
 
     def _grid_gathered(self, pc, pa, T):
         """``self.head`` on the explicit pairs of a tile of cations x all anions (x T) -> (c, A[, nT])."""

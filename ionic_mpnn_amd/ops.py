@@ -1028,6 +1028,112 @@ def transfer_head_grid_partners(u_cat, u_an, image, m=1, largest=False, where=No
     return tuple(out)
 
 
+# the rank cut (csrc/grid_rank.hip): kRankDigitBits of csrc/common.h (tests/test_rank_host.py holds them equal)
+RANK_DIGIT_BITS = 8
+RANK_MAX_PAIRS = 2 ** 32 - 2   # the entry format: a pair index stays below 2^32 - 1
+
+
+def rank_passes(C_, A_):
+    """Launches over the grid one rank cut of a C x A grid takes (impnn_grid_rank_passes): a pass per digit of the key
+    (32 bits) and per digit that holds C * A - 1."""
+    passes, top = 32 // RANK_DIGIT_BITS, max(int(C_) * int(A_) - 1, 0)
+    while top:
+        passes, top = passes + 1, top >> RANK_DIGIT_BITS
+    return passes
+
+
+def _grid_rank_outputs(lib, family, C_, A_, nT, workgroups, mask, dev):
+    planes = max(nT, 1)
+    if C_ * A_ > RANK_MAX_PAIRS:
+        raise ValueError(f"{C_ * A_} pairs: a rank cut takes at most 2^32 - 2")
+    need = C.c_size_t(0)
+    check(lib.impnn_grid_rank_workspace_bytes(family, C_, A_, nT, workgroups, C.byref(need)))
+    values = torch.empty(planes, dtype=torch.float32, device=dev)
+    cation = torch.empty(planes, dtype=torch.int32, device=dev)
+    anion = torch.empty(planes, dtype=torch.int32, device=dev)
+    count = torch.empty(planes, dtype=torch.int64, device=dev)
+    words = None
+    if mask:
+        W = int(lib.impnn_grid_mask_row_words(A_))
+        words = torch.empty((nT, C_, W) if nT > 0 else (C_, W), dtype=torch.int32, device=dev)
+    if C_ == 0 or A_ == 0:  # zero work touches nothing: no pair competes
+        values.fill_(float("nan")), cation.fill_(-1), anion.fill_(-1), count.zero_()
+        if words is not None:
+            words.zero_()
+    return (values, cation, anion, count, words), _workspace(dev, need.value), need.value
+
+
+def head_grid_rank(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, k, largest=False, where=None,
+                   mask=False, workgroups=0):
+    """The k-th best pair of ``head_grid``'s product, and with ``mask`` the k best as a packed pair mask, without the
+    product (impnn_head_grid_rank): the same arguments -> (values (nT,) float32, cation (nT,), anion (nT,) int32, count
+    (nT,) int64, words) on the device, an element per temperature (one for "melting_point"): the k-th entry (1-based)
+    under the order of ``data.grid_top_k`` and the number of competing pairs; more than count asked for: NaN / -1 / -1.
+    ``words``: None, or the int32 words (C,W), "viscosity" (nT,C,W), of the first min(k, count) pairs - the ``words`` of
+    a ``data.PairMask``.  A value has the bits ``head_grid`` gives for its pair; k is any integer >= 1.  At most
+    SELECT_MAX_T temperatures, C*A <= RANK_MAX_PAIRS.  ``where``: the (C,W) words of a pair mask: only its pairs
+    compete."""
+    require_gpu(mix_cat, mix_an, head_weights)
+    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
+    kd = HEAD_KINDS[kind]
+    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
+        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
+                         f"and {tuple(mix_an.shape)}")
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    lib = _lib.load()
+    per_d = 2 * fp_size
+    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
+    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
+    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+    T, nT = None, 0
+    if kd == 0:
+        if temperatures is None:
+            raise ValueError("the viscosity grid needs temperatures")
+        require_gpu(temperatures)
+        T = f32c(temperatures).reshape(-1)
+        nT = int(T.numel())
+    elif temperatures is not None:
+        raise ValueError("the melting-point grid takes no temperatures")
+    dev = mix_cat.device
+    k, workgroups = int(k), int(workgroups)
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
+    with torch.cuda.device(dev):
+        out, ws, nbytes = _grid_rank_outputs(lib, 0, C_, A_, nT, workgroups, mask, dev)
+        check(lib.impnn_head_grid_rank(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None, ptr(head_weights),
+                                       k, int(bool(largest)), ptr(where) if where is not None else None,
+                                       *[ptr(o) if o is not None else None for o in out], ptr(ws), nbytes, C_, A_, nT, D,
+                                       fp_size, mixing_size, workgroups, stream_ptr()))
+    return out
+
+
+def transfer_head_grid_rank(u_cat, u_an, image, k, largest=False, where=None, mask=False, workgroups=0):
+    """The k-th best pair of ``transfer_head_grid``'s product, and with ``mask`` the k best as a packed pair mask,
+    without the product (impnn_transfer_head_grid_rank) -> (values (1,), cation (1,), anion (1,), count (1,), words
+    (C,W) or None) on the device, as ``head_grid_rank``; ``where`` as there."""
+    require_gpu(u_cat, u_an, image)
+    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
+    W = TRANSFER_GRID_WIDTH
+    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
+        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
+    lib = _lib.load()
+    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
+        raise ValueError("the prepared image has the wrong length")
+    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
+    dev = u_cat.device
+    k, workgroups = int(k), int(workgroups)
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
+    with torch.cuda.device(dev):
+        out, ws, nbytes = _grid_rank_outputs(lib, 1, C_, A_, 0, workgroups, mask, dev)
+        check(lib.impnn_transfer_head_grid_rank(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), k, int(bool(largest)),
+                                                ptr(where) if where is not None else None,
+                                                *[ptr(o) if o is not None else None for o in out], ptr(ws), nbytes, C_, A_,
+                                                workgroups, stream_ptr()))
+    return out
+
+
 def _mask_bounds(lo, hi):
     lo, hi = C.c_float(lo).value, C.c_float(hi).value  # as the kernels see them: float32
     if lo != lo or hi != hi:

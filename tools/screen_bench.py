@@ -7,6 +7,7 @@ python tools/screen_bench.py [--quick] [--only viscosity|transfer]      -> one J
 python tools/screen_bench.py --select [--quick] [--only ...]            -> the top-k selection instead (see below)
 python tools/screen_bench.py --select --where FRACTION [--quick]        -> the constrained screen instead (see below)
 python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each ion's best partners instead (see below)
+python tools/screen_bench.py --rank [--where FRACTION] [--quick]        -> the best-k pair mask instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -33,7 +34,15 @@ at the configurations of --select: three alternating rounds after a warm-up of e
 two ways must return the same bits.  Plus the partner-selecting launches alone (impnn_head_grid_partners /
 impnn_transfer_head_grid_partners with their merge; a sweep above ops.SELECT_MAX_T temperatures takes several) against
 the materialising launch of the same C x A x nT, 10 calls between two HIP events, three rounds each in turn.  With
---where F both ways run under one random pair mask of density F."""
+--where F both ways run under one random pair mask of density F.
+
+--rank: MPNNModel.screen_best_mask(k = 1 % of the grid, or of the mask's pairs) against predict_grid followed by
+data.grid_best_mask on the host, at the large configurations of --select (all of them with --all-configs): three
+alternating rounds after a warm-up of each, wall time, median and spread; the two ways must return the same words.  Plus
+the launches of one rank call alone (impnn_head_grid_rank / impnn_transfer_head_grid_rank: a counting and a step launch
+per digit, ops.rank_passes of them, and the mask launch; a sweep above ops.SELECT_MAX_T temperatures takes several calls)
+against the materialising launch of the same C x A x nT, 10 calls between two HIP events, three rounds each in turn, and
+the rank cut alone (no mask launch).  With --where F both ways run under one random pair mask of density F."""
 import argparse
 import json
 import statistics
@@ -53,11 +62,13 @@ ap.add_argument("--quick", action="store_true", help="the first configuration on
 ap.add_argument("--only", choices=("viscosity", "transfer"), help="one family of configurations")
 ap.add_argument("--select", action="store_true", help="time screen_top_k against predict_grid + host selection")
 ap.add_argument("--partners", action="store_true", help="time screen_best_partners against predict_grid + host reference")
+ap.add_argument("--rank", action="store_true", help="time screen_best_mask against predict_grid + host reference")
+ap.add_argument("--all-configs", action="store_true", help="with --rank: the small configurations of --select too")
 ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: the constrained screen at this mask density; "
-                "with --partners: a random mask of this density")
+                "with --partners, --rank: a random mask of this density")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners  # another table than the default one
+other = args.select or args.partners or args.rank  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -222,7 +233,70 @@ def same_partners(a, b):
                               if y.dtype == np.float32 else y) for sa, sb in zip(a, b) for x, y in zip(sa, sb))
 
 
-if args.partners:
+RANK_CONFIGS = ("config2 2048x2048x4", "transfer 1024x1024", "transfer 4096x4096")  # the rows of the selection table
+
+if args.rank:
+    todo = [c for c in SELECT_CONFIGS if args.only in (None, c[0]) and (args.all_configs or c[1] in RANK_CONFIGS)]
+    for kind, name, D, S, C, A, nT in todo[:1] if args.quick else todo:
+        if kind == "viscosity":
+            m = MM.build_model(Va, Vb, atom_dim=D, num_steps=S, device=dev)
+            m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=D, num_steps=S, seed=1, perturb=True))
+            T = np.linspace(263.15, 393.15, nT).astype(np.float32)
+        else:
+            m, T = build_transfer(D, S), None
+        cat, _ = species(C, 1)
+        _, an = species(A, 2)
+        where_b = None if args.where is None else np.random.default_rng(5).random((C, A)) < float(args.where)
+        where = None if where_b is None else data.PairMask.from_bool(where_b, device=dev)
+        k = max((C * A if where is None else where.count()) // 100, 1)
+        old_way = lambda: data.PairMask.from_bool(data.grid_best_mask(m.predict_grid(cat, an, T), k, where=where_b))
+        new_way = lambda: m.screen_best_mask(cat, an, T, k=k, where=where)
+        _, best_old = wall(old_way)
+        _, best_new = wall(new_way)
+        t_old, t_new = [], []
+        for _ in range(3):
+            t_old.append(wall(old_way)[0])
+            t_new.append(wall(new_way)[0])
+        words = None if where is None else where.words
+        with torch.no_grad():
+            pc, pa = m.encode_ions(cat, an)
+            if kind == "viscosity":
+                w = m._packed_head()
+                mc = ops.head_ion_mix(kind, "cat", pc, w, m.fp_size, m.mixing_size)
+                ma = ops.head_ion_mix(kind, "an", pa, w, m.fp_size, m.mixing_size)
+                Td = torch.from_numpy(T).to(dev)
+                store = lambda: [ops.head_grid(kind, mc, ma, Td, w, m.fp_size, m.mixing_size) for _ in range(10)]
+                rank = lambda mask: [ops.head_grid_rank(kind, mc, ma, Td[t0:t0 + ops.SELECT_MAX_T], w, m.fp_size, m.mixing_size, k,
+                                                        where=words, mask=mask)
+                                     for _ in range(10) for t0 in range(0, nT, ops.SELECT_MAX_T)]
+            else:
+                tensors, image = m._head_tensors(), m._transfer_image()
+                uc = ops.transfer_ion_half("cat", pc, tensors, m.fp_size, m.mixing_size)
+                ua = ops.transfer_ion_half("an", pa, tensors, m.fp_size, m.mixing_size)
+                store = lambda: [ops.transfer_head_grid(uc, ua, image) for _ in range(10)]
+                rank = lambda mask: [ops.transfer_head_grid_rank(uc, ua, image, k, where=words, mask=mask) for _ in range(10)]
+            timed(store), timed(lambda: rank(True)), timed(lambda: rank(False))
+            k_store, k_rank, k_cut = [], [], []
+            for _ in range(3):
+                k_store.append(timed(store)[0] / 10 * 1e3)
+                k_rank.append(timed(lambda: rank(True))[0] / 10 * 1e3)
+                k_cut.append(timed(lambda: rank(False))[0] / 10 * 1e3)
+        passes = ops.rank_passes(C, A)
+        calls = (max(nT, 1) + ops.SELECT_MAX_T - 1) // ops.SELECT_MAX_T if kind == "viscosity" else 1
+        line = {"config": "rank " + name + ("" if args.where is None else " F=%g" % args.where), "kind": kind, "atom_dim": D,
+                "steps": S, "C": C, "A": A, "nT": nT, "k": int(k), "values": C * A * max(nT, 1), "passes": passes,
+                "mask_density": None if where is None else round(where.count() / (C * A), 4),
+                "predict_grid_plus_host_best_mask_ms": spread(t_old), "screen_best_mask_ms": spread(t_new),
+                "speedup": round(statistics.median(t_old) / statistics.median(t_new), 2),
+                "materialising_launch_us": spread(k_store), "rank_launches_us": spread(k_rank), "rank_cut_launches_us": spread(k_cut),
+                "per_pass_over_materialising": round(statistics.median(k_cut) / (passes * calls * statistics.median(k_store)), 3),
+                "mask_launch_us": round(statistics.median(k_rank) - statistics.median(k_cut), 2),
+                "same_answer": bool(np.array_equal(best_old.words.numpy(), best_new.words.cpu().numpy()))}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del m
+        torch.cuda.empty_cache()
+elif args.partners:
     todo = [c for c in SELECT_CONFIGS if args.only in (None, c[0])]
     for kind, name, D, S, C, A, nT in todo[:1] if args.quick else todo:
         if kind == "viscosity":
