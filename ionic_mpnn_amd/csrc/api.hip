@@ -545,6 +545,26 @@ int impnn_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float
                                 launch_model_head_bwd});
 }
 
+// ---- the operands of a grid launch, as the C entries take them: the head form and the transfer form
+namespace {
+GridOperands head_grid_operands(int kind, const float* mix_cat, const float* mix_an, const float* T, const float* w, int C,
+                                int A, int nT, int D, int F, int Mx, impnn_stream_t stream) {
+  return {0, kind, mix_cat, mix_an, T, w, C, A, nT, D, F, Mx, as_stream(stream)};
+}
+GridOperands transfer_grid_operands(const float* u_cat, const float* u_an, const float* image, int C, int A,
+                                    impnn_stream_t stream) {
+  return {1, 1, u_cat, u_an, nullptr, image, C, A, 0, 0, 0, 0, as_stream(stream)};
+}
+// the transfer grid's operands: 16-byte alignment, then the image size (image_floats < 0: the entry takes no image)
+int transfer_image_rule(const char* entry, bool aligned_ok, int64_t image_floats) {
+  if (!aligned_ok) return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
+  if (image_floats >= 0 && image_floats < transfer_grid_image_floats())
+    return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
+                (long long)transfer_grid_image_floats());
+  return IMPNN_OK;
+}
+}  // namespace
+
 // ---- the head over a cation x anion grid (include/impnn.h; head_grid.hip).  The family's order: shape, zero work,
 // null pointers.
 int impnn_head_ion_mix(int32_t kind, int32_t ion, const float* pooled, const float* head_weights, float* mix, int32_t M,
@@ -571,8 +591,8 @@ int impnn_head_grid(int32_t kind, const float* mix_cat, const float* mix_an, con
   if (C == 0 || A == 0) return IMPNN_OK;
   REQUIRE(mix_cat && mix_an && head_weights && out && (kind == 1 || temperatures), "null pointer");
   REQUIRE(kind == 0 || (!temperatures && !params), "the melting-point grid takes neither temperatures nor params");
-  return launch_head_grid(kind, mix_cat, mix_an, temperatures, head_weights, out, params, C, A, nT, D, F, Mx,
-                          as_stream(stream));
+  return launch_head_grid(head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                          out, params);
 }
 
 // ---- the transfer head (include/impnn.h; transfer_head.hip)
@@ -678,10 +698,7 @@ int transfer_grid_check(const TransferGridCheck& c, bool* launch) {
   if (c.weights_needed)
     for (int t = 0; t < kThTensors; ++t)
       if (!c.weights[t]) return fail(IMPNN_E_BADARG, "%s: null weight tensor %d", c.entry, t);
-  if (!c.aligned_ok) return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", c.entry);
-  if (c.image_floats >= 0 && c.image_floats < transfer_grid_image_floats())
-    return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", c.entry, (long long)c.image_floats,
-                (long long)transfer_grid_image_floats());
+  if (int rc = transfer_image_rule(c.entry, c.aligned_ok, c.image_floats)) return rc;
   if (int rc = head_widths_covered(c.entry, c.D, c.F, c.Mx)) return rc;
   *launch = true;
   return IMPNN_OK;
@@ -721,115 +738,164 @@ int impnn_transfer_head_grid(const float* u_cat, const float* u_an, const float*
   c.aligned_ok = aligned16(u_cat) && aligned16(u_an) && aligned16(image), c.image_floats = image_floats;
   bool launch;
   if (int rc = transfer_grid_check(c, &launch)) return rc;
-  return launch ? launch_transfer_head_grid(u_cat, u_an, image, out, C, A, as_stream(stream)) : IMPNN_OK;
+  return launch ? launch_transfer_head_grid(transfer_grid_operands(u_cat, u_an, image, C, A, stream), out) : IMPNN_OK;
 }
 
-// ---- top-k selection over a cation x anion grid (include/impnn.h; grid_select.hip).  One place applies the family's
-// rules in their fixed order: shape, zero work, null pointers, workspace size.
+// ---- the screening family over a cation x anion grid: top-k (grid_select.hip), best partners (grid_partners.hip), the
+// rank cut (grid_rank.hip), pair masks (grid_mask.hip).  Each rule the entries share is one helper that takes the
+// entry's name; each *_checked below lists them in its own fixed order (tests/test_cabi.py and the host tests pin it).
 namespace {
-// shape only: what the workspace query and the two entries share
-int grid_topk_shape(const char* entry, int family, int C, int A, int nT, int k, int workgroups) {
+int grid_family_rule(const char* entry, int family) {
   if (family != 0 && family != 1) return fail(IMPNN_E_BADARG, "%s: family must be 0 (head grid) or 1 (transfer grid)", entry);
-  if (C < 0 || A < 0 || nT < 0 || workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
-  if (k < 1) return fail(IMPNN_E_BADARG, "%s: k=%d must be at least 1", entry, k);
-  if (k > kSelectMaxK) return fail(IMPNN_E_UNSUPPORTED, "%s: k=%d entries (<= %d per call)", entry, k, kSelectMaxK);
+  return IMPNN_OK;
+}
+// the kind, the entry's signs (`shape_ok`), then the temperature count the kind allows (a negative nT is a bad shape)
+int grid_kind_rule(const char* entry, const GridOperands& g, bool shape_ok) {
+  if (g.family == 0 && g.kind != 0 && g.kind != 1)
+    return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", entry);
+  if (!shape_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (g.family == 0 && g.kind == 0 && g.nT == 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
+  if (g.family == 0 && g.kind == 1 && g.nT > 0)
+    return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", entry);
+  return IMPNN_OK;
+}
+int grid_no_temperatures_rule(const char* entry, const GridOperands& g) {
+  if (g.family == 0 && g.kind == 1 && g.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
+  return IMPNN_OK;
+}
+int grid_transfer_rule(const char* entry, const GridOperands& g, int64_t image_floats) {
+  if (g.family != 1) return IMPNN_OK;
+  return transfer_image_rule(entry, aligned16(g.mix_cat) && aligned16(g.mix_an) && aligned16(g.w), image_floats);
+}
+// workspace alignment (8 bytes) and mask alignment (4): `message` names the entry's buffers; q may be null
+int grid_aligned_rule(const char* entry, const void* p, const void* q, unsigned bytes, const char* message) {
+  if (((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q)) & (bytes - 1)) != 0)
+    return fail(IMPNN_E_BADARG, "%s: %s", entry, message);
+  return IMPNN_OK;
+}
+int grid_workspace_rule(const char* entry, size_t workspace_bytes, size_t need) {
+  if (workspace_bytes < need)
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", entry, workspace_bytes, need);
+  return IMPNN_OK;
+}
+int grid_select_temperatures_rule(const char* entry, int nT) {
   if (nT > kSelectMaxT)
     return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
+  return IMPNN_OK;
+}
+int grid_pairs_rule(const char* entry, int C, int A) {
   if ((int64_t)C * A >= (int64_t)1 << 32)
     return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (< 2^32 per call); split the cation axis", entry,
                 (long long)((int64_t)C * A));
   return IMPNN_OK;
 }
 
-// What the selecting entries (top-k, best partners) share of a request: the operands and the buffers between launches.
-struct GridRequest {
-  const char* entry;
-  int family, kind;
-  const float *mix_cat, *mix_an, *T, *w;
-  const void* workspace;
-  const uint32_t* where;
-  bool where_needed;  // a _where entry: a null mask is a null pointer
-  int C, A, nT, D, F, Mx;
-};
-
-// before the entry's own shape rule: the kind, the widths' signs and the temperature count of the kind
-int grid_request_kind(const GridRequest& r, bool widths_ok, int64_t image_floats) {
-  if (r.family == 0) {
-    if (r.kind != 0 && r.kind != 1) return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", r.entry);
-    if (!widths_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", r.entry);
-    if (r.kind == 0 && r.nT < 1 && r.nT >= 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", r.entry);
-    if (r.kind == 1 && r.nT > 0)
-      return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", r.entry);
-  } else if (image_floats < 0) {
-    return fail(IMPNN_E_BADARG, "%s: bad shape", r.entry);
-  }
-  return IMPNN_OK;
+// shape only: what the workspace query and the entries share
+int grid_topk_shape(const char* entry, int family, int C, int A, int nT, int k, int workgroups) {
+  if (int rc = grid_family_rule(entry, family)) return rc;
+  if (C < 0 || A < 0 || nT < 0 || workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (k < 1) return fail(IMPNN_E_BADARG, "%s: k=%d must be at least 1", entry, k);
+  if (k > kSelectMaxK) return fail(IMPNN_E_UNSUPPORTED, "%s: k=%d entries (<= %d per call)", entry, k, kSelectMaxK);
+  if (int rc = grid_select_temperatures_rule(entry, nT)) return rc;
+  return grid_pairs_rule(entry, C, A);
+}
+int grid_partners_shape(const char* entry, int family, int C, int A, int nT, int m) {
+  if (int rc = grid_family_rule(entry, family)) return rc;
+  if (C < 0 || A < 0 || nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (m < 1) return fail(IMPNN_E_BADARG, "%s: m=%d must be at least 1", entry, m);
+  if (m > kPartnersMaxM) return fail(IMPNN_E_UNSUPPORTED, "%s: m=%d partners (<= %d per call)", entry, m, kPartnersMaxM);
+  if (int rc = grid_select_temperatures_rule(entry, nT)) return rc;
+  return grid_pairs_rule(entry, C, A);
+}
+int grid_rank_limits(const char* entry, int C, int A, int nT) {
+  if ((int64_t)C * A > kRankMaxPairs)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (<= 2^32 - 2 per call)", entry, (long long)((int64_t)C * A));
+  return grid_select_temperatures_rule(entry, nT);
 }
 
-// after it: the widths' limits, zero work (IMPNN_OK with *launch == false), null pointers, alignment and the image
-// size, the workspace size (`need`: the entry's query for the request's shape)
-int grid_request_operands(const GridRequest& r, bool pointers_ok, int64_t image_floats, size_t need, size_t workspace_bytes,
-                          bool* launch) {
+// Top-k and best partners, after the entry's own shape rule: the widths' limits, zero work (IMPNN_OK with *launch ==
+// false), null pointers, alignment and the image size, the workspace size (`need`: the entry's query for the shape).
+int grid_selecting_rules(const char* entry, const GridOperands& g, bool pointers_ok, const void* workspace,
+                         const uint32_t* where, int64_t image_floats, size_t need, size_t workspace_bytes, bool* launch) {
   *launch = false;
-  if (r.family == 0)
-    if (int rc = head_widths_covered(r.entry, r.D, r.F, r.Mx)) return rc;
-  if (r.C == 0 || r.A == 0) return IMPNN_OK;
-  if (!pointers_ok || (r.where_needed && !r.where)) return fail(IMPNN_E_BADARG, "%s: null pointer", r.entry);
-  if (r.family == 0 && r.kind == 1 && r.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", r.entry);
-  if ((reinterpret_cast<uintptr_t>(r.workspace) & 7u) != 0) return fail(IMPNN_E_BADARG, "%s: the workspace must be 8-byte aligned", r.entry);
-  if ((reinterpret_cast<uintptr_t>(r.where) & 3u) != 0) return fail(IMPNN_E_BADARG, "%s: the mask must be 4-byte aligned", r.entry);
-  if (r.family == 1) {
-    if (!(aligned16(r.mix_cat) && aligned16(r.mix_an) && aligned16(r.w)))
-      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", r.entry);
-    if (image_floats < transfer_grid_image_floats())
-      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", r.entry, (long long)image_floats,
-                  (long long)transfer_grid_image_floats());
-  }
-  if (workspace_bytes < need)
-    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", r.entry, workspace_bytes, need);
+  if (g.family == 0)
+    if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
+  if (g.C == 0 || g.A == 0) return IMPNN_OK;
+  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (int rc = grid_no_temperatures_rule(entry, g)) return rc;
+  if (int rc = grid_aligned_rule(entry, workspace, nullptr, 8, "the workspace must be 8-byte aligned")) return rc;
+  if (int rc = grid_aligned_rule(entry, where, nullptr, 4, "the mask must be 4-byte aligned")) return rc;
+  if (int rc = grid_transfer_rule(entry, g, image_floats)) return rc;
+  if (int rc = grid_workspace_rule(entry, workspace_bytes, need)) return rc;
   *launch = true;
   return IMPNN_OK;
 }
 
-int grid_topk_checked(const char* entry, const GridTopkCall& c, bool widths_ok, bool pointers_ok, int64_t image_floats,
+// shape_ok: the widths' signs (head grid), image_floats >= 0 (transfer grid)
+int grid_topk_checked(const char* entry, const GridTopkCall& c, bool shape_ok, bool pointers_ok, int64_t image_floats,
                       size_t workspace_bytes) {
-  const GridRequest r{entry, c.family, c.kind, c.mix_cat, c.mix_an, c.T, c.w, c.workspace, c.where, c.masked,
-                      c.C, c.A, c.nT, c.D, c.F, c.Mx};
-  if (int rc = grid_request_kind(r, widths_ok, image_floats)) return rc;
-  if (int rc = grid_topk_shape(entry, c.family, c.C, c.A, c.nT, c.k, c.workgroups)) return rc;
+  const GridOperands& g = c.g;
+  if (int rc = grid_kind_rule(entry, g, shape_ok)) return rc;
+  if (int rc = grid_topk_shape(entry, g.family, g.C, g.A, g.nT, c.k, c.workgroups)) return rc;
   bool launch;
-  if (int rc = grid_request_operands(r, pointers_ok, image_floats,
-                                     grid_topk_workspace_bytes(c.family, c.C, c.A, c.nT, c.k, c.workgroups), workspace_bytes,
-                                     &launch))
+  if (int rc = grid_selecting_rules(entry, g, pointers_ok && (!c.masked || c.where), c.workspace, c.where, image_floats,
+                                    grid_topk_workspace_bytes(g.family, g.C, g.A, g.nT, c.k, c.workgroups), workspace_bytes,
+                                    &launch))
     return rc;
   return launch ? launch_grid_topk(c) : IMPNN_OK;
 }
 
-// ---- each ion's best partners (include/impnn.h; grid_partners.hip): the same request, its own shape rule
-int grid_partners_shape(const char* entry, int family, int C, int A, int nT, int m) {
-  if (family != 0 && family != 1) return fail(IMPNN_E_BADARG, "%s: family must be 0 (head grid) or 1 (transfer grid)", entry);
-  if (C < 0 || A < 0 || nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
-  if (m < 1) return fail(IMPNN_E_BADARG, "%s: m=%d must be at least 1", entry, m);
-  if (m > kPartnersMaxM) return fail(IMPNN_E_UNSUPPORTED, "%s: m=%d partners (<= %d per call)", entry, m, kPartnersMaxM);
-  if (nT > kSelectMaxT)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
-  if ((int64_t)C * A >= (int64_t)1 << 32)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (< 2^32 per call); split the cation axis", entry,
-                (long long)((int64_t)C * A));
-  return IMPNN_OK;
-}
-
-int grid_partners_checked(const char* entry, const GridPartnersCall& c, bool widths_ok, bool pointers_ok,
+int grid_partners_checked(const char* entry, const GridPartnersCall& c, bool shape_ok, bool pointers_ok,
                           int64_t image_floats, size_t workspace_bytes) {
-  const GridRequest r{entry, c.family, c.kind, c.mix_cat, c.mix_an, c.T, c.w, c.workspace, c.where, false,
-                      c.C, c.A, c.nT, c.D, c.F, c.Mx};
-  if (int rc = grid_request_kind(r, widths_ok, image_floats)) return rc;
-  if (int rc = grid_partners_shape(entry, c.family, c.C, c.A, c.nT, c.m)) return rc;
+  const GridOperands& g = c.g;
+  if (int rc = grid_kind_rule(entry, g, shape_ok)) return rc;
+  if (int rc = grid_partners_shape(entry, g.family, g.C, g.A, g.nT, c.m)) return rc;
   bool launch;
-  if (int rc = grid_request_operands(r, pointers_ok, image_floats,
-                                     grid_partners_workspace_bytes(c.family, c.C, c.A, c.nT, c.m), workspace_bytes, &launch))
+  if (int rc = grid_selecting_rules(entry, g, pointers_ok, c.workspace, c.where, image_floats,
+                                    grid_partners_workspace_bytes(g.family, g.C, g.A, g.nT, c.m), workspace_bytes, &launch))
     return rc;
   return launch ? launch_grid_partners(c) : IMPNN_OK;
+}
+
+// The rank cut's order: kind, shape, zero work, null pointers (then alignment and the image size), k < 1, the
+// pair-count limit, the nT limit, the workspace size, the widths.  Nothing is launched before the last.
+int grid_rank_checked(const char* entry, const GridRankCall& c, bool shape_ok, bool pointers_ok, int64_t image_floats,
+                      size_t workspace_bytes) {
+  const GridOperands& g = c.g;
+  if (int rc = grid_kind_rule(entry, g, shape_ok)) return rc;
+  if (g.C < 0 || g.A < 0 || g.nT < 0 || c.workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (g.C == 0 || g.A == 0) return IMPNN_OK;
+  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (int rc = grid_no_temperatures_rule(entry, g)) return rc;
+  if (int rc = grid_aligned_rule(entry, c.workspace, c.count, 8, "the workspace and the counts must be 8-byte aligned")) return rc;
+  if (int rc = grid_aligned_rule(entry, c.where, c.mask_words, 4, "the masks must be 4-byte aligned")) return rc;
+  if (int rc = grid_transfer_rule(entry, g, image_floats)) return rc;
+  if (c.k < 1) return fail(IMPNN_E_BADARG, "%s: k=%lld must be at least 1", entry, (long long)c.k);
+  if (int rc = grid_rank_limits(entry, g.C, g.A, g.nT)) return rc;
+  if (int rc = grid_workspace_rule(entry, workspace_bytes, grid_rank_workspace_bytes(g.family, g.C, g.A, g.nT, c.workgroups)))
+    return rc;
+  if (g.family == 0)
+    if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
+  return launch_grid_rank(c);
+}
+
+// The pair masks' order: kind, shape, the temperature count, a NaN bound, zero work, null pointers, alignment and the
+// image size, the limits of one launch.
+int grid_mask_checked(const char* entry, const GridMaskCall& c, bool shape_ok, bool pointers_ok, int64_t image_floats) {
+  const GridOperands& g = c.g;
+  if (int rc = grid_kind_rule(entry, g, shape_ok && g.C >= 0 && g.A >= 0 && g.nT >= 0)) return rc;
+  if (c.lo != c.lo || c.hi != c.hi) return fail(IMPNN_E_BADARG, "%s: a bound is NaN (an infinity means no limit)", entry);
+  if (g.C == 0 || g.A == 0) return IMPNN_OK;
+  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
+  if (int rc = grid_no_temperatures_rule(entry, g)) return rc;
+  if (int rc = grid_aligned_rule(entry, c.words, nullptr, 4, "the mask must be 4-byte aligned")) return rc;
+  if (int rc = grid_transfer_rule(entry, g, image_floats)) return rc;
+  if (g.family == 0) {
+    if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
+    if (g.nT > head_grid_max_temperatures())
+      return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, g.nT, head_grid_max_temperatures());
+  }
+  return launch_grid_mask(c);
 }
 }  // namespace
 
@@ -847,8 +913,8 @@ int impnn_head_grid_topk(int32_t kind, const float* mix_cat, const float* mix_an
                          const float* head_weights, int32_t k, int32_t largest, float* values, int32_t* cation,
                          int32_t* anion, void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT,
                          int32_t D, int32_t F, int32_t Mx, int32_t workgroups, impnn_stream_t stream) {
-  const GridTopkCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, k, largest, values, cation, anion, workspace,
-                       C, A, nT, D, F, Mx, workgroups, as_stream(stream)};
+  const GridTopkCall c{head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                       k, largest, values, cation, anion, workspace, workgroups, false, nullptr};
   return grid_topk_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
                            mix_cat && mix_an && head_weights && values && cation && anion && workspace &&
                                (kind == 1 || temperatures),
@@ -859,9 +925,9 @@ int impnn_transfer_head_grid_topk(const float* u_cat, const float* u_an, const f
                                   int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
                                   void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
                                   impnn_stream_t stream) {
-  const GridTopkCall c{1, 1, u_cat, u_an, nullptr, image, k, largest, values, cation, anion, workspace,
-                       C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
-  return grid_topk_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && workspace,
+  const GridTopkCall c{transfer_grid_operands(u_cat, u_an, image, C, A, stream), k, largest, values, cation, anion,
+                       workspace, workgroups, false, nullptr};
+  return grid_topk_checked(__func__, c, image_floats >= 0, u_cat && u_an && image && values && cation && anion && workspace,
                            image_floats, workspace_bytes);
 }
 
@@ -870,9 +936,8 @@ int impnn_head_grid_topk_where(int32_t kind, const float* mix_cat, const float* 
                                float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
                                int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F, int32_t Mx, int32_t workgroups,
                                impnn_stream_t stream) {
-  GridTopkCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, k, largest, values, cation, anion, workspace,
-                 C, A, nT, D, F, Mx, workgroups, as_stream(stream)};
-  c.masked = true, c.where = where;
+  const GridTopkCall c{head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                       k, largest, values, cation, anion, workspace, workgroups, true, where};
   return grid_topk_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
                            mix_cat && mix_an && head_weights && values && cation && anion && workspace &&
                                (kind == 1 || temperatures),
@@ -883,10 +948,9 @@ int impnn_transfer_head_grid_topk_where(const float* u_cat, const float* u_an, c
                                         const uint32_t* where, int32_t k, int32_t largest, float* values,
                                         int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
                                         int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream) {
-  GridTopkCall c{1, 1, u_cat, u_an, nullptr, image, k, largest, values, cation, anion, workspace,
-                 C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
-  c.masked = true, c.where = where;
-  return grid_topk_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && workspace,
+  const GridTopkCall c{transfer_grid_operands(u_cat, u_an, image, C, A, stream), k, largest, values, cation, anion,
+                       workspace, workgroups, true, where};
+  return grid_topk_checked(__func__, c, image_floats >= 0, u_cat && u_an && image && values && cation && anion && workspace,
                            image_floats, workspace_bytes);
 }
 
@@ -902,8 +966,8 @@ int impnn_head_grid_partners(int32_t kind, const float* mix_cat, const float* mi
                              float* cat_values, int32_t* cat_partner, float* an_values, int32_t* an_partner,
                              void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t D,
                              int32_t F, int32_t Mx, impnn_stream_t stream) {
-  const GridPartnersCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, where, m, largest, cat_values, cat_partner,
-                           an_values, an_partner, workspace, C, A, nT, D, F, Mx, as_stream(stream)};
+  const GridPartnersCall c{head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                           where, m, largest, cat_values, cat_partner, an_values, an_partner, workspace};
   return grid_partners_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
                                mix_cat && mix_an && head_weights && cat_values && cat_partner && an_values && an_partner &&
                                    workspace && (kind == 1 || temperatures),
@@ -914,62 +978,19 @@ int impnn_transfer_head_grid_partners(const float* u_cat, const float* u_an, con
                                       const uint32_t* where, int32_t m, int32_t largest, float* cat_values,
                                       int32_t* cat_partner, float* an_values, int32_t* an_partner, void* workspace,
                                       size_t workspace_bytes, int32_t C, int32_t A, impnn_stream_t stream) {
-  const GridPartnersCall c{1, 1, u_cat, u_an, nullptr, image, where, m, largest, cat_values, cat_partner, an_values,
-                           an_partner, workspace, C, A, 0, 0, 0, 0, as_stream(stream)};
-  return grid_partners_checked(__func__, c, true,
+  const GridPartnersCall c{transfer_grid_operands(u_cat, u_an, image, C, A, stream), where, m, largest, cat_values,
+                           cat_partner, an_values, an_partner, workspace};
+  return grid_partners_checked(__func__, c, image_floats >= 0,
                                u_cat && u_an && image && cat_values && cat_partner && an_values && an_partner && workspace,
                                image_floats, workspace_bytes);
 }
-
-// ---- the rank cut and the best-k pair mask (include/impnn.h; grid_rank.hip).  One place applies the family's rules in
-// their fixed order, one error text each: kind, shape, zero work, null pointers (then alignment and the image size),
-// k < 1, the pair-count limit, the nT limit, the workspace size, the widths.  Nothing is launched before the last.
-namespace {
-int grid_rank_limits(const char* entry, int C, int A, int nT) {
-  if ((int64_t)C * A > kRankMaxPairs)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld pairs (<= 2^32 - 2 per call)", entry, (long long)((int64_t)C * A));
-  if (nT > kSelectMaxT)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
-  return IMPNN_OK;
-}
-
-int grid_rank_checked(const char* entry, const GridRankCall& c, bool widths_ok, bool pointers_ok, int64_t image_floats,
-                      size_t workspace_bytes) {
-  const GridRequest r{entry, c.family, c.kind, c.mix_cat, c.mix_an, c.T, c.w, c.workspace, c.where, false,
-                      c.C, c.A, c.nT, c.D, c.F, c.Mx};
-  if (int rc = grid_request_kind(r, widths_ok, image_floats)) return rc;
-  if (c.C < 0 || c.A < 0 || c.nT < 0 || c.workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
-  if (c.C == 0 || c.A == 0) return IMPNN_OK;
-  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
-  if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
-  if ((reinterpret_cast<uintptr_t>(c.workspace) & 7u) != 0 || (reinterpret_cast<uintptr_t>(c.count) & 7u) != 0)
-    return fail(IMPNN_E_BADARG, "%s: the workspace and the counts must be 8-byte aligned", entry);
-  if (((reinterpret_cast<uintptr_t>(c.where) | reinterpret_cast<uintptr_t>(c.mask_words)) & 3u) != 0)
-    return fail(IMPNN_E_BADARG, "%s: the masks must be 4-byte aligned", entry);
-  if (c.family == 1) {
-    if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
-      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
-    if (image_floats < transfer_grid_image_floats())
-      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
-                  (long long)transfer_grid_image_floats());
-  }
-  if (c.k < 1) return fail(IMPNN_E_BADARG, "%s: k=%lld must be at least 1", entry, (long long)c.k);
-  if (int rc = grid_rank_limits(entry, c.C, c.A, c.nT)) return rc;
-  const size_t need = grid_rank_workspace_bytes(c.family, c.C, c.A, c.nT, c.workgroups);
-  if (workspace_bytes < need)
-    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", entry, workspace_bytes, need);
-  if (c.family == 0)
-    if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
-  return launch_grid_rank(c);
-}
-}  // namespace
 
 int32_t impnn_grid_rank_digit_bits(void) { return kRankDigitBits; }
 
 int32_t impnn_grid_rank_passes(int32_t C, int32_t A) { return C < 0 || A < 0 ? 0 : grid_rank_passes((int64_t)C * A); }
 
 int impnn_grid_rank_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t nT, int32_t workgroups, size_t* need) {
-  if (family != 0 && family != 1) return fail(IMPNN_E_BADARG, "%s: family must be 0 (head grid) or 1 (transfer grid)", __func__);
+  if (int rc = grid_family_rule(__func__, family)) return rc;
   if (C < 0 || A < 0 || nT < 0 || workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", __func__);
   REQUIRE(need, "null pointer");
   if (int rc = grid_rank_limits(__func__, C, A, nT)) return rc;
@@ -982,8 +1003,8 @@ int impnn_head_grid_rank(int32_t kind, const float* mix_cat, const float* mix_an
                          int32_t* cation, int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
                          size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F, int32_t Mx,
                          int32_t workgroups, impnn_stream_t stream) {
-  const GridRankCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, k, largest, where, values, cation, anion,
-                       count, mask_words, workspace, C, A, nT, D, F, Mx, workgroups, as_stream(stream)};
+  const GridRankCall c{head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                       k, largest, where, values, cation, anion, count, mask_words, workspace, workgroups};
   return grid_rank_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
                            mix_cat && mix_an && head_weights && values && cation && anion && count && workspace &&
                                (kind == 1 || temperatures),
@@ -994,56 +1015,27 @@ int impnn_transfer_head_grid_rank(const float* u_cat, const float* u_an, const f
                                   int64_t k, int32_t largest, const uint32_t* where, float* values, int32_t* cation,
                                   int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
                                   size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream) {
-  const GridRankCall c{1, 1, u_cat, u_an, nullptr, image, k, largest, where, values, cation, anion, count, mask_words,
-                       workspace, C, A, 0, 0, 0, 0, workgroups, as_stream(stream)};
-  return grid_rank_checked(__func__, c, true, u_cat && u_an && image && values && cation && anion && count && workspace,
-                           image_floats, workspace_bytes);
+  const GridRankCall c{transfer_grid_operands(u_cat, u_an, image, C, A, stream), k, largest, where, values, cation, anion,
+                       count, mask_words, workspace, workgroups};
+  return grid_rank_checked(__func__, c, image_floats >= 0,
+                           u_cat && u_an && image && values && cation && anion && count && workspace, image_floats,
+                           workspace_bytes);
 }
-
-// ---- pair masks (include/impnn.h; grid_mask.hip).  One place applies the family's rules in their fixed order: shape
-// (a NaN bound included), zero work, null pointers, alignment and the image size, the limits of one launch.
-namespace {
-int grid_mask_checked(const char* entry, const GridMaskCall& c, bool shape_ok, bool pointers_ok, int64_t image_floats) {
-  if (c.family == 0 && c.kind != 0 && c.kind != 1)
-    return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", entry);
-  if (!shape_ok || c.C < 0 || c.A < 0 || c.nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
-  if (c.family == 0 && c.kind == 0 && c.nT < 1) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
-  if (c.family == 0 && c.kind == 1 && c.nT > 0)
-    return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", entry);
-  if (c.lo != c.lo || c.hi != c.hi) return fail(IMPNN_E_BADARG, "%s: a bound is NaN (an infinity means no limit)", entry);
-  if (c.C == 0 || c.A == 0) return IMPNN_OK;
-  if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
-  if (c.family == 0 && c.kind == 1 && c.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
-  if ((reinterpret_cast<uintptr_t>(c.words) & 3u) != 0) return fail(IMPNN_E_BADARG, "%s: the mask must be 4-byte aligned", entry);
-  if (c.family == 1) {
-    if (!(aligned16(c.mix_cat) && aligned16(c.mix_an) && aligned16(c.w)))
-      return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
-    if (image_floats < transfer_grid_image_floats())
-      return fail(IMPNN_E_WORKSPACE, "%s: image of %lld floats is too small (%lld)", entry, (long long)image_floats,
-                  (long long)transfer_grid_image_floats());
-  } else {
-    if (int rc = head_widths_covered(entry, c.D, c.F, c.Mx)) return rc;
-    if (c.nT > head_grid_max_temperatures())
-      return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, c.nT, head_grid_max_temperatures());
-  }
-  return launch_grid_mask(c);
-}
-}  // namespace
 
 int64_t impnn_grid_mask_row_words(int32_t A) { return grid_mask_row_words(A); }
 
 int impnn_head_grid_mask(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
                          const float* head_weights, float lo, float hi, uint32_t* words, int32_t C, int32_t A,
                          int32_t nT, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
-  const GridMaskCall c{0, kind, mix_cat, mix_an, temperatures, head_weights, lo, hi, words, C, A, nT, D, F, Mx,
-                       as_stream(stream)};
+  const GridMaskCall c{head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                       lo, hi, words};
   return grid_mask_checked(__func__, c, D > 0 && F > 0 && Mx > 0,
                            mix_cat && mix_an && head_weights && words && (kind == 1 || temperatures), 0);
 }
 
 int impnn_transfer_head_grid_mask(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
                                   float lo, float hi, uint32_t* words, int32_t C, int32_t A, impnn_stream_t stream) {
-  const GridMaskCall c{1, 1, u_cat, u_an, nullptr, image, lo, hi, words, C, A, 0, 0, 0, 0, as_stream(stream)};
+  const GridMaskCall c{transfer_grid_operands(u_cat, u_an, image, C, A, stream), lo, hi, words};
   return grid_mask_checked(__func__, c, image_floats >= 0, u_cat && u_an && image && words, image_floats);
 }
 

@@ -281,8 +281,17 @@ int launch_validate_indices(const int32_t* conn, const int32_t* atom_ids, const 
 int launch_head_ion_mix(int kind, int ion, const float* pooled, const float* w, float* mix, int M, int D, int F, int Mx,
                         hipStream_t s);
 int head_grid_max_temperatures();
-int launch_head_grid(int kind, const float* mix_cat, const float* mix_an, const float* T, const float* w, float* out,
-                     float* params, int C, int A, int nT, int D, int F, int Mx, hipStream_t s);
+
+// The operands every grid launch shares (api.hip builds and checks them).  family 0: the head grid (`kind`, mixing
+// rows, T, the packed head of impnn_model_head in `w`); family 1: the transfer grid (u rows in mix_cat / mix_an, the
+// prepared image in `w`; kind 1, no T, no widths).
+struct GridOperands {
+  int family, kind;
+  const float *mix_cat, *mix_an, *T, *w;
+  int C, A, nT, D, F, Mx;
+  hipStream_t stream;
+};
+int launch_head_grid(const GridOperands& g, float* out, float* params);
 
 // ---- the transfer head over a cation x anion grid (transfer_grid.hip; include/impnn.h, impnn_transfer_grid_prepare /
 // impnn_transfer_ion_half / impnn_transfer_head_grid).  api.hip checks the arguments; `weights`: kThTensors pointers.
@@ -291,40 +300,33 @@ int launch_transfer_grid_prepare(const float* const* weights, const float* movin
                                  float bn_eps, float* image, hipStream_t s);
 int launch_transfer_ion_half(int ion, const float* pooled, const float* const* weights, float* u, int M, int D, int F,
                              int Mx, hipStream_t s);
-int launch_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, float* out, int C, int A,
-                              hipStream_t s);
+int launch_transfer_head_grid(const GridOperands& g, float* out);
 
 // ---- top-k selection over a cation x anion grid (grid_select.hip; include/impnn.h, impnn_head_grid_topk /
 // impnn_transfer_head_grid_topk).  The limits of one selecting launch (ops.py mirrors them):
 constexpr int kSelectMaxK = 1024;  // entries kept per temperature: one head_grid tile's worth
 constexpr int kSelectMaxT = 4;     // temperatures: 16 KiB of LDS each beside the tile's regions
-// One selecting launch.  family 0: the head grid (`kind`, mixing rows, T, the packed head `w`); family 1: the transfer
-// grid (u rows in mix_cat / mix_an, the image in w).  api.hip checks the arguments.
+// One selecting launch.  api.hip checks the arguments.
 struct GridTopkCall {
-  int family, kind;
-  const float *mix_cat, *mix_an, *T, *w;
+  GridOperands g;
   int k, largest;
   float* values;
   int32_t *cation, *anion;
   void* workspace;
-  int C, A, nT, D, F, Mx, workgroups;
-  hipStream_t stream;
-  bool masked = false;              // the _where entries: only pairs whose bit of `where` is set compete
-  const uint32_t* where = nullptr;  // (C, ceil(A / 32)) words
+  int workgroups;
+  bool masked;            // the _where entries: only pairs whose bit of `where` is set compete
+  const uint32_t* where;  // (C, ceil(A / 32)) words
 };
 int grid_topk_workgroups(int family, int C, int A, int workgroups);  // 0: the default; capped by the tile count
 size_t grid_topk_workspace_bytes(int family, int C, int A, int nT, int k, int workgroups);
 int launch_grid_topk(const GridTopkCall& c);
 
 // ---- pair masks (grid_mask.hip; include/impnn.h, impnn_head_grid_mask / impnn_transfer_head_grid_mask).  One
-// mask-writing launch: family and operands as GridTopkCall; bit (i, j) = lo <= prediction <= hi.  api.hip checks it.
+// mask-writing launch: bit (i, j) = lo <= prediction <= hi.  api.hip checks it.
 struct GridMaskCall {
-  int family, kind;
-  const float *mix_cat, *mix_an, *T, *w;
+  GridOperands g;
   float lo, hi;
   uint32_t* words;  // (C, W), viscosity (nT, C, W); W = grid_mask_row_words(A)
-  int C, A, nT, D, F, Mx;
-  hipStream_t stream;
 };
 int64_t grid_mask_row_words(int A);
 int launch_grid_mask(const GridMaskCall& c);
@@ -333,10 +335,9 @@ int launch_grid_mask(const GridMaskCall& c);
 // impnn_head_grid_partners / impnn_transfer_head_grid_partners).  The limits of one launch (ops.py mirrors them): m, at
 // most kSelectMaxT temperatures, C * A < 2^32.
 constexpr int kPartnersMaxM = 8;  // partners kept per ion: a tile column's running best lives in registers
-// One partner-selecting launch: family and operands as GridTopkCall; `where` may be null.  api.hip checks it.
+// One partner-selecting launch: `where` may be null.  api.hip checks it.
 struct GridPartnersCall {
-  int family, kind;
-  const float *mix_cat, *mix_an, *T, *w;
+  GridOperands g;
   const uint32_t* where;  // (C, ceil(A / 32)) words, or null: every pair competes
   int m, largest;
   float* cat_values;     // [max(nT,1)][C][m]
@@ -344,8 +345,6 @@ struct GridPartnersCall {
   float* an_values;      // [max(nT,1)][A][m]
   int32_t* an_partner;   // cation indices
   void* workspace;
-  int C, A, nT, D, F, Mx;
-  hipStream_t stream;
 };
 size_t grid_partners_workspace_bytes(int family, int C, int A, int nT, int m);
 int launch_grid_partners(const GridPartnersCall& c);
@@ -356,10 +355,9 @@ int launch_grid_partners(const GridPartnersCall& c);
 constexpr int kRankDigitBits = 8;
 constexpr int kRankBins = 1 << kRankDigitBits;
 constexpr int64_t kRankMaxPairs = ((int64_t)1 << 32) - 2;  // the entry format: a pair index stays below 2^32 - 1
-// One call: family and operands as GridTopkCall; `where` and `mask_words` may be null.  api.hip checks it.
+// One call: `where` and `mask_words` may be null.  api.hip checks it.
 struct GridRankCall {
-  int family, kind;
-  const float *mix_cat, *mix_an, *T, *w;
+  GridOperands g;
   int64_t k;
   int largest;
   const uint32_t* where;  // (C, ceil(A / 32)) words, or null: every pair competes
@@ -368,8 +366,7 @@ struct GridRankCall {
   int64_t* count;
   uint32_t* mask_words;   // (C, W), viscosity (nT, C, W), or null: the rank cut alone
   void* workspace;
-  int C, A, nT, D, F, Mx, workgroups;
-  hipStream_t stream;
+  int workgroups;
 };
 int grid_rank_passes(int64_t pairs);  // 4 key digits + the digits that hold pairs - 1
 int grid_rank_workgroups(int family, int C, int A, int workgroups);  // 0: the default; capped by the tile count

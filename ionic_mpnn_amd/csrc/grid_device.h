@@ -5,7 +5,7 @@
 // impnn_head_grid_partners, impnn_transfer_head_grid_partners) and the rank-cut kernels (grid_rank.hip:
 // impnn_head_grid_rank, impnn_transfer_head_grid_rank) all run, and the keys and the running top-k of the selection.
 // One definition of a tile's arithmetic, so a selected or tested value has the bits the materialised grid holds for
-// that pair.
+// that pair; and, at the end, the one host function that launches them (launch_grid_family).
 #pragma once
 
 #include "common.h"
@@ -1047,5 +1047,57 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
   if constexpr (Form::rank_count) rank_finish(sel..., sm + kTgLdsFloats, 1);
 }
 
+// ================================================================ host side: the tile geometry and the one launcher
+// Tiles along C, tiles along A and the tile's size for a family (0: head grid, 1: transfer grid).
+struct GridTiles {
+  int tile_c, tile_a, c, a;
+  int64_t count() const { return (int64_t)c * a; }
+};
+inline GridTiles grid_tiles(int family, int C, int A) {
+  const int tc = family == 0 ? kTileC : kTgTileC, ta = family == 0 ? kTileA : kTgTileA;
+  return {tc, ta, (C + tc - 1) / tc, (A + ta - 1) / ta};
+}
+// a workgroup per tile (the materialising and the mask-writing launches): the tiles must fit one launch
+inline int grid_tiles_fit(const char* what, const GridTiles& t) {
+  if (t.count() > 0x7fffffff)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: %lld tiles of %d x %d pairs exceed one launch; split the cation axis", what,
+                (long long)t.count(), t.tile_c, t.tile_a);
+  return IMPNN_OK;
+}
+
+// Every launch of head_grid_kernel / transfer_grid_kernel: `groups` workgroups, `extra_lds` bytes of dynamic LDS behind
+// the tile's own, the trailing pack of the form (none: the materialising form, which alone takes out / params).  The
+// kernel is picked here: kind 0 -> <0, 0>, kind 1 -> <1, 32> up to Mx = 32, else <1, 64>.  A request above 48 KiB
+// raises the kernel's dynamic-LDS limit first.  FAMILY is a template argument so that a translation unit instantiates
+// the kernels of the families it launches and no others.
+template <int FAMILY, class... Sel>
+void launch_grid_family(const GridOperands& g, unsigned groups, size_t extra_lds, float* out, float* params, Sel... sel) {
+  const int tiles_a = grid_tiles(FAMILY, g.C, g.A).a;
+  auto launch = [&](auto kern, size_t lds, auto... args) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kern<<<groups, 256, lds, g.stream>>>(args..., tiles_a, sel...);
+  };
+  if constexpr (FAMILY == 1) {
+    launch(transfer_grid_kernel<Sel...>, sizeof(float) * kTgLdsFloats + extra_lds, g.mix_cat, g.mix_an, g.w, out, g.C, g.A);
+  } else {
+    const float* tail = g.w + 2 * ((size_t)g.D * g.F + g.F) + 2 * ((size_t)g.F * g.Mx + g.Mx);  // behind the per-ion parts
+    const size_t lds = sizeof(float) * grid_lds_floats(g.kind, g.nT, g.F, g.Mx) + extra_lds;
+    auto head = [&](auto kern) { launch(kern, lds, g.mix_cat, g.mix_an, g.T, tail, out, params, g.C, g.A, g.nT, g.F, g.Mx); };
+    if (g.kind == 0)
+      head(head_grid_kernel<0, 0, Sel...>);
+    else if (g.Mx <= 32)
+      head(head_grid_kernel<1, 32, Sel...>);
+    else
+      head(head_grid_kernel<1, 64, Sel...>);
+  }
+}
+// the selecting, mask-writing, partner and rank forms: either family, no output of the grid itself
+template <class Sel>
+void launch_grid_kernel(const GridOperands& g, unsigned groups, size_t extra_lds, const Sel& sel) {
+  if (g.family == 0)
+    launch_grid_family<0>(g, groups, extra_lds, nullptr, nullptr, sel);
+  else
+    launch_grid_family<1>(g, groups, extra_lds, nullptr, nullptr, sel);
+}
 
 }  // namespace impnn

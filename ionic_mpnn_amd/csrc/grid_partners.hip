@@ -51,64 +51,32 @@ __global__ __launch_bounds__(256) void grid_partners_merge_kernel(const unsigned
     }
 }
 
-void tiles_of(int family, int C, int A, int* tiles_c, int* tiles_a) {
-  const int tc = family == 0 ? kTileC : kTgTileC, ta = family == 0 ? kTileA : kTgTileA;
-  *tiles_c = (C + tc - 1) / tc;
-  *tiles_a = (A + ta - 1) / ta;
-}
-
 }  // namespace
 
 size_t grid_partners_workspace_bytes(int family, int C, int A, int nT, int m) {
-  int tiles_c, tiles_a;
-  tiles_of(family, C, A, &tiles_c, &tiles_a);
-  return sizeof(unsigned long long) * (size_t)(nT > 0 ? nT : 1) * m * ((size_t)tiles_a * C + (size_t)tiles_c * A);
+  const GridTiles tiles = grid_tiles(family, C, A);
+  return sizeof(unsigned long long) * (size_t)(nT > 0 ? nT : 1) * m * ((size_t)tiles.a * C + (size_t)tiles.c * A);
 }
 
 int launch_grid_partners(const GridPartnersCall& c) {
-  int tiles_c, tiles_a;
-  tiles_of(c.family, c.C, c.A, &tiles_c, &tiles_a);
-  const int tiles = tiles_c * tiles_a;  // < 2^32 / 256 + 2^27: C * A < 2^32
-  const int nT = c.nT > 0 ? c.nT : 1;
+  const GridOperands& g = c.g;
+  const GridTiles tiles = grid_tiles(g.family, g.C, g.A);  // < 2^32 / 256 + 2^27 of them: C * A < 2^32
+  const int nT = g.nT > 0 ? g.nT : 1;
   unsigned long long* rows = static_cast<unsigned long long*>(c.workspace);
-  unsigned long long* cols = rows + (size_t)nT * tiles_a * c.C * c.m;
+  unsigned long long* cols = rows + (size_t)nT * tiles.a * g.C * c.m;
   const GridPartners sel{rows, cols, c.m, c.largest};
-  GridPartnersWhere selw;
-  static_cast<GridPartners&>(selw) = sel;
-  selw.where = c.where, selw.W = mask_row_words(c.A);
-  const size_t where_lds = c.where ? sizeof(uint32_t) * kWhereTileWords : 0;  // the tile's mask words, behind its regions
-  if (c.family == 0) {
-    const float* tail = c.w + 2 * ((size_t)c.D * c.F + c.F) + 2 * ((size_t)c.F * c.Mx + c.Mx);
-    const size_t lds = sizeof(float) * grid_lds_floats(c.kind, c.nT, c.F, c.Mx) + where_lds;  // as impnn_head_grid
-#define IMPNN_PARTNERS_AS(KIND, MXR, PACK, pack)                                                                      \
-  head_grid_kernel<KIND, MXR, PACK><<<tiles, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr, c.C, \
-                                                                   c.A, c.nT, c.F, c.Mx, tiles_a, pack)
-#define IMPNN_PARTNERS(KIND, MXR)                                                                                     \
-  do {                                                                                                                \
-    if (c.where)                                                                                                      \
-      IMPNN_PARTNERS_AS(KIND, MXR, GridPartnersWhere, selw);                                                          \
-    else                                                                                                              \
-      IMPNN_PARTNERS_AS(KIND, MXR, GridPartners, sel);                                                                \
-  } while (0)
-    if (c.kind == 0)
-      IMPNN_PARTNERS(0, 0);
-    else if (c.Mx <= 32)
-      IMPNN_PARTNERS(1, 32);
-    else
-      IMPNN_PARTNERS(1, 64);
-#undef IMPNN_PARTNERS
-#undef IMPNN_PARTNERS_AS
+  if (c.where) {  // the tile's mask words sit behind its regions
+    GridPartnersWhere selw;
+    static_cast<GridPartners&>(selw) = sel;
+    selw.where = c.where, selw.W = mask_row_words(g.A);
+    launch_grid_kernel(g, (unsigned)tiles.count(), sizeof(uint32_t) * kWhereTileWords, selw);
   } else {
-    const size_t lds = sizeof(float) * kTgLdsFloats + where_lds;
-    if (c.where)
-      transfer_grid_kernel<GridPartnersWhere><<<tiles, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, selw);
-    else
-      transfer_grid_kernel<GridPartners><<<tiles, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, sel);
+    launch_grid_kernel(g, (unsigned)tiles.count(), 0, sel);
   }
-  if (int rc = check_launch(c.family == 0 ? "head_grid_partners" : "transfer_head_grid_partners")) return rc;
-  const int64_t ions = (int64_t)nT * ((int64_t)c.C + c.A);
-  grid_partners_merge_kernel<<<(unsigned)((ions + 255) / 256), 256, 0, c.stream>>>(
-      rows, cols, tiles_a, tiles_c, c.C, c.A, nT, c.m, c.largest, c.cat_values, c.cat_partner, c.an_values, c.an_partner);
+  if (int rc = check_launch(g.family == 0 ? "head_grid_partners" : "transfer_head_grid_partners")) return rc;
+  const int64_t ions = (int64_t)nT * ((int64_t)g.C + g.A);
+  grid_partners_merge_kernel<<<(unsigned)((ions + 255) / 256), 256, 0, g.stream>>>(
+      rows, cols, tiles.a, tiles.c, g.C, g.A, nT, c.m, c.largest, c.cat_values, c.cat_partner, c.an_values, c.an_partner);
   return check_launch("grid_partners_merge");
 }
 

@@ -72,12 +72,6 @@ __global__ __launch_bounds__(kRankBins) void grid_rank_step_kernel(const uint32_
   }
 }
 
-int64_t tiles_of(int family, int C, int A, int* tiles_a) {
-  const int tc = family == 0 ? kTileC : kTgTileC, ta = family == 0 ? kTileA : kTgTileA;
-  *tiles_a = (A + ta - 1) / ta;
-  return (int64_t)((C + tc - 1) / tc) * *tiles_a;
-}
-
 }  // namespace
 
 int grid_rank_passes(int64_t pairs) {
@@ -87,8 +81,7 @@ int grid_rank_passes(int64_t pairs) {
 }
 
 int grid_rank_workgroups(int family, int C, int A, int workgroups) {
-  int tiles_a;
-  const int64_t tiles = tiles_of(family, C, A, &tiles_a);
+  const int64_t tiles = grid_tiles(family, C, A).count();
   const int64_t want = workgroups > 0 ? workgroups : kRankGroups;
   return (int)(want < tiles ? want : tiles);
 }
@@ -100,53 +93,33 @@ size_t grid_rank_workspace_bytes(int family, int C, int A, int nT, int workgroup
 }
 
 int launch_grid_rank(const GridRankCall& c) {
-  int tiles_a;
-  const int64_t tiles = tiles_of(c.family, c.C, c.A, &tiles_a);  // < 2^32 / 256 + 2^27: C * A < 2^32
-  const int G = grid_rank_workgroups(c.family, c.C, c.A, c.workgroups);
-  const int planes = c.nT > 0 ? c.nT : 1;
-  const int W = mask_row_words(c.A);
+  const GridOperands& g = c.g;
+  const int64_t tiles = grid_tiles(g.family, g.C, g.A).count();  // < 2^32 / 256 + 2^27: C * A < 2^32
+  const int G = grid_rank_workgroups(g.family, g.C, g.A, c.workgroups);
+  const int planes = g.nT > 0 ? g.nT : 1;
+  const int W = mask_row_words(g.A);
   RankState* state = static_cast<RankState*>(c.workspace);
   uint32_t* hist = reinterpret_cast<uint32_t*>(state + planes);
   const size_t where_lds = c.where ? sizeof(uint32_t) * kWhereTileWords : 0;  // the tile's mask words, behind the histogram
-  const float* tail = c.family == 0 ? c.w + 2 * ((size_t)c.D * c.F + c.F) + 2 * ((size_t)c.F * c.Mx + c.Mx) : nullptr;
-  const size_t tile_lds = sizeof(float) * (c.family == 0 ? grid_lds_floats(c.kind, c.nT, c.F, c.Mx) : (size_t)kTgLdsFloats);
-  const char* what = c.family == 0 ? "head_grid_rank" : "transfer_head_grid_rank";
-
-  // PACK is GridRank (G persistent workgroups) or GridMaskRank (a workgroup per tile)
-#define IMPNN_RANK_LAUNCH(PACK, pack, groups, lds)                                                                    \
-  do {                                                                                                                \
-    if (c.family == 1)                                                                                                \
-      transfer_grid_kernel<PACK><<<groups, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, pack); \
-    else if (c.kind == 0)                                                                                             \
-      head_grid_kernel<0, 0, PACK><<<groups, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr, c.C, \
-                                                                   c.A, c.nT, c.F, c.Mx, tiles_a, pack);              \
-    else if (c.Mx <= 32)                                                                                              \
-      head_grid_kernel<1, 32, PACK><<<groups, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr, c.C, \
-                                                                    c.A, c.nT, c.F, c.Mx, tiles_a, pack);             \
-    else                                                                                                              \
-      head_grid_kernel<1, 64, PACK><<<groups, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr, c.C, \
-                                                                    c.A, c.nT, c.F, c.Mx, tiles_a, pack);             \
-  } while (0)
-
-  const int passes = grid_rank_passes((int64_t)c.C * c.A);
+  const char* what = g.family == 0 ? "head_grid_rank" : "transfer_head_grid_rank";
+  const int passes = grid_rank_passes((int64_t)g.C * g.A);
   const int key_passes = 32 / kRankDigitBits;
   for (int p = 0; p < passes; ++p) {
     // the key's digits from bit 56 down to bit 32, then the index's from its highest non-zero byte down to bit 0
     const int shift = p < key_passes ? 64 - kRankDigitBits * (p + 1) : kRankDigitBits * (passes - 1 - p);
     const GridRank rank{state, hist, c.where, W, shift, c.largest, (unsigned)tiles};
-    IMPNN_RANK_LAUNCH(GridRank, rank, G, tile_lds + rank_lds_bytes(planes) + where_lds);  // <= 47.1 KiB
+    launch_grid_kernel(g, G, rank_lds_bytes(planes) + where_lds, rank);  // G persistent workgroups; <= 47.1 KiB of LDS
     if (int rc = check_launch(what)) return rc;
-    grid_rank_step_kernel<<<planes, kRankBins, 0, c.stream>>>(hist, G, planes, state, shift, p == passes - 1,
-                                                              (unsigned long long)(c.k - 1), c.largest, (uint32_t)c.A,
+    grid_rank_step_kernel<<<planes, kRankBins, 0, g.stream>>>(hist, G, planes, state, shift, p == passes - 1,
+                                                              (unsigned long long)(c.k - 1), c.largest, (uint32_t)g.A,
                                                               c.values, c.cation, c.anion, c.count);
     if (int rc = check_launch("grid_rank_step")) return rc;
   }
   if (c.mask_words) {
     const GridMaskRank mask{c.mask_words, state, c.where, W, c.largest};
-    IMPNN_RANK_LAUNCH(GridMaskRank, mask, (unsigned)tiles, tile_lds + where_lds);
+    launch_grid_kernel(g, (unsigned)tiles, where_lds, mask);  // a workgroup per tile
     if (int rc = check_launch(what)) return rc;
   }
-#undef IMPNN_RANK_LAUNCH
   return IMPNN_OK;
 }
 

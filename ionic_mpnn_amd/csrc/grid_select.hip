@@ -55,22 +55,10 @@ __global__ __launch_bounds__(256) void grid_select_merge_kernel(const unsigned l
   }
 }
 
-int64_t tiles_of(int family, int C, int A, int* tiles_a) {
-  const int tc = family == 0 ? kTileC : kTgTileC, ta = family == 0 ? kTileA : kTgTileA;
-  *tiles_a = (A + ta - 1) / ta;
-  return (int64_t)((C + tc - 1) / tc) * *tiles_a;
-}
-
-template <class Kernel>
-void raise_lds_limit(Kernel kern, size_t lds) {
-  if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
-
 }  // namespace
 
 int grid_topk_workgroups(int family, int C, int A, int workgroups) {
-  int tiles_a;
-  const int64_t tiles = tiles_of(family, C, A, &tiles_a);
+  const int64_t tiles = grid_tiles(family, C, A).count();
   const int64_t want = workgroups > 0 ? workgroups : kSelectGroups;
   return (int)(want < tiles ? want : tiles);
 }
@@ -80,55 +68,27 @@ size_t grid_topk_workspace_bytes(int family, int C, int A, int nT, int k, int wo
 }
 
 int launch_grid_topk(const GridTopkCall& c) {
-  int tiles_a;
-  const int64_t tiles = tiles_of(c.family, c.C, c.A, &tiles_a);  // < 2^32 / 16 + 2^26: C * A < 2^32
-  const int G = grid_topk_workgroups(c.family, c.C, c.A, c.workgroups);
-  const int nT = c.nT > 0 ? c.nT : 1;
-  const int cap = select_capacity(c.k, c.family == 0 ? kTilePairs : kTgTileC * kTgTileA);
+  const GridOperands& g = c.g;
+  const int64_t tiles = grid_tiles(g.family, g.C, g.A).count();  // < 2^32 / 16 + 2^26: C * A < 2^32
+  const int G = grid_topk_workgroups(g.family, g.C, g.A, c.workgroups);
+  const int nT = g.nT > 0 ? g.nT : 1;
+  const int cap = select_capacity(c.k, g.family == 0 ? kTilePairs : kTgTileC * kTgTileA);
   unsigned long long* ws = static_cast<unsigned long long*>(c.workspace);
   const GridSelect sel{ws, c.k, cap, c.largest, (unsigned)tiles};
-  GridSelectWhere selw;
-  static_cast<GridSelect&>(selw) = sel;
-  selw.where = c.where, selw.W = mask_row_words(c.A);
-  const size_t where_lds = c.masked ? sizeof(uint32_t) * kWhereTileWords : 0;  // the tile's mask words, behind the lists
-  const size_t sel_lds = select_lds_bytes(nT, cap) + where_lds;  // <= 64.2 KiB (4 temperatures, k = 1024)
-  if (c.family == 0) {
-    const float* tail = c.w + 2 * ((size_t)c.D * c.F + c.F) + 2 * ((size_t)c.F * c.Mx + c.Mx);
-    const size_t lds = sizeof(float) * grid_lds_floats(c.kind, c.nT, c.F, c.Mx) + sel_lds;  // <= 98.2 KiB
-#define IMPNN_SELECT_AS(KIND, MXR, PACK, pack)                                                                        \
-  do {                                                                                                                \
-    raise_lds_limit(head_grid_kernel<KIND, MXR, PACK>, lds);                                                          \
-    head_grid_kernel<KIND, MXR, PACK><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.T, tail, nullptr, nullptr,    \
-                                                                 c.C, c.A, c.nT, c.F, c.Mx, tiles_a, pack);           \
-  } while (0)
-#define IMPNN_SELECT(KIND, MXR)                                                                                       \
-  do {                                                                                                                \
-    if (c.masked)                                                                                                     \
-      IMPNN_SELECT_AS(KIND, MXR, GridSelectWhere, selw);                                                              \
-    else                                                                                                              \
-      IMPNN_SELECT_AS(KIND, MXR, GridSelect, sel);                                                                    \
-  } while (0)
-    if (c.kind == 0)
-      IMPNN_SELECT(0, 0);
-    else if (c.Mx <= 32)
-      IMPNN_SELECT(1, 32);
-    else
-      IMPNN_SELECT(1, 64);
-#undef IMPNN_SELECT
-#undef IMPNN_SELECT_AS
+  // behind the tile's regions: the lists, <= 64.2 KiB (4 temperatures, k = 1024), then the tile's mask words; with the
+  // tile <= 98.2 KiB (head grid), 59.5 KiB (transfer grid): the launcher raises the kernel's dynamic-LDS limit
+  const size_t sel_lds = select_lds_bytes(nT, cap);
+  if (c.masked) {
+    GridSelectWhere selw;
+    static_cast<GridSelect&>(selw) = sel;
+    selw.where = c.where, selw.W = mask_row_words(g.A);
+    launch_grid_kernel(g, G, sel_lds + sizeof(uint32_t) * kWhereTileWords, selw);
   } else {
-    const size_t lds = sizeof(float) * kTgLdsFloats + sel_lds;  // <= 59.5 KiB
-    if (c.masked) {
-      raise_lds_limit(transfer_grid_kernel<GridSelectWhere>, lds);
-      transfer_grid_kernel<GridSelectWhere><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, selw);
-    } else {
-      raise_lds_limit(transfer_grid_kernel<GridSelect>, lds);
-      transfer_grid_kernel<GridSelect><<<G, 256, lds, c.stream>>>(c.mix_cat, c.mix_an, c.w, nullptr, c.C, c.A, tiles_a, sel);
-    }
+    launch_grid_kernel(g, G, sel_lds, sel);
   }
-  if (int rc = check_launch(c.family == 0 ? "head_grid_topk" : "transfer_head_grid_topk")) return rc;
+  if (int rc = check_launch(g.family == 0 ? "head_grid_topk" : "transfer_head_grid_topk")) return rc;
   const int mcap = select_capacity(c.k, kMergeRound);
-  grid_select_merge_kernel<<<nT, 256, select_lds_bytes(1, mcap), c.stream>>>(ws, G, nT, c.k, mcap, c.largest, (uint32_t)c.A,
+  grid_select_merge_kernel<<<nT, 256, select_lds_bytes(1, mcap), g.stream>>>(ws, G, nT, c.k, mcap, c.largest, (uint32_t)g.A,
                                                                            c.values, c.cation, c.anion);
   return check_launch("grid_select_merge");
 }

@@ -58,21 +58,10 @@ int launch_head_ion_mix(int kind, int ion, const float* pooled, const float* w, 
 
 int head_grid_max_temperatures() { return kGridMaxT; }
 
-int launch_head_grid(int kind, const float* mix_cat, const float* mix_an, const float* T, const float* w, float* out,
-                     float* params, int C, int A, int nT, int D, int F, int Mx, hipStream_t s) {
-  const int tiles_a = (A + kTileA - 1) / kTileA;
-  const int64_t tiles = (int64_t)((C + kTileC - 1) / kTileC) * tiles_a;
-  if (tiles > 0x7fffffff)
-    return fail(IMPNN_E_UNSUPPORTED, "head_grid: %lld tiles of %d x %d pairs exceed one launch; split the cation axis",
-                (long long)tiles, kTileC, kTileA);
-  const float* tail = w + 2 * ((size_t)D * F + F) + 2 * ((size_t)F * Mx + Mx);
-  const size_t lds = sizeof(float) * grid_lds_floats(kind, nT, F, Mx);  // <= 50.0 KiB (kind 0), 41.8 KiB (kind 1)
-  if (kind == 0)
-    head_grid_kernel<0, 0><<<(int)tiles, 256, lds, s>>>(mix_cat, mix_an, T, tail, out, params, C, A, nT, F, Mx, tiles_a);
-  else if (Mx <= 32)
-    head_grid_kernel<1, 32><<<(int)tiles, 256, lds, s>>>(mix_cat, mix_an, T, tail, out, params, C, A, nT, F, Mx, tiles_a);
-  else
-    head_grid_kernel<1, 64><<<(int)tiles, 256, lds, s>>>(mix_cat, mix_an, T, tail, out, params, C, A, nT, F, Mx, tiles_a);
+int launch_head_grid(const GridOperands& g, float* out, float* params) {
+  const GridTiles tiles = grid_tiles(0, g.C, g.A);
+  if (int rc = grid_tiles_fit("head_grid", tiles)) return rc;
+  launch_grid_family<0>(g, (unsigned)tiles.count(), 0, out, params);  // <= 50.0 KiB of LDS (kind 0), 41.8 KiB (kind 1)
   return check_launch("head_grid");
 }
 

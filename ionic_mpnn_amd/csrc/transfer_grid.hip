@@ -114,14 +114,10 @@ int launch_transfer_ion_half(int ion, const float* pooled, const float* const* w
   return check_launch("transfer_ion_half");
 }
 
-int launch_transfer_head_grid(const float* u_cat, const float* u_an, const float* image, float* out, int C, int A,
-                              hipStream_t s) {
-  const int tiles_a = (A + kTgTileA - 1) / kTgTileA;
-  const int64_t tiles = (int64_t)((C + kTgTileC - 1) / kTgTileC) * tiles_a;
-  if (tiles > 0x7fffffff)
-    return fail(IMPNN_E_UNSUPPORTED, "transfer_head_grid: %lld tiles of %d x %d pairs exceed one launch; split the cation axis",
-                (long long)tiles, kTgTileC, kTgTileA);
-  transfer_grid_kernel<<<(int)tiles, 256, sizeof(float) * kTgLdsFloats, s>>>(u_cat, u_an, image, out, C, A, tiles_a);
+int launch_transfer_head_grid(const GridOperands& g, float* out) {
+  const GridTiles tiles = grid_tiles(1, g.C, g.A);
+  if (int rc = grid_tiles_fit("transfer_head_grid", tiles)) return rc;
+  launch_grid_family<1>(g, (unsigned)tiles.count(), 0, out, nullptr);
   return check_launch("transfer_head_grid");
 }
 

@@ -96,6 +96,65 @@ def ion_pair_batches(cations=None, anions=None, batch_size=4096):
     return batches, counts[0], counts[1]
 
 
+class _Screen:
+    """What every screen of ``MPNNModel`` computes after its argument check: the pooled rows of ``encode_ions`` (``pc``,
+    ``pa``), ``C``, ``A``, ``nT`` and ``planes`` (temperature rows: nT, or 1 for a model without temperatures), ``T`` and
+    ``where`` on the device, ``mfma`` (the transfer head's matrix-core grid), ``covered`` (some grid kernel covers the
+    model) and ``operands``: the ``ops.GridOperands`` of the whole grid, or None where the gathered fallback runs or the
+    grid is empty."""
+
+    def __init__(self, model, cations, anions, T, where, batch_size):
+        self.model, self.visc = model, model.kind == "viscosity"
+        self.pc, self.pa = model.encode_ions(cations, anions, batch_size)
+        self.C, self.A, self.nT = int(self.pc.shape[0]), int(self.pa.shape[0]), int(T.numel()) if self.visc else 0
+        self.planes = self.nT if self.visc else 1
+        self.mfma = model._transfer_grid_covers() and model.grid_head_mode == "auto"
+        self.covered = model._grid_kernels_cover() or self.mfma
+        if where is not None and where.words.device != self.pc.device:
+            where = data.PairMask(where.words.to(self.pc.device), where.shape)
+        self.where, self.T, self.operands = where, None, None
+        if self.C > 0 and self.A > 0:
+            self.T = T.to(model.device) if self.visc else None
+            if self.covered:
+                self.operands = model._grid_operands(self.pc, self.pa, self.T, self.mfma)
+
+    def default_pairs(self, select, workspace_per_pair=None):
+        """``max_pairs_per_launch`` where the caller gives none.  A selecting launch: the most its pair index takes,
+        or what keeps its workspace (``workspace_per_pair`` bytes) within 4 bytes per element of GRID_OUTPUT_BUDGET; a
+        materialising one: GRID_OUTPUT_BUDGET elements of output, a gathered one GRID_GATHER_PAIRS at the most."""
+        if select:
+            return SCREEN_MAX_PAIRS if workspace_per_pair is None else min(
+                SCREEN_MAX_PAIRS, max(1, int(4 * GRID_OUTPUT_BUDGET / workspace_per_pair)))
+        pairs = max(1, GRID_OUTPUT_BUDGET // max(min(self.nT, GRID_MAX_TEMPERATURES), 1))
+        return pairs if self.covered else min(pairs, GRID_GATHER_PAIRS)
+
+    def tiles(self, max_pairs_per_launch, select, workspace_per_pair=None):
+        """The host tiling: (lo, hi, t0, t1, operands, where) for every range of cations lo .. hi and of temperature
+        rows t0 .. t1 of one launch - ``select``: a selecting launch (fewer than 2^32 pairs, ops.SELECT_MAX_T
+        temperatures), else a materialising one - with the operands narrowed to the tile (None: the gathered fallback)
+        and the mask's rows lo .. hi (None: no mask).  Nothing for an empty grid."""
+        if self.C == 0 or self.A == 0:
+            return
+        if max_pairs_per_launch is None:
+            max_pairs_per_launch = self.default_pairs(select, workspace_per_pair)
+        step = max(1, min(int(max_pairs_per_launch), SCREEN_MAX_PAIRS if select else 1 << 62) // self.A)
+        t_step = ops.SELECT_MAX_T if select else GRID_MAX_TEMPERATURES
+        for lo in range(0, self.C, step):
+            hi = min(self.C, lo + step)
+            rows = self.operands.rows(lo, hi) if self.operands is not None else None
+            wh = self.where.rows(lo, hi) if self.where is not None else None
+            for t0 in range(0, self.planes, t_step):
+                t1 = min(self.planes, t0 + t_step)
+                yield lo, hi, t0, t1, rows.temperatures(t0, t1) if rows is not None else None, wh
+
+    def grid_tile(self, lo, hi, t0, t1, operands):
+        """The tile (lo, hi, t0, t1, operands) of ``tiles``, materialised on the device: (hi - lo, A[, t1 - t0])."""
+        if operands is not None:
+            return ops.grid_values(operands)
+        with torch.no_grad():
+            return self.model._grid_gathered(self.pc[lo:hi], self.pa, self.T[t0:t1] if self.visc else None)
+
+
 class MPNNModel:
     def __init__(self, kind, atom_vocab_size, bond_vocab_size, atom_dim, bond_dim, fp_size, mixing_size,
                  num_steps, fp_l2, device=None, name=None, dropout_rate=0.0, dropout_seed=None,
@@ -1063,64 +1122,19 @@ class MPNNModel:
         ``max_pairs_per_launch`` tiles the cation axis on the host; the default keeps one launch's output within
         GRID_OUTPUT_BUDGET elements (1 GiB of float32); ``batch_size``: rows per encoder launch.  Widths the head kernels do not cover (fp_size or mixing_size
         above 64) and the transfer model in "gathered" mode evaluate ``self.head`` on gathered tiles of pairs instead."""
-        if self.kind == "viscosity" and temperatures is None:
-            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
         if return_params and self.kind != "viscosity":
             raise ValueError(f"return_params: the {self.kind} model has no VFT parameters")
-        if cations is None or anions is None:
-            raise ValueError("predict_grid needs both cations and anions")
-        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
-            raise ValueError("max_pairs_per_launch must be >= 1")
-        visc = self.kind == "viscosity"
-        T = None
-        if visc:
-            T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
-                np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
-            T = T.to(torch.float32).reshape(-1)
-            if T.numel() == 0:
-                raise ValueError("temperatures must hold at least one value")
-        pc, pa = self.encode_ions(cations, anions, batch_size)
-        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
-        out = np.empty((C, A, nT) if visc else (C, A), np.float32)
-        params = np.empty((C, A, 3), np.float32) if return_params else None
-        if C == 0 or A == 0:
-            return (out, params) if return_params else out
-        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
-        covered = self._grid_kernels_cover() or mfma
-        if max_pairs_per_launch is None:
-            max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
-            if not covered:
-                max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
-        rows = max(1, int(max_pairs_per_launch) // A)
-        with torch.no_grad():
-            if visc:
-                T = T.to(self.device)
-            if mfma:
-                tensors, image = self._head_tensors(), self._transfer_image()
-                mc = ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size)
-                ma = ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size)
-            elif covered:
-                w = self._packed_head()
-                mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
-                ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
-            for lo in range(0, C, rows):
-                hi = min(C, lo + rows)
-                if not covered:
-                    out[lo:hi] = self._grid_gathered(pc[lo:hi], pa, T).cpu().numpy()
-                elif mfma:
-                    out[lo:hi] = ops.transfer_head_grid(mc[lo:hi], ma, image).cpu().numpy()
-                elif not visc:
-                    out[lo:hi] = ops.head_grid(self.kind, mc[lo:hi], ma, None, w, self.fp_size,
-                                               self.mixing_size).cpu().numpy()
-                else:
-                    for t0 in range(0, nT, GRID_MAX_TEMPERATURES):
-                        t1 = min(nT, t0 + GRID_MAX_TEMPERATURES)
-                        got = ops.head_grid(self.kind, mc[lo:hi], ma, T[t0:t1], w, self.fp_size, self.mixing_size,
-                                            return_params=return_params and t0 == 0)
-                        if return_params and t0 == 0:
-                            got, pr = got
-                            params[lo:hi] = pr.cpu().numpy()
-                        out[lo:hi, :, t0:t1] = got.cpu().numpy()
+        T = self._screen_request("predict_grid", cations, anions, temperatures, None, max_pairs_per_launch)
+        s = _Screen(self, cations, anions, T, None, batch_size)
+        out = np.empty((s.C, s.A, s.nT) if s.visc else (s.C, s.A), np.float32)
+        params = np.empty((s.C, s.A, 3), np.float32) if return_params else None
+        for lo, hi, t0, t1, g, _ in s.tiles(max_pairs_per_launch, False):
+            if g is not None and return_params and t0 == 0:
+                tile, pr = ops.grid_values(g, return_params=True)
+                params[lo:hi] = pr.cpu().numpy()
+            else:
+                tile = s.grid_tile(lo, hi, t0, t1, g)
+            (out[lo:hi, :, t0:t1] if s.visc else out[lo:hi])[...] = tile.cpu().numpy()
         return (out, params) if return_params else out
 
     def screen_mask(self, cations, anions, temperatures=None, at_least=None, at_most=None, max_pairs_per_launch=None,
@@ -1145,73 +1159,26 @@ class MPNNModel:
         ``y_mean`` / ``y_std`` first)."""
         if at_least is None and at_most is None:
             raise ValueError("screen_mask needs a bound: at_least, at_most or both")
-        lo = np.float32(-np.inf if at_least is None else at_least)
-        hi = np.float32(np.inf if at_most is None else at_most)
-        if np.isnan(lo) or np.isnan(hi):
+        lo_b = np.float32(-np.inf if at_least is None else at_least)
+        hi_b = np.float32(np.inf if at_most is None else at_most)
+        if np.isnan(lo_b) or np.isnan(hi_b):
             raise ValueError("a screen_mask bound is NaN")
-        if self.kind == "viscosity" and temperatures is None:
-            raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
-        if cations is None or anions is None:
-            raise ValueError("screen_mask needs both cations and anions")
-        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
-            raise ValueError("max_pairs_per_launch must be >= 1")
-        visc = self.kind == "viscosity"
-        T = None
-        if visc:
-            T = temperatures if isinstance(temperatures, torch.Tensor) else torch.from_numpy(
-                np.ascontiguousarray(np.asarray(temperatures, dtype=np.float32)))
-            T = T.to(torch.float32).reshape(-1)
-            if T.numel() == 0:
-                raise ValueError("temperatures must hold at least one value")
-        pc, pa = self.encode_ions(cations, anions, batch_size)
-        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
-        W = data.mask_row_words(A)
-        words = torch.zeros((nT, C, W) if visc else (C, W), dtype=torch.int32, device=self.device)
-        mask = data.PairMask(words, (C, A, nT) if visc else (C, A))
-        if C == 0 or A == 0:
-            return mask
-        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
-        covered = self._grid_kernels_cover() or mfma
-        if max_pairs_per_launch is None:
-            max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
-            if not covered:
-                max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
-        rows = max(1, int(max_pairs_per_launch) // A)
-        with torch.no_grad():
-            if visc:
-                T = T.to(self.device)
-            if mfma:
-                tensors, image = self._head_tensors(), self._transfer_image()
-                mc = ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size)
-                ma = ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size)
-            elif covered:
-                w = self._packed_head()
-                mc = ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size)
-                ma = ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size)
-            for c0 in range(0, C, rows):
-                c1 = min(C, c0 + rows)
-                if not covered:
-                    tile = self._grid_gathered(pc[c0:c1], pa, T).cpu().numpy()
-                    got = data.PairMask.from_bool((tile >= lo) & (tile <= hi), device=self.device).words
-                    if visc:
-                        words[:, c0:c1] = got
-                    else:
-                        words[c0:c1] = got
-                elif mfma:
-                    words[c0:c1] = ops.transfer_head_grid_mask(mc[c0:c1], ma, image, lo, hi)
-                elif not visc:
-                    words[c0:c1] = ops.head_grid_mask(self.kind, mc[c0:c1], ma, None, w, self.fp_size, self.mixing_size,
-                                                      lo, hi)
-                else:
-                    for t0 in range(0, nT, GRID_MAX_TEMPERATURES):
-                        t1 = min(nT, t0 + GRID_MAX_TEMPERATURES)
-                        words[t0:t1, c0:c1] = ops.head_grid_mask(self.kind, mc[c0:c1], ma, T[t0:t1], w, self.fp_size,
-                                                                 self.mixing_size, lo, hi)
-        return mask
+        T = self._screen_request("screen_mask", cations, anions, temperatures, None, max_pairs_per_launch)
+        s = _Screen(self, cations, anions, T, None, batch_size)
+        W = data.mask_row_words(s.A)
+        words = torch.zeros((s.nT, s.C, W) if s.visc else (s.C, W), dtype=torch.int32, device=self.device)
+        for lo, hi, t0, t1, g, _ in s.tiles(max_pairs_per_launch, False):
+            if g is not None:
+                got = ops.grid_mask(g, lo_b, hi_b)
+            else:
+                tile = s.grid_tile(lo, hi, t0, t1, g).cpu().numpy()
+                got = data.PairMask.from_bool((tile >= lo_b) & (tile <= hi_b), device=self.device).words
+            (words[t0:t1, lo:hi] if s.visc else words[lo:hi])[...] = got
+        return data.PairMask(words, (s.C, s.A, s.nT) if s.visc else (s.C, s.A))
 
     def _screen_request(self, what, cations, anions, temperatures, where, max_pairs_per_launch):
-        """The argument rules the selecting screens share (``screen_top_k``, ``screen_best_partners``, ``screen_rank``,
-        ``screen_best_mask``) -> the temperatures as a float32 host tensor (nT), or None for a model without them."""
+        """The argument rules the six screens share (``what``: the screen's name in the messages) -> the temperatures as
+        a float32 host tensor (nT), or None for a model without them."""
         if self.kind == "viscosity" and temperatures is None:
             raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
         if cations is None or anions is None:
@@ -1235,18 +1202,6 @@ class MPNNModel:
         if T.numel() == 0:
             raise ValueError("temperatures must hold at least one value")
         return T
-
-    def _ion_halves(self, pc, pa, mfma):
-        """The per-ion halves of the covered grid kernels -> (cation rows, anion rows, the head's weights as those
-        kernels take them): ``impnn_transfer_ion_half`` rows and the prepared image on the matrix-core path, else
-        ``impnn_head_ion_mix`` rows and the packed head."""
-        if mfma:
-            tensors, image = self._head_tensors(), self._transfer_image()
-            return (ops.transfer_ion_half("cat", pc, tensors, self.fp_size, self.mixing_size),
-                    ops.transfer_ion_half("an", pa, tensors, self.fp_size, self.mixing_size), image)
-        w = self._packed_head()
-        return (ops.head_ion_mix(self.kind, "cat", pc, w, self.fp_size, self.mixing_size),
-                ops.head_ion_mix(self.kind, "an", pa, w, self.fp_size, self.mixing_size), w)
 
     def screen_top_k(self, cations, anions, temperatures=None, k=100, largest=False, max_pairs_per_launch=None,
                      batch_size=4096, where=None):
@@ -1272,87 +1227,40 @@ class MPNNModel:
         k = int(k)
         if k < 1:
             raise ValueError("k must be >= 1")
-        visc = self.kind == "viscosity"
-        pc, pa = self.encode_ions(cations, anions, batch_size)
-        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
-        n_rows = nT if visc else 1
-        if where is not None and where.words.device != pc.device:
-            where = data.PairMask(where.words.to(pc.device), where.shape)
-        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
-        covered = self._grid_kernels_cover() or mfma
-        select = covered and k <= SCREEN_MAX_K
+        s = _Screen(self, cations, anions, T, where, batch_size)
+        A, select = s.A, s.covered and k <= SCREEN_MAX_K
         # the running best of every row: (values, flat index i * A + j as int64), at most k each
-        best = [(np.empty(0, np.float32), np.empty(0, np.int64)) for _ in range(n_rows)]
+        best = [(np.empty(0, np.float32), np.empty(0, np.int64)) for _ in range(s.planes)]
 
         def offer(row, values, flat):
             v, f = np.concatenate([best[row][0], values]), np.concatenate([best[row][1], flat])
             order = data.top_k_order(v, f, k, largest)
             best[row] = (v[order], f[order])
 
-        if C > 0 and A > 0:
-            if max_pairs_per_launch is None:
-                max_pairs_per_launch = SCREEN_MAX_PAIRS if select else max(
-                    1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
-                if not covered:
-                    max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
-            step = max(1, min(int(max_pairs_per_launch), SCREEN_MAX_PAIRS if select else 1 << 62) // A)
-            t_step = ops.SELECT_MAX_T if select else GRID_MAX_TEMPERATURES
-            with torch.no_grad():
-                if visc:
-                    T = T.to(self.device)
-                if covered:
-                    mc, ma, w = self._ion_halves(pc, pa, mfma)
-                    image = w
-                for lo in range(0, C, step):
-                    hi = min(C, lo + step)
-                    for t0 in range(0, n_rows, t_step):
-                        t1 = min(n_rows, t0 + t_step)
-                        Tt = T[t0:t1] if visc else None
-                        if select:
-                            wh = where.rows(lo, hi).words if where is not None else None
-                            if mfma:
-                                got = ops.transfer_head_grid_topk(mc[lo:hi], ma, image, k, largest, where=wh)
-                            else:
-                                got = ops.head_grid_topk(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size,
-                                                         self.mixing_size, k, largest, where=wh)
-                            v, ci, ai = (x.cpu().numpy() for x in got)
-                            for r in range(t1 - t0):
-                                used = ci[r] >= 0
-                                offer(t0 + r, v[r][used], (ci[r][used].astype(np.int64) + lo) * A + ai[r][used])
-                        else:
-                            if not covered:
-                                tile = self._grid_gathered(pc[lo:hi], pa, Tt)
-                            elif mfma:
-                                tile = ops.transfer_head_grid(mc[lo:hi], ma, image)
-                            else:
-                                tile = ops.head_grid(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size, self.mixing_size)
-                            tile = tile.cpu().numpy().reshape((hi - lo) * A, -1)
-                            flat = np.arange(lo * A, hi * A, dtype=np.int64)
-                            if where is not None:  # only the mask's pairs reach the order
-                                keep = np.flatnonzero(where.rows(lo, hi).to_bool().reshape(-1))
-                                tile, flat = tile[keep], flat[keep]
-                            for r in range(t1 - t0):
-                                order = data.top_k_order(tile[:, r], flat, k, largest)
-                                offer(t0 + r, tile[order, r], flat[order])
-        m = min(k, C * A if where is None else where.count())
-        values = np.empty((n_rows, m), np.float32)
-        cation, anion = np.empty((n_rows, m), np.int64), np.empty((n_rows, m), np.int64)
+        for lo, hi, t0, t1, g, wh in s.tiles(max_pairs_per_launch, select):
+            if select:
+                v, ci, ai = (x.cpu().numpy() for x in ops.grid_topk(g, k, largest, where=wh.words if wh is not None else None))
+                for r in range(t1 - t0):
+                    used = ci[r] >= 0
+                    offer(t0 + r, v[r][used], (ci[r][used].astype(np.int64) + lo) * A + ai[r][used])
+            else:
+                tile = s.grid_tile(lo, hi, t0, t1, g).cpu().numpy().reshape((hi - lo) * A, -1)
+                flat = np.arange(lo * A, hi * A, dtype=np.int64)
+                if wh is not None:  # only the mask's pairs reach the order
+                    keep = np.flatnonzero(wh.to_bool().reshape(-1))
+                    tile, flat = tile[keep], flat[keep]
+                for r in range(t1 - t0):
+                    order = data.top_k_order(tile[:, r], flat, k, largest)
+                    offer(t0 + r, tile[order, r], flat[order])
+        m = min(k, s.C * A if s.where is None else s.where.count())
+        values = np.empty((s.planes, m), np.float32)
+        cation, anion = np.empty((s.planes, m), np.int64), np.empty((s.planes, m), np.int64)
         for r, (v, f) in enumerate(best):
             values[r], cation[r], anion[r] = v, f // max(A, 1), f % max(A, 1)
         values[np.isnan(values)] = data.QUIET_NAN
-        if not visc:
+        if not s.visc:
             values, cation, anion = values[0], cation[0], anion[0]
         return data.TopK(values, cation, anion)
-
-    def _grid_tile(self, pc, pa, T, halves, mfma):
-        """One host tile of the materialised grid, on the device: rows ``pc`` x all anions (x ``T``); ``halves`` the
-        ``_ion_halves`` of the same rows, or None where the head kernels do not cover the model."""
-        if halves is None:
-            return self._grid_gathered(pc, pa, T)
-        mc, ma, w = halves
-        if mfma:
-            return ops.transfer_head_grid(mc, ma, w)
-        return ops.head_grid(self.kind, mc, ma, T, w, self.fp_size, self.mixing_size)
 
     def screen_best_partners(self, cations, anions, temperatures=None, m=1, largest=False, where=None,
                              max_pairs_per_launch=None, batch_size=4096):
@@ -1375,61 +1283,28 @@ class MPNNModel:
         m = int(m)
         if m < 1:
             raise ValueError("m must be >= 1")
-        visc = self.kind == "viscosity"
-        pc, pa = self.encode_ions(cations, anions, batch_size)
-        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
-        n_rows = nT if visc else 1
-        if where is not None and where.words.device != pc.device:
-            where = data.PairMask(where.words.to(pc.device), where.shape)
-        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
-        covered = self._grid_kernels_cover() or mfma
-        select = covered and m <= ops.PARTNERS_MAX_M
-        cat_v, cat_p = np.full((n_rows, C, m), data.QUIET_NAN, np.float32), np.full((n_rows, C, m), -1, np.int64)
-        an_v, an_p = np.full((n_rows, A, m), data.QUIET_NAN, np.float32), np.full((n_rows, A, m), -1, np.int64)
-        if C > 0 and A > 0:
-            t_step = ops.SELECT_MAX_T if select else GRID_MAX_TEMPERATURES
-            if max_pairs_per_launch is None:
-                if select:  # a launch's workspace: m entries per plane for every tile row and tile column
-                    tc, ta = ops.PARTNERS_TILE[1 if mfma else 0]
-                    per_pair = 8 * m * min(n_rows, t_step) * (1.0 / tc + 1.0 / ta)
-                    max_pairs_per_launch = min(SCREEN_MAX_PAIRS, max(1, int(4 * GRID_OUTPUT_BUDGET / per_pair)))
-                else:
-                    max_pairs_per_launch = max(1, GRID_OUTPUT_BUDGET // max(min(nT, GRID_MAX_TEMPERATURES), 1))
-                    if not covered:
-                        max_pairs_per_launch = min(max_pairs_per_launch, GRID_GATHER_PAIRS)
-            step = max(1, min(int(max_pairs_per_launch), SCREEN_MAX_PAIRS if select else 1 << 62) // A)
-            with torch.no_grad():
-                if visc:
-                    T = T.to(self.device)
-                halves = self._ion_halves(pc, pa, mfma) if covered else None
-                for lo in range(0, C, step):
-                    hi = min(C, lo + step)
-                    wh = where.rows(lo, hi) if where is not None else None
-                    for t0 in range(0, n_rows, t_step):
-                        t1 = min(n_rows, t0 + t_step)
-                        Tt = T[t0:t1] if visc else None
-                        if select:
-                            mc, ma, w = halves
-                            words = wh.words if wh is not None else None
-                            if mfma:
-                                got = ops.transfer_head_grid_partners(mc[lo:hi], ma, w, m, largest, where=words)
-                            else:
-                                got = ops.head_grid_partners(self.kind, mc[lo:hi], ma, Tt, w, self.fp_size,
-                                                             self.mixing_size, m, largest, where=words)
-                            cv, cp, av, ap = (x.cpu().numpy() for x in got)
-                            cp, ap = cp.astype(np.int64), ap.astype(np.int64)
-                        else:
-                            tile = self._grid_tile(pc[lo:hi], pa, Tt, (halves[0][lo:hi],) + halves[1:] if covered else None,
-                                                   mfma).cpu().numpy()
-                            got = data.grid_best_partners(tile, m, largest, where=wh)
-                            (cv, cp), (av, ap) = ((x.reshape((t1 - t0, -1, m)) for x in side) for side in got)
-                        cat_v[t0:t1, lo:hi], cat_p[t0:t1, lo:hi] = cv, cp
-                        ap = np.where(ap >= 0, ap + lo, -1)      # the tile's cations are lo .. hi of the screen
-                        for r in range(t1 - t0):                 # an anion's best so far against this tile's, same order
-                            an_v[t0 + r], an_p[t0 + r] = data.best_of(np.concatenate([an_v[t0 + r], av[r]], axis=1),
-                                                                      np.concatenate([an_p[t0 + r], ap[r]], axis=1), m, largest)
+        s = _Screen(self, cations, anions, T, where, batch_size)
+        select = s.covered and m <= ops.PARTNERS_MAX_M
+        cat_v, cat_p = np.full((s.planes, s.C, m), data.QUIET_NAN, np.float32), np.full((s.planes, s.C, m), -1, np.int64)
+        an_v, an_p = np.full((s.planes, s.A, m), data.QUIET_NAN, np.float32), np.full((s.planes, s.A, m), -1, np.int64)
+        # a selecting launch's workspace: m entries of 8 bytes per plane for every tile row and tile column
+        tc, ta = ops.PARTNERS_TILE[1 if s.mfma else 0]
+        per_pair = 8 * m * min(s.planes, ops.SELECT_MAX_T) * (1.0 / tc + 1.0 / ta)
+        for lo, hi, t0, t1, g, wh in s.tiles(max_pairs_per_launch, select, per_pair):
+            if select:
+                got = ops.grid_partners(g, m, largest, where=wh.words if wh is not None else None)
+                cv, cp, av, ap = (x.cpu().numpy() for x in got)
+                cp, ap = cp.astype(np.int64), ap.astype(np.int64)
+            else:
+                got = data.grid_best_partners(s.grid_tile(lo, hi, t0, t1, g).cpu().numpy(), m, largest, where=wh)
+                (cv, cp), (av, ap) = ((x.reshape((t1 - t0, -1, m)) for x in side) for side in got)
+            cat_v[t0:t1, lo:hi], cat_p[t0:t1, lo:hi] = cv, cp
+            ap = np.where(ap >= 0, ap + lo, -1)      # the tile's cations are lo .. hi of the screen
+            for r in range(t1 - t0):                 # an anion's best so far against this tile's, same order
+                an_v[t0 + r], an_p[t0 + r] = data.best_of(np.concatenate([an_v[t0 + r], av[r]], axis=1),
+                                                          np.concatenate([an_p[t0 + r], ap[r]], axis=1), m, largest)
         by_cation, by_anion = data.Partners(cat_v, cat_p), data.Partners(an_v, an_p)
-        if not visc:
+        if not s.visc:
             by_cation, by_anion = data.Partners(cat_v[0], cat_p[0]), data.Partners(an_v[0], an_p[0])
         return data.BestPartners(by_cation, by_anion)
 
@@ -1442,36 +1317,25 @@ class MPNNModel:
             raise ValueError("k must be >= 1")
         if len(cations["atom"]) * len(anions["atom"]) > ops.RANK_MAX_PAIRS:
             raise ValueError(f"{what}: {len(cations['atom']) * len(anions['atom'])} pairs, a rank cut takes at most 2^32 - 2")
-        visc = self.kind == "viscosity"
-        pc, pa = self.encode_ions(cations, anions, batch_size)
-        C, A, nT = int(pc.shape[0]), int(pa.shape[0]), int(T.numel()) if visc else 0
-        planes = nT if visc else 1
-        if where is not None and where.words.device != pc.device:
-            where = data.PairMask(where.words.to(pc.device), where.shape)
+        s = _Screen(self, cations, anions, T, where, batch_size)
+        C, A, planes = s.C, s.A, s.planes
         values, count = np.full(planes, data.QUIET_NAN, np.float32), np.zeros(planes, np.int64)
         cation, anion = np.full(planes, -1, np.int64), np.full(planes, -1, np.int64)
         words = torch.zeros((planes, C, data.mask_row_words(A)), dtype=torch.int32, device=self.device) if mask else None
-        mfma = self._transfer_grid_covers() and self.grid_head_mode == "auto"
-        if C > 0 and A > 0 and (self._grid_kernels_cover() or mfma):
-            with torch.no_grad():
-                mc, ma, w = self._ion_halves(pc, pa, mfma)
-                wh = where.words if where is not None else None
-                for t0 in range(0, planes, ops.SELECT_MAX_T):
-                    t1 = min(planes, t0 + ops.SELECT_MAX_T)
-                    if mfma:
-                        got = ops.transfer_head_grid_rank(mc, ma, w, k, largest, where=wh, mask=mask)
-                    else:
-                        got = ops.head_grid_rank(self.kind, mc, ma, T[t0:t1].to(self.device) if visc else None, w,
-                                                 self.fp_size, self.mixing_size, k, largest, where=wh, mask=mask)
-                    values[t0:t1], cation[t0:t1], anion[t0:t1], count[t0:t1] = (x.cpu().numpy() for x in got[:4])
-                    if mask:
-                        words[t0:t1] = got[4].reshape(t1 - t0, C, -1)
+        if s.operands is not None:  # the cation axis is not tiled
+            wh = s.where.words if s.where is not None else None
+            for t0 in range(0, planes, ops.SELECT_MAX_T):
+                t1 = min(planes, t0 + ops.SELECT_MAX_T)
+                got = ops.grid_rank(s.operands.temperatures(t0, t1), k, largest, where=wh, mask=mask)
+                values[t0:t1], cation[t0:t1], anion[t0:t1], count[t0:t1] = (x.cpu().numpy() for x in got[:4])
+                if mask:
+                    words[t0:t1] = got[4].reshape(t1 - t0, C, -1)
         elif C > 0 and A > 0:  # the host references on the grid itself
-            tk = {"temperatures": T} if visc else {}
+            tk = {"temperatures": T} if s.visc else {}
             grid = self.predict_grid(cations, anions, batch_size=batch_size, **tk)
-            values[:], cation[:], anion[:], count[:] = data.grid_rank(grid, k, largest, where)
+            values[:], cation[:], anion[:], count[:] = data.grid_rank(grid, k, largest, s.where)
             if mask:
-                best = data.grid_best_mask(grid, k, largest, where)
+                best = data.grid_best_mask(grid, k, largest, s.where)
                 words = data.PairMask.from_bool(best, device=self.device).words.reshape(planes, C, -1)
         return data.RankCut(values, cation, anion, count), words
 
@@ -1513,6 +1377,19 @@ class MPNNModel:
         if self.kind == "viscosity":
             return data.PairMask(words, (C, A, int(words.shape[0])))
         return data.PairMask(words[0], (C, A))
+
+    def _grid_operands(self, pc, pa, T, mfma):
+        """The per-ion halves of the covered grid kernels as the operands of their launches (``ops.GridOperands``):
+        ``impnn_transfer_ion_half`` rows and the prepared image on the matrix-core path, else ``impnn_head_ion_mix``
+        rows, the packed head and the temperatures ``T`` (device, or None)."""
+        fp, mx = self.fp_size, self.mixing_size
+        if mfma:
+            tensors = self._head_tensors()
+            return ops.transfer_grid_operands(ops.transfer_ion_half("cat", pc, tensors, fp, mx),
+                                              ops.transfer_ion_half("an", pa, tensors, fp, mx), self._transfer_image())
+        w = self._packed_head()
+        return ops.head_grid_operands(self.kind, ops.head_ion_mix(self.kind, "cat", pc, w, fp, mx),
+                                      ops.head_ion_mix(self.kind, "an", pa, w, fp, mx), T, w, fp, mx)
 
     def _grid_gathered(self, pc, pa, T):
         """``self.head`` on the explicit pairs of a tile of cations x all anions (x T) -> (c, A[, nT])."""

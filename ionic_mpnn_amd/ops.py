@@ -685,6 +685,11 @@ HEAD_MAX_X = 128    # pooled width (atom_dim)
 HEAD_MAX_DIM = 64   # fp_size, mixing_size
 
 
+def _require_packed_head(head_weights, k, D, fp_size, mixing_size):
+    if D < 1 or head_weights.numel() != _lib.load().impnn_model_head_floats(k, D, fp_size, mixing_size):
+        raise ValueError("packed head weights have the wrong length")
+
+
 def model_head(kind, pooled_cat, pooled_an, temperature, head_weights, fp_size, mixing_size):
     """Everything after GlobalSumPool in one launch (impnn_model_head): kind "viscosity" or "melting_point"."""
     require_gpu(pooled_cat, pooled_an, head_weights)
@@ -692,8 +697,7 @@ def model_head(kind, pooled_cat, pooled_an, temperature, head_weights, fp_size, 
     B, D = pooled_cat.shape
     k = {"viscosity": 0, "melting_point": 1}[kind]
     lib = _lib.load()
-    if head_weights.numel() != lib.impnn_model_head_floats(k, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
+    _require_packed_head(head_weights, k, D, fp_size, mixing_size)
     T = None
     if k == 0:
         require_gpu(temperature)
@@ -721,8 +725,7 @@ def head_ion_mix(kind, ion, pooled, head_weights, fp_size, mixing_size):
     k = HEAD_KINDS[kind]
     g = {"cat": 0, "an": 1, 0: 0, 1: 1}[ion]
     lib = _lib.load()
-    if head_weights.numel() != lib.impnn_model_head_floats(k, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
+    _require_packed_head(head_weights, k, D, fp_size, mixing_size)
     mix = torch.empty(M, mixing_size, dtype=torch.float32, device=pooled.device)
     with torch.cuda.device(pooled.device):
         check(lib.impnn_head_ion_mix(k, g, ptr(pooled), ptr(head_weights), ptr(mix), M, D, fp_size, mixing_size,
@@ -730,45 +733,176 @@ def head_ion_mix(kind, ion, pooled, head_weights, fp_size, mixing_size):
     return mix
 
 
-def head_grid(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, return_params=False):
-    """The head on every cation x anion pair in one launch (impnn_head_grid), from ``head_ion_mix`` rows.
-    "viscosity": temperatures (nT) in kelvin -> (C,A,nT), with return_params also the VFT parameters (C,A,3);
-    "melting_point": temperatures None -> (C,A).  Element (i,j,t) has the bits of ``model_head`` on that sample."""
+# ---- the screening family over a cation x anion grid: the operands are validated once (GridOperands), the five
+# operations (grid_values, grid_topk, grid_partners, grid_rank, grid_mask) take either family's, and the named wrappers
+# below them are "build the operands, call the operation"
+class GridOperands:
+    """The validated operands of the screening family's launches over one cation x anion grid, built by
+    ``head_grid_operands`` (family 0) or ``transfer_grid_operands`` (family 1): the contiguous float32 tensors (``cat``
+    and ``an`` rows, ``T`` or None, ``w``: the packed head or the prepared image), ``kind`` as the C entries take it (0
+    viscosity, 1 melting point and transfer) and, for the head family, ``widths`` = (D, fp_size, mixing_size).  ``lead``
+    and ``trail`` are the arguments every C entry of the family opens and closes with; the operation's own go between.
+    ``rows`` and ``temperatures`` narrow it without validating again (the host tiling of model.py)."""
+    __slots__ = ("family", "kind", "cat", "an", "T", "w", "widths")
+
+    def __init__(self, family, kind, cat, an, T, w, widths=()):
+        self.family, self.kind, self.cat, self.an, self.T, self.w, self.widths = family, kind, cat, an, T, w, widths
+
+    C = property(lambda self: int(self.cat.shape[0]))
+    A = property(lambda self: int(self.an.shape[0]))
+    nT = property(lambda self: int(self.T.numel()) if self.T is not None else 0)
+    D = property(lambda self: self.widths[0] if self.widths else None)
+    device = property(lambda self: self.cat.device)
+
+    @property
+    def lead(self):
+        if self.family == 0:
+            return self.kind, ptr(self.cat), ptr(self.an), ptr(self.T) if self.T is not None else None, ptr(self.w)
+        return ptr(self.cat), ptr(self.an), ptr(self.w), self.w.numel()
+
+    @property
+    def trail(self):
+        return (self.C, self.A, self.nT, *self.widths) if self.family == 0 else (self.C, self.A)
+
+    def rows(self, lo, hi):
+        """Cations lo .. hi of the grid."""
+        return GridOperands(self.family, self.kind, self.cat[lo:hi], self.an, self.T, self.w, self.widths)
+
+    def temperatures(self, t0, t1):
+        """Temperatures t0 .. t1 of a viscosity grid; any other grid as it is."""
+        return self if self.T is None else GridOperands(self.family, self.kind, self.cat, self.an, self.T[t0:t1], self.w,
+                                                        self.widths)
+
+
+def _require_params_kind(return_params, k):
+    if return_params and k != 0:
+        raise ValueError("return_params: only the viscosity head has VFT parameters")
+
+
+def head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, return_params=False):
+    """The arguments of ``head_grid`` and of every screening operation over its product, checked once -> GridOperands.
+    ``return_params``: ``head_grid``'s own argument, checked where it always was, between the rows and the packed head."""
     require_gpu(mix_cat, mix_an, head_weights)
     mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
     k = HEAD_KINDS[kind]
     if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
         raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
                          f"and {tuple(mix_an.shape)}")
-    if return_params and k != 0:
-        raise ValueError("return_params: only the viscosity head has VFT parameters")
-    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    _require_params_kind(return_params, k)
     lib = _lib.load()
     # the packed length depends on D through the per-ion part only: recover D from it
     per_d = 2 * fp_size
     rest = lib.impnn_model_head_floats(k, 1, fp_size, mixing_size) - per_d
     D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
-    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(k, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
-    dev = mix_cat.device
-    T, nT = None, 0
+    _require_packed_head(head_weights, k, D, fp_size, mixing_size)
+    T = None
     if k == 0:
         if temperatures is None:
             raise ValueError("the viscosity grid needs temperatures")
         require_gpu(temperatures)
         T = f32c(temperatures).reshape(-1)
-        nT = int(T.numel())
-        out = torch.empty(C_, A_, nT, dtype=torch.float32, device=dev)
-    else:
-        if temperatures is not None:
-            raise ValueError("the melting-point grid takes no temperatures")
-        out = torch.empty(C_, A_, dtype=torch.float32, device=dev)
-    params = torch.empty(C_, A_, 3, dtype=torch.float32, device=dev) if return_params else None
+    elif temperatures is not None:
+        raise ValueError("the melting-point grid takes no temperatures")
+    return GridOperands(0, k, mix_cat, mix_an, T, head_weights, (D, fp_size, mixing_size))
+
+
+def transfer_grid_operands(u_cat, u_an, image):
+    """The arguments of ``transfer_head_grid`` and of every screening operation over its product, checked once ->
+    GridOperands."""
+    require_gpu(u_cat, u_an, image)
+    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
+    W = TRANSFER_GRID_WIDTH
+    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
+        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
+    if image.dim() != 1 or image.numel() != _lib.load().impnn_transfer_grid_image_floats():
+        raise ValueError("the prepared image has the wrong length")
+    return GridOperands(1, 1, u_cat, u_an, None, image)
+
+
+def grid_values(g, return_params=False):
+    """The materialised grid of ``g`` (impnn_head_grid / impnn_transfer_head_grid): what ``head_grid`` /
+    ``transfer_head_grid`` return for the same operands."""
+    _require_params_kind(return_params, g.kind)
+    dev = g.device
+    out = torch.empty((g.C, g.A, g.nT) if g.kind == 0 else (g.C, g.A), dtype=torch.float32, device=dev)
+    params = torch.empty(g.C, g.A, 3, dtype=torch.float32, device=dev) if return_params else None
+    lib = _lib.load()
     with torch.cuda.device(dev):
-        check(lib.impnn_head_grid(k, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None, ptr(head_weights),
-                                  ptr(out), ptr(params) if params is not None else None, C_, A_, nT, D, fp_size,
-                                  mixing_size, stream_ptr()))
+        if g.family == 0:
+            check(lib.impnn_head_grid(*g.lead, ptr(out), ptr(params) if params is not None else None, *g.trail,
+                                      stream_ptr()))
+        else:
+            check(lib.impnn_transfer_head_grid(*g.lead, ptr(out), *g.trail, stream_ptr()))
     return (out, params) if return_params else out
+
+
+def _grid_entry(g, name):
+    """The C entry ``name`` of g's family: impnn_head_grid_<name> or impnn_transfer_head_grid_<name>."""
+    return getattr(_lib.load(), ("impnn_head_grid_", "impnn_transfer_head_grid_")[g.family] + name)
+
+
+def grid_topk(g, k, largest=False, workgroups=0, where=None):
+    """The k best pairs of ``g``'s grid (impnn_*_grid_topk, with ``where`` impnn_*_grid_topk_where): what
+    ``head_grid_topk`` / ``transfer_head_grid_topk`` return for the same operands."""
+    k, workgroups = int(k), int(workgroups)
+    if where is not None:
+        where = _mask_words(where, g.C, g.A, g.device)
+    with torch.cuda.device(g.device):
+        values, cation, anion, ws, nbytes = _grid_topk_outputs(_lib.load(), g.family, g.C, g.A, g.nT, k, workgroups, g.device)
+        mask = () if where is None else (ptr(where),)
+        check(_grid_entry(g, "topk" if where is None else "topk_where")(
+            *g.lead, *mask, k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, *g.trail,
+            workgroups, stream_ptr()))
+    return values, cation, anion
+
+
+def grid_partners(g, m=1, largest=False, where=None):
+    """Each ion's m best partners over ``g``'s grid (impnn_*_grid_partners): what ``head_grid_partners`` /
+    ``transfer_head_grid_partners`` return for the same operands."""
+    m = int(m)
+    if where is not None:
+        where = _mask_words(where, g.C, g.A, g.device)
+    with torch.cuda.device(g.device):
+        out, ws, nbytes = _grid_partners_outputs(_lib.load(), g.family, g.C, g.A, g.nT, m, g.device)
+        check(_grid_entry(g, "partners")(*g.lead, ptr(where) if where is not None else None, m, int(bool(largest)),
+                                         *[ptr(o) for o in out], ptr(ws), nbytes, *g.trail, stream_ptr()))
+    return tuple(out)
+
+
+def grid_rank(g, k, largest=False, where=None, mask=False, workgroups=0):
+    """The k-th best pair of ``g``'s grid and, with ``mask``, the k best as mask words (impnn_*_grid_rank): what
+    ``head_grid_rank`` / ``transfer_head_grid_rank`` return for the same operands."""
+    k, workgroups = int(k), int(workgroups)
+    if where is not None:
+        where = _mask_words(where, g.C, g.A, g.device)
+    with torch.cuda.device(g.device):
+        out, ws, nbytes = _grid_rank_outputs(_lib.load(), g.family, g.C, g.A, g.nT, workgroups, mask, g.device)
+        check(_grid_entry(g, "rank")(*g.lead, k, int(bool(largest)), ptr(where) if where is not None else None,
+                                     *[ptr(o) if o is not None else None for o in out], ptr(ws), nbytes, *g.trail,
+                                     workgroups, stream_ptr()))
+    return out
+
+
+def grid_mask(g, lo, hi):
+    """``g``'s grid as a packed pair mask (impnn_*_grid_mask): what ``head_grid_mask`` / ``transfer_head_grid_mask``
+    return for the same operands."""
+    lo, hi = C.c_float(lo).value, C.c_float(hi).value  # as the kernels see them: float32
+    if lo != lo or hi != hi:
+        raise ValueError("a mask bound is NaN (an infinity means no limit)")
+    lib = _lib.load()
+    W = int(lib.impnn_grid_mask_row_words(g.A))
+    words = torch.empty((g.nT, g.C, W) if g.kind == 0 else (g.C, W), dtype=torch.int32, device=g.device)
+    with torch.cuda.device(g.device):
+        check(_grid_entry(g, "mask")(*g.lead, lo, hi, ptr(words), *g.trail, stream_ptr()))
+    return words
+
+
+def head_grid(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, return_params=False):
+    """The head on every cation x anion pair in one launch (impnn_head_grid), from ``head_ion_mix`` rows.
+    "viscosity": temperatures (nT) in kelvin -> (C,A,nT), with return_params also the VFT parameters (C,A,3);
+    "melting_point": temperatures None -> (C,A).  Element (i,j,t) has the bits of ``model_head`` on that sample."""
+    return grid_values(head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, return_params),
+                       return_params)
 
 
 TRANSFER_GRID_WIDTH = 256  # mp_dense_1's units: the width of a ``transfer_ion_half`` row
@@ -822,20 +956,7 @@ def transfer_ion_half(ion, pooled, weights, fp_size, mixing_size):
 def transfer_head_grid(u_cat, u_an, image):
     """The transfer head on every cation x anion pair in one launch (impnn_transfer_head_grid), on the matrix cores in
     exact f32: ``transfer_ion_half`` rows (C,256) and (A,256), the image of ``transfer_grid_prepare`` -> (C,A)."""
-    require_gpu(u_cat, u_an, image)
-    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
-    W = TRANSFER_GRID_WIDTH
-    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
-        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
-    lib = _lib.load()
-    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
-        raise ValueError("the prepared image has the wrong length")
-    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
-    out = torch.empty(C_, A_, dtype=torch.float32, device=u_cat.device)
-    with torch.cuda.device(u_cat.device):
-        check(lib.impnn_transfer_head_grid(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), ptr(out), C_, A_,
-                                           stream_ptr()))
-    return out
+    return grid_values(transfer_grid_operands(u_cat, u_an, image))
 
 
 # the limits of one selecting launch: kSelectMaxK / kSelectMaxT of csrc/common.h (tests/test_screen_host.py holds them equal)
@@ -874,74 +995,14 @@ def head_grid_topk(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, m
     bits ``head_grid`` gives for its pair.  k <= SELECT_MAX_K, at most SELECT_MAX_T temperatures, C*A < 2^32.
     ``where``: the (C,W) words of a pair mask (``head_grid_mask``, ``data.PairMask``): only its pairs compete
     (impnn_head_grid_topk_where), slots past their count hold NaN / -1."""
-    require_gpu(mix_cat, mix_an, head_weights)
-    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
-    kd = HEAD_KINDS[kind]
-    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
-        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
-                         f"and {tuple(mix_an.shape)}")
-    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
-    lib = _lib.load()
-    per_d = 2 * fp_size
-    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
-    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
-    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
-    T, nT = None, 0
-    if kd == 0:
-        if temperatures is None:
-            raise ValueError("the viscosity grid needs temperatures")
-        require_gpu(temperatures)
-        T = f32c(temperatures).reshape(-1)
-        nT = int(T.numel())
-    elif temperatures is not None:
-        raise ValueError("the melting-point grid takes no temperatures")
-    dev = mix_cat.device
-    k, workgroups = int(k), int(workgroups)
-    if where is not None:
-        where = _mask_words(where, C_, A_, dev)
-    with torch.cuda.device(dev):
-        values, cation, anion, ws, nbytes = _grid_topk_outputs(lib, 0, C_, A_, nT, k, workgroups, dev)
-        if where is None:
-            check(lib.impnn_head_grid_topk(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
-                                           ptr(head_weights), k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion),
-                                           ptr(ws), nbytes, C_, A_, nT, D, fp_size, mixing_size, workgroups, stream_ptr()))
-        else:
-            check(lib.impnn_head_grid_topk_where(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
-                                                 ptr(head_weights), ptr(where), k, int(bool(largest)), ptr(values),
-                                                 ptr(cation), ptr(anion), ptr(ws), nbytes, C_, A_, nT, D, fp_size,
-                                                 mixing_size, workgroups, stream_ptr()))
-    return values, cation, anion
+    return grid_topk(head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size), k, largest, workgroups, where)
 
 
 def transfer_head_grid_topk(u_cat, u_an, image, k, largest=False, workgroups=0, where=None):
     """The k best pairs of ``transfer_head_grid``'s product without the product (impnn_transfer_head_grid_topk) ->
     values (1,k) float32, cation (1,k), anion (1,k) int32 on the device, as ``head_grid_topk``; ``where`` as there
     (impnn_transfer_head_grid_topk_where)."""
-    require_gpu(u_cat, u_an, image)
-    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
-    W = TRANSFER_GRID_WIDTH
-    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
-        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
-    lib = _lib.load()
-    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
-        raise ValueError("the prepared image has the wrong length")
-    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
-    dev = u_cat.device
-    k, workgroups = int(k), int(workgroups)
-    if where is not None:
-        where = _mask_words(where, C_, A_, dev)
-    with torch.cuda.device(dev):
-        values, cation, anion, ws, nbytes = _grid_topk_outputs(lib, 1, C_, A_, 0, k, workgroups, dev)
-        if where is None:
-            check(lib.impnn_transfer_head_grid_topk(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), k, int(bool(largest)),
-                                                    ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, C_, A_, workgroups,
-                                                    stream_ptr()))
-        else:
-            check(lib.impnn_transfer_head_grid_topk_where(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), ptr(where), k,
-                                                          int(bool(largest)), ptr(values), ptr(cation), ptr(anion), ptr(ws),
-                                                          nbytes, C_, A_, workgroups, stream_ptr()))
-    return values, cation, anion
+    return grid_topk(transfer_grid_operands(u_cat, u_an, image), k, largest, workgroups, where)
 
 
 # the limit of one partner-selecting launch: kPartnersMaxM of csrc/common.h (tests/test_partners_host.py holds them equal)
@@ -968,64 +1029,14 @@ def head_grid_partners(kind, mix_cat, mix_an, temperatures, head_weights, fp_siz
     under the order of ``data.grid_best_partners``; slots past an ion's competing partners hold NaN / -1.  A value has
     the bits ``head_grid`` gives for its pair.  m <= PARTNERS_MAX_M, at most SELECT_MAX_T temperatures, C*A < 2^32.
     ``where``: the (C,W) words of a pair mask (``head_grid_mask``, ``data.PairMask``): only its pairs compete."""
-    require_gpu(mix_cat, mix_an, head_weights)
-    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
-    kd = HEAD_KINDS[kind]
-    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
-        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
-                         f"and {tuple(mix_an.shape)}")
-    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
-    lib = _lib.load()
-    per_d = 2 * fp_size
-    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
-    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
-    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
-    T, nT = None, 0
-    if kd == 0:
-        if temperatures is None:
-            raise ValueError("the viscosity grid needs temperatures")
-        require_gpu(temperatures)
-        T = f32c(temperatures).reshape(-1)
-        nT = int(T.numel())
-    elif temperatures is not None:
-        raise ValueError("the melting-point grid takes no temperatures")
-    dev = mix_cat.device
-    m = int(m)
-    if where is not None:
-        where = _mask_words(where, C_, A_, dev)
-    with torch.cuda.device(dev):
-        out, ws, nbytes = _grid_partners_outputs(lib, 0, C_, A_, nT, m, dev)
-        check(lib.impnn_head_grid_partners(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None,
-                                           ptr(head_weights), ptr(where) if where is not None else None, m,
-                                           int(bool(largest)), *[ptr(o) for o in out], ptr(ws), nbytes, C_, A_, nT, D,
-                                           fp_size, mixing_size, stream_ptr()))
-    return tuple(out)
+    return grid_partners(head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size), m, largest, where)
 
 
 def transfer_head_grid_partners(u_cat, u_an, image, m=1, largest=False, where=None):
     """Each ion's m best partners over ``transfer_head_grid``'s product without the product
     (impnn_transfer_head_grid_partners) -> (cat_values (1,C,m), cat_partner, an_values (1,A,m), an_partner) on the
     device, as ``head_grid_partners``; ``where`` as there."""
-    require_gpu(u_cat, u_an, image)
-    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
-    W = TRANSFER_GRID_WIDTH
-    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
-        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
-    lib = _lib.load()
-    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
-        raise ValueError("the prepared image has the wrong length")
-    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
-    dev = u_cat.device
-    m = int(m)
-    if where is not None:
-        where = _mask_words(where, C_, A_, dev)
-    with torch.cuda.device(dev):
-        out, ws, nbytes = _grid_partners_outputs(lib, 1, C_, A_, 0, m, dev)
-        check(lib.impnn_transfer_head_grid_partners(ptr(u_cat), ptr(u_an), ptr(image), image.numel(),
-                                                    ptr(where) if where is not None else None, m, int(bool(largest)),
-                                                    *[ptr(o) for o in out], ptr(ws), nbytes, C_, A_, stream_ptr()))
-    return tuple(out)
+    return grid_partners(transfer_grid_operands(u_cat, u_an, image), m, largest, where)
 
 
 # the rank cut (csrc/grid_rank.hip): kRankDigitBits of csrc/common.h (tests/test_rank_host.py holds them equal)
@@ -1073,130 +1084,27 @@ def head_grid_rank(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, m
     a ``data.PairMask``.  A value has the bits ``head_grid`` gives for its pair; k is any integer >= 1.  At most
     SELECT_MAX_T temperatures, C*A <= RANK_MAX_PAIRS.  ``where``: the (C,W) words of a pair mask: only its pairs
     compete."""
-    require_gpu(mix_cat, mix_an, head_weights)
-    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
-    kd = HEAD_KINDS[kind]
-    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
-        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
-                         f"and {tuple(mix_an.shape)}")
-    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
-    lib = _lib.load()
-    per_d = 2 * fp_size
-    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
-    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
-    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
-    T, nT = None, 0
-    if kd == 0:
-        if temperatures is None:
-            raise ValueError("the viscosity grid needs temperatures")
-        require_gpu(temperatures)
-        T = f32c(temperatures).reshape(-1)
-        nT = int(T.numel())
-    elif temperatures is not None:
-        raise ValueError("the melting-point grid takes no temperatures")
-    dev = mix_cat.device
-    k, workgroups = int(k), int(workgroups)
-    if where is not None:
-        where = _mask_words(where, C_, A_, dev)
-    with torch.cuda.device(dev):
-        out, ws, nbytes = _grid_rank_outputs(lib, 0, C_, A_, nT, workgroups, mask, dev)
-        check(lib.impnn_head_grid_rank(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None, ptr(head_weights),
-                                       k, int(bool(largest)), ptr(where) if where is not None else None,
-                                       *[ptr(o) if o is not None else None for o in out], ptr(ws), nbytes, C_, A_, nT, D,
-                                       fp_size, mixing_size, workgroups, stream_ptr()))
-    return out
+    return grid_rank(head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size), k, largest, where, mask, workgroups)
 
 
 def transfer_head_grid_rank(u_cat, u_an, image, k, largest=False, where=None, mask=False, workgroups=0):
     """The k-th best pair of ``transfer_head_grid``'s product, and with ``mask`` the k best as a packed pair mask,
     without the product (impnn_transfer_head_grid_rank) -> (values (1,), cation (1,), anion (1,), count (1,), words
     (C,W) or None) on the device, as ``head_grid_rank``; ``where`` as there."""
-    require_gpu(u_cat, u_an, image)
-    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
-    W = TRANSFER_GRID_WIDTH
-    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != W or u_an.shape[1] != W:
-        raise ValueError(f"u rows must be (C,{W}) and (A,{W}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
-    lib = _lib.load()
-    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
-        raise ValueError("the prepared image has the wrong length")
-    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
-    dev = u_cat.device
-    k, workgroups = int(k), int(workgroups)
-    if where is not None:
-        where = _mask_words(where, C_, A_, dev)
-    with torch.cuda.device(dev):
-        out, ws, nbytes = _grid_rank_outputs(lib, 1, C_, A_, 0, workgroups, mask, dev)
-        check(lib.impnn_transfer_head_grid_rank(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), k, int(bool(largest)),
-                                                ptr(where) if where is not None else None,
-                                                *[ptr(o) if o is not None else None for o in out], ptr(ws), nbytes, C_, A_,
-                                                workgroups, stream_ptr()))
-    return out
-
-
-def _mask_bounds(lo, hi):
-    lo, hi = C.c_float(lo).value, C.c_float(hi).value  # as the kernels see them: float32
-    if lo != lo or hi != hi:
-        raise ValueError("a mask bound is NaN (an infinity means no limit)")
-    return lo, hi
+    return grid_rank(transfer_grid_operands(u_cat, u_an, image), k, largest, where, mask, workgroups)
 
 
 def head_grid_mask(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, lo, hi):
     """``head_grid``'s product as a packed pair mask (impnn_head_grid_mask): bit (i,j[,t]) = lo <= v <= hi for the value
     v ``head_grid`` gives that element (a NaN fails; +-inf: no limit) -> int32 words (C,W), "viscosity" (nT,C,W), W =
     ceil(A / 32), pad bits 0: the ``words`` of a ``data.PairMask`` of shape (C,A) / (C,A,nT).  No (C,A) floats exist."""
-    require_gpu(mix_cat, mix_an, head_weights)
-    mix_cat, mix_an, head_weights = f32c(mix_cat), f32c(mix_an), f32c(head_weights)
-    kd = HEAD_KINDS[kind]
-    if mix_cat.dim() != 2 or mix_an.dim() != 2 or mix_cat.shape[1] != mixing_size or mix_an.shape[1] != mixing_size:
-        raise ValueError(f"mixing rows must be (C,{mixing_size}) and (A,{mixing_size}), got {tuple(mix_cat.shape)} "
-                         f"and {tuple(mix_an.shape)}")
-    lo, hi = _mask_bounds(lo, hi)
-    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
-    lib = _lib.load()
-    per_d = 2 * fp_size
-    rest = lib.impnn_model_head_floats(kd, 1, fp_size, mixing_size) - per_d
-    D = (head_weights.numel() - rest) // per_d if head_weights.numel() > rest else 0
-    if D < 1 or head_weights.numel() != lib.impnn_model_head_floats(kd, D, fp_size, mixing_size):
-        raise ValueError("packed head weights have the wrong length")
-    dev = mix_cat.device
-    W = int(lib.impnn_grid_mask_row_words(A_))
-    T, nT = None, 0
-    if kd == 0:
-        if temperatures is None:
-            raise ValueError("the viscosity grid needs temperatures")
-        require_gpu(temperatures)
-        T = f32c(temperatures).reshape(-1)
-        nT = int(T.numel())
-        words = torch.empty(nT, C_, W, dtype=torch.int32, device=dev)
-    else:
-        if temperatures is not None:
-            raise ValueError("the melting-point grid takes no temperatures")
-        words = torch.empty(C_, W, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib.impnn_head_grid_mask(kd, ptr(mix_cat), ptr(mix_an), ptr(T) if T is not None else None, ptr(head_weights),
-                                       lo, hi, ptr(words), C_, A_, nT, D, fp_size, mixing_size, stream_ptr()))
-    return words
+    return grid_mask(head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size), lo, hi)
 
 
 def transfer_head_grid_mask(u_cat, u_an, image, lo, hi):
     """``transfer_head_grid``'s product as a packed pair mask (impnn_transfer_head_grid_mask) -> int32 words (C,W), as
     ``head_grid_mask``."""
-    require_gpu(u_cat, u_an, image)
-    u_cat, u_an, image = f32c(u_cat), f32c(u_an), f32c(image)
-    Wd = TRANSFER_GRID_WIDTH
-    if u_cat.dim() != 2 or u_an.dim() != 2 or u_cat.shape[1] != Wd or u_an.shape[1] != Wd:
-        raise ValueError(f"u rows must be (C,{Wd}) and (A,{Wd}), got {tuple(u_cat.shape)} and {tuple(u_an.shape)}")
-    lo, hi = _mask_bounds(lo, hi)
-    lib = _lib.load()
-    if image.dim() != 1 or image.numel() != lib.impnn_transfer_grid_image_floats():
-        raise ValueError("the prepared image has the wrong length")
-    C_, A_ = int(u_cat.shape[0]), int(u_an.shape[0])
-    words = torch.empty(C_, int(lib.impnn_grid_mask_row_words(A_)), dtype=torch.int32, device=u_cat.device)
-    with torch.cuda.device(u_cat.device):
-        check(lib.impnn_transfer_head_grid_mask(ptr(u_cat), ptr(u_an), ptr(image), image.numel(), lo, hi, ptr(words), C_, A_,
-                                                stream_ptr()))
-    return words
+    return grid_mask(transfer_grid_operands(u_cat, u_an, image), lo, hi)
 
 
 def transfer_head(pooled_cat, pooled_an, weights, cfg):
