@@ -650,6 +650,65 @@ int impnn_transfer_head_grid_rank(const float* u_cat, const float* u_an, const f
                                   int32_t* anion, int64_t* count, uint32_t* mask_words, void* workspace,
                                   size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream);
 
+/* ---- a deep ensemble over the grid: M members of one kind (0 viscosity, 1 melting point), trained from different
+ *      seeds or folds, evaluated inside one grid tile, and per element the mean, the spread and a confidence-bound score
+ *      of their M predictions - the third grid family, through the materialising, the mask-writing and the selecting
+ *      form.  An ensemble screen is one launch over the grid; M grids never exist.
+ *      Operands: mix_cat (M,C,Mx) and mix_an (M,A,Mx), member m's impnn_head_ion_mix rows (from its own encoder and
+ *      its own per-ion weights; D does not reach the grid); temperatures as impnn_head_grid; tails (M, tail_floats),
+ *      member m's tail section of impnn_model_head's packed layout, impnn_ensemble_grid_tail_floats(kind, F, Mx) floats:
+ *      kind 0 Wv Mx*3 | bv 3; kind 1 Wh Mx*F | bh F | Wo F | bo 1.  F, Mx <= 64 and equal for all members.
+ *      The statistic, in float32 and in this order, of the member values v_0 .. v_{M-1} of one element, where v_m has
+ *      the bits impnn_head_grid gives member m for the same mixing rows:
+ *        s = v_0; s = s + v_m, m ascending; mean = s / (float)M
+ *        q = 0; d = v_m - mean; q = fmaf(d, d, q), m ascending; std = sqrt(q / (float)M)   (population, as numpy.std)
+ *        score = fmaf(kappa, std, mean)                              kappa: any finite float
+ *      with the correctly rounded division and square root, no atomics, every sum in a fixed order: an element's bits
+ *      do not depend on the grid's size, the host tiling or the entry that produced it.  A NaN member value makes
+ *      mean, std and score NaN for that element and for no other.  M = 1: mean = v_0, std = 0, score = mean.
+ *      Limits: 1 <= M <= impnn_ensemble_grid_max_members() (8); kind 0: 1 <= nT <=
+ *      impnn_ensemble_grid_max_temperatures(kind, M) for the materialising and the mask-writing entry (4096 for every M;
+ *      0 for kind 1, which takes none) and <= impnn_ensemble_grid_topk_max_temperatures(M) for the selecting entries
+ *      (4 up to M = 6, 3 at M = 7, 2 at M = 8: the members' kept results share the LDS with the lists; split longer
+ *      sweeps, a row does not depend on the others).  The three functions return 0 for an M out of range,
+ *      impnn_ensemble_grid_tail_floats -1 for a bad argument.
+ *      impnn_ensemble_grid: mean, std, score (C,A,nT) for kind 0, (C,A) for kind 1, row-major; a NULL one is not
+ *        written, at least one is needed.  Checks in order: kind; shape (sizes, nT for the kind; IMPNN_E_BADARG); M
+ *        (below 1 IMPNN_E_BADARG, above the limit IMPNN_E_UNSUPPORTED) and kappa (NaN or infinite: IMPNN_E_BADARG); the
+ *        limits F, Mx <= 64 and nT (IMPNN_E_UNSUPPORTED); zero work (C == 0 or A == 0: IMPNN_OK, nothing touched); null
+ *        pointers; kind 1 with temperatures.  C * A * nT may exceed 2^31.
+ *      impnn_ensemble_grid_mask: words as impnn_head_grid_mask, bit (i,j[,t]) = lo <= score && score <= hi.  Checks in
+ *        order: kind; shape; M and kappa; a NaN bound; zero work; null pointers; alignment; the limits.
+ *      impnn_ensemble_grid_topk / _topk_where: outputs, order, k <= 1024, C * A < 2^32, workgroups and `where` as
+ *        impnn_head_grid_topk / _topk_where, on the score; workspace: impnn_ensemble_grid_topk_workspace_bytes bytes for
+ *        the same (M, C, A, nT, k, workgroups), 8-byte aligned (impnn_grid_topk_workspace_bytes does not serve this
+ *        family).  Checks in order: kind; shape; M and kappa; k, nT, C * A (the limits IMPNN_E_UNSUPPORTED); the
+ *        widths; zero work; null pointers, then alignment; the workspace size (IMPNN_E_WORKSPACE).
+ *      Each ion's best partners and the rank cut are not built for this family. */
+int32_t impnn_ensemble_grid_max_members(void);
+int32_t impnn_ensemble_grid_max_temperatures(int32_t kind, int32_t M);
+int32_t impnn_ensemble_grid_topk_max_temperatures(int32_t M);
+int64_t impnn_ensemble_grid_tail_floats(int32_t kind, int32_t F, int32_t Mx);
+int impnn_ensemble_grid(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an, const float* temperatures,
+                        const float* tails, float kappa, float* mean, float* std, float* score, int32_t C, int32_t A,
+                        int32_t nT, int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_ensemble_grid_mask(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                             const float* temperatures, const float* tails, float kappa, float lo, float hi,
+                             uint32_t* words, int32_t C, int32_t A, int32_t nT, int32_t F, int32_t Mx,
+                             impnn_stream_t stream);
+int impnn_ensemble_grid_topk_workspace_bytes(int32_t M, int32_t C, int32_t A, int32_t nT, int32_t k, int32_t workgroups,
+                                             size_t* need);
+int impnn_ensemble_grid_topk(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                             const float* temperatures, const float* tails, float kappa, int32_t k, int32_t largest,
+                             float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                             int32_t C, int32_t A, int32_t nT, int32_t F, int32_t Mx, int32_t workgroups,
+                             impnn_stream_t stream);
+int impnn_ensemble_grid_topk_where(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                                   const float* temperatures, const float* tails, float kappa, const uint32_t* where,
+                                   int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
+                                   void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t F,
+                                   int32_t Mx, int32_t workgroups, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

@@ -96,6 +96,16 @@ SIGNATURES = {
     "impnn_head_grid_topk_where": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, sz] + [i32] * 7 + [vp]),
     "impnn_transfer_head_grid_topk_where": (C.c_int, [vp, vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, sz, i32, i32, i32,
                                                       vp]),
+    "impnn_ensemble_grid_max_members": (i32, []),
+    "impnn_ensemble_grid_max_temperatures": (i32, [i32, i32]),
+    "impnn_ensemble_grid_topk_max_temperatures": (i32, [i32]),
+    "impnn_ensemble_grid_tail_floats": (i64, [i32, i32, i32]),
+    "impnn_ensemble_grid": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, vp, vp, vp] + [i32] * 5 + [vp]),
+    "impnn_ensemble_grid_mask": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, f32, f32, vp] + [i32] * 5 + [vp]),
+    "impnn_ensemble_grid_topk_workspace_bytes": (C.c_int, [i32] * 6 + [C.POINTER(sz)]),
+    "impnn_ensemble_grid_topk": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, sz] + [i32] * 6 + [vp]),
+    "impnn_ensemble_grid_topk_where": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz] + [i32] * 6
+                                       + [vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

@@ -555,6 +555,12 @@ GridOperands transfer_grid_operands(const float* u_cat, const float* u_an, const
                                     impnn_stream_t stream) {
   return {1, 1, u_cat, u_an, nullptr, image, C, A, 0, 0, 0, 0, as_stream(stream)};
 }
+// family 2: M members' mixing rows (M,C,Mx) / (M,A,Mx) and tails; no D
+GridOperands ensemble_grid_operands(int kind, int M, const float* mix_cat, const float* mix_an, const float* T,
+                                    const float* tails, float kappa, int C, int A, int nT, int F, int Mx,
+                                    impnn_stream_t stream) {
+  return {2, kind, mix_cat, mix_an, T, tails, C, A, nT, 0, F, Mx, as_stream(stream), M, kappa};
+}
 // the transfer grid's operands: 16-byte alignment, then the image size (image_floats < 0: the entry takes no image)
 int transfer_image_rule(const char* entry, bool aligned_ok, int64_t image_floats) {
   if (!aligned_ok) return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
@@ -751,16 +757,16 @@ int grid_family_rule(const char* entry, int family) {
 }
 // the kind, the entry's signs (`shape_ok`), then the temperature count the kind allows (a negative nT is a bad shape)
 int grid_kind_rule(const char* entry, const GridOperands& g, bool shape_ok) {
-  if (g.family == 0 && g.kind != 0 && g.kind != 1)
+  if (g.family != 1 && g.kind != 0 && g.kind != 1)
     return fail(IMPNN_E_BADARG, "%s: kind must be 0 (viscosity) or 1 (melting point)", entry);
   if (!shape_ok) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
-  if (g.family == 0 && g.kind == 0 && g.nT == 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
-  if (g.family == 0 && g.kind == 1 && g.nT > 0)
+  if (g.family != 1 && g.kind == 0 && g.nT == 0) return fail(IMPNN_E_BADARG, "%s: the viscosity grid needs nT >= 1 temperatures", entry);
+  if (g.family != 1 && g.kind == 1 && g.nT > 0)
     return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures: nT must be 0", entry);
   return IMPNN_OK;
 }
 int grid_no_temperatures_rule(const char* entry, const GridOperands& g) {
-  if (g.family == 0 && g.kind == 1 && g.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
+  if (g.family != 1 && g.kind == 1 && g.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
   return IMPNN_OK;
 }
 int grid_transfer_rule(const char* entry, const GridOperands& g, int64_t image_floats) {
@@ -778,9 +784,17 @@ int grid_workspace_rule(const char* entry, size_t workspace_bytes, size_t need) 
     return fail(IMPNN_E_WORKSPACE, "%s: workspace of %zu bytes is too small (%zu)", entry, workspace_bytes, need);
   return IMPNN_OK;
 }
-int grid_select_temperatures_rule(const char* entry, int nT) {
-  if (nT > kSelectMaxT)
-    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, kSelectMaxT);
+int grid_select_temperatures_rule(const char* entry, int nT, int most = kSelectMaxT) {
+  if (nT > most)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per selecting call)", entry, nT, most);
+  return IMPNN_OK;
+}
+// the ensemble's own arguments, checked with the shape (a head or transfer grid has none)
+int grid_ensemble_rule(const char* entry, int M, float kappa) {
+  if (M < 1) return fail(IMPNN_E_BADARG, "%s: M=%d members must be at least 1", entry, M);
+  if (M > ensemble_grid_max_members())
+    return fail(IMPNN_E_UNSUPPORTED, "%s: M=%d members (<= %d per call)", entry, M, ensemble_grid_max_members());
+  if (!(kappa - kappa == 0.f)) return fail(IMPNN_E_BADARG, "%s: kappa must be finite", entry);
   return IMPNN_OK;
 }
 int grid_pairs_rule(const char* entry, int C, int A) {
@@ -791,13 +805,21 @@ int grid_pairs_rule(const char* entry, int C, int A) {
 }
 
 // shape only: what the workspace query and the entries share
-int grid_topk_shape(const char* entry, int family, int C, int A, int nT, int k, int workgroups) {
-  if (int rc = grid_family_rule(entry, family)) return rc;
+int grid_topk_limits(const char* entry, int C, int A, int nT, int k, int workgroups, int most_temperatures) {
   if (C < 0 || A < 0 || nT < 0 || workgroups < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
   if (k < 1) return fail(IMPNN_E_BADARG, "%s: k=%d must be at least 1", entry, k);
   if (k > kSelectMaxK) return fail(IMPNN_E_UNSUPPORTED, "%s: k=%d entries (<= %d per call)", entry, k, kSelectMaxK);
-  if (int rc = grid_select_temperatures_rule(entry, nT)) return rc;
+  if (int rc = grid_select_temperatures_rule(entry, nT, most_temperatures)) return rc;
   return grid_pairs_rule(entry, C, A);
+}
+int grid_topk_shape(const char* entry, int family, int C, int A, int nT, int k, int workgroups) {
+  if (int rc = grid_family_rule(entry, family)) return rc;
+  return grid_topk_limits(entry, C, A, nT, k, workgroups, kSelectMaxT);
+}
+// the ensemble grid's: M and kappa first, then the same limits with the temperatures M members leave room for
+int ensemble_topk_shape(const char* entry, int M, float kappa, int C, int A, int nT, int k, int workgroups) {
+  if (int rc = grid_ensemble_rule(entry, M, kappa)) return rc;
+  return grid_topk_limits(entry, C, A, nT, k, workgroups, ensemble_grid_topk_max_temperatures(M));
 }
 int grid_partners_shape(const char* entry, int family, int C, int A, int nT, int m) {
   if (int rc = grid_family_rule(entry, family)) return rc;
@@ -818,7 +840,7 @@ int grid_rank_limits(const char* entry, int C, int A, int nT) {
 int grid_selecting_rules(const char* entry, const GridOperands& g, bool pointers_ok, const void* workspace,
                          const uint32_t* where, int64_t image_floats, size_t need, size_t workspace_bytes, bool* launch) {
   *launch = false;
-  if (g.family == 0)
+  if (g.family != 1)
     if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
   if (g.C == 0 || g.A == 0) return IMPNN_OK;
   if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
@@ -836,13 +858,16 @@ int grid_topk_checked(const char* entry, const GridTopkCall& c, bool shape_ok, b
                       size_t workspace_bytes) {
   const GridOperands& g = c.g;
   if (int rc = grid_kind_rule(entry, g, shape_ok)) return rc;
-  if (int rc = grid_topk_shape(entry, g.family, g.C, g.A, g.nT, c.k, c.workgroups)) return rc;
+  if (int rc = g.family == 2 ? ensemble_topk_shape(entry, g.M, g.kappa, g.C, g.A, g.nT, c.k, c.workgroups)
+                            : grid_topk_shape(entry, g.family, g.C, g.A, g.nT, c.k, c.workgroups))
+    return rc;
   bool launch;
   if (int rc = grid_selecting_rules(entry, g, pointers_ok && (!c.masked || c.where), c.workspace, c.where, image_floats,
                                     grid_topk_workspace_bytes(g.family, g.C, g.A, g.nT, c.k, c.workgroups), workspace_bytes,
                                     &launch))
     return rc;
-  return launch ? launch_grid_topk(c) : IMPNN_OK;
+  if (!launch) return IMPNN_OK;
+  return g.family == 2 ? launch_ensemble_grid_topk(c) : launch_grid_topk(c);
 }
 
 int grid_partners_checked(const char* entry, const GridPartnersCall& c, bool shape_ok, bool pointers_ok,
@@ -884,18 +909,20 @@ int grid_rank_checked(const char* entry, const GridRankCall& c, bool shape_ok, b
 int grid_mask_checked(const char* entry, const GridMaskCall& c, bool shape_ok, bool pointers_ok, int64_t image_floats) {
   const GridOperands& g = c.g;
   if (int rc = grid_kind_rule(entry, g, shape_ok && g.C >= 0 && g.A >= 0 && g.nT >= 0)) return rc;
+  if (g.family == 2)
+    if (int rc = grid_ensemble_rule(entry, g.M, g.kappa)) return rc;
   if (c.lo != c.lo || c.hi != c.hi) return fail(IMPNN_E_BADARG, "%s: a bound is NaN (an infinity means no limit)", entry);
   if (g.C == 0 || g.A == 0) return IMPNN_OK;
   if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
   if (int rc = grid_no_temperatures_rule(entry, g)) return rc;
   if (int rc = grid_aligned_rule(entry, c.words, nullptr, 4, "the mask must be 4-byte aligned")) return rc;
   if (int rc = grid_transfer_rule(entry, g, image_floats)) return rc;
-  if (g.family == 0) {
+  if (g.family != 1) {
     if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
-    if (g.nT > head_grid_max_temperatures())
-      return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, g.nT, head_grid_max_temperatures());
+    const int most = g.family == 2 ? ensemble_grid_max_temperatures(g.kind, g.M) : head_grid_max_temperatures();
+    if (g.nT > most) return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, g.nT, most);
   }
-  return launch_grid_mask(c);
+  return g.family == 2 ? launch_ensemble_grid_mask(c) : launch_grid_mask(c);
 }
 }  // namespace
 
@@ -1037,6 +1064,72 @@ int impnn_transfer_head_grid_mask(const float* u_cat, const float* u_an, const f
                                   float lo, float hi, uint32_t* words, int32_t C, int32_t A, impnn_stream_t stream) {
   const GridMaskCall c{transfer_grid_operands(u_cat, u_an, image, C, A, stream), lo, hi, words};
   return grid_mask_checked(__func__, c, image_floats >= 0, u_cat && u_an && image && words, image_floats);
+}
+
+// ---- the ensemble grid (include/impnn.h; ensemble_grid.hip): family 2 through the materialising, mask-writing and
+// selecting forms.  The materialising entry follows impnn_head_grid's order, the others go through the family's checks.
+int32_t impnn_ensemble_grid_max_members(void) { return ensemble_grid_max_members(); }
+int32_t impnn_ensemble_grid_max_temperatures(int32_t kind, int32_t M) { return ensemble_grid_max_temperatures(kind, M); }
+int32_t impnn_ensemble_grid_topk_max_temperatures(int32_t M) { return ensemble_grid_topk_max_temperatures(M); }
+int64_t impnn_ensemble_grid_tail_floats(int32_t kind, int32_t F, int32_t Mx) {
+  return (kind == 0 || kind == 1) && F > 0 && Mx > 0 ? ensemble_grid_tail_floats(kind, F, Mx) : -1;
+}
+
+int impnn_ensemble_grid(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an, const float* temperatures,
+                        const float* tails, float kappa, float* mean, float* std, float* score, int32_t C, int32_t A,
+                        int32_t nT, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  const GridOperands g = ensemble_grid_operands(kind, M, mix_cat, mix_an, temperatures, tails, kappa, C, A, nT, F, Mx, stream);
+  if (int rc = grid_kind_rule(__func__, g, C >= 0 && A >= 0 && nT >= 0 && F > 0 && Mx > 0)) return rc;
+  if (int rc = grid_ensemble_rule(__func__, M, kappa)) return rc;
+  if (int rc = head_widths_covered(__func__, 0, F, Mx)) return rc;
+  if (nT > ensemble_grid_max_temperatures(kind, M))
+    return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", __func__, nT,
+                ensemble_grid_max_temperatures(kind, M));
+  if (C == 0 || A == 0) return IMPNN_OK;
+  REQUIRE(mix_cat && mix_an && tails && (mean || std || score) && (kind == 1 || temperatures), "null pointer");
+  if (int rc = grid_no_temperatures_rule(__func__, g)) return rc;
+  return launch_ensemble_grid(g, mean, std, score);
+}
+
+int impnn_ensemble_grid_mask(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                             const float* temperatures, const float* tails, float kappa, float lo, float hi,
+                             uint32_t* words, int32_t C, int32_t A, int32_t nT, int32_t F, int32_t Mx,
+                             impnn_stream_t stream) {
+  const GridMaskCall c{ensemble_grid_operands(kind, M, mix_cat, mix_an, temperatures, tails, kappa, C, A, nT, F, Mx, stream),
+                       lo, hi, words};
+  return grid_mask_checked(__func__, c, F > 0 && Mx > 0, mix_cat && mix_an && tails && words && (kind == 1 || temperatures), 0);
+}
+
+int impnn_ensemble_grid_topk_workspace_bytes(int32_t M, int32_t C, int32_t A, int32_t nT, int32_t k, int32_t workgroups,
+                                             size_t* need) {
+  if (int rc = ensemble_topk_shape(__func__, M, 0.f, C, A, nT, k, workgroups)) return rc;
+  REQUIRE(need, "null pointer");
+  *need = grid_topk_workspace_bytes(2, C, A, nT, k, workgroups);
+  return IMPNN_OK;
+}
+
+int impnn_ensemble_grid_topk(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                             const float* temperatures, const float* tails, float kappa, int32_t k, int32_t largest,
+                             float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                             int32_t C, int32_t A, int32_t nT, int32_t F, int32_t Mx, int32_t workgroups,
+                             impnn_stream_t stream) {
+  const GridTopkCall c{ensemble_grid_operands(kind, M, mix_cat, mix_an, temperatures, tails, kappa, C, A, nT, F, Mx, stream),
+                       k, largest, values, cation, anion, workspace, workgroups, false, nullptr};
+  return grid_topk_checked(__func__, c, F > 0 && Mx > 0,
+                           mix_cat && mix_an && tails && values && cation && anion && workspace && (kind == 1 || temperatures),
+                           0, workspace_bytes);
+}
+
+int impnn_ensemble_grid_topk_where(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                                   const float* temperatures, const float* tails, float kappa, const uint32_t* where,
+                                   int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
+                                   void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t F,
+                                   int32_t Mx, int32_t workgroups, impnn_stream_t stream) {
+  const GridTopkCall c{ensemble_grid_operands(kind, M, mix_cat, mix_an, temperatures, tails, kappa, C, A, nT, F, Mx, stream),
+                       k, largest, values, cation, anion, workspace, workgroups, true, where};
+  return grid_topk_checked(__func__, c, F > 0 && Mx > 0,
+                           mix_cat && mix_an && tails && values && cation && anion && workspace && (kind == 1 || temperatures),
+                           0, workspace_bytes);
 }
 
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,

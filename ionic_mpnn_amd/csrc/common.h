@@ -284,12 +284,15 @@ int head_grid_max_temperatures();
 
 // The operands every grid launch shares (api.hip builds and checks them).  family 0: the head grid (`kind`, mixing
 // rows, T, the packed head of impnn_model_head in `w`); family 1: the transfer grid (u rows in mix_cat / mix_an, the
-// prepared image in `w`; kind 1, no T, no widths).
+// prepared image in `w`; kind 1, no T, no widths); family 2: the ensemble grid (`M` members of `kind`: mixing rows
+// (M,C,Mx) and (M,A,Mx), T, the members' tails (M, tail floats) in `w`, `kappa` of the score; no D).
 struct GridOperands {
   int family, kind;
   const float *mix_cat, *mix_an, *T, *w;
   int C, A, nT, D, F, Mx;
   hipStream_t stream;
+  int M;        // family 2
+  float kappa;  // family 2
 };
 int launch_head_grid(const GridOperands& g, float* out, float* params);
 
@@ -320,6 +323,9 @@ struct GridTopkCall {
 int grid_topk_workgroups(int family, int C, int A, int workgroups);  // 0: the default; capped by the tile count
 size_t grid_topk_workspace_bytes(int family, int C, int A, int nT, int k, int workgroups);
 int launch_grid_topk(const GridTopkCall& c);
+// the second launch of a selecting call: the G workgroups' lists in `ws` -> values, cation, anion (nT, k)
+int launch_grid_topk_merge(const unsigned long long* ws, int G, int nT, int k, int largest, int A, float* values,
+                           int32_t* cation, int32_t* anion, hipStream_t s);
 
 // ---- pair masks (grid_mask.hip; include/impnn.h, impnn_head_grid_mask / impnn_transfer_head_grid_mask).  One
 // mask-writing launch: bit (i, j) = lo <= prediction <= hi.  api.hip checks it.
@@ -330,6 +336,16 @@ struct GridMaskCall {
 };
 int64_t grid_mask_row_words(int A);
 int launch_grid_mask(const GridMaskCall& c);
+
+// ---- the ensemble grid (ensemble_grid.hip; include/impnn.h, impnn_ensemble_grid*): family 2 of GridOperands through
+// the materialising, mask-writing and selecting forms.  api.hip checks the arguments.
+int ensemble_grid_max_members();
+int ensemble_grid_max_temperatures(int kind, int M);  // a materialising or mask-writing launch; kind 1: 0
+int ensemble_grid_topk_max_temperatures(int M);       // a selecting launch: 1 .. kSelectMaxT
+int64_t ensemble_grid_tail_floats(int kind, int F, int Mx);
+int launch_ensemble_grid(const GridOperands& g, float* mean, float* std, float* score);
+int launch_ensemble_grid_mask(const GridMaskCall& c);
+int launch_ensemble_grid_topk(const GridTopkCall& c);
 
 // ---- each ion's best partners over a cation x anion grid (grid_partners.hip; include/impnn.h,
 // impnn_head_grid_partners / impnn_transfer_head_grid_partners).  The limits of one launch (ops.py mirrors them): m, at

@@ -564,6 +564,60 @@ __device__ __forceinline__ void store_rows(float* __restrict__ out, int64_t firs
   }
 }
 
+// A pair of the tile as ensemble_grid_kernel evaluates it: head_grid_kernel's statements, restated (its own stay inline:
+// its instantiations are kept instruction-identical to what they were before the ensemble grid existed).
+// Kind 0: mixed = cation row + anion row (AddTwoTensors, the cation term first), vp = Dense(3) (bias first, inputs
+// ascending), then the VFT parameters.  wts: Wv Mx*3 | bv 3.
+__device__ __forceinline__ VftParams head_pair_vft(const float* cat_row, const float* an_row, const float* wts, int Mx) {
+  const float4* pc = reinterpret_cast<const float4*>(cat_row);
+  const float4* pa = reinterpret_cast<const float4*>(an_row);
+  float v0 = wts[Mx * 3], v1 = wts[Mx * 3 + 1], v2 = wts[Mx * 3 + 2];
+  for (int k4 = 0; k4 < Mx; k4 += 4) {
+    const float4 c = pc[k4 >> 2], a = pa[k4 >> 2];
+    const float m[4] = {c.x + a.x, c.y + a.y, c.z + a.z, c.w + a.w};  // AddTwoTensors, the cation term first
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (k4 + u < Mx) {
+        const float* w = wts + (k4 + u) * 3;
+        v0 = fmaf(m[u], w[0], v0);
+        v1 = fmaf(m[u], w[1], v1);
+        v2 = fmaf(m[u], w[2], v2);
+      }
+  }
+  return head_vft_params(v0, v1, v2);
+}
+
+// Kind 1: MXR registers hold the mixed vector, then relu(Dense(F)) and Dense(1).  whT [F][S2], bh [F], wo: Wo F | bo 1.
+template <int MXR>
+__device__ __forceinline__ float head_pair_mp(const float* cat_row, const float* an_row, const float* whT, const float* bh,
+                                              const float* wo, int F, int Mx, int S2) {
+  const float4* pc = reinterpret_cast<const float4*>(cat_row);
+  const float4* pa = reinterpret_cast<const float4*>(an_row);
+  float mixed[MXR];
+#pragma unroll
+  for (int k4 = 0; k4 < MXR; k4 += 4)
+    if (k4 < Mx) {
+      const float4 c = pc[k4 >> 2], a = pa[k4 >> 2];
+      mixed[k4] = c.x + a.x, mixed[k4 + 1] = c.y + a.y, mixed[k4 + 2] = c.z + a.z, mixed[k4 + 3] = c.w + a.w;
+    }
+  float acc2 = wo[F];
+  for (int j = 0; j < F; ++j) {
+    const float4* w = reinterpret_cast<const float4*>(whT + j * S2);
+    float acc = bh[j];
+#pragma unroll
+    for (int k4 = 0; k4 < MXR; k4 += 4)
+      if (k4 < Mx) {
+        const float4 ww = w[k4 >> 2];
+        acc = fmaf(mixed[k4], ww.x, acc);
+        if (k4 + 1 < Mx) acc = fmaf(mixed[k4 + 1], ww.y, acc);
+        if (k4 + 2 < Mx) acc = fmaf(mixed[k4 + 2], ww.z, acc);
+        if (k4 + 3 < Mx) acc = fmaf(mixed[k4 + 3], ww.w, acc);
+      }
+    acc2 = fmaf(head_relu(acc), wo[j], acc2);
+  }
+  return acc2;
+}
+
 // KIND 0: MXR unused (0).  KIND 1: MXR = 32 or 64 registers hold a pair's mixed vector.
 template <int KIND, int MXR, class... Sel>
 __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict__ mix_cat,
@@ -760,6 +814,183 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
   if constexpr (Form::rank_count) rank_finish(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1);
 }
 
+// ================================================================ the ensemble grid (ensemble_grid.hip)
+// M members of one kind over the same tile: the statistic of a pair's M head values, one float per (pair, temperature)
+// for the forms the head grid has - store, mask, top-k.  A member's value has the bits head_grid_kernel gives it for the
+// same mixing rows (head_pair_vft / head_pair_mp, head_vft_eval); the statistic, in float32 and in this order:
+//   s = v_0; s = s + v_m (m ascending); mean = s / M
+//   q = 0; d = v_m - mean; q = fmaf(d, d, q) (m ascending); std = sqrt(q / M)      (the population deviation)
+//   score = fmaf(kappa, std, mean)
+// with the correctly rounded division and square root.  A NaN member value makes all three NaN, for that element only.
+constexpr int kEnsembleMaxMembers = 8;
+constexpr size_t kEnsembleLdsCap = 160 * 1024 - 256;  // a CU's LDS less the 256 static bytes of the _where form (__syncthreads_or)
+
+struct EnsembleStat {
+  float mean, std, score;
+};
+__device__ __forceinline__ EnsembleStat ensemble_stat(const float (&v)[kEnsembleMaxMembers], int M, float kappa) {
+  float s = v[0];
+#pragma unroll
+  for (int m = 1; m < kEnsembleMaxMembers; ++m)
+    if (m < M) s = s + v[m];
+  const float n = (float)M, mean = s / n;
+  float q = 0.f;
+#pragma unroll
+  for (int m = 0; m < kEnsembleMaxMembers; ++m)
+    if (m < M) {
+      const float d = v[m] - mean;
+      q = fmaf(d, d, q);
+    }
+  const float sd = sqrtf(q / n);
+  return EnsembleStat{mean, sd, fmaf(kappa, sd, mean)};
+}
+
+// the tail section of impnn_model_head's packed layout: kind 0 Wv Mx*3 | bv 3; kind 1 Wh Mx*F | bh F | Wo F | bo 1
+__host__ __device__ inline size_t ensemble_tail_floats(int kind, int F, int Mx) {
+  return kind == 0 ? (size_t)Mx * 3 + 3 : (size_t)Mx * F + 2 * (size_t)F + 1;
+}
+// The head grid's regions with M copies of the kept results (kind 0: a pair's three VFT parameters, kind 1: its value):
+// 12 KiB and 4 KiB a member.  The mixing rows and the tail weights are one member's, loaded in turn.
+__host__ __device__ inline size_t ensemble_lds_floats(int kind, int M, int nT, int F, int Mx) {
+  return grid_lds_floats(kind, nT, F, Mx) + (size_t)(M - 1) * (kind == 0 ? 3 : 1) * kTilePairs;
+}
+// Temperatures one launch takes with M members at the widest rows the head kernels cover (kHeadMaxDim), so that the
+// workgroup stays within kEnsembleLdsCap: a materialising or mask-writing launch (T / 100 sits in LDS, at most `most`),
+// and a selecting launch (a list of select_capacity(kSelectMaxK, kTilePairs) entries per temperature and the tile's
+// mask words behind the tile's regions; at most kSelectMaxT, and at least 1 for every M <= kEnsembleMaxMembers).
+inline int ensemble_max_temperatures(int M, int most) {
+  const size_t fixed = sizeof(float) * ensemble_lds_floats(0, M, 0, kHeadMaxDim, kHeadMaxDim);
+  const size_t room = (kEnsembleLdsCap - fixed) / sizeof(float) & ~(size_t)3;
+  return room < (size_t)most ? (int)room : most;
+}
+inline int ensemble_select_max_temperatures(int M) {
+  int nT = kSelectMaxT;
+  while (nT > 1 && sizeof(float) * ensemble_lds_floats(0, M, nT, kHeadMaxDim, kHeadMaxDim) +
+                           select_lds_bytes(nT, select_capacity(kSelectMaxK, kTilePairs)) +
+                           sizeof(uint32_t) * kWhereTileWords > kEnsembleLdsCap)
+    --nT;
+  return nT;
+}
+
+// What the materialising form writes: any of the three, (C,A,nT) for kind 0 and (C,A) for kind 1; a null one is skipped.
+struct EnsembleOut {
+  float *mean, *std, *score;
+};
+
+// mix_cat (M,C,Mx), mix_an (M,A,Mx), tails (M, ensemble_tail_floats).  The tile, its threads and its forms are
+// head_grid_kernel's (store, GridMask, GridSelect, GridSelectWhere); the mask and the selection use the score.
+template <int KIND, int MXR, class... Sel>
+__global__ __launch_bounds__(256) void ensemble_grid_kernel(const float* __restrict__ mix_cat,
+                                                            const float* __restrict__ mix_an,
+                                                            const float* __restrict__ T, const float* __restrict__ tails,
+                                                            EnsembleOut out, int M, float kappa, int C, int A, int nT,
+                                                            int F, int Mx, int tiles_a, Sel... sel) {
+  extern __shared__ __align__(16) float sm[];
+  using Form = GridForm<Sel...>;
+  static_assert(!Form::partners && !Form::rank_count && !Form::rank_mask, "ensemble grids: partners / rank are not built");
+  constexpr bool kSelect = Form::select;
+  constexpr int kKeep = KIND == 0 ? 3 : 1;  // floats kept per pair and member
+  const int S = mix_row_stride(Mx), S2 = (Mx + 3) & ~3;
+  float* man = sm;                     // [kTileA][S]
+  float* mcat = man + kTileA * S;      // [kTileC][S]
+  float* wts = mcat + kTileC * S;      // one member's tail weights, as head_grid_kernel lays them out
+  float* kept = wts + (KIND == 0 ? align4((size_t)Mx * 3 + 3) : (size_t)F * S2 + align4(F) + align4((size_t)F + 1));
+  float* t100 = kept + (size_t)M * kKeep * kTilePairs;  // [nT] (kind 0)
+  float* lists = sm + ensemble_lds_floats(KIND, M, nT, F, Mx);
+  const int planes = KIND == 0 ? nT : 1;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const size_t ntail = ensemble_tail_floats(KIND, F, Mx);
+  unsigned tile = blockIdx.x;
+  if constexpr (kSelect) select_init(sel..., lists, planes);
+  if constexpr (KIND == 0)
+    for (int t = tid; t < nT; t += blockDim.x) t100[t] = head_scaled_t(T[t]);  // (published by the members' barriers)
+  do {
+  const int c0 = (tile / tiles_a) * kTileC, a0 = (tile % tiles_a) * kTileA;
+  const int nc = min(kTileC, C - c0), na = min(kTileA, A - a0);
+  if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
+    if (!where_tile_any(sel..., lists, planes, c0, nc, a0 >> 5, kTileA / 32)) continue;
+  }
+
+  for (int m = 0; m < M; ++m) {
+    if (m > 0) __syncthreads();  // the last member's pairs are done with the rows and the weights
+    const float* rows_an = mix_an + ((int64_t)m * A + a0) * Mx;
+    const float* rows_cat = mix_cat + ((int64_t)m * C + c0) * Mx;
+    const float* tail = tails + (size_t)m * ntail;
+    float* keep = kept + (size_t)m * kKeep * kTilePairs;
+    for (int idx = tid; idx < na * Mx; idx += blockDim.x) {
+      const int r = idx / Mx;
+      man[r * S + (idx - r * Mx)] = rows_an[idx];
+    }
+    for (int idx = tid; idx < nc * Mx; idx += blockDim.x) {
+      const int r = idx / Mx;
+      mcat[r * S + (idx - r * Mx)] = rows_cat[idx];
+    }
+    if constexpr (KIND == 0) {
+      for (int t = tid; t < Mx * 3 + 3; t += blockDim.x) wts[t] = tail[t];
+      __syncthreads();
+      for (int ci = wave; ci < nc; ci += 4)
+        if (lane < na) {
+          const VftParams p = head_pair_vft(mcat + ci * S, man + lane * S, wts, Mx);
+          keep[ci * kTileA + lane] = p.A;
+          keep[kTilePairs + ci * kTileA + lane] = p.Bc;
+          keep[2 * kTilePairs + ci * kTileA + lane] = p.Cc;
+        }
+    } else {
+      float* whT = wts;                   // [F][S2]
+      float* bh = whT + F * S2;           // [F]
+      float* wo = bh + ((F + 3) & ~3);    // Wo F | bo 1
+      for (int idx = tid; idx < Mx * F; idx += blockDim.x) {
+        const int i = idx / F;
+        whT[(idx - i * F) * S2 + i] = tail[idx];
+      }
+      for (int t = tid; t < F; t += blockDim.x) bh[t] = tail[Mx * F + t];
+      for (int t = tid; t < F + 1; t += blockDim.x) wo[t] = tail[Mx * F + F + t];
+      __syncthreads();
+      for (int ci = wave; ci < nc; ci += 4)
+        if (lane < na) keep[ci * kTileA + lane] = head_pair_mp<MXR>(mcat + ci * S, man + lane * S, whT, bh, wo, F, Mx, S2);
+    }
+  }
+  __syncthreads();
+
+  // the statistic of pair e of the tile at temperature t, from the kept results (a pair outside the grid: unspecified
+  // finite-or-not bits of stale LDS, never stored, never live)
+  auto stat = [&](int e, int t) {
+    float v[kEnsembleMaxMembers];
+#pragma unroll
+    for (int m = 0; m < kEnsembleMaxMembers; ++m) {
+      v[m] = 0.f;
+      if (m < M) {
+        const float* keep = kept + (size_t)m * kKeep * kTilePairs + e;
+        if constexpr (KIND == 0)
+          v[m] = head_vft_eval(VftParams{keep[0], keep[kTilePairs], keep[2 * kTilePairs]}, t100[t]);
+        else
+          v[m] = keep[0];
+      }
+    }
+    return ensemble_stat(v, M, kappa);
+  };
+  if constexpr (kSelect) {
+    select_tile(sel..., lists, planes, kTilePairs, [&](int q, int t, bool* live, uint32_t* pair) {
+      const int e = q * 256 + tid, r = e >> 6, a = e & 63;
+      *live = r < nc && a < na;
+      if constexpr (Form::where) *live = *live && where_bit(sel..., lists, planes, r, a, kTileA / 32);
+      *pair = (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a);
+      return stat(e, t).score;
+    });
+  } else if constexpr (Form::mask) {
+    mask_head_tile(sel..., C, c0, a0, nc, na, planes, [&](int e, int t) { return stat(e, t).score; });
+  } else {
+    const int64_t first = ((int64_t)c0 * A + a0) * planes, pitch = (int64_t)A * planes;
+    if (out.mean)
+      store_rows(out.mean, first, pitch, nc, na * planes, planes, [&](int r, int a, int t) { return stat(r * kTileA + a, t).mean; });
+    if (out.std)
+      store_rows(out.std, first, pitch, nc, na * planes, planes, [&](int r, int a, int t) { return stat(r * kTileA + a, t).std; });
+    if (out.score)
+      store_rows(out.score, first, pitch, nc, na * planes, planes, [&](int r, int a, int t) { return stat(r * kTileA + a, t).score; });
+  }
+  } while (select_next_tile(&tile, sel...));  // (the materialising and mask forms: one tile per workgroup)
+  if constexpr (kSelect) select_finish(sel..., lists, planes);
+}
 
 // ================================================================ the transfer grid (transfer_grid.hip; grid_select.hip)
 constexpr int kH1 = 256, kH2 = 128, kH3 = 64;
@@ -1048,13 +1279,14 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
 }
 
 // ================================================================ host side: the tile geometry and the one launcher
-// Tiles along C, tiles along A and the tile's size for a family (0: head grid, 1: transfer grid).
+// Tiles along C, tiles along A and the tile's size for a family (0: head grid, 1: transfer grid, 2: ensemble grid - the
+// head grid's tile).
 struct GridTiles {
   int tile_c, tile_a, c, a;
   int64_t count() const { return (int64_t)c * a; }
 };
 inline GridTiles grid_tiles(int family, int C, int A) {
-  const int tc = family == 0 ? kTileC : kTgTileC, ta = family == 0 ? kTileA : kTgTileA;
+  const int tc = family != 1 ? kTileC : kTgTileC, ta = family != 1 ? kTileA : kTgTileA;
   return {tc, ta, (C + tc - 1) / tc, (A + ta - 1) / ta};
 }
 // a workgroup per tile (the materialising and the mask-writing launches): the tiles must fit one launch
@@ -1065,24 +1297,42 @@ inline int grid_tiles_fit(const char* what, const GridTiles& t) {
   return IMPNN_OK;
 }
 
-// Every launch of head_grid_kernel / transfer_grid_kernel: `groups` workgroups, `extra_lds` bytes of dynamic LDS behind
-// the tile's own, the trailing pack of the form (none: the materialising form, which alone takes out / params).  The
-// kernel is picked here: kind 0 -> <0, 0>, kind 1 -> <1, 32> up to Mx = 32, else <1, 64>.  A request above 48 KiB
-// raises the kernel's dynamic-LDS limit first.  FAMILY is a template argument so that a translation unit instantiates
-// the kernels of the families it launches and no others.
+// Where the materialising form of a family writes: out (every family; the ensemble's mean), params (the head grid's VFT
+// parameters), std and score (the ensemble grid).  Null: not wanted; the other forms leave all of them null.
+struct GridOut {
+  float *out = nullptr, *params = nullptr, *std = nullptr, *score = nullptr;
+};
+
+// Every launch of head_grid_kernel / transfer_grid_kernel / ensemble_grid_kernel: `groups` workgroups, `extra_lds` bytes
+// of dynamic LDS behind the tile's own, the trailing pack of the form (none: the materialising form, which alone takes
+// `out`).  The kernel is picked here: kind 0 -> <0, 0>, kind 1 -> <1, 32> up to Mx = 32, else <1, 64>.  A request above
+// 48 KiB raises the kernel's dynamic-LDS limit first.  FAMILY is a template argument so that a translation unit
+// instantiates the kernels of the families it launches and no others.
 template <int FAMILY, class... Sel>
-void launch_grid_family(const GridOperands& g, unsigned groups, size_t extra_lds, float* out, float* params, Sel... sel) {
+void launch_grid_family(const GridOperands& g, unsigned groups, size_t extra_lds, const GridOut& out, Sel... sel) {
   const int tiles_a = grid_tiles(FAMILY, g.C, g.A).a;
   auto launch = [&](auto kern, size_t lds, auto... args) {
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     kern<<<groups, 256, lds, g.stream>>>(args..., tiles_a, sel...);
   };
   if constexpr (FAMILY == 1) {
-    launch(transfer_grid_kernel<Sel...>, sizeof(float) * kTgLdsFloats + extra_lds, g.mix_cat, g.mix_an, g.w, out, g.C, g.A);
+    launch(transfer_grid_kernel<Sel...>, sizeof(float) * kTgLdsFloats + extra_lds, g.mix_cat, g.mix_an, g.w, out.out, g.C, g.A);
+  } else if constexpr (FAMILY == 2) {  // `w`: the members' tails
+    const size_t lds = sizeof(float) * ensemble_lds_floats(g.kind, g.M, g.nT, g.F, g.Mx) + extra_lds;
+    auto ens = [&](auto kern) {
+      launch(kern, lds, g.mix_cat, g.mix_an, g.T, g.w, EnsembleOut{out.out, out.std, out.score}, g.M, g.kappa, g.C, g.A,
+             g.nT, g.F, g.Mx);
+    };
+    if (g.kind == 0)
+      ens(ensemble_grid_kernel<0, 0, Sel...>);
+    else if (g.Mx <= 32)
+      ens(ensemble_grid_kernel<1, 32, Sel...>);
+    else
+      ens(ensemble_grid_kernel<1, 64, Sel...>);
   } else {
     const float* tail = g.w + 2 * ((size_t)g.D * g.F + g.F) + 2 * ((size_t)g.F * g.Mx + g.Mx);  // behind the per-ion parts
     const size_t lds = sizeof(float) * grid_lds_floats(g.kind, g.nT, g.F, g.Mx) + extra_lds;
-    auto head = [&](auto kern) { launch(kern, lds, g.mix_cat, g.mix_an, g.T, tail, out, params, g.C, g.A, g.nT, g.F, g.Mx); };
+    auto head = [&](auto kern) { launch(kern, lds, g.mix_cat, g.mix_an, g.T, tail, out.out, out.params, g.C, g.A, g.nT, g.F, g.Mx); };
     if (g.kind == 0)
       head(head_grid_kernel<0, 0, Sel...>);
     else if (g.Mx <= 32)
@@ -1091,13 +1341,13 @@ void launch_grid_family(const GridOperands& g, unsigned groups, size_t extra_lds
       head(head_grid_kernel<1, 64, Sel...>);
   }
 }
-// the selecting, mask-writing, partner and rank forms: either family, no output of the grid itself
+// the selecting, mask-writing, partner and rank forms of the head and transfer grids: no output of the grid itself
 template <class Sel>
 void launch_grid_kernel(const GridOperands& g, unsigned groups, size_t extra_lds, const Sel& sel) {
   if (g.family == 0)
-    launch_grid_family<0>(g, groups, extra_lds, nullptr, nullptr, sel);
+    launch_grid_family<0>(g, groups, extra_lds, GridOut{}, sel);
   else
-    launch_grid_family<1>(g, groups, extra_lds, nullptr, nullptr, sel);
+    launch_grid_family<1>(g, groups, extra_lds, GridOut{}, sel);
 }
 
 }  // namespace impnn

@@ -87,9 +87,14 @@ int launch_grid_topk(const GridTopkCall& c) {
     launch_grid_kernel(g, G, sel_lds, sel);
   }
   if (int rc = check_launch(g.family == 0 ? "head_grid_topk" : "transfer_head_grid_topk")) return rc;
-  const int mcap = select_capacity(c.k, kMergeRound);
-  grid_select_merge_kernel<<<nT, 256, select_lds_bytes(1, mcap), g.stream>>>(ws, G, nT, c.k, mcap, c.largest, (uint32_t)g.A,
-                                                                           c.values, c.cation, c.anion);
+  return launch_grid_topk_merge(ws, G, nT, c.k, c.largest, g.A, c.values, c.cation, c.anion, g.stream);
+}
+
+int launch_grid_topk_merge(const unsigned long long* ws, int G, int nT, int k, int largest, int A, float* values,
+                           int32_t* cation, int32_t* anion, hipStream_t s) {
+  const int mcap = select_capacity(k, kMergeRound);
+  grid_select_merge_kernel<<<nT, 256, select_lds_bytes(1, mcap), s>>>(ws, G, nT, k, mcap, largest, (uint32_t)A, values,
+                                                                    cation, anion);
   return check_launch("grid_select_merge");
 }
 

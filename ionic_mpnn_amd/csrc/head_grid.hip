@@ -61,7 +61,7 @@ int head_grid_max_temperatures() { return kGridMaxT; }
 int launch_head_grid(const GridOperands& g, float* out, float* params) {
   const GridTiles tiles = grid_tiles(0, g.C, g.A);
   if (int rc = grid_tiles_fit("head_grid", tiles)) return rc;
-  launch_grid_family<0>(g, (unsigned)tiles.count(), 0, out, params);  // <= 50.0 KiB of LDS (kind 0), 41.8 KiB (kind 1)
+  launch_grid_family<0>(g, (unsigned)tiles.count(), 0, GridOut{out, params});  // <= 50.0 KiB of LDS (kind 0), 41.8 KiB (kind 1)
   return check_launch("head_grid");
 }
 

@@ -117,7 +117,7 @@ int launch_transfer_ion_half(int ion, const float* pooled, const float* const* w
 int launch_transfer_head_grid(const GridOperands& g, float* out) {
   const GridTiles tiles = grid_tiles(1, g.C, g.A);
   if (int rc = grid_tiles_fit("transfer_head_grid", tiles)) return rc;
-  launch_grid_family<1>(g, (unsigned)tiles.count(), 0, out, nullptr);
+  launch_grid_family<1>(g, (unsigned)tiles.count(), 0, GridOut{out});
   return check_launch("transfer_head_grid");
 }
 

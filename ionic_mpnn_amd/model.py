@@ -103,20 +103,33 @@ class _Screen:
     model) and ``operands``: the ``ops.GridOperands`` of the whole grid, or None where the gathered fallback runs or the
     grid is empty."""
 
+    select_max_t, grid_max_t = ops.SELECT_MAX_T, GRID_MAX_TEMPERATURES  # temperature rows of one launch
+
     def __init__(self, model, cations, anions, T, where, batch_size):
         self.model, self.visc = model, model.kind == "viscosity"
         self.pc, self.pa = model.encode_ions(cations, anions, batch_size)
-        self.C, self.A, self.nT = int(self.pc.shape[0]), int(self.pa.shape[0]), int(T.numel()) if self.visc else 0
+        self.C, self.A = self._counts()
+        self.nT = int(T.numel()) if self.visc else 0
         self.planes = self.nT if self.visc else 1
-        self.mfma = model._transfer_grid_covers() and model.grid_head_mode == "auto"
-        self.covered = model._grid_kernels_cover() or self.mfma
-        if where is not None and where.words.device != self.pc.device:
-            where = data.PairMask(where.words.to(self.pc.device), where.shape)
+        self.mfma, self.covered = self._coverage()
+        if where is not None and where.words.device != model.device:
+            where = data.PairMask(where.words.to(model.device), where.shape)
         self.where, self.T, self.operands = where, None, None
         if self.C > 0 and self.A > 0:
             self.T = T.to(model.device) if self.visc else None
             if self.covered:
-                self.operands = model._grid_operands(self.pc, self.pa, self.T, self.mfma)
+                self.operands = self._operands()
+
+    def _operands(self):
+        return self.model._grid_operands(self.pc, self.pa, self.T, self.mfma)
+
+    def _counts(self):
+        return int(self.pc.shape[0]), int(self.pa.shape[0])
+
+    def _coverage(self):
+        """(mfma, covered) of the model."""
+        mfma = self.model._transfer_grid_covers() and self.model.grid_head_mode == "auto"
+        return mfma, self.model._grid_kernels_cover() or mfma
 
     def default_pairs(self, select, workspace_per_pair=None):
         """``max_pairs_per_launch`` where the caller gives none.  A selecting launch: the most its pair index takes,
@@ -125,20 +138,20 @@ class _Screen:
         if select:
             return SCREEN_MAX_PAIRS if workspace_per_pair is None else min(
                 SCREEN_MAX_PAIRS, max(1, int(4 * GRID_OUTPUT_BUDGET / workspace_per_pair)))
-        pairs = max(1, GRID_OUTPUT_BUDGET // max(min(self.nT, GRID_MAX_TEMPERATURES), 1))
+        pairs = max(1, GRID_OUTPUT_BUDGET // max(min(self.nT, self.grid_max_t), 1))
         return pairs if self.covered else min(pairs, GRID_GATHER_PAIRS)
 
     def tiles(self, max_pairs_per_launch, select, workspace_per_pair=None):
         """The host tiling: (lo, hi, t0, t1, operands, where) for every range of cations lo .. hi and of temperature
-        rows t0 .. t1 of one launch - ``select``: a selecting launch (fewer than 2^32 pairs, ops.SELECT_MAX_T
-        temperatures), else a materialising one - with the operands narrowed to the tile (None: the gathered fallback)
+        rows t0 .. t1 of one launch - ``select``: a selecting launch (fewer than 2^32 pairs, ``select_max_t``
+        temperatures), else a materialising one (``grid_max_t``) - with the operands narrowed to the tile (None: the gathered fallback)
         and the mask's rows lo .. hi (None: no mask).  Nothing for an empty grid."""
         if self.C == 0 or self.A == 0:
             return
         if max_pairs_per_launch is None:
             max_pairs_per_launch = self.default_pairs(select, workspace_per_pair)
         step = max(1, min(int(max_pairs_per_launch), SCREEN_MAX_PAIRS if select else 1 << 62) // self.A)
-        t_step = ops.SELECT_MAX_T if select else GRID_MAX_TEMPERATURES
+        t_step = self.select_max_t if select else self.grid_max_t
         for lo in range(0, self.C, step):
             hi = min(self.C, lo + step)
             rows = self.operands.rows(lo, hi) if self.operands is not None else None
@@ -146,6 +159,58 @@ class _Screen:
             for t0 in range(0, self.planes, t_step):
                 t1 = min(self.planes, t0 + t_step)
                 yield lo, hi, t0, t1, rows.temperatures(t0, t1) if rows is not None else None, wh
+
+    def pair_mask(self, lo_b, hi_b, max_pairs_per_launch):
+        """The screen's values within the float32 bounds as a ``data.PairMask`` (``MPNNModel.screen_mask``)."""
+        s, dev = self, self.model.device
+        W = data.mask_row_words(s.A)
+        words = torch.zeros((s.nT, s.C, W) if s.visc else (s.C, W), dtype=torch.int32, device=dev)
+        for lo, hi, t0, t1, g, _ in s.tiles(max_pairs_per_launch, False):
+            if g is not None:
+                got = ops.grid_mask(g, lo_b, hi_b)
+            else:
+                tile = s.grid_tile(lo, hi, t0, t1, g).cpu().numpy()
+                got = data.PairMask.from_bool((tile >= lo_b) & (tile <= hi_b), device=dev).words
+            (words[t0:t1, lo:hi] if s.visc else words[lo:hi])[...] = got
+        return data.PairMask(words, (s.C, s.A, s.nT) if s.visc else (s.C, s.A))
+
+    def top_k(self, k, largest, max_pairs_per_launch):
+        """The screen's k best pairs as a ``data.TopK`` (``MPNNModel.screen_top_k``): the selecting launches' results, or
+        above SCREEN_MAX_K and without a covering kernel the materialised tiles', merged under the selection's order."""
+        s = self
+        A, select = s.A, s.covered and k <= SCREEN_MAX_K
+        # the running best of every row: (values, flat index i * A + j as int64), at most k each
+        best = [(np.empty(0, np.float32), np.empty(0, np.int64)) for _ in range(s.planes)]
+
+        def offer(row, values, flat):
+            v, f = np.concatenate([best[row][0], values]), np.concatenate([best[row][1], flat])
+            order = data.top_k_order(v, f, k, largest)
+            best[row] = (v[order], f[order])
+
+        for lo, hi, t0, t1, g, wh in s.tiles(max_pairs_per_launch, select):
+            if select:
+                v, ci, ai = (x.cpu().numpy() for x in ops.grid_topk(g, k, largest, where=wh.words if wh is not None else None))
+                for r in range(t1 - t0):
+                    used = ci[r] >= 0
+                    offer(t0 + r, v[r][used], (ci[r][used].astype(np.int64) + lo) * A + ai[r][used])
+            else:
+                tile = s.grid_tile(lo, hi, t0, t1, g).cpu().numpy().reshape((hi - lo) * A, -1)
+                flat = np.arange(lo * A, hi * A, dtype=np.int64)
+                if wh is not None:  # only the mask's pairs reach the order
+                    keep = np.flatnonzero(wh.to_bool().reshape(-1))
+                    tile, flat = tile[keep], flat[keep]
+                for r in range(t1 - t0):
+                    order = data.top_k_order(tile[:, r], flat, k, largest)
+                    offer(t0 + r, tile[order, r], flat[order])
+        m = min(k, s.C * A if s.where is None else s.where.count())
+        values = np.empty((s.planes, m), np.float32)
+        cation, anion = np.empty((s.planes, m), np.int64), np.empty((s.planes, m), np.int64)
+        for r, (v, f) in enumerate(best):
+            values[r], cation[r], anion[r] = v, f // max(A, 1), f % max(A, 1)
+        values[np.isnan(values)] = data.QUIET_NAN
+        if not s.visc:
+            values, cation, anion = values[0], cation[0], anion[0]
+        return data.TopK(values, cation, anion)
 
     def grid_tile(self, lo, hi, t0, t1, operands):
         """The tile (lo, hi, t0, t1, operands) of ``tiles``, materialised on the device: (hi - lo, A[, t1 - t0])."""
@@ -1164,17 +1229,7 @@ class MPNNModel:
         if np.isnan(lo_b) or np.isnan(hi_b):
             raise ValueError("a screen_mask bound is NaN")
         T = self._screen_request("screen_mask", cations, anions, temperatures, None, max_pairs_per_launch)
-        s = _Screen(self, cations, anions, T, None, batch_size)
-        W = data.mask_row_words(s.A)
-        words = torch.zeros((s.nT, s.C, W) if s.visc else (s.C, W), dtype=torch.int32, device=self.device)
-        for lo, hi, t0, t1, g, _ in s.tiles(max_pairs_per_launch, False):
-            if g is not None:
-                got = ops.grid_mask(g, lo_b, hi_b)
-            else:
-                tile = s.grid_tile(lo, hi, t0, t1, g).cpu().numpy()
-                got = data.PairMask.from_bool((tile >= lo_b) & (tile <= hi_b), device=self.device).words
-            (words[t0:t1, lo:hi] if s.visc else words[lo:hi])[...] = got
-        return data.PairMask(words, (s.C, s.A, s.nT) if s.visc else (s.C, s.A))
+        return _Screen(self, cations, anions, T, None, batch_size).pair_mask(lo_b, hi_b, max_pairs_per_launch)
 
     def _screen_request(self, what, cations, anions, temperatures, where, max_pairs_per_launch):
         """The argument rules the six screens share (``what``: the screen's name in the messages) -> the temperatures as
@@ -1227,40 +1282,7 @@ class MPNNModel:
         k = int(k)
         if k < 1:
             raise ValueError("k must be >= 1")
-        s = _Screen(self, cations, anions, T, where, batch_size)
-        A, select = s.A, s.covered and k <= SCREEN_MAX_K
-        # the running best of every row: (values, flat index i * A + j as int64), at most k each
-        best = [(np.empty(0, np.float32), np.empty(0, np.int64)) for _ in range(s.planes)]
-
-        def offer(row, values, flat):
-            v, f = np.concatenate([best[row][0], values]), np.concatenate([best[row][1], flat])
-            order = data.top_k_order(v, f, k, largest)
-            best[row] = (v[order], f[order])
-
-        for lo, hi, t0, t1, g, wh in s.tiles(max_pairs_per_launch, select):
-            if select:
-                v, ci, ai = (x.cpu().numpy() for x in ops.grid_topk(g, k, largest, where=wh.words if wh is not None else None))
-                for r in range(t1 - t0):
-                    used = ci[r] >= 0
-                    offer(t0 + r, v[r][used], (ci[r][used].astype(np.int64) + lo) * A + ai[r][used])
-            else:
-                tile = s.grid_tile(lo, hi, t0, t1, g).cpu().numpy().reshape((hi - lo) * A, -1)
-                flat = np.arange(lo * A, hi * A, dtype=np.int64)
-                if wh is not None:  # only the mask's pairs reach the order
-                    keep = np.flatnonzero(wh.to_bool().reshape(-1))
-                    tile, flat = tile[keep], flat[keep]
-                for r in range(t1 - t0):
-                    order = data.top_k_order(tile[:, r], flat, k, largest)
-                    offer(t0 + r, tile[order, r], flat[order])
-        m = min(k, s.C * A if s.where is None else s.where.count())
-        values = np.empty((s.planes, m), np.float32)
-        cation, anion = np.empty((s.planes, m), np.int64), np.empty((s.planes, m), np.int64)
-        for r, (v, f) in enumerate(best):
-            values[r], cation[r], anion[r] = v, f // max(A, 1), f % max(A, 1)
-        values[np.isnan(values)] = data.QUIET_NAN
-        if not s.visc:
-            values, cation, anion = values[0], cation[0], anion[0]
-        return data.TopK(values, cation, anion)
+        return _Screen(self, cations, anions, T, where, batch_size).top_k(k, largest, max_pairs_per_launch)
 
     def screen_best_partners(self, cations, anions, temperatures=None, m=1, largest=False, where=None,
                              max_pairs_per_launch=None, batch_size=4096):

@@ -734,44 +734,53 @@ def head_ion_mix(kind, ion, pooled, head_weights, fp_size, mixing_size):
 
 
 # ---- the screening family over a cation x anion grid: the operands are validated once (GridOperands), the five
-# operations (grid_values, grid_topk, grid_partners, grid_rank, grid_mask) take either family's, and the named wrappers
+# operations (grid_values, grid_topk, grid_partners, grid_rank, grid_mask) take any family's, and the named wrappers
 # below them are "build the operands, call the operation"
 class GridOperands:
     """The validated operands of the screening family's launches over one cation x anion grid, built by
-    ``head_grid_operands`` (family 0) or ``transfer_grid_operands`` (family 1): the contiguous float32 tensors (``cat``
-    and ``an`` rows, ``T`` or None, ``w``: the packed head or the prepared image), ``kind`` as the C entries take it (0
-    viscosity, 1 melting point and transfer) and, for the head family, ``widths`` = (D, fp_size, mixing_size).  ``lead``
-    and ``trail`` are the arguments every C entry of the family opens and closes with; the operation's own go between.
+    ``head_grid_operands`` (family 0), ``transfer_grid_operands`` (family 1) or ``ensemble_grid_operands`` (family 2):
+    the contiguous float32 tensors (``cat`` and ``an`` rows, ``T`` or None, ``w``: the packed head, the prepared image or
+    the members' tails), ``kind`` as the C entries take it (0 viscosity, 1 melting point and transfer) and ``widths``: (D,
+    fp_size, mixing_size) for the head family, (fp_size, mixing_size) for the ensemble family, whose rows are
+    three-dimensional - (M,C,Mx) and (M,A,Mx), ``members`` = M - and which carries ``kappa`` of its score.  ``lead`` and
+    ``trail`` are the arguments every C entry of the family opens and closes with; the operation's own go between.
     ``rows`` and ``temperatures`` narrow it without validating again (the host tiling of model.py)."""
-    __slots__ = ("family", "kind", "cat", "an", "T", "w", "widths")
+    __slots__ = ("family", "kind", "cat", "an", "T", "w", "widths", "kappa")
 
-    def __init__(self, family, kind, cat, an, T, w, widths=()):
+    def __init__(self, family, kind, cat, an, T, w, widths=(), kappa=0.0):
         self.family, self.kind, self.cat, self.an, self.T, self.w, self.widths = family, kind, cat, an, T, w, widths
+        self.kappa = kappa
 
-    C = property(lambda self: int(self.cat.shape[0]))
-    A = property(lambda self: int(self.an.shape[0]))
+    C = property(lambda self: int(self.cat.shape[-2]))
+    A = property(lambda self: int(self.an.shape[-2]))
     nT = property(lambda self: int(self.T.numel()) if self.T is not None else 0)
-    D = property(lambda self: self.widths[0] if self.widths else None)
+    D = property(lambda self: self.widths[0] if self.family == 0 else None)
+    members = property(lambda self: int(self.cat.shape[0]) if self.family == 2 else 1)
     device = property(lambda self: self.cat.device)
 
     @property
     def lead(self):
+        T = ptr(self.T) if self.T is not None else None
         if self.family == 0:
-            return self.kind, ptr(self.cat), ptr(self.an), ptr(self.T) if self.T is not None else None, ptr(self.w)
+            return self.kind, ptr(self.cat), ptr(self.an), T, ptr(self.w)
+        if self.family == 2:
+            return self.kind, self.members, ptr(self.cat), ptr(self.an), T, ptr(self.w), self.kappa
         return ptr(self.cat), ptr(self.an), ptr(self.w), self.w.numel()
 
     @property
     def trail(self):
-        return (self.C, self.A, self.nT, *self.widths) if self.family == 0 else (self.C, self.A)
+        return (self.C, self.A, self.nT, *self.widths) if self.family != 1 else (self.C, self.A)
+
+    def _narrowed(self, cat, T):
+        return GridOperands(self.family, self.kind, cat, self.an, T, self.w, self.widths, self.kappa)
 
     def rows(self, lo, hi):
-        """Cations lo .. hi of the grid."""
-        return GridOperands(self.family, self.kind, self.cat[lo:hi], self.an, self.T, self.w, self.widths)
+        """Cations lo .. hi of the grid (of every member: a copy, the C entries take contiguous rows)."""
+        return self._narrowed(self.cat[lo:hi] if self.family != 2 else self.cat[:, lo:hi].contiguous(), self.T)
 
     def temperatures(self, t0, t1):
         """Temperatures t0 .. t1 of a viscosity grid; any other grid as it is."""
-        return self if self.T is None else GridOperands(self.family, self.kind, self.cat, self.an, self.T[t0:t1], self.w,
-                                                        self.widths)
+        return self if self.T is None else self._narrowed(self.cat, self.T[t0:t1])
 
 
 def _require_params_kind(return_params, k):
@@ -819,11 +828,50 @@ def transfer_grid_operands(u_cat, u_an, image):
     return GridOperands(1, 1, u_cat, u_an, None, image)
 
 
+def ensemble_grid_operands(kind, mix_cat, mix_an, temperatures, tails, fp_size, mixing_size, kappa=0.0):
+    """The operands of a deep ensemble's grid (impnn_ensemble_grid*): M members of ``kind`` -> GridOperands, family 2.
+    ``mix_cat`` (M,C,Mx) and ``mix_an`` (M,A,Mx): member m's ``head_ion_mix`` rows; ``tails`` (M, tail floats): member
+    m's tail of the packed head (impnn_ensemble_grid_tail_floats: ``packed[-tail_floats:]``); ``kappa``: the score is
+    mean + kappa * std, any finite float."""
+    require_gpu(mix_cat, mix_an, tails)
+    mix_cat, mix_an, tails = f32c(mix_cat), f32c(mix_an), f32c(tails)
+    k = HEAD_KINDS[kind]
+    lib = _lib.load()
+    if mix_cat.dim() != 3 or mix_an.dim() != 3 or mix_cat.shape[2] != mixing_size or mix_an.shape[2] != mixing_size \
+            or mix_cat.shape[0] != mix_an.shape[0]:
+        raise ValueError(f"mixing rows must be (M,C,{mixing_size}) and (M,A,{mixing_size}), got {tuple(mix_cat.shape)} "
+                         f"and {tuple(mix_an.shape)}")
+    M = int(mix_cat.shape[0])
+    if not 1 <= M <= lib.impnn_ensemble_grid_max_members():
+        raise ValueError(f"an ensemble grid takes 1 to {lib.impnn_ensemble_grid_max_members()} members, got {M}")
+    if tuple(tails.shape) != (M, lib.impnn_ensemble_grid_tail_floats(k, fp_size, mixing_size)):
+        raise ValueError("the members' tails have the wrong shape")
+    kappa = C.c_float(kappa).value  # as the kernels see it: float32
+    if kappa != kappa or kappa in (float("inf"), float("-inf")):
+        raise ValueError("kappa must be finite")
+    T = None
+    if k == 0:
+        if temperatures is None:
+            raise ValueError("the viscosity grid needs temperatures")
+        require_gpu(temperatures)
+        T = f32c(temperatures).reshape(-1)
+    elif temperatures is not None:
+        raise ValueError("the melting-point grid takes no temperatures")
+    return GridOperands(2, k, mix_cat, mix_an, T, tails, (fp_size, mixing_size), kappa)
+
+
 def grid_values(g, return_params=False):
     """The materialised grid of ``g`` (impnn_head_grid / impnn_transfer_head_grid): what ``head_grid`` /
-    ``transfer_head_grid`` return for the same operands."""
+    ``transfer_head_grid`` return for the same operands.  An ensemble grid (impnn_ensemble_grid): (mean, std, score)."""
     _require_params_kind(return_params, g.kind)
     dev = g.device
+    if g.family == 2:
+        if return_params:
+            raise ValueError("return_params: an ensemble grid has no VFT parameters of its own")
+        outs = [torch.empty((g.C, g.A, g.nT) if g.kind == 0 else (g.C, g.A), dtype=torch.float32, device=dev) for _ in range(3)]
+        with torch.cuda.device(dev):
+            check(_lib.load().impnn_ensemble_grid(*g.lead, *[ptr(o) for o in outs], *g.trail, stream_ptr()))
+        return tuple(outs)
     out = torch.empty((g.C, g.A, g.nT) if g.kind == 0 else (g.C, g.A), dtype=torch.float32, device=dev)
     params = torch.empty(g.C, g.A, 3, dtype=torch.float32, device=dev) if return_params else None
     lib = _lib.load()
@@ -837,8 +885,14 @@ def grid_values(g, return_params=False):
 
 
 def _grid_entry(g, name):
-    """The C entry ``name`` of g's family: impnn_head_grid_<name> or impnn_transfer_head_grid_<name>."""
-    return getattr(_lib.load(), ("impnn_head_grid_", "impnn_transfer_head_grid_")[g.family] + name)
+    """The C entry ``name`` of g's family: impnn_head_grid_<name>, impnn_transfer_head_grid_<name> or
+    impnn_ensemble_grid_<name>."""
+    return getattr(_lib.load(), ("impnn_head_grid_", "impnn_transfer_head_grid_", "impnn_ensemble_grid_")[g.family] + name)
+
+
+def _refuse_ensemble(g):
+    if g.family == 2:
+        raise NotImplementedError("ensemble grids: partners / rank are not built")
 
 
 def grid_topk(g, k, largest=False, workgroups=0, where=None):
@@ -848,7 +902,8 @@ def grid_topk(g, k, largest=False, workgroups=0, where=None):
     if where is not None:
         where = _mask_words(where, g.C, g.A, g.device)
     with torch.cuda.device(g.device):
-        values, cation, anion, ws, nbytes = _grid_topk_outputs(_lib.load(), g.family, g.C, g.A, g.nT, k, workgroups, g.device)
+        values, cation, anion, ws, nbytes = _grid_topk_outputs(_lib.load(), g.family, g.C, g.A, g.nT, k, workgroups, g.device,
+                                                               g.members)
         mask = () if where is None else (ptr(where),)
         check(_grid_entry(g, "topk" if where is None else "topk_where")(
             *g.lead, *mask, k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, *g.trail,
@@ -859,6 +914,7 @@ def grid_topk(g, k, largest=False, workgroups=0, where=None):
 def grid_partners(g, m=1, largest=False, where=None):
     """Each ion's m best partners over ``g``'s grid (impnn_*_grid_partners): what ``head_grid_partners`` /
     ``transfer_head_grid_partners`` return for the same operands."""
+    _refuse_ensemble(g)
     m = int(m)
     if where is not None:
         where = _mask_words(where, g.C, g.A, g.device)
@@ -872,6 +928,7 @@ def grid_partners(g, m=1, largest=False, where=None):
 def grid_rank(g, k, largest=False, where=None, mask=False, workgroups=0):
     """The k-th best pair of ``g``'s grid and, with ``mask``, the k best as mask words (impnn_*_grid_rank): what
     ``head_grid_rank`` / ``transfer_head_grid_rank`` return for the same operands."""
+    _refuse_ensemble(g)
     k, workgroups = int(k), int(workgroups)
     if where is not None:
         where = _mask_words(where, g.C, g.A, g.device)
@@ -964,10 +1021,13 @@ SELECT_MAX_K = 1024
 SELECT_MAX_T = 4
 
 
-def _grid_topk_outputs(lib, family, C_, A_, nT, k, workgroups, dev):
+def _grid_topk_outputs(lib, family, C_, A_, nT, k, workgroups, dev, members=1):
     rows = max(nT, 1)
     need = C.c_size_t(0)
-    check(lib.impnn_grid_topk_workspace_bytes(family, C_, A_, nT, k, workgroups, C.byref(need)))
+    if family == 2:  # the ensemble grid has its own query: its temperature limit depends on the members
+        check(lib.impnn_ensemble_grid_topk_workspace_bytes(members, C_, A_, nT, k, workgroups, C.byref(need)))
+    else:
+        check(lib.impnn_grid_topk_workspace_bytes(family, C_, A_, nT, k, workgroups, C.byref(need)))
     values = torch.empty(rows, k, dtype=torch.float32, device=dev)
     cation = torch.empty(rows, k, dtype=torch.int32, device=dev)
     anion = torch.empty(rows, k, dtype=torch.int32, device=dev)

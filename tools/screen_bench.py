@@ -8,6 +8,7 @@ python tools/screen_bench.py --select [--quick] [--only ...]            -> the t
 python tools/screen_bench.py --select --where FRACTION [--quick]        -> the constrained screen instead (see below)
 python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each ion's best partners instead (see below)
 python tools/screen_bench.py --rank [--where FRACTION] [--quick]        -> the best-k pair mask instead (see below)
+python tools/screen_bench.py --ensemble M [--select] [--where FRACTION] [--size N]  -> a deep ensemble instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -42,7 +43,14 @@ alternating rounds after a warm-up of each, wall time, median and spread; the tw
 the launches of one rank call alone (impnn_head_grid_rank / impnn_transfer_head_grid_rank: a counting and a step launch
 per digit, ops.rank_passes of them, and the mask launch; a sweep above ops.SELECT_MAX_T temperatures takes several calls)
 against the materialising launch of the same C x A x nT, 10 calls between two HIP events, three rounds each in turn, and
-the rank cut alone (no mask launch).  With --where F both ways run under one random pair mask of density F."""
+the rank cut alone (no mask launch).  With --where F both ways run under one random pair mask of density F.
+
+--ensemble M: ModelEnsemble of M viscosity models (atom_dim 32, 3 steps, seeds 1 .. M) over N x N pairs (--size, default
+4096) at 298.15 K.  Three alternating rounds after a warm-up of each, wall time, median and spread, of
+ensemble.predict_grid(kappa = 1) against the way to the same three grids without it: M predict_grid calls and
+data.ensemble_grid_stats on the host (the two must agree bit for bit).  With --select: ensemble.screen_top_k(k = 100,
+kappa = 1) against the same M grids, the host statistic and data.grid_top_k; with --where F both under one random pair
+mask of density F."""
 import argparse
 import json
 import statistics
@@ -66,9 +74,12 @@ ap.add_argument("--rank", action="store_true", help="time screen_best_mask again
 ap.add_argument("--all-configs", action="store_true", help="with --rank: the small configurations of --select too")
 ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: the constrained screen at this mask density; "
                 "with --partners, --rank: a random mask of this density")
+ap.add_argument("--ensemble", type=int, metavar="M", help="a ModelEnsemble of M viscosity models against M predict_grid calls "
+                "and the host statistic; with --select the top-k on the score")
+ap.add_argument("--size", type=int, default=4096, help="with --ensemble: cations = anions = this many")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners or args.rank  # another table than the default one
+other = args.select or args.partners or args.rank or args.ensemble  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -235,7 +246,42 @@ def same_partners(a, b):
 
 RANK_CONFIGS = ("config2 2048x2048x4", "transfer 1024x1024", "transfer 4096x4096")  # the rows of the selection table
 
-if args.rank:
+if args.ensemble:
+    from ionic_mpnn_amd import ModelEnsemble
+    M, N, kappa = args.ensemble, args.size, 1.0
+    members = []
+    for i in range(M):
+        m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+        m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1 + i, perturb=True))
+        members.append(m)
+    ens = ModelEnsemble(members)
+    cat, _ = species(N, 1)
+    _, an = species(N, 2)
+    where = None
+    if args.where is not None:
+        where = data.PairMask.from_bool(np.random.default_rng(0).random((N, N)) < args.where, device=dev)
+
+    def old_way():
+        stats = data.ensemble_grid_stats(np.stack([m.predict_grid(cat, an, T_ROOM) for m in members]), kappa)
+        return data.grid_top_k(stats[2], 100, False, where) if args.select else stats
+
+    def new_way():
+        if args.select:
+            return ens.screen_top_k(cat, an, T_ROOM, k=100, kappa=kappa, where=where)
+        return ens.predict_grid(cat, an, T_ROOM, kappa=kappa)
+
+    a, b = wall(old_way)[1], wall(new_way)[1]
+    t_old, t_new = [], []
+    for _ in range(3):
+        t_old.append(wall(old_way)[0])
+        t_new.append(wall(new_way)[0])
+    line = {"config": f"ensemble M={M} {N}x{N}x1" + (" select" if args.select else "") +
+            (f" where {args.where}" if where is not None else ""), "members_grids_host_ms": spread(t_old),
+            "ensemble_ms": spread(t_new), "speedup": round(statistics.median(t_old) / statistics.median(t_new), 2),
+            "same_answer": same_top(a, b)}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+elif args.rank:
     todo = [c for c in SELECT_CONFIGS if args.only in (None, c[0]) and (args.all_configs or c[1] in RANK_CONFIGS)]
     for kind, name, D, S, C, A, nT in todo[:1] if args.quick else todo:
         if kind == "viscosity":
