@@ -351,8 +351,11 @@ int impnn_head_grid(int32_t kind, const float* mix_cat, const float* mix_an, con
  *      parameter gradients to dweights[i] (same order and shapes as weights[i]; float atomics, so the sum order
  *      over workgroups is not fixed - fp32 rounding-level run-to-run differences in these ~5k values).
  *      Gradient of clip follows tf.clip_by_value / torch.clamp: passes where min <= x <= max.
- *      D <= 128, F, Mx <= 64 (these entries and the loss entries below).
+ *      D <= 128, F, Mx <= 64 (these entries and the loss entries below).  The backward keeps the weights and their
+ *      gradient sums in LDS: it takes heads of at most impnn_model_head_bwd_max_floats() packed floats
+ *      (impnn_model_head_floats rounded up to 4) and refuses wider ones with IMPNN_E_UNSUPPORTED.
  *      Replaces the autograd tape of train_viscosity.py:189-214 / train_melting_point.py:173-198. */
+int64_t impnn_model_head_bwd_max_floats(void);
 int impnn_model_head_tensors(int32_t kind, const float* pooled_cat, const float* pooled_an,
                              const float* temperature, const float* const* weights, float* out,
                              int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);

@@ -62,6 +62,7 @@ SIGNATURES = {
     "impnn_head_grid": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "impnn_model_head_tensors": (C.c_int, [i32, vp, vp, vp, PP, vp, i32, i32, i32, i32, vp]),
     "impnn_model_head_bwd": (C.c_int, [i32, vp, vp, vp, PP, vp, vp, vp, PP, i32, i32, i32, i32, vp]),
+    "impnn_model_head_bwd_max_floats": (i64, []),
     "impnn_model_head_loss_workspace_floats": (i64, [i32]),
     "impnn_model_head_loss": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "impnn_model_head_loss_bwd": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, PP, i32, i32, i32, i32,

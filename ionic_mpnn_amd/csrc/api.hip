@@ -523,6 +523,8 @@ int impnn_model_head_bwd(int32_t kind, const float* pooled_cat, const float* poo
   return model_head_checked(c, {true, weights && dout && dpooled_cat && dpooled_an && dweights, launch_model_head_bwd});
 }
 
+int64_t impnn_model_head_bwd_max_floats(void) { return model_head_bwd_max_floats(); }
+
 int64_t impnn_model_head_loss_workspace_floats(int32_t B) { return B > 0 ? model_head_loss_workspace_floats(B) : 4; }
 
 int impnn_model_head_loss(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,

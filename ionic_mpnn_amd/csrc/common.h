@@ -221,6 +221,7 @@ struct ModelHeadCall {
   hipStream_t stream;
 };
 int64_t model_head_loss_workspace_floats(int B);
+int64_t model_head_bwd_max_floats();                    // the backward's LDS fit, in packed weight floats
 int launch_model_head(const ModelHeadCall& c);          // a checked call (api.hip)
 int launch_model_head_tensors(const ModelHeadCall& c);  // a checked call (api.hip)
 int launch_model_head_bwd(const ModelHeadCall& c);      // a checked call (api.hip)

@@ -519,6 +519,13 @@ int head_tensor_table(const ModelHeadCall& c, bool with_grads, HeadTensors* ht) 
 
 int64_t model_head_loss_workspace_floats(int B) { return (B + kHeadSPB - 1) / kHeadSPB + 4; }
 
+// The most weight floats (padded to 4) the backward holds: it keeps the weights and their gradient sums in LDS next to
+// the sample vectors.  model.py asks for it before a training pass takes the fused head nodes (ops.HEAD_BWD_MAX_FLOATS).
+int64_t model_head_bwd_max_floats() {
+  const size_t vectors = (size_t)kHeadSPB * (kHdVecStride + 4 * kHeadMaxDim);
+  return (int64_t)((kHeadTableLdsCap / sizeof(float) - vectors) / 2 / 4 * 4);
+}
+
 int launch_model_head(const ModelHeadCall& c) {
   if (int rc = head_widths_covered("model_head", c.D, c.F, c.Mx)) return rc;
   const int wfloats = (int)impnn_model_head_floats(c.kind, c.D, c.F, c.Mx);
@@ -566,7 +573,8 @@ int launch_model_head_bwd(const ModelHeadCall& c) {
     hl.inv_B = 1.0f / (float)c.B;
   }
   const size_t lds = sizeof(float) * (2 * align4(ht.off[ht.n]) + (size_t)kHeadSPB * (kHdVecStride + 4 * kHeadMaxDim));
-  if (lds > kHeadTableLdsCap) return fail(IMPNN_E_UNSUPPORTED, "model_head_bwd: weights do not fit LDS");
+  if ((int64_t)align4(ht.off[ht.n]) > model_head_bwd_max_floats())
+    return fail(IMPNN_E_UNSUPPORTED, "model_head_bwd: weights do not fit LDS");
   if (lds > 48 * 1024)
     (void)hipFuncSetAttribute((const void*)model_head_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int groups = (c.B + kHeadSPB - 1) / kHeadSPB;  // bounded grid: every workgroup flushes ~|weights| atomics once

@@ -372,12 +372,14 @@ __global__ __launch_bounds__(kThThreads) void th_bwd_post(ThTensors ht, const fl
 }
 
 // Per feature: mean_b g and mean_b g * xhat (the two sums of BatchNormalization's backward); dbeta += sum g,
-// dgamma += sum g * xhat where those buffers are given.
+// dgamma += sum g * xhat where those buffers are given, each with its l2 penalty's 2 * l2 * w * dloss as th_param_grads.
 __global__ __launch_bounds__(kThThreads) void th_bn_bwd_stats(const float* __restrict__ a1,
                                                               const float* __restrict__ stat,
                                                               const float* __restrict__ g, float* __restrict__ bst,
                                                               float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                              int B) {
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float l2_gamma,
+                                                              float l2_beta, const float* __restrict__ dloss, int B) {
   __shared__ float red[kThThreads];
   const int tid = threadIdx.x, lane = tid / kThStatLanes, fl = tid % kThStatLanes;
   const int f = blockIdx.x * kThStatLanes + fl;
@@ -403,8 +405,8 @@ __global__ __launch_bounds__(kThThreads) void th_bn_bwd_stats(const float* __res
   if (lane == 0) {
     bst[f] = sg / (float)B;
     bst[kThH1 + f] = sgx / (float)B;
-    if (dbeta) dbeta[f] += sg;
-    if (dgamma) dgamma[f] += sgx;
+    if (dbeta) dbeta[f] += l2_beta != 0.f ? fmaf(2.0f * l2_beta * dloss[0], beta[f], sg) : sg;
+    if (dgamma) dgamma[f] += l2_gamma != 0.f ? fmaf(2.0f * l2_gamma * dloss[0], gamma[f], sgx) : sgx;
   }
 }
 
@@ -569,7 +571,8 @@ int launch_transfer_head_bwd(const TransferHeadCall& c) {
   if (c.bn_batch) {
     th_bn_bwd_stats<<<kThH1 / kThStatLanes, kThThreads, 0, c.stream>>>(c.saved + so.a1, c.saved + so.stat,
                                                                       c.workspace + wo.g, c.workspace + wo.bst, dw[10],
-                                                                      dw[11], B);
+                                                                      dw[11], c.weights[10], c.weights[11], c.l2[10],
+                                                                      c.l2[11], c.dloss, B);
     if (int rc = check_launch("transfer_head_bwd (statistics)")) return rc;
   }
   const bool pooled = c.dpc != nullptr;

@@ -844,7 +844,7 @@ class MPNNModel:
         if trace is None and not differentiable and self._head_kernels_cover():
             return ops.model_head(self.kind, pooled_cat, pooled_an, temperature, self._packed_head(), self.fp_size,
                                   self.mixing_size)  # one launch
-        if trace is None and differentiable and self._head_kernels_cover() and torch.is_grad_enabled():
+        if trace is None and differentiable and self._head_nodes_cover() and torch.is_grad_enabled():
             from . import autograd
             T = temperature if self.kind == "viscosity" else None
             return autograd.ModelHead.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
@@ -924,7 +924,7 @@ class MPNNModel:
         covered = y.shape[0] > 0 and self._head_kernels_cover()
         if self.kind == "transfer" and covered:
             return self._transfer_loss(self._to_device(inputs), y, training)
-        if training and torch.is_grad_enabled() and covered and self._loss_name() == "mse":
+        if training and torch.is_grad_enabled() and covered and self._head_nodes_cover() and self._loss_name() == "mse":
             # head, mse and the l2 penalties as ONE node (impnn_model_head_loss): ~25 launches fewer per step
             from . import autograd
             inputs = self._to_device(inputs)
@@ -1164,6 +1164,15 @@ class MPNNModel:
     def _head_kernels_cover(self):
         """The head kernels (model head, transfer head and their grids) cover the model's widths."""
         return self.atom_dim <= ops.HEAD_MAX_X and max(self.fp_size, self.mixing_size) <= ops.HEAD_MAX_DIM
+
+    def _head_nodes_cover(self):
+        """The one rule of a training pass: it takes the fused head nodes (autograd.ModelHead, ModelHeadLoss,
+        TransferHeadLoss) where the widths are covered AND the model head's backward holds the weights in LDS
+        (ops.model_head_bwd_fits); otherwise the head runs layer by layer.  Inference and the grids need the widths alone."""
+        if not self._head_kernels_cover():
+            return False
+        return self.kind == "transfer" or ops.model_head_bwd_fits(ops.HEAD_KINDS[self.kind], self.atom_dim, self.fp_size,
+                                                                  self.mixing_size)
 
     def _grid_kernels_cover(self):
         return self.kind != "transfer" and self._head_kernels_cover()

@@ -683,6 +683,16 @@ def gather_rows(srcs, dsts, rows):
 # the widths every head kernel covers: kHeadMaxX / kHeadMaxDim of csrc/common.h (tests/test_cabi.py holds them equal)
 HEAD_MAX_X = 128    # pooled width (atom_dim)
 HEAD_MAX_DIM = 64   # fp_size, mixing_size
+# the most packed head floats (rounded up to 4) impnn_model_head_bwd holds in LDS next to their gradient sums: the
+# library's impnn_model_head_bwd_max_floats() (tests/test_head_fuzz_host.py holds them equal)
+HEAD_BWD_MAX_FLOATS = 15360
+
+
+def model_head_bwd_fits(kind, D, fp_size, mixing_size):
+    """Whether impnn_model_head_bwd / impnn_model_head_loss_bwd take a head of these widths (``kind`` 0 / 1): the
+    launcher's LDS fit, which is narrower than the width limits."""
+    n = int(_lib.load().impnn_model_head_floats(kind, D, fp_size, mixing_size))
+    return n > 0 and (n + 3) // 4 * 4 <= HEAD_BWD_MAX_FLOATS
 
 
 def _require_packed_head(head_weights, k, D, fp_size, mixing_size):

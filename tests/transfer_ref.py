@@ -22,9 +22,21 @@ def huber(e, delta):
     return torch.where(a <= delta, 0.5 * e * e, delta * (a - 0.5 * delta))
 
 
-def head(w, pc, pa, training=False, mask=None, bn_batch=None):
-    """-> (pred (B,), new moving mean, new moving variance).  bn_batch: batch statistics (default: ``training``)."""
-    dense = lambda x, n: x @ w[f"{n}/kernel"] + w[f"{n}/bias"]
+# the 18 tensors in the order of impnn_transfer_head's `weights` (include/impnn.h)
+HEAD_TENSORS = ["cat_fp/kernel", "cat_fp/bias", "an_fp/kernel", "an_fp/bias", "cat_proj/kernel", "cat_proj/bias",
+                "an_proj/kernel", "an_proj/bias", "mp_dense_1/kernel", "mp_dense_1/bias", "mp_bn_1/gamma", "mp_bn_1/beta",
+                "mp_dense_2/kernel", "mp_dense_2/bias", "mp_dense_3/kernel", "mp_dense_3/bias", "melting_point/kernel",
+                "melting_point/bias"]
+
+
+def head(w, pc, pa, training=False, mask=None, bn_batch=None, trace=None):
+    """-> (pred (B,), new moving mean, new moving variance).  bn_batch: batch statistics (default: ``training``);
+    trace: a dict that receives every relu layer's pre-activations.  Runs in the dtype of ``w``."""
+    def dense(x, n):
+        z = x @ w[f"{n}/kernel"] + w[f"{n}/bias"]
+        if trace is not None:
+            trace[n] = z.detach()
+        return z
     fc, fa = torch.relu(dense(pc, "cat_fp")), torch.relu(dense(pa, "an_fp"))
     mix = torch.relu(dense(fc, "cat_proj")) + torch.relu(dense(fa, "an_proj"))
     a1 = torch.relu(dense(mix, "mp_dense_1"))
@@ -38,7 +50,7 @@ def head(w, pc, pa, training=False, mask=None, bn_batch=None):
     bn = (a1 - mean) / torch.sqrt(var + BN_EPS) * w["mp_bn_1/gamma"] + w["mp_bn_1/beta"]
     a2 = torch.relu(dense(bn, "mp_dense_2"))
     if training and mask is not None:
-        a2 = a2 * torch.as_tensor(mask, dtype=DT)
+        a2 = a2 * torch.as_tensor(mask, dtype=a2.dtype)
     a3 = torch.relu(dense(a2, "mp_dense_3"))
     return dense(a3, "melting_point").reshape(-1), mm, mv
 
@@ -54,4 +66,14 @@ def loss(w, inputs, y, training=True, mask=None, delta=1.0, fp_l2=1e-4, kind="hu
     e = pred - torch.as_tensor(np.asarray(y, np.float64).reshape(-1))
     per = huber(e, delta) if kind == "huber" else e * e
     reg = fp_l2 * ((w["cat_fp/kernel"] ** 2).sum() + (w["an_fp/kernel"] ** 2).sum())
+    return per.mean() + reg, e, mm, mv
+
+
+def head_loss(w, pc, pa, y, l2, training=True, mask=None, delta=1.0, kind="huber", bn_batch=None, trace=None):
+    """The head alone on given pooled vectors, one lambda per tensor of HEAD_TENSORS:
+    -> (mean L(pred - y) + sum_t l2_t sum(W_t^2), per-sample errors, moving mean, moving variance)."""
+    pred, mm, mv = head(w, pc, pa, training, mask, bn_batch, trace)
+    e = pred - torch.as_tensor(y, dtype=pred.dtype).reshape(-1)
+    per = huber(e, delta) if kind == "huber" else e * e
+    reg = sum(float(lam) * (w[n] ** 2).sum() for n, lam in zip(HEAD_TENSORS, l2) if lam)
     return per.mean() + reg, e, mm, mv
