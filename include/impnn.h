@@ -712,6 +712,59 @@ int impnn_ensemble_grid_topk_where(int32_t kind, int32_t M, const float* mix_cat
                                    void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t F,
                                    int32_t Mx, int32_t workgroups, impnn_stream_t stream);
 
+/* ---- the Pareto front of two objectives over a cation x anion grid: a sound filter on the GPU, from two planes of
+ *      values to a short candidate list that holds the whole front; the caller finishes the front of the candidates.
+ *      A pair (i, j) has the float32 values v1, v2 and the keys k1, k2 of the selection's order (the order-preserving
+ *      image of the float's bits, -0.0 < +0.0, complemented where largest1 / largest2 is 1: smaller is better) and
+ *      flat = i * A + j.  A pair competes if its `where` bit is set (NULL: every pair) and neither value is NaN.  q
+ *      dominates p iff k1(q) <= k1(p) and k2(q) <= k2(p) and (k1(q) < k1(p) or k2(q) < k2(p) or flat(q) < flat(p));
+ *      the front is the competing pairs no competing pair dominates.
+ *      The filter: bucket = (k1 - kmin) >> shift with shift = max(0, bitlength(kmax - kmin) - bits) over the range the
+ *      competing pairs span, bits = impnn_pareto_bucket_bits() (14: a 64 KiB table in LDS); table[b] = the smallest k2 of
+ *      bucket b; stair[b] = the smallest table entry below b.  A competing pair is dropped iff stair[b] <= k2: a lower
+ *      bucket means a strictly smaller k1, so the pair that holds that minimum dominates it.  Every pair of the front
+ *      survives; how many others do depends on the data.
+ *      Stages.  The planes are given in row-blocks: f1, f2 (rows, A) float32 row-major, where NULL or (rows, W) mask
+ *      words (W = impnn_grid_mask_row_words(A)), the rows of one block.  Every stage but begin and staircase is called
+ *      once per row-block, in any order of the blocks, and a stage is complete before the next one starts; all calls
+ *      go to one stream.  The state is the caller's workspace; the library keeps none.
+ *        impnn_pareto_begin      clears the workspace: key range, table, counters
+ *        impnn_pareto_range      kmin, kmax of k1 and the number of competing pairs
+ *        impnn_pareto_minima     the table; persistent workgroups, each with a private table in LDS, flushed once
+ *        impnn_pareto_staircase  stair from table, one workgroup
+ *        impnn_pareto_collect    appends the survivors of the block: values (capacity, 2) = (v1, v2) with the inputs'
+ *                                bits, cation = row0 + row and anion (capacity) int32.  The count runs on past
+ *                                `capacity`; entries beyond it are not written, so a caller that reads a count above
+ *                                its capacity repeats the collect stage alone with larger arrays: restart != 0 on the
+ *                                first block of such a round sets the count to 0 before the launch.
+ *      minima and collect must see the planes, mask and flags range saw (a key outside the range goes to the last
+ *      bucket: nothing is written out of bounds, the result is then unspecified).
+ *      workspace: impnn_pareto_workspace_bytes bytes, 8-byte aligned.  It opens with impnn_pareto_header, which the
+ *      caller may read after a stage: key_min / key_max after range (0xFFFFFFFF / 0 when nothing competes), competing
+ *      after range, candidates after collect.
+ *      Only integer atomics: range, table, counts and the set of candidates do not depend on the schedule; the order
+ *      of the candidate list does.  No float atomics, no workgroup waits for another.
+ *      Checks in order (begin and staircase: null pointer, alignment, workspace size): shape (rows, A >= 0, collect: row0,
+ *      capacity >= 0) and the largest flags (0 or 1; IMPNN_E_BADARG); zero work (rows == 0 or A == 0: IMPNN_OK, nothing
+ *      touched, the count included); null pointers (f1, f2, workspace; the outputs where capacity > 0); alignment
+ *      (planes, mask, outputs 4 bytes, workspace 8); the workspace size (IMPNN_E_WORKSPACE); rows * A <= 2^31 - 1 and
+ *      row0 + rows <= 2^31 - 1 (IMPNN_E_UNSUPPORTED).  No allocation, no synchronisation. */
+typedef struct impnn_pareto_header {
+  uint32_t key_min, key_max;
+  uint64_t competing, candidates, reserved;
+} impnn_pareto_header;
+int32_t impnn_pareto_bucket_bits(void);
+int impnn_pareto_workspace_bytes(size_t* need);
+int impnn_pareto_begin(void* workspace, size_t workspace_bytes, impnn_stream_t stream);
+int impnn_pareto_range(const float* f1, const float* f2, const uint32_t* where, int32_t largest1, int32_t largest2,
+                       void* workspace, size_t workspace_bytes, int32_t rows, int32_t A, impnn_stream_t stream);
+int impnn_pareto_minima(const float* f1, const float* f2, const uint32_t* where, int32_t largest1, int32_t largest2,
+                        void* workspace, size_t workspace_bytes, int32_t rows, int32_t A, impnn_stream_t stream);
+int impnn_pareto_staircase(void* workspace, size_t workspace_bytes, impnn_stream_t stream);
+int impnn_pareto_collect(const float* f1, const float* f2, const uint32_t* where, int32_t largest1, int32_t largest2,
+                         int64_t row0, int32_t restart, float* values, int32_t* cation, int32_t* anion, int64_t capacity,
+                         void* workspace, size_t workspace_bytes, int32_t rows, int32_t A, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

@@ -10,6 +10,7 @@ from .layers import (AddTwoTensors, BondMatrixMessage, ComputeLogEta, Dense, Emb
                      SliceParamB, SliceParamC, register_keras_serializable, reset_uids)
 from .model import MPNNModel, build_melting_point_model, build_model, load_model  # noqa: F401
 from .ensemble import ModelEnsemble  # noqa: F401
+from .pareto import Objective, screen_pareto  # noqa: F401
 
 __all__ = [
     "BondMatrixMessage", "Reduce", "GatedUpdate", "GRUUpdate", "GlobalSumPool", "Embedding", "Dense",

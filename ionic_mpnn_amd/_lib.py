@@ -107,6 +107,13 @@ SIGNATURES = {
     "impnn_ensemble_grid_topk": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, sz] + [i32] * 6 + [vp]),
     "impnn_ensemble_grid_topk_where": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz] + [i32] * 6
                                        + [vp]),
+    "impnn_pareto_bucket_bits": (i32, []),
+    "impnn_pareto_workspace_bytes": (C.c_int, [C.POINTER(sz)]),
+    "impnn_pareto_begin": (C.c_int, [vp, sz, vp]),
+    "impnn_pareto_range": (C.c_int, [vp, vp, vp, i32, i32, vp, sz, i32, i32, vp]),
+    "impnn_pareto_minima": (C.c_int, [vp, vp, vp, i32, i32, vp, sz, i32, i32, vp]),
+    "impnn_pareto_staircase": (C.c_int, [vp, sz, vp]),
+    "impnn_pareto_collect": (C.c_int, [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, i64, vp, sz, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

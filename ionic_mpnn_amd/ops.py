@@ -5,9 +5,10 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, data
 from ._lib import check, f32c, i32c, ptr, require_gpu, stream_ptr
 
 LN_EPS = 1e-3  # keras LayerNormalization default (models/layers.py:139)
@@ -1162,6 +1163,135 @@ def transfer_head_grid_rank(u_cat, u_an, image, k, largest=False, where=None, ma
     without the product (impnn_transfer_head_grid_rank) -> (values (1,), cation (1,), anion (1,), count (1,), words
     (C,W) or None) on the device, as ``head_grid_rank``; ``where`` as there."""
     return grid_rank(transfer_grid_operands(u_cat, u_an, image), k, largest, where, mask, workgroups)
+
+
+# ---- the Pareto front of two objectives (csrc/grid_pareto.hip, impnn_pareto_*): a filter over device planes, then the
+# exact front of its few candidates on the host
+PARETO_DEFAULT_CAPACITY = 4096
+
+
+class ParetoFilter:
+    """The staged Pareto filter over row-blocks of two (rows, A) float32 device planes: ``begin``, then ``range`` for
+    every block, ``minima`` for every block, ``staircase``, ``collect`` for every block - a stage is complete before the
+    next starts - and ``candidates``.  ``largest``: a flag per objective; ``capacity``: entries of the candidate arrays.
+    Owns the workspace and the candidate arrays on ``device``; every call goes to the current stream."""
+
+    def __init__(self, A, largest=(False, False), capacity=PARETO_DEFAULT_CAPACITY, device=None):
+        if len(largest) != 2:
+            raise ValueError("largest must hold one flag per objective")
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1")
+        self.lib, self.A, self.device = _lib.load(), int(A), torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ionic_mpnn_amd runs on the MI355X HIP path only (there is no CPU fallback)")
+        if self.device.index is None:  # as a tensor names its device
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.largest = (int(bool(largest[0])), int(bool(largest[1])))
+        need = C.c_size_t(0)
+        check(self.lib.impnn_pareto_workspace_bytes(C.byref(need)))
+        self.nbytes = need.value
+        self.ws = torch.empty(self.nbytes // 8, dtype=torch.int64, device=self.device)
+        self.restart = False
+        self._allocate(capacity)
+
+    def _allocate(self, capacity):
+        self.capacity = int(capacity)
+        self.values = torch.empty(self.capacity, 2, dtype=torch.float32, device=self.device)
+        self.cation = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+        self.anion = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+
+    def _block(self, f1, f2, where_words):
+        require_gpu(f1, f2, where_words)
+        if f1.dtype != torch.float32 or f2.dtype != torch.float32 or f1.dim() != 2 or f1.shape != f2.shape \
+                or f1.shape[1] != self.A or not f1.is_contiguous() or not f2.is_contiguous() \
+                or f1.device != self.device or f2.device != self.device:
+            raise ValueError(f"a row-block is two contiguous float32 (rows,{self.A}) planes on {self.device}, got "
+                             f"{f1.dtype} {tuple(f1.shape)} and {f2.dtype} {tuple(f2.shape)}")
+        rows = int(f1.shape[0])
+        if where_words is not None:
+            where_words = _mask_words(where_words, rows, self.A, self.device)
+        return (ptr(f1), ptr(f2), ptr(where_words) if where_words is not None else None, *self.largest), rows, where_words
+
+    def begin(self):
+        with torch.cuda.device(self.device):
+            check(self.lib.impnn_pareto_begin(ptr(self.ws), self.nbytes, stream_ptr()))
+        self.restart = False
+
+    def range(self, f1, f2, where_words=None):
+        lead, rows, keep = self._block(f1, f2, where_words)
+        with torch.cuda.device(self.device):
+            check(self.lib.impnn_pareto_range(*lead, ptr(self.ws), self.nbytes, rows, self.A, stream_ptr()))
+
+    def minima(self, f1, f2, where_words=None):
+        lead, rows, keep = self._block(f1, f2, where_words)
+        with torch.cuda.device(self.device):
+            check(self.lib.impnn_pareto_minima(*lead, ptr(self.ws), self.nbytes, rows, self.A, stream_ptr()))
+
+    def staircase(self):
+        with torch.cuda.device(self.device):
+            check(self.lib.impnn_pareto_staircase(ptr(self.ws), self.nbytes, stream_ptr()))
+
+    def collect(self, f1, f2, where_words=None, row0=0):
+        lead, rows, keep = self._block(f1, f2, where_words)
+        with torch.cuda.device(self.device):
+            check(self.lib.impnn_pareto_collect(*lead, int(row0), int(self.restart), ptr(self.values), ptr(self.cation),
+                                                ptr(self.anion), self.capacity, ptr(self.ws), self.nbytes, rows, self.A,
+                                                stream_ptr()))
+        if rows > 0 and self.A > 0:
+            self.restart = False
+
+    def header(self):
+        """(key_min, key_max, competing, candidates) of the workspace's impnn_pareto_header: a device-to-host copy."""
+        head = self.ws[:4].cpu().numpy()
+        keys = head[:1].view(np.uint32)
+        return int(keys[0]), int(keys[1]), int(head[1]), int(head[2])
+
+    def grow(self, capacity):
+        """Larger candidate arrays for a repeated collect stage; the next ``collect`` restarts the count."""
+        self._allocate(capacity)
+        self.restart = True
+
+    def candidates(self):
+        """-> (values (n,2) float32, cation (n,), anion (n,) int64 numpy, count, competing): the entries written, n =
+        min(count, capacity), in no order; ``count`` above the capacity: ``grow`` and collect again."""
+        _, _, competing, count = self.header()
+        n = min(count, self.capacity)
+        return (self.values[:n].cpu().numpy(), self.cation[:n].cpu().numpy().astype(np.int64),
+                self.anion[:n].cpu().numpy().astype(np.int64), count, competing)
+
+
+def pareto_run(filt, blocks):
+    """The stages of ``filt`` over ``blocks``, a callable that yields (f1, f2, where_words, row0) for every row-block
+    anew on each call, with ``collect`` repeated at a larger capacity while the count exceeds it -> ``data.ParetoFront``:
+    the exact front of the candidates, finished on the host."""
+    filt.begin()
+    for stage in (filt.range, filt.minima):
+        for f1, f2, wh, _ in blocks():
+            stage(f1, f2, wh)
+    filt.staircase()
+    while True:
+        for f1, f2, wh, row0 in blocks():
+            filt.collect(f1, f2, wh, row0)
+        values, cation, anion, count, competing = filt.candidates()
+        if count <= filt.capacity:
+            break
+        filt.grow(count)
+    flat = cation * filt.A + anion
+    keep = data.pareto_front_of(data.select_keys(values[:, 0], bool(filt.largest[0])),
+                                data.select_keys(values[:, 1], bool(filt.largest[1])), flat)
+    return data.ParetoFront(values[keep].reshape(-1, 2), cation[keep], anion[keep], competing)
+
+
+def pareto_front(f1, f2, largest=(False, False), where=None, capacity=None):
+    """The Pareto front of two (C,A) float32 device planes (impnn_pareto_*): what ``data.pareto_front`` returns for
+    their host copies.  ``where``: the (C,W) words of a pair mask; ``capacity``: entries of the first candidate arrays."""
+    require_gpu(f1, f2)
+    if f1.dim() != 2:
+        raise ValueError(f"the two objectives must be (C,A) planes, got {tuple(f1.shape)}")
+    filt = ParetoFilter(f1.shape[1], largest, PARETO_DEFAULT_CAPACITY if capacity is None else capacity, f1.device)
+    if f1.shape[0] == 0 or f1.shape[1] == 0:
+        return data.ParetoFront(np.empty((0, 2), np.float32), np.empty(0, np.int64), np.empty(0, np.int64), 0)
+    return pareto_run(filt, lambda: [(f1, f2, where, 0)])
 
 
 def head_grid_mask(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing_size, lo, hi):

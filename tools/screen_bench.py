@@ -9,6 +9,7 @@ python tools/screen_bench.py --select --where FRACTION [--quick]        -> the c
 python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each ion's best partners instead (see below)
 python tools/screen_bench.py --rank [--where FRACTION] [--quick]        -> the best-k pair mask instead (see below)
 python tools/screen_bench.py --ensemble M [--select] [--where FRACTION] [--size N]  -> a deep ensemble instead (see below)
+python tools/screen_bench.py --pareto [--where FRACTION] [--size N]     -> the Pareto front of two models instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -50,7 +51,14 @@ the rank cut alone (no mask launch).  With --where F both ways run under one ran
 ensemble.predict_grid(kappa = 1) against the way to the same three grids without it: M predict_grid calls and
 data.ensemble_grid_stats on the host (the two must agree bit for bit).  With --select: ensemble.screen_top_k(k = 100,
 kappa = 1) against the same M grids, the host statistic and data.grid_top_k; with --where F both under one random pair
-mask of density F."""
+mask of density F.
+
+--pareto: screen_pareto of a viscosity model at 298.15 K against a melting-point model (atom_dim 32, 3 steps) over N x N
+pairs (--size, default 4096), both minimised, against the way to the same front without it: two predict_grid calls and
+data.pareto_front on the host.  Three alternating rounds after a warm-up of each, wall time, median and spread; the two
+ways must return the same front.  Plus the filter's stages alone over the two resident planes (begin, range, minima,
+staircase, collect: 10 runs between two HIP events, three rounds), and the candidate count against the front size.  With
+--where F both ways run under one random pair mask of density F."""
 import argparse
 import json
 import statistics
@@ -76,10 +84,12 @@ ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: 
                 "with --partners, --rank: a random mask of this density")
 ap.add_argument("--ensemble", type=int, metavar="M", help="a ModelEnsemble of M viscosity models against M predict_grid calls "
                 "and the host statistic; with --select the top-k on the score")
-ap.add_argument("--size", type=int, default=4096, help="with --ensemble: cations = anions = this many")
+ap.add_argument("--pareto", action="store_true", help="time screen_pareto (viscosity x melting point) against two predict_grid "
+                "calls and data.pareto_front on the host")
+ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --pareto: cations = anions = this many")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners or args.rank or args.ensemble  # another table than the default one
+other = args.select or args.partners or args.rank or args.ensemble or args.pareto  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -246,7 +256,49 @@ def same_partners(a, b):
 
 RANK_CONFIGS = ("config2 2048x2048x4", "transfer 1024x1024", "transfer 4096x4096")  # the rows of the selection table
 
-if args.ensemble:
+if args.pareto:
+    from ionic_mpnn_amd import Objective, screen_pareto
+    N = args.size
+    v = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+    v.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
+    mp = MM.build_melting_point_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+    mp.load_weights(weights.init_weights("melting_point", Va, Vb, atom_dim=32, bond_dim=32 * 32, num_steps=3, seed=2, perturb=True))
+    cat, _ = species(N, 1)
+    _, an = species(N, 2)
+    where_b = None if args.where is None else np.random.default_rng(5).random((N, N)) < float(args.where)
+    where = None if where_b is None else data.PairMask.from_bool(where_b, device=dev)
+    objectives = [Objective(v, T_ROOM), Objective(mp)]
+    old_way = lambda: data.pareto_front(v.predict_grid(cat, an, T_ROOM)[:, :, 0], mp.predict_grid(cat, an), where=where_b)
+    new_way = lambda: screen_pareto(objectives, cat, an, where=where)
+    a, b = wall(old_way)[1], wall(new_way)[1]
+    t_old, t_new = [], []
+    for _ in range(3):
+        t_old.append(wall(old_way)[0])
+        t_new.append(wall(new_way)[0])
+    # the stages alone, the two planes resident
+    with torch.no_grad():
+        f1 = torch.from_numpy(np.ascontiguousarray(v.predict_grid(cat, an, T_ROOM)[:, :, 0])).to(dev)
+        f2 = torch.from_numpy(mp.predict_grid(cat, an)).to(dev)
+    words = None if where is None else where.words
+    filt = ops.ParetoFilter(N, (False, False), ops.PARETO_DEFAULT_CAPACITY, dev)
+    stages = {"begin": filt.begin, "range": lambda: filt.range(f1, f2, words), "minima": lambda: filt.minima(f1, f2, words),
+              "staircase": filt.staircase, "collect": lambda: filt.collect(f1, f2, words, 0)}
+    for fn in stages.values():
+        fn()
+    _, _, _, count, competing = filt.candidates()
+    stage_us = {n: [] for n in stages}
+    for _ in range(3):
+        for n, fn in stages.items():
+            stage_us[n].append(timed(lambda: [fn() for _ in range(10)])[0] / 10 * 1e3)
+    line = {"config": f"pareto visc x mp {N}x{N}" + ("" if where is None else " F=%g" % args.where), "C": N, "A": N,
+            "bucket_bits": int(ops._lib.load().impnn_pareto_bucket_bits()), "competing": int(b.competing), "front": int(len(b.cation)),
+            "candidates": int(count), "two_grids_plus_host_front_ms": spread(t_old), "screen_pareto_ms": spread(t_new),
+            "speedup": round(statistics.median(t_old) / statistics.median(t_new), 2),
+            "stage_launch_us": {n: spread(x) for n, x in stage_us.items()},
+            "same_answer": bool(a.competing == b.competing and same_top(a[:3], b[:3]))}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+elif args.ensemble:
     from ionic_mpnn_amd import ModelEnsemble
     M, N, kappa = args.ensemble, args.size, 1.0
     members = []
