@@ -299,6 +299,20 @@ size_t impnn_encoder_prepared_bytes(int32_t D, int32_t S, int32_t Vb, int32_t mo
 int impnn_encoder_prepare_weights(const float* weights, const float* bond_table, int32_t D, int32_t K,
                                   int32_t S, int32_t Vb, int32_t mode, void* prepared,
                                   size_t prepared_bytes, impnn_stream_t stream);
+/* The same with the atom embedding table folded in (modes 2 / 3 at atom_dim 32, S >= 1).  In step 0 a source row holds
+ * atom_table[atom id] - or zeros, for an id outside [0,Va) - so the step-0 message of an edge is one of Vb x (Va + 1)
+ * vectors that depend on the weights only.  These entries append that table (128 B per entry) to the image, each entry
+ * bit for bit what the encoder's message phase computes, and mark it in the image; the encoder then gathers step 0's
+ * messages instead of multiplying them.  impnn_encoder_run / impnn_encoder_fused_prepared find the table by themselves
+ * and use it only when Va, Vb and S of the launch are the image's - any other image, one from
+ * impnn_encoder_prepare_weights included, runs as before, with the same results.  The table is built only while it stays
+ * below 2 MiB (Vb * (Va + 1) * 128 B: half of one XCD's L2); beyond that, and for every other mode or atom_dim, the
+ * size and the image are those of the two entries above.  The image must be rebuilt when atom_table changes.
+ * `atom_table` (Va,D): 16B aligned. */
+size_t impnn_encoder_prepared_bytes_atoms(int32_t D, int32_t S, int32_t Va, int32_t Vb, int32_t mode);
+int impnn_encoder_prepare_weights_atoms(const float* weights, const float* bond_table, const float* atom_table,
+                                        int32_t Va, int32_t D, int32_t K, int32_t S, int32_t Vb, int32_t mode,
+                                        void* prepared, size_t prepared_bytes, impnn_stream_t stream);
 int impnn_encoder_fused_prepared(int32_t n_ions, const int32_t* const* atom_ids,
                                  const int32_t* const* bond_ids, const int32_t* const* conn,
                                  const float* atom_table, int32_t Va, const float* bond_table,

@@ -482,6 +482,27 @@ int impnn_encoder_prepare_weights(const float* weights, const float* bond_table,
   return launch_encoder_prepare(weights, bond_table, D, K, S, Vb, mode, prepared, as_stream(stream));
 }
 
+size_t impnn_encoder_prepared_bytes_atoms(int32_t D, int32_t S, int32_t Va, int32_t Vb, int32_t mode) {
+  if (Va <= 0 || impnn_encoder_prepared_bytes(D, S, Vb, mode) == 0) return 0;
+  return encoder_prepared_bytes_atoms(mode, D, S, Va, Vb);
+}
+
+int impnn_encoder_prepare_weights_atoms(const float* weights, const float* bond_table, const float* atom_table,
+                                        int32_t Va, int32_t D, int32_t K, int32_t S, int32_t Vb, int32_t mode,
+                                        void* prepared, size_t prepared_bytes, impnn_stream_t stream) {
+  REQUIRE(D > 0 && K > 0 && S >= 0 && Vb > 0 && Va > 0, "bad shape");
+  REQUIRE(mode >= 0 && mode <= 3, "mode must be 0 (f32), 1 (f16x2), 2 (f32 typed) or 3 (f32x3 typed)");
+  if (!encoder_fused_supported(mode, 1, 0, D, K, S, mode >= 2 ? Vb : 1))
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_prepare_weights_atoms: mode=%d D=%d K=%d Vb=%d not covered", mode, D, K, Vb);
+  if (S == 0) return IMPNN_OK;
+  REQUIRE(weights && prepared && atom_table && (mode < 2 || bond_table), "null pointer");
+  REQUIRE(aligned16(prepared) && aligned16(atom_table), "prepared buffer and atom_table must be 16B aligned");
+  if (prepared_bytes < encoder_prepared_bytes_atoms(mode, D, S, Va, Vb))
+    return fail(IMPNN_E_WORKSPACE, "encoder_prepare_weights_atoms: buffer %zu < %zu bytes", prepared_bytes,
+                encoder_prepared_bytes_atoms(mode, D, S, Va, Vb));
+  return launch_encoder_prepare_atoms(weights, bond_table, atom_table, Va, D, K, S, Vb, mode, prepared, as_stream(stream));
+}
+
 int impnn_encoder_fused_prepared(int32_t n_ions, const int32_t* const* atom_ids, const int32_t* const* bond_ids,
                                  const int32_t* const* conn, const float* atom_table, int32_t Va,
                                  const float* bond_table, int32_t Vb, const void* const* prepared, int32_t mode,

@@ -147,6 +147,27 @@ inline size_t typed_prepared_floats(int S, int Vb, bool x3 = false) {
   return s * (x3 ? kXUpdSlot : kTUpdSlot) + s * (size_t)Vb * kTMatFloats + (size_t)Vb * kTMatFloats;
 }
 
+// ---- step-0 message table.  In step 0 a source row holds atom_table[atom id] (or zeros: a slack row, an id outside
+// [0, Va)), so the message m_e = A_0[type_e] h_0[src_e] is one of Vb x (Va + 1) vectors that depend on the weights only:
+//   M0[v][a][0..31], v < Vb, a <= Va (column Va: the message of a zero row), 128 B per entry,
+// appended to the prepared buffer behind typed_prepared_floats() by the with-atoms prepare entry, each entry bit for bit
+// what the message phase computes (encoder_typed.hip: group_messages is the body of both).  The encoder's step 0 then
+// gathers rows of it instead of multiplying.  Built only while the table stays below kM0CapBytes: half of one XCD's
+// 4 MiB L2, which - with the XCD-aware share numbering - holds one ion's image (a reasoned bound, not a measured one).
+// A header in the unused tail of step 0's update slot (floats [kTUpdLds, kTUpdSlot) / [kXUpdLds, kXUpdSlot), zeros in an
+// image without a table: typed_image_kernel clears the whole slot) says whether a table follows and for which
+// vocabularies and step count; the encoder uses the table only when they equal the launch's.
+constexpr int32_t kM0Magic = 0x6d30746d;
+constexpr size_t kM0CapBytes = (size_t)2 << 20;
+struct M0Header {
+  int32_t magic, Va, Vb, S;
+};
+inline size_t m0_table_floats(int S, int Va, int Vb) {  // 0: no table for this shape
+  if (S < 1 || Va < 1 || Vb < 1) return 0;
+  const size_t n = (size_t)Vb * ((size_t)Va + 1) * kD;
+  return n * sizeof(float) <= kM0CapBytes ? n : 0;
+}
+
 constexpr int kShareCap = kECap;  // molecules of one share that plan_chunks resolves in LDS
 // Shares are equal in virtual rows, per ion and in proportion to the ion's rows - so where molecules are tiny (halide
 // anions: one atom, no bond) a share would hold as many molecules as rows.  Every molecule therefore counts at least
@@ -286,6 +307,7 @@ struct TEncParams {
   const float* atom_table;
   const float* upd[2];   // per ion: S update slots (kTUpdSlot floats each)
   const float* tmat[2];  // per ion: S x Vb type matrices in operand order
+  const float* m0[2];    // per ion: where a step-0 message table would lie (read only if the image's M0Header says so)
   const int32_t* nsub;
   const int32_t* desc;
   const unsigned char* rec;

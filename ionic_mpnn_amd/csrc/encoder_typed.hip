@@ -18,6 +18,9 @@
 //     of one d are 16 consecutive slots: conflict-free), then GatedUpdate (models/layers.py:142-156) exactly as in
 //     encoder_fused.hip's f32 mode, h updated in place.
 //
+//   step 0: h[src] is atom_table[atom id] (or zeros), so its messages depend on the weights alone; an image prepared with
+//     the atom table carries them as a table (encoder_layout.h: M0Header) and the chunk prologue gathers them instead.
+//
 // MFMA work per row is 12 D^2 (update) + 2 D^2 per in-edge, against (12 + 2 K) D^2 per row in the pull form:
 // 2.7 kflop instead of 28.7 kflop per row for the message at bond_dim 8 and 1.7 in-edges per row.
 #include "encoder_device.h"
@@ -129,6 +132,78 @@ struct Run {
   f32x4 bq[4];
   Grp first;
 };
+
+// The messages of one group: 16 MFMAs on two accumulator chains, the two k-halves joined by one v_permlane32_swap per
+// edge pair.  aq: the lane's two h values (see Grp); bq: the lane's half row of the type matrix.  Returns, for feature
+// l & 31, the message of edge l >> 5 (m01) and of edge 2 + (l >> 5) (m23).  Nothing in a 4x4x1 block depends on the other
+// edges of the group, so an edge's message is a function of (type matrix, source row) alone - which is what lets the
+// step-0 table kernel below reproduce the message phase's bits by calling this very function.
+__device__ __forceinline__ void group_messages(const f32x2v aq, const f32x4 (&bq)[4], float& m01, float& m23) {
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+#ifndef IMPNN_DIAG_NO_MSG_MFMA  // (diagnostics builds only: wrong results)
+  // instruction k (= h column 16 kh + k): A from register k & 1, block k >> 1; B = the lane's matrix element k.
+  // (Two accumulator chains; four were measured: +4 % kernel time, the registers cost more than the s_nops.)
+  acc0 = mfma1<0>(aq[0], bq[0][0], acc0);
+  acc1 = mfma1<0>(aq[1], bq[0][1], acc1);
+  acc0 = mfma1<1>(aq[0], bq[0][2], acc0);
+  acc1 = mfma1<1>(aq[1], bq[0][3], acc1);
+  acc0 = mfma1<2>(aq[0], bq[1][0], acc0);
+  acc1 = mfma1<2>(aq[1], bq[1][1], acc1);
+  acc0 = mfma1<3>(aq[0], bq[1][2], acc0);
+  acc1 = mfma1<3>(aq[1], bq[1][3], acc1);
+  acc0 = mfma1<4>(aq[0], bq[2][0], acc0);
+  acc1 = mfma1<4>(aq[1], bq[2][1], acc1);
+  acc0 = mfma1<5>(aq[0], bq[2][2], acc0);
+  acc1 = mfma1<5>(aq[1], bq[2][3], acc1);
+  acc0 = mfma1<6>(aq[0], bq[3][0], acc0);
+  acc1 = mfma1<6>(aq[1], bq[3][1], acc1);
+  acc0 = mfma1<7>(aq[0], bq[3][2], acc0);
+  acc1 = mfma1<7>(aq[1], bq[3][3], acc1);
+#else
+  acc0[0] = aq[0] + bq[0][0] + bq[3][3];
+  acc1[1] = aq[1] + bq[1][1] + bq[2][2];
+#endif
+  // acc0 + acc1 as four v_add_f32: as a vector add the compiler emits two v_pk_add_f32, which beside MFMAs cost
+  // more issue time than the four scalar adds (the same IEEE sums either way)
+  float x0 = acc0[0] + acc1[0], x1 = acc0[1] + acc1[1], x2 = acc0[2] + acc1[2], x3 = acc0[3] + acc1[3];
+  // element i of lane l: edge i, feature l & 31, k-half l >> 5.
+  // v_permlane32_swap x, y: lanes 32-63 of x <-> lanes 0-31 of y.  Afterwards x = {x.lo, y.lo},
+  // y = {x.hi, y.hi}, so x + y is edge 0 (2) complete in lanes 0-31 and edge 1 (3) in lanes 32-63.
+  // (Inline asm: the compiler's builtin for this gfx950 instruction folded its two operands into one here.
+  //  The s_nop covers the VALU-write -> permlane-read wait states the assembler does not insert.)
+  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3"
+               : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
+  m01 = x0 + x1;
+  m23 = x2 + x3;
+}
+
+// Step-0 message table (encoder_layout.h: M0Header): one wave per (bond type v, four consecutive atom ids), fed exactly
+// like a group of the message phase - lane l = 32 kh + 4 b + i holds atom_table[a0 + i][16 kh + 2 b] and [.. + 1] (zeros
+// for a0 + i >= Va: column Va is the zero row, beyond it padding), the matrix rows come from step 0's type matrices in
+// the image - so M0[v][a] carries the bits the message phase writes, 0 * inf = NaN in column Va included.
+__global__ __launch_bounds__(256) void typed_m0_kernel(const float* tmat0, const float* atom_table, float* m0,
+                                                       M0Header* hdr, int Va, int Vb, int S) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  const int nga = (Va + 4) >> 2;  // groups of four among the Va + 1 columns
+  if (w < Vb * nga) {
+    const int v = w / nga, a0 = 4 * (w - v * nga);
+    const int kh = lane >> 5, f = lane & 31;
+    const int ai = a0 + (lane & 3);
+    f32x2v aq = {0.f, 0.f};
+    if (ai < Va) aq = *reinterpret_cast<const f32x2v*>(atom_table + (size_t)ai * kD + 16 * kh + 2 * ((lane >> 2) & 7));
+    const float* bp = tmat0 + (size_t)v * kTMatFloats + kh * 512 + f * 4;
+    f32x4 bq[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bq[i] = ld4(bp + i * 128);
+    float m01, m23;
+    group_messages(aq, bq, m01, m23);
+    float* row = m0 + (size_t)v * (Va + 1) * kD + f;
+    if (a0 + kh <= Va) row[(size_t)(a0 + kh) * kD] = m01;
+    if (a0 + 2 + kh <= Va) row[(size_t)(a0 + 2 + kh) * kD] = m23;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) *hdr = M0Header{kM0Magic, Va, Vb, S};
+}
 
 // Where the loads of the NEXT step are issued (diagnostics builds may override):
 //   kPfWhere   0: the step's update image at the top of its own message phase; 1: during the previous step's atom phase,
@@ -260,6 +335,18 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     return;
   }
 
+  // Step-0 message table: one uniform read of each ion's image header.  An image without a table (the plain prepare
+  // entry, the per-call rebuild) or one built for other vocabularies takes the MFMA path below, unchanged.
+  unsigned tabmask = 0;
+  {
+    const M0Header t0 = *reinterpret_cast<const M0Header*>(p.upd[0] + kUpdLds);
+    if (t0.magic == kM0Magic && t0.Va == p.Va && t0.Vb == p.Vb && t0.S == p.S) tabmask |= 1u;
+    if (p.n_ions > 1) {
+      const M0Header t1 = *reinterpret_cast<const M0Header*>(p.upd[1] + kUpdLds);
+      if (t1.magic == kM0Magic && t1.Va == p.Va && t1.Vb == p.Vb && t1.S == p.S) tabmask |= 2u;
+    }
+  }
+
   // The record of the NEXT chunk travels in registers while the current chunk runs.
   const bool rec_big = rec_lds > kTRecPart1;  // workgroup-uniform
   const unsigned char* rec_c = p.rec + (size_t)c_begin * kTRecBytes;
@@ -283,6 +370,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     const int ntiles = (R + 15) >> 4;
     const float* upd_g = p.upd[g];
     const float* tmat_g = p.tmat[g];
+    const bool tab0 = (tabmask >> g) & 1u;  // workgroup-uniform: step 0's messages come from the table
     if (8 * tid < rec_lds) reinterpret_cast<uint2*>(recl)[tid] = rec_n8;
     if (rec_big && kTRecPart1 + 4 * tid < rec_lds) reinterpret_cast<uint32_t*>(recl + kTRecPart1)[tid] = rec_n4;
     {
@@ -294,6 +382,43 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     }
     lds_barrier();
     fill_h0();
+    if (tab0) {
+      // ---- step 0's messages from the table: m_e = M0[type_e][atom id of src_e], a gather - here, beside fill_h0
+      // (neither reads what the other writes; the barrier below orders both), not at the top of step 0: inside the step
+      // loop the same lines cost the production instantiations 12-32 bytes of scratch, here none.  Eight lanes per edge
+      // lane of the group table, one 16-byte load and one 16-byte LDS store each.  The id is clamped to column Va (the
+      // zero row's message) exactly where fill_h0 writes zeros; the destination is the group's message key (its low two
+      // bits are clear, so key ^ 4 u is the aligned unit u of the slot).  Branch-free like the message phase: an unused
+      // edge lane fetches no row of its own (all of them read the table's first 128 bytes) and stores to the dump slot.
+      // All loads of a round - one round up to 1024 edge lanes - are issued before the first store waits for any.
+      const int ngrp = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint16_t*>(recl + kTRecCounts));
+      const float* const m0_g = p.m0[g];
+      // (the lane roles are derived here, behind an opaque copy of tid: hoisted out of the chunk loop they would
+      //  occupy registers through the whole kernel, which has none to spare)
+      int tl = tid;
+      asm volatile("" : "+v"(tl));
+      const unsigned u4 = 4 * (tl & 7);               // 16-byte unit of the row
+      const int i = (tl >> 3) & 3, g0 = tl >> 5;      // edge lane of the group, first group
+      constexpr int kGR = 8;                          // loads in flight per thread
+      const unsigned dump = (unsigned)tmsg_key(p.ecap);
+      for (int gb = 0; gb < ngrp; gb += 32 * kGR) {
+        f32x4 mv[kGR];
+        unsigned dst[kGR];
+#pragma unroll
+        for (int j = 0; j < kGR; ++j) {
+          const int gi = gb + 32 * j + g0;
+          const uint4 ge = r_grp[gi < ngrp ? gi : ngrp - 1];
+          const bool ok = gi < ngrp && i < (int)__builtin_amdgcn_ubfe(ge.x, 8, 8);
+          const int id = r_rowatom[__builtin_amdgcn_ubfe(ge.y, 8 * i, 8)];
+          const unsigned col = (unsigned)id < (unsigned)p.Va ? (unsigned)id : (unsigned)p.Va;
+          const unsigned off = ((ge.x & 0xffu) * (unsigned)(p.Va + 1) + col) * kD + u4;  // the table is < 2 MiB
+          mv[j] = ld4(m0_g + (ok ? off : 0u));
+          dst[j] = (ok ? __builtin_amdgcn_ubfe(i < 2 ? ge.z : ge.w, 16 * (i & 1), 16) : dump) ^ u4;
+        }
+#pragma unroll
+        for (int j = 0; j < kGR; ++j) st4(msg + dst[j], mv[j]);
+      }
+    }
     if (tid == 0) *run_ctr = 2 * kWaves;  // runs 0 .. 2 kWaves - 1 are assigned statically (two per wave)
     lds_barrier();
     if (stamp && tid == 0) {
@@ -339,6 +464,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     if (kPfWhere != 0) fetch_pf(0);
     if (kRunsEarly >= 1) fetch_P(0);
     if (kRunsEarly >= 2) fetch_Q(0);
+    if (stamp && c == c_begin && tid == 0) stamp[13] = __builtin_amdgcn_s_memtime();  // start of the first chunk's step 0
     for (int s = 0; s < p.S; ++s) {
       const float* tm_s = tmat_g + (size_t)s * p.Vb * kTMatFloats;
       // ---- message phase: m_e = A[type_e] h[src_e], one group of <= 4 edges of one bond type per 16 MFMAs.
@@ -354,7 +480,10 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       // this loop costs matrix time: the plan hands over ready-made LDS keys (message slot incl. swizzle; unused edge
       // lanes point at a dump slot, so the stores are unconditional) and the loop body is branch-free.
       __builtin_amdgcn_s_setprio(2);
-      {
+      // (a step whose messages came from the table - see the chunk prologue - requests no matrix rows and takes no run)
+      const bool from_tab = tab0 && s == 0;  // workgroup-uniform
+      if (kPfWhere == 0) fetch_pf(s);
+      if (!from_tab) {
         const float* const abase = hbuf + acol;
         auto load_group = [&](int e, Grp& G) {
           G.ge = r_grp[e];
@@ -362,42 +491,10 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
           G.aq = *reinterpret_cast<const f32x2v*>(abase + src * HS);
         };
         auto compute = [&](const Grp& G, const f32x4 (&bq)[4]) {
-          f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-#ifndef IMPNN_DIAG_NO_MSG_MFMA  // (diagnostics builds only: wrong results)
-          // instruction k (= h column 16 kh + k): A from register k & 1, block k >> 1; B = the lane's matrix element k.
-          // (Two accumulator chains; four were measured: +4 % kernel time, the registers cost more than the s_nops.)
-          acc0 = mfma1<0>(G.aq[0], bq[0][0], acc0);
-          acc1 = mfma1<0>(G.aq[1], bq[0][1], acc1);
-          acc0 = mfma1<1>(G.aq[0], bq[0][2], acc0);
-          acc1 = mfma1<1>(G.aq[1], bq[0][3], acc1);
-          acc0 = mfma1<2>(G.aq[0], bq[1][0], acc0);
-          acc1 = mfma1<2>(G.aq[1], bq[1][1], acc1);
-          acc0 = mfma1<3>(G.aq[0], bq[1][2], acc0);
-          acc1 = mfma1<3>(G.aq[1], bq[1][3], acc1);
-          acc0 = mfma1<4>(G.aq[0], bq[2][0], acc0);
-          acc1 = mfma1<4>(G.aq[1], bq[2][1], acc1);
-          acc0 = mfma1<5>(G.aq[0], bq[2][2], acc0);
-          acc1 = mfma1<5>(G.aq[1], bq[2][3], acc1);
-          acc0 = mfma1<6>(G.aq[0], bq[3][0], acc0);
-          acc1 = mfma1<6>(G.aq[1], bq[3][1], acc1);
-          acc0 = mfma1<7>(G.aq[0], bq[3][2], acc0);
-          acc1 = mfma1<7>(G.aq[1], bq[3][3], acc1);
-#else
-          acc0[0] = G.aq[0] + bq[0][0] + bq[3][3];
-          acc1[1] = G.aq[1] + bq[1][1] + bq[2][2];
-#endif
-          // acc0 + acc1 as four v_add_f32: as a vector add the compiler emits two v_pk_add_f32, which beside MFMAs cost
-          // more issue time than the four scalar adds (the same IEEE sums either way)
-          float x0 = acc0[0] + acc1[0], x1 = acc0[1] + acc1[1], x2 = acc0[2] + acc1[2], x3 = acc0[3] + acc1[3];
-          // element i of lane l: edge i, feature l & 31, k-half l >> 5.
-          // v_permlane32_swap x, y: lanes 32-63 of x <-> lanes 0-31 of y.  Afterwards x = {x.lo, y.lo},
-          // y = {x.hi, y.hi}, so x + y is edge 0 (2) complete in lanes 0-31 and edge 1 (3) in lanes 32-63.
-          // (Inline asm: the compiler's builtin for this gfx950 instruction folded its two operands into one here.
-          //  The s_nop covers the VALU-write -> permlane-read wait states the assembler does not insert.)
-          asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3"
-                       : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3));
-          msg[__builtin_amdgcn_ubfe(G.ge.z, zsh, 16) ^ f] = x0 + x1;
-          msg[__builtin_amdgcn_ubfe(G.ge.w, zsh, 16) ^ f] = x2 + x3;
+          float m01, m23;
+          group_messages(G.aq, bq, m01, m23);
+          msg[__builtin_amdgcn_ubfe(G.ge.z, zsh, 16) ^ f] = m01;
+          msg[__builtin_amdgcn_ubfe(G.ge.w, zsh, 16) ^ f] = m23;
         };
         // A run's groups, software-pipelined: the operands of group e + 1 are requested from LDS in front of group e's
         // MFMAs (two buffers, loop unrolled by two so that neither is ever copied); the first group's were requested
@@ -446,7 +543,6 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
         };
         // the first two runs of a wave are fixed; the rest comes from the counter.  (Loads in program order on every
         // path: image, P, Q - so that the counted waits below hold.)
-        if (kPfWhere == 0) fetch_pf(s);
         if (kRunsEarly < 1) fetch_P(s);
         if (kRunsEarly < 2) fetch_Q(s);
         haveP = sP; gP = sgP; nP = snP;
@@ -711,6 +807,25 @@ int launch_encoder_typed_prepare(const float* weights, const float* bond_table, 
   return enc::launch_typed_image(ip, s);
 }
 
+// ---- the image with the step-0 message table behind it (encoder_layout.h: M0Header)
+size_t encoder_typed_prepared_bytes_atoms(int S, int Va, int Vb, bool x3) {
+  return (enc::typed_prepared_floats(S, Vb, x3) + enc::m0_table_floats(S, Va, Vb)) * sizeof(float);
+}
+
+int launch_encoder_typed_prepare_atoms(const float* weights, const float* bond_table, const float* atom_table, int Va,
+                                       int K, int S, int Vb, bool x3, void* prepared, hipStream_t s) {
+  using namespace enc;
+  // the plain image first: its typed_image_kernel clears the header, so a shape beyond the cap ends here with "none"
+  if (int rc = launch_encoder_typed_prepare(weights, bond_table, K, S, Vb, x3, prepared, s)) return rc;
+  if (m0_table_floats(S, Va, Vb) == 0) return IMPNN_OK;
+  float* img = static_cast<float*>(prepared);
+  const size_t uslot = x3 ? kXUpdSlot : kTUpdSlot;
+  const int waves = Vb * ((Va + 4) >> 2);
+  typed_m0_kernel<<<(waves + 3) / 4, 256, 0, s>>>(img + (size_t)S * uslot, atom_table, img + typed_prepared_floats(S, Vb, x3),
+                                                  reinterpret_cast<M0Header*>(img + (x3 ? kXUpdLds : kTUpdLds)), Va, Vb, S);
+  return check_launch("typed_m0");
+}
+
 int launch_encoder_typed_run(const EncoderArgs& a, const enc::Ws& w, hipStream_t s) {
   using namespace enc;
   char* base = static_cast<char*>(a.workspace);
@@ -730,6 +845,7 @@ int launch_encoder_typed_run(const EncoderArgs& a, const enc::Ws& w, hipStream_t
     }
     ep.upd[g] = prep;
     ep.tmat[g] = prep + S1 * uslot;
+    ep.m0[g] = prep + typed_prepared_floats(a.S, a.Vb, x3);
     ep.pooled[g] = a.pooled[g];
   }
   ep.atom_table = a.atom_table;

@@ -530,10 +530,13 @@ class MPNNModel:
         return self._transfer_grid_image
 
     def _prepared_weights(self, mode):
-        """Kernel-side weight images (one per ion), built once per weight version and mode."""
+        """Kernel-side weight images (one per ion), built once per weight version and mode.  The typed modes fold the atom
+        embedding in as well (the step-0 message table): invalidate_packed_weights drops the images after an in-place
+        change, weights_updated when any embedding trains."""
         if mode not in self._prepared:
             self._prepared[mode] = [ops.prepare_encoder_weights(pk, self.bond_emb.embeddings, self.atom_dim,
-                                                                self.bond_dim, self.num_steps, mode)
+                                                                self.bond_dim, self.num_steps, mode,
+                                                                atom_table=self.atom_emb.embeddings)
                                     if pk is not None else None for pk in self._packed_weights()]
         return self._prepared[mode]
 

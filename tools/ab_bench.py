@@ -54,12 +54,24 @@ prep = {}
 def call(lib):
     if hasattr(lib, "impnn_encoder_fused_prepared"):
         if id(lib) not in prep:
-            nb = int(lib.impnn_encoder_prepared_bytes(32, S, btab.shape[0], ops.ENCODER_MODES[args.mode]))
+            # a library that exports the with-atoms prepare gets the image MPNNModel keeps: with the step-0 message table
+            atoms = hasattr(lib, "impnn_encoder_prepare_weights_atoms")
+            if atoms:
+                nb = int(lib.impnn_encoder_prepared_bytes_atoms(32, S, atab.shape[0], btab.shape[0],
+                                                                ops.ENCODER_MODES[args.mode]))
+            else:
+                nb = int(lib.impnn_encoder_prepared_bytes(32, S, btab.shape[0], ops.ENCODER_MODES[args.mode]))
             bufs = [torch.empty(nb, dtype=torch.uint8, device=dev) for _ in range(2)]
             for bf, pk in zip(bufs, packed):
-                assert lib.impnn_encoder_prepare_weights(pk.data_ptr(), btab.data_ptr(), 32, 8, S, btab.shape[0],
-                                                         ops.ENCODER_MODES[args.mode], bf.data_ptr(), nb,
-                                                         torch.cuda.current_stream().cuda_stream) == 0
+                if atoms:
+                    assert lib.impnn_encoder_prepare_weights_atoms(pk.data_ptr(), btab.data_ptr(), atab.data_ptr(),
+                                                                   atab.shape[0], 32, 8, S, btab.shape[0],
+                                                                   ops.ENCODER_MODES[args.mode], bf.data_ptr(), nb,
+                                                                   torch.cuda.current_stream().cuda_stream) == 0
+                else:
+                    assert lib.impnn_encoder_prepare_weights(pk.data_ptr(), btab.data_ptr(), 32, 8, S, btab.shape[0],
+                                                             ops.ENCODER_MODES[args.mode], bf.data_ptr(), nb,
+                                                             torch.cuda.current_stream().cuda_stream) == 0
             prep[id(lib)] = bufs
         rc = lib.impnn_encoder_fused_prepared(2, mk([i[0] for i in ions]), mk([i[1] for i in ions]),
                                               mk([i[2] for i in ions]), atab.data_ptr(), atab.shape[0], btab.data_ptr(),
@@ -101,5 +113,5 @@ for r in range(args.rounds):
         tot[i].append(e0.elapsed_time(e1) / args.iters * 1e3)
         ker[i].append(float(np.mean(np.frombuffer(buf, dtype=np.float32, count=n.value))) * 1e3)
 for i, path in enumerate(args.libs):
-    print(f"{Path(path).name:24s} call: median {np.median(tot[i]):7.1f} us  min {np.min(tot[i]):7.1f} us | "
-          f"encoder kernel: median {np.median(ker[i]):7.1f} us  min {np.min(ker[i]):7.1f} us")
+    print(f"{Path(path).name:24s} call: median {np.median(tot[i]):7.1f} us  min {np.min(tot[i]):7.1f}  max {np.max(tot[i]):7.1f} us | "
+          f"encoder kernel: median {np.median(ker[i]):7.1f} us  min {np.min(ker[i]):7.1f}  max {np.max(ker[i]):7.1f} us")
