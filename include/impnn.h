@@ -779,6 +779,37 @@ int impnn_pareto_collect(const float* f1, const float* f2, const uint32_t* where
                          int64_t row0, int32_t restart, float* values, int32_t* cation, int32_t* anion, int64_t capacity,
                          void* workspace, size_t workspace_bytes, int32_t rows, int32_t A, impnn_stream_t stream);
 
+/* ---- the applicability domain of a screen: how far a candidate pair lies from anything the model was trained on.
+ *      A pair's latent vector is z(i,j) = mix_cat[i] + mix_an[j] (impnn_head_ion_mix rows (C,Mx), (A,Mx); float32, the
+ *      cation term first: the bits the head kernels add).  Against a reference set ref (R,Mx) float32, R >= 1:
+ *        for p = 0 .. R-1 ascending: d2 = 0; for k ascending: diff = z[k] - ref[p][k]; d2 = fmaf(diff, diff, d2);
+ *        the running best starts at (+inf, -1) and is replaced when d2 < best (strict: the lowest p wins among equal d2);
+ *        distance = sqrt(best), correctly rounded, nearest = p; if no row ever replaced the initial state (a NaN in the
+ *        pair's latent vector): distance NaN, nearest -1.
+ *      No |z|^2 - 2 z.r + |r|^2 expansion and no matrix-core product: a pair of the reference set has distance exactly 0.
+ *      impnn_domain_grid       distance (C,A) float32 and nearest (C,A) int32 (may be NULL), row-major, int64 indexing:
+ *                              C * A may exceed 2^31.
+ *      impnn_domain_grid_mask  words (C,W), W = impnn_grid_mask_row_words(A), the pair mask format above: bit (i,j) =
+ *                              lo <= distance && distance <= hi as float32 for the distance impnn_domain_grid writes
+ *                              (a NaN fails both; an infinity means no limit), pad bits 0, every word written by one
+ *                              workgroup.  No C x A float buffer exists.
+ *      impnn_domain_rows       the queries are given as rows z (Q,Mx) instead of as a sum -> distance (Q), nearest (Q)
+ *                              (may be NULL).  exclude_self != 0: query p skips row p of the reference (needs Q == R):
+ *                              every reference row's distance to its nearest other row.
+ *      One definition of the inner loop serves the three: an element has the same bits whichever entry produced it.
+ *      The reference streams through LDS in chunks of impnn_domain_reference_chunk() rows; the work is 2 * R * Mx lane
+ *      operations per pair, the memory traffic C + A + R rows and the output.  1 <= Mx <= 64.
+ *      Checks in order: shape (sizes >= 0, Mx >= 1, R >= 1, exclude_self with Q != R, a NaN bound; IMPNN_E_BADARG); Mx <=
+ *      64 (IMPNN_E_UNSUPPORTED); zero work (C == 0, A == 0 or Q == 0: IMPNN_OK, nothing touched); null pointers; the
+ *      tiles of 16 x 64 pairs must fit one launch (IMPNN_E_UNSUPPORTED).  No allocation, no synchronisation, no state. */
+int32_t impnn_domain_reference_chunk(void);
+int impnn_domain_grid(const float* mix_cat, const float* mix_an, const float* ref, float* distance, int32_t* nearest,
+                      int32_t C, int32_t A, int32_t R, int32_t Mx, impnn_stream_t stream);
+int impnn_domain_grid_mask(const float* mix_cat, const float* mix_an, const float* ref, float lo, float hi,
+                           uint32_t* words, int32_t C, int32_t A, int32_t R, int32_t Mx, impnn_stream_t stream);
+int impnn_domain_rows(const float* z, const float* ref, int32_t exclude_self, float* distance, int32_t* nearest,
+                      int32_t Q, int32_t R, int32_t Mx, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

@@ -116,6 +116,10 @@ SIGNATURES = {
     "impnn_pareto_minima": (C.c_int, [vp, vp, vp, i32, i32, vp, sz, i32, i32, vp]),
     "impnn_pareto_staircase": (C.c_int, [vp, sz, vp]),
     "impnn_pareto_collect": (C.c_int, [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, i64, vp, sz, i32, i32, vp]),
+    "impnn_domain_reference_chunk": (i32, []),
+    "impnn_domain_grid": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "impnn_domain_grid_mask": (C.c_int, [vp, vp, vp, f32, f32, vp, i32, i32, i32, i32, vp]),
+    "impnn_domain_rows": (C.c_int, [vp, vp, i32, vp, vp, i32, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

@@ -1155,6 +1155,53 @@ int impnn_ensemble_grid_topk_where(int32_t kind, int32_t M, const float* mix_cat
                            0, workspace_bytes);
 }
 
+// ---- the applicability domain (include/impnn.h; grid_domain.hip).  The three entries' order: shape (sizes, R >= 1,
+// Mx >= 1, exclude_self with Q != R, a NaN bound), the width limit, zero work, null pointers, then the launcher's tile count.
+namespace {
+int domain_shape_rule(const char* entry, bool sizes_ok, int R, int Mx) {
+  if (!sizes_ok || Mx < 1) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (R < 1) return fail(IMPNN_E_BADARG, "%s: R=%d reference rows must be at least 1", entry, R);
+  return IMPNN_OK;
+}
+int domain_width_rule(const char* entry, int Mx) {
+  if (Mx > kHeadMaxDim) return fail(IMPNN_E_UNSUPPORTED, "%s: Mx=%d (<= %d)", entry, Mx, kHeadMaxDim);
+  return IMPNN_OK;
+}
+}  // namespace
+
+int32_t impnn_domain_reference_chunk(void) { return domain_reference_chunk(); }
+
+int impnn_domain_grid(const float* mix_cat, const float* mix_an, const float* ref, float* distance, int32_t* nearest,
+                      int32_t C, int32_t A, int32_t R, int32_t Mx, impnn_stream_t stream) {
+  if (int rc = domain_shape_rule(__func__, C >= 0 && A >= 0, R, Mx)) return rc;
+  if (int rc = domain_width_rule(__func__, Mx)) return rc;
+  if (C == 0 || A == 0) return IMPNN_OK;
+  REQUIRE(mix_cat && mix_an && ref && distance, "null pointer");
+  return launch_domain_grid(DomainGridCall{mix_cat, mix_an, ref, distance, nearest, nullptr, 0.f, 0.f, C, A, R, Mx,
+                                           as_stream(stream)});
+}
+
+int impnn_domain_grid_mask(const float* mix_cat, const float* mix_an, const float* ref, float lo, float hi,
+                           uint32_t* words, int32_t C, int32_t A, int32_t R, int32_t Mx, impnn_stream_t stream) {
+  if (int rc = domain_shape_rule(__func__, C >= 0 && A >= 0, R, Mx)) return rc;
+  REQUIRE(lo == lo && hi == hi, "a bound is NaN (an infinity means no limit)");
+  if (int rc = domain_width_rule(__func__, Mx)) return rc;
+  if (C == 0 || A == 0) return IMPNN_OK;
+  REQUIRE(mix_cat && mix_an && ref && words, "null pointer");
+  return launch_domain_grid(DomainGridCall{mix_cat, mix_an, ref, nullptr, nullptr, words, lo, hi, C, A, R, Mx,
+                                           as_stream(stream)});
+}
+
+int impnn_domain_rows(const float* z, const float* ref, int32_t exclude_self, float* distance, int32_t* nearest,
+                      int32_t Q, int32_t R, int32_t Mx, impnn_stream_t stream) {
+  if (int rc = domain_shape_rule(__func__, Q >= 0, R, Mx)) return rc;
+  REQUIRE(!exclude_self || Q == R, "exclude_self needs the queries to be the reference rows: Q == R");
+  if (int rc = domain_width_rule(__func__, Mx)) return rc;
+  if (Q == 0) return IMPNN_OK;
+  REQUIRE(z && ref && distance, "null pointer");
+  return launch_domain_rows(DomainRowsCall{z, ref, exclude_self != 0, distance, nearest, Q, R, Mx, as_stream(stream)});
+}
+
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,
                       const int64_t* rows, int32_t n_rows, impnn_stream_t stream) {
   REQUIRE(n_tensors >= 0 && n_rows >= 0, "bad shape");

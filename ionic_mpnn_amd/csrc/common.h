@@ -338,6 +338,30 @@ struct GridMaskCall {
 int64_t grid_mask_row_words(int A);
 int launch_grid_mask(const GridMaskCall& c);
 
+// ---- the applicability domain (grid_domain.hip; include/impnn.h, impnn_domain_grid / _grid_mask / _rows): the
+// distance from a pair's latent vector mix_cat[i] + mix_an[j], or from a query row, to the nearest row of `ref` (R, Mx).
+// api.hip checks the arguments.
+struct DomainGridCall {
+  const float *mix_cat, *mix_an, *ref;
+  float* distance;   // (C, A); the materialising form
+  int32_t* nearest;  // (C, A), or null
+  uint32_t* words;   // (C, W); the mask form: distance and nearest null
+  float lo, hi;
+  int C, A, R, Mx;
+  hipStream_t stream;
+};
+struct DomainRowsCall {
+  const float *z, *ref;
+  bool exclude_self;  // query p skips row p of the reference (Q == R)
+  float* distance;    // (Q)
+  int32_t* nearest;   // (Q), or null
+  int Q, R, Mx;
+  hipStream_t stream;
+};
+int domain_reference_chunk();  // reference rows per LDS chunk of the kernels
+int launch_domain_grid(const DomainGridCall& c);
+int launch_domain_rows(const DomainRowsCall& c);
+
 // ---- the ensemble grid (ensemble_grid.hip; include/impnn.h, impnn_ensemble_grid*): family 2 of GridOperands through
 // the materialising, mask-writing and selecting forms.  api.hip checks the arguments.
 int ensemble_grid_max_members();

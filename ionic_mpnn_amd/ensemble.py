@@ -138,6 +138,13 @@ class ModelEnsemble:
             raise ValueError("k must be >= 1")
         return _EnsembleScreen(self, cations, anions, T, where, batch_size, kp).top_k(k, largest, max_pairs_per_launch)
 
+    def _no_domain(self, *args, **kwargs):
+        """The applicability domain is a distance in one model's latent space; the members' spaces differ."""
+        raise ValueError("an ensemble has no latent space of its own: fit and screen the applicability domain with one "
+                         "member model (its masks constrain the ensemble's screens through where=)")
+
+    fit_domain = domain_grid = screen_domain_mask = domain_distance = _no_domain
+
     def predict_pairs(self, cations, anions, cation_index, anion_index, temperatures=None, batch_size=4096):
         """Mean and population standard deviation of listed pairs - pair p is (cations[cation_index[p]],
         anions[anion_index[p]]) - from the members' own ``head`` on gathered pooled rows -> numpy (mean, std) of shape

@@ -1412,6 +1412,119 @@ class MPNNModel:
             return data.PairMask(words, (C, A, int(words.shape[0])))
         return data.PairMask(words[0], (C, A))
 
+    # ------------------------------------------------------------------ the applicability domain of a screen
+    def _domain_request(self, what, reference=None):
+        """The refusals the domain methods share: the transfer model, widths the head kernels do not cover, and a
+        reference set of another width."""
+        if self.kind == "transfer":
+            raise ValueError(f"{what}: the transfer model's head does not end the latent space at mix_cat_an; use the "
+                             "base viscosity model it was built from")
+        if not self._grid_kernels_cover():
+            raise ValueError(f"{what}: the head kernels do not cover atom_dim {self.atom_dim}, fp_size {self.fp_size}, "
+                             f"mixing_size {self.mixing_size} (<= {ops.HEAD_MAX_X}, {ops.HEAD_MAX_DIM}, {ops.HEAD_MAX_DIM})")
+        if reference is not None:
+            if not isinstance(reference, data.DomainReference):
+                raise TypeError(f"reference must be a data.DomainReference, got {type(reference).__name__}")
+            if reference.width != self.mixing_size:
+                raise ValueError(f"{what}: the reference set has width {reference.width}, the model's mixing_size is "
+                                 f"{self.mixing_size}")
+
+    def _domain_mix(self, cations, anions, batch_size):
+        """The per-ion halves of the latent space: ``encode_ions`` and ``ops.head_ion_mix`` -> (C,Mx), (A,Mx)."""
+        if cations is None or anions is None:
+            raise ValueError("the domain methods need both cations and anions")
+        pc, pa = self.encode_ions(cations, anions, batch_size)
+        w, fp, mx = self._packed_head(), self.fp_size, self.mixing_size
+        return ops.head_ion_mix(self.kind, "cat", pc, w, fp, mx), ops.head_ion_mix(self.kind, "an", pa, w, fp, mx)
+
+    @staticmethod
+    def _domain_row_steps(C, A, max_pairs_per_launch, default_pairs):
+        """The host tiling of the cation axis: (lo, hi) per launch."""
+        if max_pairs_per_launch is not None and int(max_pairs_per_launch) < 1:
+            raise ValueError("max_pairs_per_launch must be >= 1")
+        pairs = default_pairs if max_pairs_per_launch is None else int(max_pairs_per_launch)
+        step = max(1, pairs // max(A, 1))
+        return [(lo, min(C, lo + step)) for lo in range(0, C, step)] if A > 0 else []
+
+    def fit_domain(self, cations, anions, cation_index, anion_index, batch_size=4096):
+        """The training pairs as a reference set in the model's latent space -> ``data.DomainReference``.  A pair's
+        latent vector is the ``mix_cat_an`` layer, head_ion_mix(cat)[i] + head_ion_mix(an)[j] in float32 - where the
+        reference's transfer script cuts the network; for a viscosity model it does not depend on temperature.
+        ``cation_index`` / ``anion_index`` list the training pairs as indices into the species dicts
+        (``data.unique_ions`` produces that form); repeated pairs are listed once, sorted by (cation, anion)
+        (``data.unique_pairs``).  ``self_distance`` is every pair's distance to its nearest other pair
+        (``ops.domain_rows(rows, rows, exclude_self=True)``), from which ``DomainReference.radius`` takes a threshold.
+        The reference set is a snapshot of the weights at this moment: after further training fit it again - nothing
+        checks that it is still current."""
+        self._domain_request("fit_domain")
+        ci, ai = data.unique_pairs(cation_index, anion_index, len(cations["atom"]), len(anions["atom"]))
+        if len(ci) == 0:
+            raise ValueError("fit_domain needs at least one training pair")
+        mc, ma = self._domain_mix(cations, anions, batch_size)
+        rows = mc[torch.from_numpy(ci.astype(np.int64)).to(self.device)] + ma[torch.from_numpy(ai.astype(np.int64)).to(self.device)]
+        self_distance, _ = ops.domain_rows(rows, rows, exclude_self=True)
+        return data.DomainReference(rows, ci, ai, self_distance.cpu().numpy())
+
+    def domain_grid(self, cations, anions, reference, max_pairs_per_launch=None, batch_size=4096):
+        """Every pair's distance to the reference set in the latent space, and the training pair it lies nearest to
+        (impnn_domain_grid) -> numpy (distance (C,A) float32, nearest (C,A) int32): ``nearest[i,j]`` is a row of
+        ``reference`` (``reference.cation`` / ``.anion`` name the pair), the lowest among equally near ones; a pair of
+        the reference set has distance exactly 0.  What ``data.grid_domain`` computes in float64.  The cation axis is
+        tiled on the host as in ``predict_grid``: the two outputs of a pair count against GRID_OUTPUT_BUDGET, and an
+        element's bits do not depend on the tiling."""
+        self._domain_request("domain_grid", reference)
+        mc, ma = self._domain_mix(cations, anions, batch_size)
+        C, A = int(mc.shape[0]), int(ma.shape[0])
+        distance, nearest = np.empty((C, A), np.float32), np.empty((C, A), np.int32)
+        for lo, hi in self._domain_row_steps(C, A, max_pairs_per_launch, GRID_OUTPUT_BUDGET // 2):
+            d, n = ops.domain_grid(mc[lo:hi], ma, reference.rows)
+            distance[lo:hi], nearest[lo:hi] = d.cpu().numpy(), n.cpu().numpy()
+        return distance, nearest
+
+    def screen_domain_mask(self, cations, anions, reference, at_most=None, at_least=None, max_pairs_per_launch=None,
+                           batch_size=4096):
+        """The pairs whose distance to the reference set lies within the bounds, as a packed pair mask written on the
+        GPU (impnn_domain_grid_mask): bit (i,j) is set where ``at_least <= distance <= at_most`` for the distance
+        ``domain_grid`` gives that pair -> ``data.PairMask`` of shape (C,A) for either kind - it takes no temperatures -
+        its words on the model's device.  At least one bound is needed; a missing one is -inf / +inf; bounds are
+        compared as float32, a NaN distance fails.  No C x A float buffer exists.  It composes with every screen:
+
+            dom    = visc_model.fit_domain(cat, an, train_cation_index, train_anion_index)
+            inside = visc_model.screen_domain_mask(cat, an, dom, at_most=dom.radius(0.95))
+            best   = visc_model.screen_top_k(cat, an, [298.15], k=100, where=liquid & inside & ~known)"""
+        if at_least is None and at_most is None:
+            raise ValueError("screen_domain_mask needs a bound: at_most, at_least or both")
+        lo_b = np.float32(-np.inf if at_least is None else at_least)
+        hi_b = np.float32(np.inf if at_most is None else at_most)
+        if np.isnan(lo_b) or np.isnan(hi_b):
+            raise ValueError("a screen_domain_mask bound is NaN")
+        self._domain_request("screen_domain_mask", reference)
+        mc, ma = self._domain_mix(cations, anions, batch_size)
+        C, A = int(mc.shape[0]), int(ma.shape[0])
+        words = torch.zeros((C, data.mask_row_words(A)), dtype=torch.int32, device=self.device)
+        # (a launch holds fewer than 2^31 tiles of 16 x 64 pairs)
+        for lo, hi in self._domain_row_steps(C, A, max_pairs_per_launch, 1 << 40):
+            words[lo:hi] = ops.domain_grid_mask(mc[lo:hi], ma, reference.rows, lo_b, hi_b)
+        return data.PairMask(words, (C, A))
+
+    def domain_distance(self, inputs, reference, batch_size=None):
+        """The distance of listed pairs - a record list in ``predict``'s input format - to the reference set -> numpy
+        (distance (n,) float32, nearest (n,) int32): ``encode_pooled``, the two ``ops.head_ion_mix`` halves, their
+        float32 sum and ``ops.domain_rows``.  A record of a reference pair gets 0."""
+        self._domain_request("domain_distance", reference)
+        n = len(inputs["cat_atom"])
+        bs = n if not batch_size else int(batch_size)
+        distance, nearest = np.empty(n, np.float32), np.empty(n, np.int32)
+        w, fp, mx = self._packed_head(), self.fp_size, self.mixing_size
+        for lo in range(0, n, max(bs, 1)):
+            chunk = {k: v[lo:lo + bs] for k, v in inputs.items() if k != "temperature"}
+            with torch.no_grad():
+                pc, pa = self.encode_pooled({k: self._as_device_tensor(k, v) for k, v in chunk.items()})
+            z = ops.head_ion_mix(self.kind, "cat", pc, w, fp, mx) + ops.head_ion_mix(self.kind, "an", pa, w, fp, mx)
+            d, p = ops.domain_rows(z, reference.rows)
+            distance[lo:lo + bs], nearest[lo:lo + bs] = d.cpu().numpy(), p.cpu().numpy()
+        return distance, nearest
+
     def _grid_operands(self, pc, pa, T, mfma):
         """The per-ion halves of the covered grid kernels as the operands of their launches (``ops.GridOperands``):
         ``impnn_transfer_ion_half`` rows and the prepared image on the matrix-core path, else ``impnn_head_ion_mix``
@@ -1435,14 +1548,15 @@ class MPNNModel:
             return self.head(pcg, pag).reshape(c, A)
         return self.head(pcg, pag, T[None, None, :].expand(c, A, nT).reshape(-1, 1).contiguous()).reshape(c, A, nT)
 
+    def _as_device_tensor(self, name, v):
+        if isinstance(v, np.ndarray):
+            v = torch.from_numpy(v)
+        if not isinstance(v, torch.Tensor):
+            raise TypeError(f"input {name!r} must be a numpy array or torch tensor")
+        return v.to(self.device, non_blocking=True)
+
     def _to_device(self, inputs):
-        out = {}
-        for k, v in inputs.items():
-            if isinstance(v, np.ndarray):
-                v = torch.from_numpy(v)
-            if not isinstance(v, torch.Tensor):
-                raise TypeError(f"input {k!r} must be a numpy array or torch tensor")
-            out[k] = v.to(self.device, non_blocking=True)
+        out = {k: self._as_device_tensor(k, v) for k, v in inputs.items()}
         if self.kind == "viscosity" and "temperature" not in out:
             raise KeyError("the viscosity model needs a 'temperature' input (train_viscosity.py:160)")
         return out

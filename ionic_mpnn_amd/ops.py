@@ -1319,6 +1319,88 @@ def transfer_head_grid_mask(u_cat, u_an, image, lo, hi):
     return grid_mask(transfer_grid_operands(u_cat, u_an, image), lo, hi)
 
 
+# ---- the applicability domain (include/impnn.h, impnn_domain_*): the distance from a pair's latent vector mix_cat[i] +
+# mix_an[j] - the head's `mixed` - to the nearest row of a reference set, the host reference is data.grid_domain
+def domain_reference_chunk():
+    """Reference rows per LDS chunk of the domain kernels (impnn_domain_reference_chunk): what a test sizes R by."""
+    return int(_lib.load().impnn_domain_reference_chunk())
+
+
+def _domain_operands(ref, exclude_self=False, **queries):
+    """The rules of the ``domain_*`` calls, checked before any library call: every tensor float32 and 2-D, one width
+    1 <= Mx <= HEAD_MAX_DIM, R >= 1, ``exclude_self`` with one query per reference row, everything on one GPU -> the
+    contiguous tensors, the queries first."""
+    named = list(queries.items()) + [("ref", ref)]
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{name} must be 2-D (rows, Mx), got {tuple(t.shape)}")
+    Mx = int(ref.shape[1])
+    for name, t in named:
+        if t.shape[1] != Mx:
+            raise ValueError(f"{name} has width {t.shape[1]}, the reference rows have width {Mx}")
+    if not 1 <= Mx <= HEAD_MAX_DIM:
+        raise ValueError(f"Mx={Mx}: the domain kernels cover widths 1 to {HEAD_MAX_DIM}")
+    if ref.shape[0] < 1:
+        raise ValueError("the reference set is empty: R must be at least 1")
+    if exclude_self and named[0][1].shape[0] != ref.shape[0]:
+        raise ValueError(f"exclude_self needs one query per reference row, got {named[0][1].shape[0]} queries and "
+                         f"{ref.shape[0]} rows")
+    require_gpu(*[t for _, t in named])
+    if any(t.device != ref.device for _, t in named):
+        raise ValueError("the rows and the reference set must be on one device")
+    return [t.contiguous() for _, t in named]
+
+
+def domain_grid(mix_cat, mix_an, ref):
+    """Every pair's distance to the reference set (impnn_domain_grid): ``mix_cat`` (C,Mx), ``mix_an`` (A,Mx) -
+    ``head_ion_mix`` rows - and ``ref`` (R,Mx) -> (distance (C,A) float32, nearest (C,A) int32) on the device: the
+    Euclidean distance from mix_cat[i] + mix_an[j] to its nearest reference row and that row's index (the lowest among
+    equals); NaN / -1 where the pair's vector holds a NaN.  What ``data.grid_domain`` computes in float64."""
+    mix_cat, mix_an, ref = _domain_operands(ref, mix_cat=mix_cat, mix_an=mix_an)
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    distance = torch.empty(C_, A_, dtype=torch.float32, device=ref.device)
+    nearest = torch.empty(C_, A_, dtype=torch.int32, device=ref.device)
+    with torch.cuda.device(ref.device):
+        check(_lib.load().impnn_domain_grid(ptr(mix_cat), ptr(mix_an), ptr(ref), ptr(distance), ptr(nearest), C_, A_,
+                                            int(ref.shape[0]), int(ref.shape[1]), stream_ptr()))
+    return distance, nearest
+
+
+def domain_grid_mask(mix_cat, mix_an, ref, lo, hi):
+    """``domain_grid``'s distance as a packed pair mask (impnn_domain_grid_mask): bit (i,j) = lo <= distance <= hi as
+    float32 for the distance ``domain_grid`` gives that pair (a NaN fails; +-inf: no limit) -> int32 words (C,W), W =
+    ceil(A / 32), pad bits 0: the ``words`` of a ``data.PairMask`` of shape (C,A).  No (C,A) floats exist."""
+    lo, hi = C.c_float(lo).value, C.c_float(hi).value  # as the kernels see them: float32
+    if lo != lo or hi != hi:
+        raise ValueError("a mask bound is NaN (an infinity means no limit)")
+    mix_cat, mix_an, ref = _domain_operands(ref, mix_cat=mix_cat, mix_an=mix_an)
+    C_, A_ = int(mix_cat.shape[0]), int(mix_an.shape[0])
+    words = torch.empty(C_, data.mask_row_words(A_), dtype=torch.int32, device=ref.device)
+    with torch.cuda.device(ref.device):
+        check(_lib.load().impnn_domain_grid_mask(ptr(mix_cat), ptr(mix_an), ptr(ref), lo, hi, ptr(words), C_, A_,
+                                                 int(ref.shape[0]), int(ref.shape[1]), stream_ptr()))
+    return words
+
+
+def domain_rows(z, ref, exclude_self=False):
+    """The distance of explicit query rows ``z`` (Q,Mx) to the reference set (impnn_domain_rows) -> (distance (Q,)
+    float32, nearest (Q,) int32) on the device; a row equal to mix_cat[i] + mix_an[j] gets the bits of ``domain_grid``'s
+    element (i,j).  ``exclude_self``: query p skips reference row p (Q == R): with ``z`` the reference rows themselves,
+    every reference row's distance to its nearest other row (NaN / -1 when R == 1)."""
+    z, ref = _domain_operands(ref, bool(exclude_self), z=z)
+    Q = int(z.shape[0])
+    distance = torch.empty(Q, dtype=torch.float32, device=ref.device)
+    nearest = torch.empty(Q, dtype=torch.int32, device=ref.device)
+    with torch.cuda.device(ref.device):
+        check(_lib.load().impnn_domain_rows(ptr(z), ptr(ref), int(bool(exclude_self)), ptr(distance), ptr(nearest), Q,
+                                            int(ref.shape[0]), int(ref.shape[1]), stream_ptr()))
+    return distance, nearest
+
+
 def transfer_head(pooled_cat, pooled_an, weights, cfg):
     """The transfer model's head in inference, one launch (impnn_transfer_head): ``weights`` the 18 tensors in the
     order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg -> (B,1)."""

@@ -10,6 +10,7 @@ python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each 
 python tools/screen_bench.py --rank [--where FRACTION] [--quick]        -> the best-k pair mask instead (see below)
 python tools/screen_bench.py --ensemble M [--select] [--where FRACTION] [--size N]  -> a deep ensemble instead (see below)
 python tools/screen_bench.py --pareto [--where FRACTION] [--size N]     -> the Pareto front of two models instead (see below)
+python tools/screen_bench.py --domain R [--size N]                       -> the applicability domain instead (see below)
 
 Method: three alternating rounds (expanded, grid, expanded, grid, ...) after one warm-up of each, HIP events around each
 call on the current stream plus a host synchronisation (both entries end with a device-to-host copy), median per side.
@@ -58,7 +59,16 @@ pairs (--size, default 4096), both minimised, against the way to the same front 
 data.pareto_front on the host.  Three alternating rounds after a warm-up of each, wall time, median and spread; the two
 ways must return the same front.  Plus the filter's stages alone over the two resident planes (begin, range, minima,
 staircase, collect: 10 runs between two HIP events, three rounds), and the candidate count against the front size.  With
---where F both ways run under one random pair mask of density F."""
+--where F both ways run under one random pair mask of density F.
+
+--domain R: the applicability domain of a viscosity model (atom_dim 32, 3 steps) over N x N pairs (--size, default 4096)
+against R reference pairs drawn from the grid: MPNNModel.screen_domain_mask(at_most = radius(0.95)) and
+MPNNModel.domain_grid against the torch path a user would write without them - gathered tiles of z = mix_cat[i] +
+mix_an[j], torch.cdist against the reference rows, min - from the same encode_ions and head_ion_mix rows.  Three
+alternating rounds after a warm-up of each, wall time, median and spread.  Plus the launches alone over resident mixing
+rows (impnn_domain_grid, impnn_domain_grid_mask, and the torch tile loop), 5 calls between two HIP events, three rounds
+each in turn, the kernel's 2 * R * Mx lane operations per pair over its time, and how far the torch distances lie from
+the kernel's (torch.cdist expands |z|^2 - 2 z.r + |r|^2 on the matrix cores: a training pair is not at exactly 0)."""
 import argparse
 import json
 import statistics
@@ -86,10 +96,12 @@ ap.add_argument("--ensemble", type=int, metavar="M", help="a ModelEnsemble of M 
                 "and the host statistic; with --select the top-k on the score")
 ap.add_argument("--pareto", action="store_true", help="time screen_pareto (viscosity x melting point) against two predict_grid "
                 "calls and data.pareto_front on the host")
-ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --pareto: cations = anions = this many")
+ap.add_argument("--domain", type=int, metavar="R", help="time screen_domain_mask and domain_grid over R reference pairs "
+                "against gathered tiles, torch.cdist and min")
+ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --pareto, --domain: cations = anions = this many")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners or args.rank or args.ensemble or args.pareto  # another table than the default one
+other = args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -256,7 +268,74 @@ def same_partners(a, b):
 
 RANK_CONFIGS = ("config2 2048x2048x4", "transfer 1024x1024", "transfer 4096x4096")  # the rows of the selection table
 
-if args.pareto:
+DOMAIN_TILE_FLOATS = 1 << 28  # the torch path's pairs x R distance tile: 1 GiB of float32
+
+if args.domain:
+    N, R = args.size, args.domain
+    m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+    m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
+    cat, _ = species(N, 1)
+    _, an = species(N, 2)
+    flat = np.random.default_rng(3).choice(N * N, size=R, replace=False)
+    dom = m.fit_domain(cat, an, flat // N, flat % N)
+    radius = dom.radius(0.95)
+    Mx = m.mixing_size
+
+    def mixing_rows():
+        with torch.no_grad():
+            pc, pa = m.encode_ions(cat, an)
+            w = m._packed_head()
+            return ops.head_ion_mix("viscosity", "cat", pc, w, m.fp_size, Mx), ops.head_ion_mix("viscosity", "an", pa, w, m.fp_size, Mx)
+
+    def torch_tiles(mc, ma):
+        """Gathered tiles of z, torch.cdist, min -> (distance, nearest) (N,N) on the device."""
+        rows = max(1, DOMAIN_TILE_FLOATS // (N * len(dom)))
+        ds, ns = [], []
+        for lo in range(0, N, rows):
+            z = (mc[lo:lo + rows, None, :] + ma[None, :, :]).reshape(-1, Mx)
+            d, n = torch.cdist(z, dom.rows).min(dim=1)
+            ds.append(d)
+            ns.append(n)
+        return torch.cat(ds).reshape(N, N), torch.cat(ns).reshape(N, N)
+
+    def torch_way():
+        d, n = torch_tiles(*mixing_rows())
+        return d.cpu().numpy(), n.cpu().numpy(), data.PairMask.from_bool((d <= float(radius)).cpu().numpy())
+
+    new_mask = lambda: m.screen_domain_mask(cat, an, dom, at_most=radius)
+    new_grid = lambda: m.domain_grid(cat, an, dom)
+    (d_t, n_t, mask_t), mask_k, (d_k, n_k) = wall(torch_way)[1], wall(new_mask)[1], wall(new_grid)[1]
+    t_torch, t_mask, t_grid = [], [], []
+    for _ in range(3):
+        t_torch.append(wall(torch_way)[0])
+        t_mask.append(wall(new_mask)[0])
+        t_grid.append(wall(new_grid)[0])
+    mc, ma = mixing_rows()
+    runs = {"domain_grid": lambda: [ops.domain_grid(mc, ma, dom.rows) for _ in range(5)],
+            "domain_grid_mask": lambda: [ops.domain_grid_mask(mc, ma, dom.rows, -np.inf, radius) for _ in range(5)],
+            "torch_tiles": lambda: [torch_tiles(mc, ma) for _ in range(5)]}
+    got = {n: [] for n in runs}
+    for fn in runs.values():
+        timed(fn)
+    for _ in range(3):
+        for n, fn in runs.items():
+            got[n].append(timed(fn)[0] / 5 * 1e3)
+    far = d_k > 0
+    line = {"config": f"domain {N}x{N} R={len(dom)} Mx={Mx}", "C": N, "A": N, "R": len(dom), "Mx": Mx, "radius": float(radius),
+            "inside": int(mask_k.count()), "torch_cdist_min_ms": spread(t_torch), "screen_domain_mask_ms": spread(t_mask),
+            "domain_grid_ms": spread(t_grid),
+            "speedup_mask": round(statistics.median(t_torch) / statistics.median(t_mask), 2),
+            "speedup_grid": round(statistics.median(t_torch) / statistics.median(t_grid), 2),
+            "launch_us": {n: spread(x) for n, x in got.items()},
+            "kernel_lane_ops_per_s": round(N * N * 2.0 * len(dom) * Mx / (statistics.median(got["domain_grid"]) * 1e-6), 0),
+            "torch_max_rel_diff": float(np.max(np.abs(d_t[far] - d_k[far]) / d_k[far])),
+            "torch_max_at_training_pairs": float(d_t[dom.cation, dom.anion].max()),
+            "kernel_max_at_training_pairs": float(d_k[dom.cation, dom.anion].max()),
+            "torch_nearest_differs": int((n_t != n_k).sum()),
+            "torch_mask_bits_differ": int((mask_t.to_bool() != mask_k.to_bool()).sum())}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+elif args.pareto:
     from ionic_mpnn_amd import Objective, screen_pareto
     N = args.size
     v = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
