@@ -255,7 +255,10 @@ int impnn_global_sum_pool(const float* h, const int32_t* atom_ids, float* out, i
  *                                 num_steps=6), N <= 256, E <= 1024, Vb <= 512: the same arithmetic as a short sequence
  *                                 of launches per call on compact kept rows (per type-run GEMMs for the messages,
  *                                 slot-order sums, GatedUpdate on 64-row tiles; csrc/encoder_wide.hip); `workgroups`
- *                                 is ignored there.
+ *                                 is ignored there.  A batch must keep its compact rows within 32-bit float offsets,
+ *                                 (n_ions B N + 128 n_ions + 128) D < 2^31 (52 427 pairs at N = 160, D = 128), and its
+ *                                 edge slots within 32-bit indices: impnn_encoder_workspace_bytes answers
+ *                                 IMPNN_E_UNSUPPORTED beyond that - split the batch.
  *    IMPNN_ENCODER_F32X3_TYPED (3): mode 2 with the GatedUpdate GEMMs on the bf16 matrix pipe: every f32 operand is carried
  *                                 EXACTLY as three bf16 terms (3 x 8 significant bits, fp32's exponent range) and all nine
  *                                 cross products are accumulated in f32 (9 x v_mfma_f32_16x16x32_bf16 per 8 f32 MFMAs):

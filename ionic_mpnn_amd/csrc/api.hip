@@ -355,6 +355,9 @@ int impnn_encoder_workspace_bytes(int32_t n_ions, int32_t B, int32_t N, int32_t 
   if (!encoder_fused_supported(mode, N, E, D, K, S, Vb))
     return fail(IMPNN_E_UNSUPPORTED, "encoder_fused: mode=%d shape N=%d E=%d D=%d K=%d S=%d Vb=%d not covered", mode,
                 N, E, D, K, S, Vb);
+  if (D != enc::kD && !encoder_wide_batch_covered(n_ions, B, N, E, D, Vb))  // before anything is allocated for it
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_fused: batch of %d pairs x (N=%d, E=%d) at D=%d exceeds 32-bit row / edge "
+                "indices or row offsets: split the batch", B, N, E, D);
   *bytes = encoder_fused_workspace_bytes(mode, n_ions, B, N, E, D, S, Vb, encoder_workgroups(n_ions, B, workgroups, N, E, mode));
   return IMPNN_OK;
 }

@@ -2317,6 +2317,17 @@ size_t encoder_wide_workspace_bytes(int n_ions, int B, int N, int E, int D, int 
   return wide::ws_layout(n_ions, B, N, E, D, S, Vb, x3).total;
 }
 
+// Do the kernels' 32-bit indices cover a batch of this shape?  Sorted positions and compact rows are 32-bit indices
+// (vmax, rmax), and the update kernels address a row's sources as 32-bit FLOAT offsets from `agg` (wide::agg_off: row
+// codes up to rmax, the row of zeros, times D).  While messages are named directly wide_direct_sources() bounds more
+// than that; with every row's sum in agg (the largest batches) this is the only bound on rmax * D, so it is part of
+// the shape coverage: at D = 128 a batch passes it up to 16.7 M rows - 52 427 pairs of the explicit-hydrogen shape
+// (N = 160), 209 710 pairs at N = 40.  (Every other row * D product of this file is formed in 64 bits.)
+bool encoder_wide_batch_covered(int n_ions, int B, int N, int E, int D, int Vb) {
+  const wide::Ws w = wide::ws_layout(n_ions, B, N, E, D, 0, Vb, false);  // rmax and vmax depend on neither S nor the mode
+  return w.vmax < INT_MAX && (w.rmax + 1) * (int64_t)D < ((int64_t)1 << 31);
+}
+
 size_t encoder_wide_prepared_bytes(int D, int S, int Vb, bool x3) { return wide::prepared_bytes(D, S, Vb, x3); }
 
 int launch_encoder_wide_prepare(const float* weights, const float* bond_table, int D, int K, int S, int Vb, bool x3,
@@ -2373,9 +2384,9 @@ int launch_encoder_wide(const EncoderArgs& a, hipStream_t s) {
   const bool x3 = a.mode == 3;
   const Ws w = ws_layout(a.n_ions, a.B, a.N, a.E, a.D, a.S, a.Vb, x3);
   if (!aligned16(a.workspace)) return fail(IMPNN_E_BADARG, "encoder_fused: workspace must be 16B aligned");
-  if (w.vmax >= INT_MAX || w.rmax >= INT_MAX)  // sorted positions and compact rows are 32-bit indices
-    return fail(IMPNN_E_UNSUPPORTED, "encoder_fused: batch of %d pairs x (N=%d, E=%d) exceeds 32-bit row / edge indices",
-                a.B, a.N, a.E);
+  if (!encoder_wide_batch_covered(a.n_ions, a.B, a.N, a.E, a.D, a.Vb))  // (impnn_encoder_workspace_bytes says so first)
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_fused: batch of %d pairs x (N=%d, E=%d) at D=%d exceeds 32-bit row / edge "
+                "indices or row offsets", a.B, a.N, a.E, a.D);
   char* base = static_cast<char*>(a.workspace);
   auto I = [&](size_t off) { return reinterpret_cast<int32_t*>(base + off); };
   auto F = [&](size_t off) { return reinterpret_cast<float*>(base + off); };

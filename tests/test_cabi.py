@@ -90,6 +90,44 @@ def test_encoder_shape_coverage_is_reported():
     assert lib.impnn_encoder_prepared_bytes(128, 6, 72, F32) == 0 and lib.impnn_encoder_prepared_bytes(48, 6, 72, TYPED) == 0
 
 
+def test_wide_encoder_refuses_batches_beyond_its_32_bit_offsets():
+    """The wide encoder's coverage of a BATCH (csrc/encoder_wide.hip, encoder_wide_batch_covered): its update kernels
+    address a row's aggregated messages as 32-bit float offsets from `agg` - rows up to rmax, the row of zeros, times D -
+    and sorted edge positions up to vmax are 32-bit indices.  With every row's sum in agg (the largest batches) nothing
+    else bounds rmax * D, so impnn_encoder_workspace_bytes refuses such a batch before anything is allocated for it:
+    one shape on each side of each bound."""
+    lib = _lib.load()
+    need = C.c_size_t(0)
+    TYPED, X3, Vb = 2, 3, 72
+
+    def rmax(B, N):            # compact rows of two ions: whole 128-row tiles, each ion aligned to 128
+        return (2 * B * N + 2 * 128 + 127) // 128 * 128
+
+    def vmax(B, E, D):         # sorted positions: a type's run is padded to whole message tiles
+        return 2 * B * E + (2 * Vb + 2) * (64 if D == 128 else 128)
+
+    def covered(B, N, E, D, mode=TYPED):
+        rc = lib.impnn_encoder_workspace_bytes(2, B, N, E, D, 8, 6, Vb, mode, 0, C.byref(need))
+        assert rc in (0, -2), rc
+        if rc:
+            assert b"32-bit" in lib.impnn_last_error_string()
+        return rc == 0
+
+    # rows: (rmax + 1) * D < 2^31.  The explicit-hydrogen shape at D = 128 passes it up to 52 427 pairs
+    for B, N, E, D in ((52427, 160, 640, 128), (209710, 40, 80, 128), (104856, 160, 640, 64)):
+        assert (rmax(B, N) + 1) * D < 2 ** 31 <= (rmax(B + 1, N) + 1) * D and vmax(B + 1, E, D) < 2 ** 31 - 1
+        for mode in (TYPED, X3):
+            assert covered(B, N, E, D, mode) and need.value > (rmax(B, N) * D * 4) * 2
+            assert not covered(B + 1, N, E, D, mode)
+    # edges: vmax < 2^31 - 1 (few rows, many edge slots)
+    for D in (128, 64):
+        B = (2 ** 31 - 2 - (2 * Vb + 2) * (64 if D == 128 else 128)) // (2 * 1024)
+        assert vmax(B, 1024, D) < 2 ** 31 - 1 <= vmax(B + 1, 1024, D) and (rmax(B + 1, 1) + 1) * D < 2 ** 31
+        assert covered(B, 1, 1024, D) and not covered(B + 1, 1, 1024, D)
+    # the atom_dim 32 encoders have their own records and are not concerned
+    assert lib.impnn_encoder_workspace_bytes(2, 60000, 160, 640, 32, 8, 3, Vb, TYPED, 0, C.byref(need)) == 0
+
+
 def test_encoder_sizing_has_no_hidden_state():
     """The workgroup count is an argument, not library state: two host threads sizing workspaces with different
     counts at the same time always get the answer that belongs to their own arguments."""
