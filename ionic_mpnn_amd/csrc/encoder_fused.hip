@@ -669,6 +669,7 @@ int launch_encoder_phase(const EncoderArgs& a, hipStream_t s, bool plan_phase) {
   pp.nsub = reinterpret_cast<int32_t*>(base + w.nsub_off);
   pp.desc = reinterpret_cast<int32_t*>(base + w.desc_off);
   pp.rec = reinterpret_cast<unsigned char*>(base + w.rec_off);
+  pp.slist = reinterpret_cast<uint32_t*>(base + w.slist_off);
   pp.header = reinterpret_cast<PlanHeader*>(base);
   pp.typed = typed ? 1 : 0;
   pp.ecap = tecap_of(a.E);

@@ -116,6 +116,16 @@ __host__ __device__ constexpr int tmsg_off(int s, int u) { return s * kD + ((u ^
 // the same as one XOR per lane: float offset of feature f (0..31) of slot s = tmsg_key(s) ^ f
 __host__ __device__ constexpr int tmsg_key(int s) { return s * kD + (((s >> 1) & 7) << 2); }
 static_assert(tmsg_key(kTECapBig + 1) < 65536, "message keys travel as 16 bits");
+// Slot-ordered source list of a chunk (typed plans; a workspace region of its own, ecap words per chunk, read from global
+// memory only): one u32 per valid message slot s < edges - the valid slots are dense, slot(row, d) = jdptr[d] + row covers
+// [0, edges) - with the edge's bond type in the top 8 bits and the atom id of its source row in the low 24; an id that is
+// negative or >= kSrcIdNone is stored as kSrcIdNone, which the encoder clamps to column Va of the step-0 table exactly
+// where fill_h0 writes zeros.  Words at and beyond `edges` (the descriptor's z) are never written and never trusted.
+constexpr uint32_t kSrcIdNone = 0xffffffu;
+__host__ __device__ constexpr uint32_t tsrc_word(int type, int atom_id) {
+  return ((uint32_t)type << 24) | ((uint32_t)atom_id < kSrcIdNone ? (uint32_t)atom_id : kSrcIdNone);
+}
+static_assert(kTECap % 8 == 0 && kTECapBig % 8 == 0, "the encoder moves step-0 messages in granules of 8 slots");
 // per-step update image (mode 2): the gate kernels in the A-operand order of v_mfma_f32_16x16x4_f32 - 24 blocks
 // (gate, T, half, u) of 64 lanes x 4 floats, lane (a = l & 15, q = l >> 4), element r:
 //     W_gate[(32 half + 16 u + 4 q + r) * 32 + 16 T + a]       (keras kernel (64, 32): [input][output])
@@ -180,12 +190,12 @@ inline int plan_vmin(int n_ions, int B, int vrmax, int nwg) {
 }
 constexpr int kMaxHops = 128;     // chunks of one share (Ws::max_sub <= kMaxHops: encoder_workgroups sees to it)
 
-// chunk descriptor (int4): {first molecule, molecules, 0, rows | ion << 16}
+// chunk descriptor (int4): {first molecule, molecules, valid edges (typed plans; 0 in pull-form plans), rows | ion << 16}
 constexpr int kPB = 16;  // molecules per plan_stats workgroup (= partial-sum granularity)
 
 // ---- workspace layout (bytes, all 256-aligned sections)
 struct Ws {
-  size_t img_off, rows_off, vr_off, partial_off, share_off, nsub_off, desc_off, rec_off, total;
+  size_t img_off, rows_off, vr_off, partial_off, share_off, nsub_off, desc_off, rec_off, slist_off, total;
   int nwg;      // persistent encoder workgroups (= compute units)
   int max_sub;  // chunk slots per workgroup (upper bound of chunks in one share)
   int nblk;     // 16-molecule blocks per ion
@@ -248,6 +258,8 @@ inline Ws ws_layout(int n_ions, int B, int N, int E, int S, int Vb, int nwg, boo
   off = align_up(off + (size_t)nwg * w.max_sub * 4 * sizeof(int32_t), 256);
   w.rec_off = off;
   off = align_up(off + (size_t)nwg * w.max_sub * w.rec_bytes, 256);
+  w.slist_off = off;  // typed plans: the chunks' slot-ordered source lists (tsrc_word), tecap_of(E) words per chunk
+  if (typed) off = align_up(off + (size_t)nwg * w.max_sub * tecap_of(E) * sizeof(uint32_t), 256);
   w.total = off;
   return w;
 }
@@ -262,6 +274,7 @@ struct PlanParams {
   int32_t* nsub;      // [nwg]           chunks of every encoder workgroup
   int32_t* desc;      // [nwg][max_sub][4]
   unsigned char* rec; // [nwg][max_sub][kRecBytes]
+  uint32_t* slist;    // typed: [nwg][max_sub][ecap] slot-ordered source lists (tsrc_word)
   int n_ions, B, N, E, Va, Vb, nwg, max_sub, nblk;
   int grid_sub;  // plan_chunks workgroups launched per share (<= max_sub)
   int typed;     // 1: typed records (kTRecBytes), ecap / kRCap valid edges per virtual row
@@ -311,6 +324,7 @@ struct TEncParams {
   const int32_t* nsub;
   const int32_t* desc;
   const unsigned char* rec;
+  const uint32_t* slist;  // per chunk: ecap words, the source of every valid message slot (tsrc_word)
   const PlanHeader* header;
   int n_ions, B, S, Va, Vb, max_sub;
   int atab_lds;

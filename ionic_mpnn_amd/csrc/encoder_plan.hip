@@ -797,7 +797,7 @@ __global__ __launch_bounds__(kRCap, 5) void plan_chunks_kernel(PlanParams p) {  
 //       (prefix over the suffix counts); wave 1: groups per type, first group of every type, the run table
 //   P4  rows take their place; per-row tables of the record; the type's groups with their headers
 //   P5  per valid edge: its rank among the in-edges of its row in edge-slot order = the tickets with a smaller slot
-//       number -> message slot; a place in a group of its type
+//       number -> message slot; a place in a group of its type; its word in the slot-ordered source list
 //   P6  group table -> record
 // Dynamic LDS: the group table (16 B x tgrp_cap).
 constexpr int kTick = 16;
@@ -829,13 +829,13 @@ __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams 
   const int mb_local = T.cb[sl], M = T.cb[sl + 1] - mb_local, m0 = first_mol + mb_local;
   const int base = T.shst[mb_local];
   const int R = T.shst[mb_local + M] - base;
-  const int idx = j * p.max_sub + sl;
-  if (tid == 0) reinterpret_cast<int4*>(p.desc)[idx] = make_int4(m0, M, 0, R | (g << 16));
+  const int idx = j * p.max_sub + sl;  // (the descriptor is written in P4: it carries the chunk's valid-edge count)
   const int32_t* ids_g = p.atom_ids[g];
   const int32_t* conn_g = p.conn[g];
   const int32_t* bond_g = p.bond_ids[g];
   const int32_t* rows_g = p.rows + (int64_t)g * p.B;
   unsigned char* rec = p.rec + (size_t)idx * kTRecBytes;
+  uint32_t* r_slist = p.slist + (size_t)idx * p.ecap;
   uint16_t* r_rowdeg = reinterpret_cast<uint16_t*>(rec + kTRecRowdeg);
   unsigned char* r_tilemax = rec + kTRecTilemax;
   uint16_t* r_moloff = reinterpret_cast<uint16_t*>(rec + kTRecMoloff);
@@ -1075,6 +1075,10 @@ __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams 
       r_cw[1] = (uint16_t)jdp[kRCap];
       r_cw[2] = (uint16_t)dcl;
     }
+    // z: the valid edges = the message slots in use (never beyond ecap, whatever an overflowed plan counted: the encoder
+    // sizes its step-0 transfers by it)
+    if (tid == 0)
+      reinterpret_cast<int4*>(p.desc)[idx] = make_int4(m0, M, jdp[kRCap] < p.ecap ? jdp[kRCap] : p.ecap, R | (g << 16));
   }
   {
     // the groups of type `tid`: x = type | edges << 8 | groups of this type from this one on << 24; unused edge lanes
@@ -1149,6 +1153,9 @@ __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams 
           unsigned char* ge = reinterpret_cast<unsigned char*>(&grp[gb[k] + (ix[k] >> 2)]);
           ge[4 + (ix[k] & 3)] = (unsigned char)srow[k];
           reinterpret_cast<uint16_t*>(ge + 8)[ix[k] & 3] = (uint16_t)tmsg_key(rank[k] + row[k]);
+          // the same edge in the slot-ordered source list: its type and the atom id of its source row
+          if (rank[k] + row[k] < p.ecap)
+            r_slist[rank[k] + row[k]] = tsrc_word((int)(en[k].x >> 16), idl[(en[k].x >> 8) & 0xffu]);
         }
       }
     }

@@ -19,7 +19,9 @@
 //     encoder_fused.hip's f32 mode, h updated in place.
 //
 //   step 0: h[src] is atom_table[atom id] (or zeros), so its messages depend on the weights alone; an image prepared with
-//     the atom table carries them as a table (encoder_layout.h: M0Header) and the chunk prologue gathers them instead.
+//     the atom table carries them as a table (encoder_layout.h: M0Header), and its rows travel L2 -> LDS by
+//     global_load_lds, addressed by the plan's slot-ordered source list, while the PREVIOUS chunk is pooled; step 0's
+//     update image goes the same way.
 //
 // MFMA work per row is 12 D^2 (update) + 2 D^2 per in-edge, against (12 + 2 K) D^2 per row in the pull form:
 // 2.7 kflop instead of 28.7 kflop per row for the message at bond_dim 8 and 1.7 in-edges per row.
@@ -123,6 +125,22 @@ __device__ __forceinline__ f32x4 mfma1(float a, float b, f32x4 c) {
 // One group of the message phase: its record entry and the A operands of its 16 MFMAs - lane l = 32 kh + 4 b + i holds
 // h[source row of edge i][16 kh + 2 b] and [.. + 2 b + 1]: one ds_read_b64 per lane, no lane idle, two registers.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+// global_load_lds_dwordx4: lane l's 16 bytes at gsrc -> LDS at dst + 16 l (dst: wave-uniform), no register in between.
+// As an asm statement, not as __builtin_amdgcn_global_load_lds: the compiler orders a transfer it knows of against EVERY
+// later LDS access it cannot tell apart from the destination - it waited vmcnt(0) between any two transfers into the message
+// buffer and in front of the pool's first LDS read, which is the overlap this is for.  A transfer issued here is unknown
+// to the compiler's s_waitcnt bookkeeping (its own counted waits only become longer: loads return in order), so whoever
+// reads the destination waits vmcnt(0) explicitly, then a barrier, then reads.  M0 is the compiler's: saved and restored;
+// the s_nop is the wait state between a scalar write of M0 and a vector-memory instruction that reads it.
+__device__ __forceinline__ void glds16(const void* gsrc, const float* dst) {
+  const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_ptr_t)dst);
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(gsrc), "s"(lds_dst)
+               : "memory");
+}
 struct Grp {
   uint4 ge;
   f32x2v aq;
@@ -312,8 +330,12 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
         v0 = ld4(atab + id * kTAS + 8 * sub);
         v1 = ld4(atab + id * kTAS + 8 * sub + 4);
       } else {
-        v0 = ld4(p.atom_table + (int64_t)id * kD + 8 * sub);
-        v1 = ld4(p.atom_table + (int64_t)id * kD + 8 * sub + 4);
+        // (an opaque copy of the lane's part: the 64-bit address atom_table + 8 sub would otherwise be kept - spilled -
+        //  through the whole kernel for this cold path)
+        int sb = sub;
+        asm volatile("" : "+v"(sb));
+        v0 = ld4(p.atom_table + (int64_t)id * kD + 8 * sb);
+        v1 = ld4(p.atom_table + (int64_t)id * kD + 8 * sb + 4);
       }
     }
     st4(hbuf + row * HS + 8 * sub, v0);
@@ -354,6 +376,68 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
   uint32_t rec_n4 = rec_big ? reinterpret_cast<const uint32_t*>(rec_c + kTRecPart1)[tid] : 0u;
   int4 dsc_next = reinterpret_cast<const int4*>(p.desc)[c_begin];
 
+  // ---- Step 0's inputs of chunk `cn` (descriptor dn), global -> LDS without a register in between (glds16):
+  //   * step 0's update image of the chunk's ion -> wupd, 64 units of 16 bytes per instruction;
+  //   * if that ion's image carries the table: the chunk's step-0 messages -> msg.  The valid message slots are dense in
+  //     [0, edges) and a slot is 128 contiguous bytes, so one instruction fills the eight slots base .. base + 7: lane l
+  //     copies, for slot s = base + (l >> 3), the unit that tmsg_off places at position l & 7 of the slot, out of row
+  //     M0[type][min(id, Va)] - type and id from the plan's slot-ordered list (encoder_layout.h: tsrc_word).  Slots at
+  //     and beyond `edges` (the list holds nothing there: never read) copy row 0 into slots nothing reads; edges <= ecap
+  //     and ecap is a multiple of 8, so the rounding reaches neither the dump slot nor the slot of zeros.
+  // Called where nothing reads or writes msg and wupd - the kernel preamble, and behind the end-of-step barrier of a
+  // chunk's last step - so the transfers fly under the pool and the record copy; the prologue barrier in front of step 0
+  // waits for them (vmcnt(0)).  `dn` must be cn's descriptor: the table bit is the NEXT chunk's ion's.
+  auto fetch_step0 = [&](const int4 dn, int cn) {
+    const int gn = __builtin_amdgcn_readfirstlane(dn.w) >> 16;
+    const float* const ug = p.upd[gn];
+    static_assert(kUpdLds % 256 == 0, "whole 64-lane transfers");
+    // (the lane and wave roles are derived here, behind opaque copies of the two ids: hoisted out of the chunk loop they
+    //  would occupy registers - vector and scalar - through the whole kernel, which has none to spare)
+    int ln = lane, wv = wave;
+    asm volatile("" : "+v"(ln), "+s"(wv));
+    const bool tabn = (tabmask >> gn) & 1u;  // workgroup-uniform
+    int edges = __builtin_amdgcn_readfirstlane(dn.z);
+    edges = tabn ? (edges < p.ecap ? edges : p.ecap) : 0;
+    constexpr int kIt = (kTECapBig / 8 + kWaves - 1) / kWaves;  // granules per wave at most
+    // All list words first: one round trip, not one per granule.  Unconditional loads (a clamped address inside the
+    // chunk's list; the word is dropped where the slot is not in use), all of them landed in front of the first message
+    // transfer (the empty asm below): nothing the compiler knows of is then in flight behind this lambda, so it places
+    // no s_waitcnt of its own - which would wait for the transfers as well - in front of the pool.
+    uint32_t sw[kIt];
+    if (tabn) {
+      const uint32_t* const lst = p.slist + (size_t)cn * p.ecap;
+#pragma unroll
+      for (int i = 0; i < kIt; ++i) {
+        const int sl = 8 * (wv + i * kWaves) + (ln >> 3);
+        const uint32_t word = lst[sl < edges ? sl : 0];
+        sw[i] = sl < edges ? word : 0u;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < kIt; ++i) sw[i] = 0u;
+    }
+    constexpr int kUIt = (kUpdLds / 256 + kWaves - 1) / kWaves;
+#pragma unroll
+    for (int i = 0; i < kUIt; ++i) {  // (under the list's round trip)
+      const int ub = 64 * (wv + i * kWaves);
+      if (ub < kUpdLds / 4) glds16(ug + 4 * (ub + ln), wupd + 4 * ub);  // (wave-uniform)
+    }
+    static_assert(kIt == 5, "the list words are landed by name");
+    asm volatile("" : "+v"(sw[0]), "+v"(sw[1]), "+v"(sw[2]), "+v"(sw[3]), "+v"(sw[4]) : : "memory");
+    const float* const m0_g = p.m0[gn];
+#pragma unroll
+    for (int i = 0; i < kIt; ++i) {
+      const int base = 8 * (wv + i * kWaves);
+      if (base < edges) {  // (wave-uniform)
+        const int sl = base + (ln >> 3);
+        const unsigned type = min(sw[i] >> 24, (unsigned)p.Vb - 1u), col = min(sw[i] & kSrcIdNone, (unsigned)p.Va);
+        const unsigned off = (type * (unsigned)(p.Va + 1) + col) * kD + 4u * ((ln & 7) ^ ((sl >> 1) & 7));  // the table is < 2 MiB
+        glds16(m0_g + off, msg + kD * base);
+      }
+    }
+  };
+  fetch_step0(dsc_next, c_begin);
+
   // message-phase lane roles (see the message phase below)
   const uint32_t* const grp_x = reinterpret_cast<const uint32_t*>(r_grp);
   const int kh = lane >> 5, f = lane & 31;
@@ -373,54 +457,22 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     const bool tab0 = (tabmask >> g) & 1u;  // workgroup-uniform: step 0's messages come from the table
     if (8 * tid < rec_lds) reinterpret_cast<uint2*>(recl)[tid] = rec_n8;
     if (rec_big && kTRecPart1 + 4 * tid < rec_lds) reinterpret_cast<uint32_t*>(recl + kTRecPart1)[tid] = rec_n4;
-    {
+    lds_barrier();
+    fill_h0();
+    // (step 0's messages - when the image carries the table - and its update image are on their way into LDS since the
+    //  previous chunk's last step: fetch_step0)
+    if (tid == 0) *run_ctr = 2 * kWaves;  // runs 0 .. 2 kWaves - 1 are assigned statically (two per wave)
+    // Prologue barrier: h0 is in place - and so is everything fetch_step0 sent on its way: every wave waits for its own
+    // transfers (vmcnt(0), explicitly: the compiler does not know of them - glds16), the barrier then publishes them to
+    // the others.
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    {  // the record of the next chunk (behind the wait above, so that it does not wait for these loads as well)
       const int cn = (c + 1) < c_end ? (c + 1) : c;  // clamped: unconditional loads
       const unsigned char* rn = p.rec + (size_t)cn * kTRecBytes;
       rec_n8 = reinterpret_cast<const uint2*>(rn)[tid];
       if (rec_big) rec_n4 = reinterpret_cast<const uint32_t*>(rn + kTRecPart1)[tid];
       dsc_next = reinterpret_cast<const int4*>(p.desc)[cn];
     }
-    lds_barrier();
-    fill_h0();
-    if (tab0) {
-      // ---- step 0's messages from the table: m_e = M0[type_e][atom id of src_e], a gather - here, beside fill_h0
-      // (neither reads what the other writes; the barrier below orders both), not at the top of step 0: inside the step
-      // loop the same lines cost the production instantiations 12-32 bytes of scratch, here none.  Eight lanes per edge
-      // lane of the group table, one 16-byte load and one 16-byte LDS store each.  The id is clamped to column Va (the
-      // zero row's message) exactly where fill_h0 writes zeros; the destination is the group's message key (its low two
-      // bits are clear, so key ^ 4 u is the aligned unit u of the slot).  Branch-free like the message phase: an unused
-      // edge lane fetches no row of its own (all of them read the table's first 128 bytes) and stores to the dump slot.
-      // All loads of a round - one round up to 1024 edge lanes - are issued before the first store waits for any.
-      const int ngrp = __builtin_amdgcn_readfirstlane(*reinterpret_cast<const uint16_t*>(recl + kTRecCounts));
-      const float* const m0_g = p.m0[g];
-      // (the lane roles are derived here, behind an opaque copy of tid: hoisted out of the chunk loop they would
-      //  occupy registers through the whole kernel, which has none to spare)
-      int tl = tid;
-      asm volatile("" : "+v"(tl));
-      const unsigned u4 = 4 * (tl & 7);               // 16-byte unit of the row
-      const int i = (tl >> 3) & 3, g0 = tl >> 5;      // edge lane of the group, first group
-      constexpr int kGR = 8;                          // loads in flight per thread
-      const unsigned dump = (unsigned)tmsg_key(p.ecap);
-      for (int gb = 0; gb < ngrp; gb += 32 * kGR) {
-        f32x4 mv[kGR];
-        unsigned dst[kGR];
-#pragma unroll
-        for (int j = 0; j < kGR; ++j) {
-          const int gi = gb + 32 * j + g0;
-          const uint4 ge = r_grp[gi < ngrp ? gi : ngrp - 1];
-          const bool ok = gi < ngrp && i < (int)__builtin_amdgcn_ubfe(ge.x, 8, 8);
-          const int id = r_rowatom[__builtin_amdgcn_ubfe(ge.y, 8 * i, 8)];
-          const unsigned col = (unsigned)id < (unsigned)p.Va ? (unsigned)id : (unsigned)p.Va;
-          const unsigned off = ((ge.x & 0xffu) * (unsigned)(p.Va + 1) + col) * kD + u4;  // the table is < 2 MiB
-          mv[j] = ld4(m0_g + (ok ? off : 0u));
-          dst[j] = (ok ? __builtin_amdgcn_ubfe(i < 2 ? ge.z : ge.w, 16 * (i & 1), 16) : dump) ^ u4;
-        }
-#pragma unroll
-        for (int j = 0; j < kGR; ++j) st4(msg + dst[j], mv[j]);
-      }
-    }
-    if (tid == 0) *run_ctr = 2 * kWaves;  // runs 0 .. 2 kWaves - 1 are assigned statically (two per wave)
-    lds_barrier();
     if (stamp && tid == 0) {
       const unsigned long long t = __builtin_amdgcn_s_memtime();
       t_pro += t - t_mark;
@@ -460,8 +512,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
 #pragma unroll
       for (int i = 0; i < 4; ++i) Q.bq[i] = ld4(tm + soQ + lboffQ + i * 128);
     };
-    // step 0: everything that later steps request during the previous atom phase is requested here
-    if (kPfWhere != 0) fetch_pf(0);
+    // step 0: what later steps request during the previous atom phase is requested here (its update image is in LDS)
     if (kRunsEarly >= 1) fetch_P(0);
     if (kRunsEarly >= 2) fetch_Q(0);
     if (stamp && c == c_begin && tid == 0) stamp[13] = __builtin_amdgcn_s_memtime();  // start of the first chunk's step 0
@@ -480,9 +531,16 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       // this loop costs matrix time: the plan hands over ready-made LDS keys (message slot incl. swizzle; unused edge
       // lanes point at a dump slot, so the stores are unconditional) and the loop body is branch-free.
       __builtin_amdgcn_s_setprio(2);
-      // (a step whose messages came from the table - see the chunk prologue - requests no matrix rows and takes no run)
+      // (a step whose messages came from the table - fetch_step0 - requests no matrix rows and takes no run)
       const bool from_tab = tab0 && s == 0;  // workgroup-uniform
-      if (kPfWhere == 0) fetch_pf(s);
+      if (kPfWhere == 0) {
+        if (s > 0) {
+          fetch_pf(s);
+        } else {  // (defined on this path too: left as they are, the registers would stay live around the whole step loop)
+#pragma unroll
+          for (int i = 0; i < kNPf; ++i) pf[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
       if (!from_tab) {
         const float* const abase = hbuf + acol;
         auto load_group = [&](int e, Grp& G) {
@@ -580,11 +638,18 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
             }
           }
         }
+        // A wave without a run P or Q leaves that run's four loads unused - and, to the compiler, in flight until the
+        // registers are written again, which would be in the pool: its wait there would wait for fetch_step0's transfers
+        // as well.  Landed here, in front of the mid-step barrier, the wait costs nothing.
+        landed(P.bq);
+        landed(Q.bq);
       }
-      // this step's update image -> LDS (ordered by the mid-step barrier)
+      // this step's update image -> LDS (ordered by the mid-step barrier); step 0's is there already (fetch_step0)
+      if (s > 0) {
 #pragma unroll
-      for (int i = 0; i < kNPf; ++i)
-        if (4 * (tid + i * kThreads) < kUpdLds) st4(wupd + 4 * (tid + i * kThreads), pf[i]);
+        for (int i = 0; i < kNPf; ++i)
+          if (4 * (tid + i * kThreads) < kUpdLds) st4(wupd + 4 * (tid + i * kThreads), pf[i]);
+      }
       const bool mstamp = stamp && c == c_begin && s == 1;
       if (mstamp && lane == 0) stamp[16 + wave] = __builtin_amdgcn_s_memtime();
       // Mid-step barrier: every message is in LDS and every read of h by the message phase is done (h is updated in
@@ -756,6 +821,15 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       t_mark = t;
     }
 
+    // the message buffer and the update image are idle from here to the next chunk's step 0: its inputs start their way
+    // (the next record and descriptor, requested a whole chunk's steps ago, are landed by name first: with nothing it knows
+    //  of in flight the compiler places no s_waitcnt of its own into the pool, which would wait for the transfers as well)
+    asm volatile(""
+                 : "+v"(rec_n8.x), "+v"(rec_n8.y), "+v"(rec_n4), "+v"(dsc_next.x), "+v"(dsc_next.y), "+v"(dsc_next.z),
+                   "+v"(dsc_next.w)
+                 :
+                 : "memory");
+    if (c + 1 < c_end) fetch_step0(dsc_next, c + 1);
     pool(M, m0, g);
     lds_barrier();  // the record / h buffers are rewritten by the next chunk's prologue
     if (stamp && tid == 0) {
@@ -852,6 +926,7 @@ int launch_encoder_typed_run(const EncoderArgs& a, const enc::Ws& w, hipStream_t
   ep.nsub = reinterpret_cast<const int32_t*>(base + w.nsub_off);
   ep.desc = reinterpret_cast<const int32_t*>(base + w.desc_off);
   ep.rec = reinterpret_cast<const unsigned char*>(base + w.rec_off);
+  ep.slist = reinterpret_cast<const uint32_t*>(base + w.slist_off);
   ep.header = reinterpret_cast<const PlanHeader*>(base);
   ep.n_ions = a.n_ions; ep.B = a.B; ep.S = a.S; ep.Va = a.Va; ep.Vb = a.Vb; ep.max_sub = w.max_sub;
   ep.ln_eps = a.ln_eps;
