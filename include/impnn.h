@@ -281,6 +281,16 @@ size_t impnn_encoder_plan_overflow_offset(void);
 int impnn_encoder_workspace_bytes(int32_t n_ions, int32_t B, int32_t N, int32_t E, int32_t D,
                                   int32_t K, int32_t S, int32_t Vb, int32_t mode, int32_t workgroups,
                                   size_t* bytes);
+/* Where the chunk plan of such a call lies in its workspace (atom_dim 32 only; other widths: IMPNN_E_UNSUPPORTED).  Same
+ * arguments and refusals as impnn_encoder_workspace_bytes; launches nothing, writes nothing into a workspace.
+ *   out = { nwg, max_sub, rows_off, vr_off, nsub_off, desc_off, ecap (0 for pull-form plans), plan_vmin }
+ * nwg: persistent workgroups (`workgroups` resolved); max_sub: chunk slots per workgroup; byte offsets of int32 tables:
+ * rows / vr [n_ions][B] (kept rows / virtual rows of every molecule), nsub [nwg] (chunks of a workgroup), desc
+ * [nwg][max_sub][4] = {first molecule, molecules, valid edges (typed plans), virtual rows | ion << 16}; ecap: valid edges
+ * a typed chunk holds; plan_vmin: the least virtual rows a molecule counts.  For tests and diagnostics: the layout is
+ * not part of the ABI's promises beyond this query. */
+int impnn_encoder_plan_layout(int32_t n_ions, int32_t B, int32_t N, int32_t E, int32_t D, int32_t K,
+                              int32_t S, int32_t Vb, int32_t mode, int32_t workgroups, int64_t out[8]);
 int impnn_encoder_fused(int32_t n_ions, const int32_t* const* atom_ids,
                         const int32_t* const* bond_ids, const int32_t* const* conn,
                         const float* atom_table, int32_t Va, const float* bond_table, int32_t Vb,

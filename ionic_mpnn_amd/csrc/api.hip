@@ -362,6 +362,29 @@ int impnn_encoder_workspace_bytes(int32_t n_ions, int32_t B, int32_t N, int32_t 
   return IMPNN_OK;
 }
 
+// Where the plan of such a call lies in its workspace (atom_dim 32): the same functions the plan and the run size and
+// address it with (encoder_workgroups, enc::ws_layout, enc::plan_vmin).  Host arithmetic only.
+int impnn_encoder_plan_layout(int32_t n_ions, int32_t B, int32_t N, int32_t E, int32_t D, int32_t K, int32_t S,
+                              int32_t Vb, int32_t mode, int32_t workgroups, int64_t out[8]) {
+  REQUIRE(out, "null pointer");
+  size_t total = 0;
+  if (int rc = impnn_encoder_workspace_bytes(n_ions, B, N, E, D, K, S, Vb, mode, workgroups, &total)) return rc;
+  if (D != enc::kD)
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_plan_layout: atom_dim %d has no chunk plan (atom_dim 32 only)", D);
+  const bool typed = mode >= 2;
+  const int nwg = encoder_workgroups(n_ions, B, workgroups, N, E, mode);
+  const enc::Ws w = enc::ws_layout(n_ions, B, N, E, S, Vb, nwg, typed, mode == 3);
+  out[0] = w.nwg;
+  out[1] = w.max_sub;
+  out[2] = (int64_t)w.rows_off;
+  out[3] = (int64_t)w.vr_off;
+  out[4] = (int64_t)w.nsub_off;
+  out[5] = (int64_t)w.desc_off;
+  out[6] = typed ? enc::tecap_of(E) : 0;
+  out[7] = enc::plan_vmin(n_ions, B, enc::vr_max_of(N, E, typed), w.nwg);
+  return IMPNN_OK;
+}
+
 static int encoder_common(const char* fn, int32_t n_ions, const int32_t* const* atom_ids,
                           const int32_t* const* bond_ids, const int32_t* const* conn, const float* atom_table,
                           int32_t Va, const float* bond_table, int32_t Vb, const float* const* weights,

@@ -3,6 +3,7 @@ the tensor's device and torch's current stream.  Shapes/dtypes follow the refere
 (int32 ids and connectivity, float32 state)."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -453,6 +454,39 @@ def _raise_on_overflow(ws):
     if int(ws[off:off + 4].view(torch.int32).item()) != 0:
         raise EncoderOverflow("a molecule of this batch does not fit one chunk of the fused encoder "
                               "(> 256 kept rows, > 512 valid edges or an in-degree > 255)")
+
+
+PlanLayout = collections.namedtuple("PlanLayout", "nwg max_sub rows_off vr_off nsub_off desc_off ecap plan_vmin")
+Plan = collections.namedtuple("Plan", "rows vr nsub desc ion")
+
+
+def encoder_plan_layout(n_ions, B, N, E, D, K, S, Vb, mode="f32t", workgroups=0):
+    """Where the chunk plan of such a call lies in its workspace (impnn_encoder_plan_layout; atom_dim 32 only): the
+    resolved workgroup count, the chunk slots per workgroup, byte offsets of the plan's tables, the valid edges a typed
+    chunk holds (0: pull-form records) and the least virtual rows a molecule counts.  No device call."""
+    out = (C.c_int64 * 8)()
+    lib = _lib.load()
+    rc = lib.impnn_encoder_plan_layout(n_ions, B, N, E, D, K, S, Vb, ENCODER_MODES[mode], int(workgroups), out)
+    if rc == _lib.IMPNN_E_UNSUPPORTED:
+        raise EncoderUnsupported(lib.impnn_last_error_string().decode())
+    check(rc)
+    return PlanLayout(*[int(v) for v in out])
+
+
+def read_plan(ws, layout, n_ions, B):
+    """Copies a finished plan out of its workspace `ws` (a uint8 tensor; the caller has waited for the plan) -> host
+    numpy arrays: rows, vr [n_ions][B]; nsub [nwg]; desc [nwg][max_sub][4] = first molecule, molecules, valid edges,
+    virtual rows; ion [nwg][max_sub] (out of the descriptor's last word).  Slots at and beyond nsub[j] hold whatever the
+    workspace held before."""
+    def table(off, count):
+        return ws[off:off + 4 * count].view(torch.int32).cpu().numpy().copy()
+    rows = table(layout.rows_off, n_ions * B).reshape(n_ions, B)
+    vr = table(layout.vr_off, n_ions * B).reshape(n_ions, B)
+    nsub = table(layout.nsub_off, layout.nwg)
+    desc = table(layout.desc_off, layout.nwg * layout.max_sub * 4).reshape(layout.nwg, layout.max_sub, 4)
+    ion = desc[:, :, 3] >> 16
+    desc[:, :, 3] &= 0xffff
+    return Plan(rows, vr, nsub, desc, ion)
 
 
 class EncoderUnsupported(RuntimeError):

@@ -128,6 +128,70 @@ def test_wide_encoder_refuses_batches_beyond_its_32_bit_offsets():
     assert lib.impnn_encoder_workspace_bytes(2, 60000, 160, 640, 32, 8, 3, Vb, TYPED, 0, C.byref(need)) == 0
 
 
+def test_encoder_plan_layout_follows_the_size_query():
+    """impnn_encoder_plan_layout: the refusals of impnn_encoder_workspace_bytes in the same order (plus: atom_dim 32
+    only), every table inside the workspace the size query asks for, and the documented floor of 16 workgroups."""
+    lib = _lib.load()
+    need = C.c_size_t(0)
+    out = (C.c_int64 * 8)()
+    F32, F16X2, TYPED, X3 = 0, 1, 2, 3
+    ok = (2, 4096, 40, 80, 32, 8, 3, 72, TYPED, 0)
+    names = ("n_ions", "B", "N", "E", "D", "K", "S", "Vb", "mode", "workgroups")
+
+    def both(**kw):
+        args = [kw.get(n, v) for n, v in zip(names, ok)]
+        for i in range(8):
+            out[i] = -7
+        rc_b, msg_b = lib.impnn_encoder_workspace_bytes(*args, C.byref(need)), lib.impnn_last_error_string()
+        rc_l, msg_l = lib.impnn_encoder_plan_layout(*args, out), lib.impnn_last_error_string()
+        if rc_l:
+            assert list(out) == [-7] * 8, kw   # a refusal writes nothing
+        return rc_b, msg_b, rc_l, msg_l, args
+
+    assert lib.impnn_encoder_plan_layout(*ok, None) == -1 and b"null pointer" in lib.impnn_last_error_string()
+    # the argument refusals: the same status and the same words
+    for kw in (dict(n_ions=0), dict(n_ions=3), dict(B=-1), dict(N=0), dict(E=-1), dict(D=0), dict(K=0), dict(S=-1), dict(Vb=0),
+               dict(mode=4), dict(mode=-1), dict(workgroups=-1), dict(n_ions=3, mode=4, workgroups=-1)):
+        rc_b, msg_b, rc_l, msg_l, _ = both(**kw)
+        assert rc_b == rc_l == -1 and msg_b == msg_l, kw
+    # the coverage refusals
+    for kw in (dict(K=1024, mode=F32), dict(N=160, E=640, mode=F32), dict(D=48), dict(D=128, mode=F32), dict(Vb=257),
+               dict(D=128, E=1100)):
+        rc_b, msg_b, rc_l, msg_l, _ = both(**kw)
+        assert rc_b == rc_l == -2 and msg_b == msg_l and b"not covered" in msg_l, kw
+    # wide states have no chunk plan: covered by the size query, refused here
+    for kw in (dict(D=64), dict(D=128), dict(D=128, mode=X3), dict(D=128, N=160, E=640)):
+        rc_b, _, rc_l, msg_l, _ = both(**kw)
+        assert rc_b == 0 and rc_l == -2 and b"atom_dim 32 only" in msg_l, kw
+    # atom_dim 32: every table lies inside what the size query asks for, in the order of the layout
+    for kw in (dict(), dict(mode=F32), dict(mode=F16X2), dict(mode=X3), dict(B=0), dict(B=1), dict(B=3, workgroups=16),
+               dict(n_ions=1, B=777), dict(N=160, E=640), dict(N=160, E=640, K=1024, S=4), dict(B=60000, N=160, E=640),
+               dict(N=4, E=0, B=3000, workgroups=16), dict(workgroups=48), dict(workgroups=200), dict(S=0)):
+        rc_b, _, rc_l, _, args = both(**kw)
+        assert rc_b == 0 and rc_l == 0, kw
+        nwg, max_sub, rows_off, vr_off, nsub_off, desc_off, ecap, vmin = list(out)
+        n_ions, B, E, mode, wgs = args[0], args[1], args[3], args[8], args[9]
+        total = need.value
+        assert nwg >= 16, kw
+        assert 1 <= max_sub <= 128 and 1 <= vmin <= 256, kw
+        assert 256 <= rows_off and rows_off + 4 * n_ions * B <= vr_off and vr_off + 4 * n_ions * B <= nsub_off, kw
+        assert nsub_off + 4 * nwg <= desc_off and desc_off + 16 * nwg * max_sub <= total, kw
+        assert all(off % 256 == 0 and off <= total for off in (rows_off, vr_off, nsub_off, desc_off)), kw
+        assert ecap == (0 if mode < TYPED else 640 if E > 512 else 512), kw
+        if 0 < wgs <= 256:
+            assert nwg % max(wgs, 16) == 0, kw
+    # a request below 16 workgroups is a request for 16: the same layout, the same size
+    for mode in (F32, TYPED):
+        want = None
+        for wgs in (1, 2, 3, 15, 16):
+            rc_b, _, rc_l, _, _ = both(mode=mode, workgroups=wgs, B=200, N=12, E=24)
+            assert rc_b == 0 and rc_l == 0 and out[0] == 16
+            want = want or (list(out), need.value)
+            assert (list(out), need.value) == want, wgs
+        both(mode=mode, workgroups=17, B=200, N=12, E=24)
+        assert out[0] == 17 and (list(out), need.value) != want
+
+
 def test_encoder_sizing_has_no_hidden_state():
     """The workgroup count is an argument, not library state: two host threads sizing workspaces with different
     counts at the same time always get the answer that belongs to their own arguments."""
