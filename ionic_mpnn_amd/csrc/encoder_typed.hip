@@ -27,6 +27,7 @@
 // 2.7 kflop instead of 28.7 kflop per row for the message at bond_dim 8 and 1.7 in-edges per row.
 #include "encoder_device.h"
 #include "encoder_layout.h"
+#include "kernel_device.h"
 
 namespace impnn {
 namespace enc {
@@ -54,7 +55,7 @@ static_assert(lds_fixed_bytes(true, kTVbMax, kTECap) <= 160 * 1024 && lds_fixed_
 // triples are exact in the MFMA's f32 accumulator, so a GEMM differs from the f32-MFMA one only in the order the
 // (exact) products are added.  v_mfma_f32_16x16x32_bf16 is 16 cycles for 32 k; nine of them replace eight
 // v_mfma_f32_16x16x4_f32 of 32 cycles - on a pipe that, unlike the f32 one, co-executes with the VALU.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef bf16x8_t bf16x8;  // (kernel_device.h)
 struct B3 {
   bf16x8 p0, p1, p2;
 };
@@ -65,17 +66,7 @@ struct B3 {
 // rows it reports non-finite are a superset of mode 2's, and a finite row equals mode 2's up to summation order
 // (tests/test_gpu_encoder.py::test_f32x3_propagates_nan_and_inf_like_f32t; measured: guarding the split costs 4 us per
 // 4096-pair launch and still leaves the 0 * inf terms).
-// two values -> their three packed bf16 pairs (5.5 VALU per value: and, sub, and, sub per value; three perms per pair)
-__device__ __forceinline__ void split_pair(float x, float y, unsigned& w0, unsigned& w1, unsigned& w2) {
-  const unsigned xb = __builtin_bit_cast(unsigned, x), yb = __builtin_bit_cast(unsigned, y);
-  const float x1 = x - __builtin_bit_cast(float, xb & 0xffff0000u), y1 = y - __builtin_bit_cast(float, yb & 0xffff0000u);
-  const unsigned x1b = __builtin_bit_cast(unsigned, x1), y1b = __builtin_bit_cast(unsigned, y1);
-  const float x2 = x1 - __builtin_bit_cast(float, x1b & 0xffff0000u), y2 = y1 - __builtin_bit_cast(float, y1b & 0xffff0000u);
-  // pack the upper halves: low 16 bits <- x, high 16 bits <- y   (v_perm_b32: bytes [y3 y2 x3 x2])
-  w0 = __builtin_amdgcn_perm(yb, xb, 0x07060302u);
-  w1 = __builtin_amdgcn_perm(y1b, x1b, 0x07060302u);
-  w2 = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, y2), __builtin_bit_cast(unsigned, x2), 0x07060302u);
-}
+// (split_pair, kernel_device.h: two values -> their three packed bf16 pairs)
 __device__ __forceinline__ B3 split8x3(f32x4 a, f32x4 b) {
   union {
     bf16x8 v;
@@ -91,9 +82,6 @@ __device__ __forceinline__ B3 split8x3(f32x4 a, f32x4 b) {
   r.p2 = q2.v;
   return r;
 }
-__device__ __forceinline__ f32x4 mfmab(bf16x8 a, bf16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 // c0 += W0 b, c1 += W1 b (W: three planes at blk, blk + 512, blk + 1024): all nine cross products, smallest first, the
 // two accumulator chains interleaved (a dependent v_mfma_f32_16x16x32_bf16 waits ~4 cycles for its predecessor).
 __device__ __forceinline__ void mma9x2(f32x4& c0, f32x4& c1, const __bf16* blk0, const __bf16* blk1, int lane, const B3& b) {
@@ -103,15 +91,15 @@ __device__ __forceinline__ void mma9x2(f32x4& c0, f32x4& c1, const __bf16* blk0,
   const bf16x8 a10 = *reinterpret_cast<const bf16x8*>(blk1 + lane * 8);
   const bf16x8 a11 = *reinterpret_cast<const bf16x8*>(blk1 + 512 + lane * 8);
   const bf16x8 a12 = *reinterpret_cast<const bf16x8*>(blk1 + 1024 + lane * 8);
-  c0 = mfmab(a02, b.p2, c0);  c1 = mfmab(a12, b.p2, c1);
-  c0 = mfmab(a01, b.p2, c0);  c1 = mfmab(a11, b.p2, c1);
-  c0 = mfmab(a02, b.p1, c0);  c1 = mfmab(a12, b.p1, c1);
-  c0 = mfmab(a00, b.p2, c0);  c1 = mfmab(a10, b.p2, c1);
-  c0 = mfmab(a02, b.p0, c0);  c1 = mfmab(a12, b.p0, c1);
-  c0 = mfmab(a01, b.p1, c0);  c1 = mfmab(a11, b.p1, c1);
-  c0 = mfmab(a00, b.p1, c0);  c1 = mfmab(a10, b.p1, c1);
-  c0 = mfmab(a01, b.p0, c0);  c1 = mfmab(a11, b.p0, c1);
-  c0 = mfmab(a00, b.p0, c0);  c1 = mfmab(a10, b.p0, c1);
+  c0 = mfma_bf16(a02, b.p2, c0);  c1 = mfma_bf16(a12, b.p2, c1);
+  c0 = mfma_bf16(a01, b.p2, c0);  c1 = mfma_bf16(a11, b.p2, c1);
+  c0 = mfma_bf16(a02, b.p1, c0);  c1 = mfma_bf16(a12, b.p1, c1);
+  c0 = mfma_bf16(a00, b.p2, c0);  c1 = mfma_bf16(a10, b.p2, c1);
+  c0 = mfma_bf16(a02, b.p0, c0);  c1 = mfma_bf16(a12, b.p0, c1);
+  c0 = mfma_bf16(a01, b.p1, c0);  c1 = mfma_bf16(a11, b.p1, c1);
+  c0 = mfma_bf16(a00, b.p1, c0);  c1 = mfma_bf16(a10, b.p1, c1);
+  c0 = mfma_bf16(a01, b.p0, c0);  c1 = mfma_bf16(a11, b.p0, c1);
+  c0 = mfma_bf16(a00, b.p0, c0);  c1 = mfma_bf16(a10, b.p0, c1);
 }
 
 // v_mfma_f32_4x4x1_16b_f32 with CBSZ = 3: the 16 blocks form two groups of 8 (lanes 0-31 / 32-63) and every block of a

@@ -1,4 +1,5 @@
-// Device and launch helpers shared by train_kernels.hip and message_typed.hip.
+// Device and launch helpers shared by train_kernels.hip, layer_kernels.hip, message_typed.hip, encoder_typed.hip and the
+// wide encoder (wide_device.h).
 #pragma once
 
 #include "common.h"
@@ -13,6 +14,35 @@ __device__ __forceinline__ f32x4_t ldv4(const float* p) { return *reinterpret_ca
 __device__ __forceinline__ void stv4(float* p, f32x4_t v) { *reinterpret_cast<f32x4_t*>(p) = v; }
 __device__ __forceinline__ f32x4_t mfma_f32(float a, float b, f32x4_t c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ float fsig(float x) {
+  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * x));
+}
+// sum over the 16 lanes of a DPP row, result in every lane of the row
+__device__ __forceinline__ float row16_sum_f(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, true));  // row_ror:1
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, true));  // row_ror:2
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, true));  // row_ror:4
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, true));  // row_ror:8
+  return v;
+}
+
+// f32 GEMM products on the bf16 matrix pipe (modes "f32x3"; encoder_typed.hip has the discussion): an f32 value is the
+// exact sum of three bf16 terms, and all nine cross products of two such triples are exact in the f32 accumulator.
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ f32x4_t mfma_bf16(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+// two values -> their three packed bf16 pairs (5.5 VALU per value: and, sub, and, sub per value; three perms per pair)
+__device__ __forceinline__ void split_pair(float x, float y, unsigned& w0, unsigned& w1, unsigned& w2) {
+  const unsigned xb = __builtin_bit_cast(unsigned, x), yb = __builtin_bit_cast(unsigned, y);
+  const float x1 = x - __builtin_bit_cast(float, xb & 0xffff0000u), y1 = y - __builtin_bit_cast(float, yb & 0xffff0000u);
+  const unsigned x1b = __builtin_bit_cast(unsigned, x1), y1b = __builtin_bit_cast(unsigned, y1);
+  const float x2 = x1 - __builtin_bit_cast(float, x1b & 0xffff0000u), y2 = y1 - __builtin_bit_cast(float, y1b & 0xffff0000u);
+  // pack the upper halves: low 16 bits <- x, high 16 bits <- y   (v_perm_b32: bytes [y3 y2 x3 x2])
+  w0 = __builtin_amdgcn_perm(yb, xb, 0x07060302u);
+  w1 = __builtin_amdgcn_perm(y1b, x1b, 0x07060302u);
+  w2 = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, y2), __builtin_bit_cast(unsigned, x2), 0x07060302u);
 }
 
 inline int grid_for(int64_t items, int cap = 256 * 8) {

@@ -6,22 +6,14 @@
 // has a bit-checkable counterpart with the reference's own tensor boundaries.
 //
 // Reference lines each kernel follows are cited at the kernel.
-#include "common.h"
+#include "kernel_device.h"
 
 namespace impnn {
 
 namespace {
 
-constexpr int kBlock = 256;
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4_t ldv4(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
-__device__ __forceinline__ f32x4_t mfma_f32(float a, float b, f32x4_t c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float fsig(float x) {
-  return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * x));
-}
+// (its own: the wide encoder's ftanh spells the fused multiply-add out, here contraction is the compiler's - the two
+//  do not compile to the same instructions)
 __device__ __forceinline__ float ftanh(float x) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177793f * x));
 }
@@ -732,16 +724,8 @@ __global__ __launch_bounds__(256) void gated_update_d32_kernel(
 // (3 x 2D x D floats: 393 KB at D = 128) stream through LDS in slices of 16 input rows.  Orientation
 // out (rows x features) = c (rows x 2D) W (2D x D): rows on the MFMA M dimension, features on N, so the keras
 // kernels are read as stored.  K index ordered 16u + 4q + r: one 16-byte LDS read of c feeds four steps.
-// Row reductions of LayerNorm: 16-lane DPP rows (features) x the feature tiles in registers.
+// Row reductions of LayerNorm: 16-lane DPP rows (features; row16_sum_f) x the feature tiles in registers.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float row16_sum_f(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, true));
-  return v;
-}
-
 template <int NT, class... Drop>  // NT = D / 16 feature tiles; Drop: as gated_update_kernel
 __global__ __launch_bounds__(256) void gated_update_wide_kernel(
     const float* __restrict__ h, const float* __restrict__ agg, const float* __restrict__ Wz,
@@ -1235,13 +1219,6 @@ __global__ void validate_indices_kernel(const int32_t* conn, const int32_t* atom
   if (c0) atomicAdd(&counts[0], c0);
   if (c1) atomicAdd(&counts[1], c1);
   if (c2) atomicAdd(&counts[2], c2);
-}
-
-inline int grid_for(int64_t items, int block = kBlock, int cap = 256 * 8) {
-  int64_t g = (items + block - 1) / block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
 }
 
 constexpr size_t kMaxLds = 160 * 1024;

@@ -553,14 +553,7 @@ __global__ __launch_bounds__(BS) void gated_update_bwd_kernel(
 // stride 68) for the forward recompute, and as stored ((gate, in) rows of D outputs, stride 36) for the products
 // with the pre-activation gradients.  Outputs and partial sums are those of gated_update_bwd_kernel.
 // ---------------------------------------------------------------------------------------
-// sum over the 16 lanes of a DPP row (the rows of one feature quarter), result in every lane of the row
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, true));  // row_ror:1
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, true));  // row_ror:2
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, true));  // row_ror:4
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, true));  // row_ror:8
-  return v;
-}
+// (row16_sum_f sums over the 16 lanes of a DPP row: here the rows of one feature quarter)
 constexpr int kBwT = 68;  // stride of the transposed kernels (rows: gate*32 + out, cols: 2D inputs)
 constexpr int kBwN = 36;  // stride of the natural kernels (rows: gate*64 + in, cols: D outputs)
 
@@ -816,7 +809,7 @@ __global__ __launch_bounds__(kBlock, SAVED ? 2 : 1) void gated_update_bwd_d32_ke
     for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float v = row16_sum(sums[w5][blk][i]);
+        const float v = row16_sum_f(sums[w5][blk][i]);
         if (a == 0) red[(wave * 5 + w5) * D + 16 * blk + 4 * q + i] = v;
       }
   __syncthreads();
@@ -1069,7 +1062,7 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
       }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float v = row16_sum(sum[g]);
+      const float v = row16_sum_f(sum[g]);
       if (a == 0) part[fg * 64 + 16 * rt + 4 * q + g] = v;
     }
     __syncthreads();
@@ -1088,7 +1081,7 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
       }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float v = row16_sum(var[g]);
+      const float v = row16_sum_f(var[g]);
       if (a == 0) part[256 + fg * 64 + 16 * rt + 4 * q + g] = v;
     }
     __syncthreads();
@@ -1119,7 +1112,7 @@ __global__ __launch_bounds__(1024) void gated_update_bwd_wide16_kernel(
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float v1 = row16_sum(m1[g]), v2 = row16_sum(m2[g]);
+      const float v1 = row16_sum_f(m1[g]), v2 = row16_sum_f(m2[g]);
       if (a == 0) {
         part[512 + fg * 64 + 16 * rt + 4 * q + g] = v1;
         part[768 + fg * 64 + 16 * rt + 4 * q + g] = v2;

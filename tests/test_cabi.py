@@ -60,7 +60,7 @@ def test_encoder_shape_coverage_is_reported():
     for mode in (F32, F16X2, TYPED):
         assert lib.impnn_encoder_workspace_bytes(2, 4096, 40, 80, 32, 8, 3, 72, mode, 0, C.byref(need)) == 0
         assert 0 < need.value < (64 << 20)
-        # wide states (train_viscosity.py with atom_dim=128): the per-bond-type mode only (csrc/encoder_wide.hip)
+        # wide states (train_viscosity.py with atom_dim=128): the per-bond-type mode only (csrc/encoder_wide.hip, wide_*.hip)
         rc = lib.impnn_encoder_workspace_bytes(2, 4096, 40, 80, 128, 8, 6, 72, mode, 0, C.byref(need))
         assert rc == (0 if mode == TYPED else -2)
     assert (256 << 20) < need.value < (2 << 30)
@@ -92,7 +92,7 @@ def test_encoder_shape_coverage_is_reported():
 
 def test_wide_encoder_refuses_batches_beyond_its_32_bit_offsets():
     """The wide encoder's coverage of a BATCH (csrc/encoder_wide.hip, encoder_wide_batch_covered): its update kernels
-    address a row's aggregated messages as 32-bit float offsets from `agg` - rows up to rmax, the row of zeros, times D -
+    (csrc/wide_update.hip, wide_update_x3.hip) address a row's aggregated messages as 32-bit float offsets from `agg` - rows up to rmax, the row of zeros, times D -
     and sorted edge positions up to vmax are 32-bit indices.  With every row's sum in agg (the largest batches) nothing
     else bounds rmax * D, so impnn_encoder_workspace_bytes refuses such a batch before anything is allocated for it:
     one shape on each side of each bound."""

@@ -1,4 +1,5 @@
-"""Wide atom states (atom_dim 64 / 128) through the encoder entries: csrc/encoder_wide.hip against the oracle
+"""Wide atom states (atom_dim 64 / 128) through the encoder entries: csrc/encoder_wide.hip and its stage files
+csrc/wide_*.hip against the oracle
 (oracle/mpnn_oracle.py, the restatement of models/layers.py:57-164 and train_viscosity.py:166-190) and against the
 layer-at-a-time HIP kernels.  Tolerance 1e-5 relative (BASELINE.json north_star), conftest.assert_close."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Wide encoder fuzz (csrc/encoder_wide.hip): every update-kernel variant and both ways of feeding it aggregated
+"""Wide encoder fuzz (csrc/encoder_wide.hip, csrc/wide_*.hip): every update-kernel variant and both ways of feeding it aggregated
 messages, on the adversarial batches of tests/wide_cases.py, against oracle.mpnn_oracle.encode in fp64.
 
 In-process, the launcher's own choice: each case ASSERTS its premises from the device's CU count (which kernels the

@@ -1,8 +1,8 @@
-"""Deterministic adversarial batches for the wide encoder (csrc/encoder_wide.hip, atom_dim 64 / 128), shared by
-tests/test_gpu_wide_fuzz.py, tests/wide_child.py and tests/test_wide_cases_host.py.
+"""Deterministic adversarial batches for the wide encoder (csrc/encoder_wide.hip and csrc/wide_*.hip, atom_dim 64 /
+128), shared by tests/test_gpu_wide_fuzz.py, tests/wide_child.py and tests/test_wide_cases_host.py.
 
 A case is `build(name, D)`: shapes, inputs, weights (weights.init_weights(..., perturb=True)) and
-  * its premises as a function of the CU count - the launcher's documented rules (launch_encoder_wide), so that a test
+  * its premises as a function of the CU count - the launcher's rules (choose_launch, csrc/encoder_wide.hip), so that a test
     can ASSERT which kernels the case reaches instead of assuming it;
   * a numpy restatement of the plan kernels (wide_count / wide_scan): valid edges by the valid_type rule, kept rows per
     molecule, ion bases aligned to 128 rows, valid-edge counts per (ion, bond type), in-degrees; and from it the
@@ -205,7 +205,7 @@ class Case:
 
     # -- premises ---------------------------------------------------------------------------------------------
     def premises(self, cus, B=None, kept_end=None):
-        """What the launcher decides for this batch on a device of `cus` CUs (launch_encoder_wide)."""
+        """What the launcher decides for this batch on a device of `cus` CUs (choose_launch, csrc/encoder_wide.hip)."""
         mols = 2 * (self.B if B is None else B)
         rows = mols * self.N                                    # the bound it goes by: the kept rows live on the device
         t_live = -(-(self.plan["kept_end"] if kept_end is None else kept_end) // ROW_ALIGN)

@@ -1,6 +1,6 @@
 """A fresh process for the wide encoder's launch overrides (IMPNN_WIDE_NO_DIRECT, IMPNN_WIDE_TILE_ROWS,
-IMPNN_WIDE_X3_BIG: the library reads each once per process).  tests/test_gpu_wide_fuzz.py starts it with the
-overrides in its environment:
+IMPNN_WIDE_X3_BIG: the library reads each once per process, in choose_launch of csrc/encoder_wide.hip).
+tests/test_gpu_wide_fuzz.py starts it with the overrides in its environment:
 
     python wide_child.py OUT.npz CASE:D [CASE:D ...]
 
