@@ -51,6 +51,23 @@ __device__ __forceinline__ f32x4 tanh4(f32x4 x) {
   for (int i = 0; i < 4; ++i) r[i] = __builtin_amdgcn_rcpf(d[i]);
   return 1.0f - 2.0f * as_tuple(r);
 }
+// s + s[lane ^ 16] + (that sum)[lane ^ 32] in every lane, on the vector ALU: the bits of
+//   s += __shfl_xor(s, 16); s += __shfl_xor(s, 32);
+// (IEEE addition is commutative) without the two LDS round trips of ds_bpermute_b32.  With x = y = s,
+// v_permlane16_swap x, y (odd rows of 16 lanes of x <-> even rows of y) leaves x = rows (s0, s0, s2, s2) and
+// y = rows (s1, s1, s3, s3); v_permlane32_swap (lanes 32-63 of x <-> lanes 0-31 of y) does the same with the wave's
+// halves.  The swaps move only lanes that EXEC enables, so this is for wave-uniform code (EXEC all ones).
+// (Inline asm with two named registers: the operands must be two copies of s, which the builtin does not promise.
+//  The s_nop covers the VALU-write -> permlane-read wait states the assembler does not insert.)
+__device__ __forceinline__ float sum_xor16_xor32(float s) {
+  float x = s, y = s;
+  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+  s = x + y;
+  x = s;
+  y = s;
+  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
+  return x + y;
+}
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 

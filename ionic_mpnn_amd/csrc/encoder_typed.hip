@@ -699,6 +699,10 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
           if (kRunsEarly >= 1) fetch_P(s + 1);
           if (kRunsEarly >= 2) fetch_Q(s + 1);
         }
+        // (Measured and dropped, DESIGN.md 4.1 "Atom phase": these reads of h and of the z / r biases in front of the Reduce
+        //  loop - GEMMs + gates -0.5 K cycles for the stamped wave, the epilogue +0.4 K, the kernel +1 %; and the agg half
+        //  of z behind r's last MFMA, to run under the gate of r - it spills unless the candidate's biases are read late,
+        //  and that makes the compiler split everything first and issue the MFMAs back to back: +1.5 %.)
         const f32x4 h0 = ld4(hbuf + row * HS + 4 * q);
         const f32x4 h1 = ld4(hbuf + row * HS + 16 + 4 * q);
 
@@ -769,23 +773,25 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
           fetch_pf(s + 1);
         }
         if (mstamp && wave == 1 && lane == 0) stamp[9] = __builtin_amdgcn_s_memtime();
+        // LayerNorm's gamma and beta are requested here, in front of the tanh: the GEMM operands are dead, so the
+        // registers are free, and the round trip passes under the blend and the two cross-lane sums instead of behind the
+        // v_rsq.  (sched_barrier: the scheduler otherwise sinks the four reads back down to their first use.)
+        const f32x4 gm0 = ld4(wvec + 3 * kD + 4 * q), gm1 = ld4(wvec + 3 * kD + 16 + 4 * q);
+        const f32x4 bt0 = ld4(wvec + 4 * kD + 4 * q), bt1 = ld4(wvec + 4 * kD + 16 + 4 * q);
+        __builtin_amdgcn_sched_barrier(0);
         // ---- blend, LayerNorm, residual  (models/layers.py:153-155); (1-z) h + z t == h + z (t - h)
         f32x4 n0 = z0 * (tanh4<false>(t0) - h0) + h0;
         f32x4 n1 = z1 * (tanh4<false>(t1) - h1) + h1;
         const f32x4 s4 = n0 + n1;
-        float sum = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
+        // (the four feature quads of an atom sit in lanes l, l ^ 16, l ^ 32, l ^ 48; has_tile is wave-uniform, so EXEC
+        //  is all ones here, which the lane swaps of sum_xor16_xor32 need)
+        const float sum = sum_xor16_xor32((s4[0] + s4[1]) + (s4[2] + s4[3]));
         const float mean = sum * (1.0f / kD);
         n0 -= mean;
         n1 -= mean;
         const f32x4 q4 = n0 * n0 + n1 * n1;
-        float var = (q4[0] + q4[1]) + (q4[2] + q4[3]);
-        var += __shfl_xor(var, 16);
-        var += __shfl_xor(var, 32);
+        const float var = sum_xor16_xor32((q4[0] + q4[1]) + (q4[2] + q4[3]));
         const float inv = __builtin_amdgcn_rsqf(var * (1.0f / kD) + p.ln_eps);
-        const f32x4 gm0 = ld4(wvec + 3 * kD + 4 * q), gm1 = ld4(wvec + 3 * kD + 16 + 4 * q);
-        const f32x4 bt0 = ld4(wvec + 4 * kD + 4 * q), bt1 = ld4(wvec + 4 * kD + 16 + 4 * q);
         const f32x4 o0 = n0 * (gm0 * inv) + (bt0 + h0);
         const f32x4 o1 = n1 * (gm1 * inv) + (bt1 + h1);
         st4(hbuf + row * HS + 4 * q, o0);
