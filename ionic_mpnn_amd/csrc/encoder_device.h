@@ -39,6 +39,37 @@ __device__ __forceinline__ f32x4 sigmoid4(f32x4 x) {
   for (int i = 0; i < 4; ++i) r[i] = __builtin_amdgcn_rcpf(d[i]);
   return as_tuple(r);
 }
+// The same values - the same IEEE operations per element - in single-lane instructions, for mode "f32x3" of the typed
+// encoder: beside MFMAs of the bf16 pipe a packed f32 instruction costs a SIMD more issue time than its two scalar
+// forms (measured there: -2 % kernel time for the gates, another -2 % for the epilogue; beside the exact-f32 MFMA,
+// which takes the vector ALU's own issue slots, the packed forms are the faster ones).  A value that went through
+// lane1 lives in a register of its own (no instruction is emitted), so the compiler does not pair neighbouring
+// elements up again.
+__device__ __forceinline__ float lane1(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+__device__ __forceinline__ f32x4 sigmoid4_lanes(f32x4 x) {
+  f32x4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    r[i] = __builtin_amdgcn_rcpf(lane1(lane1(__builtin_amdgcn_exp2f(lane1(x[i] * -1.44269504088896f))) + 1.0f));
+  return r;
+}
+__device__ __forceinline__ f32x4 mul4_lanes(f32x4 a, f32x4 b) {
+  f32x4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = lane1(a[i] * b[i]);
+  return r;
+}
+__device__ __forceinline__ f32x4 tanh4_lanes(f32x4 x) {
+  f32x4 r;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    r[i] = lane1(1.0f -
+                 2.0f * __builtin_amdgcn_rcpf(lane1(lane1(__builtin_amdgcn_exp2f(lane1(x[i] * 2.88539008177793f))) + 1.0f)));
+  return r;
+}
 template <bool SCALED>
 __device__ __forceinline__ f32x4 tanh4(f32x4 x) {
   const f32x4 a = x * splat_sgpr(SCALED ? 2.88539008177793f / kAcc : 2.88539008177793f);

@@ -223,6 +223,54 @@ __global__ __launch_bounds__(256) void typed_m0_kernel(const float* tmat0, const
 #define IMPNN_T_EARLY 0
 #endif
 constexpr int kPfWhere = IMPNN_T_PF, kRunsEarly = IMPNN_T_EARLY;
+// Reduce (models/layers.py:57-83), the in-edge ranks d0 .. d0 + N - 1 of a tile's rows in one LDS round trip: agg += the
+// rows' messages of these ranks, in rank order; a rank a row does not have reads the slot of zeros (x + 0 = x: no branch,
+// all 2 N loads of the round in flight together).  jdptr: the record's u16[260] incl. padding, d0 a multiple of 4 (one
+// aligned 8-byte read, d0 + 3 <= 258).  LANES: the adds as single-lane instructions (mode 3 runs them beside the MFMAs
+// of the gates' h halves, where a v_pk_add_f32 costs more issue time than two v_add_f32; the same IEEE sums either way).
+template <int N, bool LANES>
+__device__ __forceinline__ void reduce_ranks(const float* msg, const uint16_t* jdptr, int d0, int deg, int row, int q,
+                                             int zero_slot, f32x4& agg0, f32x4& agg1) {
+  const uint2 jd = *reinterpret_cast<const uint2*>(jdptr + d0);
+  const int first[4] = {(int)(jd.x & 0xffffu), (int)(jd.x >> 16), (int)(jd.y & 0xffffu), (int)(jd.y >> 16)};
+  f32x4 m0v[N], m1v[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const int o = tmsg_off(d0 + j < deg ? first[j] + row : zero_slot, q);
+    m0v[j] = ld4(msg + o);
+    m1v[j] = ld4(msg + (o ^ 16));  // unit 4 + q of the same slot
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    if constexpr (LANES) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        agg0[i] = lane1(agg0[i] + m0v[j][i]);
+        agg1[i] = lane1(agg1[i] + m1v[j][i]);
+      }
+    } else {
+      agg0 += m0v[j];
+      agg1 += m1v[j];
+    }
+  }
+}
+
+// One statement of quad arithmetic for both instruction forms: quad<false>(f, a...) is f on whole quads (packed f32
+// instructions), quad<true> applies f element by element, and keep1 - lane1 for a single element, nothing for a quad -
+// marks the results that stay in registers of their own, so that the elements are not paired up again.
+__device__ __forceinline__ float keep1(float v) { return lane1(v); }
+__device__ __forceinline__ f32x4 keep1(f32x4 v) { return v; }
+template <bool LANES, class F, class... A>
+__device__ __forceinline__ f32x4 quad(F f, A... a) {
+  if constexpr (LANES) {
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = f(a[i]...);
+    return r;
+  } else {
+    return f(a...);
+  }
+}
 
 template <bool STAMPS, bool X3, int HS = kTHS>
 __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel(TEncParams p) {
@@ -663,31 +711,36 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       if (has_tile) {
         const int tile = my_tile;
         const int row = tile * 16 + a;
-        // ---- Reduce (models/layers.py:57-83): in-edge messages summed in edge-slot order, four in-edge ranks per
-        // round trip: the ranks a row does not have read the slot of zeros (x + 0 = x: no branch, every load of a
-        // round is in flight together).
         const int deg = r_rowdeg[row];
         const int maxdeg = __builtin_amdgcn_readfirstlane(r_tilemax[tile]);
+        // ---- gates z, r (models/layers.py:144-147) and candidate (:150-151): out^T = W^T [h | agg]^T.  z and r accumulate
+        // bias, then W_h h, then W_agg agg; the first half needs no message.  Mode 3 issues it HERE, in front of Reduce: the
+        // bf16 pipe co-executes with the vector ALU and the LDS, so Reduce's round trips pass under these 36 MFMAs - and with
+        // the h halves out of the way the gates' single-lane arithmetic below fits the registers (without this order it
+        // spills 8 bytes).  The order of every sum is unchanged.  (The exact-f32 MFMA shares the issue port with the
+        // vector ALU: nothing passes under it, and reads of h in front of Reduce alone cost time - DESIGN.md 4.1.)
+        f32x4 h0, h1, z0, z1, r0, r1;
+        // (mode 3's A operands: block ((gate*2 + T)*2 + half) of the image, 3 x 512 bf16)
+        [[maybe_unused]] const __bf16* const wb = reinterpret_cast<const __bf16*>(wupd);
+        if constexpr (X3) {
+          h0 = ld4(hbuf + row * HS + 4 * q);
+          h1 = ld4(hbuf + row * HS + 16 + 4 * q);
+          z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
+          r0 = ld4(wvec + 1 * kD + 4 * q), r1 = ld4(wvec + 1 * kD + 16 + 4 * q);
+          const B3 sh = split8x3(h0, h1);
+          mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 0) * 1536, wb + ((0 * 2 + 1) * 2 + 0) * 1536, lane, sh);
+          mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 0) * 1536, wb + ((1 * 2 + 1) * 2 + 0) * 1536, lane, sh);
+        }
+        // ---- Reduce: in-edge messages summed in edge-slot order, in the form the tile's largest in-degree (wave-uniform)
+        // asks for: one rank per round trip, two, or a loop of four per round.  agg starts at +0 in every form, and what
+        // the short forms leave out are adds of the slot of zeros (x + 0 = x for every x that a sum 0 + m can be, a first
+        // message of -0 included): the same bits as the loop's.
         f32x4 agg0 = {0.f, 0.f, 0.f, 0.f}, agg1 = agg0;
-        for (int d0 = 0; d0 < maxdeg; d0 += 4) {
-          const uint2 jd = *reinterpret_cast<const uint2*>(r_jdptr + d0);  // d0 + 3 <= 258 (u16[260] incl. padding)
-          int sl[4];
-          sl[0] = d0 + 0 < deg ? (int)(jd.x & 0xffffu) + row : zero_slot;
-          sl[1] = d0 + 1 < deg ? (int)(jd.x >> 16) + row : zero_slot;
-          sl[2] = d0 + 2 < deg ? (int)(jd.y & 0xffffu) + row : zero_slot;
-          sl[3] = d0 + 3 < deg ? (int)(jd.y >> 16) + row : zero_slot;
-          f32x4 m0v[4], m1v[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int o = tmsg_off(sl[j], q);
-            m0v[j] = ld4(msg + o);
-            m1v[j] = ld4(msg + (o ^ 16));  // unit 4 + q of the same slot
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            agg0 += m0v[j];
-            agg1 += m1v[j];
-          }
+        if (maxdeg <= 2) {
+          if (maxdeg == 1) reduce_ranks<1, X3>(msg, r_jdptr, 0, deg, row, q, zero_slot, agg0, agg1);
+          if (maxdeg == 2) reduce_ranks<2, X3>(msg, r_jdptr, 0, deg, row, q, zero_slot, agg0, agg1);
+        } else {
+          for (int d0 = 0; d0 < maxdeg; d0 += 4) reduce_ranks<4, X3>(msg, r_jdptr, d0, deg, row, q, zero_slot, agg0, agg1);
         }
         if (mstamp && wave == 1 && lane == 0) stamp[8] = __builtin_amdgcn_s_memtime();
         // (Mode 3, measured and dropped: a static priority for two of a SIMD's four waves, so that they run ahead and the
@@ -699,29 +752,24 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
           if (kRunsEarly >= 1) fetch_P(s + 1);
           if (kRunsEarly >= 2) fetch_Q(s + 1);
         }
-        // (Measured and dropped, DESIGN.md 4.1 "Atom phase": these reads of h and of the z / r biases in front of the Reduce
-        //  loop - GEMMs + gates -0.5 K cycles for the stamped wave, the epilogue +0.4 K, the kernel +1 %; and the agg half
-        //  of z behind r's last MFMA, to run under the gate of r - it spills unless the candidate's biases are read late,
-        //  and that makes the compiler split everything first and issue the MFMAs back to back: +1.5 %.)
-        const f32x4 h0 = ld4(hbuf + row * HS + 4 * q);
-        const f32x4 h1 = ld4(hbuf + row * HS + 16 + 4 * q);
-
-        // ---- gates z, r (models/layers.py:144-147) and candidate (:150-151): out^T = W^T [h | agg]^T
-        f32x4 z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
-        f32x4 r0 = ld4(wvec + 1 * kD + 4 * q), r1 = ld4(wvec + 1 * kD + 16 + 4 * q);
+        if constexpr (!X3) {
+          h0 = ld4(hbuf + row * HS + 4 * q);
+          h1 = ld4(hbuf + row * HS + 16 + 4 * q);
+          z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
+          r0 = ld4(wvec + 1 * kD + 4 * q), r1 = ld4(wvec + 1 * kD + 16 + 4 * q);
+        }
         f32x4 t0 = ld4(wvec + 2 * kD + 4 * q), t1 = ld4(wvec + 2 * kD + 16 + 4 * q);
         if constexpr (X3) {
-          const __bf16* wb = reinterpret_cast<const __bf16*>(wupd);  // block ((gate*2 + T)*2 + half): 3 x 512 bf16
-          const B3 sh = split8x3(h0, h1);
+          // (Measured and dropped, DESIGN.md 4.1: the candidate's agg half in front of sigmoid(r), to run under the gate -
+          //  no spill in this order, but +0.7 us per launch, and the sums of t change their order.)
           const B3 sa = split8x3(agg0, agg1);
-          mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 0) * 1536, wb + ((0 * 2 + 1) * 2 + 0) * 1536, lane, sh);
-          mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 0) * 1536, wb + ((1 * 2 + 1) * 2 + 0) * 1536, lane, sh);
           mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 1) * 1536, wb + ((0 * 2 + 1) * 2 + 1) * 1536, lane, sa);
           mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 1) * 1536, wb + ((1 * 2 + 1) * 2 + 1) * 1536, lane, sa);
-          z0 = sigmoid4<false>(z0);
-          z1 = sigmoid4<false>(z1);
-          const f32x4 rh0 = sigmoid4<false>(r0) * h0;  // :149
-          const f32x4 rh1 = sigmoid4<false>(r1) * h1;
+          // the gates in single-lane instructions (encoder_device.h): the scheduler interleaves them with the MFMAs
+          z0 = sigmoid4_lanes(z0);
+          z1 = sigmoid4_lanes(z1);
+          const f32x4 rh0 = mul4_lanes(sigmoid4_lanes(r0), h0);  // :149
+          const f32x4 rh1 = mul4_lanes(sigmoid4_lanes(r1), h1);
           const B3 srh = split8x3(rh0, rh1);
           mma9x2(t0, t1, wb + ((2 * 2 + 0) * 2 + 0) * 1536, wb + ((2 * 2 + 1) * 2 + 0) * 1536, lane, srh);
           mma9x2(t0, t1, wb + ((2 * 2 + 0) * 2 + 1) * 1536, wb + ((2 * 2 + 1) * 2 + 1) * 1536, lane, sa);
@@ -747,6 +795,8 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
               }
             }
           }
+          // (packed here: the f32 MFMA takes the vector ALU's issue slots, so what counts is the number of instructions -
+          //  the single-lane forms were measured in this loop too: +1.8 us per launch)
           z0 = sigmoid4<false>(z0);
           z1 = sigmoid4<false>(z1);
           const f32x4 rh0 = sigmoid4<false>(r0) * h0;  // :149
@@ -779,21 +829,26 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
         const f32x4 gm0 = ld4(wvec + 3 * kD + 4 * q), gm1 = ld4(wvec + 3 * kD + 16 + 4 * q);
         const f32x4 bt0 = ld4(wvec + 4 * kD + 4 * q), bt1 = ld4(wvec + 4 * kD + 16 + 4 * q);
         __builtin_amdgcn_sched_barrier(0);
-        // ---- blend, LayerNorm, residual  (models/layers.py:153-155); (1-z) h + z t == h + z (t - h)
-        f32x4 n0 = z0 * (tanh4<false>(t0) - h0) + h0;
-        f32x4 n1 = z1 * (tanh4<false>(t1) - h1) + h1;
-        const f32x4 s4 = n0 + n1;
-        // (the four feature quads of an atom sit in lanes l, l ^ 16, l ^ 32, l ^ 48; has_tile is wave-uniform, so EXEC
-        //  is all ones here, which the lane swaps of sum_xor16_xor32 need)
+        // ---- blend, LayerNorm, residual  (models/layers.py:153-155); (1-z) h + z t == h + z (t - h).
+        // (The four feature quads of an atom sit in lanes l, l ^ 16, l ^ 32, l ^ 48; has_tile is wave-uniform, so EXEC is
+        //  all ones here, which the lane swaps of sum_xor16_xor32 need.)
+        // Stated once, for a quad in packed instructions or - mode 3 - element by element in single-lane instructions
+        // (quad, keep1 above): a wave's epilogue runs beside the other three waves' bf16 MFMAs, and there the packed forms
+        // cost the SIMD more issue time than they save; beside the exact-f32 MFMA they are the faster ones.
+        const f32x4 th0 = X3 ? tanh4_lanes(t0) : tanh4<false>(t0), th1 = X3 ? tanh4_lanes(t1) : tanh4<false>(t1);
+        const auto blend = [](auto z, auto th, auto h) { return keep1(z * (th - h) + h); };
+        f32x4 n0 = quad<X3>(blend, z0, th0, h0), n1 = quad<X3>(blend, z1, th1, h1);
+        const f32x4 s4 = quad<X3>([](auto x, auto y) { return keep1(x + y); }, n0, n1);
         const float sum = sum_xor16_xor32((s4[0] + s4[1]) + (s4[2] + s4[3]));
         const float mean = sum * (1.0f / kD);
-        n0 -= mean;
-        n1 -= mean;
-        const f32x4 q4 = n0 * n0 + n1 * n1;
+        const auto center = [mean](auto n) { return keep1(n - mean); };
+        n0 = quad<X3>(center, n0);
+        n1 = quad<X3>(center, n1);
+        const f32x4 q4 = quad<X3>([](auto x, auto y) { return keep1(x * x + y * y); }, n0, n1);
         const float var = sum_xor16_xor32((q4[0] + q4[1]) + (q4[2] + q4[3]));
         const float inv = __builtin_amdgcn_rsqf(var * (1.0f / kD) + p.ln_eps);
-        const f32x4 o0 = n0 * (gm0 * inv) + (bt0 + h0);
-        const f32x4 o1 = n1 * (gm1 * inv) + (bt1 + h1);
+        const auto affine = [inv](auto n, auto gm, auto bt, auto h) { return keep1(n * keep1(gm * inv) + keep1(bt + h)); };
+        const f32x4 o0 = quad<X3>(affine, n0, gm0, bt0, h0), o1 = quad<X3>(affine, n1, gm1, bt1, h1);
         st4(hbuf + row * HS + 4 * q, o0);
         st4(hbuf + row * HS + 16 + 4 * q, o1);
         if (mstamp && wave == 1 && lane == 0) stamp[10] = __builtin_amdgcn_s_memtime();
