@@ -415,6 +415,27 @@ int impnn_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float
                               float* const* dweights, int32_t B, int32_t D, int32_t F, int32_t Mx,
                               impnn_stream_t stream);
 
+/* ---- the same with per-sample weights (keras model.fit(sample_weight=...), reduction sum_over_batch_size):
+ *        loss = (1/B) * sum_b w_b * (pred_b - y_b)^2 + sum_t l2[t] * sum(W_t^2)
+ *      B counts EVERY sample of the batch, those of weight 0 included - it is not sum_b w_b; the penalties are not
+ *      weighted.  `sample_weight`: B device floats directly after `y`, 4-byte aligned, expected finite and >= 0 (the
+ *      library does not read the values on the host; the Python layer checks them).  sample_weight == NULL is valid
+ *      and IS the unweighted entry: impnn_model_head_loss[_bwd] are these entries with a null weight, and a null
+ *      weight runs the kernels without any weight instruction, so the unweighted bits do not depend on this family.
+ *      The backward's gradient seed per sample is w_b * 2 (pred_b - y_b) / B * dloss.  Same workspace
+ *      (impnn_model_head_loss_workspace_floats), same launches, same fixed summation order, same status codes in the
+ *      same order as the unweighted entries (a misaligned sample_weight: IMPNN_E_BADARG after the null pointers). */
+int impnn_weighted_model_head_loss(int32_t kind, const float* pooled_cat, const float* pooled_an,
+                                   const float* temperature, const float* const* weights, const float* l2,
+                                   const float* y, const float* sample_weight, float* pred, float* loss,
+                                   float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F,
+                                   int32_t Mx, impnn_stream_t stream);
+int impnn_weighted_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float* pooled_an,
+                                       const float* temperature, const float* const* weights, const float* l2,
+                                       const float* y, const float* sample_weight, const float* dloss,
+                                       float* dpooled_cat, float* dpooled_an, float* const* dweights, int32_t B,
+                                       int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+
 /* ---- a9 in two halves, for callers that pipeline batches.  impnn_encoder_plan runs only the
  *      graph-dependent plan kernels (row counts, shares, chunk records) of a batch into `workspace`;
  *      impnn_encoder_run runs only the encoder kernel from a planned workspace.  The plan needs no
@@ -508,6 +529,32 @@ int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an
                                  const int64_t* step, int32_t layer_word, const float* saved, int64_t saved_floats,
                                  float* workspace, int64_t workspace_floats, float* dpooled_cat, float* dpooled_an,
                                  int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+
+/* ---- the transfer head's loss with per-sample weights (keras sample_weight, reduction sum_over_batch_size):
+ *        loss = (1/B) * sum_b w_b * L(pred_b - y_b) + sum_t l2[t] * sum(W_t^2),  L as above (squared error or Huber)
+ *      B counts EVERY sample of the batch, those of weight 0 included - it is not sum_b w_b.  The weights touch the loss
+ *      only: BatchNormalization's batch and moving statistics, the Dropout mask and the penalties are those of the
+ *      unweighted pass.  `sample_weight`: B device floats directly after `y`, 4-byte aligned, expected finite and >= 0
+ *      (values are not read on the host).  sample_weight == NULL is valid and IS the unweighted entry:
+ *      impnn_transfer_head_loss[_bwd] are these entries with a null weight, and a null weight runs kernels without any
+ *      weight instruction.  The backward's gradient seed per sample is w_b * L'(pred_b - y_b) / B * dloss.  Workspaces,
+ *      launches, summation order and status codes as the unweighted entries (a misaligned sample_weight:
+ *      IMPNN_E_BADARG after the null pointers). */
+int impnn_weighted_transfer_head_loss(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                                      const float* l2, float* moving_mean, float* moving_var, float bn_momentum,
+                                      float bn_eps, int32_t bn_batch, const float* y, const float* sample_weight,
+                                      int32_t loss_kind, float delta, float rate, uint64_t seed, const int64_t* step,
+                                      int32_t layer_word, float* saved, int64_t saved_floats, float* pred, float* loss,
+                                      float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F,
+                                      int32_t Mx, impnn_stream_t stream);
+int impnn_weighted_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                                          float* const* dweights, const float* l2, int32_t bn_batch, const float* y,
+                                          const float* sample_weight, int32_t loss_kind, float delta,
+                                          const float* dloss, float rate, uint64_t seed, const int64_t* step,
+                                          int32_t layer_word, const float* saved, int64_t saved_floats,
+                                          float* workspace, int64_t workspace_floats, float* dpooled_cat,
+                                          float* dpooled_an, int32_t B, int32_t D, int32_t F, int32_t Mx,
+                                          impnn_stream_t stream);
 
 /* ---- the transfer head over a Cartesian product: C cations x A anions from C + A encoder rows, on the matrix cores.
  *      mix = relu(proj_cat) + relu(proj_an) is a sum and mp_dense_1 is linear in it before its relu, so

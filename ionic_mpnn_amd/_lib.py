@@ -70,6 +70,10 @@ SIGNATURES = {
     "impnn_model_head_loss": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "impnn_model_head_loss_bwd": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, PP, i32, i32, i32, i32,
                                             vp]),
+    "impnn_weighted_model_head_loss": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, vp, i64, i32, i32,
+                                                 i32, i32, vp]),
+    "impnn_weighted_model_head_loss_bwd": (C.c_int, [i32, vp, vp, vp, PP, C.POINTER(f32), vp, vp, vp, vp, vp, PP, i32,
+                                                     i32, i32, i32, vp]),
     "impnn_transfer_head_saved_floats": (i64, [i32, i32, i32]),
     "impnn_transfer_head_bwd_workspace_floats": (i64, [i32, i32, i32]),
     "impnn_transfer_head_loss_workspace_floats": (i64, [i32]),
@@ -78,6 +82,10 @@ SIGNATURES = {
                                  + [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "impnn_transfer_head_loss_bwd": (C.c_int, [vp, vp, PP, PP, C.POINTER(f32), i32, vp, i32, f32, vp] + _DROP
                                      + [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),
+    "impnn_weighted_transfer_head_loss": (C.c_int, [vp, vp, PP, C.POINTER(f32), vp, vp, f32, f32, i32, vp, vp, i32, f32]
+                                          + _DROP + [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
+    "impnn_weighted_transfer_head_loss_bwd": (C.c_int, [vp, vp, PP, PP, C.POINTER(f32), i32, vp, vp, i32, f32, vp]
+                                              + _DROP + [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),
     "impnn_transfer_grid_image_floats": (i64, []),
     "impnn_transfer_grid_prepare": (C.c_int, [PP, vp, vp, f32, vp, i64, vp]),
     "impnn_transfer_ion_half": (C.c_int, [i32, vp, PP, vp, i32, i32, i32, i32, vp]),

@@ -423,10 +423,32 @@ class ModelHead(torch.autograd.Function):
         return (None, None, None, dpc, dpa, None) + tuple(None if s is not None else g for s, g in zip(sinks, grads))
 
 
+class WeightedL2(tuple):
+    """ModelHeadLoss's ``l2`` argument with the batch's per-sample weights attached: the lambdas as a tuple, the
+    weights (a (B) float32 device tensor) as ``.sample_weight``.  A plain sequence of lambdas is the unweighted loss."""
+
+    def __new__(cls, l2, sample_weight):
+        self = super().__new__(cls, l2)
+        self.sample_weight = sample_weight
+        return self
+
+
+def _sample_weight(w, B, device):
+    """The weight tensor a loss node hands to the library: contiguous float32 (B) on the node's device, or None."""
+    if w is None:
+        return None
+    w = f32c(w.detach()).reshape(-1)
+    if w.numel() != B or w.device != device:
+        raise ValueError("sample_weight must hold one value per sample, on the batch's device")
+    return w
+
+
 class ModelHeadLoss(torch.autograd.Function):
     """Head + keras "mse" + l2 penalties as one node -> the scalar loss (impnn_model_head_loss[_bwd]).  ``l2``: one
     lambda per weight tensor; ``workspace``: a persistent float tensor whose first word is zero (the kernel's arrival
-    counter; see include/impnn.h)."""
+    counter; see include/impnn.h).  Per-sample weights ride in ``l2``: pass ``WeightedL2(l2, sample_weight)`` and the
+    node calls impnn_weighted_model_head_loss[_bwd]: loss = (1/B) sum_b w_b (pred_b - y_b)^2 + penalties.  The weight
+    is kept for the backward and gets no gradient."""
 
     @staticmethod
     def forward(ctx, kind, fp_size, mixing_size, l2, workspace, pooled_cat, pooled_an, temperature, y, *weights):
@@ -436,17 +458,24 @@ class ModelHeadLoss(torch.autograd.Function):
         T = f32c(temperature).reshape(-1) if kind == 0 else None
         if y.numel() != B or (T is not None and T.numel() != B):
             raise ValueError("y / temperature must hold one value per sample")
+        sw = _sample_weight(getattr(l2, "sample_weight", None), B, pooled_cat.device)
         lib = _lib.load()
         if workspace.numel() < lib.impnn_model_head_loss_workspace_floats(B):
             raise ValueError("loss workspace too small")
         loss = torch.empty((), dtype=torch.float32, device=pooled_cat.device)
         lam = (C.c_float * len(weights))(*[float(v) for v in l2])
         table = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
-        _lib_call(pooled_cat.device, lib.impnn_model_head_loss, kind, ptr(pooled_cat), ptr(pooled_an),
-                  ptr(T) if T is not None else None, table, lam, ptr(y), None, ptr(loss), ptr(workspace),
-                  workspace.numel(), B, D, fp_size, mixing_size)
+        if sw is None:
+            _lib_call(pooled_cat.device, lib.impnn_model_head_loss, kind, ptr(pooled_cat), ptr(pooled_an),
+                      ptr(T) if T is not None else None, table, lam, ptr(y), None, ptr(loss), ptr(workspace),
+                      workspace.numel(), B, D, fp_size, mixing_size)
+        else:
+            _lib_call(pooled_cat.device, lib.impnn_weighted_model_head_loss, kind, ptr(pooled_cat), ptr(pooled_an),
+                      ptr(T) if T is not None else None, table, lam, ptr(y), ptr(sw), None, ptr(loss), ptr(workspace),
+                      workspace.numel(), B, D, fp_size, mixing_size)
         ctx.save_for_backward(pooled_cat, pooled_an, y, *(() if T is None else (T,)), *weights)
         ctx.meta = (kind, fp_size, mixing_size, tuple(float(v) for v in l2), weights)
+        ctx.sample_weight = sw  # no gradient flows to it: kept beside the saved tensors
         return loss
 
     @staticmethod
@@ -464,8 +493,15 @@ class ModelHeadLoss(torch.autograd.Function):
         lam = (C.c_float * len(weights))(*l2)
         wt = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
         gt = (C.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
-        _lib_call(dloss.device, _lib.load().impnn_model_head_loss_bwd, kind, ptr(pooled_cat), ptr(pooled_an),
-                  ptr(T) if T is not None else None, wt, lam, ptr(y), ptr(dloss), ptr(dpc), ptr(dpa), gt, B, D, F, Mx)
+        sw = ctx.sample_weight
+        if sw is None:
+            _lib_call(dloss.device, _lib.load().impnn_model_head_loss_bwd, kind, ptr(pooled_cat), ptr(pooled_an),
+                      ptr(T) if T is not None else None, wt, lam, ptr(y), ptr(dloss), ptr(dpc), ptr(dpa), gt, B, D, F,
+                      Mx)
+        else:
+            _lib_call(dloss.device, _lib.load().impnn_weighted_model_head_loss_bwd, kind, ptr(pooled_cat),
+                      ptr(pooled_an), ptr(T) if T is not None else None, wt, lam, ptr(y), ptr(sw), ptr(dloss), ptr(dpc),
+                      ptr(dpa), gt, B, D, F, Mx)
         return (None, None, None, None, None, dpc, dpa, None, None) + tuple(
             None if s is not None else g for s, g in zip(sinks, grads))
 
@@ -474,8 +510,9 @@ class ModelHeadLoss(torch.autograd.Function):
 class TransferHeadLoss(torch.autograd.Function):
     """The transfer model's head + Huber / squared error + l2 penalties as one node -> the scalar loss
     (impnn_transfer_head_loss[_bwd]).  ``cfg``: MPNNModel._transfer_cfg (widths, l2, the moving statistics, which
-    the forward moves in place when cfg["bn_batch"], the pass's ops.Dropout or None, the loss); ``workspace``: a
-    persistent float tensor whose first word is zero.  The backward adds the gradients of the tensors that ask for one
+    the forward moves in place when cfg["bn_batch"], the pass's ops.Dropout or None, the loss, and optionally
+    cfg["sample_weight"]: (B) per-sample weights, which select impnn_weighted_transfer_head_loss[_bwd] and get no
+    gradient); ``workspace``: a persistent float tensor whose first word is zero.  The backward adds the gradients of the tensors that ask for one
     into their sinks and leaves the frozen ones alone; it writes the pooled vectors' gradients only when they ask."""
 
     @staticmethod
@@ -485,6 +522,7 @@ class TransferHeadLoss(torch.autograd.Function):
         B, D = pooled_cat.shape
         if y.numel() != B:
             raise ValueError("y must hold one value per sample")
+        sw = _sample_weight(cfg.get("sample_weight"), B, pooled_cat.device)
         lib = _lib.load()
         F, Mx = cfg["fp_size"], cfg["mixing_size"]
         keep = any(ctx.needs_input_grad) or cfg["bn_batch"]
@@ -495,12 +533,15 @@ class TransferHeadLoss(torch.autograd.Function):
         table = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
         drop = cfg["dropout"]
         dargs = drop.args() if drop is not None and drop.rate > 0.0 else (0.0, C.c_uint64(0), None, 0)
-        _lib_call(pooled_cat.device, lib.impnn_transfer_head_loss, ptr(pooled_cat), ptr(pooled_an), table, lam,
+        entry = lib.impnn_transfer_head_loss if sw is None else lib.impnn_weighted_transfer_head_loss
+        _lib_call(pooled_cat.device, entry, ptr(pooled_cat), ptr(pooled_an), table, lam,
                   ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]), cfg["momentum"], cfg["epsilon"],
-                  1 if cfg["bn_batch"] else 0, ptr(y), cfg["loss_kind"], cfg["delta"], *dargs,
-                  ptr(saved) if keep else None, n_saved, None, ptr(loss), ptr(workspace), workspace.numel(), B, D, F, Mx)
+                  1 if cfg["bn_batch"] else 0, ptr(y), *(() if sw is None else (ptr(sw),)), cfg["loss_kind"],
+                  cfg["delta"], *dargs, ptr(saved) if keep else None, n_saved, None, ptr(loss), ptr(workspace),
+                  workspace.numel(), B, D, F, Mx)
         ctx.save_for_backward(pooled_cat, pooled_an, y, *weights)
         ctx.meta = (cfg, saved, dargs, weights)
+        ctx.sample_weight = sw  # no gradient flows to it: kept beside the saved tensors
         return loss
 
     @staticmethod
@@ -523,7 +564,10 @@ class TransferHeadLoss(torch.autograd.Function):
         lam = (C.c_float * len(weights))(*[float(v) for v in cfg["l2"]])
         wt = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
         gt = (C.c_void_p * len(weights))(*[g.data_ptr() if g is not None else None for g in grads])
-        _lib_call(dloss.device, lib.impnn_transfer_head_loss_bwd, ptr(pooled_cat), ptr(pooled_an), wt, gt, lam,
-                  1 if cfg["bn_batch"] else 0, ptr(y), cfg["loss_kind"], cfg["delta"], ptr(dloss), *dargs, ptr(saved),
-                  saved.numel(), ptr(ws), wsn, ptr(dpc) if pooled else None, ptr(dpa) if pooled else None, B, D, F, Mx)
+        sw = ctx.sample_weight
+        entry = lib.impnn_transfer_head_loss_bwd if sw is None else lib.impnn_weighted_transfer_head_loss_bwd
+        _lib_call(dloss.device, entry, ptr(pooled_cat), ptr(pooled_an), wt, gt, lam,
+                  1 if cfg["bn_batch"] else 0, ptr(y), *(() if sw is None else (ptr(sw),)), cfg["loss_kind"],
+                  cfg["delta"], ptr(dloss), *dargs, ptr(saved), saved.numel(), ptr(ws), wsn,
+                  ptr(dpc) if pooled else None, ptr(dpa) if pooled else None, B, D, F, Mx)
         return (None, None, dpc, dpa, None) + tuple(None if s is not None else g for s, g in zip(sinks, grads))

@@ -243,6 +243,8 @@ int model_head_checked(const ModelHeadCall& c, ModelHeadForm form) {
     return fail(IMPNN_E_BADARG, "%s: bad shape", c.entry);
   if (c.B == 0) return IMPNN_OK;
   if (!(c.pc && c.pa && form.tensors && (c.kind == 1 || c.T))) return fail(IMPNN_E_BADARG, "%s: null pointer", c.entry);
+  if (reinterpret_cast<uintptr_t>(c.sample_weight) % sizeof(float))
+    return fail(IMPNN_E_BADARG, "%s: sample_weight must be 4-byte aligned", c.entry);
   if (c.workspace && c.workspace_floats < impnn_model_head_loss_workspace_floats(c.B))
     return fail(IMPNN_E_WORKSPACE, "model_head_loss: workspace of %lld floats is too small", (long long)c.workspace_floats);
   return form.launch(c);
@@ -574,24 +576,62 @@ int64_t impnn_model_head_bwd_max_floats(void) { return model_head_bwd_max_floats
 
 int64_t impnn_model_head_loss_workspace_floats(int32_t B) { return B > 0 ? model_head_loss_workspace_floats(B) : 4; }
 
+// The loss entries are the weighted launcher with a null weight: one body each, named for the entry that was called.
+namespace {
+int model_head_loss_entry(const char* entry, int32_t kind, const float* pooled_cat, const float* pooled_an,
+                          const float* temperature, const float* const* weights, const float* l2, const float* y,
+                          const float* sample_weight, float* pred, float* loss, float* workspace,
+                          int64_t workspace_floats, int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  ModelHeadCall c = model_head(entry, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.weights = weights, c.l2 = l2, c.y = y, c.sample_weight = sample_weight, c.out = pred, c.loss = loss;
+  c.workspace = workspace, c.workspace_floats = workspace_floats;
+  return model_head_checked(c, {false, weights && l2 && y && loss && workspace, launch_model_head_tensors});
+}
+int model_head_loss_bwd_entry(const char* entry, int32_t kind, const float* pooled_cat, const float* pooled_an,
+                              const float* temperature, const float* const* weights, const float* l2, const float* y,
+                              const float* sample_weight, const float* dloss, float* dpooled_cat, float* dpooled_an,
+                              float* const* dweights, int32_t B, int32_t D, int32_t F, int32_t Mx,
+                              impnn_stream_t stream) {
+  ModelHeadCall c = model_head(entry, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
+  c.weights = weights, c.l2 = l2, c.y = y, c.sample_weight = sample_weight, c.dloss = dloss, c.dpc = dpooled_cat;
+  c.dpa = dpooled_an, c.dweights = dweights;
+  return model_head_checked(c, {false, weights && l2 && y && dloss && dpooled_cat && dpooled_an && dweights,
+                                launch_model_head_bwd});
+}
+}  // namespace
+
 int impnn_model_head_loss(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,
                           const float* const* weights, const float* l2, const float* y, float* pred, float* loss,
                           float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F, int32_t Mx,
                           impnn_stream_t stream) {
-  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
-  c.weights = weights, c.l2 = l2, c.y = y, c.out = pred, c.loss = loss, c.workspace = workspace;
-  c.workspace_floats = workspace_floats;
-  return model_head_checked(c, {false, weights && l2 && y && loss && workspace, launch_model_head_tensors});
+  return model_head_loss_entry(__func__, kind, pooled_cat, pooled_an, temperature, weights, l2, y, nullptr, pred, loss,
+                               workspace, workspace_floats, B, D, F, Mx, stream);
+}
+
+int impnn_weighted_model_head_loss(int32_t kind, const float* pooled_cat, const float* pooled_an,
+                                   const float* temperature, const float* const* weights, const float* l2,
+                                   const float* y, const float* sample_weight, float* pred, float* loss,
+                                   float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F,
+                                   int32_t Mx, impnn_stream_t stream) {
+  return model_head_loss_entry(__func__, kind, pooled_cat, pooled_an, temperature, weights, l2, y, sample_weight, pred,
+                               loss, workspace, workspace_floats, B, D, F, Mx, stream);
 }
 
 int impnn_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float* pooled_an, const float* temperature,
                               const float* const* weights, const float* l2, const float* y, const float* dloss,
                               float* dpooled_cat, float* dpooled_an, float* const* dweights, int32_t B, int32_t D,
                               int32_t F, int32_t Mx, impnn_stream_t stream) {
-  ModelHeadCall c = model_head(__func__, kind, pooled_cat, pooled_an, temperature, B, D, F, Mx, stream);
-  c.weights = weights, c.l2 = l2, c.y = y, c.dloss = dloss, c.dpc = dpooled_cat, c.dpa = dpooled_an, c.dweights = dweights;
-  return model_head_checked(c, {false, weights && l2 && y && dloss && dpooled_cat && dpooled_an && dweights,
-                                launch_model_head_bwd});
+  return model_head_loss_bwd_entry(__func__, kind, pooled_cat, pooled_an, temperature, weights, l2, y, nullptr, dloss,
+                                   dpooled_cat, dpooled_an, dweights, B, D, F, Mx, stream);
+}
+
+int impnn_weighted_model_head_loss_bwd(int32_t kind, const float* pooled_cat, const float* pooled_an,
+                                       const float* temperature, const float* const* weights, const float* l2,
+                                       const float* y, const float* sample_weight, const float* dloss,
+                                       float* dpooled_cat, float* dpooled_an, float* const* dweights, int32_t B,
+                                       int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  return model_head_loss_bwd_entry(__func__, kind, pooled_cat, pooled_an, temperature, weights, l2, y, sample_weight,
+                                   dloss, dpooled_cat, dpooled_an, dweights, B, D, F, Mx, stream);
 }
 
 // ---- the operands of a grid launch, as the C entries take them: the head form and the transfer form
@@ -675,6 +715,82 @@ int impnn_transfer_head(const float* pooled_cat, const float* pooled_an, const f
   return launch_transfer_head(c);
 }
 
+// The loss entries are the weighted launcher with a null weight (as the model head's): one body per direction, which
+// names the entry that was called in its errors.
+namespace {
+#define REQUIRE_IN(entry, cond, what)                                 \
+  do {                                                                \
+    if (!(cond)) return fail(IMPNN_E_BADARG, "%s: %s", entry, what);  \
+  } while (0)
+
+int transfer_head_loss_entry(const char* entry, const float* pooled_cat, const float* pooled_an,
+                             const float* const* weights, const float* l2, float* moving_mean, float* moving_var,
+                             float bn_momentum, float bn_eps, int32_t bn_batch, const float* y,
+                             const float* sample_weight, int32_t loss_kind, float delta, float rate, uint64_t seed,
+                             const int64_t* step, int32_t layer_word, float* saved, int64_t saved_floats, float* pred,
+                             float* loss, float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F,
+                             int32_t Mx, impnn_stream_t stream) {
+  TransferHeadCall c{};
+  c.dropout = rate != 0.f;
+  if (c.dropout) {
+    if (int rc = check_dropout(entry, rate, seed, step, layer_word, &c.drop)) return rc;
+  }
+  REQUIRE_IN(entry, B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE_IN(entry, loss_kind == 0 || (loss_kind == 1 && delta > 0.f),
+             "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
+  REQUIRE_IN(entry, bn_eps >= 0.f && bn_momentum >= 0.f && bn_momentum <= 1.f,
+             "bn_eps >= 0 and 0 <= bn_momentum <= 1 required");
+  REQUIRE_IN(entry, pooled_cat && pooled_an && weights && l2 && moving_mean && moving_var && y && loss && workspace,
+             "null pointer");
+  REQUIRE_IN(entry, reinterpret_cast<uintptr_t>(sample_weight) % sizeof(float) == 0,
+             "sample_weight must be 4-byte aligned");
+  REQUIRE_IN(entry, saved || !bn_batch, "the batch statistics need the saved buffer");
+  if (saved && saved_floats < transfer_head_saved_floats(B, F, Mx))
+    return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", entry, (long long)saved_floats);
+  if (workspace_floats < impnn_transfer_head_loss_workspace_floats(B))
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", entry, (long long)workspace_floats);
+  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.l2 = l2, c.moving_mean = moving_mean;
+  c.moving_var = moving_var, c.bn_momentum = bn_momentum, c.bn_eps = bn_eps, c.bn_batch = bn_batch != 0, c.y = y;
+  c.sample_weight = sample_weight;
+  c.loss_kind = loss_kind, c.delta = delta, c.saved = saved, c.out = pred, c.loss = loss, c.workspace = workspace;
+  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
+  return launch_transfer_head(c);
+}
+
+int transfer_head_loss_bwd_entry(const char* entry, const float* pooled_cat, const float* pooled_an,
+                                 const float* const* weights, float* const* dweights, const float* l2,
+                                 int32_t bn_batch, const float* y, const float* sample_weight, int32_t loss_kind,
+                                 float delta, const float* dloss, float rate, uint64_t seed, const int64_t* step,
+                                 int32_t layer_word, const float* saved, int64_t saved_floats, float* workspace,
+                                 int64_t workspace_floats, float* dpooled_cat, float* dpooled_an, int32_t B, int32_t D,
+                                 int32_t F, int32_t Mx, impnn_stream_t stream) {
+  TransferHeadCall c{};
+  c.dropout = rate != 0.f;
+  if (c.dropout) {
+    if (int rc = check_dropout(entry, rate, seed, step, layer_word, &c.drop)) return rc;
+  }
+  REQUIRE_IN(entry, B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE_IN(entry, loss_kind == 0 || (loss_kind == 1 && delta > 0.f),
+             "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
+  REQUIRE_IN(entry, pooled_cat && pooled_an && weights && dweights && l2 && y && dloss && saved && workspace,
+             "null pointer");
+  REQUIRE_IN(entry, reinterpret_cast<uintptr_t>(sample_weight) % sizeof(float) == 0,
+             "sample_weight must be 4-byte aligned");
+  REQUIRE_IN(entry, (dpooled_cat != nullptr) == (dpooled_an != nullptr), "dpooled_cat and dpooled_an: both or neither");
+  if (saved_floats < transfer_head_saved_floats(B, F, Mx))
+    return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", entry, (long long)saved_floats);
+  if (workspace_floats < transfer_head_bwd_workspace_floats(B, F, Mx))
+    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", entry, (long long)workspace_floats);
+  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.dweights = dweights, c.l2 = l2;
+  c.bn_batch = bn_batch != 0, c.y = y, c.sample_weight = sample_weight, c.loss_kind = loss_kind, c.delta = delta;
+  c.dloss = dloss;
+  c.saved = const_cast<float*>(saved), c.workspace = workspace, c.dpc = dpooled_cat, c.dpa = dpooled_an;
+  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
+  return launch_transfer_head_bwd(c);
+}
+#undef REQUIRE_IN
+}  // namespace
+
 int impnn_transfer_head_loss(const float* pooled_cat, const float* pooled_an, const float* const* weights,
                              const float* l2, float* moving_mean, float* moving_var, float bn_momentum, float bn_eps,
                              int32_t bn_batch, const float* y, int32_t loss_kind, float delta, float rate,
@@ -682,26 +798,21 @@ int impnn_transfer_head_loss(const float* pooled_cat, const float* pooled_an, co
                              int64_t saved_floats, float* pred, float* loss, float* workspace,
                              int64_t workspace_floats, int32_t B, int32_t D, int32_t F, int32_t Mx,
                              impnn_stream_t stream) {
-  TransferHeadCall c{};
-  c.dropout = rate != 0.f;
-  if (c.dropout) {
-    if (int rc = check_dropout(__func__, rate, seed, step, layer_word, &c.drop)) return rc;
-  }
-  REQUIRE(B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  REQUIRE(loss_kind == 0 || (loss_kind == 1 && delta > 0.f), "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
-  REQUIRE(bn_eps >= 0.f && bn_momentum >= 0.f && bn_momentum <= 1.f, "bn_eps >= 0 and 0 <= bn_momentum <= 1 required");
-  REQUIRE(pooled_cat && pooled_an && weights && l2 && moving_mean && moving_var && y && loss && workspace,
-          "null pointer");
-  REQUIRE(saved || !bn_batch, "the batch statistics need the saved buffer");
-  if (saved && saved_floats < transfer_head_saved_floats(B, F, Mx))
-    return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", __func__, (long long)saved_floats);
-  if (workspace_floats < impnn_transfer_head_loss_workspace_floats(B))
-    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", __func__, (long long)workspace_floats);
-  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.l2 = l2, c.moving_mean = moving_mean;
-  c.moving_var = moving_var, c.bn_momentum = bn_momentum, c.bn_eps = bn_eps, c.bn_batch = bn_batch != 0, c.y = y;
-  c.loss_kind = loss_kind, c.delta = delta, c.saved = saved, c.out = pred, c.loss = loss, c.workspace = workspace;
-  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
-  return launch_transfer_head(c);
+  return transfer_head_loss_entry(__func__, pooled_cat, pooled_an, weights, l2, moving_mean, moving_var, bn_momentum,
+                                  bn_eps, bn_batch, y, nullptr, loss_kind, delta, rate, seed, step, layer_word, saved,
+                                  saved_floats, pred, loss, workspace, workspace_floats, B, D, F, Mx, stream);
+}
+
+int impnn_weighted_transfer_head_loss(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                                      const float* l2, float* moving_mean, float* moving_var, float bn_momentum,
+                                      float bn_eps, int32_t bn_batch, const float* y, const float* sample_weight,
+                                      int32_t loss_kind, float delta, float rate, uint64_t seed, const int64_t* step,
+                                      int32_t layer_word, float* saved, int64_t saved_floats, float* pred, float* loss,
+                                      float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F,
+                                      int32_t Mx, impnn_stream_t stream) {
+  return transfer_head_loss_entry(__func__, pooled_cat, pooled_an, weights, l2, moving_mean, moving_var, bn_momentum,
+                                  bn_eps, bn_batch, y, sample_weight, loss_kind, delta, rate, seed, step, layer_word,
+                                  saved, saved_floats, pred, loss, workspace, workspace_floats, B, D, F, Mx, stream);
 }
 
 int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an, const float* const* weights,
@@ -710,24 +821,23 @@ int impnn_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an
                                  const int64_t* step, int32_t layer_word, const float* saved, int64_t saved_floats,
                                  float* workspace, int64_t workspace_floats, float* dpooled_cat, float* dpooled_an,
                                  int32_t B, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
-  TransferHeadCall c{};
-  c.dropout = rate != 0.f;
-  if (c.dropout) {
-    if (int rc = check_dropout(__func__, rate, seed, step, layer_word, &c.drop)) return rc;
-  }
-  REQUIRE(B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
-  REQUIRE(loss_kind == 0 || (loss_kind == 1 && delta > 0.f), "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
-  REQUIRE(pooled_cat && pooled_an && weights && dweights && l2 && y && dloss && saved && workspace, "null pointer");
-  REQUIRE((dpooled_cat != nullptr) == (dpooled_an != nullptr), "dpooled_cat and dpooled_an: both or neither");
-  if (saved_floats < transfer_head_saved_floats(B, F, Mx))
-    return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", __func__, (long long)saved_floats);
-  if (workspace_floats < transfer_head_bwd_workspace_floats(B, F, Mx))
-    return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", __func__, (long long)workspace_floats);
-  c.pc = pooled_cat, c.pa = pooled_an, c.weights = weights, c.dweights = dweights, c.l2 = l2;
-  c.bn_batch = bn_batch != 0, c.y = y, c.loss_kind = loss_kind, c.delta = delta, c.dloss = dloss;
-  c.saved = const_cast<float*>(saved), c.workspace = workspace, c.dpc = dpooled_cat, c.dpa = dpooled_an;
-  c.B = B, c.D = D, c.F = F, c.Mx = Mx, c.stream = as_stream(stream);
-  return launch_transfer_head_bwd(c);
+  return transfer_head_loss_bwd_entry(__func__, pooled_cat, pooled_an, weights, dweights, l2, bn_batch, y, nullptr,
+                                      loss_kind, delta, dloss, rate, seed, step, layer_word, saved, saved_floats,
+                                      workspace, workspace_floats, dpooled_cat, dpooled_an, B, D, F, Mx, stream);
+}
+
+int impnn_weighted_transfer_head_loss_bwd(const float* pooled_cat, const float* pooled_an, const float* const* weights,
+                                          float* const* dweights, const float* l2, int32_t bn_batch, const float* y,
+                                          const float* sample_weight, int32_t loss_kind, float delta,
+                                          const float* dloss, float rate, uint64_t seed, const int64_t* step,
+                                          int32_t layer_word, const float* saved, int64_t saved_floats,
+                                          float* workspace, int64_t workspace_floats, float* dpooled_cat,
+                                          float* dpooled_an, int32_t B, int32_t D, int32_t F, int32_t Mx,
+                                          impnn_stream_t stream) {
+  return transfer_head_loss_bwd_entry(__func__, pooled_cat, pooled_an, weights, dweights, l2, bn_batch, y,
+                                      sample_weight, loss_kind, delta, dloss, rate, seed, step, layer_word, saved,
+                                      saved_floats, workspace, workspace_floats, dpooled_cat, dpooled_an, B, D, F, Mx,
+                                      stream);
 }
 
 // ---- the transfer head over a cation x anion grid (include/impnn.h; transfer_grid.hip).  One place applies the

@@ -202,9 +202,10 @@ inline int head_widths_covered(const char* what, int D, int F, int Mx) {
   return IMPNN_OK;
 }
 
-// ---- one model head call (include/impnn.h: impnn_model_head, _tensors, _bwd, _loss, _loss_bwd).  api.hip fills it from
-// the entry's arguments and checks it (model_head_checked); the launchers (model_head.hip) read it.  Pointers an entry
-// does not take stay null; `y` is what makes a call a loss call.
+// ---- one model head call (include/impnn.h: impnn_model_head, _tensors, _bwd, _loss, _loss_bwd and
+// impnn_weighted_model_head_loss[_bwd]).  api.hip fills it from the entry's arguments and checks it
+// (model_head_checked); the launchers (model_head.hip) read it.  Pointers an entry does not take stay null; `y` is what
+// makes a call a loss call.
 struct ModelHeadCall {
   const char* entry;  // the exported entry, named by the error text
   int kind;           // 0 viscosity, 1 melting point
@@ -215,6 +216,7 @@ struct ModelHeadCall {
   const float* dout;            // backward, plain
   float *out, *dpc, *dpa;       // forward (optional in the loss forward); backward
   const float *l2, *y, *dloss;  // loss entries: host lambdas per tensor, targets; backward: device scalar
+  const float* sample_weight;   // weighted loss entries: (B) device floats next to y; null: the unweighted loss
   float *loss, *workspace;      // loss forward: device scalar; model_head_loss_workspace_floats
   int64_t workspace_floats;
   int B, D, F, Mx;
@@ -256,6 +258,7 @@ struct TransferHeadCall {
   float bn_momentum, bn_eps;
   bool bn_batch;  // normalise with the batch statistics and move the moving ones (else: the moving statistics)
   const float* y;
+  const float* sample_weight;  // (B) device floats next to y: the loss is (1/B) sum_b w_b L_b; null: unweighted
   int loss_kind;  // 0 squared error, 1 Huber(delta)
   float delta;
   const float* dloss;

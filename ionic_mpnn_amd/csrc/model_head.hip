@@ -1,5 +1,6 @@
 // f1  The model head: everything after GlobalSumPool, one launch (train_viscosity.py:189,197-214 +
-// models/layers.py:10-49; train_melting_point.py:173,191-198), behind impnn_model_head, _tensors, _bwd, _loss, _loss_bwd.
+// models/layers.py:10-49; train_melting_point.py:173,191-198), behind impnn_model_head, _tensors, _bwd, _loss, _loss_bwd
+// and impnn_weighted_model_head_loss[_bwd] (the loss with per-sample weights).
 //   fp_g  = relu(pooled_g @ Wfp_g + bfp_g)         (D -> F)     g in {cat, an}
 //   mixed = relu(fp_cat @ Wp_cat + bp_cat) + relu(fp_an @ Wp_an + bp_an)      (F -> Mx)
 //   kind 0: vp = mixed @ Wv + bv (Mx -> 3); A = vp0; Bc = clip(softplus(vp1), 0, 20);
@@ -112,6 +113,15 @@ struct HeadLoss {
   unsigned int* counter; // forward: arrival ticket, zero before the first call, left at zero by every call
   float inv_B;
 };
+// With sample weights (keras sum_over_batch_size): (1/B) sum_b w_b (pred_b - y_b)^2 + the same penalties; B counts the
+// samples of weight 0 too.  The weights are an argument of the weighted kernel instances alone: a call without them
+// launches the instances whose argument block is the unweighted loss's, with no weight instruction and no multiply by 1.
+template <bool kWeighted>
+struct HeadLossArg : HeadLoss {};
+template <>
+struct HeadLossArg<true> : HeadLoss {
+  const float* w;  // (B) sample weights, read for live samples only
+};
 __device__ __forceinline__ float head_l2(const HeadTensors& ht, int sgm) {
   float v = ht.l2[0];
 #pragma unroll
@@ -209,11 +219,13 @@ __device__ __forceinline__ void head_forward_mix(const float* ws, const float* x
   __syncthreads();
 }
 
+// kWeighted: a loss call with sample weights (hl.y and hl.w set); the other instance has no trace of them
+template <bool kWeighted>
 __global__ __launch_bounds__(256) void model_head_tensors_kernel(int kind, const float* __restrict__ pc,
                                                                  const float* __restrict__ pa,
                                                                  const float* __restrict__ T, HeadTensors ht,
                                                                  float* __restrict__ out, int B, int D, int F, int Mx,
-                                                                 HeadLoss hl) {
+                                                                 HeadLossArg<kWeighted> hl) {
   extern __shared__ __align__(16) float hsm[];
   __shared__ float red[256];
   __shared__ float sq[kHeadSPB];
@@ -251,7 +263,10 @@ __global__ __launch_bounds__(256) void model_head_tensors_kernel(int kind, const
         pred = vp[0] + Bc / (T[b] / 100.0f + Cc + 1e-6f);
         if (out) out[b] = pred;
       }
-      if (hl.y) sq[sl] = live ? (pred - hl.y[b]) * (pred - hl.y[b]) : 0.f;
+      if constexpr (kWeighted)
+        sq[sl] = live ? hl.w[b] * ((pred - hl.y[b]) * (pred - hl.y[b])) : 0.f;
+      else if (hl.y)
+        sq[sl] = live ? (pred - hl.y[b]) * (pred - hl.y[b]) : 0.f;
     }
   } else {
     const float* Wh = wt;
@@ -267,7 +282,10 @@ __global__ __launch_bounds__(256) void model_head_tensors_kernel(int kind, const
       float acc = Wo[F];
       for (int j = 0; j < F; ++j) acc = fmaf(hid[sl * kHeadMaxDim + j], Wo[j], acc);
       if (live && out) out[b] = acc;
-      if (hl.y) sq[sl] = live ? (acc - hl.y[b]) * (acc - hl.y[b]) : 0.f;
+      if constexpr (kWeighted)
+        sq[sl] = live ? hl.w[b] * ((acc - hl.y[b]) * (acc - hl.y[b])) : 0.f;
+      else if (hl.y)
+        sq[sl] = live ? (acc - hl.y[b]) * (acc - hl.y[b]) : 0.f;
     }
   }
   if (!hl.y) return;
@@ -312,11 +330,12 @@ __device__ __forceinline__ int head_vec_off(int which) {
 // weights, form the parameter gradients' outer products and flush them - the three phases that scale with the packed
 // weight count (25 K floats at atom_dim 128) and made the kernel ~96 us at every batch below 2048, alone on the stream
 // between the two halves of a training step.
+template <bool kWeighted>
 __global__ __launch_bounds__(1024) void model_head_bwd_kernel(int kind, const float* __restrict__ pc,
                                                              const float* __restrict__ pa, const float* __restrict__ T,
                                                              HeadTensors ht, const float* __restrict__ dout,
                                                              float* __restrict__ dpc, float* __restrict__ dpa, int B,
-                                                             int D, int F, int Mx, HeadLoss hl) {
+                                                             int D, int F, int Mx, HeadLossArg<kWeighted> hl) {
   extern __shared__ __align__(16) float hsm[];
   const int total = head_total(ht);
   const int tpad = (total + 3) & ~3;
@@ -369,8 +388,10 @@ __global__ __launch_bounds__(1024) void model_head_bwd_kernel(int kind, const fl
       __syncthreads();
     }
     const float* mx = V(kVMix);
-    // gradient of the prediction: given (plain head), or 2 (pred - y) / B * dloss once pred is known (loss entries)
-    const float gscale = hl.y ? 2.0f * hl.inv_B * hl.dloss[0] : 0.f;
+    // gradient of the prediction: given (plain head), or 2 (pred - y) / B * dloss once pred is known (loss entries),
+    // times the sample's weight where the call has weights
+    float gscale = hl.y ? 2.0f * hl.inv_B * hl.dloss[0] : 0.f;
+    if constexpr (kWeighted) gscale = live ? gscale * hl.w[b] : 0.f;
     float d = (live && !hl.y) ? dout[b] : 0.f;
     float* top = V(kVTop);
     // ---- top of the head: kVTop = gradient of [A,b,c] (kind 0) / of the hidden pre-activation (kind 1)
@@ -554,10 +575,20 @@ int launch_model_head_tensors(const ModelHeadCall& c) {
   }
   const size_t lds = sizeof(float) * (align4(ht.off[ht.n]) + (size_t)kHeadSPB * (2 * kHeadMaxX + 6 * kHeadMaxDim));
   if (lds > kHeadTableLdsCap) return fail(IMPNN_E_UNSUPPORTED, "model_head: weights do not fit LDS");
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)model_head_tensors_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  model_head_tensors_kernel<<<(c.B + kHeadSPB - 1) / kHeadSPB, 256, lds, c.stream>>>(c.kind, c.pc, c.pa, c.T, ht, c.out,
-                                                                                   c.B, c.D, c.F, c.Mx, hl);
+  auto launch = [&](auto kernel, auto arg) {
+    static_cast<HeadLoss&>(arg) = hl;
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kernel<<<(c.B + kHeadSPB - 1) / kHeadSPB, 256, lds, c.stream>>>(c.kind, c.pc, c.pa, c.T, ht, c.out, c.B, c.D, c.F,
+                                                                  c.Mx, arg);
+  };
+  if (c.y && c.sample_weight) {
+    HeadLossArg<true> arg{};
+    arg.w = c.sample_weight;
+    launch(model_head_tensors_kernel<true>, arg);
+  } else {
+    launch(model_head_tensors_kernel<false>, HeadLossArg<false>{});
+  }
   return check_launch("model_head_tensors");
 }
 
@@ -575,11 +606,21 @@ int launch_model_head_bwd(const ModelHeadCall& c) {
   const size_t lds = sizeof(float) * (2 * align4(ht.off[ht.n]) + (size_t)kHeadSPB * (kHdVecStride + 4 * kHeadMaxDim));
   if ((int64_t)align4(ht.off[ht.n]) > model_head_bwd_max_floats())
     return fail(IMPNN_E_UNSUPPORTED, "model_head_bwd: weights do not fit LDS");
-  if (lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)model_head_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const int groups = (c.B + kHeadSPB - 1) / kHeadSPB;  // bounded grid: every workgroup flushes ~|weights| atomics once
-  model_head_bwd_kernel<<<groups < 512 ? groups : 512, 1024, lds, c.stream>>>(c.kind, c.pc, c.pa, c.T, ht, c.dout, c.dpc,
-                                                                            c.dpa, c.B, c.D, c.F, c.Mx, hl);
+  auto launch = [&](auto kernel, auto arg) {
+    static_cast<HeadLoss&>(arg) = hl;
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kernel<<<groups < 512 ? groups : 512, 1024, lds, c.stream>>>(c.kind, c.pc, c.pa, c.T, ht, c.dout, c.dpc, c.dpa, c.B,
+                                                               c.D, c.F, c.Mx, arg);
+  };
+  if (c.y && c.sample_weight) {
+    HeadLossArg<true> arg{};
+    arg.w = c.sample_weight;
+    launch(model_head_bwd_kernel<true>, arg);
+  } else {
+    launch(model_head_bwd_kernel<false>, HeadLossArg<false>{});
+  }
   return check_launch("model_head_bwd");
 }
 

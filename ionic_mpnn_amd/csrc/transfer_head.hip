@@ -1,7 +1,8 @@
 // The transfer-learning head (train_melting_point_transfer.py:95-103) behind GlobalSumPool, forward, loss and backward:
 //   pooled_cat, pooled_an -> fp Dense relu (per ion) -> proj Dense relu (per ion) -> add
 //     -> Dense 256 relu -> BatchNormalization -> Dense 128 relu -> Dropout -> Dense 64 relu -> Dense 1
-//     -> Huber(delta) or squared error against y, mean over the batch, + l2 penalties
+//     -> Huber(delta) or squared error against y, mean over the batch (with sample weights: (1/B) sum_b w_b L_b),
+//        + l2 penalties
 // Tensor order of `weights` / `dweights` (kThTensors pointers, keras shapes: kernels (in,out)):
 //   0 Wfp_cat 1 bfp_cat 2 Wfp_an 3 bfp_an 4 Wp_cat 5 bp_cat 6 Wp_an 7 bp_an 8 W1 9 b1 10 gamma 11 beta 12 W2 13 b2
 //   14 W3 15 b3 16 Wo 17 bo
@@ -86,6 +87,9 @@ struct ThLoss {
   int kind;               // 0: squared error, 1: Huber
   float inv_B;
 };
+// With sample weights the loss is (1/B) sum_b w_b L_b, B counting the samples of weight 0 too.  The weights are the last
+// argument of th_forward and th_bwd_post, which only their weighted instances look at: a call without them launches the
+// instances that hold no weight instruction and no multiply by 1.
 
 __device__ __forceinline__ float th_loss_value(int kind, float delta, float e) {
   if (kind == 0) return e * e;
@@ -175,12 +179,15 @@ __device__ __forceinline__ void th_load_tile(float* lds, int ls, const float* g,
 // flags of th_forward
 enum { kThPre = 1, kThPost = 2, kThBatchStats = 4 };
 
+// kWeighted: a loss call with sample weights (hl.y and hl.w set); the other instance has no trace of them.  The
+// weights touch the loss only: BatchNormalization's statistics and the dropout masks do not see them.
+template <bool kWeighted>
 __global__ __launch_bounds__(kThThreads) void th_forward(const float* __restrict__ pc, const float* __restrict__ pa,
                                                          ThTensors ht, const float* __restrict__ moving_mean,
                                                          const float* __restrict__ moving_var, float bn_eps, int flags,
                                                          float* __restrict__ saved, float* __restrict__ out, int B,
                                                          int D, int F, int Mx, bool dropout, DropoutArgs drop,
-                                                         ThLoss hl) {
+                                                         ThLoss hl, const float* __restrict__ sw) {
   __shared__ ThSmem sm;
   __shared__ int is_last;
   const int tid = threadIdx.x;
@@ -260,7 +267,12 @@ __global__ __launch_bounds__(kThThreads) void th_forward(const float* __restrict
   if (tid == 0) {
     float sum = 0.f;
     for (int s = 0; s < kThSPB; ++s)
-      if (b0 + s < B) sum += th_loss_value(hl.kind, hl.delta, sm.small[s] - hl.y[b0 + s]);
+      if (b0 + s < B) {
+        if constexpr (kWeighted)
+          sum += sw[b0 + s] * th_loss_value(hl.kind, hl.delta, sm.small[s] - hl.y[b0 + s]);
+        else
+          sum += th_loss_value(hl.kind, hl.delta, sm.small[s] - hl.y[b0 + s]);
+      }
     __hip_atomic_store(&hl.partial[blockIdx.x], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __threadfence();
     const unsigned int ticket = atomicAdd(hl.counter, 1u);
@@ -325,19 +337,29 @@ __global__ __launch_bounds__(kThThreads) void th_bn_stats(const float* __restric
 }
 
 // Backward from the loss to the gradient of BatchNormalization's output: dz3 (B,64), dz2 (B,128), g (B,256).
+// kWeighted: the prediction's gradient seed carries the sample's weight w[b] (live samples only read it); the other
+// instance never looks at its last argument.
+template <bool kWeighted>
 __global__ __launch_bounds__(kThThreads) void th_bwd_post(ThTensors ht, const float* __restrict__ saved,
                                                           float* __restrict__ work, const float* __restrict__ y,
                                                           const float* __restrict__ dloss, int loss_kind, float delta,
-                                                          int B, int F, int Mx, bool dropout, DropoutArgs drop) {
+                                                          int B, int F, int Mx, bool dropout, DropoutArgs drop,
+                                                          const float* __restrict__ w) {
   __shared__ ThSmem sm;
   const int tid = threadIdx.x, b0 = blockIdx.x * kThSPB;
   const ThSaved so = th_saved(B, F, Mx);
   const ThWork wo = th_work(B, F, Mx);
   th_load_tile(sm.a2, kThH2, saved + so.a2, kThH2, b0, B);
   th_load_tile(sm.a3, kThH3, saved + so.a3, kThH3, b0, B);
-  if (tid < kThSPB)
-    sm.small[tid] = b0 + tid < B ? th_loss_grad(loss_kind, delta, saved[so.pred + b0 + tid] - y[b0 + tid]) / (float)B * dloss[0]
-                                 : 0.f;
+  if (tid < kThSPB) {
+    if constexpr (kWeighted)
+      sm.small[tid] = b0 + tid < B ? w[b0 + tid] * th_loss_grad(loss_kind, delta, saved[so.pred + b0 + tid] - y[b0 + tid]) /
+                                         (float)B * dloss[0]
+                                   : 0.f;
+    else
+      sm.small[tid] = b0 + tid < B ? th_loss_grad(loss_kind, delta, saved[so.pred + b0 + tid] - y[b0 + tid]) / (float)B * dloss[0]
+                                   : 0.f;
+  }
   __syncthreads();
   if (tid < kThSPB && b0 + tid < B) work[wo.dpred + b0 + tid] = sm.small[tid];
   float* dz3 = sm.fp;  // [kThSPB][kThH3]
@@ -533,23 +555,27 @@ int launch_transfer_head(const TransferHeadCall& c) {
     hl.delta = c.delta, hl.kind = c.loss_kind, hl.inv_B = 1.0f / (float)c.B;
   }
   const int groups = (c.B + kThSPB - 1) / kThSPB;
+  // the launch that ends with the loss: the weighted instance where the call has weights
+  auto loss_forward = [&](int flags) {
+    const bool weighted = c.y && c.sample_weight;
+    const auto kernel = weighted ? th_forward<true> : th_forward<false>;
+    kernel<<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps, flags, c.saved,
+                                                c.out, c.B, c.D, c.F, c.Mx, c.dropout, c.drop, hl,
+                                                weighted ? c.sample_weight : nullptr);
+  };
   const ThSaved so = th_saved(c.B, c.F, c.Mx);
   if (c.bn_batch) {
-    th_forward<<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps, kThPre,
+    th_forward<false><<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps, kThPre,
                                                     c.saved, nullptr, c.B, c.D, c.F, c.Mx, false, DropoutArgs{},
-                                                    ThLoss{});
+                                                    ThLoss{}, nullptr);
     if (int rc = check_launch("transfer_head (pre)")) return rc;
     th_bn_stats<<<kThH1 / kThStatLanes, kThThreads, 0, c.stream>>>(c.saved + so.a1, c.saved + so.stat, c.moving_mean,
                                                                    c.moving_var, c.bn_momentum, c.bn_eps, c.B);
     if (int rc = check_launch("transfer_head (statistics)")) return rc;
-    th_forward<<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps,
-                                                    kThPost | kThBatchStats, c.saved, c.out, c.B, c.D, c.F, c.Mx,
-                                                    c.dropout, c.drop, hl);
+    loss_forward(kThPost | kThBatchStats);
     return check_launch("transfer_head (post)");
   }
-  th_forward<<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps,
-                                                  kThPre | kThPost, c.saved, c.out, c.B, c.D, c.F, c.Mx, c.dropout,
-                                                  c.drop, hl);
+  loss_forward(kThPre | kThPost);
   return check_launch("transfer_head");
 }
 
@@ -565,8 +591,9 @@ int launch_transfer_head_bwd(const TransferHeadCall& c) {
   const ThSaved so = th_saved(B, F, Mx);
   const ThWork wo = th_work(B, F, Mx);
   float* const* dw = c.dweights;
-  th_bwd_post<<<groups, kThThreads, 0, c.stream>>>(ht, c.saved, c.workspace, c.y, c.dloss, c.loss_kind, c.delta, B, F,
-                                                   Mx, c.dropout, c.drop);
+  const auto bwd_post = c.sample_weight ? th_bwd_post<true> : th_bwd_post<false>;
+  bwd_post<<<groups, kThThreads, 0, c.stream>>>(ht, c.saved, c.workspace, c.y, c.dloss, c.loss_kind, c.delta, B, F, Mx,
+                                                c.dropout, c.drop, c.sample_weight);
   if (int rc = check_launch("transfer_head_bwd (post)")) return rc;
   if (c.bn_batch) {
     th_bn_bwd_stats<<<kThH1 / kThStatLanes, kThThreads, 0, c.stream>>>(c.saved + so.a1, c.saved + so.stat,

@@ -921,12 +921,16 @@ class MPNNModel:
             return lam + [0.0] * 10
         return lam + ([0.0, 0.0] if self.kind == "viscosity" else [self.fp_l2, 0.0, 0.0, 0.0])
 
-    def _loss(self, inputs, y, training):
+    def _loss(self, inputs, y, training, sample_weight=None):
+        """The batch loss.  ``sample_weight`` (one finite value >= 0 per sample, or None) makes it keras's weighted
+        loss, (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too; it touches the loss only, never
+        BatchNormalization's statistics or a dropout mask."""
         from . import train
         y = torch.as_tensor(y, dtype=torch.float32).to(self.device).reshape(-1, 1)
+        sw = train.checked_sample_weight(sample_weight, int(y.shape[0]), self.device)
         covered = y.shape[0] > 0 and self._head_kernels_cover()
         if self.kind == "transfer" and covered:
-            return self._transfer_loss(self._to_device(inputs), y, training)
+            return self._transfer_loss(self._to_device(inputs), y, training, sw)
         if training and torch.is_grad_enabled() and covered and self._head_nodes_cover() and self._loss_name() == "mse":
             # head, mse and the l2 penalties as ONE node (impnn_model_head_loss): ~25 launches fewer per step
             from . import autograd
@@ -937,11 +941,14 @@ class MPNNModel:
                 ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
             pc, pa = self.encode_pooled(inputs, fused=False, training=True)
             T = inputs.get("temperature") if self.kind == "viscosity" else None
+            l2 = self._head_l2() if sw is None else autograd.WeightedL2(self._head_l2(), sw)
             return autograd.ModelHeadLoss.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
-                                                self.mixing_size, self._head_l2(), ws, pc, pa, T, y,
-                                                *self._head_tensors())
+                                                self.mixing_size, l2, ws, pc, pa, T, y, *self._head_tensors())
         pred = self(inputs, training=True) if training else self(inputs)
         fn = train.mse if self._loss_name() == "mse" else train.Huber(self._loss_delta())
+        if sw is not None:
+            unweighted = fn
+            fn = lambda y_true, y_pred: unweighted(y_true, y_pred, sw)
         if training:
             return fn(y, pred) + self.regularization_loss()
         with torch.no_grad():
@@ -955,8 +962,9 @@ class MPNNModel:
         mode = self.resolve_encoder_mode(N, E)
         return mode is not None and ops.encoder_overflow_possible(N, E, self.atom_dim, mode)
 
-    def _transfer_loss(self, inputs, y, training):
-        """The transfer model's loss as one node (impnn_transfer_head_loss[_bwd]).  An encoder with nothing to train
+    def _transfer_loss(self, inputs, y, training, sample_weight=None):
+        """The transfer model's loss as one node (impnn_transfer_head_loss[_bwd], the weighted entries with a
+        ``sample_weight``).  An encoder with nothing to train
         computes the pooled vectors as inference does - fused encoder where the shape allows, no graph, nothing saved -
         unless its GatedUpdate dropout has to apply; otherwise the layered pass keeps a graph from the first trained
         step up (_first_trained_step)."""
@@ -977,11 +985,15 @@ class MPNNModel:
                 else:
                     pc, pa = self.encode_pooled(inputs, fused=False if training and self._overflow_check(inputs) else None)
         with torch.set_grad_enabled(training and torch.is_grad_enabled()):
-            return autograd.TransferHeadLoss.apply(self._transfer_cfg(training, ds), ws, pc, pa, y,
-                                                   *self._head_tensors())
+            cfg = self._transfer_cfg(training, ds)
+            if sample_weight is not None:
+                cfg = dict(cfg, sample_weight=sample_weight)
+            return autograd.TransferHeadLoss.apply(cfg, ws, pc, pa, y, *self._head_tensors())
 
-    def train_on_batch(self, inputs, y, group=None, n_global=None):
+    def train_on_batch(self, inputs, y, sample_weight=None, group=None, n_global=None):
         """One optimizer step on one mini-batch -> the batch loss (MSE + penalties) as a 0-d tensor.
+        ``sample_weight``: one finite value >= 0 per sample (of this rank's shard): the loss is keras's
+        (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too.
         With torch.distributed initialised (or ``group`` given) every rank calls this with its shard of
         the global mini-batch: the gradients are averaged over ranks (weighted by shard size) with one
         all-reduce of the flat gradient buffer, then every rank applies the same step.  ``n_global``: size of the
@@ -991,7 +1003,10 @@ class MPNNModel:
             self.compile()
         opt = self.optimizer
         n_local = len(inputs["cat_atom"])
-        loss = self._loss(inputs, y, training=True) if n_local else None
+        if sample_weight is not None and not n_local:
+            from . import train
+            train.checked_sample_weight(sample_weight, 0)
+        loss = self._loss(inputs, y, training=True, sample_weight=sample_weight) if n_local else None
         if idist.is_distributed():
             if n_global is not None:
                 weight = float(n_local) / float(n_global) if n_global > 0 else 0.0
@@ -1009,18 +1024,22 @@ class MPNNModel:
         self.weights_updated()
         return loss.detach() if loss is not None else torch.zeros((), device=opt.flat_grad.device)
 
-    def evaluate(self, inputs, y, batch_size=32):
-        """model.evaluate: sample-weighted mean of the batch losses (MSE + penalties)."""
+    def evaluate(self, inputs, y, batch_size=32, sample_weight=None):
+        """model.evaluate: sample-count-weighted mean of the batch losses (MSE + penalties); with ``sample_weight`` a
+        batch loss is the weighted one, (1/B) sum_b w_b L_b + penalties."""
+        from . import train
         n = len(inputs["cat_atom"])
+        sw = train.checked_sample_weight(sample_weight, n, self.device)
         tot = torch.zeros((), dtype=torch.float64, device=self.device)
         for lo in range(0, n, batch_size):
             sl = slice(lo, min(n, lo + batch_size))
-            loss = self._loss({k: v[sl] for k, v in inputs.items()}, y[sl], training=False)
+            loss = self._loss({k: v[sl] for k, v in inputs.items()}, y[sl], training=False,
+                              sample_weight=None if sw is None else sw[sl])
             tot.add_(loss, alpha=sl.stop - sl.start)  # summed on the device: one host sync per evaluate()
         return float(tot) / max(n, 1)
 
     def fit(self, x, y, validation_data=None, epochs=1, batch_size=32, callbacks=None, shuffle=True, verbose=0,
-            seed=None, graph=True):
+            seed=None, graph=True, sample_weight=None):
         """model.fit as the trainers call it (train_viscosity.py:328-338): per epoch a fresh shuffle,
         mini-batches of ``batch_size``, `loss` = sample-weighted mean of the batch losses, `val_loss` from
         evaluate(); callbacks see on_train_begin / on_epoch_end / on_train_end.  Returns a History.
@@ -1028,13 +1047,22 @@ class MPNNModel:
         (train.GraphedTrainStep); the last, smaller batch of an epoch runs eagerly.
         Under torch.distributed every rank passes the FULL (x, y): the shuffle seed is rank 0's (broadcast once), every
         global mini-batch is cut into contiguous shards (data.shard_bounds), so all ranks run the same number of steps
-        with the same sample order, and the reported loss is the global sample-weighted mean."""
+        with the same sample order, and the reported loss is the global sample-weighted mean.
+        ``sample_weight``: one finite value >= 0 per training sample (data.balanced_weights, data.bootstrap_weights):
+        every batch loss becomes (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too; the weights
+        are uploaded once and cut like y.  ``validation_data`` may be ``(x, y)`` or ``(x, y, sample_weight)``."""
         from . import train
         if getattr(self, "optimizer", None) is None:
             self.compile()
-        x = self._to_device(x)
         y = np.asarray(y, dtype=np.float32)
         n = len(y)
+        w_host = train.checked_sample_weight(sample_weight, n)  # raises before anything reaches the device
+        if validation_data is not None and len(validation_data) not in (2, 3):
+            raise ValueError("validation_data must be (x, y) or (x, y, sample_weight)")
+        val_w_host = None
+        if validation_data is not None and len(validation_data) == 3:
+            val_w_host = train.checked_sample_weight(validation_data[2], len(np.asarray(validation_data[1])))
+        x = self._to_device(x)
         if n:  # once per data set (one device sync), not per batch: raise where tf-CPU's gather / scatter_nd would
             for pfx in ("cat", "an"):
                 ops.validate_indices(conn=x[f"{pfx}_connectivity"], atom_ids=x[f"{pfx}_atom"], bond_ids=x[f"{pfx}_bond"],
@@ -1060,6 +1088,7 @@ class MPNNModel:
         graphed = None
         use_graph = bool(graph) and not distributed and n >= batch_size
         y_dev = torch.from_numpy(y).to(self.device).reshape(-1, 1)
+        w_dev = None if w_host is None else w_host.to(self.device)  # uploaded once, like y_dev
         val_dev = None
         for epoch in range(int(epochs)):
             order = rng.permutation(n) if shuffle else np.arange(n)
@@ -1071,18 +1100,24 @@ class MPNNModel:
                 if use_graph and len(idx) == batch_size:
                     if graphed is None:
                         x = {k: v.contiguous() for k, v in x.items()}
-                        graphed = train.GraphedTrainStep(self, {k: v[tidx] for k, v in x.items()}, y[idx],
-                                                         resident=(x, y_dev))
-                    loss = graphed.step_on_rows(x, y_dev, tidx)
+                        if w_dev is None:
+                            graphed = train.GraphedTrainStep(self, {k: v[tidx] for k, v in x.items()}, y[idx],
+                                                             resident=(x, y_dev))
+                        else:
+                            graphed = train.GraphedTrainStep(self, {k: v[tidx] for k, v in x.items()}, y[idx],
+                                                             resident=(x, y_dev, w_dev), sample_weight=w_dev[tidx])
+                    loss = graphed.step_on_rows(x, y_dev, tidx, w_dev)
                 elif distributed:
                     from .data import shard_bounds
                     s0, s1 = shard_bounds(len(idx), world, rank)
                     sidx = tidx[s0:s1]
-                    loss = self.train_on_batch({k: v[sidx] for k, v in x.items()}, y_dev[sidx], n_global=len(idx))
+                    loss = self.train_on_batch({k: v[sidx] for k, v in x.items()}, y_dev[sidx],
+                                               None if w_dev is None else w_dev[sidx], n_global=len(idx))
                     tot.add_(loss, alpha=s1 - s0)  # shard means, weighted by shard size; summed over ranks below
                     continue
                 else:
-                    loss = self.train_on_batch({k: v[tidx] for k, v in x.items()}, y_dev[tidx])
+                    loss = self.train_on_batch({k: v[tidx] for k, v in x.items()}, y_dev[tidx],
+                                               None if w_dev is None else w_dev[tidx])
                 tot.add_(loss, alpha=len(idx))
             if distributed:  # every rank summed its shards' losses: one all-reduce per epoch for the logged mean
                 if tdist.get_backend() == "nccl":
@@ -1095,9 +1130,10 @@ class MPNNModel:
             if validation_data is not None:
                 if val_dev is None:  # uploaded once, not per epoch
                     val_dev = (self._to_device(validation_data[0]),
-                               torch.from_numpy(np.asarray(validation_data[1], np.float32)).to(self.device))
+                               torch.from_numpy(np.asarray(validation_data[1], np.float32)).to(self.device),
+                               None if val_w_host is None else val_w_host.to(self.device))
                 # the sample-weighted mean does not depend on how the set is cut: large forward-only batches
-                logs["val_loss"] = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096))
+                logs["val_loss"] = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096), val_dev[2])
             hist._log(epoch, logs)
             if verbose:
                 print(f"Epoch {epoch + 1}/{epochs} - " + " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()), flush=True)

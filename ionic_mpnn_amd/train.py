@@ -98,18 +98,27 @@ class GraphedTrainStep:
     Inputs are copied into static buffers; every kernel argument that changes between steps lives in device
     memory (the Adam step counter, the dropout step counter that the captured snapshot launch advances)."""
 
-    def __init__(self, model, inputs, y, resident=None):
+    def __init__(self, model, inputs, y, resident=None, sample_weight=None):
         """``resident=(x, y_dev)``: the whole padded training set lives on the device; the captured step then starts
         with the gather of the rows in ``self.static_rows`` (impnn_gather_rows) and ``step_on_rows`` only refreshes
-        those 8*batch bytes between replays."""
+        those 8*batch bytes between replays.  ``sample_weight`` (one value per sample of the batch) makes it the
+        weighted step: the weights sit in a static buffer like y, and ``resident=(x, y_dev, w_dev)`` gathers their
+        rows inside the capture too, with a second gather launch behind the first (the first takes at most 8 tensors
+        and stays as the unweighted step has it)."""
         self.model = model
         dev = model.device
         self.static_in = {k: v.clone() for k, v in model._to_device(inputs).items()}
         self.static_y = torch.as_tensor(np.asarray(y, np.float32)).to(dev).reshape(-1, 1).clone()
         self.batch = int(self.static_y.shape[0])
+        self.static_w = None
+        if sample_weight is not None:
+            self.static_w = checked_sample_weight(sample_weight, self.batch, dev).reshape(-1, 1).clone()
         self.resident = None
+        self.resident_w = None
         if resident is not None:
-            x, y_dev = resident
+            if (len(resident) == 3) != (self.static_w is not None):
+                raise ValueError("resident=(x, y_dev, w_dev) goes with sample_weight, resident=(x, y_dev) without")
+            x, y_dev = resident[0], resident[1]
             keys = list(self.static_in)
             ok = len(keys) + 1 <= 8 and all(
                 x[k].is_contiguous() and x[k].dtype == self.static_in[k].dtype and x[k].element_size() == 4
@@ -117,6 +126,11 @@ class GraphedTrainStep:
             if ok:
                 self.resident = ([x[k] for k in keys] + [y_dev], [self.static_in[k] for k in keys] + [self.static_y])
                 self.static_rows = torch.zeros(self.batch, dtype=torch.int64, device=dev)
+                if self.static_w is not None:
+                    w_dev = resident[2]
+                    if not (w_dev.is_contiguous() and w_dev.dtype == torch.float32 and w_dev.numel() == y_dev.numel()):
+                        raise ValueError("resident weights must be a contiguous float32 tensor, one value per sample")
+                    self.resident_w = ([w_dev.reshape(-1, 1)], [self.static_w])
         opt = model.optimizer
         saved_w = [t.detach().clone() for _, t in model.variables()]  # (with BatchNormalization's moving statistics)
         saved_o = opt.state()
@@ -146,7 +160,12 @@ class GraphedTrainStep:
         if self.resident is not None:
             from . import ops
             ops.gather_rows(self.resident[0], self.resident[1], self.static_rows)
-        loss = m._loss(self.static_in, self.static_y, training=True)
+            if self.resident_w is not None:
+                ops.gather_rows(self.resident_w[0], self.resident_w[1], self.static_rows)
+        if self.static_w is None:
+            loss = m._loss(self.static_in, self.static_y, training=True)
+        else:
+            loss = m._loss(self.static_in, self.static_y, training=True, sample_weight=self.static_w)
         loss.backward()
         m.join_training_streams()
         m.optimizer.apply_gradients()
@@ -156,24 +175,32 @@ class GraphedTrainStep:
     def matches(self, inputs):
         return all(tuple(inputs[k].shape) == tuple(v.shape) for k, v in self.static_in.items())
 
-    def step_on_rows(self, x, y_dev, rows):
+    def step_on_rows(self, x, y_dev, rows, w_dev=None):
         """One step on the mini-batch ``rows`` (device int64 tensor, len = batch) of a device-resident data set:
         the rows are gathered straight into the static buffers (one index_select per tensor, no staging copy, no
-        host round trip)."""
+        host round trip).  ``w_dev``: the data set's weights, for a step that was built with ``sample_weight``."""
+        if (w_dev is not None) != (self.static_w is not None):
+            raise ValueError("a step captured with sample_weight takes weights on every call, one without takes none")
         if self.resident is not None and x[next(iter(self.static_in))] is self.resident[0][0]:
             self.static_rows.copy_(rows)  # the gather is the first node of the graph
         else:
             for k, v in self.static_in.items():
                 torch.index_select(x[k], 0, rows, out=v)
             torch.index_select(y_dev, 0, rows, out=self.static_y)
+            if w_dev is not None:
+                torch.index_select(w_dev.reshape(-1, 1), 0, rows, out=self.static_w)
         self.graph.replay()
         self.model.weights_updated()
         return self.static_loss
 
-    def __call__(self, inputs, y):
+    def __call__(self, inputs, y, sample_weight=None):
+        if (sample_weight is not None) != (self.static_w is not None):
+            raise ValueError("a step captured with sample_weight takes weights on every call, one without takes none")
         for k, v in self.static_in.items():
             v.copy_(inputs[k], non_blocking=True)
         self.static_y.copy_(torch.as_tensor(np.asarray(y, np.float32)).reshape(-1, 1), non_blocking=True)
+        if sample_weight is not None:
+            self.static_w.copy_(checked_sample_weight(sample_weight, self.batch).reshape(-1, 1), non_blocking=True)
         self.graph.replay()
         self.model.weights_updated()
         return self.static_loss
@@ -258,15 +285,56 @@ class Huber:
     def get_config(self):
         return {"name": "huber_loss", "delta": self.delta}
 
-    def __call__(self, y_true, y_pred):
+    def __call__(self, y_true, y_pred, sample_weight=None):
         e = y_pred.reshape(y_true.shape[0], -1) - y_true.reshape(y_true.shape[0], -1)
         a = e.abs()
-        return torch.mean(torch.where(a <= self.delta, 0.5 * e * e, self.delta * (a - 0.5 * self.delta)))
+        per = torch.where(a <= self.delta, 0.5 * e * e, self.delta * (a - 0.5 * self.delta))
+        if sample_weight is None:
+            return torch.mean(per)
+        return _weighted_batch_mean(per, sample_weight)
 
 
-def mse(y_true, y_pred):
-    """keras "mse": mean over the last axis, then over the batch."""
-    return torch.mean((y_pred.reshape(y_true.shape[0], -1) - y_true.reshape(y_true.shape[0], -1)) ** 2)
+def mse(y_true, y_pred, sample_weight=None):
+    """keras "mse": mean over the last axis, then over the batch; with ``sample_weight`` (one value per sample)
+    (1/B) sum_b w_b * mean_last(e_b^2), keras's sum_over_batch_size: B counts the samples of weight 0 too."""
+    per = (y_pred.reshape(y_true.shape[0], -1) - y_true.reshape(y_true.shape[0], -1)) ** 2
+    if sample_weight is None:
+        return torch.mean(per)
+    return _weighted_batch_mean(per, sample_weight)
+
+
+def _weighted_batch_mean(per, sample_weight):
+    """(1/B) sum_b w_b * mean over the last axis of per[b]: the weighted twin of torch.mean(per)."""
+    w = torch.as_tensor(sample_weight, dtype=per.dtype, device=per.device).reshape(-1)
+    if w.numel() != per.shape[0]:
+        raise ValueError("sample_weight must hold one value per sample")
+    return torch.sum(w * per.mean(dim=1)) / per.shape[0]
+
+
+def checked_sample_weight(sample_weight, n, device=None):
+    """``sample_weight`` as fit / evaluate / train_on_batch take it -> a float32 (n) tensor on ``device`` (host when
+    None), or None.  Weights are one finite value >= 0 per sample: anything else is a ValueError here, before any
+    library call.  A tensor that already lives on a GPU is only checked for its length - fit checked its values on
+    the host when it uploaded them, and reading them back would stall every step."""
+    if sample_weight is None:
+        return None
+    if isinstance(sample_weight, torch.Tensor) and sample_weight.device.type != "cpu":
+        if sample_weight.numel() != n:
+            raise ValueError(f"sample_weight holds {sample_weight.numel()} values for {n} samples")
+        w = sample_weight.detach().to(torch.float32).reshape(-1)
+        return w if device is None else w.to(device)
+    w = np.asarray(sample_weight.detach().numpy() if isinstance(sample_weight, torch.Tensor) else sample_weight)
+    if w.dtype == object or not (np.issubdtype(w.dtype, np.number) or w.dtype == bool):
+        raise ValueError("sample_weight must be numeric")
+    if w.size != n or (w.ndim > 1 and w.shape[0] != n):
+        raise ValueError(f"sample_weight holds {w.size} values for {n} samples")
+    w = w.astype(np.float32).reshape(-1)
+    if not np.all(np.isfinite(w)):
+        raise ValueError("sample_weight must be finite (no NaN, no infinity)")
+    if np.any(w < 0):
+        raise ValueError("sample_weight must not be negative")
+    t = torch.from_numpy(np.ascontiguousarray(w))
+    return t if device is None else t.to(device)
 
 
 def slice_inputs(inputs, idx):
