@@ -984,6 +984,48 @@ int impnn_adam_clipnorm_step(const void* var_table, const int64_t* sizes, int32_
 int impnn_adam_clipnorm_step_counted(const void* var_table, const int64_t* sizes, int32_t n_vars,
                                      int64_t* step_counter, float lr, float beta1, float beta2, float eps,
                                      float clipnorm, impnn_stream_t stream);
+/*  The same with the learning rate in DEVICE memory too, plus tf.clip_by_global_norm and keras's decoupled weight
+ *  decay.  lr_record: a caller-owned device record of 32 four-byte words (i32 or f32 as marked), 4-byte aligned:
+ *      word 0   i32  kind: 0 constant, 1 ExponentialDecay, 2 CosineDecay, 3 PiecewiseConstantDecay
+ *      word 1   i32  flags: bit 0 = staircase (ExponentialDecay)
+ *      word 2   f32  lr (constant) / initial_learning_rate
+ *      word 3   f32  decay_rate (ExponentialDecay) / alpha (CosineDecay)
+ *      word 4   i32  decay_steps (> 0)
+ *      word 5   i32  warmup_steps (CosineDecay; 0: no warm-up)
+ *      word 6   f32  CosineDecay: the rate the cosine starts from (warmup_target, or word 2 again without one)
+ *      word 7   i32  PiecewiseConstantDecay: number of boundaries, 0 .. 8
+ *      8..15    i32  boundaries, increasing
+ *      16..24   f32  values: values[i] while s <= boundaries[i], values[count] after the last boundary
+ *      25..31        reserved, 0
+ *  The kernel forms the rate of the update itself: with s = *step_counter - 1 after the increment (the updates
+ *  already applied; keras reads its schedule at `iterations` before the update, the bias correction uses s + 1),
+ *      constant     lr
+ *      exponential  lr0 * decay_rate ^ (s / decay_steps), floor(s / decay_steps) with staircase
+ *      cosine       s < warmup_steps: lr0 + (target - lr0) * s / warmup_steps;  else with s' = s - warmup_steps
+ *                   target * ((1 - alpha) * 0.5 * (1 + cos(pi * min(s', decay_steps) / decay_steps)) + alpha)
+ *      piecewise    as above
+ *  in f32.  The host changes the rate by writing the record on the stream (no argument is frozen into a captured
+ *  graph).  The record is not validated by this entry (it is device memory): impnn_lr_schedule_check validates a
+ *  HOST copy before upload; a kind the kernel does not know gives a NaN rate.
+ *  clipnorm: per variable as above; global_clipnorm > 0: g <- g * c / max(||g||_global, c) over all variables of the
+ *  call (both > 0: IMPNN_E_BADARG).  A launch ahead of the update writes the sum of squares of every (variable,
+ *  slice) into `workspace` (impnn_adam_step_scheduled_workspace_floats(n_vars) floats, needed only with
+ *  global_clipnorm); every workgroup of the update adds them in index order - no float atomics, one scale for all
+ *  elements, the same bits on every run.  An all-zero gradient gives scale 1; a non-finite global norm makes every
+ *  update of that step NaN (w, m, v), as tf.clip_by_global_norm does.
+ *  weight_decay > 0: w <- w - lr_s * weight_decay * w ahead of the Adam update, with the step's rate lr_s, for the
+ *  variables whose word in decay_flags (DEVICE, n_vars i32) is non-zero. */
+int64_t impnn_adam_step_scheduled_workspace_floats(int32_t n_vars);
+int impnn_adam_step_scheduled(const void* var_table, const int64_t* sizes, int32_t n_vars, int64_t* step_counter,
+                              const void* lr_record, float beta1, float beta2, float eps, float clipnorm,
+                              float global_clipnorm, float weight_decay, const int32_t* decay_flags, float* workspace,
+                              int64_t workspace_floats, impnn_stream_t stream);
+/*  Validates a HOST copy of a learning-rate record (32 words): IMPNN_E_UNSUPPORTED for an unknown kind or more than
+ *  8 boundaries, IMPNN_E_BADARG for decay_steps <= 0, a negative decay_rate, boundaries out of order or a
+ *  non-finite value. */
+int impnn_lr_schedule_check(const void* host_record);
+/*  out[i] = the rate the update kernel would use at s = steps[i] (DEVICE pointers; the kernel's own function). */
+int impnn_lr_schedule_eval(const void* lr_record, const int64_t* steps, float* out, int32_t n, impnn_stream_t stream);
 
 /* ---- measurement: HIP-event timing of the dominant kernel (encoder_fused_kernel / encoder_typed_kernel), recorded on the
  *      stream the kernel is launched on.  After impnn_profile_enable(capacity) every

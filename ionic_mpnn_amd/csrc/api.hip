@@ -1673,6 +1673,62 @@ int impnn_adam_clipnorm_step_counted(const void* var_table, const int64_t* sizes
                               as_stream(stream));
 }
 
+int impnn_lr_schedule_check(const void* host_record) {
+  REQUIRE(host_record, "null pointer");
+  int32_t r[kLrWords];
+  std::memcpy(r, host_record, sizeof(r));
+  const auto f = [&](int i) { float x; std::memcpy(&x, &r[i], 4); return x; };
+  const auto finite = [](float x) { return x - x == 0.f; };
+  if (r[kLrKind] < kLrConstant || r[kLrKind] > kLrPiecewise)
+    return fail(IMPNN_E_UNSUPPORTED, "%s: unknown schedule kind %d", __func__, r[kLrKind]);
+  REQUIRE(finite(f(kLrBase)), "the base rate is not finite");
+  if (r[kLrKind] == kLrExponential || r[kLrKind] == kLrCosine) {
+    REQUIRE(r[kLrDecaySteps] > 0, "decay_steps must be > 0");
+    REQUIRE(finite(f(kLrParam)), "decay_rate / alpha is not finite");
+  }
+  if (r[kLrKind] == kLrExponential) REQUIRE(f(kLrParam) >= 0.f, "decay_rate must be >= 0");
+  if (r[kLrKind] == kLrCosine) REQUIRE(r[kLrWarmupSteps] >= 0 && finite(f(kLrTarget)), "bad warm-up");
+  if (r[kLrKind] == kLrPiecewise) {
+    if (r[kLrBoundaryCount] < 0 || r[kLrBoundaryCount] > kLrMaxBoundaries)
+      return fail(IMPNN_E_UNSUPPORTED, "%s: %d boundaries (at most %d)", __func__, r[kLrBoundaryCount], kLrMaxBoundaries);
+    for (int i = 0; i + 1 < r[kLrBoundaryCount]; ++i)
+      REQUIRE(r[kLrBoundaries + i] < r[kLrBoundaries + i + 1], "boundaries must increase");
+    for (int i = 0; i <= r[kLrBoundaryCount]; ++i) REQUIRE(finite(f(kLrValues + i)), "a value is not finite");
+  }
+  return IMPNN_OK;
+}
+
+int impnn_lr_schedule_eval(const void* record, const int64_t* steps, float* out, int32_t n, impnn_stream_t stream) {
+  REQUIRE(n >= 0, "bad count");
+  if (n == 0) return IMPNN_OK;
+  REQUIRE(record && steps && out, "null pointer");
+  REQUIRE((reinterpret_cast<uintptr_t>(record) & 3u) == 0, "the record must be 4-byte aligned");
+  return launch_lr_schedule_eval(record, steps, out, n, as_stream(stream));
+}
+
+int64_t impnn_adam_step_scheduled_workspace_floats(int32_t n_vars) { return adam_scheduled_workspace(n_vars); }
+
+int impnn_adam_step_scheduled(const void* var_table, const int64_t* sizes, int32_t n_vars, int64_t* step_counter,
+                              const void* lr_record, float beta1, float beta2, float eps, float clipnorm,
+                              float global_clipnorm, float weight_decay, const int32_t* decay_flags, float* workspace,
+                              int64_t workspace_floats, impnn_stream_t stream) {
+  REQUIRE(n_vars >= 0, "bad arguments");
+  REQUIRE(!(clipnorm > 0.f && global_clipnorm > 0.f), "clipnorm and global_clipnorm exclude each other");
+  REQUIRE(weight_decay >= 0.f && weight_decay - weight_decay == 0.f, "weight_decay must be finite and >= 0");
+  if (n_vars == 0) return IMPNN_OK;
+  REQUIRE(var_table && sizes && step_counter && lr_record, "null pointer");
+  REQUIRE((reinterpret_cast<uintptr_t>(lr_record) & 3u) == 0, "the record must be 4-byte aligned");
+  REQUIRE(!(weight_decay > 0.f) || decay_flags, "weight_decay without decay_flags");
+  if (global_clipnorm > 0.f) {
+    if (workspace_floats < adam_scheduled_workspace(n_vars))
+      return fail(IMPNN_E_WORKSPACE, "%s: workspace of %lld floats is too small", __func__, (long long)workspace_floats);
+    REQUIRE(workspace, "null workspace");
+  }
+  return launch_adam_scheduled(var_table, sizes, n_vars, step_counter, lr_record, beta1, beta2, eps, clipnorm,
+                               global_clipnorm, weight_decay, weight_decay > 0.f ? decay_flags : nullptr,
+                               workspace, as_stream(stream));
+}
+
 int impnn_batch_assemble(int32_t n_ions, const int32_t* sample_idx, int32_t B, int32_t M,
                          const int32_t* const* atom_flat, const int32_t* const* atom_off,
                          const int32_t* const* edge_flat, const int32_t* const* bond_flat,

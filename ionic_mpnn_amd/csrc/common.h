@@ -448,6 +448,17 @@ int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t
                         float* out, hipStream_t s);
 int launch_adam_clipnorm(const void* table, const void* sizes, int n_vars, int64_t step, int64_t* step_dev, float lr,
                          float b1, float b2, float eps, float clipnorm, hipStream_t s);
+// The learning-rate record of impnn_adam_step_scheduled (include/impnn.h): word indices and schedule kinds.
+enum : int {
+  kLrKind = 0, kLrFlags = 1, kLrBase = 2, kLrParam = 3, kLrDecaySteps = 4, kLrWarmupSteps = 5, kLrTarget = 6,
+  kLrBoundaryCount = 7, kLrBoundaries = 8, kLrValues = 16, kLrWords = 32, kLrMaxBoundaries = 8,
+  kLrConstant = 0, kLrExponential = 1, kLrCosine = 2, kLrPiecewise = 3
+};
+int64_t adam_scheduled_workspace(int n_vars);
+int launch_adam_scheduled(const void* table, const void* sizes, int n_vars, int64_t* step_dev, const void* record,
+                          float b1, float b2, float eps, float clipnorm, float global_clipnorm, float weight_decay,
+                          const int32_t* decay_flags, float* partials, hipStream_t s);
+int launch_lr_schedule_eval(const void* record, const int64_t* steps, float* out, int n, hipStream_t s);
 
 // ---- batch assembly (loader_kernels.hip)
 int launch_batch_assemble(int n_ions, const int32_t* sample_idx, int B, int M, const int32_t* const* atom_flat,

@@ -903,7 +903,10 @@ class MPNNModel:
                 t.grad = None
         if self.kind == "transfer":
             self._bn_training = bool(self.mp_bn_1.trainable)
-        self.optimizer.build([t for _, t in tv])
+        if isinstance(self.optimizer, train.Adam):  # the names are what exclude_from_weight_decay matches
+            self.optimizer.build([t for _, t in tv], names=[n for n, _ in tv])
+        else:
+            self.optimizer.build([t for _, t in tv])
         return self
 
     def regularization_loss(self):
@@ -1042,7 +1045,7 @@ class MPNNModel:
             seed=None, graph=True, sample_weight=None):
         """model.fit as the trainers call it (train_viscosity.py:328-338): per epoch a fresh shuffle,
         mini-batches of ``batch_size``, `loss` = sample-weighted mean of the batch losses, `val_loss` from
-        evaluate(); callbacks see on_train_begin / on_epoch_end / on_train_end.  Returns a History.
+        evaluate(); callbacks see on_train_begin / on_epoch_begin / on_epoch_end / on_train_end.  Returns a History.
         ``graph=True`` (single process): full-size mini-batches replay one captured hipGraph of the whole step
         (train.GraphedTrainStep); the last, smaller batch of an epoch runs eagerly.
         Under torch.distributed every rank passes the FULL (x, y): the shuffle seed is rank 0's (broadcast once), every
@@ -1091,6 +1094,9 @@ class MPNNModel:
         w_dev = None if w_host is None else w_host.to(self.device)  # uploaded once, like y_dev
         val_dev = None
         for epoch in range(int(epochs)):
+            for cb in callbacks:
+                if hasattr(cb, "on_epoch_begin"):
+                    cb.on_epoch_begin(epoch, {})
             order = rng.permutation(n) if shuffle else np.arange(n)
             order_dev = torch.from_numpy(order).to(self.device)  # one upload per epoch
             tot = torch.zeros((), dtype=torch.float64, device=self.device)

@@ -4,7 +4,7 @@ Adam(1e-3, clipnorm=1.0) + MSE (+ the l2(1e-4) penalty of the fingerprint Dense 
 (train_viscosity.py:189,227-230,328-338; train_melting_point.py:173,205-208,300-311).
 
 Forward and backward of the message-passing layers run in libimpnn (ionic_mpnn_amd.autograd); the
-optimizer step of all variables is one launch (impnn_adam_clipnorm_step); the head after GlobalSumPool, the
+optimizer step of all variables is one launch (impnn_adam_step_scheduled); the head after GlobalSumPool, the
 mse and the l2 penalties are one node too (impnn_model_head_loss[_bwd]) - torch.autograd only keeps the graph, no
 torch arithmetic kernel runs in a step.  Multi-GPU: one process per GPU, every rank takes
 its contiguous shard of each mini-batch, and the flat gradient buffer is averaged with ONE all-reduce
@@ -20,15 +20,217 @@ from . import _lib
 from ._lib import check, stream_ptr
 
 
+# ---- learning-rate schedules (keras.optimizers.schedules).  __call__(step) in float64 on the host is the definition;
+# the optimizer kernel evaluates the same formula in float32 from a 32-word device record (include/impnn.h,
+# impnn_adam_step_scheduled), ``step`` being the number of updates already applied.
+LR_RECORD_WORDS, LR_MAX_BOUNDARIES = 32, 8
+LR_CONSTANT, LR_EXPONENTIAL, LR_COSINE, LR_PIECEWISE = 0, 1, 2, 3
+
+
+def _lr_record(kind, lr0, flags=0, param=0.0, decay_steps=0, warmup_steps=0, target=0.0, boundaries=(), values=()):
+    rec = np.zeros(LR_RECORD_WORDS, np.int32)
+    f = rec.view(np.float32)
+    rec[0], rec[1], rec[4], rec[5], rec[7] = kind, flags, decay_steps, warmup_steps, len(boundaries)
+    f[2], f[3], f[6] = lr0, param, target
+    rec[8:8 + len(boundaries)] = boundaries
+    f[16:16 + len(values)] = values
+    return rec
+
+
+def _finite(x, what):
+    x = float(x)
+    if not np.isfinite(x):
+        raise ValueError(f"{what} must be finite, got {x}")
+    return x
+
+
+def _steps(x, what, low):
+    if int(x) != x or not low <= int(x) < 2 ** 31:
+        raise ValueError(f"{what} must be an integer >= {low} (and below 2^31), got {x!r}")
+    return int(x)
+
+
+class LearningRateSchedule:
+    """Base of the schedules: ``__call__(step)`` -> rate (float64), ``get_config`` / ``from_config``, and ``_record()``,
+    the device record of the schedule."""
+
+    def __call__(self, step):
+        raise NotImplementedError
+
+    def get_config(self):
+        raise NotImplementedError
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+class ExponentialDecay(LearningRateSchedule):
+    """keras ExponentialDecay: lr0 * decay_rate ** (step / decay_steps), floor(step / decay_steps) with staircase."""
+
+    def __init__(self, initial_learning_rate, decay_steps, decay_rate, staircase=False, name="ExponentialDecay"):
+        self.initial_learning_rate = _finite(initial_learning_rate, "initial_learning_rate")
+        self.decay_steps = _steps(decay_steps, "decay_steps", 1)
+        self.decay_rate = _finite(decay_rate, "decay_rate")
+        if self.decay_rate < 0.0:
+            raise ValueError(f"decay_rate must be >= 0, got {self.decay_rate}")
+        self.staircase, self.name = bool(staircase), name
+
+    def __call__(self, step):
+        p = float(step) / float(self.decay_steps)
+        return self.initial_learning_rate * self.decay_rate ** (np.floor(p) if self.staircase else p)
+
+    def get_config(self):
+        return {"initial_learning_rate": self.initial_learning_rate, "decay_steps": self.decay_steps,
+                "decay_rate": self.decay_rate, "staircase": self.staircase, "name": self.name}
+
+    def _record(self):
+        return _lr_record(LR_EXPONENTIAL, self.initial_learning_rate, flags=int(self.staircase), param=self.decay_rate,
+                          decay_steps=self.decay_steps)
+
+
+class CosineDecay(LearningRateSchedule):
+    """keras CosineDecay: with ``warmup_target`` a linear warm-up from initial_learning_rate to warmup_target over
+    ``warmup_steps``, then, from ``target`` (warmup_target, or initial_learning_rate without one),
+    target * ((1 - alpha) * 0.5 * (1 + cos(pi * min(step', decay_steps) / decay_steps)) + alpha), step' counted from the
+    end of the warm-up."""
+
+    def __init__(self, initial_learning_rate, decay_steps, alpha=0.0, name="CosineDecay", warmup_target=None,
+                 warmup_steps=0):
+        self.initial_learning_rate = _finite(initial_learning_rate, "initial_learning_rate")
+        self.decay_steps = _steps(decay_steps, "decay_steps", 1)
+        self.alpha, self.name = _finite(alpha, "alpha"), name
+        self.warmup_target = None if warmup_target is None else _finite(warmup_target, "warmup_target")
+        self.warmup_steps = _steps(warmup_steps, "warmup_steps", 0)
+
+    def _warmup(self):
+        return self.warmup_steps if self.warmup_target is not None else 0
+
+    def __call__(self, step):
+        step, warm = float(step), self._warmup()
+        target = self.initial_learning_rate if self.warmup_target is None else self.warmup_target
+        if step < warm:
+            return (target - self.initial_learning_rate) * (step / warm) + self.initial_learning_rate
+        frac = min(step - warm, float(self.decay_steps)) / float(self.decay_steps)
+        return target * ((1.0 - self.alpha) * 0.5 * (1.0 + np.cos(np.pi * frac)) + self.alpha)
+
+    def get_config(self):
+        return {"initial_learning_rate": self.initial_learning_rate, "decay_steps": self.decay_steps,
+                "alpha": self.alpha, "name": self.name, "warmup_target": self.warmup_target,
+                "warmup_steps": self.warmup_steps}
+
+    def _record(self):
+        target = self.initial_learning_rate if self.warmup_target is None else self.warmup_target
+        return _lr_record(LR_COSINE, self.initial_learning_rate, param=self.alpha, decay_steps=self.decay_steps,
+                          warmup_steps=self._warmup(), target=target)
+
+
+class PiecewiseConstantDecay(LearningRateSchedule):
+    """keras PiecewiseConstantDecay: values[i] while step <= boundaries[i], the last value after the last boundary; at
+    most 8 boundaries (the device record holds no more)."""
+
+    def __init__(self, boundaries, values, name="PiecewiseConstant"):
+        self.boundaries = [_steps(b, "a boundary", 0) for b in boundaries]
+        self.values = [_finite(v, "a value") for v in values]
+        self.name = name
+        if len(self.values) != len(self.boundaries) + 1:
+            raise ValueError("values must have one element more than boundaries")
+        if len(self.boundaries) > LR_MAX_BOUNDARIES:
+            raise ValueError(f"at most {LR_MAX_BOUNDARIES} boundaries, got {len(self.boundaries)}")
+        if any(a >= b for a, b in zip(self.boundaries, self.boundaries[1:])):
+            raise ValueError("boundaries must increase")
+
+    def __call__(self, step):
+        for b, v in zip(self.boundaries, self.values):
+            if step <= b:
+                return v
+        return self.values[-1]
+
+    def get_config(self):
+        return {"boundaries": list(self.boundaries), "values": list(self.values), "name": self.name}
+
+    def _record(self):
+        return _lr_record(LR_PIECEWISE, self.values[0], boundaries=self.boundaries, values=self.values)
+
+
+_SCHEDULES = {c.__name__: c for c in (ExponentialDecay, CosineDecay, PiecewiseConstantDecay)}
+
+
+def _checked_rate(value):
+    """A learning rate as the optimizer keeps it: a schedule object as it is, anything else as a finite float."""
+    return value if isinstance(value, LearningRateSchedule) else _finite(value, "learning_rate")
+
+
 class Adam:
     """keras.optimizers.Adam(learning_rate, clipnorm): per-variable tf.clip_by_norm, then Adam with
-    epsilon 1e-7 and the bias-corrected step size lr*sqrt(1-b2^t)/(1-b1^t)."""
+    epsilon 1e-7 and the bias-corrected step size lr*sqrt(1-b2^t)/(1-b1^t).
 
-    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None):
-        self.learning_rate, self.beta_1, self.beta_2 = float(learning_rate), float(beta_1), float(beta_2)
-        self.epsilon, self.clipnorm = float(epsilon), (None if clipnorm is None else float(clipnorm))
+    ``learning_rate`` is a float or a schedule (ExponentialDecay, CosineDecay, PiecewiseConstantDecay).  Once built, the
+    rate lives in a small device record that the optimizer kernel reads on every step, so an assignment to
+    ``optimizer.learning_rate`` reaches the next update, also the next replay of a captured step.  ``global_clipnorm``
+    (tf.clip_by_global_norm over all variables; excludes ``clipnorm``; a non-finite global norm makes the whole update
+    NaN, as in TensorFlow) and ``weight_decay`` (keras's decoupled w <- w - lr_t * wd * w ahead of the update; see
+    ``exclude_from_weight_decay``) run in the same launch."""
+
+    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, global_clipnorm=None,
+                 weight_decay=None):
         self._vars = None
         self._step_dev = None
+        self._lr = _checked_rate(learning_rate)
+        self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+        self.epsilon, self.clipnorm = float(epsilon), (None if clipnorm is None else float(clipnorm))
+        self.global_clipnorm = None if global_clipnorm is None else float(global_clipnorm)
+        self.weight_decay = None if weight_decay is None else _finite(weight_decay, "weight_decay")
+        if self.clipnorm is not None and self.global_clipnorm is not None:
+            raise ValueError("clipnorm and global_clipnorm exclude each other")
+        if self.global_clipnorm is not None and not self.global_clipnorm > 0.0:
+            raise ValueError(f"global_clipnorm must be > 0, got {self.global_clipnorm}")
+        if self.weight_decay is not None and self.weight_decay < 0.0:
+            raise ValueError(f"weight_decay must be >= 0, got {self.weight_decay}")
+        self._no_decay = []
+
+    @property
+    def learning_rate(self):
+        """The host copy of the rate: a float, or the schedule object."""
+        return self._lr
+
+    @learning_rate.setter
+    def learning_rate(self, value):
+        value = _checked_rate(value)
+        if self._vars is not None:
+            self._write_record(value)
+        self._lr = value
+
+    def _record(self, rate=None):
+        rate = self._lr if rate is None else rate
+        return rate._record() if isinstance(rate, LearningRateSchedule) else _lr_record(LR_CONSTANT, rate)
+
+    def _write_record(self, rate=None):
+        """The device record <- the host rate: one small copy on the current stream, which the next update (or replay
+        of a captured step) reads.  No recapture, no synchronisation of the device."""
+        rec = self._record(rate)
+        check(_lib.load().impnn_lr_schedule_check(C.c_void_p(rec.ctypes.data)))
+        self._record_dev.copy_(torch.from_numpy(rec))
+
+    def current_learning_rate(self):
+        """The rate the next update will use, as the optimizer kernel's own function computes it from the device record
+        and the device counter (synchronises)."""
+        if self._vars is None:
+            lr = self._lr(0) if isinstance(self._lr, LearningRateSchedule) else self._lr
+            return float(np.float32(lr))
+        out = torch.empty(1, dtype=torch.float32, device=self._record_dev.device)
+        with torch.cuda.device(out.device):
+            check(_lib.load().impnn_lr_schedule_eval(C.c_void_p(self._record_dev.data_ptr()),
+                                                     C.c_void_p(self._step_dev.data_ptr()),
+                                                     C.c_void_p(out.data_ptr()), 1, stream_ptr()))
+        return float(out.item())
+
+    def exclude_from_weight_decay(self, var_names):
+        """Variables whose name (as ``model.trainable_variables()`` gives it) contains one of ``var_names`` do not
+        decay.  Before ``compile`` / ``build`` only."""
+        if self._vars is not None:
+            raise RuntimeError("exclude_from_weight_decay must be called before the optimizer is built")
+        self._no_decay = [str(s) for s in var_names]
 
     @property
     def iterations(self):
@@ -36,14 +238,33 @@ class Adam:
         return int(self._step_dev.item()) if self._step_dev is not None else 0
 
     def get_config(self):
-        return {"name": "Adam", "learning_rate": self.learning_rate, "beta_1": self.beta_1, "beta_2": self.beta_2,
-                "epsilon": self.epsilon, "clipnorm": self.clipnorm}
+        lr = self._lr
+        if isinstance(lr, LearningRateSchedule):
+            lr = {"class_name": type(lr).__name__, "config": lr.get_config()}
+        cfg = {"name": "Adam", "learning_rate": lr, "beta_1": self.beta_1, "beta_2": self.beta_2,
+               "epsilon": self.epsilon, "clipnorm": self.clipnorm}
+        if self.global_clipnorm is not None:
+            cfg["global_clipnorm"] = self.global_clipnorm
+        if self.weight_decay is not None:
+            cfg["weight_decay"] = self.weight_decay
+        return cfg
 
-    def build(self, variables):
+    @classmethod
+    def from_config(cls, config):
+        config = {k: v for k, v in config.items() if k != "name"}
+        lr = config.get("learning_rate")
+        if isinstance(lr, dict):
+            config["learning_rate"] = _SCHEDULES[lr["class_name"]].from_config(lr["config"])
+        return cls(**config)
+
+    def build(self, variables, names=None):
         """variables: list of leaf tensors on one GPU.  Gradients live in ONE flat buffer (views become the
         variables' .grad), so the data-parallel average is a single collective and the kernel's pointer table
-        stays valid for the whole run (also inside a captured hipGraph)."""
+        stays valid for the whole run (also inside a captured hipGraph).  ``names``: the variables' names, which
+        ``exclude_from_weight_decay`` matches."""
         variables = list(variables)
+        if self._no_decay and self.weight_decay is not None and names is None:
+            raise ValueError("exclude_from_weight_decay needs the variables' names: build(variables, names=[...])")
         dev = variables[0].device
         sizes = [int(v.numel()) for v in variables]
         total = sum(sizes)
@@ -62,7 +283,19 @@ class Adam:
         # data_ptr values are < 2^63: store them as int64 bit patterns
         self._table = torch.tensor(table, dtype=torch.int64, device=dev)
         self._sizes = torch.tensor(sizes, dtype=torch.int64, device=dev)
+        self._record_dev = torch.zeros(LR_RECORD_WORDS, dtype=torch.int32, device=dev)
+        self._decay_flags = self._norm_ws = None
+        if self.weight_decay is not None:
+            names = [""] * len(variables) if names is None else list(names)
+            if len(names) != len(variables):
+                raise ValueError("names must have one entry per variable")
+            self._decay_flags = torch.tensor([int(not any(s in n for s in self._no_decay)) for n in names],
+                                             dtype=torch.int32, device=dev)
+        if self.global_clipnorm is not None:
+            need = int(_lib.load().impnn_adam_step_scheduled_workspace_floats(len(variables)))
+            self._norm_ws = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)
         self._vars = variables
+        self._write_record()
 
     def zero_grad(self):
         self.flat_grad.zero_()
@@ -75,7 +308,8 @@ class Adam:
 
     def apply_gradients(self):
         """One launch: clip, moments, update for every variable (gradients are read from the flat buffer);
-        the step counter is advanced on the device, so the call can sit inside a captured graph."""
+        the step counter is advanced on the device and the rate is read from the device record, so the call can sit
+        inside a captured graph.  ``global_clipnorm`` adds one launch ahead of it (the sums of squares)."""
         if self._vars is None:
             raise RuntimeError("Adam.build(variables) has not been called")
         lo, hi = self.flat_grad.data_ptr(), self.flat_grad.data_ptr() + 4 * self.flat_grad.numel()
@@ -85,10 +319,14 @@ class Adam:
                                    "use optimizer.zero_grad() instead of setting .grad = None")
         dev = self.flat_grad.device
         with torch.cuda.device(dev):
-            check(_lib.load().impnn_adam_clipnorm_step_counted(
+            ws = self._norm_ws
+            check(_lib.load().impnn_adam_step_scheduled(
                 C.c_void_p(self._table.data_ptr()), C.c_void_p(self._sizes.data_ptr()), len(self._vars),
-                C.c_void_p(self._step_dev.data_ptr()), self.learning_rate, self.beta_1, self.beta_2, self.epsilon,
-                self.clipnorm if self.clipnorm else 0.0, stream_ptr()))
+                C.c_void_p(self._step_dev.data_ptr()), C.c_void_p(self._record_dev.data_ptr()), self.beta_1,
+                self.beta_2, self.epsilon, self.clipnorm if self.clipnorm else 0.0, self.global_clipnorm or 0.0,
+                self.weight_decay or 0.0,
+                None if self._decay_flags is None else C.c_void_p(self._decay_flags.data_ptr()),
+                None if ws is None else C.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(), stream_ptr()))
 
 
 class GraphedTrainStep:
@@ -231,11 +469,76 @@ class Callback:
     def on_train_begin(self, logs=None):
         pass
 
+    def on_epoch_begin(self, epoch, logs=None):
+        pass
+
     def on_epoch_end(self, epoch, logs=None):
         pass
 
     def on_train_end(self, logs=None):
         pass
+
+
+def _constant_rate(optimizer, who):
+    lr = optimizer.learning_rate
+    if isinstance(lr, LearningRateSchedule):
+        raise ValueError(f"{who} sets a constant learning rate: the optimizer's rate is a {type(lr).__name__} schedule")
+    return float(lr)
+
+
+class ReduceLROnPlateau(Callback):
+    """keras.callbacks.ReduceLROnPlateau with mode "min": when ``monitor`` has not improved by ``min_delta`` for
+    ``patience`` epochs, the rate becomes max(rate * factor, min_lr) and ``cooldown`` epochs pass before the count
+    starts again.  The assignment reaches a captured step's next replay (Adam keeps the rate in device memory).
+    ``self.rates``: [(epoch, rate)] of the rates it set."""
+
+    def __init__(self, monitor="val_loss", factor=0.1, patience=10, min_delta=1e-4, cooldown=0, min_lr=0.0):
+        super().__init__()
+        if float(factor) >= 1.0:
+            raise ValueError("ReduceLROnPlateau does not support a factor >= 1.0")
+        self.monitor, self.factor, self.patience = monitor, float(factor), int(patience)
+        self.min_delta, self.cooldown, self.min_lr = float(min_delta), int(cooldown), float(min_lr)
+        self.best, self.wait, self.cooldown_counter, self.rates = np.inf, 0, 0, []
+
+    def on_train_begin(self, logs=None):
+        self.best, self.wait, self.cooldown_counter, self.rates = np.inf, 0, 0, []
+        _constant_rate(self.model.optimizer, "ReduceLROnPlateau")
+
+    def on_epoch_end(self, epoch, logs=None):
+        cur = (logs or {}).get(self.monitor)
+        if cur is None:
+            return
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.wait = 0
+        if cur < self.best - self.min_delta:
+            self.best, self.wait = cur, 0
+        elif self.cooldown_counter <= 0:
+            self.wait += 1
+            if self.wait >= self.patience:
+                old = _constant_rate(self.model.optimizer, "ReduceLROnPlateau")
+                if old > self.min_lr:
+                    new = max(old * self.factor, self.min_lr)
+                    self.model.optimizer.learning_rate = new
+                    self.rates.append((epoch, new))
+                    self.cooldown_counter, self.wait = self.cooldown, 0
+
+
+class LearningRateScheduler(Callback):
+    """keras.callbacks.LearningRateScheduler: at the start of every epoch the rate becomes ``schedule(epoch, rate)``.
+    ``self.rates``: [(epoch, rate)] of the rates it set."""
+
+    def __init__(self, schedule):
+        super().__init__()
+        self.schedule, self.rates = schedule, []
+
+    def on_train_begin(self, logs=None):
+        self.rates = []
+
+    def on_epoch_begin(self, epoch, logs=None):
+        new = float(self.schedule(epoch, _constant_rate(self.model.optimizer, "LearningRateScheduler")))
+        self.model.optimizer.learning_rate = new
+        self.rates.append((epoch, new))
 
 
 class EarlyStopping(Callback):

@@ -1,7 +1,9 @@
 """Epoch time of model.fit at the reference's batch 32 (train_viscosity.py:328-338) on a device-resident synthetic
 training set: the whole loop (shuffle, batch gather, graphed step, loss bookkeeping), not only the step.
 ``--weighted``: the same with per-sample weights (bootstrap counts): the weighted loss kernels and one more gathered
-tensor in the captured step."""
+tensor in the captured step.  ``--optimizer schedule``: the rate follows a CosineDecay with warm-up that the optimizer
+kernel evaluates from its device record; ``--optimizer global_clipnorm``: tf.clip_by_global_norm in place of the
+per-variable clip (one more launch per step, the sums of squares) under the same schedule."""
 import argparse
 import json
 import sys
@@ -21,10 +23,17 @@ ap.add_argument("--epochs", type=int, default=6)
 ap.add_argument("--atom-dim", type=int, default=32)
 ap.add_argument("--steps", type=int, default=3, help="message-passing steps")
 ap.add_argument("--weighted", action="store_true", help="fit with sample_weight (bootstrap counts)")
+ap.add_argument("--optimizer", choices=("plain", "schedule", "global_clipnorm"), default="plain",
+                help="plain: Adam(1e-3, clipnorm=1.0); schedule: a CosineDecay rate; global_clipnorm: that and a global clip")
 args = ap.parse_args()
 Va, Vb = 124, 72
 m = MM.build_model(Va, Vb, atom_dim=args.atom_dim, num_steps=args.steps, device="cuda")
-m.compile(train.Adam(1e-3, clipnorm=1.0))
+if args.optimizer == "plain":
+    opt = train.Adam(1e-3, clipnorm=1.0)
+else:
+    rate = train.CosineDecay(1e-4, 8 * args.samples // args.batch, alpha=0.1, warmup_target=1e-3, warmup_steps=50)
+    opt = train.Adam(rate, **({"clipnorm": 1.0} if args.optimizer == "schedule" else {"global_clipnorm": 1.0}))
+m.compile(opt)
 x = synthetic.make_batch(args.samples, max_atoms=40, max_edges=80, atom_vocab_size=Va, bond_vocab_size=Vb, seed=0)
 y = np.random.default_rng(0).normal(1.0, 0.5, size=args.samples).astype(np.float32)
 x = m._to_device(x)
@@ -48,5 +57,5 @@ for _ in range(200):
     g.graph.replay()
 torch.cuda.synchronize()
 replay_ms = (time.perf_counter() - t1) / 200 * 1e3
-print(json.dumps({"samples": args.samples, "batch": args.batch, "weighted": args.weighted, "ms_per_epoch": dt * 1e3, "ms_per_step": dt * 1e3 / steps, "ms_per_replay_only": replay_ms,
+print(json.dumps({"samples": args.samples, "batch": args.batch, "weighted": args.weighted, "optimizer": args.optimizer, "ms_per_epoch": dt * 1e3, "ms_per_step": dt * 1e3 / steps, "ms_per_replay_only": replay_ms,
                   "pairs_per_s": args.samples / dt, "loss": h.history["loss"]}))
