@@ -1027,6 +1027,38 @@ int impnn_lr_schedule_check(const void* host_record);
 /*  out[i] = the rate the update kernel would use at s = steps[i] (DEVICE pointers; the kernel's own function). */
 int impnn_lr_schedule_eval(const void* lr_record, const int64_t* steps, float* out, int32_t n, impnn_stream_t stream);
 
+/* ---- regression metrics: segmented sums of (pred, y, sample_weight) in fp64 (csrc/metrics.hip), from which the host
+ *      forms MAE, MSE, RMSE, bias, the maximal error and R^2 (ionic_mpnn_amd.train, compile(metrics=...)).
+ *  The n samples are cut into n_seg segments: segment s holds the samples b = order[k] for
+ *  seg_offsets[s] <= k < seg_offsets[s + 1] (seg_offsets: DEVICE, n_seg + 1 ascending values in [0, n]; NULL with
+ *  n_seg == 1 is the one segment [0, n); order: DEVICE, n indices in [0, n), NULL is the identity).  Per sample, every
+ *  operation in fp64 on the converted float32 values,
+ *      e = scale * (pred[b] - y[b]),  yr = offset + scale * y[b],  w = sample_weight[b]  (NULL: w = 1)
+ *  (offset and scale carry a standardised target back to its unit), and a segment's record of
+ *  impnn_regression_sums_words() = 8 doubles is
+ *      0  the number of samples         4  sum w * (e * e)
+ *      1  sum w                         5  sum w * yr
+ *      2  sum w * e                     6  sum w * (yr * yr)
+ *      3  sum w * |e|                   7  max |e| over the samples with w > 0: NaN if one of those e is NaN, 0 for an
+ *                                          empty segment
+ *  sums: DEVICE, n_seg x 8 doubles.  accumulate == 0 overwrites them; accumulate != 0 adds words 0..6 to what they hold
+ *  and word 7 takes the maximum (a NaN stays): one thread per word does the read-modify-write, calls are ordered by
+ *  the stream, no atomic.  An empty segment writes, or adds, zeros.
+ *  Order of the additions: a thread adds its elements in index order, then lanes, waves by a fixed tree; a segment
+ *  belongs to one wave (n / n_seg <= 512) or one workgroup, a single segment to one wave (n <= 64) or one workgroup
+ *  of 256 (n <= 16384) or 1024 threads - correct at any n, fast where a training step or a table of short segments
+ *  needs it.  The path follows (n, n_seg) alone, never the data: the same call gives the same bits.  No product is
+ *  contracted into an addition, so every term is the double the host reference forms.  No workspace, no allocation,
+ *  no synchronisation.  A position or an index outside [0, n) is not read (the result is then unspecified).
+ *  Status codes, in this order: IMPNN_E_BADARG for n < 0, n_seg < 1, a null pred / y / sums, a null seg_offsets with
+ *  n_seg > 1, a misaligned pointer (4 bytes: pred, y, sample_weight, order; 8 bytes: seg_offsets, sums), a scale that
+ *  is zero or not finite, an offset that is not finite, order with n >= 2^31; then n == 0 with one segment is
+ *  IMPNN_OK (nothing is launched under accumulate, the record is zeroed otherwise).  No IMPNN_E_UNSUPPORTED case. */
+int64_t impnn_regression_sums_words(void);
+int impnn_regression_sums(const float* pred, const float* y, const float* sample_weight, const int32_t* order,
+                          const int64_t* seg_offsets, int64_t n, int32_t n_seg, double offset, double scale,
+                          int32_t accumulate, double* sums, impnn_stream_t stream);
+
 /* ---- measurement: HIP-event timing of the dominant kernel (encoder_fused_kernel / encoder_typed_kernel), recorded on the
  *      stream the kernel is launched on.  After impnn_profile_enable(capacity) every
  *      impnn_encoder_fused call of this thread records one (start, stop) event pair around that

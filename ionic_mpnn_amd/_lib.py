@@ -164,6 +164,8 @@ SIGNATURES = {
     "impnn_adam_step_scheduled": (C.c_int, [vp, vp, i32, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, i64, vp]),
     "impnn_lr_schedule_check": (C.c_int, [vp]),
     "impnn_lr_schedule_eval": (C.c_int, [vp, vp, vp, i32, vp]),
+    "impnn_regression_sums_words": (i64, []),
+    "impnn_regression_sums": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, i32, vp, vp]),
     "impnn_batch_assemble": (C.c_int, [i32, vp, i32, i32, PP, PP, PP, PP, PP, i32, i32, i32, PP, PP, PP, vp, vp, vp]),
     "impnn_gather_rows": (C.c_int, [i32, PP, PP, C.POINTER(i64), vp, i32, vp]),
     "impnn_validate_indices": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

@@ -425,11 +425,14 @@ class ModelHead(torch.autograd.Function):
 
 class WeightedL2(tuple):
     """ModelHeadLoss's ``l2`` argument with the batch's per-sample weights attached: the lambdas as a tuple, the
-    weights (a (B) float32 device tensor) as ``.sample_weight``.  A plain sequence of lambdas is the unweighted loss."""
+    weights (a (B) float32 device tensor, or None) as ``.sample_weight``.  A plain sequence of lambdas is the unweighted
+    loss.  ``pred``: a persistent (B) float32 device buffer that the loss kernel fills with the pass's predictions (the
+    metrics of compile(metrics=...) read it); None, as from a plain sequence, passes the null pointer."""
 
-    def __new__(cls, l2, sample_weight):
+    def __new__(cls, l2, sample_weight, pred=None):
         self = super().__new__(cls, l2)
         self.sample_weight = sample_weight
+        self.pred = pred
         return self
 
 
@@ -441,6 +444,15 @@ def _sample_weight(w, B, device):
     if w.numel() != B or w.device != device:
         raise ValueError("sample_weight must hold one value per sample, on the batch's device")
     return w
+
+
+def _pred_buffer(pred, B, device):
+    """The predictions' buffer a loss node hands to the library: contiguous float32 (B) on the node's device, or None."""
+    if pred is None:
+        return None
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.numel() != B or pred.device != device:
+        raise ValueError("pred must be a contiguous float32 buffer of one value per sample, on the batch's device")
+    return pred
 
 
 class ModelHeadLoss(torch.autograd.Function):
@@ -459,6 +471,8 @@ class ModelHeadLoss(torch.autograd.Function):
         if y.numel() != B or (T is not None and T.numel() != B):
             raise ValueError("y / temperature must hold one value per sample")
         sw = _sample_weight(getattr(l2, "sample_weight", None), B, pooled_cat.device)
+        pred = _pred_buffer(getattr(l2, "pred", None), B, pooled_cat.device)
+        pp = None if pred is None else ptr(pred)
         lib = _lib.load()
         if workspace.numel() < lib.impnn_model_head_loss_workspace_floats(B):
             raise ValueError("loss workspace too small")
@@ -467,11 +481,11 @@ class ModelHeadLoss(torch.autograd.Function):
         table = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
         if sw is None:
             _lib_call(pooled_cat.device, lib.impnn_model_head_loss, kind, ptr(pooled_cat), ptr(pooled_an),
-                      ptr(T) if T is not None else None, table, lam, ptr(y), None, ptr(loss), ptr(workspace),
+                      ptr(T) if T is not None else None, table, lam, ptr(y), pp, ptr(loss), ptr(workspace),
                       workspace.numel(), B, D, fp_size, mixing_size)
         else:
             _lib_call(pooled_cat.device, lib.impnn_weighted_model_head_loss, kind, ptr(pooled_cat), ptr(pooled_an),
-                      ptr(T) if T is not None else None, table, lam, ptr(y), ptr(sw), None, ptr(loss), ptr(workspace),
+                      ptr(T) if T is not None else None, table, lam, ptr(y), ptr(sw), pp, ptr(loss), ptr(workspace),
                       workspace.numel(), B, D, fp_size, mixing_size)
         ctx.save_for_backward(pooled_cat, pooled_an, y, *(() if T is None else (T,)), *weights)
         ctx.meta = (kind, fp_size, mixing_size, tuple(float(v) for v in l2), weights)
@@ -512,7 +526,8 @@ class TransferHeadLoss(torch.autograd.Function):
     (impnn_transfer_head_loss[_bwd]).  ``cfg``: MPNNModel._transfer_cfg (widths, l2, the moving statistics, which
     the forward moves in place when cfg["bn_batch"], the pass's ops.Dropout or None, the loss, and optionally
     cfg["sample_weight"]: (B) per-sample weights, which select impnn_weighted_transfer_head_loss[_bwd] and get no
-    gradient); ``workspace``: a persistent float tensor whose first word is zero.  The backward adds the gradients of the tensors that ask for one
+    gradient, and cfg["pred"]: a (B) float32 buffer the forward fills with the pass's predictions);
+    ``workspace``: a persistent float tensor whose first word is zero.  The backward adds the gradients of the tensors that ask for one
     into their sinks and leaves the frozen ones alone; it writes the pooled vectors' gradients only when they ask."""
 
     @staticmethod
@@ -523,6 +538,7 @@ class TransferHeadLoss(torch.autograd.Function):
         if y.numel() != B:
             raise ValueError("y must hold one value per sample")
         sw = _sample_weight(cfg.get("sample_weight"), B, pooled_cat.device)
+        pred = _pred_buffer(cfg.get("pred"), B, pooled_cat.device)
         lib = _lib.load()
         F, Mx = cfg["fp_size"], cfg["mixing_size"]
         keep = any(ctx.needs_input_grad) or cfg["bn_batch"]
@@ -537,7 +553,8 @@ class TransferHeadLoss(torch.autograd.Function):
         _lib_call(pooled_cat.device, entry, ptr(pooled_cat), ptr(pooled_an), table, lam,
                   ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]), cfg["momentum"], cfg["epsilon"],
                   1 if cfg["bn_batch"] else 0, ptr(y), *(() if sw is None else (ptr(sw),)), cfg["loss_kind"],
-                  cfg["delta"], *dargs, ptr(saved) if keep else None, n_saved, None, ptr(loss), ptr(workspace),
+                  cfg["delta"], *dargs, ptr(saved) if keep else None, n_saved, None if pred is None else ptr(pred),
+                  ptr(loss), ptr(workspace),
                   workspace.numel(), B, D, F, Mx)
         ctx.save_for_backward(pooled_cat, pooled_an, y, *weights)
         ctx.meta = (cfg, saved, dargs, weights)

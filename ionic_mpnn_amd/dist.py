@@ -11,6 +11,7 @@ are replicated.  Two optional epilogue collectives exist for callers that want t
   * all_reduce_loss_stats   - sum of squared error + sample count (2 scalars) for the MSE.
   * shard_loss_weight / all_reduce_flat_gradients_ - data-parallel training: loss weight of a shard and the
     single all-reduce of the flat gradient buffer (ionic_mpnn_amd.train).
+  * all_reduce_metric_sums_ - the regression-sum records of compile(metrics=...), once per epoch beside the loss.
 
 Payloads are <= ~1 MB/rank (B=65536, D=32), i.e. latency-bound on xGMI's point-to-point links; one
 fused buffer per call, RCCL picks its direct algorithms at this size.
@@ -113,6 +114,25 @@ def all_reduce_flat_gradients_(flat, group=None):
     if is_distributed():
         dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
     return flat
+
+
+def all_reduce_metric_sums_(record, group=None):
+    """The regression-sum records (..., 8) float64 (train.regression_sums_reference) of every rank's shard -> the record
+    of all samples, in place on every rank: words 0 to 6 are sums, word 7 (max |e|) takes the maximum and stays NaN
+    where any rank holds a NaN.  An empty shard contributes its zeros.  Through a CPU copy under gloo, as fit's loss."""
+    if not is_distributed():
+        return record
+    on_device = dist.get_backend(group) == "nccl"
+    r = record if on_device else record.detach().cpu()
+    nan = torch.isnan(r[..., 7])
+    sums = torch.cat([r[..., :7], nan.to(r.dtype).unsqueeze(-1)], dim=-1).contiguous()
+    peak = torch.where(nan, torch.zeros_like(r[..., 7]), r[..., 7]).contiguous()
+    dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(peak, op=dist.ReduceOp.MAX, group=group)
+    peak = torch.where(sums[..., 7] > 0, torch.full_like(peak, float("nan")), peak)
+    with torch.no_grad():
+        record.copy_(torch.cat([sums[..., :7], peak.unsqueeze(-1)], dim=-1))
+    return record
 
 
 class ShardedForward:

@@ -883,18 +883,24 @@ class MPNNModel:
         fixed order of ``variables()``."""
         return [(n, w) for n, w, lyr in self._owned_tensors() if lyr.trainable]
 
-    def compile(self, optimizer=None, loss="mse"):
+    def compile(self, optimizer=None, loss="mse", metrics=None, weighted_metrics=None):
         """model.compile(optimizer=Adam(1e-3, clipnorm=1.0), loss="mse") (train_viscosity.py:227-230) or
         loss=Huber(delta=1.0) / "huber" (train_melting_point_transfer.py:193-196).  Reads every ``layer.trainable``
         as Keras does: the optimizer (a fresh state per compile) holds the trainable variables only, the frozen ones
-        ask for no gradient and no training step changes them; a flag changed later counts from the next compile."""
+        ask for no gradient and no training step changes them; a flag changed later counts from the next compile.
+        ``metrics`` / ``weighted_metrics``: names ("mae", "mse", "rmse", "bias", "max_error", "r2") or train.Metric
+        objects.  ``metrics`` ignore ``sample_weight`` and are logged as ``<name>``, ``weighted_metrics`` use it and are
+        logged as ``weighted_<name>`` (``val_`` in front for the validation set); fit and evaluate add them up on the
+        device (train.MetricSet).  With neither, fit, evaluate and the captured step are what they are without."""
         from . import train
         if not (loss in ("mse", "huber") or isinstance(loss, train.Huber)):
             raise ValueError("loss must be 'mse', 'huber' or a train.Huber object")
+        metric_set = train.MetricSet(metrics, weighted_metrics)  # an unknown name raises before anything is touched
         tv = self.trainable_variables()
         if not tv:
             raise ValueError("no trainable variable: every layer of the model is frozen")
         self.loss = loss
+        self._metric_set = metric_set if len(metric_set) else None
         self.optimizer = optimizer if optimizer is not None else train.Adam(1e-3, clipnorm=1.0)
         names = {n for n, _ in tv}
         for n, t in self._named_tensors().items():
@@ -924,16 +930,38 @@ class MPNNModel:
             return lam + [0.0] * 10
         return lam + ([0.0, 0.0] if self.kind == "viscosity" else [self.fp_l2, 0.0, 0.0, 0.0])
 
-    def _loss(self, inputs, y, training, sample_weight=None):
+    def _metric_pred(self, B):
+        """The first B floats of the persistent buffer a fused loss kernel writes its predictions to."""
+        buf = getattr(self, "_metric_pred_buf", None)
+        if buf is None or buf.numel() < B:
+            if buf is not None:  # a captured step may hold its address: a buffer that was outgrown is kept, not freed
+                self._metric_pred_kept = getattr(self, "_metric_pred_kept", []) + [buf]
+            buf = self._metric_pred_buf = torch.zeros(max(B, 4096), dtype=torch.float32, device=self.device)
+        return buf[:B]
+
+    def _loss(self, inputs, y, training, sample_weight=None, metric_slot=None):
         """The batch loss.  ``sample_weight`` (one finite value >= 0 per sample, or None) makes it keras's weighted
         loss, (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too; it touches the loss only, never
-        BatchNormalization's statistics or a dropout mask."""
+        BatchNormalization's statistics or a dropout mask.  ``metric_slot`` ("train" / "eval"; a model compiled with
+        metrics): the pass's predictions are kept and added to that slot's records behind the loss, one
+        impnn_regression_sums launch per record; None leaves every call as it is without metrics."""
         from . import train
         y = torch.as_tensor(y, dtype=torch.float32).to(self.device).reshape(-1, 1)
         sw = train.checked_sample_weight(sample_weight, int(y.shape[0]), self.device)
+        ms = getattr(self, "_metric_set", None) if metric_slot is not None else None
+        if ms is None or y.shape[0] == 0:
+            return self._loss_and_pred(inputs, y, training, sw, False)[0]
+        loss, pred = self._loss_and_pred(inputs, y, training, sw, True)
+        ms.accumulate(metric_slot, pred.detach().to(torch.float32).reshape(-1).contiguous(), y.reshape(-1), sw)
+        return loss
+
+    def _loss_and_pred(self, inputs, y, training, sw, keep_pred):
+        """(loss, predictions or None) of _loss; ``keep_pred`` hands the fused loss kernels a buffer for them."""
+        from . import train
         covered = y.shape[0] > 0 and self._head_kernels_cover()
+        pbuf = self._metric_pred(int(y.shape[0])) if keep_pred else None
         if self.kind == "transfer" and covered:
-            return self._transfer_loss(self._to_device(inputs), y, training, sw)
+            return self._transfer_loss(self._to_device(inputs), y, training, sw, pbuf), pbuf
         if training and torch.is_grad_enabled() and covered and self._head_nodes_cover() and self._loss_name() == "mse":
             # head, mse and the l2 penalties as ONE node (impnn_model_head_loss): ~25 launches fewer per step
             from . import autograd
@@ -944,18 +972,18 @@ class MPNNModel:
                 ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
             pc, pa = self.encode_pooled(inputs, fused=False, training=True)
             T = inputs.get("temperature") if self.kind == "viscosity" else None
-            l2 = self._head_l2() if sw is None else autograd.WeightedL2(self._head_l2(), sw)
+            l2 = self._head_l2() if sw is None and pbuf is None else autograd.WeightedL2(self._head_l2(), sw, pbuf)
             return autograd.ModelHeadLoss.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
-                                                self.mixing_size, l2, ws, pc, pa, T, y, *self._head_tensors())
+                                                self.mixing_size, l2, ws, pc, pa, T, y, *self._head_tensors()), pbuf
         pred = self(inputs, training=True) if training else self(inputs)
         fn = train.mse if self._loss_name() == "mse" else train.Huber(self._loss_delta())
         if sw is not None:
             unweighted = fn
             fn = lambda y_true, y_pred: unweighted(y_true, y_pred, sw)
         if training:
-            return fn(y, pred) + self.regularization_loss()
+            return fn(y, pred) + self.regularization_loss(), pred
         with torch.no_grad():
-            return fn(y, pred) + self.regularization_loss()
+            return fn(y, pred) + self.regularization_loss(), pred
 
     def _overflow_check(self, inputs):
         """True where the fused encoder would end with its host-side overflow check (N > 256 or E > 255: a molecule
@@ -965,7 +993,7 @@ class MPNNModel:
         mode = self.resolve_encoder_mode(N, E)
         return mode is not None and ops.encoder_overflow_possible(N, E, self.atom_dim, mode)
 
-    def _transfer_loss(self, inputs, y, training, sample_weight=None):
+    def _transfer_loss(self, inputs, y, training, sample_weight=None, pred=None):
         """The transfer model's loss as one node (impnn_transfer_head_loss[_bwd], the weighted entries with a
         ``sample_weight``).  An encoder with nothing to train
         computes the pooled vectors as inference does - fused encoder where the shape allows, no graph, nothing saved -
@@ -991,16 +1019,19 @@ class MPNNModel:
             cfg = self._transfer_cfg(training, ds)
             if sample_weight is not None:
                 cfg = dict(cfg, sample_weight=sample_weight)
+            if pred is not None:  # the head kernel writes the pass's predictions there (the metrics read them)
+                cfg = dict(cfg, pred=pred)
             return autograd.TransferHeadLoss.apply(cfg, ws, pc, pa, y, *self._head_tensors())
 
-    def train_on_batch(self, inputs, y, sample_weight=None, group=None, n_global=None):
+    def train_on_batch(self, inputs, y, sample_weight=None, group=None, n_global=None, metric_slot=None):
         """One optimizer step on one mini-batch -> the batch loss (MSE + penalties) as a 0-d tensor.
         ``sample_weight``: one finite value >= 0 per sample (of this rank's shard): the loss is keras's
         (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too.
         With torch.distributed initialised (or ``group`` given) every rank calls this with its shard of
         the global mini-batch: the gradients are averaged over ranks (weighted by shard size) with one
         all-reduce of the flat gradient buffer, then every rank applies the same step.  ``n_global``: size of the
-        global mini-batch when the caller knows it (fit does) - saves the blocking all-reduce that counts it."""
+        global mini-batch when the caller knows it (fit does) - saves the blocking all-reduce that counts it.
+        ``metric_slot``: fit passes "train" for a model compiled with metrics (see _loss)."""
         from . import dist as idist
         if getattr(self, "optimizer", None) is None:
             self.compile()
@@ -1009,7 +1040,8 @@ class MPNNModel:
         if sample_weight is not None and not n_local:
             from . import train
             train.checked_sample_weight(sample_weight, 0)
-        loss = self._loss(inputs, y, training=True, sample_weight=sample_weight) if n_local else None
+        kw = {} if metric_slot is None else {"metric_slot": metric_slot}
+        loss = self._loss(inputs, y, training=True, sample_weight=sample_weight, **kw) if n_local else None
         if idist.is_distributed():
             if n_global is not None:
                 weight = float(n_local) / float(n_global) if n_global > 0 else 0.0
@@ -1027,19 +1059,32 @@ class MPNNModel:
         self.weights_updated()
         return loss.detach() if loss is not None else torch.zeros((), device=opt.flat_grad.device)
 
-    def evaluate(self, inputs, y, batch_size=32, sample_weight=None):
+    def evaluate(self, inputs, y, batch_size=32, sample_weight=None, return_dict=False):
         """model.evaluate: sample-count-weighted mean of the batch losses (MSE + penalties); with ``sample_weight`` a
-        batch loss is the weighted one, (1/B) sum_b w_b L_b + penalties."""
+        batch loss is the weighted one, (1/B) sum_b w_b L_b + penalties.  A model compiled with metrics returns
+        ``[loss, *metrics]`` in compile order (``return_dict``: {"loss": ..., "<name>": ...}): every batch's inference
+        predictions are added to the device records behind its loss, and the records come back with the loss sum in
+        the one synchronisation."""
         from . import train
         n = len(inputs["cat_atom"])
         sw = train.checked_sample_weight(sample_weight, n, self.device)
+        ms = getattr(self, "_metric_set", None)
+        kw = {}
+        if ms is not None:
+            records = ms.buffer("eval", self.device).zero_()
+            kw = {"metric_slot": "eval"}
         tot = torch.zeros((), dtype=torch.float64, device=self.device)
         for lo in range(0, n, batch_size):
             sl = slice(lo, min(n, lo + batch_size))
             loss = self._loss({k: v[sl] for k, v in inputs.items()}, y[sl], training=False,
-                              sample_weight=None if sw is None else sw[sl])
+                              sample_weight=None if sw is None else sw[sl], **kw)
             tot.add_(loss, alpha=sl.stop - sl.start)  # summed on the device: one host sync per evaluate()
-        return float(tot) / max(n, 1)
+        if ms is None:
+            loss = float(tot) / max(n, 1)
+            return {"loss": loss} if return_dict else loss
+        host = torch.cat([tot.reshape(1), records.reshape(-1)]).cpu().numpy()
+        out = {"loss": float(host[0]) / max(n, 1), **ms.results(host[1:])}
+        return out if return_dict else list(out.values())
 
     def fit(self, x, y, validation_data=None, epochs=1, batch_size=32, callbacks=None, shuffle=True, verbose=0,
             seed=None, graph=True, sample_weight=None):
@@ -1053,7 +1098,10 @@ class MPNNModel:
         with the same sample order, and the reported loss is the global sample-weighted mean.
         ``sample_weight``: one finite value >= 0 per training sample (data.balanced_weights, data.bootstrap_weights):
         every batch loss becomes (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too; the weights
-        are uploaded once and cut like y.  ``validation_data`` may be ``(x, y)`` or ``(x, y, sample_weight)``."""
+        are uploaded once and cut like y.  ``validation_data`` may be ``(x, y)`` or ``(x, y, sample_weight)``.
+        A model compiled with metrics logs them too: the training ones are keras's running metrics, added up on the
+        device from every step's training-pass predictions (inside the captured step) and read with the loss at the
+        end of the epoch; the validation ones come from evaluate() as ``val_<name>``."""
         from . import train
         if getattr(self, "optimizer", None) is None:
             self.compile()
@@ -1093,6 +1141,8 @@ class MPNNModel:
         y_dev = torch.from_numpy(y).to(self.device).reshape(-1, 1)
         w_dev = None if w_host is None else w_host.to(self.device)  # uploaded once, like y_dev
         val_dev = None
+        ms = getattr(self, "_metric_set", None)
+        mkw = {} if ms is None else {"metric_slot": "train"}
         for epoch in range(int(epochs)):
             for cb in callbacks:
                 if hasattr(cb, "on_epoch_begin"):
@@ -1100,6 +1150,8 @@ class MPNNModel:
             order = rng.permutation(n) if shuffle else np.arange(n)
             order_dev = torch.from_numpy(order).to(self.device)  # one upload per epoch
             tot = torch.zeros((), dtype=torch.float64, device=self.device)
+            if ms is not None:  # the epoch's running records: zeroed on the stream, outside any graph
+                records = ms.buffer("train", self.device).zero_()
             for lo in range(0, n, batch_size):
                 idx = order[lo:lo + batch_size]
                 tidx = order_dev[lo:lo + batch_size]
@@ -1118,12 +1170,12 @@ class MPNNModel:
                     s0, s1 = shard_bounds(len(idx), world, rank)
                     sidx = tidx[s0:s1]
                     loss = self.train_on_batch({k: v[sidx] for k, v in x.items()}, y_dev[sidx],
-                                               None if w_dev is None else w_dev[sidx], n_global=len(idx))
+                                               None if w_dev is None else w_dev[sidx], n_global=len(idx), **mkw)
                     tot.add_(loss, alpha=s1 - s0)  # shard means, weighted by shard size; summed over ranks below
                     continue
                 else:
                     loss = self.train_on_batch({k: v[tidx] for k, v in x.items()}, y_dev[tidx],
-                                               None if w_dev is None else w_dev[tidx])
+                                               None if w_dev is None else w_dev[tidx], **mkw)
                 tot.add_(loss, alpha=len(idx))
             if distributed:  # every rank summed its shards' losses: one all-reduce per epoch for the logged mean
                 if tdist.get_backend() == "nccl":
@@ -1132,14 +1184,24 @@ class MPNNModel:
                     t_cpu = tot.cpu()
                     tdist.all_reduce(t_cpu)
                     tot = t_cpu.to(self.device)
-            logs = {"loss": float(tot) / max(n, 1)}
+                if ms is not None:
+                    idist.all_reduce_metric_sums_(records)
+            if ms is None:
+                logs = {"loss": float(tot) / max(n, 1)}
+            else:  # the records come back with the loss sum: still one synchronisation per epoch
+                host = torch.cat([tot.reshape(1), records.reshape(-1)]).cpu().numpy()
+                logs = {"loss": float(host[0]) / max(n, 1), **ms.results(host[1:])}
             if validation_data is not None:
                 if val_dev is None:  # uploaded once, not per epoch
                     val_dev = (self._to_device(validation_data[0]),
                                torch.from_numpy(np.asarray(validation_data[1], np.float32)).to(self.device),
                                None if val_w_host is None else val_w_host.to(self.device))
                 # the sample-weighted mean does not depend on how the set is cut: large forward-only batches
-                logs["val_loss"] = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096), val_dev[2])
+                if ms is None:
+                    logs["val_loss"] = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096), val_dev[2])
+                else:
+                    val = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096), val_dev[2], return_dict=True)
+                    logs.update({"val_" + k: v for k, v in val.items()})
             hist._log(epoch, logs)
             if verbose:
                 print(f"Epoch {epoch + 1}/{epochs} - " + " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()), flush=True)
@@ -1153,6 +1215,24 @@ class MPNNModel:
                 cb.on_train_end({})
         self.history = hist
         return hist
+
+    def error_table(self, x, y, groups, sample_weight=None, batch_size=4096, scale=1.0, offset=0.0):
+        """Per-group errors of the model on (x, y) -> data.ErrorTable(group, count, weight, bias, mae, rmse,
+        max_error), one row per distinct id of ``groups`` (an ion pair's ``pair_id``) in np.unique order;
+        ``.worst(k, by="mae")`` names the groups the model gets worst.  The predictions of all batches stay in one
+        device buffer, one segmented launch reduces them (data.error_table_on_device), and only the (G, 8) records reach
+        the host.  ``scale`` / ``offset`` report in the target's unit.  data.error_table is the host reference."""
+        from . import train
+        n = len(x["cat_atom"])
+        y_dev = torch.as_tensor(np.asarray(y, np.float32).reshape(-1)).to(self.device)
+        if y_dev.numel() != n:
+            raise ValueError(f"y holds {y_dev.numel()} values for {n} samples")
+        sw = train.checked_sample_weight(sample_weight, n, self.device)
+        pred = torch.empty(n, dtype=torch.float32, device=self.device)
+        for lo in range(0, n, int(batch_size)):
+            hi = min(n, lo + int(batch_size))
+            pred[lo:hi] = self({k: v[lo:hi] for k, v in x.items()}).reshape(-1)
+        return data.error_table_on_device(pred, y_dev, groups, sw, scale, offset)
 
     def predict(self, inputs, batch_size=None, fused=None):
         """model.predict(x) (train_viscosity.py:366): returns a numpy (n,1) array.  The reference's

@@ -727,6 +727,52 @@ def gather_rows(srcs, dsts, rows):
         check(_lib.load().impnn_gather_rows(n, st, dt, bt, ptr(rows), n_rows, stream_ptr()))
 
 
+REGRESSION_SUM_WORDS = 8   # impnn_regression_sums_words()
+
+
+def regression_sums(pred, y, sample_weight=None, order=None, seg_offsets=None, offset=0.0, scale=1.0, out=None,
+                    accumulate=False):
+    """Segmented regression sums (impnn_regression_sums; train.regression_sums_reference is the definition) -> the
+    (n_seg, 8) float64 device tensor of the records: samples, sum w, sum w e, sum w |e|, sum w e^2, sum w yr,
+    sum w yr^2, max |e| over w > 0, with e = scale * (pred - y) and yr = offset + scale * y in fp64.
+
+    ``pred`` / ``y`` / ``sample_weight`` (optional: w = 1): float32, one value per sample.  ``seg_offsets`` (device
+    int64, n_seg + 1 ascending values in [0, n]) cuts the positions 0 .. n-1 into segments, ``order`` (device int32,
+    optional) names the sample at each position; without ``seg_offsets`` all samples are one segment.  ``out``: the
+    records' tensor to write, or with ``accumulate`` to add to (word 7 takes the maximum); stream-ordered, one launch,
+    the same bits at every call."""
+    require_gpu(pred, y, sample_weight, order, seg_offsets, out)
+    for t, what in ((pred, "pred"), (y, "y"), (sample_weight, "sample_weight")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"{what} must be a contiguous float32 tensor")
+    n = pred.numel()
+    if y.numel() != n or (sample_weight is not None and sample_weight.numel() != n):
+        raise ValueError("pred, y and sample_weight must hold one value per sample")
+    if order is not None and (order.dtype != torch.int32 or not order.is_contiguous() or order.numel() != n):
+        raise TypeError("order must be a contiguous int32 tensor of one index per sample")
+    n_seg = 1
+    if seg_offsets is not None:
+        if seg_offsets.dtype != torch.int64 or not seg_offsets.is_contiguous() or seg_offsets.numel() < 2:
+            raise TypeError("seg_offsets must be a contiguous int64 tensor of n_seg + 1 values")
+        n_seg = seg_offsets.numel() - 1
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate adds to the records in `out`")
+        out = torch.empty(n_seg, REGRESSION_SUM_WORDS, dtype=torch.float64, device=pred.device)
+    elif out.dtype != torch.float64 or not out.is_contiguous() or tuple(out.shape) != (n_seg, REGRESSION_SUM_WORDS):
+        raise TypeError(f"out must be a contiguous float64 tensor of shape ({n_seg}, {REGRESSION_SUM_WORDS})")
+    if any(t is not None and t.device != pred.device for t in (y, sample_weight, order, seg_offsets, out)):
+        raise ValueError("regression_sums: all tensors must live on one device")
+    if n == 0:  # (an empty tensor has no address to hand over) every segment is empty: zeros, or nothing to add
+        return out if accumulate else out.zero_()
+    with torch.cuda.device(pred.device):
+        check(_lib.load().impnn_regression_sums(
+            ptr(pred), ptr(y), None if sample_weight is None else ptr(sample_weight),
+            None if order is None else ptr(order), None if seg_offsets is None else ptr(seg_offsets), n, n_seg,
+            float(offset), float(scale), 1 if accumulate else 0, ptr(out), stream_ptr()))
+    return out
+
+
 # the widths every head kernel covers: kHeadMaxX / kHeadMaxDim of csrc/common.h (tests/test_cabi.py holds them equal)
 HEAD_MAX_X = 128    # pooled width (atom_dim)
 HEAD_MAX_DIM = 64   # fp_size, mixing_size

@@ -334,7 +334,9 @@ class GraphedTrainStep:
     (torch.cuda.CUDAGraph) and replayed per mini-batch: the reference trains with batches of 32
     (train_viscosity.py:332), where a step is ~150 small launches and the host, not the GPU, sets the pace.
     Inputs are copied into static buffers; every kernel argument that changes between steps lives in device
-    memory (the Adam step counter, the dropout step counter that the captured snapshot launch advances)."""
+    memory (the Adam step counter, the dropout step counter that the captured snapshot launch advances).  A model
+    compiled with metrics keeps the training pass's predictions in a persistent buffer and the captured step ends
+    with one impnn_regression_sums launch per metric record, adding the batch to the epoch's running record."""
 
     def __init__(self, model, inputs, y, resident=None, sample_weight=None):
         """``resident=(x, y_dev)``: the whole padded training set lives on the device; the captured step then starts
@@ -374,6 +376,9 @@ class GraphedTrainStep:
         saved_o = opt.state()
         ctr = model.dropout_counter()  # the dropout step counter: the warm-up steps advance it, like the Adam state
         saved_c = ctr.clone() if ctr is not None else None
+        # with compiled metrics the step ends with their regression_sums launches, which add to the epoch's records
+        self.metrics = model._metric_set if getattr(model, "_metric_set", None) else None
+        saved_m = self.metrics.buffer("train", dev).clone() if self.metrics else None
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):  # warm-up off the default stream, as graph capture requires
@@ -389,6 +394,8 @@ class GraphedTrainStep:
         opt.load_state(saved_o)
         if ctr is not None:
             ctr.copy_(saved_c)
+        if saved_m is not None:
+            self.metrics.buffer("train", dev).copy_(saved_m)
         opt.zero_grad()
         self._cache_refs = model._cache_refs()  # frozen layers' cached tensors the captured kernels read
         model.weights_updated()
@@ -400,10 +407,11 @@ class GraphedTrainStep:
             ops.gather_rows(self.resident[0], self.resident[1], self.static_rows)
             if self.resident_w is not None:
                 ops.gather_rows(self.resident_w[0], self.resident_w[1], self.static_rows)
+        kw = {"metric_slot": "train"} if self.metrics else {}  # without metrics: the call, and the graph, as ever
         if self.static_w is None:
-            loss = m._loss(self.static_in, self.static_y, training=True)
+            loss = m._loss(self.static_in, self.static_y, training=True, **kw)
         else:
-            loss = m._loss(self.static_in, self.static_y, training=True, sample_weight=self.static_w)
+            loss = m._loss(self.static_in, self.static_y, training=True, sample_weight=self.static_w, **kw)
         loss.backward()
         m.join_training_streams()
         m.optimizer.apply_gradients()
@@ -486,22 +494,42 @@ def _constant_rate(optimizer, who):
     return float(lr)
 
 
+def _monitor_mode(mode, monitor):
+    """keras's ``mode`` of a monitoring callback -> "min" or "max": "auto" is "max" for a monitor whose name ends in
+    ``r2`` (R^2 grows as the model improves) and "min" for every other one (losses and errors)."""
+    if mode not in ("auto", "min", "max"):
+        raise ValueError(f"mode must be 'auto', 'min' or 'max', got {mode!r}")
+    if mode == "auto":
+        return "max" if str(monitor).endswith("r2") else "min"
+    return mode
+
+
 class ReduceLROnPlateau(Callback):
-    """keras.callbacks.ReduceLROnPlateau with mode "min": when ``monitor`` has not improved by ``min_delta`` for
+    """keras.callbacks.ReduceLROnPlateau: when ``monitor`` has not improved by ``min_delta`` for
     ``patience`` epochs, the rate becomes max(rate * factor, min_lr) and ``cooldown`` epochs pass before the count
     starts again.  The assignment reaches a captured step's next replay (Adam keeps the rate in device memory).
-    ``self.rates``: [(epoch, rate)] of the rates it set."""
+    ``mode``: "min" (an improvement is a smaller value), "max" (a larger one: R^2) or "auto" (by the monitor's name,
+    _monitor_mode).  ``self.rates``: [(epoch, rate)] of the rates it set."""
 
-    def __init__(self, monitor="val_loss", factor=0.1, patience=10, min_delta=1e-4, cooldown=0, min_lr=0.0):
+    def __init__(self, monitor="val_loss", factor=0.1, patience=10, min_delta=1e-4, cooldown=0, min_lr=0.0, mode="auto"):
         super().__init__()
         if float(factor) >= 1.0:
             raise ValueError("ReduceLROnPlateau does not support a factor >= 1.0")
         self.monitor, self.factor, self.patience = monitor, float(factor), int(patience)
         self.min_delta, self.cooldown, self.min_lr = float(min_delta), int(cooldown), float(min_lr)
-        self.best, self.wait, self.cooldown_counter, self.rates = np.inf, 0, 0, []
+        self.mode = _monitor_mode(mode, monitor)
+        self.best, self.wait, self.cooldown_counter, self.rates = self._worst(), 0, 0, []
+
+    def _worst(self):
+        return np.inf if self.mode == "min" else -np.inf
+
+    def _improved(self, cur):
+        if self.mode == "min":
+            return cur < self.best - self.min_delta
+        return cur > self.best + self.min_delta
 
     def on_train_begin(self, logs=None):
-        self.best, self.wait, self.cooldown_counter, self.rates = np.inf, 0, 0, []
+        self.best, self.wait, self.cooldown_counter, self.rates = self._worst(), 0, 0, []
         _constant_rate(self.model.optimizer, "ReduceLROnPlateau")
 
     def on_epoch_end(self, epoch, logs=None):
@@ -511,7 +539,7 @@ class ReduceLROnPlateau(Callback):
         if self.cooldown_counter > 0:
             self.cooldown_counter -= 1
             self.wait = 0
-        if cur < self.best - self.min_delta:
+        if self._improved(cur):
             self.best, self.wait = cur, 0
         elif self.cooldown_counter <= 0:
             self.wait += 1
@@ -542,17 +570,24 @@ class LearningRateScheduler(Callback):
 
 
 class EarlyStopping(Callback):
-    """keras.callbacks.EarlyStopping(monitor, patience, restore_best_weights) with mode "min"
-    (train_viscosity.py:334)."""
+    """keras.callbacks.EarlyStopping(monitor, patience, restore_best_weights) (train_viscosity.py:334).  ``mode``:
+    "min", "max" (the best epoch is the one of the largest value: ``monitor="val_r2"``) or "auto" (_monitor_mode)."""
 
-    def __init__(self, monitor="val_loss", patience=0, restore_best_weights=False, min_delta=0.0):
+    def __init__(self, monitor="val_loss", patience=0, restore_best_weights=False, min_delta=0.0, mode="auto"):
         super().__init__()
         self.monitor, self.patience, self.restore_best_weights = monitor, int(patience), bool(restore_best_weights)
         self.min_delta = abs(float(min_delta))
-        self.best, self.wait, self.best_weights, self.stopped_epoch, self.best_epoch = np.inf, 0, None, 0, 0
+        self.mode = _monitor_mode(mode, monitor)
+        self.on_train_begin()
+
+    def _improved(self, cur):
+        if self.mode == "min":
+            return cur < self.best - self.min_delta
+        return cur > self.best + self.min_delta
 
     def on_train_begin(self, logs=None):
-        self.best, self.wait, self.best_weights, self.stopped_epoch, self.best_epoch = np.inf, 0, None, 0, 0
+        worst = np.inf if self.mode == "min" else -np.inf
+        self.best, self.wait, self.best_weights, self.stopped_epoch, self.best_epoch = worst, 0, None, 0, 0
 
     def on_epoch_end(self, epoch, logs=None):
         cur = (logs or {}).get(self.monitor)
@@ -561,7 +596,7 @@ class EarlyStopping(Callback):
         if self.restore_best_weights and self.best_weights is None:
             self.best_weights = self.model.state_dict()
         self.wait += 1
-        if cur < self.best - self.min_delta:
+        if self._improved(cur):
             self.best, self.best_epoch, self.wait = cur, epoch, 0
             if self.restore_best_weights:
                 self.best_weights = self.model.state_dict()
@@ -595,6 +630,212 @@ class Huber:
         if sample_weight is None:
             return torch.mean(per)
         return _weighted_batch_mean(per, sample_weight)
+
+
+# ---- regression metrics (model.compile(metrics=[...], weighted_metrics=[...])).  Everything a metric needs is in one
+# 8-word fp64 record per set of samples, which the device adds up batch by batch (ops.regression_sums,
+# include/impnn.h: impnn_regression_sums) and the host reads once per evaluate / epoch.
+RECORD_WORDS = 8
+MAX_METRIC_SCALES = 4   # distinct (scale, offset) pairs of one compile
+W_COUNT, W_SUM_W, W_SUM_E, W_SUM_ABS, W_SUM_SQ, W_SUM_Y, W_SUM_YY, W_MAX_ABS = range(RECORD_WORDS)
+
+
+def regression_sums_reference(pred, y, sample_weight=None, groups=None, offset=0.0, scale=1.0):
+    """The definition of the record, and the host reference of ops.regression_sums: numpy fp64 -> (n_seg, 8).
+
+    With e = scale * (pred - y), yr = offset + scale * y and w = sample_weight (1 without), every term formed in
+    float64 from the float32 values, a segment's record is
+        0 samples | 1 sum w | 2 sum w*e | 3 sum w*|e| | 4 sum w*(e*e) | 5 sum w*yr | 6 sum w*(yr*yr) |
+        7 max |e| over the samples with w > 0: NaN if one of those e is NaN, 0 for an empty segment.
+    ``groups`` (one id per sample) cuts the samples into one segment per distinct id, in ``np.unique`` order; without
+    it all samples are the one segment.  ``offset`` / ``scale`` carry a standardised target back to its unit."""
+    p = np.asarray(pred, np.float32).reshape(-1).astype(np.float64)
+    t = np.asarray(y, np.float32).reshape(-1).astype(np.float64)
+    if p.shape != t.shape:
+        raise ValueError("pred and y must hold one value per sample")
+    w = np.ones_like(p) if sample_weight is None else np.asarray(sample_weight, np.float32).reshape(-1).astype(np.float64)
+    if w.shape != p.shape:
+        raise ValueError("sample_weight must hold one value per sample")
+    scale, offset = float(scale), float(offset)
+    if groups is None:
+        segments = [np.arange(len(p))]
+    else:
+        g = np.asarray(groups).reshape(-1)
+        if g.shape != p.shape:
+            raise ValueError("groups must hold one id per sample")
+        ids, inv = np.unique(g, return_inverse=True)
+        order = np.argsort(inv, kind="stable")
+        cuts = np.searchsorted(inv[order], np.arange(len(ids) + 1))
+        segments = [order[cuts[s]:cuts[s + 1]] for s in range(len(ids))]
+    out = np.zeros((len(segments), RECORD_WORDS), np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for s, idx in enumerate(segments):
+            e = scale * (p[idx] - t[idx])
+            yr = offset + scale * t[idx]
+            ws, ae = w[idx], np.abs(e)
+            live = ae[ws > 0]
+            out[s] = [len(idx), ws.sum(), (ws * e).sum(), (ws * ae).sum(), (ws * (e * e)).sum(), (ws * yr).sum(),
+                      (ws * (yr * yr)).sum(), live.max() if live.size else 0.0]
+    return out
+
+
+class Metric:
+    """A regression metric: ``result(record)`` turns one 8-word record (regression_sums_reference) into the value, in
+    float64 on the host.  ``scale`` / ``offset`` name the unit the errors are reported in (e = scale * (pred - y), the
+    true value is offset + scale * y): metrics of one (scale, offset) share one device record.  Means are the word
+    over the sum of the weights, and 0 where that sum is 0 (keras's divide_no_nan)."""
+
+    default_name = None
+
+    def __init__(self, name=None, scale=1.0, offset=0.0):
+        self.name = str(name if name is not None else self.default_name)
+        self.scale, self.offset = _finite(scale, "scale"), _finite(offset, "offset")
+        if self.scale == 0.0:
+            raise ValueError("scale must not be zero")
+
+    @staticmethod
+    def _record(record):
+        r = np.asarray(record, np.float64).reshape(-1)
+        if r.size != RECORD_WORDS:
+            raise ValueError(f"a metric takes one record of {RECORD_WORDS} words, got {np.shape(record)}")
+        return r
+
+    @staticmethod
+    def _mean(r, word):
+        return float(r[word] / r[W_SUM_W]) if r[W_SUM_W] != 0.0 else 0.0
+
+    def result(self, record):
+        raise NotImplementedError
+
+    def get_config(self):
+        return {"name": self.name, "scale": self.scale, "offset": self.offset}
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+class MeanAbsoluteError(Metric):
+    """sum w |e| / sum w."""
+    default_name = "mae"
+
+    def result(self, record):
+        return self._mean(self._record(record), W_SUM_ABS)
+
+
+class MeanSquaredError(Metric):
+    """sum w e^2 / sum w."""
+    default_name = "mse"
+
+    def result(self, record):
+        return self._mean(self._record(record), W_SUM_SQ)
+
+
+class RootMeanSquaredError(Metric):
+    """sqrt(sum w e^2 / sum w)."""
+    default_name = "rmse"
+
+    def result(self, record):
+        return float(np.sqrt(self._mean(self._record(record), W_SUM_SQ)))
+
+
+class MeanError(Metric):
+    """The bias, sum w e / sum w: positive where the model predicts too high."""
+    default_name = "bias"
+
+    def result(self, record):
+        return self._mean(self._record(record), W_SUM_E)
+
+
+class MaxError(Metric):
+    """max |e| over the samples of weight > 0 (NaN if one of them is NaN)."""
+    default_name = "max_error"
+
+    def result(self, record):
+        return float(self._record(record)[W_MAX_ABS])
+
+
+class R2Score(Metric):
+    """The reference's R^2 (utils/mp_utils.py r2_numpy, with its + 1e-6) from the sums, with weights:
+    1 - sum w e^2 / (sum w yr^2 - (sum w yr)^2 / sum w + epsilon); 0 where sum w is 0."""
+    default_name = "r2"
+
+    def __init__(self, name=None, epsilon=1e-6, scale=1.0, offset=0.0):
+        super().__init__(name, scale, offset)
+        self.epsilon = _finite(epsilon, "epsilon")
+
+    def result(self, record):
+        r = self._record(record)
+        if r[W_SUM_W] == 0.0:
+            return 0.0
+        ss_tot = r[W_SUM_YY] - r[W_SUM_Y] * r[W_SUM_Y] / r[W_SUM_W]
+        return float(1.0 - r[W_SUM_SQ] / (ss_tot + self.epsilon))
+
+    def get_config(self):
+        return dict(super().get_config(), epsilon=self.epsilon)
+
+
+METRICS = {"mae": MeanAbsoluteError, "mse": MeanSquaredError, "rmse": RootMeanSquaredError, "bias": MeanError,
+           "max_error": MaxError, "r2": R2Score}
+
+
+def get_metric(m):
+    """A name of METRICS or a Metric object -> the object; anything else is a ValueError."""
+    if isinstance(m, Metric):
+        return m
+    if isinstance(m, str) and m in METRICS:
+        return METRICS[m]()
+    raise ValueError(f"unknown metric {m!r}: a train.Metric object or one of {sorted(METRICS)}")
+
+
+class MetricSet:
+    """What ``compile(metrics=, weighted_metrics=)`` resolves to: the metrics in compile order under their log keys
+    (``<name>``, ``weighted_<name>``) and the device records behind them - one per (scale, offset, weighted), in one
+    persistent (n_records, 8) float64 buffer per ``slot`` ("train": the epoch's running record, "eval": evaluate's).
+    A metric of ``metrics`` never sees ``sample_weight``; one of ``weighted_metrics`` does."""
+
+    def __init__(self, metrics=None, weighted_metrics=None):
+        self.entries, self.records = [], []   # (key, metric, record index); (scale, offset, weighted)
+        for weighted, given in ((False, metrics), (True, weighted_metrics)):
+            for m in ([] if given is None else [given] if isinstance(given, (str, Metric)) else list(given)):
+                m = get_metric(m)
+                rec = (m.scale, m.offset, weighted)
+                if rec not in self.records:
+                    self.records.append(rec)
+                key = ("weighted_" if weighted else "") + m.name
+                if key in self.keys:
+                    raise ValueError(f"two metrics are logged as {key!r}: give one of them another name")
+                self.entries.append((key, m, self.records.index(rec)))
+        if len({(s, o) for s, o, _ in self.records}) > MAX_METRIC_SCALES:
+            raise ValueError(f"at most {MAX_METRIC_SCALES} distinct (scale, offset) pairs in one compile")
+        self._buffers = {}
+
+    @property
+    def keys(self):
+        return [k for k, _, _ in self.entries]
+
+    def __len__(self):
+        return len(self.entries)
+
+    def buffer(self, slot, device):
+        """The slot's records: allocated once and kept (a captured step holds their address), on the model's device."""
+        buf = self._buffers.get(slot)
+        if buf is None:
+            buf = self._buffers[slot] = torch.zeros(len(self.records), RECORD_WORDS, dtype=torch.float64, device=device)
+        return buf
+
+    def accumulate(self, slot, pred, y, sample_weight=None):
+        """One impnn_regression_sums launch per record on the current stream: adds the batch to the slot's records."""
+        from . import ops
+        buf = self.buffer(slot, pred.device)
+        for i, (scale, offset, weighted) in enumerate(self.records):
+            ops.regression_sums(pred, y, sample_weight if weighted else None, offset=offset, scale=scale,
+                                out=buf[i:i + 1], accumulate=True)
+
+    def results(self, records, prefix=""):
+        """The host copy (n_records, 8) of a slot -> {prefix + key: value} in compile order."""
+        records = np.asarray(records, np.float64).reshape(len(self.records), RECORD_WORDS)
+        return {prefix + key: m.result(records[i]) for key, m, i in self.entries}
 
 
 def mse(y_true, y_pred, sample_weight=None):

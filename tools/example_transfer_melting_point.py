@@ -1,6 +1,7 @@
 """The reference's transfer trainer (train_melting_point_transfer.py main(), :150-260) on this package: train a small
 viscosity model, save it, cut it at mix_cat_an and put the melting-point head on it (build_transfer_model), stage 1
-with the base frozen, stage 2 with the last two message-passing steps unfrozen, Huber loss, early stopping, R2 / MAE.
+with the base frozen, stage 2 with the last two message-passing steps unfrozen, Huber loss, early stopping, R2 / MAE in
+kelvin from the device records (metrics with scale = the targets' std, offset = their mean).
 Data are synthetic (ionic_mpnn_amd.synthetic) with targets that are known functions of the graphs - the point is the
 plumbing, not chemistry.
     python tools/example_transfer_melting_point.py [--records 600] [--epochs 30]"""
@@ -15,7 +16,7 @@ import numpy as np
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from ionic_mpnn_amd import build_model, data, synthetic  # noqa: E402
 from ionic_mpnn_amd.model import build_transfer_model  # noqa: E402
-from ionic_mpnn_amd.train import Adam, EarlyStopping, Huber  # noqa: E402
+from ionic_mpnn_amd.train import Adam, EarlyStopping, Huber, MeanAbsoluteError, R2Score  # noqa: E402
 
 UNFREEZE_KEYS = ["cat_bmm_2", "cat_bmm_3", "an_bmm_2", "an_bmm_3", "gated_update_2", "gated_update_3",
                  "gated_update_6", "gated_update_7", "mix_cat_an"]                     # :214-220
@@ -54,22 +55,23 @@ def main():
     for layer in model.layers:                                                         # stage 1, :189-205
         if not layer.name.startswith("mp_") and layer.name != "melting_point":
             layer.trainable = False
-    model.compile(optimizer=Adam(1e-3), loss=Huber(delta=1.0))
+    kelvin = lambda: [MeanAbsoluteError(scale=float(std), offset=float(mean)), R2Score(scale=float(std), offset=float(mean))]
+    model.compile(optimizer=Adam(1e-3), loss=Huber(delta=1.0), metrics=kelvin())
     h1 = model.fit(x["train"], ys[parts["train"]], validation_data=(x["dev"], ys[parts["dev"]]), epochs=a.epochs,
                    batch_size=32, callbacks=cb(), seed=a.seed)
     for layer in model.layers:                                                         # stage 2, :222-238
         if any(k in layer.name for k in UNFREEZE_KEYS):
             layer.trainable = True
-    model.compile(optimizer=Adam(1e-4), loss=Huber(delta=1.0))
+    model.compile(optimizer=Adam(1e-4), loss=Huber(delta=1.0), metrics=kelvin())
     h2 = model.fit(x["train"], ys[parts["train"]], validation_data=(x["dev"], ys[parts["dev"]]), epochs=a.epochs,
                    batch_size=32, callbacks=cb(), seed=a.seed)
     out["stage1_val_loss"] = [h1.history["val_loss"][0], min(h1.history["val_loss"])]
     out["stage2_val_loss"] = [h2.history["val_loss"][0], min(h2.history["val_loss"])]
     out["stage2_trained_variables"] = len(model.trainable_variables())
     for name, ids in parts.items():
-        pred = model.predict(x[name]).flatten() * std + mean
-        out[f"{name}_r2"] = float(data.r2_numpy(y[ids], pred))
-        out[f"{name}_mae"] = float(np.mean(np.abs(y[ids] - pred)))
+        res = model.evaluate(x[name], ys[ids], batch_size=4096, return_dict=True)   # "loss" in Huber units, the rest in K
+        print(name, res)
+        out[f"{name}_r2"], out[f"{name}_mae"] = res["r2"], res["mae"]
     print(json.dumps(out))
     return out
 

@@ -3,7 +3,9 @@ training set: the whole loop (shuffle, batch gather, graphed step, loss bookkeep
 ``--weighted``: the same with per-sample weights (bootstrap counts): the weighted loss kernels and one more gathered
 tensor in the captured step.  ``--optimizer schedule``: the rate follows a CosineDecay with warm-up that the optimizer
 kernel evaluates from its device record; ``--optimizer global_clipnorm``: tf.clip_by_global_norm in place of the
-per-variable clip (one more launch per step, the sums of squares) under the same schedule."""
+per-variable clip (one more launch per step, the sums of squares) under the same schedule.  ``--metrics``: compiled with
+metrics=["mae", "r2"]: the loss kernel keeps the predictions and the captured step ends with one
+impnn_regression_sums launch that adds the batch to the epoch's record."""
 import argparse
 import json
 import sys
@@ -25,6 +27,7 @@ ap.add_argument("--steps", type=int, default=3, help="message-passing steps")
 ap.add_argument("--weighted", action="store_true", help="fit with sample_weight (bootstrap counts)")
 ap.add_argument("--optimizer", choices=("plain", "schedule", "global_clipnorm"), default="plain",
                 help="plain: Adam(1e-3, clipnorm=1.0); schedule: a CosineDecay rate; global_clipnorm: that and a global clip")
+ap.add_argument("--metrics", action="store_true", help='compile(metrics=["mae", "r2"]): running metrics on the device')
 args = ap.parse_args()
 Va, Vb = 124, 72
 m = MM.build_model(Va, Vb, atom_dim=args.atom_dim, num_steps=args.steps, device="cuda")
@@ -33,7 +36,7 @@ if args.optimizer == "plain":
 else:
     rate = train.CosineDecay(1e-4, 8 * args.samples // args.batch, alpha=0.1, warmup_target=1e-3, warmup_steps=50)
     opt = train.Adam(rate, **({"clipnorm": 1.0} if args.optimizer == "schedule" else {"global_clipnorm": 1.0}))
-m.compile(opt)
+m.compile(opt, **({"metrics": ["mae", "r2"]} if args.metrics else {}))
 x = synthetic.make_batch(args.samples, max_atoms=40, max_edges=80, atom_vocab_size=Va, bond_vocab_size=Vb, seed=0)
 y = np.random.default_rng(0).normal(1.0, 0.5, size=args.samples).astype(np.float32)
 x = m._to_device(x)
@@ -57,5 +60,5 @@ for _ in range(200):
     g.graph.replay()
 torch.cuda.synchronize()
 replay_ms = (time.perf_counter() - t1) / 200 * 1e3
-print(json.dumps({"samples": args.samples, "batch": args.batch, "weighted": args.weighted, "optimizer": args.optimizer, "ms_per_epoch": dt * 1e3, "ms_per_step": dt * 1e3 / steps, "ms_per_replay_only": replay_ms,
-                  "pairs_per_s": args.samples / dt, "loss": h.history["loss"]}))
+print(json.dumps({"samples": args.samples, "batch": args.batch, "weighted": args.weighted, "optimizer": args.optimizer, "metrics": args.metrics, "ms_per_epoch": dt * 1e3, "ms_per_step": dt * 1e3 / steps, "ms_per_replay_only": replay_ms,
+                  "pairs_per_s": args.samples / dt, "loss": h.history["loss"], **{k: v for k, v in h.history.items() if k != "loss"}}))
