@@ -556,6 +556,33 @@ int impnn_weighted_transfer_head_loss_bwd(const float* pooled_cat, const float* 
                                           float* dpooled_an, int32_t B, int32_t D, int32_t F, int32_t Mx,
                                           impnn_stream_t stream);
 
+/* ---- the transfer head's loss over indexed rows (stage 1 of transfer learning: a frozen encoder's pooled vectors are
+ *      computed once per distinct ion and kept): sample b reads cat_table[cat_row[b]] (cat_table (C,D)) and
+ *      an_table[an_row[b]] (an_table (A,D)) where the entries above read pooled_cat[b] / pooled_an[b]; no gathered
+ *      (B,D) copy exists.  `cat_row` / `an_row`: B device int32 each, 4-byte aligned, expected in [0,C) / [0,A) (values
+ *      are not read on the host; an index outside its table reads a row of zeros).  Everything behind the load is the
+ *      code of the entries above - BatchNormalization with batch or moving statistics, the Dropout mask keyed on the
+ *      sample's position in the batch, the loss and every sum's order - so the results have the bits of
+ *      impnn_weighted_transfer_head_loss[_bwd] on the gathered rows.  `sample_weight` may be NULL (the unweighted
+ *      loss).  The backward has no dpooled: a trainable encoder is the entries above.  Launches and workspaces as the
+ *      entries above.  B == 0: IMPNN_OK, nothing touched.  Status codes in the order above; a null or misaligned index,
+ *      or C < 1 / A < 1, is IMPNN_E_BADARG after the null pointers and the weights' alignment. */
+int impnn_transfer_head_loss_rows(const float* cat_table, const float* an_table, const int32_t* cat_row,
+                                  const int32_t* an_row, const float* const* weights, const float* l2,
+                                  float* moving_mean, float* moving_var, float bn_momentum, float bn_eps,
+                                  int32_t bn_batch, const float* y, const float* sample_weight, int32_t loss_kind,
+                                  float delta, float rate, uint64_t seed, const int64_t* step, int32_t layer_word,
+                                  float* saved, int64_t saved_floats, float* pred, float* loss, float* workspace,
+                                  int64_t workspace_floats, int32_t B, int32_t C, int32_t A, int32_t D, int32_t F,
+                                  int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_head_loss_rows_bwd(const float* cat_table, const float* an_table, const int32_t* cat_row,
+                                      const int32_t* an_row, const float* const* weights, float* const* dweights,
+                                      const float* l2, int32_t bn_batch, const float* y, const float* sample_weight,
+                                      int32_t loss_kind, float delta, const float* dloss, float rate, uint64_t seed,
+                                      const int64_t* step, int32_t layer_word, const float* saved,
+                                      int64_t saved_floats, float* workspace, int64_t workspace_floats, int32_t B,
+                                      int32_t C, int32_t A, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream);
+
 /* ---- the transfer head over a Cartesian product: C cations x A anions from C + A encoder rows, on the matrix cores.
  *      mix = relu(proj_cat) + relu(proj_an) is a sum and mp_dense_1 is linear in it before its relu, so
  *        a1[i,j] = relu(u_cat[i] + u_an[j]),  u_cat = mix_cat W1 (C,256),  u_an = mix_an W1 + b1 (A,256)

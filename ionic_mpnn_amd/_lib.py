@@ -86,6 +86,11 @@ SIGNATURES = {
                                           + _DROP + [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
     "impnn_weighted_transfer_head_loss_bwd": (C.c_int, [vp, vp, PP, PP, C.POINTER(f32), i32, vp, vp, i32, f32, vp]
                                               + _DROP + [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp]),
+    "impnn_transfer_head_loss_rows": (C.c_int, [vp, vp, vp, vp, PP, C.POINTER(f32), vp, vp, f32, f32, i32, vp, vp, i32,
+                                                f32] + _DROP + [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32,
+                                                                vp]),
+    "impnn_transfer_head_loss_rows_bwd": (C.c_int, [vp, vp, vp, vp, PP, PP, C.POINTER(f32), i32, vp, vp, i32, f32, vp]
+                                          + _DROP + [vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp]),
     "impnn_transfer_grid_image_floats": (i64, []),
     "impnn_transfer_grid_prepare": (C.c_int, [PP, vp, vp, f32, vp, i64, vp]),
     "impnn_transfer_ion_half": (C.c_int, [i32, vp, PP, vp, i32, i32, i32, i32, vp]),

@@ -455,6 +455,22 @@ def _pred_buffer(pred, B, device):
     return pred
 
 
+def _table_rows(rows, cat_table, an_table):
+    """The index pair an indexed loss node hands to the library: contiguous int32 (B) each on the tables' device, or
+    None.  Their range is the caller's to check (data.FrozenEncodings does, on the host, when it is built)."""
+    if rows is None:
+        return None
+    cat_row, an_row = rows
+    for r in (cat_row, an_row):
+        if r.dtype != torch.int32 or r.dim() != 1 or not r.is_contiguous() or r.device != cat_table.device:
+            raise ValueError("cat_row / an_row must be contiguous 1-d int32 tensors on the tables' device")
+    if cat_row.numel() != an_row.numel():
+        raise ValueError("cat_row and an_row must hold one index per sample each")
+    if cat_table.shape[0] < 1 or an_table.shape[0] < 1 or cat_table.shape[1] != an_table.shape[1]:
+        raise ValueError("the tables need at least one row each and one width")
+    return cat_row, an_row
+
+
 class ModelHeadLoss(torch.autograd.Function):
     """Head + keras "mse" + l2 penalties as one node -> the scalar loss (impnn_model_head_loss[_bwd]).  ``l2``: one
     lambda per weight tensor; ``workspace``: a persistent float tensor whose first word is zero (the kernel's arrival
@@ -527,6 +543,9 @@ class TransferHeadLoss(torch.autograd.Function):
     the forward moves in place when cfg["bn_batch"], the pass's ops.Dropout or None, the loss, and optionally
     cfg["sample_weight"]: (B) per-sample weights, which select impnn_weighted_transfer_head_loss[_bwd] and get no
     gradient, and cfg["pred"]: a (B) float32 buffer the forward fills with the pass's predictions);
+    cfg["rows"] = (cat_row, an_row), (B) int32 device tensors: ``pooled_cat`` (C,D) / ``pooled_an`` (A,D) are tables of
+    ion rows and sample b reads pooled_cat[cat_row[b]], pooled_an[an_row[b]] (impnn_transfer_head_loss_rows[_bwd]; the
+    tables get no gradient: a trainable encoder is the plain form);
     ``workspace``: a persistent float tensor whose first word is zero.  The backward adds the gradients of the tensors that ask for one
     into their sinks and leaves the frozen ones alone; it writes the pooled vectors' gradients only when they ask."""
 
@@ -535,6 +554,11 @@ class TransferHeadLoss(torch.autograd.Function):
         pooled_cat, pooled_an, y = f32c(pooled_cat), f32c(pooled_an), f32c(y).reshape(-1)
         weights = tuple(f32c(w) for w in weights)
         B, D = pooled_cat.shape
+        rows = _table_rows(cfg.get("rows"), pooled_cat, pooled_an)
+        if rows is not None:
+            if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+                raise ValueError("the indexed transfer loss has no gradient for its tables")
+            B = int(rows[0].numel())
         if y.numel() != B:
             raise ValueError("y must hold one value per sample")
         sw = _sample_weight(cfg.get("sample_weight"), B, pooled_cat.device)
@@ -549,15 +573,24 @@ class TransferHeadLoss(torch.autograd.Function):
         table = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
         drop = cfg["dropout"]
         dargs = drop.args() if drop is not None and drop.rate > 0.0 else (0.0, C.c_uint64(0), None, 0)
-        entry = lib.impnn_transfer_head_loss if sw is None else lib.impnn_weighted_transfer_head_loss
-        _lib_call(pooled_cat.device, entry, ptr(pooled_cat), ptr(pooled_an), table, lam,
-                  ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]), cfg["momentum"], cfg["epsilon"],
-                  1 if cfg["bn_batch"] else 0, ptr(y), *(() if sw is None else (ptr(sw),)), cfg["loss_kind"],
-                  cfg["delta"], *dargs, ptr(saved) if keep else None, n_saved, None if pred is None else ptr(pred),
-                  ptr(loss), ptr(workspace),
-                  workspace.numel(), B, D, F, Mx)
+        if rows is not None:
+            _lib_call(pooled_cat.device, lib.impnn_transfer_head_loss_rows, ptr(pooled_cat), ptr(pooled_an),
+                      ptr(rows[0]), ptr(rows[1]), table, lam, ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]),
+                      cfg["momentum"], cfg["epsilon"], 1 if cfg["bn_batch"] else 0, ptr(y),
+                      None if sw is None else ptr(sw), cfg["loss_kind"], cfg["delta"], *dargs,
+                      ptr(saved) if keep else None, n_saved, None if pred is None else ptr(pred), ptr(loss),
+                      ptr(workspace), workspace.numel(), B, pooled_cat.shape[0], pooled_an.shape[0], D, F, Mx)
+        else:
+            entry = lib.impnn_transfer_head_loss if sw is None else lib.impnn_weighted_transfer_head_loss
+            _lib_call(pooled_cat.device, entry, ptr(pooled_cat), ptr(pooled_an), table, lam,
+                      ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]), cfg["momentum"], cfg["epsilon"],
+                      1 if cfg["bn_batch"] else 0, ptr(y), *(() if sw is None else (ptr(sw),)), cfg["loss_kind"],
+                      cfg["delta"], *dargs, ptr(saved) if keep else None, n_saved, None if pred is None else ptr(pred),
+                      ptr(loss), ptr(workspace),
+                      workspace.numel(), B, D, F, Mx)
         ctx.save_for_backward(pooled_cat, pooled_an, y, *weights)
         ctx.meta = (cfg, saved, dargs, weights)
+        ctx.rows = rows  # integer tensors: kept beside the saved tensors
         ctx.sample_weight = sw  # no gradient flows to it: kept beside the saved tensors
         return loss
 
@@ -566,6 +599,9 @@ class TransferHeadLoss(torch.autograd.Function):
         cfg, saved, dargs, params = ctx.meta
         pooled_cat, pooled_an, y, *weights = ctx.saved_tensors
         B, D = pooled_cat.shape
+        rows = ctx.rows
+        if rows is not None:
+            B = int(rows[0].numel())
         F, Mx = cfg["fp_size"], cfg["mixing_size"]
         dloss = f32c(dloss).reshape(1)
         lib = _lib.load()
@@ -582,6 +618,12 @@ class TransferHeadLoss(torch.autograd.Function):
         wt = (C.c_void_p * len(weights))(*[w.data_ptr() for w in weights])
         gt = (C.c_void_p * len(weights))(*[g.data_ptr() if g is not None else None for g in grads])
         sw = ctx.sample_weight
+        if rows is not None:
+            _lib_call(dloss.device, lib.impnn_transfer_head_loss_rows_bwd, ptr(pooled_cat), ptr(pooled_an), ptr(rows[0]),
+                      ptr(rows[1]), wt, gt, lam, 1 if cfg["bn_batch"] else 0, ptr(y), None if sw is None else ptr(sw),
+                      cfg["loss_kind"], cfg["delta"], ptr(dloss), *dargs, ptr(saved), saved.numel(), ptr(ws), wsn, B,
+                      pooled_cat.shape[0], pooled_an.shape[0], D, F, Mx)
+            return (None, None, None, None, None) + tuple(None if s is not None else g for s, g in zip(sinks, grads))
         entry = lib.impnn_transfer_head_loss_bwd if sw is None else lib.impnn_weighted_transfer_head_loss_bwd
         _lib_call(dloss.device, entry, ptr(pooled_cat), ptr(pooled_an), wt, gt, lam,
                   1 if cfg["bn_batch"] else 0, ptr(y), *(() if sw is None else (ptr(sw),)), cfg["loss_kind"],

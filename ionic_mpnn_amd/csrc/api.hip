@@ -716,12 +716,27 @@ int impnn_transfer_head(const float* pooled_cat, const float* pooled_an, const f
 }
 
 // The loss entries are the weighted launcher with a null weight (as the model head's): one body per direction, which
-// names the entry that was called in its errors.
+// names the entry that was called in its errors.  The *_rows entries are the same bodies with an index (ThRows): a
+// null ThRows is the call as it was.
 namespace {
+struct ThRows {
+  const int32_t *cat_row, *an_row;
+  int32_t C, A;
+};
 #define REQUIRE_IN(entry, cond, what)                                 \
   do {                                                                \
     if (!(cond)) return fail(IMPNN_E_BADARG, "%s: %s", entry, what);  \
   } while (0)
+
+// the index of an indexed entry, behind the null pointers and the weights' alignment
+int check_th_rows(const char* entry, const ThRows& r) {
+  REQUIRE_IN(entry, r.cat_row && r.an_row, "null row index");
+  REQUIRE_IN(entry, reinterpret_cast<uintptr_t>(r.cat_row) % sizeof(int32_t) == 0 &&
+                        reinterpret_cast<uintptr_t>(r.an_row) % sizeof(int32_t) == 0,
+             "cat_row and an_row must be 4-byte aligned");
+  REQUIRE_IN(entry, r.C >= 1 && r.A >= 1, "the tables need at least one row each (C, A >= 1)");
+  return IMPNN_OK;
+}
 
 int transfer_head_loss_entry(const char* entry, const float* pooled_cat, const float* pooled_an,
                              const float* const* weights, const float* l2, float* moving_mean, float* moving_var,
@@ -729,13 +744,14 @@ int transfer_head_loss_entry(const char* entry, const float* pooled_cat, const f
                              const float* sample_weight, int32_t loss_kind, float delta, float rate, uint64_t seed,
                              const int64_t* step, int32_t layer_word, float* saved, int64_t saved_floats, float* pred,
                              float* loss, float* workspace, int64_t workspace_floats, int32_t B, int32_t D, int32_t F,
-                             int32_t Mx, impnn_stream_t stream) {
+                             int32_t Mx, impnn_stream_t stream, const ThRows* rows = nullptr) {
   TransferHeadCall c{};
   c.dropout = rate != 0.f;
   if (c.dropout) {
     if (int rc = check_dropout(entry, rate, seed, step, layer_word, &c.drop)) return rc;
   }
-  REQUIRE_IN(entry, B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE_IN(entry, (B > 0 || (rows && B == 0)) && D > 0 && F > 0 && Mx > 0, "bad shape");
+  if (B == 0) return IMPNN_OK;  // (an indexed entry only: no sample, nothing is touched)
   REQUIRE_IN(entry, loss_kind == 0 || (loss_kind == 1 && delta > 0.f),
              "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
   REQUIRE_IN(entry, bn_eps >= 0.f && bn_momentum >= 0.f && bn_momentum <= 1.f,
@@ -744,6 +760,10 @@ int transfer_head_loss_entry(const char* entry, const float* pooled_cat, const f
              "null pointer");
   REQUIRE_IN(entry, reinterpret_cast<uintptr_t>(sample_weight) % sizeof(float) == 0,
              "sample_weight must be 4-byte aligned");
+  if (rows) {
+    if (int rc = check_th_rows(entry, *rows)) return rc;
+    c.cat_row = rows->cat_row, c.an_row = rows->an_row, c.C = rows->C, c.A = rows->A;
+  }
   REQUIRE_IN(entry, saved || !bn_batch, "the batch statistics need the saved buffer");
   if (saved && saved_floats < transfer_head_saved_floats(B, F, Mx))
     return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", entry, (long long)saved_floats);
@@ -763,19 +783,24 @@ int transfer_head_loss_bwd_entry(const char* entry, const float* pooled_cat, con
                                  float delta, const float* dloss, float rate, uint64_t seed, const int64_t* step,
                                  int32_t layer_word, const float* saved, int64_t saved_floats, float* workspace,
                                  int64_t workspace_floats, float* dpooled_cat, float* dpooled_an, int32_t B, int32_t D,
-                                 int32_t F, int32_t Mx, impnn_stream_t stream) {
+                                 int32_t F, int32_t Mx, impnn_stream_t stream, const ThRows* rows = nullptr) {
   TransferHeadCall c{};
   c.dropout = rate != 0.f;
   if (c.dropout) {
     if (int rc = check_dropout(entry, rate, seed, step, layer_word, &c.drop)) return rc;
   }
-  REQUIRE_IN(entry, B > 0 && D > 0 && F > 0 && Mx > 0, "bad shape");
+  REQUIRE_IN(entry, (B > 0 || (rows && B == 0)) && D > 0 && F > 0 && Mx > 0, "bad shape");
+  if (B == 0) return IMPNN_OK;  // (an indexed entry only: no sample, no gradient is added)
   REQUIRE_IN(entry, loss_kind == 0 || (loss_kind == 1 && delta > 0.f),
              "loss_kind must be 0 (squared error) or 1 (Huber, delta > 0)");
   REQUIRE_IN(entry, pooled_cat && pooled_an && weights && dweights && l2 && y && dloss && saved && workspace,
              "null pointer");
   REQUIRE_IN(entry, reinterpret_cast<uintptr_t>(sample_weight) % sizeof(float) == 0,
              "sample_weight must be 4-byte aligned");
+  if (rows) {
+    if (int rc = check_th_rows(entry, *rows)) return rc;
+    c.cat_row = rows->cat_row, c.an_row = rows->an_row, c.C = rows->C, c.A = rows->A;
+  }
   REQUIRE_IN(entry, (dpooled_cat != nullptr) == (dpooled_an != nullptr), "dpooled_cat and dpooled_an: both or neither");
   if (saved_floats < transfer_head_saved_floats(B, F, Mx))
     return fail(IMPNN_E_WORKSPACE, "%s: saved buffer of %lld floats is too small", entry, (long long)saved_floats);
@@ -838,6 +863,35 @@ int impnn_weighted_transfer_head_loss_bwd(const float* pooled_cat, const float* 
                                       sample_weight, loss_kind, delta, dloss, rate, seed, step, layer_word, saved,
                                       saved_floats, workspace, workspace_floats, dpooled_cat, dpooled_an, B, D, F, Mx,
                                       stream);
+}
+
+int impnn_transfer_head_loss_rows(const float* cat_table, const float* an_table, const int32_t* cat_row,
+                                  const int32_t* an_row, const float* const* weights, const float* l2,
+                                  float* moving_mean, float* moving_var, float bn_momentum, float bn_eps,
+                                  int32_t bn_batch, const float* y, const float* sample_weight, int32_t loss_kind,
+                                  float delta, float rate, uint64_t seed, const int64_t* step, int32_t layer_word,
+                                  float* saved, int64_t saved_floats, float* pred, float* loss, float* workspace,
+                                  int64_t workspace_floats, int32_t B, int32_t C, int32_t A, int32_t D, int32_t F,
+                                  int32_t Mx, impnn_stream_t stream) {
+  const ThRows rows{cat_row, an_row, C, A};
+  return transfer_head_loss_entry(__func__, cat_table, an_table, weights, l2, moving_mean, moving_var, bn_momentum,
+                                  bn_eps, bn_batch, y, sample_weight, loss_kind, delta, rate, seed, step, layer_word,
+                                  saved, saved_floats, pred, loss, workspace, workspace_floats, B, D, F, Mx, stream,
+                                  &rows);
+}
+
+int impnn_transfer_head_loss_rows_bwd(const float* cat_table, const float* an_table, const int32_t* cat_row,
+                                      const int32_t* an_row, const float* const* weights, float* const* dweights,
+                                      const float* l2, int32_t bn_batch, const float* y, const float* sample_weight,
+                                      int32_t loss_kind, float delta, const float* dloss, float rate, uint64_t seed,
+                                      const int64_t* step, int32_t layer_word, const float* saved,
+                                      int64_t saved_floats, float* workspace, int64_t workspace_floats, int32_t B,
+                                      int32_t C, int32_t A, int32_t D, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  const ThRows rows{cat_row, an_row, C, A};
+  return transfer_head_loss_bwd_entry(__func__, cat_table, an_table, weights, dweights, l2, bn_batch, y,
+                                      sample_weight, loss_kind, delta, dloss, rate, seed, step, layer_word, saved,
+                                      saved_floats, workspace, workspace_floats, nullptr, nullptr, B, D, F, Mx, stream,
+                                      &rows);
 }
 
 // ---- the transfer head over a cation x anion grid (include/impnn.h; transfer_grid.hip).  One place applies the

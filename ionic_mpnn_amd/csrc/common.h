@@ -250,7 +250,9 @@ int launch_global_sum_pool(const float* h, const int32_t* ids, float* out, int B
 // ---- the transfer head (transfer_head.hip; include/impnn.h, impnn_transfer_head*).  api.hip fills and checks it.
 constexpr int kThTensors = 18;
 struct TransferHeadCall {
-  const float *pc, *pa;
+  const float *pc, *pa;             // (B,D) each; with cat_row: the tables (C,D), (A,D)
+  const int32_t *cat_row, *an_row;  // indexed entries: (B) rows of the tables per sample; null: pc / pa hold the samples
+  int C, A;                         // rows of the tables (indexed entries)
   const float* const* weights;  // kThTensors device pointers
   float* const* dweights;       // backward: kThTensors device pointers, null where a tensor is frozen
   const float* l2;              // host, kThTensors lambdas

@@ -181,13 +181,18 @@ enum { kThPre = 1, kThPost = 2, kThBatchStats = 4 };
 
 // kWeighted: a loss call with sample weights (hl.y and hl.w set); the other instance has no trace of them.  The
 // weights touch the loss only: BatchNormalization's statistics and the dropout masks do not see them.
-template <bool kWeighted>
+// kRows: pc (C,D) and pa (A,D) are tables of ion rows and sample b reads pc[crow[b]], pa[arow[b]] (a stage-1 fit over
+// cached encodings); an index outside its table reads a row of zeros.  Only the tile load differs: the other instances
+// never look at crow / arow / C / A.
+template <bool kWeighted, bool kRows>
 __global__ __launch_bounds__(kThThreads) void th_forward(const float* __restrict__ pc, const float* __restrict__ pa,
                                                          ThTensors ht, const float* __restrict__ moving_mean,
                                                          const float* __restrict__ moving_var, float bn_eps, int flags,
                                                          float* __restrict__ saved, float* __restrict__ out, int B,
                                                          int D, int F, int Mx, bool dropout, DropoutArgs drop,
-                                                         ThLoss hl, const float* __restrict__ sw) {
+                                                         ThLoss hl, const float* __restrict__ sw,
+                                                         const int* __restrict__ crow, const int* __restrict__ arow,
+                                                         int C, int A) {
   __shared__ ThSmem sm;
   __shared__ int is_last;
   const int tid = threadIdx.x;
@@ -196,7 +201,16 @@ __global__ __launch_bounds__(kThThreads) void th_forward(const float* __restrict
   if (flags & kThPre) {
     for (int idx = tid; idx < kThSPB * 2 * D; idx += kThThreads) {
       const int s = idx / (2 * D), r = idx - s * 2 * D, g = r / D, i = r - g * D;
-      sm.x[(s * 2 + g) * kHeadMaxX + i] = b0 + s < B ? (g == 0 ? pc : pa)[(int64_t)(b0 + s) * D + i] : 0.f;
+      if constexpr (kRows) {
+        float v = 0.f;
+        if (b0 + s < B) {
+          const int row = (g == 0 ? crow : arow)[b0 + s];
+          if ((unsigned)row < (unsigned)(g == 0 ? C : A)) v = (g == 0 ? pc : pa)[(int64_t)row * D + i];
+        }
+        sm.x[(s * 2 + g) * kHeadMaxX + i] = v;
+      } else {
+        sm.x[(s * 2 + g) * kHeadMaxX + i] = b0 + s < B ? (g == 0 ? pc : pa)[(int64_t)(b0 + s) * D + i] : 0.f;
+      }
     }
     __syncthreads();
     for (int g = 0; g < 2; ++g)
@@ -492,7 +506,9 @@ __global__ __launch_bounds__(kThThreads) void th_bwd_pre(ThTensors ht, const flo
 
 // Parameter gradients: job q adds, for every element (i, j) of its (I, J) tensor,
 //   sum_b a[b * lda + i] * g[b * ldg + j]   (a null: a bias, sum_b g[b * ldg + j])   + 2 * l2 * w[i, j] * dloss
-// to out[i * J + j]; one thread per element, the batch in order (no atomics).
+// to out[i * J + j]; one thread per element, the batch in order (no atomics).  kRows: a job with `arow` reads row
+// arow[b] of its nrow-row table `a` in place of row b (an index outside the table: a row of zeros); the other instance
+// never looks at arow / nrow.
 constexpr int kThJobs = 16;
 struct ThJobs {
   const float* a[kThJobs];
@@ -500,10 +516,13 @@ struct ThJobs {
   const float* w[kThJobs];
   float* out[kThJobs];
   int lda[kThJobs], ldg[kThJobs], I[kThJobs], J[kThJobs];
+  const int* arow[kThJobs];
+  int nrow[kThJobs];
   int first_block[kThJobs + 1];
   float l2[kThJobs];
   int n;
 };
+template <bool kRows>
 __global__ __launch_bounds__(kThThreads) void th_param_grads(ThJobs jobs, const float* __restrict__ dloss, int B) {
   int q = 0;
   for (int t = 1; t < kThJobs; ++t)
@@ -516,7 +535,16 @@ __global__ __launch_bounds__(kThThreads) void th_param_grads(ThJobs jobs, const 
   const float* __restrict__ g = jobs.g[q];
   const int lda = jobs.lda[q], ldg = jobs.ldg[q];
   float acc = 0.f;
-  if (a) {
+  if (kRows && a && jobs.arow[q]) {
+    const int* __restrict__ ar = jobs.arow[q];
+    const unsigned nrow = (unsigned)jobs.nrow[q];
+#pragma unroll 4
+    for (int b = 0; b < B; ++b) {
+      const int row = ar[b];
+      const float av = (unsigned)row < nrow ? a[(int64_t)row * lda + i] : 0.f;
+      acc = fmaf(av, g[(int64_t)b * ldg + j], acc);
+    }
+  } else if (a) {
 #pragma unroll 4
     for (int b = 0; b < B; ++b) acc = fmaf(a[(int64_t)b * lda + i], g[(int64_t)b * ldg + j], acc);
   } else {
@@ -556,18 +584,24 @@ int launch_transfer_head(const TransferHeadCall& c) {
   }
   const int groups = (c.B + kThSPB - 1) / kThSPB;
   // the launch that ends with the loss: the weighted instance where the call has weights
+  // (the indexed instances where the launch holds the tile load of an indexed call; the index is null otherwise)
+  const bool rows = c.cat_row != nullptr;
   auto loss_forward = [&](int flags) {
     const bool weighted = c.y && c.sample_weight;
-    const auto kernel = weighted ? th_forward<true> : th_forward<false>;
+    const bool indexed = rows && (flags & kThPre);
+    const auto kernel = indexed ? (weighted ? th_forward<true, true> : th_forward<false, true>)
+                                : (weighted ? th_forward<true, false> : th_forward<false, false>);
     kernel<<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps, flags, c.saved,
                                                 c.out, c.B, c.D, c.F, c.Mx, c.dropout, c.drop, hl,
-                                                weighted ? c.sample_weight : nullptr);
+                                                weighted ? c.sample_weight : nullptr, indexed ? c.cat_row : nullptr,
+                                                indexed ? c.an_row : nullptr, c.C, c.A);
   };
   const ThSaved so = th_saved(c.B, c.F, c.Mx);
   if (c.bn_batch) {
-    th_forward<false><<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps, kThPre,
-                                                    c.saved, nullptr, c.B, c.D, c.F, c.Mx, false, DropoutArgs{},
-                                                    ThLoss{}, nullptr);
+    const auto pre = rows ? th_forward<false, true> : th_forward<false, false>;
+    pre<<<groups, kThThreads, 0, c.stream>>>(c.pc, c.pa, ht, c.moving_mean, c.moving_var, c.bn_eps, kThPre, c.saved,
+                                             nullptr, c.B, c.D, c.F, c.Mx, false, DropoutArgs{}, ThLoss{}, nullptr,
+                                             c.cat_row, c.an_row, c.C, c.A);
     if (int rc = check_launch("transfer_head (pre)")) return rc;
     th_bn_stats<<<kThH1 / kThStatLanes, kThThreads, 0, c.stream>>>(c.saved + so.a1, c.saved + so.stat, c.moving_mean,
                                                                    c.moving_var, c.bn_momentum, c.bn_eps, c.B);
@@ -613,9 +647,12 @@ int launch_transfer_head_bwd(const TransferHeadCall& c) {
   // statistics BatchNormalization is frozen and has none)
   ThJobs jobs{};
   int nblocks = 0;
-  auto add = [&](int t, const float* a, int lda, const float* g, int ldg, int I, int J) {
+  bool indexed = false;
+  auto add = [&](int t, const float* a, int lda, const float* g, int ldg, int I, int J, const int* arow = nullptr,
+                 int nrow = 0) {
     if (!dw[t]) return;
     const int q = jobs.n++;
+    jobs.arow[q] = arow, jobs.nrow[q] = nrow, indexed = indexed || arow;
     jobs.a[q] = a, jobs.lda[q] = lda, jobs.g[q] = g, jobs.ldg[q] = ldg, jobs.I[q] = I, jobs.J[q] = J;
     jobs.w[q] = c.weights[t], jobs.out[q] = dw[t], jobs.l2[q] = c.l2[t];
     jobs.first_block[q] = nblocks;
@@ -624,7 +661,8 @@ int launch_transfer_head_bwd(const TransferHeadCall& c) {
   const float* sv = c.saved;
   const float* wk = c.workspace;
   for (int g = 0; g < 2; ++g) {
-    add(2 * g, g == 0 ? c.pc : c.pa, D, wk + wo.dfp + g * F, 2 * F, D, F);
+    add(2 * g, g == 0 ? c.pc : c.pa, D, wk + wo.dfp + g * F, 2 * F, D, F, g == 0 ? c.cat_row : c.an_row,
+        g == 0 ? c.C : c.A);
     add(2 * g + 1, nullptr, 0, wk + wo.dfp + g * F, 2 * F, 1, F);
     add(4 + 2 * g, sv + so.fp + g * F, 2 * F, wk + wo.dpr + g * Mx, 2 * Mx, F, Mx);
     add(5 + 2 * g, nullptr, 0, wk + wo.dpr + g * Mx, 2 * Mx, 1, Mx);
@@ -639,7 +677,8 @@ int launch_transfer_head_bwd(const TransferHeadCall& c) {
   add(17, nullptr, 0, wk + wo.dpred, 1, 1, 1);
   jobs.first_block[jobs.n] = nblocks;
   if (jobs.n == 0) return IMPNN_OK;
-  th_param_grads<<<nblocks, kThThreads, 0, c.stream>>>(jobs, c.dloss, B);
+  const auto param_grads = indexed ? th_param_grads<true> : th_param_grads<false>;
+  param_grads<<<nblocks, kThThreads, 0, c.stream>>>(jobs, c.dloss, B);
   return check_launch("transfer_head_bwd (parameters)");
 }
 

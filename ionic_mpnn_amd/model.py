@@ -285,6 +285,7 @@ class MPNNModel:
         self.encoder_mode = "auto"  # "auto" | "f32t" | "f32x3" | "f32" | "f16x2" (ops.encoder_fused)
         self.encoder_workgroups = 0  # persistent workgroups per encoder launch (0: library default, one per CU)
         self._transfer_grid_image = None
+        self._encoder_version = 0  # moves on whenever the encoder's packed weights are dropped (data.FrozenEncodings)
         self.grid_head_mode = "auto"  # "auto" | "gathered": predict_grid's head for the transfer model
 
     # ------------------------------------------------------------------ construction
@@ -471,6 +472,7 @@ class MPNNModel:
         self._prepared = {}
         self._split_deg_limit = None
         self._head_packed = None
+        self._encoder_version += 1
         for p in ("cat", "an"):
             for lyr in self.branches[p]["bmm"]:
                 lyr.invalidate_cache()
@@ -487,11 +489,19 @@ class MPNNModel:
                if n.endswith("_embedding") or "_bmm_" in n or "_gu_" in n]
         if any(t.requires_grad for t in enc):
             self._packed, self._prepared, self._split_deg_limit = None, {}, None
+            self._encoder_version += 1
         table = self.bond_emb.embeddings.requires_grad
         for p in ("cat", "an"):
             for lyr in self.branches[p]["bmm"]:
                 if table or lyr.bond_transform.requires_grad:
                     lyr.invalidate_cache()
+
+    @property
+    def encoder_version(self):
+        """The version of the encoder's weights: ``invalidate_packed_weights`` (so ``load_weights``) and every
+        ``weights_updated`` of a model whose encoder trains move it on, with the packed weights they drop.  What was
+        computed from the encoder at an older version (data.FrozenEncodings) is stale."""
+        return self._encoder_version
 
     def _cache_refs(self):
         """The cached tensors a captured step may read (kept alive by train.GraphedTrainStep)."""
@@ -1023,6 +1033,100 @@ class MPNNModel:
                 cfg = dict(cfg, pred=pred)
             return autograd.TransferHeadLoss.apply(cfg, ws, pc, pa, y, *self._head_tensors())
 
+    # ---- stage 1 of transfer learning over cached encodings (data.FrozenEncodings; DESIGN.md "Cached encodings")
+    def _frozen_cache_check(self):
+        """ValueError unless a training pass of this model needs the encoder for nothing but its pooled rows, and those
+        cannot change: what ``cache_frozen_encoder=True`` and ``frozen_encodings`` require."""
+        from . import dist as idist
+        why = None
+        if self.kind != "transfer":
+            why = f"it is a {self.kind} model: only the transfer model's head reads indexed rows"
+        elif self._encoder_trains():
+            why = "an encoder layer is trainable (stage 2): its pooled rows change with every step"
+        elif self.dropout_rate > 0.0:
+            why = (f"the encoder's GatedUpdate dropout rate is {self.dropout_rate}: a training pass applies it to frozen "
+                   "steps too, so the pooled rows differ from step to step")
+        elif not self._head_kernels_cover():
+            why = (f"the head kernels do not cover atom_dim {self.atom_dim}, fp_size {self.fp_size}, mixing_size "
+                   f"{self.mixing_size} (<= {ops.HEAD_MAX_X}, {ops.HEAD_MAX_DIM}, {ops.HEAD_MAX_DIM})")
+        elif idist.is_distributed():
+            why = "torch.distributed is initialised: data-parallel fits encode per shard"
+        if why is not None:
+            raise ValueError(f"cache_frozen_encoder: the frozen encoder cannot be cached - {why}")
+
+    def frozen_encodings(self, inputs, batch_size=4096):
+        """data.FrozenEncodings of padded model inputs: every distinct ion through ``encode_ions`` once.  Refused
+        (ValueError) where ``fit(cache_frozen_encoder=True)`` is."""
+        self._frozen_cache_check()
+        return data.FrozenEncodings.build(self, inputs, batch_size)
+
+    def _loss_encoded(self, enc, cat_row, an_row, y, training, sample_weight=None, metric_slot=None):
+        """``_loss`` of the samples (enc.cat[cat_row[b]], enc.an[an_row[b]]) without their inputs: the head's loss node
+        over indexed rows (impnn_transfer_head_loss_rows[_bwd]) - no encoder launch, no gathered copy.  ``cat_row`` /
+        ``an_row``: (B) int32 device tensors, rows of ``enc``'s index."""
+        from . import autograd, train
+        self._frozen_cache_check()
+        if enc.stale(self):
+            raise ValueError(f"the encodings were made at encoder version {enc.version}, the model is at "
+                             f"{self.encoder_version} (load_weights, or a step that trained the encoder): build them again")
+        y = torch.as_tensor(y, dtype=torch.float32).to(self.device).reshape(-1, 1)
+        B = int(y.shape[0])
+        if B == 0:
+            raise ValueError("the indexed loss needs at least one sample")
+        sw = train.checked_sample_weight(sample_weight, B, self.device)
+        ms = getattr(self, "_metric_set", None) if metric_slot is not None else None
+        pbuf = self._metric_pred(B) if ms is not None else None
+        need = int(ops._lib.load().impnn_transfer_head_loss_workspace_floats(B))
+        ws = getattr(self, "_loss_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
+        ds = ops.dropout_step(self.dropout_counter()) if training else None  # (the head's Dropout: one mask per pass)
+        with torch.set_grad_enabled(training and torch.is_grad_enabled()):
+            cfg = dict(self._transfer_cfg(training, ds), rows=(cat_row, an_row))
+            if sw is not None:
+                cfg["sample_weight"] = sw
+            if pbuf is not None:
+                cfg["pred"] = pbuf
+            loss = autograd.TransferHeadLoss.apply(cfg, ws, enc.cat, enc.an, y, *self._head_tensors())
+        if ms is not None:
+            ms.accumulate(metric_slot, pbuf, y.reshape(-1), sw)
+        return loss
+
+    def train_on_encoded_batch(self, enc, rows, y, sample_weight=None, metric_slot=None):
+        """``train_on_batch`` on the samples ``rows`` (device int64) of ``enc`` (data.FrozenEncodings): ``y`` and
+        ``sample_weight`` hold one value per sample of the batch."""
+        if getattr(self, "optimizer", None) is None:
+            self.compile()
+        kw = {} if metric_slot is None else {"metric_slot": metric_slot}
+        loss = self._loss_encoded(enc, torch.index_select(enc.cat_row, 0, rows), torch.index_select(enc.an_row, 0, rows),
+                                  y, True, sample_weight, **kw)
+        loss.backward()
+        self.optimizer.apply_gradients()
+        self.optimizer.zero_grad()
+        self.weights_updated()
+        return loss.detach()
+
+    def _evaluate_encoded(self, enc, y, batch_size, sw, return_dict):
+        """``evaluate`` over cached encodings: the same sums, every batch through the indexed loss."""
+        n = len(enc)
+        ms = getattr(self, "_metric_set", None)
+        kw = {}
+        if ms is not None:
+            records = ms.buffer("eval", self.device).zero_()
+            kw = {"metric_slot": "eval"}
+        tot = torch.zeros((), dtype=torch.float64, device=self.device)
+        for lo in range(0, n, batch_size):
+            sl = slice(lo, min(n, lo + batch_size))
+            loss = self._loss_encoded(enc, enc.cat_row[sl], enc.an_row[sl], y[sl], False,
+                                      None if sw is None else sw[sl], **kw)
+            tot.add_(loss, alpha=sl.stop - sl.start)
+        if ms is None:
+            loss = float(tot) / max(n, 1)
+            return {"loss": loss} if return_dict else loss
+        host = torch.cat([tot.reshape(1), records.reshape(-1)]).cpu().numpy()
+        out = {"loss": float(host[0]) / max(n, 1), **ms.results(host[1:])}
+        return out if return_dict else list(out.values())
+
     def train_on_batch(self, inputs, y, sample_weight=None, group=None, n_global=None, metric_slot=None):
         """One optimizer step on one mini-batch -> the batch loss (MSE + penalties) as a 0-d tensor.
         ``sample_weight``: one finite value >= 0 per sample (of this rank's shard): the loss is keras's
@@ -1059,13 +1163,24 @@ class MPNNModel:
         self.weights_updated()
         return loss.detach() if loss is not None else torch.zeros((), device=opt.flat_grad.device)
 
-    def evaluate(self, inputs, y, batch_size=32, sample_weight=None, return_dict=False):
+    def evaluate(self, inputs, y, batch_size=32, sample_weight=None, return_dict=False, cache_frozen_encoder=False):
         """model.evaluate: sample-count-weighted mean of the batch losses (MSE + penalties); with ``sample_weight`` a
         batch loss is the weighted one, (1/B) sum_b w_b L_b + penalties.  A model compiled with metrics returns
         ``[loss, *metrics]`` in compile order (``return_dict``: {"loss": ..., "<name>": ...}): every batch's inference
         predictions are added to the device records behind its loss, and the records come back with the loss sum in
-        the one synchronisation."""
+        the one synchronisation.  ``cache_frozen_encoder`` (a transfer model with a frozen encoder; ``fit`` names the
+        refusals): every distinct ion is encoded once and the batches run the indexed loss; ``inputs`` may then be a
+        data.FrozenEncodings made earlier."""
         from . import train
+        if cache_frozen_encoder or isinstance(inputs, data.FrozenEncodings):
+            self._frozen_cache_check()
+            n = len(inputs) if isinstance(inputs, data.FrozenEncodings) else len(inputs["cat_atom"])
+            sw = train.checked_sample_weight(sample_weight, n, self.device)
+            enc = inputs if isinstance(inputs, data.FrozenEncodings) else data.FrozenEncodings.build(self, inputs)
+            y_dev = torch.as_tensor(np.asarray(y, np.float32) if not torch.is_tensor(y) else y).to(self.device)
+            if y_dev.numel() != n:
+                raise ValueError(f"y holds {y_dev.numel()} values for {n} samples")
+            return self._evaluate_encoded(enc, y_dev.reshape(-1, 1), int(batch_size), sw, return_dict)
         n = len(inputs["cat_atom"])
         sw = train.checked_sample_weight(sample_weight, n, self.device)
         ms = getattr(self, "_metric_set", None)
@@ -1087,7 +1202,7 @@ class MPNNModel:
         return out if return_dict else list(out.values())
 
     def fit(self, x, y, validation_data=None, epochs=1, batch_size=32, callbacks=None, shuffle=True, verbose=0,
-            seed=None, graph=True, sample_weight=None):
+            seed=None, graph=True, sample_weight=None, cache_frozen_encoder=False):
         """model.fit as the trainers call it (train_viscosity.py:328-338): per epoch a fresh shuffle,
         mini-batches of ``batch_size``, `loss` = sample-weighted mean of the batch losses, `val_loss` from
         evaluate(); callbacks see on_train_begin / on_epoch_begin / on_epoch_end / on_train_end.  Returns a History.
@@ -1101,10 +1216,17 @@ class MPNNModel:
         are uploaded once and cut like y.  ``validation_data`` may be ``(x, y)`` or ``(x, y, sample_weight)``.
         A model compiled with metrics logs them too: the training ones are keras's running metrics, added up on the
         device from every step's training-pass predictions (inside the captured step) and read with the loss at the
-        end of the epoch; the validation ones come from evaluate() as ``val_<name>``."""
+        end of the epoch; the validation ones come from evaluate() as ``val_<name>``.
+        ``cache_frozen_encoder=True`` (stage 1 of transfer learning): every distinct ion of ``x`` and of the validation
+        set is encoded once, before the first epoch (data.FrozenEncodings), and every step - the captured one and the
+        eager last batch - and the validation run the head's loss over indexed rows: no encoder launch, no batch
+        gather.  A ValueError names the reason where that is not possible: not a transfer model, a trainable encoder
+        layer, GatedUpdate dropout above 0, widths the head kernels do not cover, torch.distributed."""
         from . import train
         if getattr(self, "optimizer", None) is None:
             self.compile()
+        if cache_frozen_encoder:
+            self._frozen_cache_check()
         y = np.asarray(y, dtype=np.float32)
         n = len(y)
         w_host = train.checked_sample_weight(sample_weight, n)  # raises before anything reaches the device
@@ -1143,10 +1265,18 @@ class MPNNModel:
         val_dev = None
         ms = getattr(self, "_metric_set", None)
         mkw = {} if ms is None else {"metric_slot": "train"}
+        enc = val_enc = None
+        if cache_frozen_encoder and n:  # both sets' ions once, before the first epoch
+            enc = data.FrozenEncodings.build(self, x)
+            if validation_data is not None and len(validation_data[0]["cat_atom"]):
+                val_enc = data.FrozenEncodings.build(self, validation_data[0])
         for epoch in range(int(epochs)):
             for cb in callbacks:
                 if hasattr(cb, "on_epoch_begin"):
                     cb.on_epoch_begin(epoch, {})
+            if enc is not None and enc.stale(self):  # (a callback loaded weights: encode again, capture again)
+                enc, graphed = data.FrozenEncodings.build(self, x), None
+                val_enc = None if val_enc is None else data.FrozenEncodings.build(self, validation_data[0])
             order = rng.permutation(n) if shuffle else np.arange(n)
             order_dev = torch.from_numpy(order).to(self.device)  # one upload per epoch
             tot = torch.zeros((), dtype=torch.float64, device=self.device)
@@ -1155,7 +1285,17 @@ class MPNNModel:
             for lo in range(0, n, batch_size):
                 idx = order[lo:lo + batch_size]
                 tidx = order_dev[lo:lo + batch_size]
-                if use_graph and len(idx) == batch_size:
+                if enc is not None:
+                    if use_graph and len(idx) == batch_size:
+                        if graphed is None:
+                            graphed = train.GraphedTrainStep(
+                                self, tidx, y[idx], resident=(enc, y_dev) if w_dev is None else (enc, y_dev, w_dev),
+                                sample_weight=None if w_dev is None else w_dev[tidx])
+                        loss = graphed.step_on_rows(enc, y_dev, tidx, w_dev)
+                    else:
+                        loss = self.train_on_encoded_batch(enc, tidx, y_dev[tidx],
+                                                           None if w_dev is None else w_dev[tidx], **mkw)
+                elif use_graph and len(idx) == batch_size:
                     if graphed is None:
                         x = {k: v.contiguous() for k, v in x.items()}
                         if w_dev is None:
@@ -1197,10 +1337,11 @@ class MPNNModel:
                                torch.from_numpy(np.asarray(validation_data[1], np.float32)).to(self.device),
                                None if val_w_host is None else val_w_host.to(self.device))
                 # the sample-weighted mean does not depend on how the set is cut: large forward-only batches
+                val_x = val_dev[0] if val_enc is None else val_enc
                 if ms is None:
-                    logs["val_loss"] = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096), val_dev[2])
+                    logs["val_loss"] = self.evaluate(val_x, val_dev[1], max(batch_size, 4096), val_dev[2])
                 else:
-                    val = self.evaluate(val_dev[0], val_dev[1], max(batch_size, 4096), val_dev[2], return_dict=True)
+                    val = self.evaluate(val_x, val_dev[1], max(batch_size, 4096), val_dev[2], return_dict=True)
                     logs.update({"val_" + k: v for k, v in val.items()})
             hist._log(epoch, logs)
             if verbose:

@@ -1495,3 +1495,121 @@ def transfer_head(pooled_cat, pooled_an, weights, cfg):
                                               ptr(cfg["moving_variance"]), cfg["epsilon"], ptr(out), B, D,
                                               cfg["fp_size"], cfg["mixing_size"], stream_ptr()))
     return out
+
+
+def _transfer_loss_operands(cat, an, cat_row, an_row, weights, y, sample_weight):
+    """The operands of the transfer head's loss entries, checked once -> (cat, an, rows | None, weights, y, sw, B).
+    With ``cat_row`` / ``an_row`` the first two are tables (C,D), (A,D) and the batch is the indices'; an index given
+    as a host array is checked against its table here and uploaded, one that already lives on the GPU is checked for
+    its dtype and length only (data.FrozenEncodings checked its values when it was built) - the rule of the sample
+    weights."""
+    require_gpu(cat, an, y, *weights)
+    cat, an, y = f32c(cat), f32c(an), f32c(y).reshape(-1)
+    weights = [f32c(w) for w in weights]
+    if len(weights) != 18:
+        raise ValueError("the transfer head takes 18 weight tensors (include/impnn.h)")
+    if cat.dim() != 2 or an.dim() != 2 or cat.shape[1] != an.shape[1]:
+        raise ValueError("the pooled operands must be (rows, D) matrices of one width")
+    rows = None
+    if (cat_row is None) != (an_row is None):
+        raise ValueError("cat_row and an_row: both or neither")
+    if cat_row is not None:
+        rows = []
+        for name, r, n in (("cat_row", cat_row, cat.shape[0]), ("an_row", an_row, an.shape[0])):
+            if not (torch.is_tensor(r) and r.is_cuda):
+                h = np.asarray(r.numpy() if torch.is_tensor(r) else r)
+                if h.ndim != 1 or not np.issubdtype(h.dtype, np.integer):
+                    raise ValueError(f"{name} must be a 1-d integer array")
+                if h.size and (h.min() < 0 or h.max() >= n):
+                    raise ValueError(f"{name} holds an index outside its table of {n} rows")
+                r = torch.from_numpy(np.ascontiguousarray(h, dtype=np.int32)).to(cat.device)
+            if r.dtype != torch.int32 or r.dim() != 1 or not r.is_contiguous() or r.device != cat.device:
+                raise ValueError(f"{name} must be a contiguous 1-d int32 tensor on the tables' device")
+            rows.append(r)
+        if rows[0].numel() != rows[1].numel():
+            raise ValueError("cat_row and an_row must hold one index per sample each")
+        if cat.shape[0] < 1 or an.shape[0] < 1:
+            raise ValueError("the tables need at least one row each")
+    elif cat.shape != an.shape:
+        raise ValueError("pooled_cat and pooled_an must hold one row per sample each")
+    B = int(rows[0].numel()) if rows is not None else int(cat.shape[0])
+    if y.numel() != B:
+        raise ValueError("y must hold one value per sample")
+    sw = None
+    if sample_weight is not None:
+        require_gpu(sample_weight)
+        sw = f32c(sample_weight).reshape(-1)
+        if sw.numel() != B:
+            raise ValueError("sample_weight must hold one value per sample")
+    return cat, an, rows, weights, y, sw, B
+
+
+def _transfer_drop_args(cfg):
+    drop = cfg.get("dropout")
+    return drop.args() if drop is not None and drop.rate > 0.0 else (0.0, C.c_uint64(0), None, 0)
+
+
+def transfer_head_loss_rows(cat_table, an_table, cat_row, an_row, weights, cfg, y, workspace, sample_weight=None,
+                            keep=True):
+    """The transfer head's loss over indexed rows, forward (impnn_transfer_head_loss_rows): sample b is
+    (cat_table[cat_row[b]], an_table[an_row[b]]) -> (loss 0-d, pred (B), saved or None), no autograd (the training
+    node is autograd.TransferHeadLoss with cfg["rows"]).  ``cfg``: MPNNModel._transfer_cfg; ``workspace``: a float
+    tensor whose first word is zero; ``keep``: fill the buffer the backward reads.  With ``cat_row = an_row = None`` the
+    first two arguments are the samples' own rows and the call is impnn_weighted_transfer_head_loss: the same code
+    behind the load, the same bits on the gathered rows."""
+    cat, an, rows, weights, y, sw, B = _transfer_loss_operands(cat_table, an_table, cat_row, an_row, weights, y,
+                                                               sample_weight)
+    lib = _lib.load()
+    F, Mx, D = cfg["fp_size"], cfg["mixing_size"], int(cat.shape[1])
+    keep = bool(keep) or bool(cfg["bn_batch"])
+    n_saved = int(lib.impnn_transfer_head_saved_floats(B, F, Mx)) if keep and B else 0
+    saved = torch.empty(n_saved, dtype=torch.float32, device=cat.device) if keep else None
+    loss = torch.zeros((), dtype=torch.float32, device=cat.device)
+    pred = torch.empty(B, dtype=torch.float32, device=cat.device)
+    lam = (C.c_float * 18)(*[float(v) for v in cfg["l2"]])
+    table = (C.c_void_p * 18)(*[w.data_ptr() for w in weights])
+    head = (table, lam, ptr(cfg["moving_mean"]), ptr(cfg["moving_variance"]), cfg["momentum"], cfg["epsilon"],
+            1 if cfg["bn_batch"] else 0, ptr(y), None if sw is None else ptr(sw), cfg["loss_kind"], cfg["delta"],
+            *_transfer_drop_args(cfg), ptr(saved) if keep else None, n_saved, ptr(pred), ptr(loss), ptr(workspace),
+            workspace.numel())
+    with torch.cuda.device(cat.device):
+        if rows is None:
+            check(lib.impnn_weighted_transfer_head_loss(ptr(cat), ptr(an), *head, B, D, F, Mx, stream_ptr()))
+        else:
+            check(lib.impnn_transfer_head_loss_rows(ptr(cat), ptr(an), ptr(rows[0]), ptr(rows[1]), *head, B,
+                                                    int(cat.shape[0]), int(an.shape[0]), D, F, Mx, stream_ptr()))
+    return loss, pred, saved
+
+
+def transfer_head_loss_rows_bwd(cat_table, an_table, cat_row, an_row, weights, dweights, cfg, y, dloss, saved,
+                                sample_weight=None):
+    """The backward of ``transfer_head_loss_rows`` (impnn_transfer_head_loss_rows_bwd): ADDS the parameter gradients
+    into ``dweights[t]`` (18 entries; None: a frozen tensor, nothing is computed for it).  ``cfg`` and ``saved`` are
+    the forward's.  ``cat_row = an_row = None``: impnn_weighted_transfer_head_loss_bwd on the samples' own rows,
+    without dpooled."""
+    cat, an, rows, weights, y, sw, B = _transfer_loss_operands(cat_table, an_table, cat_row, an_row, weights, y,
+                                                               sample_weight)
+    if len(dweights) != 18:
+        raise ValueError("dweights: one entry (a tensor or None) per weight tensor")
+    for g, w in zip(dweights, weights):
+        if g is not None and (g.dtype != torch.float32 or not g.is_contiguous() or g.shape != w.shape
+                              or g.device != w.device):
+            raise ValueError("a gradient buffer must be a contiguous float32 tensor of its weight's shape and device")
+    require_gpu(dloss, saved)
+    lib = _lib.load()
+    F, Mx, D = cfg["fp_size"], cfg["mixing_size"], int(cat.shape[1])
+    dloss = f32c(dloss).reshape(1)
+    wsn = int(lib.impnn_transfer_head_bwd_workspace_floats(B, F, Mx))
+    ws = torch.empty(max(wsn, 1), dtype=torch.float32, device=cat.device)
+    lam = (C.c_float * 18)(*[float(v) for v in cfg["l2"]])
+    wt = (C.c_void_p * 18)(*[w.data_ptr() for w in weights])
+    gt = (C.c_void_p * 18)(*[g.data_ptr() if g is not None else None for g in dweights])
+    tail = (wt, gt, lam, 1 if cfg["bn_batch"] else 0, ptr(y), None if sw is None else ptr(sw), cfg["loss_kind"],
+            cfg["delta"], ptr(dloss), *_transfer_drop_args(cfg), ptr(saved), saved.numel(), ptr(ws), wsn)
+    with torch.cuda.device(cat.device):
+        if rows is None:
+            check(lib.impnn_weighted_transfer_head_loss_bwd(ptr(cat), ptr(an), *tail, None, None, B, D, F, Mx,
+                                                            stream_ptr()))
+        else:
+            check(lib.impnn_transfer_head_loss_rows_bwd(ptr(cat), ptr(an), ptr(rows[0]), ptr(rows[1]), *tail, B,
+                                                        int(cat.shape[0]), int(an.shape[0]), D, F, Mx, stream_ptr()))

@@ -344,9 +344,21 @@ class GraphedTrainStep:
         those 8*batch bytes between replays.  ``sample_weight`` (one value per sample of the batch) makes it the
         weighted step: the weights sit in a static buffer like y, and ``resident=(x, y_dev, w_dev)`` gathers their
         rows inside the capture too, with a second gather launch behind the first (the first takes at most 8 tensors
-        and stays as the unweighted step has it)."""
+        and stays as the unweighted step has it).
+        ``resident=(enc, y_dev[, w_dev])`` with a data.FrozenEncodings (stage 1 of transfer learning; the model's
+        ``frozen_encodings`` names the refusals): ``inputs`` is the first batch's sample rows (device int64).  The
+        captured step is then one gather of the batch's two ion indices, targets and weights, the head's loss over
+        indexed rows, its backward and the optimizer: no encoder launch, and ``step_on_rows`` copies only the rows."""
+        from .data import FrozenEncodings
         self.model = model
         dev = model.device
+        self.enc = resident[0] if resident is not None and isinstance(resident[0], FrozenEncodings) else None
+        if self.enc is not None:
+            model._frozen_cache_check()
+            if self.enc.stale(model):
+                raise ValueError("the encodings are older than the model's encoder weights: build them again")
+            rows0 = torch.as_tensor(inputs, dtype=torch.int64).to(dev).reshape(-1)
+            inputs = {}
         self.static_in = {k: v.clone() for k, v in model._to_device(inputs).items()}
         self.static_y = torch.as_tensor(np.asarray(y, np.float32)).to(dev).reshape(-1, 1).clone()
         self.batch = int(self.static_y.shape[0])
@@ -355,7 +367,25 @@ class GraphedTrainStep:
             self.static_w = checked_sample_weight(sample_weight, self.batch, dev).reshape(-1, 1).clone()
         self.resident = None
         self.resident_w = None
-        if resident is not None:
+        if self.enc is not None:
+            if (len(resident) == 3) != (self.static_w is not None):
+                raise ValueError("resident=(enc, y_dev, w_dev) goes with sample_weight, resident=(enc, y_dev) without")
+            enc, y_dev = self.enc, resident[1]
+            if rows0.numel() != self.batch:
+                raise ValueError("inputs must hold one sample row per value of y")
+            if not (y_dev.is_contiguous() and y_dev.dtype == torch.float32 and y_dev.numel() == len(enc)):
+                raise ValueError("resident targets must be a contiguous float32 tensor, one value per sample")
+            self.static_rows = rows0.clone()
+            self.static_cat_row = torch.index_select(enc.cat_row, 0, rows0)
+            self.static_an_row = torch.index_select(enc.an_row, 0, rows0)
+            srcs, dsts = [enc.cat_row, enc.an_row, y_dev.reshape(-1, 1)], [self.static_cat_row, self.static_an_row, self.static_y]
+            if self.static_w is not None:
+                w_dev = resident[2]
+                if not (w_dev.is_contiguous() and w_dev.dtype == torch.float32 and w_dev.numel() == len(enc)):
+                    raise ValueError("resident weights must be a contiguous float32 tensor, one value per sample")
+                srcs, dsts = srcs + [w_dev.reshape(-1, 1)], dsts + [self.static_w]
+            self.enc_gather = (srcs, dsts)
+        elif resident is not None:
             if (len(resident) == 3) != (self.static_w is not None):
                 raise ValueError("resident=(x, y_dev, w_dev) goes with sample_weight, resident=(x, y_dev) without")
             x, y_dev = resident[0], resident[1]
@@ -402,6 +432,16 @@ class GraphedTrainStep:
 
     def _step(self):
         m = self.model
+        if self.enc is not None:
+            from . import ops
+            ops.gather_rows(self.enc_gather[0], self.enc_gather[1], self.static_rows)
+            kw = {"metric_slot": "train"} if self.metrics else {}
+            loss = m._loss_encoded(self.enc, self.static_cat_row, self.static_an_row, self.static_y, True,
+                                   self.static_w, **kw)
+            loss.backward()
+            m.optimizer.apply_gradients()
+            m.optimizer.zero_grad()
+            return loss.detach()
         if self.resident is not None:
             from . import ops
             ops.gather_rows(self.resident[0], self.resident[1], self.static_rows)
@@ -419,6 +459,8 @@ class GraphedTrainStep:
         return loss.detach()
 
     def matches(self, inputs):
+        if self.enc is not None:
+            return inputs is self.enc
         return all(tuple(inputs[k].shape) == tuple(v.shape) for k, v in self.static_in.items())
 
     def step_on_rows(self, x, y_dev, rows, w_dev=None):
@@ -427,7 +469,11 @@ class GraphedTrainStep:
         host round trip).  ``w_dev``: the data set's weights, for a step that was built with ``sample_weight``."""
         if (w_dev is not None) != (self.static_w is not None):
             raise ValueError("a step captured with sample_weight takes weights on every call, one without takes none")
-        if self.resident is not None and x[next(iter(self.static_in))] is self.resident[0][0]:
+        if self.enc is not None:
+            if x is not self.enc or self.enc.stale(self.model):
+                raise ValueError("a step captured over encodings replays on those encodings, while they are current")
+            self.static_rows.copy_(rows)  # the gather of the batch's indices, targets and weights is the first node
+        elif self.resident is not None and x[next(iter(self.static_in))] is self.resident[0][0]:
             self.static_rows.copy_(rows)  # the gather is the first node of the graph
         else:
             for k, v in self.static_in.items():
@@ -440,6 +486,8 @@ class GraphedTrainStep:
         return self.static_loss
 
     def __call__(self, inputs, y, sample_weight=None):
+        if self.enc is not None:
+            raise ValueError("a step captured over encodings takes sample rows: step_on_rows(enc, y_dev, rows)")
         if (sample_weight is not None) != (self.static_w is not None):
             raise ValueError("a step captured with sample_weight takes weights on every call, one without takes none")
         for k, v in self.static_in.items():
