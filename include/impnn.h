@@ -905,6 +905,18 @@ int impnn_domain_rows(const float* z, const float* ref, int32_t exclude_self, fl
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,
                       const int64_t* rows, int32_t n_rows, impnn_stream_t stream);
 
+/*  Cached frozen steps (data.FrozenStates): the atom states of every distinct ion after its last frozen step live in
+ *  one table per ion; a training pass starts from the batch's rows of them.
+ *  out[t][b, :] = table[t][rows[t][b], :] for t < n_ions (1 or 2), one launch.  tables / rows / out / row_floats /
+ *  table_rows are HOST arrays; rows[t] is a device int32 array of B indices.  row_floats[t] > 0 and a multiple of 4
+ *  (16-byte lanes; tables[t] and out[t] 16-byte aligned, rows[t] 4-byte aligned); the two ions may differ in it.  An
+ *  index outside [0, table_rows[t]) writes a row of zeros and reads nothing.  B == 0: no launch.  A row is cut into
+ *  pieces of 4 KB, one workgroup each; row offsets are 64-bit.  Status: IMPNN_E_BADARG for n_ions outside 1..2, B < 0,
+ *  a null pointer, a non-positive or non-multiple-of-4 row_floats, a negative table_rows, a misaligned pointer;
+ *  IMPNN_E_UNSUPPORTED where B x pieces exceeds one launch.  There is no backward: the rows are constants of a pass. */
+int impnn_state_rows(int32_t n_ions, const float* const* tables, const int32_t* const* rows, float* const* out,
+                     const int64_t* row_floats, const int64_t* table_rows, int32_t B, impnn_stream_t stream);
+
 /* ---- f4: backward of the layer-at-a-time path and the optimizer step - what Keras autodiff and
  *      keras.optimizers.Adam(1e-3, clipnorm=1.0) do inside model.fit (train_viscosity.py:227-230,328-338;
  *      train_melting_point.py:205-208).  Every kernel is the adjoint of the forward entry of the same name,

@@ -173,6 +173,7 @@ SIGNATURES = {
     "impnn_regression_sums": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, i32, vp, vp]),
     "impnn_batch_assemble": (C.c_int, [i32, vp, i32, i32, PP, PP, PP, PP, PP, i32, i32, i32, PP, PP, PP, vp, vp, vp]),
     "impnn_gather_rows": (C.c_int, [i32, PP, PP, C.POINTER(i64), vp, i32, vp]),
+    "impnn_state_rows": (C.c_int, [i32, PP, PP, PP, C.POINTER(i64), C.POINTER(i64), i32, vp]),
     "impnn_validate_indices": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "impnn_profile_enable": (C.c_int, [i32]),
     "impnn_profile_collect": (C.c_int, [C.POINTER(C.c_float), i32, C.POINTER(i32)]),

@@ -1400,6 +1400,23 @@ int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* ds
   return launch_gather_rows(n_tensors, src, dst, row_bytes, rows, n_rows, as_stream(stream));
 }
 
+int impnn_state_rows(int32_t n_ions, const float* const* tables, const int32_t* const* rows, float* const* out,
+                     const int64_t* row_floats, const int64_t* table_rows, int32_t B, impnn_stream_t stream) {
+  REQUIRE(n_ions >= 1 && n_ions <= 2, "n_ions must be 1 or 2");
+  REQUIRE(B >= 0, "bad shape");
+  if (B == 0) return IMPNN_OK;
+  REQUIRE(tables && rows && out && row_floats && table_rows, "null pointer");
+  for (int t = 0; t < n_ions; ++t) {
+    REQUIRE(tables[t] && rows[t] && out[t], "null pointer");
+    REQUIRE(row_floats[t] > 0 && row_floats[t] % 4 == 0, "row_floats must be a positive multiple of 4");
+    REQUIRE(table_rows[t] >= 0, "table_rows must not be negative");
+    REQUIRE(((reinterpret_cast<uintptr_t>(tables[t]) | reinterpret_cast<uintptr_t>(out[t])) & 15u) == 0,
+            "tables and out must be 16-byte aligned");
+    REQUIRE((reinterpret_cast<uintptr_t>(rows[t]) & 3u) == 0, "rows must be 4-byte aligned");
+  }
+  return launch_state_rows(n_ions, tables, rows, out, row_floats, table_rows, B, as_stream(stream));
+}
+
 int impnn_profile_enable(int32_t capacity) {
   REQUIRE(capacity > 0 && capacity <= (1 << 20), "capacity out of range");
   impnn_profile_disable();

@@ -279,6 +279,8 @@ int launch_transfer_head(const TransferHeadCall& c);
 int launch_transfer_head_bwd(const TransferHeadCall& c);
 int launch_gather_rows(int n, const void* const* src, void* const* dst, const int64_t* row_bytes, const int64_t* rows,
                        int n_rows, hipStream_t s);
+int launch_state_rows(int n_ions, const float* const* tables, const int32_t* const* rows, float* const* out,
+                      const int64_t* row_floats, const int64_t* table_rows, int B, hipStream_t s);
 int launch_validate_indices(const int32_t* conn, const int32_t* atom_ids, const int32_t* bond_ids,
                             int32_t* counts, int B, int N, int E, int Va, int Vb, hipStream_t s);
 

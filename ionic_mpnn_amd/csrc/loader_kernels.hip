@@ -91,6 +91,42 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherRows g, const in
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Cached frozen steps (data.FrozenStates): out[t][b, :] = table[t][rows[t][b], :] for one or two ions, each with its
+// own int32 index and its own row length.  A row is the atom states of one ion, N * D floats (20 KB at N = 160,
+// D = 32), so it is cut into pieces of 4 KB: one workgroup per (sample, piece), 256 lanes x one 16-byte load and
+// store, the tail piece cut per lane.  The index is read once per workgroup; an index outside the table writes zeros
+// and reads nothing.  Row offsets are 64-bit (C * N * D may pass 2^31).
+// ---------------------------------------------------------------------------------------
+constexpr int kStatePieceFloats = 1024;  // 256 lanes x 4 floats
+struct StateRows {
+  const float* table[2];
+  const int32_t* rows[2];
+  float* out[2];
+  long long row_floats[2];
+  long long table_rows[2];
+  int pieces[2];  // ceil(row_floats / kStatePieceFloats)
+};
+__global__ __launch_bounds__(256) void state_rows_kernel(StateRows g, int pieces_max) {
+  const int t = blockIdx.y;  // uniform: constant-index selects stay scalar
+  const float* table = t ? g.table[1] : g.table[0];
+  const int32_t* rows = t ? g.rows[1] : g.rows[0];
+  float* out = t ? g.out[1] : g.out[0];
+  const long long row_floats = t ? g.row_floats[1] : g.row_floats[0];
+  const long long table_rows = t ? g.table_rows[1] : g.table_rows[0];
+  const int pieces = t ? g.pieces[1] : g.pieces[0];
+  const int b = blockIdx.x / pieces_max;
+  const int piece = blockIdx.x - b * pieces_max;
+  if (piece >= pieces) return;  // (the other ion's rows are longer)
+  const long long r = rows[b];
+  const bool present = r >= 0 && r < table_rows;
+  const long long at = (long long)piece * kStatePieceFloats + 4 * (int)threadIdx.x;
+  if (at >= row_floats) return;  // the tail piece, per lane (row_floats is a multiple of 4: whole lanes only)
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (present) v = *reinterpret_cast<const float4*>(table + r * row_floats + at);
+  *reinterpret_cast<float4*>(out + (long long)b * row_floats + at) = v;
+}
+
 }  // namespace
 
 int launch_batch_assemble(int n_ions, const int32_t* sample_idx, int B, int M, const int32_t* const* atom_flat,
@@ -130,6 +166,23 @@ int launch_gather_rows(int n, const void* const* src, void* const* dst, const in
   }
   gather_rows_kernel<<<dim3(n_rows < 4096 ? n_rows : 4096, n), 256, 0, s>>>(g, rows, n_rows);
   return check_launch("gather_rows");
+}
+
+int launch_state_rows(int n_ions, const float* const* tables, const int32_t* const* rows, float* const* out,
+                      const int64_t* row_floats, const int64_t* table_rows, int B, hipStream_t s) {
+  StateRows g{};
+  int pieces_max = 0;
+  for (int t = 0; t < n_ions; ++t) {
+    const int64_t pieces = (row_floats[t] + kStatePieceFloats - 1) / kStatePieceFloats;
+    if (pieces * B > 0x7fffffff)
+      return fail(IMPNN_E_UNSUPPORTED, "state_rows: %lld pieces of ion %d x %d samples exceed one launch",
+                  (long long)pieces, t, B);
+    g.table[t] = tables[t]; g.rows[t] = rows[t]; g.out[t] = out[t];
+    g.row_floats[t] = row_floats[t]; g.table_rows[t] = table_rows[t]; g.pieces[t] = (int)pieces;
+    pieces_max = pieces > pieces_max ? (int)pieces : pieces_max;
+  }
+  state_rows_kernel<<<dim3((unsigned)B * pieces_max, n_ions), 256, 0, s>>>(g, pieces_max);
+  return check_launch("state_rows");
 }
 
 }  // namespace impnn

@@ -286,6 +286,7 @@ class MPNNModel:
         self.encoder_workgroups = 0  # persistent workgroups per encoder launch (0: library default, one per CU)
         self._transfer_grid_image = None
         self._encoder_version = 0  # moves on whenever the encoder's packed weights are dropped (data.FrozenEncodings)
+        self._frozen_state_version = 0  # moves on when weights are written from outside a step (data.FrozenStates)
         self.grid_head_mode = "auto"  # "auto" | "gathered": predict_grid's head for the transfer model
 
     # ------------------------------------------------------------------ construction
@@ -473,6 +474,7 @@ class MPNNModel:
         self._split_deg_limit = None
         self._head_packed = None
         self._encoder_version += 1
+        self._frozen_state_version += 1
         for p in ("cat", "an"):
             for lyr in self.branches[p]["bmm"]:
                 lyr.invalidate_cache()
@@ -502,6 +504,20 @@ class MPNNModel:
         ``weights_updated`` of a model whose encoder trains move it on, with the packed weights they drop.  What was
         computed from the encoder at an older version (data.FrozenEncodings) is stale."""
         return self._encoder_version
+
+    @property
+    def frozen_state_version(self):
+        """The version of the weights a step cannot change: ``invalidate_packed_weights`` (so ``load_weights``) moves
+        it on, ``weights_updated`` does not - a training step writes trainable variables only, and what was computed
+        from the frozen ones (data.FrozenStates) stays valid while ``frozen_prefix()`` stays what it was."""
+        return self._frozen_state_version
+
+    def frozen_prefix(self):
+        """{"cat": s, "an": s}: per ion, what ``_first_trained_step`` returns inside a differentiated pass, read from
+        the ``requires_grad`` flags that ``compile()`` set.  0: nothing is cacheable (an embedding or step 0 trains);
+        1..num_steps-1: the atom embedding and steps 0..s-1 are frozen; None: the ion's whole encoder is."""
+        with torch.enable_grad():
+            return {p: self._first_trained_step(p) for p in ("cat", "an")}
 
     def _cache_refs(self):
         """The cached tensors a captured step may read (kept alive by train.GraphedTrainStep)."""
@@ -656,16 +672,31 @@ class MPNNModel:
         return ops.Dropout(self.dropout_rate, self.dropout_seed, ops.dropout_layer_word(lid, idist.dropout_rank()), step)
 
     def encode_layered(self, prefix, atom_ids, bond_ids, conn, trace=None, typed=True, type_mats=None,
-                       dropout_step=None):
+                       dropout_step=None, start=0, h0=None):
         """encode() layer at a time (train_viscosity.py:171-187) -> pooled (B,D); type_mats: _all_type_matrices().
-        dropout_step: the pass's dropout snapshot (a training pass of a model with dropout_rate > 0), else None."""
+        dropout_step: the pass's dropout snapshot (a training pass of a model with dropout_rate > 0), else None.
+        ``start=s, h0=h`` (cached frozen steps, data.FrozenStates): the pass resumes at step s from the atom states
+        ``h0`` (B,N,D) as they stand after step s-1 - no atom embedding launch, no step below s; every row of ``h0``,
+        padding included, must be finite.  s may not lie above the ion's first trained step."""
         br = self.branches[prefix]
         graph = ops.IonGraph(atom_ids, bond_ids, conn, self.bond_vocab_size)  # the message calls of all layers share it
-        h = self.atom_emb(atom_ids)
+        s0 = self._first_trained_step(prefix)
+        if h0 is None:
+            if start != 0:
+                raise ValueError("encode_layered: start > 0 needs the atom states h0 to start from")
+            h = self.atom_emb(atom_ids)
+        else:
+            if not 0 < start < self.num_steps or trace is not None or not typed:
+                raise ValueError(f"encode_layered: a resumed pass starts at a step in 1..{self.num_steps - 1}, typed, "
+                                 "without a trace")
+            if s0 is not None and start > s0:
+                raise ValueError(f"encode_layered: start={start} lies above the {prefix} ion's first trained step {s0}")
+            if tuple(h0.shape) != tuple(atom_ids.shape) + (self.atom_dim,) or h0.dtype != torch.float32:
+                raise ValueError(f"encode_layered: h0 must be float32 {tuple(atom_ids.shape) + (self.atom_dim,)}")
+            h = h0
         bond = self.bond_emb(bond_ids)
         if not typed:
             bond = bond.dense()
-        s0 = self._first_trained_step(prefix)
         one_node = typed and trace is None and s0 is not None  # training: a whole step as one autograd node
         # inference through the layered path (what serves atom_dim 64 / 128): GatedUpdate only on the rows an
         # encode() loop has to carry - padding atoms can reach neither a message nor the pool (include/impnn.h,
@@ -679,7 +710,7 @@ class MPNNModel:
             #  AND backward on the list, impnn_gated_update_rows_bwd - padding atoms carry no gradient; below that a
             #  step is bound by its launch count and the list's own launches cost more than the skipped rows save)
             rows = ops.kept_row_index(atom_ids, bond_ids, conn, self.bond_vocab_size)
-        for i in range(self.num_steps):
+        for i in range(start, self.num_steps):
             drop = self._layer_dropout(prefix, i, dropout_step) if dropout_step is not None else None
             if one_node and i >= s0:
                 from . import autograd
@@ -725,9 +756,16 @@ class MPNNModel:
         return self._pipeline.plan(ions, self.atom_dim, self.bond_dim, self.num_steps, self.atom_vocab_size,
                                    self.bond_vocab_size, mode=mode, workgroups=self.encoder_workgroups)
 
-    def encode_pooled(self, inputs, fused=None, trace=None, plan=None, training=False, dropout_step=None):
+    def encode_pooled(self, inputs, fused=None, trace=None, plan=None, training=False, dropout_step=None, states=None):
         """Both ions' GlobalSumPool outputs: the hot path.  ``training`` (layer at a time only):
-        a training pass - GatedUpdate's dropout applies when the model has a rate above 0."""
+        a training pass - GatedUpdate's dropout applies when the model has a rate above 0.
+        ``states=(st, cat_row, an_row)`` (a training pass over data.FrozenStates; cat_row / an_row: the batch's (B)
+        int32 rows of st's tables): one impnn_state_rows launch for both ions comes first; an ion with frozen steps
+        resumes the layered pass behind them, an ion whose whole encoder is frozen takes its row as its pooled vector."""
+        if states is not None:
+            if plan is not None or fused or trace is not None or not training:
+                raise ValueError("states go with a layered training pass (no plan, no fused encoder, no trace)")
+            return self._encode_resumed(inputs, states)
         if plan is not None:
             mode = plan.mode
             pc, pa = self._pipeline.run(plan, self.atom_emb.embeddings, self.bond_emb.embeddings,
@@ -772,7 +810,37 @@ class MPNNModel:
         return (self.encode_layered("cat", ca, cb, cc, trace, type_mats=tm, dropout_step=ds),
                 self.encode_layered("an", aa, ab, ac, trace, type_mats=tm, dropout_step=ds))
 
-    def _encode_two_streams(self, cat, an, tm, dropout_step=None):
+    def _encode_resumed(self, inputs, states):
+        """encode_pooled over cached frozen steps (DESIGN.md 6.1 "Cached frozen steps"; ``_loss`` has refused what
+        ``_frozen_steps_check`` refuses, GatedUpdate dropout among it: the pass has no dropout snapshot)."""
+        st, cat_row, an_row = states
+        if st.stale(self):
+            raise ValueError(f"the states were made at frozen-state version {st.version} for the prefix {st.steps}, the "
+                             f"model is at {self.frozen_state_version} with {self.frozen_prefix()} (load_weights, or a "
+                             "compile that moved the first trained step): build them again")
+        pre = st.steps
+        ions = {"cat": (inputs["cat_atom"], inputs["cat_bond"], inputs["cat_connectivity"]),
+                "an": (inputs["an_atom"], inputs["an_bond"], inputs["an_connectivity"])}
+        B = int(ions["cat"][0].shape[0])
+        kept = [(p, t, r) for p, t, r in (("cat", st.cat, cat_row), ("an", st.an, an_row)) if pre[p] != 0]
+        for p, t, r in kept:
+            if r.numel() != B or (pre[p] is not None and t.shape[1] != ions[p][0].shape[1]):
+                raise ValueError(f"the {p} states hold rows of {t.shape[1]} atoms for {r.numel()} samples; the batch has "
+                                 f"{B} samples of {ions[p][0].shape[1]} atoms")
+        got = dict(zip([p for p, _, _ in kept],
+                       ops.state_rows([t for _, t, _ in kept], [r for _, _, r in kept])))  # one launch, both ions
+        layered = [p for p in ("cat", "an") if pre[p] is not None]
+        tm = self._all_type_matrices()
+        resume = {p: (pre[p], got.get(p)) for p in layered}
+        ca = ions["cat"][0]
+        if len(layered) == 2 and getattr(self, "two_streams", True) and ca.is_cuda \
+                and ca.shape[0] <= int(os.environ.get("IMPNN_TWO_STREAM_MAX_BATCH", TWO_STREAM_MAX_BATCH)):
+            return self._encode_two_streams(ions["cat"], ions["an"], tm, None, resume)
+        # (an ion whose whole encoder is frozen: its gathered (B,1,D) row IS its pooled vector)
+        return tuple(self.encode_layered(p, *ions[p], None, type_mats=tm, start=resume[p][0], h0=resume[p][1])
+                     if p in resume else got[p].reshape(B, self.atom_dim) for p in ("cat", "an"))
+
+    def _encode_two_streams(self, cat, an, tm, dropout_step=None, resume=None):
         """Layer-at-a-time path: the two ions' chains are independent until the head, and most of their kernels
         leave part of the chip idle (a batch-32 kernel nearly all of it) - the anion chain runs on a second HIP stream
         (in training: a parallel branch of the captured hipGraph; autograd replays each node's backward on the stream
@@ -798,10 +866,14 @@ class MPNNModel:
             t.record_stream(side)
         if dropout_step is not None:
             dropout_step.record_stream(side)
+        # (resume: {ion: (start, h0)} of a pass over cached frozen steps; the side stream reads the anion's gathered h0)
+        kc, ka = ({} if resume is None else dict(zip(("start", "h0"), resume[p])) for p in ("cat", "an"))
+        if ka.get("h0") is not None:
+            ka["h0"].record_stream(side)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
-            pa = self.encode_layered("an", *an, None, type_mats=tm, dropout_step=dropout_step)
-        pc = self.encode_layered("cat", *cat, None, type_mats=tm, dropout_step=dropout_step)
+            pa = self.encode_layered("an", *an, None, type_mats=tm, dropout_step=dropout_step, **ka)
+        pc = self.encode_layered("cat", *cat, None, type_mats=tm, dropout_step=dropout_step, **kc)
         cur.wait_stream(side)
         pa.record_stream(cur)
         self._side_stream_used = True
@@ -949,29 +1021,35 @@ class MPNNModel:
             buf = self._metric_pred_buf = torch.zeros(max(B, 4096), dtype=torch.float32, device=self.device)
         return buf[:B]
 
-    def _loss(self, inputs, y, training, sample_weight=None, metric_slot=None):
+    def _loss(self, inputs, y, training, sample_weight=None, metric_slot=None, states=None):
         """The batch loss.  ``sample_weight`` (one finite value >= 0 per sample, or None) makes it keras's weighted
         loss, (1/B) sum_b w_b L_b + penalties, B counting the samples of weight 0 too; it touches the loss only, never
         BatchNormalization's statistics or a dropout mask.  ``metric_slot`` ("train" / "eval"; a model compiled with
         metrics): the pass's predictions are kept and added to that slot's records behind the loss, one
-        impnn_regression_sums launch per record; None leaves every call as it is without metrics."""
+        impnn_regression_sums launch per record; None leaves every call as it is without metrics.
+        ``states=(st, cat_row, an_row)``: a training pass that resumes each ion's encoder from its rows of a
+        data.FrozenStates (encode_pooled); refused where ``_frozen_steps_check`` refuses."""
         from . import train
+        if states is not None:
+            self._frozen_steps_check()
+            if not training:
+                raise ValueError("cache_frozen_steps: states serve a training pass; inference runs the fused encoder")
         y = torch.as_tensor(y, dtype=torch.float32).to(self.device).reshape(-1, 1)
         sw = train.checked_sample_weight(sample_weight, int(y.shape[0]), self.device)
         ms = getattr(self, "_metric_set", None) if metric_slot is not None else None
         if ms is None or y.shape[0] == 0:
-            return self._loss_and_pred(inputs, y, training, sw, False)[0]
-        loss, pred = self._loss_and_pred(inputs, y, training, sw, True)
+            return self._loss_and_pred(inputs, y, training, sw, False, states)[0]
+        loss, pred = self._loss_and_pred(inputs, y, training, sw, True, states)
         ms.accumulate(metric_slot, pred.detach().to(torch.float32).reshape(-1).contiguous(), y.reshape(-1), sw)
         return loss
 
-    def _loss_and_pred(self, inputs, y, training, sw, keep_pred):
+    def _loss_and_pred(self, inputs, y, training, sw, keep_pred, states=None):
         """(loss, predictions or None) of _loss; ``keep_pred`` hands the fused loss kernels a buffer for them."""
         from . import train
         covered = y.shape[0] > 0 and self._head_kernels_cover()
         pbuf = self._metric_pred(int(y.shape[0])) if keep_pred else None
         if self.kind == "transfer" and covered:
-            return self._transfer_loss(self._to_device(inputs), y, training, sw, pbuf), pbuf
+            return self._transfer_loss(self._to_device(inputs), y, training, sw, pbuf, states), pbuf
         if training and torch.is_grad_enabled() and covered and self._head_nodes_cover() and self._loss_name() == "mse":
             # head, mse and the l2 penalties as ONE node (impnn_model_head_loss): ~25 launches fewer per step
             from . import autograd
@@ -980,11 +1058,13 @@ class MPNNModel:
             ws = getattr(self, "_loss_ws", None)
             if ws is None or ws.numel() < need:
                 ws = self._loss_ws = torch.zeros(max(need, 1024), dtype=torch.float32, device=self.device)
-            pc, pa = self.encode_pooled(inputs, fused=False, training=True)
+            pc, pa = self.encode_pooled(inputs, fused=False, training=True, states=states)
             T = inputs.get("temperature") if self.kind == "viscosity" else None
             l2 = self._head_l2() if sw is None and pbuf is None else autograd.WeightedL2(self._head_l2(), sw, pbuf)
             return autograd.ModelHeadLoss.apply({"viscosity": 0, "melting_point": 1}[self.kind], self.fp_size,
                                                 self.mixing_size, l2, ws, pc, pa, T, y, *self._head_tensors()), pbuf
+        if states is not None:  # (_frozen_steps_check lets only the two fused loss nodes through)
+            raise ValueError("cache_frozen_steps: an empty batch has no resumed pass")
         pred = self(inputs, training=True) if training else self(inputs)
         fn = train.mse if self._loss_name() == "mse" else train.Huber(self._loss_delta())
         if sw is not None:
@@ -1003,7 +1083,7 @@ class MPNNModel:
         mode = self.resolve_encoder_mode(N, E)
         return mode is not None and ops.encoder_overflow_possible(N, E, self.atom_dim, mode)
 
-    def _transfer_loss(self, inputs, y, training, sample_weight=None, pred=None):
+    def _transfer_loss(self, inputs, y, training, sample_weight=None, pred=None, states=None):
         """The transfer model's loss as one node (impnn_transfer_head_loss[_bwd], the weighted entries with a
         ``sample_weight``).  An encoder with nothing to train
         computes the pooled vectors as inference does - fused encoder where the shape allows, no graph, nothing saved -
@@ -1018,7 +1098,7 @@ class MPNNModel:
         # one snapshot of the step counter per training pass, shared by the encoder's GatedUpdates and the head
         ds = ops.dropout_step(self.dropout_counter()) if training else None
         if training and self._encoder_trains():
-            pc, pa = self.encode_pooled(inputs, fused=False, training=True, dropout_step=ds)
+            pc, pa = self.encode_pooled(inputs, fused=False, training=True, dropout_step=ds, states=states)
         else:
             with torch.no_grad():
                 if training and self.dropout_rate > 0.0:
@@ -1127,6 +1207,83 @@ class MPNNModel:
         out = {"loss": float(host[0]) / max(n, 1), **ms.results(host[1:])}
         return out if return_dict else list(out.values())
 
+    # ---- fine-tuning over cached frozen steps (data.FrozenStates; DESIGN.md "Cached frozen steps")
+    def _frozen_steps_check(self):
+        """ValueError unless a training pass of this model can start each ion's layered encoder behind steps that
+        cannot change: what ``cache_frozen_steps=True`` and ``frozen_states`` require.  Raised before the library is
+        reached."""
+        from . import dist as idist
+        pre = self.frozen_prefix()
+        why = None
+        if pre["cat"] == 0 and pre["an"] == 0:
+            why = "nothing below the first trained step is frozen (an embedding or step 0 of both ions trains)"
+        elif pre["cat"] is None and pre["an"] is None:
+            why = ("the whole encoder is frozen: no step is left to resume" +
+                   (" - cache_frozen_encoder=True serves this case" if self.kind == "transfer" else ""))
+        elif self.dropout_rate > 0.0:
+            why = (f"the encoder's GatedUpdate dropout rate is {self.dropout_rate}: a training pass draws masks on frozen "
+                   "steps too, so their atom states differ from step to step")
+        elif idist.is_distributed():
+            why = "torch.distributed is initialised: data-parallel fits keep no states"
+        elif not self._head_kernels_cover():
+            why = (f"the training pass is not one of the fused loss nodes: the head kernels do not cover atom_dim "
+                   f"{self.atom_dim}, fp_size {self.fp_size}, mixing_size {self.mixing_size}")
+        elif self.kind != "transfer" and self._loss_name() != "mse":
+            why = (f"the training pass is not one of the fused loss nodes: a {self.kind} model compiled with "
+                   f"{self._loss_name()} runs its head layer by layer")
+        elif not self._head_nodes_cover():  # (asks the library for the head's size: the last question)
+            why = (f"the training pass is not one of the fused loss nodes: the head's backward does not hold atom_dim "
+                   f"{self.atom_dim}, fp_size {self.fp_size}, mixing_size {self.mixing_size} in LDS")
+        if why is not None:
+            raise ValueError(f"cache_frozen_steps: the frozen steps cannot be cached - {why}")
+
+    def frozen_states(self, inputs, batch_size=4096):
+        """data.FrozenStates of padded model inputs: every distinct ion once through its frozen steps.  Refused
+        (ValueError) where ``fit(cache_frozen_steps=True)`` is."""
+        self._frozen_steps_check()
+        return data.FrozenStates.build(self, inputs, batch_size)
+
+    def frozen_step_states(self, prefix, ions, steps, batch_size=4096):
+        """The atom states (n, N, D) of the distinct ions ``ions`` ({"atom", "bond", "connectivity"}, padded int32
+        arrays) after steps 0..steps-1 of the ``prefix`` ion's encoder: the table of data.FrozenStates.  Runs under
+        no_grad on the layered kernels a training pass uses below its first trained step (typed message, Reduce,
+        GatedUpdate over ALL rows: no kept-row list, so padding rows hold the finite values those kernels compute)."""
+        br = self.branches[prefix]
+        atom, bond, conn = (torch.from_numpy(a) for a in _ion_numpy(ions, f"{prefix} ions"))
+        n, N = int(atom.shape[0]), int(atom.shape[1])
+        out = torch.empty((n, N, self.atom_dim), dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            for lo in range(0, n, int(batch_size)):
+                sl = slice(lo, min(n, lo + int(batch_size)))
+                a, b, c = (t[sl].to(self.device).contiguous() for t in (atom, bond, conn))
+                graph = ops.IonGraph(a, b, c, self.bond_vocab_size)
+                h, bd = self.atom_emb(a), self.bond_emb(b)
+                for i in range(steps):
+                    m = ops.bmm_message_typed(h, bd.ids, c, br["bmm"][i]._type_matrices(bd.table), graph)
+                    h = br["update"][i]([h, br["reduce"][i]([m, c[:, :, 1], h])])
+                out[sl] = h
+        return out
+
+    def train_on_state_batch(self, states, x, rows, y, sample_weight=None, metric_slot=None):
+        """``train_on_batch`` on the samples ``rows`` (device int64) of the device-resident padded inputs ``x``, each
+        ion's encoder resumed from ``states`` (data.FrozenStates of ``x``): ``y`` and ``sample_weight`` hold one value
+        per sample of the batch."""
+        if getattr(self, "optimizer", None) is None:
+            self.compile()
+        self._frozen_steps_check()
+        kw = {} if metric_slot is None else {"metric_slot": metric_slot}
+        x = self._to_device(x)
+        rows = torch.as_tensor(rows, dtype=torch.int64).to(self.device).reshape(-1)
+        loss = self._loss({k: v[rows] for k, v in x.items()}, y, training=True, sample_weight=sample_weight,
+                          states=(states, torch.index_select(states.cat_row, 0, rows),
+                                  torch.index_select(states.an_row, 0, rows)), **kw)
+        loss.backward()
+        self.join_training_streams()
+        self.optimizer.apply_gradients()
+        self.optimizer.zero_grad()
+        self.weights_updated()
+        return loss.detach()
+
     def train_on_batch(self, inputs, y, sample_weight=None, group=None, n_global=None, metric_slot=None):
         """One optimizer step on one mini-batch -> the batch loss (MSE + penalties) as a 0-d tensor.
         ``sample_weight``: one finite value >= 0 per sample (of this rank's shard): the loss is keras's
@@ -1202,7 +1359,7 @@ class MPNNModel:
         return out if return_dict else list(out.values())
 
     def fit(self, x, y, validation_data=None, epochs=1, batch_size=32, callbacks=None, shuffle=True, verbose=0,
-            seed=None, graph=True, sample_weight=None, cache_frozen_encoder=False):
+            seed=None, graph=True, sample_weight=None, cache_frozen_encoder=False, cache_frozen_steps=False):
         """model.fit as the trainers call it (train_viscosity.py:328-338): per epoch a fresh shuffle,
         mini-batches of ``batch_size``, `loss` = sample-weighted mean of the batch losses, `val_loss` from
         evaluate(); callbacks see on_train_begin / on_epoch_begin / on_epoch_end / on_train_end.  Returns a History.
@@ -1221,10 +1378,22 @@ class MPNNModel:
         set is encoded once, before the first epoch (data.FrozenEncodings), and every step - the captured one and the
         eager last batch - and the validation run the head's loss over indexed rows: no encoder launch, no batch
         gather.  A ValueError names the reason where that is not possible: not a transfer model, a trainable encoder
-        layer, GatedUpdate dropout above 0, widths the head kernels do not cover, torch.distributed."""
+        layer, GatedUpdate dropout above 0, widths the head kernels do not cover, torch.distributed.
+        ``cache_frozen_steps=True`` (stage 2, or any fine-tuning with the lower steps frozen): every distinct ion of
+        ``x`` runs once through the steps below its first trained one (data.FrozenStates), before the first epoch and
+        again at the start of an epoch that finds the states stale; every training step - the captured one and the
+        eager last batch - gathers the batch's rows with one impnn_state_rows launch and resumes the layered pass
+        there.  Validation is unchanged (inference runs the fused encoder).  A ValueError names the reason where that
+        is not possible: nothing frozen below the first trained step, the whole encoder frozen, GatedUpdate dropout
+        above 0, torch.distributed, a training pass that is not one of the fused loss nodes, both cache flags."""
         from . import train
         if getattr(self, "optimizer", None) is None:
             self.compile()
+        if cache_frozen_steps and cache_frozen_encoder:
+            raise ValueError("cache_frozen_steps: given together with cache_frozen_encoder - a model has either a "
+                             "frozen encoder (cache_frozen_encoder) or frozen lower steps (cache_frozen_steps)")
+        if cache_frozen_steps:
+            self._frozen_steps_check()
         if cache_frozen_encoder:
             self._frozen_cache_check()
         y = np.asarray(y, dtype=np.float32)
@@ -1270,10 +1439,16 @@ class MPNNModel:
             enc = data.FrozenEncodings.build(self, x)
             if validation_data is not None and len(validation_data[0]["cat_atom"]):
                 val_enc = data.FrozenEncodings.build(self, validation_data[0])
+        st = None
+        if cache_frozen_steps and n:  # every distinct ion through its frozen steps once, before the first epoch
+            x = {k: v.contiguous() for k, v in x.items()}
+            st = data.FrozenStates.build(self, x)
         for epoch in range(int(epochs)):
             for cb in callbacks:
                 if hasattr(cb, "on_epoch_begin"):
                     cb.on_epoch_begin(epoch, {})
+            if st is not None and st.stale(self):  # (a callback loaded weights: the states again, capture again)
+                st, graphed = data.FrozenStates.build(self, x), None
             if enc is not None and enc.stale(self):  # (a callback loaded weights: encode again, capture again)
                 enc, graphed = data.FrozenEncodings.build(self, x), None
                 val_enc = None if val_enc is None else data.FrozenEncodings.build(self, validation_data[0])
@@ -1298,13 +1473,17 @@ class MPNNModel:
                 elif use_graph and len(idx) == batch_size:
                     if graphed is None:
                         x = {k: v.contiguous() for k, v in x.items()}
+                        skw = {} if st is None else {"states": st}
                         if w_dev is None:
                             graphed = train.GraphedTrainStep(self, {k: v[tidx] for k, v in x.items()}, y[idx],
-                                                             resident=(x, y_dev))
+                                                             resident=(x, y_dev), **skw)
                         else:
                             graphed = train.GraphedTrainStep(self, {k: v[tidx] for k, v in x.items()}, y[idx],
-                                                             resident=(x, y_dev, w_dev), sample_weight=w_dev[tidx])
+                                                             resident=(x, y_dev, w_dev), sample_weight=w_dev[tidx], **skw)
                     loss = graphed.step_on_rows(x, y_dev, tidx, w_dev)
+                elif st is not None:
+                    loss = self.train_on_state_batch(st, x, tidx, y_dev[tidx], None if w_dev is None else w_dev[tidx],
+                                                     **mkw)
                 elif distributed:
                     from .data import shard_bounds
                     s0, s1 = shard_bounds(len(idx), world, rank)

@@ -727,6 +727,38 @@ def gather_rows(srcs, dsts, rows):
         check(_lib.load().impnn_gather_rows(n, st, dt, bt, ptr(rows), n_rows, stream_ptr()))
 
 
+def state_rows(tables, rows, out=None):
+    """out[t][b] = tables[t][rows[t][b]] for one or two ions in one launch (impnn_state_rows): the batch's rows of
+    data.FrozenStates, where a resumed training pass starts.  tables[t]: contiguous float32 (R_t, ...) whose row holds
+    a multiple of 4 floats; rows[t]: contiguous device int32, B indices (one outside its table yields a row of zeros);
+    out[t]: (B, ...) buffers to fill (a captured step's static ones), made here when None.  -> the list of outputs."""
+    n = len(tables)
+    if n not in (1, 2) or len(rows) != n or (out is not None and len(out) != n):
+        raise ValueError("state_rows takes one or two tables, each with its index (and its output)")
+    B = int(rows[0].numel())
+    if out is None:
+        out = [torch.empty((B,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device) for t in tables]
+    require_gpu(*tables, *rows, *out)
+    rf = []
+    for tb, r, o in zip(tables, rows, out):
+        if tb.dtype != torch.float32 or o.dtype != torch.float32 or not (tb.is_contiguous() and o.is_contiguous()):
+            raise TypeError("state_rows needs contiguous float32 tables and outputs")
+        if r.dtype != torch.int32 or not r.is_contiguous() or r.dim() != 1 or r.numel() != B:
+            raise TypeError("state_rows needs one contiguous int32 index of B rows per table")
+        if tb.dim() < 2 or tuple(o.shape) != (B,) + tuple(tb.shape[1:]):
+            raise ValueError(f"state_rows: shapes {tuple(tb.shape)} -> {tuple(o.shape)} for {B} rows")
+        rf.append(int(np.prod(tb.shape[1:])))
+    if B == 0:
+        return out
+    with torch.cuda.device(out[0].device):
+        check(_lib.load().impnn_state_rows(
+            n, C.cast((C.c_void_p * n)(*[t.data_ptr() for t in tables]), _lib.PP),
+            C.cast((C.c_void_p * n)(*[t.data_ptr() for t in rows]), _lib.PP),
+            C.cast((C.c_void_p * n)(*[t.data_ptr() for t in out]), _lib.PP), (C.c_int64 * n)(*rf),
+            (C.c_int64 * n)(*[int(t.shape[0]) for t in tables]), B, stream_ptr()))
+    return out
+
+
 REGRESSION_SUM_WORDS = 8   # impnn_regression_sums_words()
 
 

@@ -338,7 +338,7 @@ class GraphedTrainStep:
     compiled with metrics keeps the training pass's predictions in a persistent buffer and the captured step ends
     with one impnn_regression_sums launch per metric record, adding the batch to the epoch's running record."""
 
-    def __init__(self, model, inputs, y, resident=None, sample_weight=None):
+    def __init__(self, model, inputs, y, resident=None, sample_weight=None, states=None):
         """``resident=(x, y_dev)``: the whole padded training set lives on the device; the captured step then starts
         with the gather of the rows in ``self.static_rows`` (impnn_gather_rows) and ``step_on_rows`` only refreshes
         those 8*batch bytes between replays.  ``sample_weight`` (one value per sample of the batch) makes it the
@@ -348,10 +348,23 @@ class GraphedTrainStep:
         ``resident=(enc, y_dev[, w_dev])`` with a data.FrozenEncodings (stage 1 of transfer learning; the model's
         ``frozen_encodings`` names the refusals): ``inputs`` is the first batch's sample rows (device int64).  The
         captured step is then one gather of the batch's two ion indices, targets and weights, the head's loss over
-        indexed rows, its backward and the optimizer: no encoder launch, and ``step_on_rows`` copies only the rows."""
+        indexed rows, its backward and the optimizer: no encoder launch, and ``step_on_rows`` copies only the rows.
+        ``states=st`` (a data.FrozenStates of the resident ``x``; the model's ``frozen_states`` names the refusals):
+        each ion's encoder resumes behind its frozen steps.  The batch's two ion indices ride in the second gather
+        launch, with the weights where there are any; then one impnn_state_rows node gathers the states and the
+        layered pass starts there.  ``step_on_rows`` still refreshes only the sample rows, and refuses to replay once
+        the states are stale."""
         from .data import FrozenEncodings
         self.model = model
         dev = model.device
+        self.states = states
+        if states is not None:
+            model._frozen_steps_check()
+            if resident is None or isinstance(resident[0], FrozenEncodings):
+                raise ValueError("cache_frozen_steps: states=st goes with resident=(x, y_dev[, w_dev])")
+            if states.stale(model):
+                raise ValueError("cache_frozen_steps: the states are older than the model's frozen weights or were "
+                                 "made for another prefix: build them again")
         self.enc = resident[0] if resident is not None and isinstance(resident[0], FrozenEncodings) else None
         if self.enc is not None:
             model._frozen_cache_check()
@@ -401,6 +414,15 @@ class GraphedTrainStep:
                     if not (w_dev.is_contiguous() and w_dev.dtype == torch.float32 and w_dev.numel() == y_dev.numel()):
                         raise ValueError("resident weights must be a contiguous float32 tensor, one value per sample")
                     self.resident_w = ([w_dev.reshape(-1, 1)], [self.static_w])
+            if states is not None:
+                if not ok or len(states) != y_dev.numel():
+                    raise ValueError("cache_frozen_steps: the captured step gathers from resident 4-byte tensors, and "
+                                     "the states hold one index per resident sample")
+                self.static_cat_row = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+                self.static_an_row = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+                srcs, dsts = self.resident_w if self.resident_w is not None else ([], [])
+                self.resident_w = (srcs + [states.cat_row.reshape(-1, 1), states.an_row.reshape(-1, 1)],
+                                   dsts + [self.static_cat_row.reshape(-1, 1), self.static_an_row.reshape(-1, 1)])
         opt = model.optimizer
         saved_w = [t.detach().clone() for _, t in model.variables()]  # (with BatchNormalization's moving statistics)
         saved_o = opt.state()
@@ -448,6 +470,8 @@ class GraphedTrainStep:
             if self.resident_w is not None:
                 ops.gather_rows(self.resident_w[0], self.resident_w[1], self.static_rows)
         kw = {"metric_slot": "train"} if self.metrics else {}  # without metrics: the call, and the graph, as ever
+        if self.states is not None:
+            kw["states"] = (self.states, self.static_cat_row, self.static_an_row)
         if self.static_w is None:
             loss = m._loss(self.static_in, self.static_y, training=True, **kw)
         else:
@@ -473,6 +497,11 @@ class GraphedTrainStep:
             if x is not self.enc or self.enc.stale(self.model):
                 raise ValueError("a step captured over encodings replays on those encodings, while they are current")
             self.static_rows.copy_(rows)  # the gather of the batch's indices, targets and weights is the first node
+        elif self.states is not None:
+            if x[next(iter(self.static_in))] is not self.resident[0][0] or self.states.stale(self.model):
+                raise ValueError("cache_frozen_steps: a step captured over states replays on the resident data it was "
+                                 "built with, while the states are current")
+            self.static_rows.copy_(rows)
         elif self.resident is not None and x[next(iter(self.static_in))] is self.resident[0][0]:
             self.static_rows.copy_(rows)  # the gather is the first node of the graph
         else:
@@ -488,6 +517,8 @@ class GraphedTrainStep:
     def __call__(self, inputs, y, sample_weight=None):
         if self.enc is not None:
             raise ValueError("a step captured over encodings takes sample rows: step_on_rows(enc, y_dev, rows)")
+        if self.states is not None:
+            raise ValueError("a step captured over states takes sample rows: step_on_rows(x, y_dev, rows)")
         if (sample_weight is not None) != (self.static_w is not None):
             raise ValueError("a step captured with sample_weight takes weights on every call, one without takes none")
         for k, v in self.static_in.items():
