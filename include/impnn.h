@@ -326,6 +326,19 @@ size_t impnn_encoder_prepared_bytes_atoms(int32_t D, int32_t S, int32_t Va, int3
 int impnn_encoder_prepare_weights_atoms(const float* weights, const float* bond_table, const float* atom_table,
                                         int32_t Va, int32_t D, int32_t K, int32_t S, int32_t Vb, int32_t mode,
                                         void* prepared, size_t prepared_bytes, impnn_stream_t stream);
+/* The with-atoms image with a second table behind the first: in step 0 the accumulators of the gates z and r, after the
+ * bias and W_h h and before W_agg agg, depend on (step 0's weights, atom id) only - Va + 1 rows of 64 floats (z 0..31,
+ * r 0..31; row Va: a zero row), each bit for bit what the encoder's atom phase computes, so its step 0 loads them
+ * instead of multiplying.  Built exactly where the message table is (same 2 MiB rule, modes 2 / 3, atom_dim 32, S >= 1):
+ * the size is that of impnn_encoder_prepared_bytes_atoms plus (Va + 1) * 256 bytes, rounded up to 16, and without a
+ * message table size and image are the with-atoms entries'.  The encoder uses the gate table only together with the
+ * message table and only when the image says it is there: images of the entries above keep running as they did, with
+ * the same results.  Same arguments, refusals and rebuild rule (atom_table, or any weight of step 0) as
+ * impnn_encoder_prepare_weights_atoms. */
+size_t impnn_encoder_prepared_bytes_gates(int32_t D, int32_t S, int32_t Va, int32_t Vb, int32_t mode);
+int impnn_encoder_prepare_weights_gates(const float* weights, const float* bond_table, const float* atom_table,
+                                        int32_t Va, int32_t D, int32_t K, int32_t S, int32_t Vb, int32_t mode,
+                                        void* prepared, size_t prepared_bytes, impnn_stream_t stream);
 int impnn_encoder_fused_prepared(int32_t n_ions, const int32_t* const* atom_ids,
                                  const int32_t* const* bond_ids, const int32_t* const* conn,
                                  const float* atom_table, int32_t Va, const float* bond_table,

@@ -52,6 +52,8 @@ SIGNATURES = {
     "impnn_encoder_prepare_weights": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
     "impnn_encoder_prepared_bytes_atoms": (sz, [i32, i32, i32, i32, i32]),
     "impnn_encoder_prepare_weights_atoms": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "impnn_encoder_prepared_bytes_gates": (sz, [i32, i32, i32, i32, i32]),
+    "impnn_encoder_prepare_weights_gates": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
     "impnn_encoder_fused_prepared": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, i32, vp, i32,
                                                C.POINTER(vp), i32, C.POINTER(vp), i32, i32, i32, i32, i32, i32, f32,
                                                i32, vp, sz, vp]),

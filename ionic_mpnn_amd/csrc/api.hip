@@ -531,6 +531,29 @@ int impnn_encoder_prepare_weights_atoms(const float* weights, const float* bond_
   return launch_encoder_prepare_atoms(weights, bond_table, atom_table, Va, D, K, S, Vb, mode, prepared, as_stream(stream));
 }
 
+size_t impnn_encoder_prepared_bytes_gates(int32_t D, int32_t S, int32_t Va, int32_t Vb, int32_t mode) {
+  const size_t atoms = impnn_encoder_prepared_bytes_atoms(D, S, Va, Vb, mode);
+  if (atoms == 0) return 0;
+  const size_t gates = encoder_prepared_bytes_gates(mode, D, S, Va, Vb);
+  return gates > atoms ? (gates + 15) & ~(size_t)15 : atoms;  // no gate table: the with-atoms size as it is
+}
+
+int impnn_encoder_prepare_weights_gates(const float* weights, const float* bond_table, const float* atom_table,
+                                        int32_t Va, int32_t D, int32_t K, int32_t S, int32_t Vb, int32_t mode,
+                                        void* prepared, size_t prepared_bytes, impnn_stream_t stream) {
+  REQUIRE(D > 0 && K > 0 && S >= 0 && Vb > 0 && Va > 0, "bad shape");
+  REQUIRE(mode >= 0 && mode <= 3, "mode must be 0 (f32), 1 (f16x2), 2 (f32 typed) or 3 (f32x3 typed)");
+  if (!encoder_fused_supported(mode, 1, 0, D, K, S, mode >= 2 ? Vb : 1))
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_prepare_weights_gates: mode=%d D=%d K=%d Vb=%d not covered", mode, D, K, Vb);
+  if (S == 0) return IMPNN_OK;
+  REQUIRE(weights && prepared && atom_table && (mode < 2 || bond_table), "null pointer");
+  REQUIRE(aligned16(prepared) && aligned16(atom_table), "prepared buffer and atom_table must be 16B aligned");
+  if (prepared_bytes < impnn_encoder_prepared_bytes_gates(D, S, Va, Vb, mode))
+    return fail(IMPNN_E_WORKSPACE, "encoder_prepare_weights_gates: buffer %zu < %zu bytes", prepared_bytes,
+                impnn_encoder_prepared_bytes_gates(D, S, Va, Vb, mode));
+  return launch_encoder_prepare_gates(weights, bond_table, atom_table, Va, D, K, S, Vb, mode, prepared, as_stream(stream));
+}
+
 int impnn_encoder_fused_prepared(int32_t n_ions, const int32_t* const* atom_ids, const int32_t* const* bond_ids,
                                  const int32_t* const* conn, const float* atom_table, int32_t Va,
                                  const float* bond_table, int32_t Vb, const void* const* prepared, int32_t mode,

@@ -509,6 +509,10 @@ int launch_encoder_prepare(const float* weights, const float* bond_table, int D,
 size_t encoder_prepared_bytes_atoms(int mode, int D, int S, int Va, int Vb);
 int launch_encoder_prepare_atoms(const float* weights, const float* bond_table, const float* atom_table, int Va, int D,
                                  int K, int S, int Vb, int mode, void* prepared, hipStream_t s);
+// ... and with the step-0 gate table behind that (only where the message table is built)
+size_t encoder_prepared_bytes_gates(int mode, int D, int S, int Va, int Vb);
+int launch_encoder_prepare_gates(const float* weights, const float* bond_table, const float* atom_table, int Va, int D,
+                                 int K, int S, int Vb, int mode, void* prepared, hipStream_t s);
 int ensure_lds_limit(const void* kern, int slot);
 int device_compute_units();  // CUs of the current device (cached per device index)
 // Rows per workgroup of the wide (atom_dim 64 / 128) GatedUpdate forward / backward kernels: 64, or 16 below 8 K rows,

@@ -524,6 +524,9 @@ int launch_encoder_typed_prepare(const float* weights, const float* bond_table, 
 size_t encoder_typed_prepared_bytes_atoms(int S, int Va, int Vb, bool x3);
 int launch_encoder_typed_prepare_atoms(const float* weights, const float* bond_table, const float* atom_table, int Va,
                                        int K, int S, int Vb, bool x3, void* prepared, hipStream_t s);
+size_t encoder_typed_prepared_bytes_gates(int S, int Va, int Vb, bool x3);
+int launch_encoder_typed_prepare_gates(const float* weights, const float* bond_table, const float* atom_table, int Va,
+                                       int K, int S, int Vb, bool x3, void* prepared, hipStream_t s);
 int launch_encoder_typed_run(const EncoderArgs& a, const enc::Ws& w, hipStream_t s);
 
 bool encoder_fused_supported(int mode, int N, int E, int D, int K, int S, int Vb) {
@@ -623,6 +626,18 @@ int launch_encoder_prepare_atoms(const float* weights, const float* bond_table, 
                                  int K, int S, int Vb, int mode, void* prepared, hipStream_t s) {
   if (S > 0 && D == enc::kD && mode >= 2)
     return launch_encoder_typed_prepare_atoms(weights, bond_table, atom_table, Va, K, S, Vb, mode == 3, prepared, s);
+  return launch_encoder_prepare(weights, bond_table, D, K, S, Vb, mode, prepared, s);
+}
+
+size_t encoder_prepared_bytes_gates(int mode, int D, int S, int Va, int Vb) {
+  if (D == enc::kD && mode >= 2) return encoder_typed_prepared_bytes_gates(S, Va, Vb, mode == 3);
+  return encoder_prepared_bytes(mode, D, S, Vb);
+}
+
+int launch_encoder_prepare_gates(const float* weights, const float* bond_table, const float* atom_table, int Va, int D,
+                                 int K, int S, int Vb, int mode, void* prepared, hipStream_t s) {
+  if (S > 0 && D == enc::kD && mode >= 2)
+    return launch_encoder_typed_prepare_gates(weights, bond_table, atom_table, Va, K, S, Vb, mode == 3, prepared, s);
   return launch_encoder_prepare(weights, bond_table, D, K, S, Vb, mode, prepared, s);
 }
 

@@ -178,6 +178,24 @@ inline size_t m0_table_floats(int S, int Va, int Vb) {  // 0: no table for this 
   return n * sizeof(float) <= kM0CapBytes ? n : 0;
 }
 
+// ---- step-0 gate table.  In step 0 the z and r accumulators of a row, after the bias and the W_h h half and before the
+// W_agg agg half, are a function of (step 0's weights, atom id) as well:
+//   G0[a][0..63], a <= Va (column Va: a zero row), z features 0..31 then r features 0..31, 256 B per entry,
+// built by typed_g0_kernel through the device function the atom phase itself calls (encoder_typed.hip: gates_h_half), so
+// an entry is bit for bit the starting value of the agg half.  It lies behind M0 and exists only where M0 does (the
+// with-gates prepare entries); a second header, 16 bytes behind M0Header in the same cleared tail, announces it.
+constexpr int32_t kG0Magic = 0x67307467;
+constexpr int kG0Row = 2 * kD;
+struct G0Header {
+  int32_t magic, Va, Vb, S;
+};
+constexpr int kG0HeaderFloatOff = 4;  // floats behind M0Header's place (kTUpdLds / kXUpdLds)
+static_assert(sizeof(M0Header) == 4 * kG0HeaderFloatOff && kTUpdLds + 8 <= kTUpdSlot && kXUpdLds + 8 <= kXUpdSlot,
+              "both headers fit the slot's tail");
+inline size_t g0_table_floats(int S, int Va, int Vb) {  // 0: no table for this shape
+  return m0_table_floats(S, Va, Vb) ? ((size_t)Va + 1) * kG0Row : 0;
+}
+
 constexpr int kShareCap = kECap;  // molecules of one share that plan_chunks resolves in LDS
 // Shares are equal in virtual rows, per ion and in proportion to the ion's rows - so where molecules are tiny (halide
 // anions: one atom, no bond) a share would hold as many molecules as rows.  Every molecule therefore counts at least
@@ -321,6 +339,7 @@ struct TEncParams {
   const float* upd[2];   // per ion: S update slots (kTUpdSlot floats each)
   const float* tmat[2];  // per ion: S x Vb type matrices in operand order
   const float* m0[2];    // per ion: where a step-0 message table would lie (read only if the image's M0Header says so)
+  const float* g0[2];    // per ion: where a step-0 gate table would lie behind it (read only if G0Header says so)
   const int32_t* nsub;
   const int32_t* desc;
   const unsigned char* rec;

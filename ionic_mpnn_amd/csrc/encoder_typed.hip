@@ -21,7 +21,8 @@
 //   step 0: h[src] is atom_table[atom id] (or zeros), so its messages depend on the weights alone; an image prepared with
 //     the atom table carries them as a table (encoder_layout.h: M0Header), and its rows travel L2 -> LDS by
 //     global_load_lds, addressed by the plan's slot-ordered source list, while the PREVIOUS chunk is pooled; step 0's
-//     update image goes the same way.
+//     update image goes the same way.  The same holds for the z / r gate accumulators after their h half (bias + W_h h):
+//     an image of the with-gates entry carries them as a second table (G0Header) and step 0's atom phase loads a row.
 //
 // MFMA work per row is 12 D^2 (update) + 2 D^2 per in-edge, against (12 + 2 K) D^2 per row in the pull form:
 // 2.7 kflop instead of 28.7 kflop per row for the message at bond_dim 8 and 1.7 in-edges per row.
@@ -211,6 +212,80 @@ __global__ __launch_bounds__(256) void typed_m0_kernel(const float* tmat0, const
   if (blockIdx.x == 0 && threadIdx.x == 0) *hdr = M0Header{kM0Magic, Va, Vb, S};
 }
 
+// The h half of the gates z and r (models/layers.py:144-147): bias, then W_h h, for the 16 rows of a tile - lane (a, q)
+// holds h[row a][4 q ..] (h0) and [16 + 4 q ..] (h1) and receives the accumulators of the same features.  wupd / wvec: an
+// update image and its vectors, in LDS (the atom phase) or in global memory (typed_g0_kernel below): one body for both,
+// as group_messages is for the messages, so that a row of the step-0 gate table holds the bits the atom phase computes.
+// Mode 3: the two mma9x2 on split8x3(h); mode 2: the half == 0 turns of the gate loop.
+template <bool X3>
+__device__ __forceinline__ void gates_h_half(const float* wupd, const float* wvec, int lane, int q, const f32x4 h0,
+                                             const f32x4 h1, f32x4& z0, f32x4& z1, f32x4& r0, f32x4& r1) {
+  z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
+  r0 = ld4(wvec + 1 * kD + 4 * q), r1 = ld4(wvec + 1 * kD + 16 + 4 * q);
+  if constexpr (X3) {
+    // (mode 3's A operands: block ((gate*2 + T)*2 + half) of the image, 3 x 512 bf16)
+    const __bf16* const wb = reinterpret_cast<const __bf16*>(wupd);
+    const B3 sh = split8x3(h0, h1);
+    mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 0) * 1536, wb + ((0 * 2 + 1) * 2 + 0) * 1536, lane, sh);
+    mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 0) * 1536, wb + ((1 * 2 + 1) * 2 + 0) * 1536, lane, sh);
+  } else {
+    // A operands: block ((gate*2 + T)*2 + half)*2 + u of the image, 16 B per lane, lane-linear (conflict-free)
+    const float* wl = wupd + 4 * lane;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const f32x4 Az0 = ld4(wl + ((0 * 2 + 0) * 4 + u) * 256);
+      const f32x4 Az1 = ld4(wl + ((0 * 2 + 1) * 4 + u) * 256);
+      const f32x4 Ar0 = ld4(wl + ((1 * 2 + 0) * 4 + u) * 256);
+      const f32x4 Ar1 = ld4(wl + ((1 * 2 + 1) * 4 + u) * 256);
+      const f32x4 Bv = u == 0 ? h0 : h1;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        z0 = mfma4(Az0[r], Bv[r], z0);
+        z1 = mfma4(Az1[r], Bv[r], z1);
+        r0 = mfma4(Ar0[r], Bv[r], r0);
+        r1 = mfma4(Ar1[r], Bv[r], r1);
+      }
+    }
+  }
+}
+
+// Step-0 gate table (encoder_layout.h: G0Header): one wave per 16 consecutive atom ids, fed exactly like a tile of the atom
+// phase - lane (a, q) holds atom_table[a0 + a][4 q ..] and [16 + 4 q ..], zeros for a0 + a >= Va (column Va is the zero
+// row: computed, not copied from the bias, so a non-finite weight gives the 0 * inf = NaN the atom phase gives) - with
+// step 0's update image read from the prepared buffer.  G0[a] = z 0..31, r 0..31.
+template <bool X3>
+__global__ __launch_bounds__(64) void typed_g0_kernel(const float* upd0, const float* atom_table, float* g0, G0Header* hdr,
+                                                      int Va, int Vb, int S) {
+  const int lane = threadIdx.x, a = lane & 15, q = lane >> 4;
+  const int ai = 16 * blockIdx.x + a;
+  f32x4 h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
+  if (ai < Va) {
+    h0 = ld4(atom_table + (size_t)ai * kD + 4 * q);
+    h1 = ld4(atom_table + (size_t)ai * kD + 16 + 4 * q);
+  }
+  f32x4 z0, z1, r0, r1;
+  gates_h_half<X3>(upd0, upd0 + (X3 ? kXVecFloatOff : kTVecFloatOff), lane, q, h0, h1, z0, z1, r0, r1);
+  if (ai <= Va) {
+    float* row = g0 + (size_t)ai * kG0Row + 4 * q;
+    st4(row, z0);
+    st4(row + 16, z1);
+    st4(row + 32, r0);
+    st4(row + 48, r1);
+  }
+  if (blockIdx.x == 0 && lane == 0) *hdr = G0Header{kG0Magic, Va, Vb, S};
+}
+
+// Which of the two step-0 savings an instantiation takes (diagnostics builds may switch either off):
+//   IMPNN_T_G0     the z / r accumulators of a step-0 tile start from the gate table instead of bias + W_h h
+//   IMPNN_T_POOLB  the pool reads a molecule's row indices, then its rows, five at a time
+#ifndef IMPNN_T_G0
+#define IMPNN_T_G0 1
+#endif
+#ifndef IMPNN_T_POOLB
+#define IMPNN_T_POOLB 1
+#endif
+constexpr bool kUseG0 = IMPNN_T_G0 != 0, kPoolBatch = IMPNN_T_POOLB != 0;
+
 // Where the loads of the NEXT step are issued (diagnostics builds may override):
 //   kPfWhere   0: the step's update image at the top of its own message phase; 1: during the previous step's atom phase,
 //              in front of the GEMMs; 2: behind the GEMMs (registers are free there, the vector-memory path still idle)
@@ -339,9 +414,32 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       if (m < M) {
         const int nr = r_molrows[m], mo = r_moloff[m];
-        for (int n = part; n < nr; n += 8) {
-          const int pr = r_poolrow[mo + n];
-          if (pr & 0x8000) acc += ld4(hbuf + (pr & 0xff) * HS + 4 * f4);
+        if constexpr (kPoolBatch) {
+          // Five of the lane's rows per turn (a molecule of <= 40 rows: one turn): their indices in one LDS round trip,
+          // the rows in a second, then the adds in ascending n - not two dependent round trips per row.  A row that is
+          // not pooled, or lies beyond the molecule, adds +0 instead of nothing: acc starts at +0 and no sum of it is
+          // -0, so x + 0 = x holds for every value it takes - the same bits.  (All loads unconditional: index 0 and
+          // row 0 where there is nothing to read.)
+          constexpr int kPB5 = 5;
+          for (int n0 = part; n0 < nr; n0 += 8 * kPB5) {
+            int pr[kPB5];
+#pragma unroll
+            for (int j = 0; j < kPB5; ++j) {
+              const int n = n0 + 8 * j;
+              const int w = r_poolrow[n < nr ? mo + n : 0];
+              pr[j] = n < nr ? w : 0;
+            }
+            f32x4 v[kPB5];
+#pragma unroll
+            for (int j = 0; j < kPB5; ++j) v[j] = ld4(hbuf + (pr[j] & 0xff) * HS + 4 * f4);
+#pragma unroll
+            for (int j = 0; j < kPB5; ++j) acc += (pr[j] & 0x8000) ? v[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+        } else {
+          for (int n = part; n < nr; n += 8) {
+            const int pr = r_poolrow[mo + n];
+            if (pr & 0x8000) acc += ld4(hbuf + (pr & 0xff) * HS + 4 * f4);
+          }
         }
       }
 #pragma unroll
@@ -402,6 +500,16 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     if (p.n_ions > 1) {
       const M0Header t1 = *reinterpret_cast<const M0Header*>(p.upd[1] + kUpdLds);
       if (t1.magic == kM0Magic && t1.Va == p.Va && t1.Vb == p.Vb && t1.S == p.S) tabmask |= 2u;
+    }
+  }
+  // Step-0 gate table: only behind a message table that is in use, and only if the second header agrees (an image of the
+  // with-atoms entry or any older one holds zeros there).
+  // Bits 2 and 3 of the same word (the kernel has no scalar register to spare for a second one).
+  if constexpr (kUseG0) {
+    for (int g = 0; g < p.n_ions; ++g) {
+      if (!((tabmask >> g) & 1u)) continue;
+      const G0Header t = *reinterpret_cast<const G0Header*>(p.upd[g] + kUpdLds + kG0HeaderFloatOff);
+      if (t.magic == kG0Magic && t.Va == p.Va && t.Vb == p.Vb && t.S == p.S) tabmask |= 4u << g;
     }
   }
 
@@ -719,17 +827,42 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
         // the h halves out of the way the gates' single-lane arithmetic below fits the registers (without this order it
         // spills 8 bytes).  The order of every sum is unchanged.  (The exact-f32 MFMA shares the issue port with the
         // vector ALU: nothing passes under it, and reads of h in front of Reduce alone cost time - DESIGN.md 4.1.)
+        // Step 0 of an ion whose image carries the gate table: h is atom_table[id] or zeros, so bias + W_h h is row
+        // min(id, Va) of G0 (clamped exactly where fill_h0 writes zeros) - four 16-byte loads from L2, requested here so
+        // that they pass under Reduce and land, in the accumulators themselves, where the agg half starts.  No bias
+        // read, no split of h, none of the h half's MFMAs; h itself is still read, for r * h and the blend.
         f32x4 h0, h1, z0, z1, r0, r1;
+        // (workgroup-uniform; evaluated where it is asked, from an opaque copy of the mask: as a value of the chunk the
+        //  compiler keeps it - and the table's address - in scalar registers over all steps, and the kernel has none left:
+        //  what it spills there costs vector registers)
+        auto gate_tab = [&]() -> bool {
+          if constexpr (!kUseG0) return false;
+          unsigned tm = tabmask;
+          asm volatile("" : "+s"(tm));
+          return s == 0 && ((tm >> (2 + g)) & 1u);
+        };
+        auto load_gates = [&]() {
+          const int id = r_rowatom[row];
+          const unsigned col = (unsigned)id < (unsigned)p.Va ? (unsigned)id : (unsigned)p.Va;
+          // (the table's address is read here, through an opaque copy of the ion: held over the chunk it would cost the
+          //  scalar registers the kernel does not have)
+          int gg = g;
+          asm volatile("" : "+s"(gg));
+          // (a 32-bit byte offset beside the scalar base - the table is < 4 MiB / Vb: one address register, not two)
+          const unsigned boff = col * (unsigned)(kG0Row * sizeof(float)) + 16u * (unsigned)q;
+          const float* const gp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.g0[gg]) + boff);
+          z0 = ld4(gp), z1 = ld4(gp + 16);
+          r0 = ld4(gp + 32), r1 = ld4(gp + 48);
+        };
         // (mode 3's A operands: block ((gate*2 + T)*2 + half) of the image, 3 x 512 bf16)
         [[maybe_unused]] const __bf16* const wb = reinterpret_cast<const __bf16*>(wupd);
         if constexpr (X3) {
           h0 = ld4(hbuf + row * HS + 4 * q);
           h1 = ld4(hbuf + row * HS + 16 + 4 * q);
-          z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
-          r0 = ld4(wvec + 1 * kD + 4 * q), r1 = ld4(wvec + 1 * kD + 16 + 4 * q);
-          const B3 sh = split8x3(h0, h1);
-          mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 0) * 1536, wb + ((0 * 2 + 1) * 2 + 0) * 1536, lane, sh);
-          mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 0) * 1536, wb + ((1 * 2 + 1) * 2 + 0) * 1536, lane, sh);
+          if (gate_tab())
+            load_gates();
+          else
+            gates_h_half<true>(wupd, wvec, lane, q, h0, h1, z0, z1, r0, r1);
         }
         // ---- Reduce: in-edge messages summed in edge-slot order, in the form the tile's largest in-degree (wave-uniform)
         // asks for: one rank per round trip, two, or a loop of four per round.  agg starts at +0 in every form, and what
@@ -755,8 +888,12 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
         if constexpr (!X3) {
           h0 = ld4(hbuf + row * HS + 4 * q);
           h1 = ld4(hbuf + row * HS + 16 + 4 * q);
-          z0 = ld4(wvec + 0 * kD + 4 * q), z1 = ld4(wvec + 0 * kD + 16 + 4 * q);
-          r0 = ld4(wvec + 1 * kD + 4 * q), r1 = ld4(wvec + 1 * kD + 16 + 4 * q);
+          // (mode 2 asks for its table rows only here: in front of Reduce the sixteen registers they land in are not
+          //  free - the instantiation spilled 60 bytes - so their round trip is hidden by the SIMD's other waves alone)
+          if (gate_tab())
+            load_gates();
+          else
+            gates_h_half<false>(wupd, wvec, lane, q, h0, h1, z0, z1, r0, r1);
         }
         f32x4 t0 = ld4(wvec + 2 * kD + 4 * q), t1 = ld4(wvec + 2 * kD + 16 + 4 * q);
         if constexpr (X3) {
@@ -776,23 +913,21 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
         } else {
           // A operands: block ((gate*2 + T)*2 + half)*2 + u of the image, 16 B per lane, lane-linear (conflict-free)
           const float* wl = wupd + 4 * lane;
+          // (the h half - the gate loop's half == 0 turns - ran above: gates_h_half, or the gate table)
 #pragma unroll
-          for (int half = 0; half < 2; ++half) {
+          for (int u = 0; u < 2; ++u) {
+            const int hu = 2 + u;
+            const f32x4 Az0 = ld4(wl + ((0 * 2 + 0) * 4 + hu) * 256);
+            const f32x4 Az1 = ld4(wl + ((0 * 2 + 1) * 4 + hu) * 256);
+            const f32x4 Ar0 = ld4(wl + ((1 * 2 + 0) * 4 + hu) * 256);
+            const f32x4 Ar1 = ld4(wl + ((1 * 2 + 1) * 4 + hu) * 256);
+            const f32x4 Bv = u == 0 ? agg0 : agg1;
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              const int hu = half * 2 + u;
-              const f32x4 Az0 = ld4(wl + ((0 * 2 + 0) * 4 + hu) * 256);
-              const f32x4 Az1 = ld4(wl + ((0 * 2 + 1) * 4 + hu) * 256);
-              const f32x4 Ar0 = ld4(wl + ((1 * 2 + 0) * 4 + hu) * 256);
-              const f32x4 Ar1 = ld4(wl + ((1 * 2 + 1) * 4 + hu) * 256);
-              const f32x4 Bv = half == 0 ? (u == 0 ? h0 : h1) : (u == 0 ? agg0 : agg1);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                z0 = mfma4(Az0[r], Bv[r], z0);
-                z1 = mfma4(Az1[r], Bv[r], z1);
-                r0 = mfma4(Ar0[r], Bv[r], r0);
-                r1 = mfma4(Ar1[r], Bv[r], r1);
-              }
+            for (int r = 0; r < 4; ++r) {
+              z0 = mfma4(Az0[r], Bv[r], z0);
+              z1 = mfma4(Az1[r], Bv[r], z1);
+              r0 = mfma4(Ar0[r], Bv[r], r0);
+              r1 = mfma4(Ar1[r], Bv[r], r1);
             }
           }
           // (packed here: the f32 MFMA takes the vector ALU's issue slots, so what counts is the number of instructions -
@@ -949,6 +1084,28 @@ int launch_encoder_typed_prepare_atoms(const float* weights, const float* bond_t
   return check_launch("typed_m0");
 }
 
+// ---- the same with the step-0 gate table behind the message table (encoder_layout.h: G0Header); where no message table
+// is built there is no gate table either, and size and image are the with-atoms entry's
+size_t encoder_typed_prepared_bytes_gates(int S, int Va, int Vb, bool x3) {
+  return encoder_typed_prepared_bytes_atoms(S, Va, Vb, x3) + enc::g0_table_floats(S, Va, Vb) * sizeof(float);
+}
+
+int launch_encoder_typed_prepare_gates(const float* weights, const float* bond_table, const float* atom_table, int Va,
+                                       int K, int S, int Vb, bool x3, void* prepared, hipStream_t s) {
+  using namespace enc;
+  if (int rc = launch_encoder_typed_prepare_atoms(weights, bond_table, atom_table, Va, K, S, Vb, x3, prepared, s)) return rc;
+  if (g0_table_floats(S, Va, Vb) == 0) return IMPNN_OK;
+  float* img = static_cast<float*>(prepared);
+  float* g0 = img + typed_prepared_floats(S, Vb, x3) + m0_table_floats(S, Va, Vb);
+  G0Header* hdr = reinterpret_cast<G0Header*>(img + (x3 ? kXUpdLds : kTUpdLds) + kG0HeaderFloatOff);
+  const int tiles = (Va + 16) / 16;  // Va + 1 columns
+  if (x3)
+    typed_g0_kernel<true><<<tiles, 64, 0, s>>>(img, atom_table, g0, hdr, Va, Vb, S);
+  else
+    typed_g0_kernel<false><<<tiles, 64, 0, s>>>(img, atom_table, g0, hdr, Va, Vb, S);
+  return check_launch("typed_g0");
+}
+
 int launch_encoder_typed_run(const EncoderArgs& a, const enc::Ws& w, hipStream_t s) {
   using namespace enc;
   char* base = static_cast<char*>(a.workspace);
@@ -969,6 +1126,7 @@ int launch_encoder_typed_run(const EncoderArgs& a, const enc::Ws& w, hipStream_t
     ep.upd[g] = prep;
     ep.tmat[g] = prep + S1 * uslot;
     ep.m0[g] = prep + typed_prepared_floats(a.S, a.Vb, x3);
+    ep.g0[g] = ep.m0[g] + m0_table_floats(a.S, a.Va, a.Vb);
     ep.pooled[g] = a.pooled[g];
   }
   ep.atom_table = a.atom_table;

@@ -557,8 +557,9 @@ class MPNNModel:
 
     def _prepared_weights(self, mode):
         """Kernel-side weight images (one per ion), built once per weight version and mode.  The typed modes fold the atom
-        embedding in as well (the step-0 message table): invalidate_packed_weights drops the images after an in-place
-        change, weights_updated when any embedding trains."""
+        embedding in as well (the step-0 message table and, behind it, the step-0 gate table - both depend on the atom
+        embedding and on step 0's weights): invalidate_packed_weights drops the images after an in-place change,
+        weights_updated when any embedding trains."""
         if mode not in self._prepared:
             self._prepared[mode] = [ops.prepare_encoder_weights(pk, self.bond_emb.embeddings, self.atom_dim,
                                                                 self.bond_dim, self.num_steps, mode,

@@ -519,13 +519,14 @@ def split_mode_degree_limit(atom_table, bond_table, steps, D):
     return float("inf") if per_deg == 0.0 else 0.999 * FP16_MAX / per_deg
 
 
-def prepare_encoder_weights(packed, bond_table, D, K, num_steps, mode="f32t", atom_table=None):
+def prepare_encoder_weights(packed, bond_table, D, K, num_steps, mode="f32t", atom_table=None, gates=True):
     """Builds the encoder's kernel-side weight image once (impnn_encoder_prepare_weights); pass the
     result as `prepared` to encoder_fused while the weights stay unchanged.  Mode "f32t" folds the bond
     embedding table into the image (the per-bond-type matrices), so it must be rebuilt when that table changes.
     With `atom_table` (the atom embedding, (Va, D)) the typed modes also fold it in: the image then carries the table of
-    step-0 messages (impnn_encoder_prepare_weights_atoms) the encoder gathers from, and must be rebuilt when the atom
-    embedding changes too.  The results are the same bits either way."""
+    step-0 messages the encoder gathers from and, behind it, the table of step 0's gate accumulators after their h half
+    (impnn_encoder_prepare_weights_gates; gates=False: the message table alone, impnn_encoder_prepare_weights_atoms),
+    and must be rebuilt when the atom embedding changes too.  The results are the same bits every way."""
     require_gpu(packed, bond_table, atom_table)
     packed, bond_table = f32c(packed), f32c(bond_table)
     S, Vb = int(num_steps), int(bond_table.shape[0])
@@ -535,15 +536,17 @@ def prepare_encoder_weights(packed, bond_table, D, K, num_steps, mode="f32t", at
     else:
         atom_table = f32c(atom_table)
         Va = int(atom_table.shape[0])
-        nbytes = int(lib.impnn_encoder_prepared_bytes_atoms(D, S, Va, Vb, ENCODER_MODES[mode]))
+        size_of = lib.impnn_encoder_prepared_bytes_gates if gates else lib.impnn_encoder_prepared_bytes_atoms
+        build = lib.impnn_encoder_prepare_weights_gates if gates else lib.impnn_encoder_prepare_weights_atoms
+        nbytes = int(size_of(D, S, Va, Vb, ENCODER_MODES[mode]))
     out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=packed.device)
     with torch.cuda.device(packed.device):
         if atom_table is None:
             rc = lib.impnn_encoder_prepare_weights(ptr(packed), ptr(bond_table), D, K, S, Vb, ENCODER_MODES[mode],
                                                    ptr(out), nbytes, stream_ptr())
         else:
-            rc = lib.impnn_encoder_prepare_weights_atoms(ptr(packed), ptr(bond_table), ptr(atom_table), Va, D, K, S, Vb,
-                                                         ENCODER_MODES[mode], ptr(out), nbytes, stream_ptr())
+            rc = build(ptr(packed), ptr(bond_table), ptr(atom_table), Va, D, K, S, Vb, ENCODER_MODES[mode], ptr(out),
+                       nbytes, stream_ptr())
     if rc == _lib.IMPNN_E_UNSUPPORTED:
         raise EncoderUnsupported(lib.impnn_last_error_string().decode())
     check(rc)

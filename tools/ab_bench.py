@@ -55,19 +55,19 @@ def call(lib):
     if hasattr(lib, "impnn_encoder_fused_prepared"):
         if id(lib) not in prep:
             # a library that exports the with-atoms prepare gets the image MPNNModel keeps: with the step-0 message table
-            atoms = hasattr(lib, "impnn_encoder_prepare_weights_atoms")
+            # (and one that exports the with-gates prepare: the step-0 gate table behind it as well)
+            atoms = next((s for s in ("gates", "atoms") if hasattr(lib, "impnn_encoder_prepare_weights_" + s)), None)
             if atoms:
-                nb = int(lib.impnn_encoder_prepared_bytes_atoms(32, S, atab.shape[0], btab.shape[0],
-                                                                ops.ENCODER_MODES[args.mode]))
+                nb = int(getattr(lib, "impnn_encoder_prepared_bytes_" + atoms)(32, S, atab.shape[0], btab.shape[0],
+                                                                               ops.ENCODER_MODES[args.mode]))
             else:
                 nb = int(lib.impnn_encoder_prepared_bytes(32, S, btab.shape[0], ops.ENCODER_MODES[args.mode]))
             bufs = [torch.empty(nb, dtype=torch.uint8, device=dev) for _ in range(2)]
             for bf, pk in zip(bufs, packed):
                 if atoms:
-                    assert lib.impnn_encoder_prepare_weights_atoms(pk.data_ptr(), btab.data_ptr(), atab.data_ptr(),
-                                                                   atab.shape[0], 32, 8, S, btab.shape[0],
-                                                                   ops.ENCODER_MODES[args.mode], bf.data_ptr(), nb,
-                                                                   torch.cuda.current_stream().cuda_stream) == 0
+                    assert getattr(lib, "impnn_encoder_prepare_weights_" + atoms)(
+                        pk.data_ptr(), btab.data_ptr(), atab.data_ptr(), atab.shape[0], 32, 8, S, btab.shape[0],
+                        ops.ENCODER_MODES[args.mode], bf.data_ptr(), nb, torch.cuda.current_stream().cuda_stream) == 0
                 else:
                     assert lib.impnn_encoder_prepare_weights(pk.data_ptr(), btab.data_ptr(), 32, 8, S, btab.shape[0],
                                                              ops.ENCODER_MODES[args.mode], bf.data_ptr(), nb,
@@ -93,7 +93,9 @@ for lib in libs:
     torch.cuda.synchronize()
     outs.append([p.clone() for p in pooled])
 for i in range(1, len(libs)):
-    print(f"variant {i} vs 0: max abs diff {max(float((a - b).abs().max()) for a, b in zip(outs[0], outs[i])):.3e}")
+    same = all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(outs[0], outs[i]))
+    print(f"variant {i} vs 0: max abs diff {max(float((a - b).abs().max()) for a, b in zip(outs[0], outs[i])):.3e}"
+          f"  same bits: {same}")
 
 tot = [[] for _ in libs]
 ker = [[] for _ in libs]

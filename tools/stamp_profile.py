@@ -67,14 +67,17 @@ if mode in ("f32t", "f32x3"):
     # step 0 of the first chunk: stamp 13 marks its start where the library writes it (0 in older builds); for any build,
     # with S = 3, the mean chunk's steps less two steps 1 estimate it.  With a step-0 message table in the image
     # (MPNNModel._prepared_weights builds one) step 0 has no message phase: its gather runs in the chunk prologue, so
-    # compare prologue + steps per chunk, not step 0 alone.
+    # compare prologue + steps per chunk, not step 0 alone.  With the step-0 gate table behind it (a library that exports
+    # impnn_encoder_prepare_weights_gates) step 0's atom phase also starts its z / r accumulators from a table row: what
+    # that saves shows in the step-0 line against step 1's atom phase, and in steps per chunk.
     if S == 3:
         est = (steps / nch)[ok].mean() - 2 * end.mean()
         print(f"step 0, estimated as steps per chunk - 2 x step 1: {est:.0f}")
     has13 = ok & (st[:, 13] > 0)
     if has13.any():
         d0 = (st[:, 14] - st[:, 13])[has13]
-        print(f"step 0 of the first chunk ({has13.sum()} workgroups): duration {d0.mean():.0f}  (step 1: {end.mean():.0f})")
+        print(f"step 0 of the first chunk ({has13.sum()} workgroups): duration {d0.mean():.0f}  (step 1: {end.mean():.0f}, "
+              f"its atom phase + end barrier: {(end - mid).mean():.0f})")
     print(f"per chunk, prologue + steps + pool: {((pro + steps + pool) / nch).mean():.0f}")
     if (st[:, 11] > 0).any():  # round 3: wave 1's atom phase in detail (its tile: one of the heaviest)
         a = st[ok]
