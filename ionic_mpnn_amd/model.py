@@ -287,6 +287,7 @@ class MPNNModel:
         self._transfer_grid_image = None
         self._encoder_version = 0  # moves on whenever the encoder's packed weights are dropped (data.FrozenEncodings)
         self._frozen_state_version = 0  # moves on when weights are written from outside a step (data.FrozenStates)
+        self._frozen_prefix_epoch = 0  # moves on when a compile() changes frozen_prefix() (data.FrozenStates)
         self.grid_head_mode = "auto"  # "auto" | "gathered": predict_grid's head for the transfer model
 
     # ------------------------------------------------------------------ construction
@@ -480,19 +481,25 @@ class MPNNModel:
                 lyr.invalidate_cache()
 
     def weights_updated(self):
-        """After an optimizer step: drops the caches that hold copies of variables the step changed.  The packed
-        encoder weights and a frozen message layer's type matrices stay when nothing they were built from trains - a
-        captured training step reads them on every replay."""
-        self._head_packed = None
+        """After an optimizer step: drops the caches that hold copies of variables the step changed, and only those.
+        The packed head, the packed encoder weights, an image and a frozen message layer's type matrices stay when
+        nothing they were built from trains - a captured training step reads them on every replay."""
+        if any(t.requires_grad for t in self._head_tensors()):
+            self._head_packed = None
         if self.kind == "transfer" and (getattr(self, "_bn_training", self.mp_bn_1.trainable)
                                         or any(t.requires_grad for t in self._head_tensors()[10:])):
             self._transfer_grid_image = None  # (a frozen tail keeps its image, as a frozen encoder its prepared weights)
-        enc = [t for n, t in self._named_tensors().items()
-               if n.endswith("_embedding") or "_bmm_" in n or "_gu_" in n]
-        if any(t.requires_grad for t in enc):
-            self._packed, self._prepared, self._split_deg_limit = None, {}, None
+        steps = any(t.requires_grad for n, t in self._named_tensors().items() if "_bmm_" in n or "_gu_" in n)
+        atom, table = self.atom_emb.embeddings.requires_grad, self.bond_emb.embeddings.requires_grad
+        if steps:
+            self._packed = None
+        if steps or atom or table:
+            # an image holds the step weights; the typed modes fold the bond table in as well and, at atom_dim 32, the
+            # atom table (include/impnn.h, impnn_encoder_prepare_weights_gates); the degree limit reads both tables
+            stale = lambda m: steps or (m in ("f32t", "f32x3") and (table or (atom and self.atom_dim == 32)))
+            self._prepared = {m: image for m, image in self._prepared.items() if not stale(m)}
+            self._split_deg_limit = None
             self._encoder_version += 1
-        table = self.bond_emb.embeddings.requires_grad
         for p in ("cat", "an"):
             for lyr in self.branches[p]["bmm"]:
                 if table or lyr.bond_transform.requires_grad:
@@ -511,6 +518,13 @@ class MPNNModel:
         it on, ``weights_updated`` does not - a training step writes trainable variables only, and what was computed
         from the frozen ones (data.FrozenStates) stays valid while ``frozen_prefix()`` stays what it was."""
         return self._frozen_state_version
+
+    @property
+    def frozen_prefix_epoch(self):
+        """Counts the ``compile()`` calls that changed ``frozen_prefix()``.  A step under another prefix may have trained
+        what lies below the old one, and ``weights_updated`` leaves ``frozen_state_version`` alone: states made before
+        such a compile are stale even when a later compile brings their prefix back (data.FrozenStates)."""
+        return self._frozen_prefix_epoch
 
     def frozen_prefix(self):
         """{"cat": s, "an": s}: per ion, what ``_first_trained_step`` returns inside a differentiated pass, read from
@@ -559,7 +573,7 @@ class MPNNModel:
         """Kernel-side weight images (one per ion), built once per weight version and mode.  The typed modes fold the atom
         embedding in as well (the step-0 message table and, behind it, the step-0 gate table - both depend on the atom
         embedding and on step 0's weights): invalidate_packed_weights drops the images after an in-place change,
-        weights_updated when any embedding trains."""
+        weights_updated the images whose sources train (a typed image also when an embedding does)."""
         if mode not in self._prepared:
             self._prepared[mode] = [ops.prepare_encoder_weights(pk, self.bond_emb.embeddings, self.atom_dim,
                                                                 self.bond_dim, self.num_steps, mode,
@@ -568,8 +582,9 @@ class MPNNModel:
         return self._prepared[mode]
 
     def _packed_weights(self):
-        if self._packed is None:
-            packed = []
+        if self._packed is None or self._split_deg_limit is None:
+            # (the limit alone is missing after a step that trained an embedding and no step weight: weights_updated)
+            packed, limit = [], None
             for p in ("cat", "an"):
                 br = self.branches[p]
                 steps = []
@@ -583,8 +598,10 @@ class MPNNModel:
                 packed.append(ops.pack_step_weights(steps))
                 lim = ops.split_mode_degree_limit(self.atom_emb.embeddings, self.bond_emb.embeddings, steps,
                                                   self.atom_dim)
-                self._split_deg_limit = lim if self._split_deg_limit is None else min(self._split_deg_limit, lim)
-            self._packed = packed
+                limit = lim if limit is None else min(limit, lim)
+            if self._packed is None:
+                self._packed = packed
+            self._split_deg_limit = limit
         return self._packed
 
     def resolve_encoder_mode(self, N, E=None):
@@ -924,7 +941,10 @@ class MPNNModel:
             x = self.mix([self.cat_proj(fp_cat), self.an_proj(fp_an)])
             if trace is not None:
                 trace["cat/fp"], trace["an/fp"], trace["mixed"] = fp_cat, fp_an, x
-            x = self.mp_bn_1(self.mp_dense_1(x), training=training and getattr(self, "_bn_training", True))
+            bn_batch = training and getattr(self, "_bn_training", True)
+            if bn_batch and self.mp_bn_1.trainable:
+                self._transfer_grid_image = None  # the layer moves its moving statistics, which the grid image holds
+            x = self.mp_bn_1(self.mp_dense_1(x), training=bn_batch)
             x = self.mp_dropout(self.mp_dense_2(x), training=training, counter=self.dropout_counter())
             return self.melting_point(self.mp_dense_3(x))
         if trace is None and not differentiable and self._head_kernels_cover():
@@ -986,10 +1006,13 @@ class MPNNModel:
         self._metric_set = metric_set if len(metric_set) else None
         self.optimizer = optimizer if optimizer is not None else train.Adam(1e-3, clipnorm=1.0)
         names = {n for n, _ in tv}
+        before = self.frozen_prefix()
         for n, t in self._named_tensors().items():
             t.requires_grad_(n in names)
             if n not in names:
                 t.grad = None
+        if self.frozen_prefix() != before:
+            self._frozen_prefix_epoch += 1
         if self.kind == "transfer":
             self._bn_training = bool(self.mp_bn_1.trainable)
         if isinstance(self.optimizer, train.Adam):  # the names are what exclude_from_weight_decay matches

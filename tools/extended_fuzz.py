@@ -3,7 +3,9 @@
 dense multigraph cases for further seeds, every exact-f32 form the shape allows, against the fp64 oracle.
 python tools/extended_fuzz.py [--first 24] [--count 150]      (GPU box; test infrastructure, uses oracle/)
 python tools/extended_fuzz.py --train [--first 32] [--count 64]: the whole-model gradient fuzz of
-tests/test_gpu_train_fuzz.py (run_model_case) for further seeds instead."""
+tests/test_gpu_train_fuzz.py (run_model_case) for further seeds instead.
+python tools/extended_fuzz.py --cache [--first 1] [--count 16]: the cache fuzz of tests/test_gpu_cache_fuzz.py
+(run_sequence) on the sequences tests/cache_cases.py generates for further seeds instead."""
 import argparse
 import sys
 from pathlib import Path
@@ -24,8 +26,25 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--first", type=int, default=24)
 ap.add_argument("--count", type=int, default=150)
 ap.add_argument("--train", action="store_true")
+ap.add_argument("--cache", action="store_true")
 args = ap.parse_args()
 bad, ran = [], 0
+if args.cache:
+    import tempfile  # noqa: E402
+    import cache_cases as CC  # noqa: E402
+    import test_gpu_cache_fuzz as TC  # noqa: E402
+    for seed in range(args.first, args.first + args.count):
+        for case in CC.generate(seed):
+            try:
+                with tempfile.TemporaryDirectory() as tmp:
+                    TC.run_sequence(case, Path(tmp))
+                ran += 1
+            except AssertionError as e:  # a stale copy or a broken guard; anything else (a HIP error) ends the run
+                bad.append(("cache", seed, case.name, [ev["kind"] for ev in case.events], str(e)[:300]))
+    print(f"{ran} sequences over seeds {args.first} .. {args.first + args.count - 1}: {len(bad)} failures")
+    for b in bad:
+        print(b)
+    sys.exit(1 if bad else 0)
 if args.train:
     import test_gpu_train_fuzz as TF  # noqa: E402
     for seed in range(args.first, args.first + args.count):
