@@ -826,6 +826,57 @@ int impnn_ensemble_grid_topk_where(int32_t kind, int32_t M, const float* mix_cat
                                    void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t nT, int32_t F,
                                    int32_t Mx, int32_t workgroups, impnn_stream_t stream);
 
+/* ---- Monte-Carlo dropout of the transfer head over the grid: S stochastic passes of one trained transfer model, with
+ *      the head's Dropout (between Dense 128 and Dense 64) on and BatchNormalization on its moving statistics, evaluated
+ *      inside one grid tile, and per pair the mean, the spread and a confidence-bound score of the S values - the fourth
+ *      grid family, through the materialising, the mask-writing and the selecting form.
+ *      Operands: u_cat, u_an, image, image_floats as impnn_transfer_head_grid; multipliers (S,128) float32, 16-byte
+ *      aligned: sample s multiplies feature j of relu(Dense 128) by multipliers[s][j] - a feature whose multiplier is 0
+ *      is 0 (also where the activation is not finite), any other is relu(a2)[j] * multipliers[s][j].  Then Dense 64,
+ *      relu and Dense 1 exactly as impnn_transfer_head_grid: with every multiplier 1 a sample has that entry's bits.
+ *      impnn_dropout_mask(seed, step, layer word, rate, NULL, NULL, S, 128, ...) writes the table of a Dropout: row s
+ *      is the mask a training pass at that step applies to batch row s.  No generator runs inside the grid kernel.
+ *      The table is the same for every pair of the grid (the "fixed set of masks" form of MC dropout): a pair's S
+ *      values, and so its statistic, depend on its two u rows, the image and the table only, not on the tile, the
+ *      launch, the host tiling or the grid's size.
+ *      The statistic of a pair's values v_0 .. v_{S-1}, in float32 and in this order (impnn_ensemble_grid's, for S):
+ *        s = v_0; s = s + v_i, i ascending; mean = s / (float)S
+ *        q = 0; d = v_i - mean; q = fmaf(d, d, q), i ascending; std = sqrt(q / (float)S)   (population, as numpy.std)
+ *        score = fmaf(kappa, std, mean)                              kappa: any finite float
+ *      A NaN sample makes mean, std and score NaN for that pair and for no other.  S = 1: std = 0, score = mean.
+ *      Limit: 1 <= S <= impnn_transfer_mc_grid_max_samples() (64: the samples' values and the table share a compute
+ *      unit's LDS with the selecting form's list and mask words).
+ *      impnn_transfer_mc_grid: mean, std, score (C,A) and samples (S,C,A), row-major; a NULL one is not written, at
+ *        least one is needed.  Checks in order: shape (IMPNN_E_BADARG); S (below 1 IMPNN_E_BADARG, above the limit
+ *        IMPNN_E_UNSUPPORTED) and kappa (NaN or infinite: IMPNN_E_BADARG); zero work (C == 0 or A == 0: IMPNN_OK, nothing
+ *        touched); null pointers; alignment, then the image size (IMPNN_E_WORKSPACE).
+ *      impnn_transfer_mc_grid_mask: words as impnn_transfer_head_grid_mask, bit (i,j) = lo <= score && score <= hi.
+ *        Checks in order: shape; S and kappa; a NaN bound; zero work; null pointers; alignment and the image size.
+ *      impnn_transfer_mc_grid_topk / _topk_where: outputs (1,k), order, k <= 1024, C * A < 2^32, workgroups and `where`
+ *        as impnn_transfer_head_grid_topk / _topk_where, on the score; workspace:
+ *        impnn_transfer_mc_grid_topk_workspace_bytes bytes for the same (S, C, A, k, workgroups), 8-byte aligned.  Checks
+ *        in order: shape; S and kappa; k, C * A (the limits IMPNN_E_UNSUPPORTED); zero work; null pointers, then
+ *        alignment and the image size; the workspace size (IMPNN_E_WORKSPACE).
+ *      Each ion's best partners, the rank cut and Pareto objectives are not built for this family. */
+int32_t impnn_transfer_mc_grid_max_samples(void);
+int impnn_transfer_mc_grid(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                           const float* multipliers, int32_t S, float kappa, float* mean, float* std, float* score,
+                           float* samples, int32_t C, int32_t A, impnn_stream_t stream);
+int impnn_transfer_mc_grid_mask(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                const float* multipliers, int32_t S, float kappa, float lo, float hi, uint32_t* words,
+                                int32_t C, int32_t A, impnn_stream_t stream);
+int impnn_transfer_mc_grid_topk_workspace_bytes(int32_t S, int32_t C, int32_t A, int32_t k, int32_t workgroups,
+                                                size_t* need);
+int impnn_transfer_mc_grid_topk(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                const float* multipliers, int32_t S, float kappa, int32_t k, int32_t largest,
+                                float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                                int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream);
+int impnn_transfer_mc_grid_topk_where(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                      const float* multipliers, int32_t S, float kappa, const uint32_t* where,
+                                      int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
+                                      void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
+                                      impnn_stream_t stream);
+
 /* ---- the Pareto front of two objectives over a cation x anion grid: a sound filter on the GPU, from two planes of
  *      values to a short candidate list that holds the whole front; the caller finishes the front of the candidates.
  *      A pair (i, j) has the float32 values v1, v2 and the keys k1, k2 of the selection's order (the order-preserving

@@ -10,10 +10,11 @@ from .layers import (AddTwoTensors, BondMatrixMessage, ComputeLogEta, Dense, Emb
                      SliceParamB, SliceParamC, register_keras_serializable, reset_uids)
 from .model import MPNNModel, build_melting_point_model, build_model, load_model  # noqa: F401
 from .ensemble import ModelEnsemble  # noqa: F401
+from .mc_dropout import McDropout  # noqa: F401
 from .pareto import Objective, screen_pareto  # noqa: F401
 
 __all__ = [
     "BondMatrixMessage", "Reduce", "GatedUpdate", "GRUUpdate", "GlobalSumPool", "Embedding", "Dense",
     "AddTwoTensors", "SliceParamA", "SliceParamB", "SliceParamC", "ScaleTemperature", "ComputeLogEta",
-    "build_model", "build_melting_point_model", "MPNNModel", "load_model", "ModelEnsemble",
+    "build_model", "build_melting_point_model", "MPNNModel", "load_model", "ModelEnsemble", "McDropout",
 ]

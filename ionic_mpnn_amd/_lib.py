@@ -125,6 +125,14 @@ SIGNATURES = {
     "impnn_ensemble_grid_topk": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, sz] + [i32] * 6 + [vp]),
     "impnn_ensemble_grid_topk_where": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, vp, i32, i32, vp, vp, vp, vp, sz] + [i32] * 6
                                        + [vp]),
+    "impnn_transfer_mc_grid_max_samples": (i32, []),
+    "impnn_transfer_mc_grid": (C.c_int, [vp, vp, vp, i64, vp, i32, f32, vp, vp, vp, vp, i32, i32, vp]),
+    "impnn_transfer_mc_grid_mask": (C.c_int, [vp, vp, vp, i64, vp, i32, f32, f32, f32, vp, i32, i32, vp]),
+    "impnn_transfer_mc_grid_topk_workspace_bytes": (C.c_int, [i32] * 5 + [C.POINTER(sz)]),
+    "impnn_transfer_mc_grid_topk": (C.c_int, [vp, vp, vp, i64, vp, i32, f32, i32, i32, vp, vp, vp, vp, sz, i32, i32, i32,
+                                              vp]),
+    "impnn_transfer_mc_grid_topk_where": (C.c_int, [vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp, vp, vp, vp, sz, i32,
+                                                    i32, i32, vp]),
     "impnn_pareto_bucket_bits": (i32, []),
     "impnn_pareto_workspace_bytes": (C.c_int, [C.POINTER(sz)]),
     "impnn_pareto_begin": (C.c_int, [vp, sz, vp]),

@@ -673,6 +673,12 @@ GridOperands ensemble_grid_operands(int kind, int M, const float* mix_cat, const
                                     impnn_stream_t stream) {
   return {2, kind, mix_cat, mix_an, T, tails, C, A, nT, 0, F, Mx, as_stream(stream), M, kappa};
 }
+// family 3: the transfer grid's operands, S samples' multipliers (S,128) and kappa
+GridOperands transfer_mc_grid_operands(const float* u_cat, const float* u_an, const float* image,
+                                       const float* multipliers, int S, float kappa, int C, int A,
+                                       impnn_stream_t stream) {
+  return {3, 1, u_cat, u_an, nullptr, image, C, A, 0, 0, 0, 0, as_stream(stream), S, kappa, multipliers};
+}
 // the transfer grid's operands: 16-byte alignment, then the image size (image_floats < 0: the entry takes no image)
 int transfer_image_rule(const char* entry, bool aligned_ok, int64_t image_floats) {
   if (!aligned_ok) return fail(IMPNN_E_BADARG, "%s: u rows and the image must be 16-byte aligned", entry);
@@ -1005,9 +1011,15 @@ int grid_no_temperatures_rule(const char* entry, const GridOperands& g) {
   if (g.family != 1 && g.kind == 1 && g.T) return fail(IMPNN_E_BADARG, "%s: the melting-point grid takes no temperatures", entry);
   return IMPNN_OK;
 }
+// the families whose operands are u rows and the prepared image: no widths, no temperatures
+bool grid_takes_image(const GridOperands& g) { return g.family == 1 || g.family == 3; }
 int grid_transfer_rule(const char* entry, const GridOperands& g, int64_t image_floats) {
-  if (g.family != 1) return IMPNN_OK;
-  return transfer_image_rule(entry, aligned16(g.mix_cat) && aligned16(g.mix_an) && aligned16(g.w), image_floats);
+  if (!grid_takes_image(g)) return IMPNN_OK;
+  if (int rc = transfer_image_rule(entry, aligned16(g.mix_cat) && aligned16(g.mix_an) && aligned16(g.w), image_floats))
+    return rc;
+  if (g.family == 3 && !aligned16(g.multipliers))
+    return fail(IMPNN_E_BADARG, "%s: the multipliers must be 16-byte aligned", entry);
+  return IMPNN_OK;
 }
 // workspace alignment (8 bytes) and mask alignment (4): `message` names the entry's buffers; q may be null
 int grid_aligned_rule(const char* entry, const void* p, const void* q, unsigned bytes, const char* message) {
@@ -1030,6 +1042,14 @@ int grid_ensemble_rule(const char* entry, int M, float kappa) {
   if (M < 1) return fail(IMPNN_E_BADARG, "%s: M=%d members must be at least 1", entry, M);
   if (M > ensemble_grid_max_members())
     return fail(IMPNN_E_UNSUPPORTED, "%s: M=%d members (<= %d per call)", entry, M, ensemble_grid_max_members());
+  if (!(kappa - kappa == 0.f)) return fail(IMPNN_E_BADARG, "%s: kappa must be finite", entry);
+  return IMPNN_OK;
+}
+// the transfer MC grid's own arguments, checked with the shape
+int grid_mc_rule(const char* entry, int S, float kappa) {
+  if (S < 1) return fail(IMPNN_E_BADARG, "%s: S=%d samples must be at least 1", entry, S);
+  if (S > transfer_mc_grid_max_samples())
+    return fail(IMPNN_E_UNSUPPORTED, "%s: S=%d samples (<= %d per call)", entry, S, transfer_mc_grid_max_samples());
   if (!(kappa - kappa == 0.f)) return fail(IMPNN_E_BADARG, "%s: kappa must be finite", entry);
   return IMPNN_OK;
 }
@@ -1057,6 +1077,11 @@ int ensemble_topk_shape(const char* entry, int M, float kappa, int C, int A, int
   if (int rc = grid_ensemble_rule(entry, M, kappa)) return rc;
   return grid_topk_limits(entry, C, A, nT, k, workgroups, ensemble_grid_topk_max_temperatures(M));
 }
+// the transfer MC grid's: S and kappa first, then the same limits (it takes no temperatures)
+int mc_topk_shape(const char* entry, int S, float kappa, int C, int A, int k, int workgroups) {
+  if (int rc = grid_mc_rule(entry, S, kappa)) return rc;
+  return grid_topk_limits(entry, C, A, 0, k, workgroups, kSelectMaxT);
+}
 int grid_partners_shape(const char* entry, int family, int C, int A, int nT, int m) {
   if (int rc = grid_family_rule(entry, family)) return rc;
   if (C < 0 || A < 0 || nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
@@ -1076,7 +1101,7 @@ int grid_rank_limits(const char* entry, int C, int A, int nT) {
 int grid_selecting_rules(const char* entry, const GridOperands& g, bool pointers_ok, const void* workspace,
                          const uint32_t* where, int64_t image_floats, size_t need, size_t workspace_bytes, bool* launch) {
   *launch = false;
-  if (g.family != 1)
+  if (!grid_takes_image(g))
     if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
   if (g.C == 0 || g.A == 0) return IMPNN_OK;
   if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
@@ -1094,8 +1119,9 @@ int grid_topk_checked(const char* entry, const GridTopkCall& c, bool shape_ok, b
                       size_t workspace_bytes) {
   const GridOperands& g = c.g;
   if (int rc = grid_kind_rule(entry, g, shape_ok)) return rc;
-  if (int rc = g.family == 2 ? ensemble_topk_shape(entry, g.M, g.kappa, g.C, g.A, g.nT, c.k, c.workgroups)
-                            : grid_topk_shape(entry, g.family, g.C, g.A, g.nT, c.k, c.workgroups))
+  if (int rc = g.family == 2   ? ensemble_topk_shape(entry, g.M, g.kappa, g.C, g.A, g.nT, c.k, c.workgroups)
+               : g.family == 3 ? mc_topk_shape(entry, g.M, g.kappa, g.C, g.A, c.k, c.workgroups)
+                               : grid_topk_shape(entry, g.family, g.C, g.A, g.nT, c.k, c.workgroups))
     return rc;
   bool launch;
   if (int rc = grid_selecting_rules(entry, g, pointers_ok && (!c.masked || c.where), c.workspace, c.where, image_floats,
@@ -1103,7 +1129,7 @@ int grid_topk_checked(const char* entry, const GridTopkCall& c, bool shape_ok, b
                                     &launch))
     return rc;
   if (!launch) return IMPNN_OK;
-  return g.family == 2 ? launch_ensemble_grid_topk(c) : launch_grid_topk(c);
+  return g.family == 2 ? launch_ensemble_grid_topk(c) : g.family == 3 ? launch_transfer_mc_grid_topk(c) : launch_grid_topk(c);
 }
 
 int grid_partners_checked(const char* entry, const GridPartnersCall& c, bool shape_ok, bool pointers_ok,
@@ -1147,18 +1173,20 @@ int grid_mask_checked(const char* entry, const GridMaskCall& c, bool shape_ok, b
   if (int rc = grid_kind_rule(entry, g, shape_ok && g.C >= 0 && g.A >= 0 && g.nT >= 0)) return rc;
   if (g.family == 2)
     if (int rc = grid_ensemble_rule(entry, g.M, g.kappa)) return rc;
+  if (g.family == 3)
+    if (int rc = grid_mc_rule(entry, g.M, g.kappa)) return rc;
   if (c.lo != c.lo || c.hi != c.hi) return fail(IMPNN_E_BADARG, "%s: a bound is NaN (an infinity means no limit)", entry);
   if (g.C == 0 || g.A == 0) return IMPNN_OK;
   if (!pointers_ok) return fail(IMPNN_E_BADARG, "%s: null pointer", entry);
   if (int rc = grid_no_temperatures_rule(entry, g)) return rc;
   if (int rc = grid_aligned_rule(entry, c.words, nullptr, 4, "the mask must be 4-byte aligned")) return rc;
   if (int rc = grid_transfer_rule(entry, g, image_floats)) return rc;
-  if (g.family != 1) {
+  if (!grid_takes_image(g)) {
     if (int rc = head_widths_covered(entry, g.D, g.F, g.Mx)) return rc;
     const int most = g.family == 2 ? ensemble_grid_max_temperatures(g.kind, g.M) : head_grid_max_temperatures();
     if (g.nT > most) return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, g.nT, most);
   }
-  return g.family == 2 ? launch_ensemble_grid_mask(c) : launch_grid_mask(c);
+  return g.family == 2 ? launch_ensemble_grid_mask(c) : g.family == 3 ? launch_transfer_mc_grid_mask(c) : launch_grid_mask(c);
 }
 }  // namespace
 
@@ -1366,6 +1394,61 @@ int impnn_ensemble_grid_topk_where(int32_t kind, int32_t M, const float* mix_cat
   return grid_topk_checked(__func__, c, F > 0 && Mx > 0,
                            mix_cat && mix_an && tails && values && cation && anion && workspace && (kind == 1 || temperatures),
                            0, workspace_bytes);
+}
+
+// ---- Monte-Carlo dropout of the transfer head over the grid (include/impnn.h; transfer_mc_grid.hip): family 3 through
+// the materialising, mask-writing and selecting forms.  The materialising entry follows impnn_transfer_head_grid's
+// order with S and kappa behind the shape, the others go through the family's checks.
+int32_t impnn_transfer_mc_grid_max_samples(void) { return transfer_mc_grid_max_samples(); }
+
+int impnn_transfer_mc_grid(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                           const float* multipliers, int32_t S, float kappa, float* mean, float* std, float* score,
+                           float* samples, int32_t C, int32_t A, impnn_stream_t stream) {
+  const GridOperands g = transfer_mc_grid_operands(u_cat, u_an, image, multipliers, S, kappa, C, A, stream);
+  if (int rc = grid_kind_rule(__func__, g, C >= 0 && A >= 0 && image_floats >= 0)) return rc;
+  if (int rc = grid_mc_rule(__func__, S, kappa)) return rc;
+  if (C == 0 || A == 0) return IMPNN_OK;
+  REQUIRE(u_cat && u_an && image && multipliers && (mean || std || score || samples), "null pointer");
+  if (int rc = grid_transfer_rule(__func__, g, image_floats)) return rc;
+  return launch_transfer_mc_grid(g, mean, std, score, samples);
+}
+
+int impnn_transfer_mc_grid_mask(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                const float* multipliers, int32_t S, float kappa, float lo, float hi, uint32_t* words,
+                                int32_t C, int32_t A, impnn_stream_t stream) {
+  const GridMaskCall c{transfer_mc_grid_operands(u_cat, u_an, image, multipliers, S, kappa, C, A, stream), lo, hi, words};
+  return grid_mask_checked(__func__, c, image_floats >= 0, u_cat && u_an && image && multipliers && words, image_floats);
+}
+
+int impnn_transfer_mc_grid_topk_workspace_bytes(int32_t S, int32_t C, int32_t A, int32_t k, int32_t workgroups,
+                                                size_t* need) {
+  if (int rc = mc_topk_shape(__func__, S, 0.f, C, A, k, workgroups)) return rc;
+  REQUIRE(need, "null pointer");
+  *need = grid_topk_workspace_bytes(3, C, A, 0, k, workgroups);
+  return IMPNN_OK;
+}
+
+int impnn_transfer_mc_grid_topk(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                const float* multipliers, int32_t S, float kappa, int32_t k, int32_t largest,
+                                float* values, int32_t* cation, int32_t* anion, void* workspace, size_t workspace_bytes,
+                                int32_t C, int32_t A, int32_t workgroups, impnn_stream_t stream) {
+  const GridTopkCall c{transfer_mc_grid_operands(u_cat, u_an, image, multipliers, S, kappa, C, A, stream), k, largest,
+                       values, cation, anion, workspace, workgroups, false, nullptr};
+  return grid_topk_checked(__func__, c, image_floats >= 0,
+                           u_cat && u_an && image && multipliers && values && cation && anion && workspace, image_floats,
+                           workspace_bytes);
+}
+
+int impnn_transfer_mc_grid_topk_where(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                      const float* multipliers, int32_t S, float kappa, const uint32_t* where,
+                                      int32_t k, int32_t largest, float* values, int32_t* cation, int32_t* anion,
+                                      void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
+                                      impnn_stream_t stream) {
+  const GridTopkCall c{transfer_mc_grid_operands(u_cat, u_an, image, multipliers, S, kappa, C, A, stream), k, largest,
+                       values, cation, anion, workspace, workgroups, true, where};
+  return grid_topk_checked(__func__, c, image_floats >= 0,
+                           u_cat && u_an && image && multipliers && values && cation && anion && workspace, image_floats,
+                           workspace_bytes);
 }
 
 // ---- the applicability domain (include/impnn.h; grid_domain.hip).  The three entries' order: shape (sizes, R >= 1,

@@ -293,14 +293,16 @@ int head_grid_max_temperatures();
 // The operands every grid launch shares (api.hip builds and checks them).  family 0: the head grid (`kind`, mixing
 // rows, T, the packed head of impnn_model_head in `w`); family 1: the transfer grid (u rows in mix_cat / mix_an, the
 // prepared image in `w`; kind 1, no T, no widths); family 2: the ensemble grid (`M` members of `kind`: mixing rows
-// (M,C,Mx) and (M,A,Mx), T, the members' tails (M, tail floats) in `w`, `kappa` of the score; no D).
+// (M,C,Mx) and (M,A,Mx), T, the members' tails (M, tail floats) in `w`, `kappa` of the score; no D); family 3: the
+// transfer MC grid (family 1's operands, `M` samples, their `multipliers` (M,128) and `kappa`).
 struct GridOperands {
   int family, kind;
   const float *mix_cat, *mix_an, *T, *w;
   int C, A, nT, D, F, Mx;
   hipStream_t stream;
-  int M;        // family 2
-  float kappa;  // family 2
+  int M;        // family 2: members; family 3: samples
+  float kappa;  // families 2 and 3
+  const float* multipliers;  // family 3
 };
 int launch_head_grid(const GridOperands& g, float* out, float* params);
 
@@ -378,6 +380,14 @@ int64_t ensemble_grid_tail_floats(int kind, int F, int Mx);
 int launch_ensemble_grid(const GridOperands& g, float* mean, float* std, float* score);
 int launch_ensemble_grid_mask(const GridMaskCall& c);
 int launch_ensemble_grid_topk(const GridTopkCall& c);
+
+// ---- Monte-Carlo dropout of the transfer head over the grid (transfer_mc_grid.hip; include/impnn.h,
+// impnn_transfer_mc_grid*): family 3 of GridOperands through the materialising, mask-writing and selecting forms.
+// api.hip checks the arguments.
+int transfer_mc_grid_max_samples();
+int launch_transfer_mc_grid(const GridOperands& g, float* mean, float* std, float* score, float* samples);
+int launch_transfer_mc_grid_mask(const GridMaskCall& c);
+int launch_transfer_mc_grid_topk(const GridTopkCall& c);
 
 // ---- each ion's best partners over a cation x anion grid (grid_partners.hip; include/impnn.h,
 // impnn_head_grid_partners / impnn_transfer_head_grid_partners).  The limits of one launch (ops.py mirrors them): m, at

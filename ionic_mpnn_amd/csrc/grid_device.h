@@ -1280,13 +1280,14 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
 
 // ================================================================ host side: the tile geometry and the one launcher
 // Tiles along C, tiles along A and the tile's size for a family (0: head grid, 1: transfer grid, 2: ensemble grid - the
-// head grid's tile).
+// head grid's tile, 3: transfer MC grid - the transfer grid's tile).
 struct GridTiles {
   int tile_c, tile_a, c, a;
   int64_t count() const { return (int64_t)c * a; }
 };
 inline GridTiles grid_tiles(int family, int C, int A) {
-  const int tc = family != 1 ? kTileC : kTgTileC, ta = family != 1 ? kTileA : kTgTileA;
+  const bool head = family != 1 && family != 3;
+  const int tc = head ? kTileC : kTgTileC, ta = head ? kTileA : kTgTileA;
   return {tc, ta, (C + tc - 1) / tc, (A + ta - 1) / ta};
 }
 // a workgroup per tile (the materialising and the mask-writing launches): the tiles must fit one launch

@@ -1762,6 +1762,15 @@ class MPNNModel:
             raise ValueError("k must be >= 1")
         return _Screen(self, cations, anions, T, where, batch_size).top_k(k, largest, max_pairs_per_launch)
 
+    def mc_dropout(self, samples=32, draw=0):
+        """Monte-Carlo dropout of the transfer head as a screening model -> ``mc_dropout.McDropout``: ``samples``
+        stochastic passes with ``mp_dropout`` on (the masks of dropout step ``draw``, the same for every pair) and
+        BatchNormalization on its moving statistics, and ``predict_grid`` / ``screen_mask`` / ``screen_top_k`` /
+        ``predict_pairs`` on their mean, spread and mean + kappa * std (impnn_transfer_mc_grid*).  Only the transfer
+        model has a head Dropout: any other kind, and widths the transfer grid does not cover, raise a ValueError."""
+        from .mc_dropout import McDropout
+        return McDropout(self, samples, draw)
+
     def screen_best_partners(self, cations, anions, temperatures=None, m=1, largest=False, where=None,
                              max_pairs_per_launch=None, batch_size=4096):
         """For every cation of a screen its ``m`` best anions, and for every anion its ``m`` best cations, selected on

@@ -876,24 +876,26 @@ def head_ion_mix(kind, ion, pooled, head_weights, fp_size, mixing_size):
 # below them are "build the operands, call the operation"
 class GridOperands:
     """The validated operands of the screening family's launches over one cation x anion grid, built by
-    ``head_grid_operands`` (family 0), ``transfer_grid_operands`` (family 1) or ``ensemble_grid_operands`` (family 2):
+    ``head_grid_operands`` (family 0), ``transfer_grid_operands`` (family 1), ``ensemble_grid_operands`` (family 2) or
+    ``transfer_mc_grid_operands`` (family 3: family 1's tensors, ``multipliers`` (S,128) - ``samples`` = S - and ``kappa``):
     the contiguous float32 tensors (``cat`` and ``an`` rows, ``T`` or None, ``w``: the packed head, the prepared image or
     the members' tails), ``kind`` as the C entries take it (0 viscosity, 1 melting point and transfer) and ``widths``: (D,
     fp_size, mixing_size) for the head family, (fp_size, mixing_size) for the ensemble family, whose rows are
     three-dimensional - (M,C,Mx) and (M,A,Mx), ``members`` = M - and which carries ``kappa`` of its score.  ``lead`` and
     ``trail`` are the arguments every C entry of the family opens and closes with; the operation's own go between.
     ``rows`` and ``temperatures`` narrow it without validating again (the host tiling of model.py)."""
-    __slots__ = ("family", "kind", "cat", "an", "T", "w", "widths", "kappa")
+    __slots__ = ("family", "kind", "cat", "an", "T", "w", "widths", "kappa", "multipliers")
 
-    def __init__(self, family, kind, cat, an, T, w, widths=(), kappa=0.0):
+    def __init__(self, family, kind, cat, an, T, w, widths=(), kappa=0.0, multipliers=None):
         self.family, self.kind, self.cat, self.an, self.T, self.w, self.widths = family, kind, cat, an, T, w, widths
-        self.kappa = kappa
+        self.kappa, self.multipliers = kappa, multipliers
 
     C = property(lambda self: int(self.cat.shape[-2]))
     A = property(lambda self: int(self.an.shape[-2]))
     nT = property(lambda self: int(self.T.numel()) if self.T is not None else 0)
     D = property(lambda self: self.widths[0] if self.family == 0 else None)
     members = property(lambda self: int(self.cat.shape[0]) if self.family == 2 else 1)
+    samples = property(lambda self: int(self.multipliers.shape[0]) if self.family == 3 else 1)
     device = property(lambda self: self.cat.device)
 
     @property
@@ -903,14 +905,15 @@ class GridOperands:
             return self.kind, ptr(self.cat), ptr(self.an), T, ptr(self.w)
         if self.family == 2:
             return self.kind, self.members, ptr(self.cat), ptr(self.an), T, ptr(self.w), self.kappa
-        return ptr(self.cat), ptr(self.an), ptr(self.w), self.w.numel()
+        image = ptr(self.cat), ptr(self.an), ptr(self.w), self.w.numel()
+        return image if self.family == 1 else (*image, ptr(self.multipliers), self.samples, self.kappa)
 
     @property
     def trail(self):
-        return (self.C, self.A, self.nT, *self.widths) if self.family != 1 else (self.C, self.A)
+        return (self.C, self.A, self.nT, *self.widths) if self.family in (0, 2) else (self.C, self.A)
 
     def _narrowed(self, cat, T):
-        return GridOperands(self.family, self.kind, cat, self.an, T, self.w, self.widths, self.kappa)
+        return GridOperands(self.family, self.kind, cat, self.an, T, self.w, self.widths, self.kappa, self.multipliers)
 
     def rows(self, lo, hi):
         """Cations lo .. hi of the grid (of every member: a copy, the C entries take contiguous rows)."""
@@ -998,11 +1001,49 @@ def ensemble_grid_operands(kind, mix_cat, mix_an, temperatures, tails, fp_size, 
     return GridOperands(2, k, mix_cat, mix_an, T, tails, (fp_size, mixing_size), kappa)
 
 
+def transfer_mc_grid_operands(u_cat, u_an, image, multipliers, kappa=0.0):
+    """The operands of Monte-Carlo dropout over the transfer head's grid (impnn_transfer_mc_grid*) -> GridOperands,
+    family 3.  ``u_cat``, ``u_an``, ``image`` as ``transfer_grid_operands``; ``multipliers`` (S,128) float32: sample s
+    multiplies feature j of relu(Dense 128) by ``multipliers[s, j]`` (0: the feature is dropped) - for a Dropout,
+    ``dropout_mask(dropout, rows=S, D=128)``, whose row s is the mask a training pass at that step gives batch row s.
+    The table is the same for every pair (the "fixed set of masks" form of MC dropout): a pair's S values, and so its
+    mean, spread and score, depend only on its two u rows, the image and the table - not on the tile, the launch, the
+    host tiling or the grid's size.  ``kappa``: the score is mean + kappa * std, any finite float."""
+    g = transfer_grid_operands(u_cat, u_an, image)
+    require_gpu(multipliers)
+    multipliers = f32c(multipliers)
+    most = int(_lib.load().impnn_transfer_mc_grid_max_samples())
+    if multipliers.dim() != 2 or multipliers.shape[1] != TRANSFER_MC_WIDTH or not 1 <= multipliers.shape[0] <= most:
+        raise ValueError(f"multipliers must be (S,{TRANSFER_MC_WIDTH}) with 1 <= S <= {most}, got {tuple(multipliers.shape)}")
+    kappa = C.c_float(kappa).value  # as the kernels see it: float32
+    if kappa != kappa or kappa in (float("inf"), float("-inf")):
+        raise ValueError("kappa must be finite")
+    return GridOperands(3, 1, g.cat, g.an, None, g.w, (), kappa, multipliers)
+
+
+def transfer_mc_grid(g, return_samples=False):
+    """The materialised statistic of a family-3 ``g`` (impnn_transfer_mc_grid) -> (mean, std, score), each (C,A); with
+    ``return_samples`` also the S sample planes (S,C,A), whose statistic in ``data.ensemble_grid_stats``'s order the
+    three are."""
+    if g.family != 3:
+        raise ValueError("transfer_mc_grid takes the operands of transfer_mc_grid_operands")
+    dev = g.device
+    outs = [torch.empty(g.C, g.A, dtype=torch.float32, device=dev) for _ in range(3)]
+    samples = torch.empty(g.samples, g.C, g.A, dtype=torch.float32, device=dev) if return_samples else None
+    with torch.cuda.device(dev):
+        check(_lib.load().impnn_transfer_mc_grid(*g.lead, *[ptr(o) for o in outs],
+                                                 ptr(samples) if samples is not None else None, *g.trail, stream_ptr()))
+    return (*outs, samples) if return_samples else tuple(outs)
+
+
 def grid_values(g, return_params=False):
     """The materialised grid of ``g`` (impnn_head_grid / impnn_transfer_head_grid): what ``head_grid`` /
-    ``transfer_head_grid`` return for the same operands.  An ensemble grid (impnn_ensemble_grid): (mean, std, score)."""
+    ``transfer_head_grid`` return for the same operands.  An ensemble grid (impnn_ensemble_grid) and a transfer MC grid
+    (impnn_transfer_mc_grid): (mean, std, score)."""
     _require_params_kind(return_params, g.kind)
     dev = g.device
+    if g.family == 3:
+        return transfer_mc_grid(g)
     if g.family == 2:
         if return_params:
             raise ValueError("return_params: an ensemble grid has no VFT parameters of its own")
@@ -1023,14 +1064,17 @@ def grid_values(g, return_params=False):
 
 
 def _grid_entry(g, name):
-    """The C entry ``name`` of g's family: impnn_head_grid_<name>, impnn_transfer_head_grid_<name> or
-    impnn_ensemble_grid_<name>."""
-    return getattr(_lib.load(), ("impnn_head_grid_", "impnn_transfer_head_grid_", "impnn_ensemble_grid_")[g.family] + name)
+    """The C entry ``name`` of g's family: impnn_head_grid_<name>, impnn_transfer_head_grid_<name>,
+    impnn_ensemble_grid_<name> or impnn_transfer_mc_grid_<name>."""
+    return getattr(_lib.load(), ("impnn_head_grid_", "impnn_transfer_head_grid_", "impnn_ensemble_grid_",
+                                 "impnn_transfer_mc_grid_")[g.family] + name)
 
 
 def _refuse_ensemble(g):
     if g.family == 2:
         raise NotImplementedError("ensemble grids: partners / rank are not built")
+    if g.family == 3:
+        raise NotImplementedError("transfer MC grids: partners / rank are not built")
 
 
 def grid_topk(g, k, largest=False, workgroups=0, where=None):
@@ -1041,7 +1085,7 @@ def grid_topk(g, k, largest=False, workgroups=0, where=None):
         where = _mask_words(where, g.C, g.A, g.device)
     with torch.cuda.device(g.device):
         values, cation, anion, ws, nbytes = _grid_topk_outputs(_lib.load(), g.family, g.C, g.A, g.nT, k, workgroups, g.device,
-                                                               g.members)
+                                                               g.members if g.family != 3 else g.samples)
         mask = () if where is None else (ptr(where),)
         check(_grid_entry(g, "topk" if where is None else "topk_where")(
             *g.lead, *mask, k, int(bool(largest)), ptr(values), ptr(cation), ptr(anion), ptr(ws), nbytes, *g.trail,
@@ -1101,6 +1145,7 @@ def head_grid(kind, mix_cat, mix_an, temperatures, head_weights, fp_size, mixing
 
 
 TRANSFER_GRID_WIDTH = 256  # mp_dense_1's units: the width of a ``transfer_ion_half`` row
+TRANSFER_MC_WIDTH = 128    # mp_dense_2's units: the features mp_dropout thins, the width of a multiplier row
 
 
 def _transfer_weight_table(weights):
@@ -1164,6 +1209,8 @@ def _grid_topk_outputs(lib, family, C_, A_, nT, k, workgroups, dev, members=1):
     need = C.c_size_t(0)
     if family == 2:  # the ensemble grid has its own query: its temperature limit depends on the members
         check(lib.impnn_ensemble_grid_topk_workspace_bytes(members, C_, A_, nT, k, workgroups, C.byref(need)))
+    elif family == 3:  # the transfer MC grid's: ``members`` is its sample count
+        check(lib.impnn_transfer_mc_grid_topk_workspace_bytes(members, C_, A_, k, workgroups, C.byref(need)))
     else:
         check(lib.impnn_grid_topk_workspace_bytes(family, C_, A_, nT, k, workgroups, C.byref(need)))
     values = torch.empty(rows, k, dtype=torch.float32, device=dev)

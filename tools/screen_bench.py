@@ -9,6 +9,7 @@ python tools/screen_bench.py --select --where FRACTION [--quick]        -> the c
 python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each ion's best partners instead (see below)
 python tools/screen_bench.py --rank [--where FRACTION] [--quick]        -> the best-k pair mask instead (see below)
 python tools/screen_bench.py --ensemble M [--select] [--where FRACTION] [--size N]  -> a deep ensemble instead (see below)
+python tools/screen_bench.py --mc S [--select] [--where FRACTION] [--size N]        -> Monte-Carlo dropout instead (see below)
 python tools/screen_bench.py --pareto [--where FRACTION] [--size N]     -> the Pareto front of two models instead (see below)
 python tools/screen_bench.py --domain R [--size N]                       -> the applicability domain instead (see below)
 
@@ -54,6 +55,14 @@ data.ensemble_grid_stats on the host (the two must agree bit for bit).  With --s
 kappa = 1) against the same M grids, the host statistic and data.grid_top_k; with --where F both under one random pair
 mask of density F.
 
+--mc S: MPNNModel.mc_dropout(S) of a transfer model (atom_dim 32, 3 steps) over N x N pairs (--size, default 4096).  Five
+alternating rounds after a warm-up of each, wall time, median and spread, of mc.predict_grid(kappa = 1) beside the
+deterministic predict_grid of the same model and species (one grid against the mean, spread and score of S).  Then the
+launches alone over resident u rows, 10 calls between two HIP events, five rounds each in turn: impnn_transfer_mc_grid
+(mean, std and score written) beside impnn_transfer_head_grid, their ratio beside the MFMA-count expectation
+(1024 + 256 S) / 1280, and the f32 MFMA rate of both.  With --select: mc.screen_top_k(k = 100, kappa = 1) beside the
+model's screen_top_k, and the selecting launches of both; with --where F under one random pair mask of density F.
+
 --pareto: screen_pareto of a viscosity model at 298.15 K against a melting-point model (atom_dim 32, 3 steps) over N x N
 pairs (--size, default 4096), both minimised, against the way to the same front without it: two predict_grid calls and
 data.pareto_front on the host.  Three alternating rounds after a warm-up of each, wall time, median and spread; the two
@@ -94,14 +103,16 @@ ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: 
                 "with --partners, --rank: a random mask of this density")
 ap.add_argument("--ensemble", type=int, metavar="M", help="a ModelEnsemble of M viscosity models against M predict_grid calls "
                 "and the host statistic; with --select the top-k on the score")
+ap.add_argument("--mc", type=int, metavar="S", help="MC dropout of a transfer model with S samples beside its deterministic grid; "
+                "with --select the top-k on the score")
 ap.add_argument("--pareto", action="store_true", help="time screen_pareto (viscosity x melting point) against two predict_grid "
                 "calls and data.pareto_front on the host")
 ap.add_argument("--domain", type=int, metavar="R", help="time screen_domain_mask and domain_grid over R reference pairs "
                 "against gathered tiles, torch.cdist and min")
-ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --pareto, --domain: cations = anions = this many")
+ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --mc, --pareto, --domain: cations = anions = this many")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain  # another table than the default one
+other = args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain or args.mc  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -375,6 +386,58 @@ elif args.pareto:
             "speedup": round(statistics.median(t_old) / statistics.median(t_new), 2),
             "stage_launch_us": {n: spread(x) for n, x in stage_us.items()},
             "same_answer": bool(a.competing == b.competing and same_top(a[:3], b[:3]))}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+elif args.mc:
+    S, N, kappa = args.mc, args.size, 1.0
+    t = build_transfer(32, 3)
+    mcd = t.mc_dropout(S)
+    cat, _ = species(N, 1)
+    _, an = species(N, 2)
+    where = None
+    if args.where is not None:
+        where = data.PairMask.from_bool(np.random.default_rng(0).random((N, N)) < args.where, device=dev)
+    if args.select:
+        plain = lambda: t.screen_top_k(cat, an, k=SELECT_K, where=where)
+        sampled = lambda: mcd.screen_top_k(cat, an, k=SELECT_K, kappa=kappa, where=where)
+    else:
+        plain = lambda: t.predict_grid(cat, an)
+        sampled = lambda: mcd.predict_grid(cat, an, kappa=kappa)
+    wall(plain), wall(sampled)
+    t_plain, t_mc = [], []
+    for _ in range(5):
+        t_plain.append(wall(plain)[0])
+        t_mc.append(wall(sampled)[0])
+    with torch.no_grad():
+        pc, pa = t.encode_ions(cat, an)
+        tensors, image = t._head_tensors(), t._transfer_image()
+        uc = ops.transfer_ion_half("cat", pc, tensors, t.fp_size, t.mixing_size)
+        ua = ops.transfer_ion_half("an", pa, tensors, t.fp_size, t.mixing_size)
+        g1, g3 = ops.transfer_grid_operands(uc, ua, image), ops.transfer_mc_grid_operands(uc, ua, image, mcd.multipliers(), kappa)
+        words = None if where is None else where.words
+        if args.select:
+            k_plain = lambda: [ops.grid_topk(g1, SELECT_K, where=words) for _ in range(10)]
+            k_mc = lambda: [ops.grid_topk(g3, SELECT_K, where=words) for _ in range(10)]
+        else:
+            k_plain = lambda: [ops.grid_values(g1) for _ in range(10)]
+            k_mc = lambda: [ops.grid_values(g3) for _ in range(10)]
+        timed(k_plain), timed(k_mc)
+        us_plain, us_mc = [], []
+        for _ in range(5):
+            us_plain.append(timed(k_plain)[0] / 10 * 1e3)
+            us_mc.append(timed(k_mc)[0] / 10 * 1e3)
+    ratio = statistics.median(us_mc) / statistics.median(us_plain)
+    expect = (1024 + 256 * S) / 1280
+    live = N * N if where is None or not args.select else None  # (a masked selection passes over empty tiles)
+    mc_flop = 2 * (256 * 128 + S * (128 * 64 + 64))
+    line = {"config": f"mc S={S} {N}x{N}" + (" select" if args.select else "") + (f" where {args.where}" if where is not None else ""),
+            "samples": S, "C": N, "A": N, "deterministic_ms": spread(t_plain), "mc_dropout_ms": spread(t_mc),
+            "wall_ratio": round(statistics.median(t_mc) / statistics.median(t_plain), 2),
+            "deterministic_launch_us": spread(us_plain), "mc_launch_us": spread(us_mc), "launch_ratio": round(ratio, 2),
+            "mfma_count_ratio": round(expect, 2), "launch_ratio_over_expected": round(ratio / expect, 2)}
+    if live is not None:
+        line["deterministic_of_f32_mfma_peak"] = round(live * PAIR_FLOP / (statistics.median(us_plain) * 1e-6) / MFMA_F32_PEAK, 3)
+        line["mc_of_f32_mfma_peak"] = round(live * mc_flop / (statistics.median(us_mc) * 1e-6) / MFMA_F32_PEAK, 3)
     print(json.dumps(line), flush=True)
     lines.append(line)
 elif args.ensemble:
