@@ -23,9 +23,13 @@
 //     global_load_lds, addressed by the plan's slot-ordered source list, while the PREVIOUS chunk is pooled; step 0's
 //     update image goes the same way.  The same holds for the z / r gate accumulators after their h half (bias + W_h h):
 //     an image of the with-gates entry carries them as a second table (G0Header) and step 0's atom phase loads a row.
+//     With both tables nothing fills the h buffer for step 0: a tile's wave takes its rows' h quads into registers in front
+//     of the prologue barrier and runs that step's atom phase outside the step loop, without a mid-step barrier.
 //
 // MFMA work per row is 12 D^2 (update) + 2 D^2 per in-edge, against (12 + 2 K) D^2 per row in the pull form:
 // 2.7 kflop instead of 28.7 kflop per row for the message at bond_dim 8 and 1.7 in-edges per row.
+#include <type_traits>
+
 #include "encoder_device.h"
 #include "encoder_layout.h"
 #include "kernel_device.h"
@@ -285,6 +289,29 @@ __global__ __launch_bounds__(64) void typed_g0_kernel(const float* upd0, const f
 #define IMPNN_T_POOLB 1
 #endif
 constexpr bool kUseG0 = IMPNN_T_G0 != 0, kPoolBatch = IMPNN_T_POOLB != 0;
+// The start of a table-fed chunk - one whose ion's image carries both tables.  IMPNN_T_PEEL is on; IMPNN_T_REC2 and
+// IMPNN_T_IMGH were measured and dropped and are off: each made the kernel slower than the peel alone.
+//   IMPNN_T_PEEL   step 0 leaves the step loop: its tile's h rows and Reduce's record words are requested in front of
+//                  the prologue barrier, nothing fills h, and the mid-step barrier of that step is gone
+#ifndef IMPNN_T_PEEL
+#define IMPNN_T_PEEL 1
+#endif
+// (Measured and dropped, DESIGN.md 4.1: the tile's G0 rows among those pre-loads, and the scalar chain of the wave's two fixed
+//  runs in front of that barrier too - the transfers of fetch_step0 have landed when the prologue barrier is reached, so what
+//  is requested in front of it is waited for in full, by all sixteen waves.)
+//   IMPNN_T_REC2   a launch in which every ion is table-fed keeps TWO record buffers, the second where the LDS copy of
+//                  the atom table lay (nothing but fill_h0 read it): the next chunk's record is stored into the idle one
+//                  behind step 0, so the store behind the pool and its barrier are gone
+//   IMPNN_T_IMGH   fetch_step0 leaves the h-half blocks of z and r out of step 0's update image when the chunk's ion has
+//                  the gate table: step 0 never reads them (mode 3: 12 of the image's 37 one-KB granules)
+#ifndef IMPNN_T_REC2
+#define IMPNN_T_REC2 0
+#endif
+#ifndef IMPNN_T_IMGH
+#define IMPNN_T_IMGH 0
+#endif
+constexpr bool kPeel = kUseG0 && IMPNN_T_PEEL != 0, kTwoRec = kPeel && IMPNN_T_REC2 != 0;
+constexpr bool kSkipImgH = kUseG0 && IMPNN_T_IMGH != 0;
 
 // Where the loads of the NEXT step are issued (diagnostics builds may override):
 //   kPfWhere   0: the step's update image at the top of its own message phase; 1: during the previous step's atom phase,
@@ -300,13 +327,13 @@ constexpr bool kUseG0 = IMPNN_T_G0 != 0, kPoolBatch = IMPNN_T_POOLB != 0;
 constexpr int kPfWhere = IMPNN_T_PF, kRunsEarly = IMPNN_T_EARLY;
 // Reduce (models/layers.py:57-83), the in-edge ranks d0 .. d0 + N - 1 of a tile's rows in one LDS round trip: agg += the
 // rows' messages of these ranks, in rank order; a rank a row does not have reads the slot of zeros (x + 0 = x: no branch,
-// all 2 N loads of the round in flight together).  jdptr: the record's u16[260] incl. padding, d0 a multiple of 4 (one
-// aligned 8-byte read, d0 + 3 <= 258).  LANES: the adds as single-lane instructions (mode 3 runs them beside the MFMAs
+// all 2 N loads of the round in flight together).  jd: the four u16 of the record's jdptr at d0 (u16[260] incl. padding,
+// d0 a multiple of 4: one aligned 8-byte read, d0 + 3 <= 258).
+// LANES: the adds as single-lane instructions (mode 3 runs them beside the MFMAs
 // of the gates' h halves, where a v_pk_add_f32 costs more issue time than two v_add_f32; the same IEEE sums either way).
 template <int N, bool LANES>
-__device__ __forceinline__ void reduce_ranks(const float* msg, const uint16_t* jdptr, int d0, int deg, int row, int q,
+__device__ __forceinline__ void reduce_ranks(const float* msg, const uint2 jd, int d0, int deg, int row, int q,
                                              int zero_slot, f32x4& agg0, f32x4& agg1) {
-  const uint2 jd = *reinterpret_cast<const uint2*>(jdptr + d0);
   const int first[4] = {(int)(jd.x & 0xffffu), (int)(jd.x >> 16), (int)(jd.y & 0xffffu), (int)(jd.y >> 16)};
   f32x4 m0v[N], m1v[N];
 #pragma unroll
@@ -347,6 +374,14 @@ __device__ __forceinline__ f32x4 quad(F f, A... a) {
   }
 }
 
+// What a tile's wave holds of step 0 of a table-fed chunk when it leaves the prologue barrier (lane (a, q) of row a): the
+// row's h quads and Reduce's first record words.
+struct Step0Pre {
+  f32x4 h0, h1;
+  uint2 jd;
+  int deg, maxdeg;
+};
+
 template <bool STAMPS, bool X3, int HS = kTHS>
 __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel(TEncParams p) {
   extern __shared__ __align__(16) float smem[];
@@ -357,19 +392,32 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
   float* const hbuf = smem + off_h(X3);
   float* const msg = smem + off_msg(X3, HS);
   const int zero_slot = p.ecap + 1;  // (dump slot: p.ecap)
-  unsigned char* const recl = reinterpret_cast<unsigned char*>(smem + off_rec(X3, p.ecap, HS));
-  const int rec_lds = p.rec_lds;                                 // trec_lds_bytes(Vb)
-  float* const atab = reinterpret_cast<float*>(recl + rec_lds);  // Va rows + one zero row (when it fits)
-  const uint16_t* const r_rowdeg = reinterpret_cast<const uint16_t*>(recl + kTRecRowdeg);
-  const unsigned char* const r_tilemax = recl + kTRecTilemax;
-  const uint16_t* const r_moloff = reinterpret_cast<const uint16_t*>(recl + kTRecMoloff);
-  const uint16_t* const r_molrows = reinterpret_cast<const uint16_t*>(recl + kTRecMolrows);
-  const uint16_t* const r_poolrow = reinterpret_cast<const uint16_t*>(recl + kTRecPoolrow);
-  const int32_t* const r_rowatom = reinterpret_cast<const int32_t*>(recl + kTRecRowatom);
-  const uint16_t* const r_jdptr = reinterpret_cast<const uint16_t*>(recl + kTRecJdptr);
-  const uint16_t* const r_runs = reinterpret_cast<const uint16_t*>(recl + trec_runs_off(p.Vb, p.ecap));
-  int* const run_ctr = reinterpret_cast<int*>(recl + kTRecCounts + 8);  // next dynamically assigned type run
-  const uint4* const r_grp = reinterpret_cast<const uint4*>(recl + kTRecGrp);
+  // The record buffer of the current chunk: recl0, or - two record buffers (kTwoRec, below) - recl0 + rec_lds in turn.
+  unsigned char* const recl0 = reinterpret_cast<unsigned char*>(smem + off_rec(X3, p.ecap, HS));
+  const int rec_lds = p.rec_lds;                                  // trec_lds_bytes(Vb)
+  float* const atab = reinterpret_cast<float*>(recl0 + rec_lds);  // Va rows + one zero row (when it fits)
+  unsigned char* recl;
+  const uint16_t *r_rowdeg, *r_moloff, *r_molrows, *r_poolrow, *r_jdptr, *r_runs;
+  const unsigned char* r_tilemax;
+  const int32_t* r_rowatom;
+  int* run_ctr;  // next dynamically assigned type run
+  const uint4* r_grp;
+  const uint32_t* grp_x;
+  auto use_record = [&](unsigned char* base) {
+    recl = base;
+    r_rowdeg = reinterpret_cast<const uint16_t*>(recl + kTRecRowdeg);
+    r_tilemax = recl + kTRecTilemax;
+    r_moloff = reinterpret_cast<const uint16_t*>(recl + kTRecMoloff);
+    r_molrows = reinterpret_cast<const uint16_t*>(recl + kTRecMolrows);
+    r_poolrow = reinterpret_cast<const uint16_t*>(recl + kTRecPoolrow);
+    r_rowatom = reinterpret_cast<const int32_t*>(recl + kTRecRowatom);
+    r_jdptr = reinterpret_cast<const uint16_t*>(recl + kTRecJdptr);
+    r_runs = reinterpret_cast<const uint16_t*>(recl + trec_runs_off(p.Vb, p.ecap));
+    run_ctr = reinterpret_cast<int*>(recl + kTRecCounts + 8);
+    r_grp = reinterpret_cast<const uint4*>(recl + kTRecGrp);
+    grp_x = reinterpret_cast<const uint32_t*>(r_grp);
+  };
+  use_record(recl0);
 
   const int tid = threadIdx.x, lane = tid & 63;
   // (readfirstlane: uniform to the compiler too, so the run loop's conditions stay scalar - and no register spills)
@@ -397,9 +445,12 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
   const int c_end = c_begin + __builtin_amdgcn_readfirstlane(p.nsub[blockIdx.x]);
   if (c_begin >= c_end) return;
 
-  if (p.atab_lds)
+  bool atab_in_lds = p.atab_lds;  // (false as well where the second record buffer takes its place: below)
+  auto copy_atab = [&]() {
     for (int t = tid; t < (p.Va + 1) * (kTAS / 4); t += kThreads)  // kTAS == kD: a verbatim copy + one zero row
       st4(atab + 4 * t, t < p.Va * (kD / 4) ? ld4(p.atom_table + 4 * t) : f32x4{0.f, 0.f, 0.f, 0.f});
+  };
+  if (p.atab_lds && p.S == 0) copy_atab();
   if (tid < kD) msg[zero_slot * kD + tid] = 0.f;  // never written again: what a row reads beyond its in-degree
   unsigned long long t_pro = 0, t_steps = 0, t_pool = 0, t_mark = 0, t_msg = 0;
   if (stamp && tid == 0) t_mark = __builtin_amdgcn_s_memtime();
@@ -460,7 +511,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     const int id = r_rowatom[row];
     f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
     if ((unsigned)id < (unsigned)p.Va) {
-      if (p.atab_lds) {
+      if (atab_in_lds) {
         v0 = ld4(atab + id * kTAS + 8 * sub);
         v1 = ld4(atab + id * kTAS + 8 * sub + 4);
       } else {
@@ -513,6 +564,18 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     }
   }
 
+  // Two record buffers: every ion of the launch table-fed (so every chunk is peeled and nothing but the pre-loads reads the
+  // atom table - they take it from L2 then, with fill_h0's select), and a second record fits where the host made room for
+  // the LDS copy of the table.  Workgroup-uniform.  The buffers alternate chunk by chunk; the next chunk's record reaches
+  // the idle one from the registers it travels in, behind step 0's end-of-step barrier (its loads were requested a whole
+  // atom phase earlier; the idle buffer's last readers were the previous chunk's pool, in front of that pool's barrier).
+  bool two_rec = false;
+  if constexpr (kTwoRec)
+    two_rec = p.atab_lds && tabmask == (p.n_ions > 1 ? 0xfu : 0x5u) && rec_lds <= (p.Va + 1) * kTAS * (int)sizeof(float);
+  if (two_rec) atab_in_lds = false;
+  if (atab_in_lds) copy_atab();
+  bool rec_in_lds = false;  // the current chunk's record is in its buffer already
+
   // The record of the NEXT chunk travels in registers while the current chunk runs.
   const bool rec_big = rec_lds > kTRecPart1;  // workgroup-uniform
   const unsigned char* rec_c = p.rec + (size_t)c_begin * kTRecBytes;
@@ -561,10 +624,15 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       for (int i = 0; i < kIt; ++i) sw[i] = 0u;
     }
     constexpr int kUIt = (kUpdLds / 256 + kWaves - 1) / kWaves;
+    // (kSkipImgH: with the gate table in use, step 0 starts z and r behind their h half, so the blocks that multiply h -
+    //  half 0 of the gates' blocks, image layout as in gates_h_half - are not sent; every later step stores its whole image)
+    const bool gaten = kSkipImgH && ((tabmask >> (2 + gn)) & 1u);  // workgroup-uniform
 #pragma unroll
     for (int i = 0; i < kUIt; ++i) {  // (under the list's round trip)
-      const int ub = 64 * (wv + i * kWaves);
-      if (ub < kUpdLds / 4) glds16(ug + 4 * (ub + ln), wupd + 4 * ub);  // (wave-uniform)
+      const int gi = wv + i * kWaves, ub = 64 * gi;  // granule of 1 KB
+      // mode 3: block ((gate*2 + T)*2 + half) is 3 granules; mode 2: block ((gate*2 + T)*2 + half)*2 + u is one
+      const bool h_half = X3 ? (gi < 24 && ((gi / 3) & 1) == 0) : (gi < 16 && (gi & 2) == 0);
+      if (ub < kUpdLds / 4 && !(gaten && h_half)) glds16(ug + 4 * (ub + ln), wupd + 4 * ub);  // (wave-uniform)
     }
     static_assert(kIt == 5, "the list words are landed by name");
     asm volatile("" : "+v"(sw[0]), "+v"(sw[1]), "+v"(sw[2]), "+v"(sw[3]), "+v"(sw[4]) : : "memory");
@@ -583,7 +651,6 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
   fetch_step0(dsc_next, c_begin);
 
   // message-phase lane roles (see the message phase below)
-  const uint32_t* const grp_x = reinterpret_cast<const uint32_t*>(r_grp);
   const int kh = lane >> 5, f = lane & 31;
   const int boff = kh * 512 + f * 4;
   const int ysh = 8 * (lane & 3), zsh = 16 * kh;
@@ -599,10 +666,68 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     const float* upd_g = p.upd[g];
     const float* tmat_g = p.tmat[g];
     const bool tab0 = (tabmask >> g) & 1u;  // workgroup-uniform: step 0's messages come from the table
-    if (8 * tid < rec_lds) reinterpret_cast<uint2*>(recl)[tid] = rec_n8;
-    if (rec_big && kTRecPart1 + 4 * tid < rec_lds) reinterpret_cast<uint32_t*>(recl + kTRecPart1)[tid] = rec_n4;
-    lds_barrier();
-    fill_h0();
+    auto store_record = [&](unsigned char* dst) {
+      if (8 * tid < rec_lds) reinterpret_cast<uint2*>(dst)[tid] = rec_n8;
+      if (rec_big && kTRecPart1 + 4 * tid < rec_lds) reinterpret_cast<uint32_t*>(dst + kTRecPart1)[tid] = rec_n4;
+    };
+    if (!rec_in_lds) {
+      store_record(recl);
+      lds_barrier();
+    }
+    // A table-fed chunk (both tables): step 0 has no message phase and takes the h half of its gates from G0, so nothing
+    // reads h in that step but lane (a, q) its own row's quads - for r h, the blend and the residual.  Those go straight
+    // into the registers of the tile's wave, with Reduce's record words, HERE: every register of the message phase is
+    // free, and the LDS round trips pass in front of the prologue barrier.  No fill_h0 - 1024 threads, five LDS accesses
+    // each in a chain three deep - and step 0 runs outside the step loop (below), without a mid-step barrier.  Rows of
+    // hbuf that belong to no tile of this chunk keep the previous chunk's bytes; nothing reads them.
+    const bool peel = kPeel && ((tabmask >> g) & 1u) && ((tabmask >> (2 + g)) & 1u);  // workgroup-uniform
+    // Tile -> wave map as in encoder_fused.hip: waves w, w+4, w+8, w+12 share a SIMD; tiles are ordered heavy -> light,
+    // the SIMD groups with one tile fewer take the heaviest.  (Evaluated where it is asked: no register held for it.)
+    auto tile_of_wave = [&](const int wave) -> int {
+      int my_tile = -1;
+      const int grp = wave & 3, slot = wave >> 2, q4 = ntiles >> 2, r4 = ntiles & 3;
+      const int heavy = (4 - r4) * q4;
+      if (grp >= r4) {
+        if (slot < q4) my_tile = slot * (4 - r4) + (grp - r4);
+      } else if (slot <= q4) {
+        my_tile = heavy + slot * r4 + grp;
+      }
+      return my_tile < ntiles ? my_tile : -1;
+    };
+    // (Given a value on every path: left undefined for the waves without a tile, the compiler keeps five of the quads in
+    //  scratch between the two places - 100-120 bytes in every instantiation.)
+    Step0Pre pre{};
+    auto preload_step0 = [&]() {
+      // (lane and wave roles from opaque copies of the ids, as in fetch_step0: shared with the step loop's atom phase they
+      //  would be held in registers through every message phase)
+      int ln = lane, wv = wave;
+      asm volatile("" : "+v"(ln), "+s"(wv));
+      const int a = ln & 15, q = ln >> 4;
+      const int tile = tile_of_wave(wv);
+      if (tile >= 0) {
+        const int row = tile * 16 + a;
+        const int id = r_rowatom[row];
+        pre.deg = r_rowdeg[row];
+        pre.maxdeg = r_tilemax[tile];
+        pre.jd = *reinterpret_cast<const uint2*>(r_jdptr);
+        // (clamped exactly where fill_h0 writes zeros: the zero row of the LDS atom table)
+        const unsigned col = (unsigned)id < (unsigned)p.Va ? (unsigned)id : (unsigned)p.Va;
+        if (atab_in_lds) {
+          pre.h0 = ld4(atab + col * kTAS + 4 * q);
+          pre.h1 = ld4(atab + col * kTAS + 16 + 4 * q);
+        } else {
+          pre.h0 = pre.h1 = f32x4{0.f, 0.f, 0.f, 0.f};
+          if ((unsigned)id < (unsigned)p.Va) {
+            pre.h0 = ld4(p.atom_table + (int64_t)id * kD + 4 * q);
+            pre.h1 = ld4(p.atom_table + (int64_t)id * kD + 16 + 4 * q);
+          }
+        }
+      }
+    };
+    if (peel)
+      preload_step0();
+    else
+      fill_h0();
     // (step 0's messages - when the image carries the table - and its update image are on their way into LDS since the
     //  previous chunk's last step: fetch_step0)
     if (tid == 0) *run_ctr = 2 * kWaves;  // runs 0 .. 2 kWaves - 1 are assigned statically (two per wave)
@@ -626,9 +751,9 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
 
     // Two type runs per wave are in flight at any time (P, Q).  The first two of every step are fixed - runs `wave` and
     // `wave + 16` of the chunk's run table, the same in all S steps - so their group range and bond type are resolved
-    // once per chunk, and their matrix rows for step s + 1 are requested during step s's atom phase, in front of the
-    // GEMMs: the vector-memory path, which bounds the message phase (~280 KB of matrix rows per chunk-step through one
-    // CU's L2 port), has nothing else to do there.  The step's update image travels the same way.
+    // once per chunk, and their matrix rows for step s + 1 are requested during step s's atom phase, in
+    // front of the GEMMs: the vector-memory path, which bounds the message phase (~280 KB of matrix rows per chunk-step
+    // through one CU's L2 port), has nothing else to do there.  The step's update image travels the same way.
     Run P, Q;
     int gP = 0, nP = 0, gQ = 0, nQ = 0;
     bool haveP = false, haveQ = false;
@@ -659,8 +784,222 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     // step 0: what later steps request during the previous atom phase is requested here (its update image is in LDS)
     if (kRunsEarly >= 1) fetch_P(0);
     if (kRunsEarly >= 2) fetch_Q(0);
+    // ---- atom phase: one 16-atom tile per wave (tile_of_wave above), for step s.  Stated once and instantiated twice:
+    // FIRST = step 0 of a table-fed chunk, outside the step loop - the rows' h quads and Reduce's record words are in `pre`
+    // (requested in front of the prologue barrier), so nothing is live around the loop's back edge for it, and the z / r
+    // accumulators start from G0 without a branch; otherwise a step of the loop.
+    auto atom_phase = [&](auto first_step, const int s) {
+      constexpr bool FIRST = decltype(first_step)::value;
+      const bool mstamp = !FIRST && stamp && c == c_begin && s == 1;
+      // (FIRST: lane and wave roles from opaque copies of the ids, so that nothing it derives from them is shared with - and
+      //  held in registers for - the instantiation inside the step loop)
+      int ln = lane, wv = wave;
+      if constexpr (FIRST) asm volatile("" : "+v"(ln), "+s"(wv));
+      const int lane = ln, wave = wv, a = ln & 15, q = ln >> 4;
+      const int my_tile = tile_of_wave(wave);
+      const bool has_tile = my_tile >= 0;
+      if (has_tile) {
+        const int tile = my_tile;
+        const int row = tile * 16 + a;
+        const int deg = FIRST ? pre.deg : (int)r_rowdeg[row];
+        const int maxdeg = __builtin_amdgcn_readfirstlane(FIRST ? pre.maxdeg : (int)r_tilemax[tile]);
+        // ---- gates z, r (models/layers.py:144-147) and candidate (:150-151): out^T = W^T [h | agg]^T.  z and r accumulate
+        // bias, then W_h h, then W_agg agg; the first half needs no message.  Mode 3 issues it HERE, in front of Reduce: the
+        // bf16 pipe co-executes with the vector ALU and the LDS, so Reduce's round trips pass under these 36 MFMAs - and with
+        // the h halves out of the way the gates' single-lane arithmetic below fits the registers (without this order it
+        // spills 8 bytes).  The order of every sum is unchanged.  (The exact-f32 MFMA shares the issue port with the
+        // vector ALU: nothing passes under it, and reads of h in front of Reduce alone cost time - DESIGN.md 4.1.)
+        // Step 0 of an ion whose image carries the gate table: h is atom_table[id] or zeros, so bias + W_h h is row
+        // min(id, Va) of G0 (clamped exactly where fill_h0 writes zeros) - four 16-byte loads from L2, requested here so
+        // that they pass under Reduce and land, in the accumulators themselves, where the agg half starts.  No bias
+        // read, no split of h, none of the h half's MFMAs; h itself is still read, for r * h and the blend.
+        // FIRST: h is in `pre` already - no read of the h buffer (nothing filled it) - and the gate table is taken for granted.
+        f32x4 h0, h1, z0, z1, r0, r1;
+        if constexpr (FIRST) h0 = pre.h0, h1 = pre.h1;
+        // (workgroup-uniform; evaluated where it is asked, from an opaque copy of the mask: as a value of the chunk the
+        //  compiler keeps it - and the table's address - in scalar registers over all steps, and the kernel has none left:
+        //  what it spills there costs vector registers)
+        auto gate_tab = [&]() -> bool {
+          if constexpr (!kUseG0 || kPeel) return false;  // (kPeel: every chunk with the gate bit takes FIRST)
+          unsigned tm = tabmask;
+          asm volatile("" : "+s"(tm));
+          return s == 0 && ((tm >> (2 + g)) & 1u);
+        };
+        auto load_gates = [&]() {
+          const int id = r_rowatom[row];
+          const unsigned col = (unsigned)id < (unsigned)p.Va ? (unsigned)id : (unsigned)p.Va;
+          // (the table's address is read here, through an opaque copy of the ion: held over the chunk it would cost the
+          //  scalar registers the kernel does not have)
+          int gg = g;
+          asm volatile("" : "+s"(gg));
+          // (a 32-bit byte offset beside the scalar base - the table is < 4 MiB / Vb: one address register, not two)
+          const unsigned boff = col * (unsigned)(kG0Row * sizeof(float)) + 16u * (unsigned)q;
+          const float* const gp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.g0[gg]) + boff);
+          z0 = ld4(gp), z1 = ld4(gp + 16);
+          r0 = ld4(gp + 32), r1 = ld4(gp + 48);
+        };
+        // (mode 3's A operands: block ((gate*2 + T)*2 + half) of the image, 3 x 512 bf16)
+        [[maybe_unused]] const __bf16* const wb = reinterpret_cast<const __bf16*>(wupd);
+        if constexpr (X3 && FIRST) {
+          load_gates();
+        } else if constexpr (X3) {
+          h0 = ld4(hbuf + row * HS + 4 * q);
+          h1 = ld4(hbuf + row * HS + 16 + 4 * q);
+          if (gate_tab())
+            load_gates();
+          else
+            gates_h_half<true>(wupd, wvec, lane, q, h0, h1, z0, z1, r0, r1);
+        }
+        // ---- Reduce: in-edge messages summed in edge-slot order, in the form the tile's largest in-degree (wave-uniform)
+        // asks for: one rank per round trip, two, or a loop of four per round.  agg starts at +0 in every form, and what
+        // the short forms leave out are adds of the slot of zeros (x + 0 = x for every x that a sum 0 + m can be, a first
+        // message of -0 included): the same bits as the loop's.
+        f32x4 agg0 = {0.f, 0.f, 0.f, 0.f}, agg1 = agg0;
+        auto jd_at = [&](int d0) -> uint2 {  // (FIRST: the words of d0 = 0 came with `pre`)
+          if constexpr (FIRST)
+            if (d0 == 0) return pre.jd;
+          return *reinterpret_cast<const uint2*>(r_jdptr + d0);
+        };
+        if (maxdeg <= 2) {
+          if (maxdeg == 1) reduce_ranks<1, X3>(msg, jd_at(0), 0, deg, row, q, zero_slot, agg0, agg1);
+          if (maxdeg == 2) reduce_ranks<2, X3>(msg, jd_at(0), 0, deg, row, q, zero_slot, agg0, agg1);
+        } else {
+          for (int d0 = 0; d0 < maxdeg; d0 += 4) reduce_ranks<4, X3>(msg, jd_at(d0), d0, deg, row, q, zero_slot, agg0, agg1);
+        }
+        if (mstamp && wave == 1 && lane == 0) stamp[8] = __builtin_amdgcn_s_memtime();
+        // (Mode 3, measured and dropped: a static priority for two of a SIMD's four waves, so that they run ahead and the
+        //  vector work of one pair overlaps the bf16 MFMAs of the other: +2 % kernel time - the waves that fall behind
+        //  then set the length of the phase.)
+        __builtin_amdgcn_s_setprio(1);
+        if (s + 1 < p.S) {  // in flight under the GEMMs (see above)
+          if (kPfWhere == 1) fetch_pf(s + 1);
+          if (kRunsEarly >= 1) fetch_P(s + 1);
+          if (kRunsEarly >= 2) fetch_Q(s + 1);
+        }
+        if constexpr (!X3 && FIRST) {
+          load_gates();
+        } else if constexpr (!X3) {
+          h0 = ld4(hbuf + row * HS + 4 * q);
+          h1 = ld4(hbuf + row * HS + 16 + 4 * q);
+          // (mode 2 asks for its table rows only here: in front of Reduce the sixteen registers they land in are not
+          //  free - the instantiation spilled 60 bytes - so their round trip is hidden by the SIMD's other waves alone)
+          if (gate_tab())
+            load_gates();
+          else
+            gates_h_half<false>(wupd, wvec, lane, q, h0, h1, z0, z1, r0, r1);
+        }
+        f32x4 t0 = ld4(wvec + 2 * kD + 4 * q), t1 = ld4(wvec + 2 * kD + 16 + 4 * q);
+        if constexpr (X3) {
+          // (Measured and dropped, DESIGN.md 4.1: the candidate's agg half in front of sigmoid(r), to run under the gate -
+          //  no spill in this order, but +0.7 us per launch, and the sums of t change their order.)
+          const B3 sa = split8x3(agg0, agg1);
+          mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 1) * 1536, wb + ((0 * 2 + 1) * 2 + 1) * 1536, lane, sa);
+          mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 1) * 1536, wb + ((1 * 2 + 1) * 2 + 1) * 1536, lane, sa);
+          // the gates in single-lane instructions (encoder_device.h): the scheduler interleaves them with the MFMAs
+          z0 = sigmoid4_lanes(z0);
+          z1 = sigmoid4_lanes(z1);
+          const f32x4 rh0 = mul4_lanes(sigmoid4_lanes(r0), h0);  // :149
+          const f32x4 rh1 = mul4_lanes(sigmoid4_lanes(r1), h1);
+          const B3 srh = split8x3(rh0, rh1);
+          mma9x2(t0, t1, wb + ((2 * 2 + 0) * 2 + 0) * 1536, wb + ((2 * 2 + 1) * 2 + 0) * 1536, lane, srh);
+          mma9x2(t0, t1, wb + ((2 * 2 + 0) * 2 + 1) * 1536, wb + ((2 * 2 + 1) * 2 + 1) * 1536, lane, sa);
+        } else {
+          // A operands: block ((gate*2 + T)*2 + half)*2 + u of the image, 16 B per lane, lane-linear (conflict-free)
+          const float* wl = wupd + 4 * lane;
+          // (the h half - the gate loop's half == 0 turns - ran above: gates_h_half, or the gate table)
+#pragma unroll
+          for (int u = 0; u < 2; ++u) {
+            const int hu = 2 + u;
+            const f32x4 Az0 = ld4(wl + ((0 * 2 + 0) * 4 + hu) * 256);
+            const f32x4 Az1 = ld4(wl + ((0 * 2 + 1) * 4 + hu) * 256);
+            const f32x4 Ar0 = ld4(wl + ((1 * 2 + 0) * 4 + hu) * 256);
+            const f32x4 Ar1 = ld4(wl + ((1 * 2 + 1) * 4 + hu) * 256);
+            const f32x4 Bv = u == 0 ? agg0 : agg1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              z0 = mfma4(Az0[r], Bv[r], z0);
+              z1 = mfma4(Az1[r], Bv[r], z1);
+              r0 = mfma4(Ar0[r], Bv[r], r0);
+              r1 = mfma4(Ar1[r], Bv[r], r1);
+            }
+          }
+          // (packed here: the f32 MFMA takes the vector ALU's issue slots, so what counts is the number of instructions -
+          //  the single-lane forms were measured in this loop too: +1.8 us per launch)
+          z0 = sigmoid4<false>(z0);
+          z1 = sigmoid4<false>(z1);
+          const f32x4 rh0 = sigmoid4<false>(r0) * h0;  // :149
+          const f32x4 rh1 = sigmoid4<false>(r1) * h1;
+#pragma unroll
+          for (int half = 0; half < 2; ++half) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const int hu = half * 2 + u;
+              const f32x4 Ah0 = ld4(wl + ((2 * 2 + 0) * 4 + hu) * 256);
+              const f32x4 Ah1 = ld4(wl + ((2 * 2 + 1) * 4 + hu) * 256);
+              const f32x4 Bv = half == 0 ? (u == 0 ? rh0 : rh1) : (u == 0 ? agg0 : agg1);
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                t0 = mfma4(Ah0[r], Bv[r], t0);
+                t1 = mfma4(Ah1[r], Bv[r], t1);
+              }
+            }
+          }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        if (kPfWhere == 2 && s + 1 < p.S) {
+          asm volatile("" ::: "memory");  // behind the GEMMs: their registers are free only now
+          fetch_pf(s + 1);
+        }
+        if (mstamp && wave == 1 && lane == 0) stamp[9] = __builtin_amdgcn_s_memtime();
+        // LayerNorm's gamma and beta are requested here, in front of the tanh: the GEMM operands are dead, so the
+        // registers are free, and the round trip passes under the blend and the two cross-lane sums instead of behind the
+        // v_rsq.  (sched_barrier: the scheduler otherwise sinks the four reads back down to their first use.)
+        const f32x4 gm0 = ld4(wvec + 3 * kD + 4 * q), gm1 = ld4(wvec + 3 * kD + 16 + 4 * q);
+        const f32x4 bt0 = ld4(wvec + 4 * kD + 4 * q), bt1 = ld4(wvec + 4 * kD + 16 + 4 * q);
+        __builtin_amdgcn_sched_barrier(0);
+        // ---- blend, LayerNorm, residual  (models/layers.py:153-155); (1-z) h + z t == h + z (t - h).
+        // (The four feature quads of an atom sit in lanes l, l ^ 16, l ^ 32, l ^ 48; has_tile is wave-uniform, so EXEC is
+        //  all ones here, which the lane swaps of sum_xor16_xor32 need.)
+        // Stated once, for a quad in packed instructions or - mode 3 - element by element in single-lane instructions
+        // (quad, keep1 above): a wave's epilogue runs beside the other three waves' bf16 MFMAs, and there the packed forms
+        // cost the SIMD more issue time than they save; beside the exact-f32 MFMA they are the faster ones.
+        const f32x4 th0 = X3 ? tanh4_lanes(t0) : tanh4<false>(t0), th1 = X3 ? tanh4_lanes(t1) : tanh4<false>(t1);
+        const auto blend = [](auto z, auto th, auto h) { return keep1(z * (th - h) + h); };
+        f32x4 n0 = quad<X3>(blend, z0, th0, h0), n1 = quad<X3>(blend, z1, th1, h1);
+        const f32x4 s4 = quad<X3>([](auto x, auto y) { return keep1(x + y); }, n0, n1);
+        const float sum = sum_xor16_xor32((s4[0] + s4[1]) + (s4[2] + s4[3]));
+        const float mean = sum * (1.0f / kD);
+        const auto center = [mean](auto n) { return keep1(n - mean); };
+        n0 = quad<X3>(center, n0);
+        n1 = quad<X3>(center, n1);
+        const f32x4 q4 = quad<X3>([](auto x, auto y) { return keep1(x * x + y * y); }, n0, n1);
+        const float var = sum_xor16_xor32((q4[0] + q4[1]) + (q4[2] + q4[3]));
+        const float inv = __builtin_amdgcn_rsqf(var * (1.0f / kD) + p.ln_eps);
+        const auto affine = [inv](auto n, auto gm, auto bt, auto h) { return keep1(n * keep1(gm * inv) + keep1(bt + h)); };
+        const f32x4 o0 = quad<X3>(affine, n0, gm0, bt0, h0), o1 = quad<X3>(affine, n1, gm1, bt1, h1);
+        st4(hbuf + row * HS + 4 * q, o0);
+        st4(hbuf + row * HS + 16 + 4 * q, o1);
+        if (mstamp && wave == 1 && lane == 0) stamp[10] = __builtin_amdgcn_s_memtime();
+      }
+      if (!has_tile && s + 1 < p.S) {  // waves without a tile in this chunk
+        if (kPfWhere != 0) fetch_pf(s + 1);
+        if (kRunsEarly >= 1) fetch_P(s + 1);
+        if (kRunsEarly >= 2) fetch_Q(s + 1);
+      }
+      if (mstamp && wave == 1 && lane == 0) stamp[11] = __builtin_amdgcn_s_memtime();
+    };
     if (stamp && c == c_begin && tid == 0) stamp[13] = __builtin_amdgcn_s_memtime();  // start of the first chunk's step 0
-    for (int s = 0; s < p.S; ++s) {
+    if (peel) {  // step 0 of a table-fed chunk: the atom phase alone, then the end-of-step barrier
+      __builtin_amdgcn_s_setprio(2);  // (as at the top of a step of the loop: Reduce ran at this priority in step 0 too)
+      atom_phase(std::true_type{}, 0);
+      lds_barrier();
+      if (two_rec) {  // the next chunk's record -> the idle buffer; published by the barrier behind the pool
+        store_record(recl == recl0 ? recl0 + rec_lds : recl0);
+        rec_in_lds = true;
+      }
+      if (stamp && c == c_begin && tid == 0) stamp[14] = __builtin_amdgcn_s_memtime();
+    }
+    for (int s = peel ? 1 : 0; s < p.S; ++s) {
       const float* tm_s = tmat_g + (size_t)s * p.Vb * kTMatFloats;
       // ---- message phase: m_e = A[type_e] h[src_e], one group of <= 4 edges of one bond type per 16 MFMAs.
       // v_mfma_f32_4x4x1_16b: 16 independent 4x4 blocks.  Block b < 8 accumulates, for feature quad b, the k < 16
@@ -803,197 +1142,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
       if (mstamp && tid == 0) stamp[12] = __builtin_amdgcn_s_memtime();
       if (stamp && tid == 0 && c == c_begin && s == 1) t_msg = __builtin_amdgcn_s_memtime();
 
-      // ---- atom phase: one 16-atom tile per wave.  Tile -> wave map as in encoder_fused.hip: waves w, w+4, w+8,
-      // w+12 share a SIMD; tiles are ordered heavy -> light, the SIMD groups with one tile fewer take the heaviest.
-      int my_tile = -1;
-      {
-        const int grp = wave & 3, slot = wave >> 2, q4 = ntiles >> 2, r4 = ntiles & 3;
-        const int heavy = (4 - r4) * q4;
-        if (grp >= r4) {
-          if (slot < q4) my_tile = slot * (4 - r4) + (grp - r4);
-        } else if (slot <= q4) {
-          my_tile = heavy + slot * r4 + grp;
-        }
-      }
-      const bool has_tile = my_tile >= 0 && my_tile < ntiles;
-      if (has_tile) {
-        const int tile = my_tile;
-        const int row = tile * 16 + a;
-        const int deg = r_rowdeg[row];
-        const int maxdeg = __builtin_amdgcn_readfirstlane(r_tilemax[tile]);
-        // ---- gates z, r (models/layers.py:144-147) and candidate (:150-151): out^T = W^T [h | agg]^T.  z and r accumulate
-        // bias, then W_h h, then W_agg agg; the first half needs no message.  Mode 3 issues it HERE, in front of Reduce: the
-        // bf16 pipe co-executes with the vector ALU and the LDS, so Reduce's round trips pass under these 36 MFMAs - and with
-        // the h halves out of the way the gates' single-lane arithmetic below fits the registers (without this order it
-        // spills 8 bytes).  The order of every sum is unchanged.  (The exact-f32 MFMA shares the issue port with the
-        // vector ALU: nothing passes under it, and reads of h in front of Reduce alone cost time - DESIGN.md 4.1.)
-        // Step 0 of an ion whose image carries the gate table: h is atom_table[id] or zeros, so bias + W_h h is row
-        // min(id, Va) of G0 (clamped exactly where fill_h0 writes zeros) - four 16-byte loads from L2, requested here so
-        // that they pass under Reduce and land, in the accumulators themselves, where the agg half starts.  No bias
-        // read, no split of h, none of the h half's MFMAs; h itself is still read, for r * h and the blend.
-        f32x4 h0, h1, z0, z1, r0, r1;
-        // (workgroup-uniform; evaluated where it is asked, from an opaque copy of the mask: as a value of the chunk the
-        //  compiler keeps it - and the table's address - in scalar registers over all steps, and the kernel has none left:
-        //  what it spills there costs vector registers)
-        auto gate_tab = [&]() -> bool {
-          if constexpr (!kUseG0) return false;
-          unsigned tm = tabmask;
-          asm volatile("" : "+s"(tm));
-          return s == 0 && ((tm >> (2 + g)) & 1u);
-        };
-        auto load_gates = [&]() {
-          const int id = r_rowatom[row];
-          const unsigned col = (unsigned)id < (unsigned)p.Va ? (unsigned)id : (unsigned)p.Va;
-          // (the table's address is read here, through an opaque copy of the ion: held over the chunk it would cost the
-          //  scalar registers the kernel does not have)
-          int gg = g;
-          asm volatile("" : "+s"(gg));
-          // (a 32-bit byte offset beside the scalar base - the table is < 4 MiB / Vb: one address register, not two)
-          const unsigned boff = col * (unsigned)(kG0Row * sizeof(float)) + 16u * (unsigned)q;
-          const float* const gp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(p.g0[gg]) + boff);
-          z0 = ld4(gp), z1 = ld4(gp + 16);
-          r0 = ld4(gp + 32), r1 = ld4(gp + 48);
-        };
-        // (mode 3's A operands: block ((gate*2 + T)*2 + half) of the image, 3 x 512 bf16)
-        [[maybe_unused]] const __bf16* const wb = reinterpret_cast<const __bf16*>(wupd);
-        if constexpr (X3) {
-          h0 = ld4(hbuf + row * HS + 4 * q);
-          h1 = ld4(hbuf + row * HS + 16 + 4 * q);
-          if (gate_tab())
-            load_gates();
-          else
-            gates_h_half<true>(wupd, wvec, lane, q, h0, h1, z0, z1, r0, r1);
-        }
-        // ---- Reduce: in-edge messages summed in edge-slot order, in the form the tile's largest in-degree (wave-uniform)
-        // asks for: one rank per round trip, two, or a loop of four per round.  agg starts at +0 in every form, and what
-        // the short forms leave out are adds of the slot of zeros (x + 0 = x for every x that a sum 0 + m can be, a first
-        // message of -0 included): the same bits as the loop's.
-        f32x4 agg0 = {0.f, 0.f, 0.f, 0.f}, agg1 = agg0;
-        if (maxdeg <= 2) {
-          if (maxdeg == 1) reduce_ranks<1, X3>(msg, r_jdptr, 0, deg, row, q, zero_slot, agg0, agg1);
-          if (maxdeg == 2) reduce_ranks<2, X3>(msg, r_jdptr, 0, deg, row, q, zero_slot, agg0, agg1);
-        } else {
-          for (int d0 = 0; d0 < maxdeg; d0 += 4) reduce_ranks<4, X3>(msg, r_jdptr, d0, deg, row, q, zero_slot, agg0, agg1);
-        }
-        if (mstamp && wave == 1 && lane == 0) stamp[8] = __builtin_amdgcn_s_memtime();
-        // (Mode 3, measured and dropped: a static priority for two of a SIMD's four waves, so that they run ahead and the
-        //  vector work of one pair overlaps the bf16 MFMAs of the other: +2 % kernel time - the waves that fall behind
-        //  then set the length of the phase.)
-        __builtin_amdgcn_s_setprio(1);
-        if (s + 1 < p.S) {  // in flight under the GEMMs (see above)
-          if (kPfWhere == 1) fetch_pf(s + 1);
-          if (kRunsEarly >= 1) fetch_P(s + 1);
-          if (kRunsEarly >= 2) fetch_Q(s + 1);
-        }
-        if constexpr (!X3) {
-          h0 = ld4(hbuf + row * HS + 4 * q);
-          h1 = ld4(hbuf + row * HS + 16 + 4 * q);
-          // (mode 2 asks for its table rows only here: in front of Reduce the sixteen registers they land in are not
-          //  free - the instantiation spilled 60 bytes - so their round trip is hidden by the SIMD's other waves alone)
-          if (gate_tab())
-            load_gates();
-          else
-            gates_h_half<false>(wupd, wvec, lane, q, h0, h1, z0, z1, r0, r1);
-        }
-        f32x4 t0 = ld4(wvec + 2 * kD + 4 * q), t1 = ld4(wvec + 2 * kD + 16 + 4 * q);
-        if constexpr (X3) {
-          // (Measured and dropped, DESIGN.md 4.1: the candidate's agg half in front of sigmoid(r), to run under the gate -
-          //  no spill in this order, but +0.7 us per launch, and the sums of t change their order.)
-          const B3 sa = split8x3(agg0, agg1);
-          mma9x2(z0, z1, wb + ((0 * 2 + 0) * 2 + 1) * 1536, wb + ((0 * 2 + 1) * 2 + 1) * 1536, lane, sa);
-          mma9x2(r0, r1, wb + ((1 * 2 + 0) * 2 + 1) * 1536, wb + ((1 * 2 + 1) * 2 + 1) * 1536, lane, sa);
-          // the gates in single-lane instructions (encoder_device.h): the scheduler interleaves them with the MFMAs
-          z0 = sigmoid4_lanes(z0);
-          z1 = sigmoid4_lanes(z1);
-          const f32x4 rh0 = mul4_lanes(sigmoid4_lanes(r0), h0);  // :149
-          const f32x4 rh1 = mul4_lanes(sigmoid4_lanes(r1), h1);
-          const B3 srh = split8x3(rh0, rh1);
-          mma9x2(t0, t1, wb + ((2 * 2 + 0) * 2 + 0) * 1536, wb + ((2 * 2 + 1) * 2 + 0) * 1536, lane, srh);
-          mma9x2(t0, t1, wb + ((2 * 2 + 0) * 2 + 1) * 1536, wb + ((2 * 2 + 1) * 2 + 1) * 1536, lane, sa);
-        } else {
-          // A operands: block ((gate*2 + T)*2 + half)*2 + u of the image, 16 B per lane, lane-linear (conflict-free)
-          const float* wl = wupd + 4 * lane;
-          // (the h half - the gate loop's half == 0 turns - ran above: gates_h_half, or the gate table)
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int hu = 2 + u;
-            const f32x4 Az0 = ld4(wl + ((0 * 2 + 0) * 4 + hu) * 256);
-            const f32x4 Az1 = ld4(wl + ((0 * 2 + 1) * 4 + hu) * 256);
-            const f32x4 Ar0 = ld4(wl + ((1 * 2 + 0) * 4 + hu) * 256);
-            const f32x4 Ar1 = ld4(wl + ((1 * 2 + 1) * 4 + hu) * 256);
-            const f32x4 Bv = u == 0 ? agg0 : agg1;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              z0 = mfma4(Az0[r], Bv[r], z0);
-              z1 = mfma4(Az1[r], Bv[r], z1);
-              r0 = mfma4(Ar0[r], Bv[r], r0);
-              r1 = mfma4(Ar1[r], Bv[r], r1);
-            }
-          }
-          // (packed here: the f32 MFMA takes the vector ALU's issue slots, so what counts is the number of instructions -
-          //  the single-lane forms were measured in this loop too: +1.8 us per launch)
-          z0 = sigmoid4<false>(z0);
-          z1 = sigmoid4<false>(z1);
-          const f32x4 rh0 = sigmoid4<false>(r0) * h0;  // :149
-          const f32x4 rh1 = sigmoid4<false>(r1) * h1;
-#pragma unroll
-          for (int half = 0; half < 2; ++half) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              const int hu = half * 2 + u;
-              const f32x4 Ah0 = ld4(wl + ((2 * 2 + 0) * 4 + hu) * 256);
-              const f32x4 Ah1 = ld4(wl + ((2 * 2 + 1) * 4 + hu) * 256);
-              const f32x4 Bv = half == 0 ? (u == 0 ? rh0 : rh1) : (u == 0 ? agg0 : agg1);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                t0 = mfma4(Ah0[r], Bv[r], t0);
-                t1 = mfma4(Ah1[r], Bv[r], t1);
-              }
-            }
-          }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        if (kPfWhere == 2 && s + 1 < p.S) {
-          asm volatile("" ::: "memory");  // behind the GEMMs: their registers are free only now
-          fetch_pf(s + 1);
-        }
-        if (mstamp && wave == 1 && lane == 0) stamp[9] = __builtin_amdgcn_s_memtime();
-        // LayerNorm's gamma and beta are requested here, in front of the tanh: the GEMM operands are dead, so the
-        // registers are free, and the round trip passes under the blend and the two cross-lane sums instead of behind the
-        // v_rsq.  (sched_barrier: the scheduler otherwise sinks the four reads back down to their first use.)
-        const f32x4 gm0 = ld4(wvec + 3 * kD + 4 * q), gm1 = ld4(wvec + 3 * kD + 16 + 4 * q);
-        const f32x4 bt0 = ld4(wvec + 4 * kD + 4 * q), bt1 = ld4(wvec + 4 * kD + 16 + 4 * q);
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- blend, LayerNorm, residual  (models/layers.py:153-155); (1-z) h + z t == h + z (t - h).
-        // (The four feature quads of an atom sit in lanes l, l ^ 16, l ^ 32, l ^ 48; has_tile is wave-uniform, so EXEC is
-        //  all ones here, which the lane swaps of sum_xor16_xor32 need.)
-        // Stated once, for a quad in packed instructions or - mode 3 - element by element in single-lane instructions
-        // (quad, keep1 above): a wave's epilogue runs beside the other three waves' bf16 MFMAs, and there the packed forms
-        // cost the SIMD more issue time than they save; beside the exact-f32 MFMA they are the faster ones.
-        const f32x4 th0 = X3 ? tanh4_lanes(t0) : tanh4<false>(t0), th1 = X3 ? tanh4_lanes(t1) : tanh4<false>(t1);
-        const auto blend = [](auto z, auto th, auto h) { return keep1(z * (th - h) + h); };
-        f32x4 n0 = quad<X3>(blend, z0, th0, h0), n1 = quad<X3>(blend, z1, th1, h1);
-        const f32x4 s4 = quad<X3>([](auto x, auto y) { return keep1(x + y); }, n0, n1);
-        const float sum = sum_xor16_xor32((s4[0] + s4[1]) + (s4[2] + s4[3]));
-        const float mean = sum * (1.0f / kD);
-        const auto center = [mean](auto n) { return keep1(n - mean); };
-        n0 = quad<X3>(center, n0);
-        n1 = quad<X3>(center, n1);
-        const f32x4 q4 = quad<X3>([](auto x, auto y) { return keep1(x * x + y * y); }, n0, n1);
-        const float var = sum_xor16_xor32((q4[0] + q4[1]) + (q4[2] + q4[3]));
-        const float inv = __builtin_amdgcn_rsqf(var * (1.0f / kD) + p.ln_eps);
-        const auto affine = [inv](auto n, auto gm, auto bt, auto h) { return keep1(n * keep1(gm * inv) + keep1(bt + h)); };
-        const f32x4 o0 = quad<X3>(affine, n0, gm0, bt0, h0), o1 = quad<X3>(affine, n1, gm1, bt1, h1);
-        st4(hbuf + row * HS + 4 * q, o0);
-        st4(hbuf + row * HS + 16 + 4 * q, o1);
-        if (mstamp && wave == 1 && lane == 0) stamp[10] = __builtin_amdgcn_s_memtime();
-      }
-      if (!has_tile && s + 1 < p.S) {  // waves without a tile in this chunk
-        if (kPfWhere != 0) fetch_pf(s + 1);
-        if (kRunsEarly >= 1) fetch_P(s + 1);
-        if (kRunsEarly >= 2) fetch_Q(s + 1);
-      }
-      if (mstamp && wave == 1 && lane == 0) stamp[11] = __builtin_amdgcn_s_memtime();
+      atom_phase(std::false_type{}, s);
       // End-of-step barrier: every row of h is updated, every read of the message buffer and of the update image is
       // done.  (LDS traffic only: the run prefetch above stays in flight across it.)
       lds_barrier();
@@ -1016,6 +1165,7 @@ __global__ __launch_bounds__(kThreads, kThreads / 256) void encoder_typed_kernel
     if (c + 1 < c_end) fetch_step0(dsc_next, c + 1);
     pool(M, m0, g);
     lds_barrier();  // the record / h buffers are rewritten by the next chunk's prologue
+    if (two_rec) use_record(recl == recl0 ? recl0 + rec_lds : recl0);
     if (stamp && tid == 0) {
       const unsigned long long t = __builtin_amdgcn_s_memtime();
       t_pool += t - t_mark;

@@ -21,6 +21,8 @@ ap.add_argument("--rounds", type=int, default=12)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--mode", default="f16x2")
+ap.add_argument("--plain", action="store_true",
+                help="canonical weights through impnn_encoder_fused: plain images, rebuilt per call (no step-0 table)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -52,7 +54,7 @@ prep = {}
 
 
 def call(lib):
-    if hasattr(lib, "impnn_encoder_fused_prepared"):
+    if not args.plain and hasattr(lib, "impnn_encoder_fused_prepared"):
         if id(lib) not in prep:
             # a library that exports the with-atoms prepare gets the image MPNNModel keeps: with the step-0 message table
             # (and one that exports the with-gates prepare: the step-0 gate table behind it as well)
