@@ -291,6 +291,15 @@ int impnn_encoder_workspace_bytes(int32_t n_ions, int32_t B, int32_t N, int32_t 
  * not part of the ABI's promises beyond this query. */
 int impnn_encoder_plan_layout(int32_t n_ions, int32_t B, int32_t N, int32_t E, int32_t D, int32_t K,
                               int32_t S, int32_t Vb, int32_t mode, int32_t workgroups, int64_t out[8]);
+/* Where the chunk records of such a call lie (typed modes 2 and 3 only; pull-form modes: IMPNN_E_UNSUPPORTED).  Same
+ * arguments and refusals as impnn_encoder_plan_layout otherwise; launches nothing.
+ *   out = { rec_off, rec_stride, grp_off, runs_off, nrun_off }
+ * rec_off: byte offset of the records in the workspace, record (j, sl) of desc [nwg][max_sub] at rec_off +
+ * (j * max_sub + sl) * rec_stride; inside a record: grp_off, the group table (16 bytes per group, the first word = bond
+ * type | edges << 8), in run order; runs_off, the run table (u16: first group of every run, then the group count),
+ * ordered by run length descending, then type, then piece; nrun_off, the run count (u16).  For tests and diagnostics. */
+int impnn_encoder_plan_records(int32_t n_ions, int32_t B, int32_t N, int32_t E, int32_t D, int32_t K,
+                               int32_t S, int32_t Vb, int32_t mode, int32_t workgroups, int64_t out[5]);
 int impnn_encoder_fused(int32_t n_ions, const int32_t* const* atom_ids,
                         const int32_t* const* bond_ids, const int32_t* const* conn,
                         const float* atom_table, int32_t Va, const float* bond_table, int32_t Vb,

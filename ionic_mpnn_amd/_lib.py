@@ -45,6 +45,7 @@ SIGNATURES = {
     "impnn_encoder_plan_overflow_offset": (sz, []),
     "impnn_encoder_workspace_bytes": (C.c_int, [i32] * 10 + [C.POINTER(sz)]),
     "impnn_encoder_plan_layout": (C.c_int, [i32] * 10 + [C.POINTER(i64)]),
+    "impnn_encoder_plan_records": (C.c_int, [i32] * 10 + [C.POINTER(i64)]),
     "impnn_encoder_fused": (C.c_int, [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, i32, vp, i32,
                                       C.POINTER(vp), i32, C.POINTER(vp), i32, i32, i32, i32, i32, i32, f32, i32, vp,
                                       sz, vp]),

@@ -387,6 +387,26 @@ int impnn_encoder_plan_layout(int32_t n_ions, int32_t B, int32_t N, int32_t E, i
   return IMPNN_OK;
 }
 
+// Where the chunk records of such a call lie (typed modes, atom_dim 32).  Host arithmetic only.
+int impnn_encoder_plan_records(int32_t n_ions, int32_t B, int32_t N, int32_t E, int32_t D, int32_t K, int32_t S,
+                               int32_t Vb, int32_t mode, int32_t workgroups, int64_t out[5]) {
+  REQUIRE(out, "null pointer");
+  size_t total = 0;
+  if (int rc = impnn_encoder_workspace_bytes(n_ions, B, N, E, D, K, S, Vb, mode, workgroups, &total)) return rc;
+  if (D != enc::kD)
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_plan_records: atom_dim %d has no chunk plan (atom_dim 32 only)", D);
+  if (mode < 2)
+    return fail(IMPNN_E_UNSUPPORTED, "encoder_plan_records: mode %d has pull-form records (typed modes only)", mode);
+  const int nwg = encoder_workgroups(n_ions, B, workgroups, N, E, mode);
+  const enc::Ws w = enc::ws_layout(n_ions, B, N, E, S, Vb, nwg, true, mode == 3);
+  out[0] = (int64_t)w.rec_off;
+  out[1] = w.rec_bytes;
+  out[2] = enc::kTRecGrp;
+  out[3] = enc::trec_runs_off(Vb, enc::tecap_of(E));
+  out[4] = enc::kTRecNrun;
+  return IMPNN_OK;
+}
+
 static int encoder_common(const char* fn, int32_t n_ions, const int32_t* const* atom_ids,
                           const int32_t* const* bond_ids, const int32_t* const* conn, const float* atom_table,
                           int32_t Va, const float* bond_table, int32_t Vb, const float* const* weights,

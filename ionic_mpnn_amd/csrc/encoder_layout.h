@@ -85,9 +85,10 @@ constexpr int kTRecRowatom = 2096;   // i32[kRCap]
 constexpr int kTRecCounts = 3120;    // u16 groups, u16 edges, u16 max in-degree
 constexpr int kTRecJdptr = 3136;     // u16[258]      : first message slot of in-edge index d
 constexpr int kTRecNrun = 3664;      // u16           : type runs (bond types present in the chunk)
-constexpr int kTRecGrp = 3712;       // uint4[tgrp_cap(Vb)]: x = type | edges << 8 | groups of the type from here on << 24,
+constexpr int kTRecGrp = 3712;       // uint4[tgrp_cap(Vb)]: x = type | edges << 8 (bits 24-31 are zero: nothing reads them),
                                      //   y = 4 x u8 placed source row, z/w = 4 x u16 message key (tmsg_key of the edge's
-                                     //   slot; the dump slot for unused lanes); in type order
+                                     //   slot; the dump slot for unused lanes); in RUN order: run i of the run table covers
+                                     //   groups [runs[i], runs[i + 1]), and the runs lie longest first
 // A chunk holds <= ecap edges of <= Vb types: at most ecap/4 full groups plus one partial group per type.  The run
 // table (u16: first group of every run, + end) follows the group table, so a record's used bytes - and the LDS the
 // encoder spends on it - depend on the bond vocabulary: 7.2 KB at Vb = 72, 12 KB at Vb = 256.
@@ -95,6 +96,9 @@ constexpr int kTRecGrp = 3712;       // uint4[tgrp_cap(Vb)]: x = type | edges <<
 // pieces of <= gmax = max(2, ceil(groups of the chunk / kTRunTarget)) groups, so that a chunk of FEW bond types - real
 // molecules have a handful - still gives every wave its share (uncut, a chunk of 6 types kept 6 of 16 waves busy:
 // 2.46 M pairs/s at the explicit-hydrogen shape against 3.79 M with 71 uniformly drawn types).  Runs <= types + kTRunTarget.
+// The table is ordered by run length descending, then type, then piece: a wave's two fixed runs are among the 32 longest
+// and the counter deals the short ones last, so the phase does not end on a long run drawn late.  A type with more than
+// gmax groups therefore has its full pieces in one place of the group table and its remainder in another.
 constexpr int kTRunTarget = 32;
 __host__ __device__ constexpr int tgrp_cap(int Vb, int ecap) { return ecap / 4 + (Vb < kTVbMax ? Vb : kTVbMax); }
 __host__ __device__ constexpr int trec_runs_off(int Vb, int ecap) { return kTRecGrp + 16 * tgrp_cap(Vb, ecap); }

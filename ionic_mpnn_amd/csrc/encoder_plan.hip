@@ -794,13 +794,29 @@ __global__ __launch_bounds__(kRCap, 5) void plan_chunks_kernel(PlanParams p) {  
 //       ticket list (<= kTick entries; rows with more take the slow path of P4) - and the type histogram
 //   P2  in-degree histogram of the rows
 //   P3  wave 0: rows placed before every in-degree bin (prefix over the histogram) and the jagged-diagonal pointers
-//       (prefix over the suffix counts); wave 1: groups per type, first group of every type, the run table
+//       (prefix over the suffix counts); wave 1: groups per type, the run table longest run first, where every type's
+//       groups lie in it (tgb_pack)
 //   P4  rows take their place; per-row tables of the record; the type's groups with their headers
 //   P5  per valid edge: its rank among the in-edges of its row in edge-slot order = the tickets with a smaller slot
 //       number -> message slot; a place in a group of its type; its word in the slot-ordered source list
 //   P6  group table -> record
 // Dynamic LDS: the group table (16 B x tgrp_cap).
 constexpr int kTick = 16;
+// IMPNN_T_RUNLPT  the run table in order of non-increasing run length (0: in type order, as it was - DESIGN.md 4.1)
+#ifndef IMPNN_T_RUNLPT
+#define IMPNN_T_RUNLPT 1
+#endif
+constexpr bool kRunLpt = IMPNN_T_RUNLPT != 0;
+// Where the groups of a type lie in the group table: its full pieces (the first `full_groups` groups of the type) from
+// `full_base` on, the remainder from `rem_base` on - 9 bits each.
+static_assert(tgrp_cap(kTVbMax, kTECapBig) < 512, "group indices travel as 9 bits");
+__device__ __forceinline__ int tgb_pack(int full_base, int full_groups, int rem_base) {
+  return full_base | (full_groups << 9) | (rem_base << 18);
+}
+__device__ __forceinline__ int tgb_group(int w, int jg) {  // the type's jg-th group
+  const int nfg = (w >> 9) & 511;
+  return jg < nfg ? (w & 511) + jg : (w >> 18) + jg - nfg;
+}
 __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams p) {  // <= 128 VGPRs: 4 workgroups per CU
   __shared__ int32_t moloff[kRCap + 2], molrows[kRCap], cnt[kRCap + 64], place[kRCap];  // cnt, thist: + a spare word per lane
   __shared__ int32_t idl[kRCap];  // atom id of the logical row (-1: a slack row)
@@ -1031,28 +1047,87 @@ __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams 
     const int s4 = ng.x + ng.y + ng.z + ng.w;
     const int incl = wave_incl_scan(s4);
     const int ex = incl - s4;
-    reinterpret_cast<int4*>(tgb)[lane] = make_int4(ex, ex + ng.x, ex + ng.x + ng.y, ex + ng.x + ng.y + ng.z);
-    // run table: the groups of every type that has groups, in type order, cut into runs of <= gmax groups (+ end;
-    // encoder_layout.h).  The encoder's waves take runs from it one at a time (an LDS counter), so the message phase is
-    // balanced dynamically - given enough runs.
+    // run table: the groups of every type that has groups, cut into runs of <= gmax groups (+ end; encoder_layout.h).
+    // The encoder's waves take runs from it one at a time (an LDS counter), so the message phase is balanced
+    // dynamically - given enough runs.
     const int ngrp_all = __builtin_amdgcn_readlane(incl, 63);
     int gmax = (ngrp_all + kTRunTarget - 1) / kTRunTarget;
     gmax = gmax < 2 ? 2 : gmax;
     const float rgm = 1.0f / (float)gmax;
-    const int4 nr = make_int4(fast_div(ng.x + gmax - 1, gmax, rgm), fast_div(ng.y + gmax - 1, gmax, rgm),
-                              fast_div(ng.z + gmax - 1, gmax, rgm), fast_div(ng.w + gmax - 1, gmax, rgm));
-    const int r4 = nr.x + nr.y + nr.z + nr.w;
-    const int rincl = wave_incl_scan(r4);
-    int ri = rincl - r4;
     uint16_t* runs = reinterpret_cast<uint16_t*>(rec + trec_runs_off(p.Vb, p.ecap));
-    for (int i = 0; i < nr.x; ++i) runs[ri++] = (uint16_t)(ex + i * gmax);
-    for (int i = 0; i < nr.y; ++i) runs[ri++] = (uint16_t)(ex + ng.x + i * gmax);
-    for (int i = 0; i < nr.z; ++i) runs[ri++] = (uint16_t)(ex + ng.x + ng.y + i * gmax);
-    for (int i = 0; i < nr.w; ++i) runs[ri++] = (uint16_t)(ex + ng.x + ng.y + ng.z + i * gmax);
-    if (lane == 63) {
-      runs[rincl] = (uint16_t)incl;
-      *reinterpret_cast<uint16_t*>(rec + kTRecNrun) = (uint16_t)rincl;
-      misc[0] = incl;
+    if (kRunLpt) {
+      // Longest run first (length descending, then type, then piece): the counter then deals the one-group runs last,
+      // so that no wave draws a long run when the others are done.  A type's full pieces (gmax groups each) come first:
+      // full run k of the chunk starts at group k * gmax.  The remainders (1 .. gmax - 1 groups, at most one per type)
+      // follow, by a counting sort over their lengths: a ballot per length and held type gives the types of that length
+      // in type order.  The group table lies in run order, so a type has TWO bases, tgb_pack.
+      const int ngv[4] = {ng.x, ng.y, ng.z, ng.w};
+      int nf[4], rem[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        nf[i] = fast_div(ngv[i], gmax, rgm);
+        rem[i] = ngv[i] - nf[i] * gmax;
+      }
+      const int f4 = nf[0] + nf[1] + nf[2] + nf[3];
+      const int fincl = wave_incl_scan(f4);
+      static_assert(kTRunTarget <= 64, "one lane per full run");
+      const int nfull = __builtin_amdgcn_readlane(fincl, 63);  // <= groups / gmax <= kTRunTarget
+      const int run_cap = p.Vb + kTRunTarget;                  // (runs <= types + kTRunTarget: the table holds them and the end)
+      if (lane < nfull && lane < run_cap) runs[lane] = (uint16_t)(lane * gmax);
+      int rb[4] = {0, 0, 0, 0};
+      int nrun = nfull, gnext = nfull * gmax;
+      const unsigned long long below = (1ull << lane) - 1ull;
+      for (int len = gmax - 1; len >= 1; --len) {
+        int before = 0, all = 0;  // types of this length in lower lanes; in the wave
+        unsigned long long b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          b[i] = __ballot(rem[i] == len);
+          before += (int)__builtin_popcountll(b[i] & below);
+          all += (int)__builtin_popcountll(b[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (rem[i] == len) {
+            rb[i] = gnext + before * len;
+            if (nrun + before < run_cap) runs[nrun + before] = (uint16_t)rb[i];
+            ++before;
+          }
+        }
+        nrun += all;
+        gnext += all * len;
+      }
+      int fb = (fincl - f4) * gmax, packed[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        packed[i] = tgb_pack(fb, nf[i] * gmax, rb[i]);
+        fb += nf[i] * gmax;
+      }
+      reinterpret_cast<int4*>(tgb)[lane] = make_int4(packed[0], packed[1], packed[2], packed[3]);
+      if (lane == 63) {
+        runs[nrun < run_cap ? nrun : run_cap] = (uint16_t)incl;
+        *reinterpret_cast<uint16_t*>(rec + kTRecNrun) = (uint16_t)nrun;
+        misc[0] = incl;
+      }
+    } else {
+      // type order: every group of a type in one block (both bases of tgb_pack are the same)
+      const int exv[4] = {ex, ex + ng.x, ex + ng.x + ng.y, ex + ng.x + ng.y + ng.z};
+      reinterpret_cast<int4*>(tgb)[lane] = make_int4(tgb_pack(exv[0], 0, exv[0]), tgb_pack(exv[1], 0, exv[1]),
+                                                     tgb_pack(exv[2], 0, exv[2]), tgb_pack(exv[3], 0, exv[3]));
+      const int4 nr = make_int4(fast_div(ng.x + gmax - 1, gmax, rgm), fast_div(ng.y + gmax - 1, gmax, rgm),
+                                fast_div(ng.z + gmax - 1, gmax, rgm), fast_div(ng.w + gmax - 1, gmax, rgm));
+      const int r4 = nr.x + nr.y + nr.z + nr.w;
+      const int rincl = wave_incl_scan(r4);
+      int ri = rincl - r4;
+      for (int i = 0; i < nr.x; ++i) runs[ri++] = (uint16_t)(ex + i * gmax);
+      for (int i = 0; i < nr.y; ++i) runs[ri++] = (uint16_t)(ex + ng.x + i * gmax);
+      for (int i = 0; i < nr.z; ++i) runs[ri++] = (uint16_t)(ex + ng.x + ng.y + i * gmax);
+      for (int i = 0; i < nr.w; ++i) runs[ri++] = (uint16_t)(ex + ng.x + ng.y + ng.z + i * gmax);
+      if (lane == 63) {
+        runs[rincl] = (uint16_t)incl;
+        *reinterpret_cast<uint16_t*>(rec + kTRecNrun) = (uint16_t)rincl;
+        misc[0] = incl;
+      }
     }
   }
   lds_barrier();
@@ -1081,14 +1156,15 @@ __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams 
       reinterpret_cast<int4*>(p.desc)[idx] = make_int4(m0, M, jdp[kRCap] < p.ecap ? jdp[kRCap] : p.ecap, R | (g << 16));
   }
   {
-    // the groups of type `tid`: x = type | edges << 8 | groups of this type from this one on << 24; unused edge lanes
-    // write to the dump slot
+    // the groups of type `tid`: x = type | edges << 8 (| groups of this type from this one on << 24 in type order, where
+    // they follow each other); unused edge lanes write to the dump slot
     const int n_t = thist[tid];
     const int ng = (n_t + 3) >> 2, gb = tgb[tid];
     const uint32_t dump = (uint32_t)tmsg_key(p.ecap) * 0x10001u;
     for (int jg = 0; jg < ng; ++jg) {
       const int c = n_t - 4 * jg;
-      grp[gb + jg] = make_uint4((uint32_t)tid | ((uint32_t)(c < 4 ? c : 4) << 8) | ((uint32_t)(ng - jg) << 24), 0u, dump, dump);
+      grp[tgb_group(gb, jg)] = make_uint4((uint32_t)tid | ((uint32_t)(c < 4 ? c : 4) << 8) |
+                                              (kRunLpt ? 0u : (uint32_t)(ng - jg) << 24), 0u, dump, dump);
     }
   }
   lds_barrier();
@@ -1150,7 +1226,7 @@ __global__ __launch_bounds__(kRCap, 4) void plan_chunks_typed_kernel(PlanParams 
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         if (ok[k]) {
-          unsigned char* ge = reinterpret_cast<unsigned char*>(&grp[gb[k] + (ix[k] >> 2)]);
+          unsigned char* ge = reinterpret_cast<unsigned char*>(&grp[tgb_group(gb[k], ix[k] >> 2)]);
           ge[4 + (ix[k] & 3)] = (unsigned char)srow[k];
           reinterpret_cast<uint16_t*>(ge + 8)[ix[k] & 3] = (uint16_t)tmsg_key(rank[k] + row[k]);
           // the same edge in the slot-ordered source list: its type and the atom id of its source row

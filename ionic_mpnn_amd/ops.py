@@ -489,6 +489,37 @@ def read_plan(ws, layout, n_ions, B):
     return Plan(rows, vr, nsub, desc, ion)
 
 
+PlanRecords = collections.namedtuple("PlanRecords", "rec_off rec_stride grp_off runs_off nrun_off")
+ChunkTables = collections.namedtuple("ChunkTables", "nrun runs grp_type grp_edges grp")
+
+
+def encoder_plan_records(n_ions, B, N, E, D, K, S, Vb, mode="f32t", workgroups=0):
+    """Where the chunk records of such a call lie in its workspace (impnn_encoder_plan_records; typed modes, atom_dim 32):
+    byte offset and stride of the records, and inside a record the offsets of the group table, the run table and the run
+    count.  No device call."""
+    out = (C.c_int64 * 5)()
+    lib = _lib.load()
+    rc = lib.impnn_encoder_plan_records(n_ions, B, N, E, D, K, S, Vb, ENCODER_MODES[mode], int(workgroups), out)
+    if rc == _lib.IMPNN_E_UNSUPPORTED:
+        raise EncoderUnsupported(lib.impnn_last_error_string().decode())
+    check(rc)
+    return PlanRecords(*[int(v) for v in out])
+
+
+def read_plan_records(ws, layout, chunk):
+    """Copies the run and group tables of one chunk out of a finished plan's workspace `ws` (a uint8 tensor; the caller
+    has waited for the plan).  `layout`: encoder_plan_records(...) of the call; `chunk`: the record's index, j * max_sub
+    + sl for chunk sl of workgroup j.  -> nrun; runs [nrun + 1] (first group of every run, then the group count);
+    per group its bond type and edge count; grp [groups][4], the groups' four words."""
+    off = layout.rec_off + int(chunk) * layout.rec_stride
+    rec = ws[off:off + layout.rec_stride].cpu().numpy().copy()
+    nrun = int(rec[layout.nrun_off:layout.nrun_off + 2].view("<u2")[0])
+    runs = rec[layout.runs_off:layout.runs_off + 2 * (nrun + 1)].view("<u2").astype("int64")
+    ngrp = int(runs[nrun])
+    grp = rec[layout.grp_off:layout.grp_off + 16 * ngrp].view("<u4").reshape(ngrp, 4)
+    return ChunkTables(nrun, runs, (grp[:, 0] & 0xff).astype("int64"), ((grp[:, 0] >> 8) & 0xff).astype("int64"), grp)
+
+
 class EncoderUnsupported(RuntimeError):
     pass
 

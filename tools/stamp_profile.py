@@ -61,9 +61,10 @@ if mode in ("f32t", "f32x3"):
     mid = (st[:, 12] - t0)[ok]
     end = (st[:, 15] - t0)[ok]
     srt = np.sort(arr, axis=1)
+    # (the mean of the sixteen finish times is what the phase could reach with its work dealt evenly; the last is what it takes)
     print(f"step 1 of the first chunk ({ok.sum()} workgroups): duration {end.mean():.0f}; message phase: waves done at "
-          f"min {srt[:, 0].mean():.0f} / median {srt[:, 8].mean():.0f} / last {srt[:, 15].mean():.0f}, barrier released "
-          f"{mid.mean():.0f}; atom phase + end barrier {(end - mid).mean():.0f}")
+          f"min {srt[:, 0].mean():.0f} / median {srt[:, 8].mean():.0f} / mean {arr.mean():.0f} / last {srt[:, 15].mean():.0f}, "
+          f"barrier released {mid.mean():.0f}; atom phase + end barrier {(end - mid).mean():.0f}")
     # step 0 of the first chunk: stamp 13 marks its start where the library writes it (0 in older builds); for any build,
     # with S = 3, the mean chunk's steps less two steps 1 estimate it.  With a step-0 message table in the image
     # (MPNNModel._prepared_weights builds one) step 0 has no message phase: its gather runs in the chunk prologue, so
