@@ -970,6 +970,41 @@ int impnn_domain_grid_mask(const float* mix_cat, const float* mix_an, const floa
 int impnn_domain_rows(const float* z, const float* ref, int32_t exclude_self, float* distance, int32_t* nearest,
                       int32_t Q, int32_t R, int32_t Mx, impnn_stream_t stream);
 
+/* ---- a diverse batch: k pairs of the grid that lie far from the reference set and from each other, by farthest-point
+ *      (k-center greedy) selection in the latent space of the domain entries above.
+ *      Distance.  z(i,j) = mix_cat[i] + mix_an[j] in float32, the cation term first.  dist(z, r) is the float32 distance
+ *      of the domain entries: d2 = 0; for k ascending: diff = z[k] - r[k]; d2 = fmaf(diff, diff, d2); then the correctly
+ *      rounded sqrt.  No dot-product expansion, no matrix-core product.
+ *      State.  D_0(i,j) is the value impnn_domain_grid writes for ref (R >= 1 rows).
+ *      Step, for t = 0 .. k-1:
+ *        the candidates are the pairs whose `where` bit is set (where == NULL: all pairs; the pair mask format above,
+ *        (C,W) words) and whose D_t > 0: a NaN distance is no candidate, and a pair at distance exactly 0 coincides with
+ *        a known or chosen pair and is no candidate either;
+ *        the pick p_t is the candidate with the largest float32 D_t, the lowest pair index i * A + j among equal D_t;
+ *        D_{t+1} = min(D_t, dist(z, z(p_t))): the value impnn_domain_grid would write against ref plus the rows z(p_0)
+ *        .. z(p_t).  The chosen pair's own new distance is exactly 0, so it cannot be picked twice;
+ *        with no candidate left the selection ends with n = t < k picks.
+ *      Result.  cation[k], anion[k] int32 and distance[k] float32 - each pick's D_t when it was chosen, non-increasing -
+ *      with -1 / -1 / NaN in the slots from n on; counts[2] int64: counts[0] = n, counts[1] = the number of candidates
+ *      at t = 0.
+ *      The order is defined on float32 values because near-ties are the rule on a product grid (z(i,j) - z(i,j') and
+ *      z(i',j) - z(i',j') differ by rounding only); the picks do not depend on the schedule: a pick is the maximum of
+ *      a 64-bit key (distance bits high, complemented pair index low) by integer atomics.
+ *      workspace: impnn_diverse_workspace_bytes(C, A, k) bytes, 16-byte aligned - the (C,A) float32 state, one flag per
+ *      tile of 16 x 64 pairs and 4 KiB of records per pick; its content after the call is unspecified.  One launch writes the
+ *      state, k - 1 launches of 8 bytes of state traffic per pair follow, each reads its predecessor's pick from the
+ *      records; the host does not wait in between.
+ *      Limits: 1 <= Mx <= 64, 1 <= k <= impnn_diverse_max_k() (4096: a launch per pick), C * A < 2^32.
+ *      Checks in order: shape (sizes >= 0, Mx >= 1, R >= 1) and k < 1 (IMPNN_E_BADARG); Mx <= 64, k and C * A within the
+ *      limits (IMPNN_E_UNSUPPORTED); zero work (C == 0 or A == 0: IMPNN_OK, nothing touched); null pointers (where may
+ *      be NULL); alignment (workspace 16, counts 8, where 4 bytes); the workspace size (IMPNN_E_WORKSPACE).  No
+ *      allocation, no synchronisation, no state. */
+int32_t impnn_diverse_max_k(void);
+int impnn_diverse_workspace_bytes(int32_t C, int32_t A, int32_t k, size_t* need);
+int impnn_diverse_select(const float* mix_cat, const float* mix_an, const float* ref, const uint32_t* where, int32_t k,
+                         int32_t* cation, int32_t* anion, float* distance, int64_t* counts, void* workspace,
+                         size_t workspace_bytes, int32_t C, int32_t A, int32_t R, int32_t Mx, impnn_stream_t stream);
+
 /*  Mini-batch gather from a device-resident, already padded data set (model.fit over the arrays of
  *  train_viscosity.py:288-314): row rows[r] of tensor t -> row r of dst[t], for up to 8 tensors in one launch.
  *  src / dst / row_bytes are HOST arrays (device pointers, bytes per row: positive multiples of 4); `rows` is a device

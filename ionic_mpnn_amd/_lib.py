@@ -145,6 +145,9 @@ SIGNATURES = {
     "impnn_domain_grid": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "impnn_domain_grid_mask": (C.c_int, [vp, vp, vp, f32, f32, vp, i32, i32, i32, i32, vp]),
     "impnn_domain_rows": (C.c_int, [vp, vp, i32, vp, vp, i32, i32, i32, vp]),
+    "impnn_diverse_max_k": (i32, []),
+    "impnn_diverse_workspace_bytes": (C.c_int, [i32, i32, i32, C.POINTER(sz)]),
+    "impnn_diverse_select": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),

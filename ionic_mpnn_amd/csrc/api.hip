@@ -1518,6 +1518,41 @@ int impnn_domain_rows(const float* z, const float* ref, int32_t exclude_self, fl
   return launch_domain_rows(DomainRowsCall{z, ref, exclude_self != 0, distance, nearest, Q, R, Mx, as_stream(stream)});
 }
 
+// ---- the diverse batch (include/impnn.h; grid_diverse.hip).  The domain entries' order, with k beside the shape and
+// the limits: shape and k < 1, the width, k and pair-count limits, zero work, null pointers, alignment, the workspace size.
+namespace {
+int diverse_shape_rule(const char* entry, int C, int A, int R, int Mx, int k) {
+  if (int rc = domain_shape_rule(entry, C >= 0 && A >= 0, R, Mx)) return rc;
+  if (k < 1) return fail(IMPNN_E_BADARG, "%s: k=%d must be at least 1", entry, k);
+  if (int rc = domain_width_rule(entry, Mx)) return rc;
+  if (k > kDiverseMaxK) return fail(IMPNN_E_UNSUPPORTED, "%s: k=%d picks (<= %d per call)", entry, k, kDiverseMaxK);
+  return grid_pairs_rule(entry, C, A);
+}
+}  // namespace
+
+int32_t impnn_diverse_max_k(void) { return kDiverseMaxK; }
+
+int impnn_diverse_workspace_bytes(int32_t C, int32_t A, int32_t k, size_t* need) {
+  if (int rc = diverse_shape_rule(__func__, C, A, 1, 1, k)) return rc;
+  REQUIRE(need, "null pointer");
+  *need = diverse_workspace_bytes(C, A, k);
+  return IMPNN_OK;
+}
+
+int impnn_diverse_select(const float* mix_cat, const float* mix_an, const float* ref, const uint32_t* where, int32_t k,
+                         int32_t* cation, int32_t* anion, float* distance, int64_t* counts, void* workspace,
+                         size_t workspace_bytes, int32_t C, int32_t A, int32_t R, int32_t Mx, impnn_stream_t stream) {
+  if (int rc = diverse_shape_rule(__func__, C, A, R, Mx, k)) return rc;
+  if (C == 0 || A == 0) return IMPNN_OK;
+  REQUIRE(mix_cat && mix_an && ref && cation && anion && distance && counts && workspace, "null pointer");
+  if (int rc = grid_aligned_rule(__func__, workspace, nullptr, 16, "the workspace must be 16-byte aligned")) return rc;
+  if (int rc = grid_aligned_rule(__func__, counts, nullptr, 8, "the counts must be 8-byte aligned")) return rc;
+  if (int rc = grid_aligned_rule(__func__, where, nullptr, 4, "the mask must be 4-byte aligned")) return rc;
+  if (int rc = grid_workspace_rule(__func__, workspace_bytes, diverse_workspace_bytes(C, A, k))) return rc;
+  return launch_diverse_select(DiverseCall{mix_cat, mix_an, ref, where, k, cation, anion, distance, counts, workspace, C,
+                                           A, R, Mx, as_stream(stream)});
+}
+
 int impnn_gather_rows(int32_t n_tensors, const void* const* src, void* const* dst, const int64_t* row_bytes,
                       const int64_t* rows, int32_t n_rows, impnn_stream_t stream) {
   REQUIRE(n_tensors >= 0 && n_rows >= 0, "bad shape");

@@ -371,6 +371,23 @@ int domain_reference_chunk();  // reference rows per LDS chunk of the kernels
 int launch_domain_grid(const DomainGridCall& c);
 int launch_domain_rows(const DomainRowsCall& c);
 
+// ---- the diverse batch (grid_diverse.hip; include/impnn.h, impnn_diverse_select): k pairs by farthest-point selection
+// over the domain distance.  api.hip checks the arguments.
+constexpr int kDiverseMaxK = 4096;  // picks per call: one launch each
+struct DiverseCall {
+  const float *mix_cat, *mix_an, *ref;
+  const uint32_t* where;  // (C, W) mask words, or null: every pair
+  int k;
+  int32_t *cation, *anion;  // (k)
+  float* distance;          // (k)
+  int64_t* counts;          // (2): n, competing
+  void* workspace;
+  int C, A, R, Mx;
+  hipStream_t stream;
+};
+size_t diverse_workspace_bytes(int C, int A, int k);
+int launch_diverse_select(const DiverseCall& c);
+
 // ---- the ensemble grid (ensemble_grid.hip; include/impnn.h, impnn_ensemble_grid*): family 2 of GridOperands through
 // the materialising, mask-writing and selecting forms.  api.hip checks the arguments.
 int ensemble_grid_max_members();

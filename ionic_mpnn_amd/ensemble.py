@@ -143,7 +143,7 @@ class ModelEnsemble:
         raise ValueError("an ensemble has no latent space of its own: fit and screen the applicability domain with one "
                          "member model (its masks constrain the ensemble's screens through where=)")
 
-    fit_domain = domain_grid = screen_domain_mask = domain_distance = _no_domain
+    fit_domain = domain_grid = screen_domain_mask = domain_distance = screen_diverse = _no_domain
 
     def predict_pairs(self, cations, anions, cation_index, anion_index, temperatures=None, batch_size=4096):
         """Mean and population standard deviation of listed pairs - pair p is (cations[cation_index[p]],

@@ -1982,6 +1982,37 @@ class MPNNModel:
             words[lo:hi] = ops.domain_grid_mask(mc[lo:hi], ma, reference.rows, lo_b, hi_b)
         return data.PairMask(words, (C, A))
 
+    def screen_diverse(self, cations, anions, reference, k=24, where=None, batch_size=4096):
+        """Which ``k`` candidates to make next: a batch of pairs far from the reference set and from each other, by
+        farthest-point (k-center greedy) selection in the latent space, on the GPU (impnn_diverse_select) ->
+        ``data.DiverseSelection``: ``cation`` / ``anion`` (n,) int64 in the order of the picks, ``distance`` (n,) float32
+        - each pick's distance to the training pairs and the earlier picks when it was chosen, non-increasing - and
+        ``competing``, the number of candidates.  Every step takes the farthest pair that still competes - the lowest
+        (cation, anion) among equal float32 distances - and adds it to the reference set; a pair competes while its
+        distance is > 0, so a training pair, a pair that coincides with one, a chosen pair and a NaN never do.  n < k
+        when the candidates run out.  ``where``: a ``data.PairMask`` of shape (C,A); only its pairs compete:
+
+            dom   = visc_model.fit_domain(cat, an, train_cation_index, train_anion_index)
+            cand  = visc_model.screen_best_mask(cat, an, [298.15], k=liquid.count() // 100, where=liquid & ~known).temperature(0)
+            batch = visc_model.screen_diverse(cat, an, dom, k=24, where=cand)
+
+        The C x A float32 state lives in the library's workspace for the call; the picks need C*A < 2^32."""
+        k = int(k)
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        self._domain_request("screen_diverse", reference)
+        if where is not None and not isinstance(where, data.PairMask):
+            raise TypeError(f"where must be a data.PairMask, got {type(where).__name__}")
+        mc, ma = self._domain_mix(cations, anions, batch_size)
+        C, A = int(mc.shape[0]), int(ma.shape[0])
+        if where is not None and where.shape != (C, A):
+            raise ValueError(f"where must be a PairMask of shape {(C, A)}, got {where.shape}")
+        words = None if where is None else where.words.to(self.device)
+        cation, anion, distance, counts = ops.domain_diverse(mc, ma, reference.rows, k, where=words)
+        n, competing = (int(v) for v in counts.cpu().numpy())
+        return data.DiverseSelection(cation[:n].cpu().numpy().astype(np.int64), anion[:n].cpu().numpy().astype(np.int64),
+                                     distance[:n].cpu().numpy(), competing)
+
     def domain_distance(self, inputs, reference, batch_size=None):
         """The distance of listed pairs - a record list in ``predict``'s input format - to the reference set -> numpy
         (distance (n,) float32, nearest (n,) int32): ``encode_pooled``, the two ``ops.head_ion_mix`` halves, their

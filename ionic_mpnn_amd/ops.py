@@ -1594,6 +1594,47 @@ def domain_rows(z, ref, exclude_self=False):
     return distance, nearest
 
 
+# the limit of one diverse selection: kDiverseMaxK of csrc/common.h (tests/test_diverse_host.py holds them equal)
+DIVERSE_MAX_K = 4096
+
+
+def domain_diverse(mix_cat, mix_an, ref, k, where=None):
+    """A diverse batch of ``k`` pairs by farthest-point selection (impnn_diverse_select): starting from every pair's
+    ``domain_grid`` distance to ``ref``, k times the farthest pair that still competes is taken (the lowest i * A + j
+    among equal float32 distances) and joins the reference set -> (cation (k,) int32, anion (k,) int32, distance (k,)
+    float32, counts (2,) int64) on the device, without a host synchronisation: ``counts[0]`` = n picks were made (the
+    slots from n on hold -1 / -1 / NaN), ``counts[1]`` pairs competed at the start.  ``distance[t]`` has the bits
+    ``domain_grid`` gives pick t against ``ref`` plus the latent vectors of picks 0 .. t-1.  A pair competes while its
+    distance is > 0 (not NaN, not a pair of the reference set, not chosen before) and its bit of ``where`` - the (C,W)
+    words of a pair mask, or a ``data.PairMask`` - is set.  k <= DIVERSE_MAX_K, C*A < 2^32.  What ``data.grid_diverse``
+    computes in float64."""
+    mix_cat, mix_an, ref = _domain_operands(ref, mix_cat=mix_cat, mix_an=mix_an)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if k > DIVERSE_MAX_K:
+        raise ValueError(f"k={k}: one diverse selection takes at most {DIVERSE_MAX_K} picks")
+    C_, A_, dev = int(mix_cat.shape[0]), int(mix_an.shape[0]), ref.device
+    if where is not None:
+        where = _mask_words(where, C_, A_, dev)
+    lib = _lib.load()
+    need = C.c_size_t(0)
+    check(lib.impnn_diverse_workspace_bytes(C_, A_, k, C.byref(need)))
+    cation = torch.empty(k, dtype=torch.int32, device=dev)
+    anion = torch.empty(k, dtype=torch.int32, device=dev)
+    distance = torch.empty(k, dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    if C_ == 0 or A_ == 0:  # zero work touches nothing: no pair in any slot
+        cation.fill_(-1), anion.fill_(-1), distance.fill_(float("nan")), counts.zero_()
+        return cation, anion, distance, counts
+    ws = _workspace(dev, need.value)
+    with torch.cuda.device(dev):
+        check(lib.impnn_diverse_select(ptr(mix_cat), ptr(mix_an), ptr(ref), None if where is None else ptr(where), k,
+                                       ptr(cation), ptr(anion), ptr(distance), ptr(counts), ptr(ws), need.value, C_, A_,
+                                       int(ref.shape[0]), int(ref.shape[1]), stream_ptr()))
+    return cation, anion, distance, counts
+
+
 def transfer_head(pooled_cat, pooled_an, weights, cfg):
     """The transfer model's head in inference, one launch (impnn_transfer_head): ``weights`` the 18 tensors in the
     order of include/impnn.h, ``cfg`` MPNNModel._transfer_cfg -> (B,1)."""

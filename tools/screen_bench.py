@@ -77,7 +77,17 @@ mix_an[j], torch.cdist against the reference rows, min - from the same encode_io
 alternating rounds after a warm-up of each, wall time, median and spread.  Plus the launches alone over resident mixing
 rows (impnn_domain_grid, impnn_domain_grid_mask, and the torch tile loop), 5 calls between two HIP events, three rounds
 each in turn, the kernel's 2 * R * Mx lane operations per pair over its time, and how far the torch distances lie from
-the kernel's (torch.cdist expands |z|^2 - 2 z.r + |r|^2 on the matrix cores: a training pair is not at exactly 0)."""
+the kernel's (torch.cdist expands |z|^2 - 2 z.r + |r|^2 on the matrix cores: a training pair is not at exactly 0).
+
+--diverse K: MPNNModel.screen_diverse (K picks by farthest-point selection, impnn_diverse_select) of the same model over
+N x N pairs against R reference pairs (--reference, default 7700), against the torch loop a user would write from the
+same mixing rows: D from ops.domain_grid, then K times an argmax under the mask (one host round trip each) and
+torch.minimum with the distances to z[pick] over a materialised z (N x N x Mx floats).  Three alternating rounds after a
+warm-up of each, wall time, median and spread; how many picks the two ways share (the torch loop orders its own float32
+distances and breaks ties as torch.argmax does).  Plus the launches alone over resident mixing rows, 3 calls between
+two HIP events, three rounds each in turn: the whole selection, the selection with k = 1 (the init pass) beside
+impnn_domain_grid, and from the two the time of one step and its 8 bytes of state traffic per pair over that time.
+With --where F both ways run under one random pair mask of density F."""
 import argparse
 import json
 import statistics
@@ -109,10 +119,13 @@ ap.add_argument("--pareto", action="store_true", help="time screen_pareto (visco
                 "calls and data.pareto_front on the host")
 ap.add_argument("--domain", type=int, metavar="R", help="time screen_domain_mask and domain_grid over R reference pairs "
                 "against gathered tiles, torch.cdist and min")
-ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --mc, --pareto, --domain: cations = anions = this many")
+ap.add_argument("--diverse", type=int, metavar="K", help="time screen_diverse (K picks by farthest-point selection) against "
+                "the torch loop over a materialised z; --reference R reference pairs, --where F a random mask of that density")
+ap.add_argument("--reference", type=int, default=7700, metavar="R", help="with --diverse: the reference pairs")
+ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --mc, --pareto, --domain, --diverse: cations = anions = this many")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain or args.mc  # another table than the default one
+other = args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain or args.mc or args.diverse  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -281,7 +294,77 @@ RANK_CONFIGS = ("config2 2048x2048x4", "transfer 1024x1024", "transfer 4096x4096
 
 DOMAIN_TILE_FLOATS = 1 << 28  # the torch path's pairs x R distance tile: 1 GiB of float32
 
-if args.domain:
+if args.diverse:
+    N, R, K = args.size, args.reference, args.diverse
+    m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+    m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
+    cat, _ = species(N, 1)
+    _, an = species(N, 2)
+    rng = np.random.default_rng(3)
+    flat = rng.choice(N * N, size=R, replace=False)
+    dom = m.fit_domain(cat, an, flat // N, flat % N)
+    Mx = m.mixing_size
+    where_h = None if args.where is None else rng.random((N, N)) < args.where
+    where = None if where_h is None else data.PairMask.from_bool(where_h, device=dev)
+    live = None if where_h is None else torch.from_numpy(where_h).to(dev)
+
+    def mixing_rows():
+        with torch.no_grad():
+            pc, pa = m.encode_ions(cat, an)
+            w = m._packed_head()
+            return ops.head_ion_mix("viscosity", "cat", pc, w, m.fp_size, Mx), ops.head_ion_mix("viscosity", "an", pa, w, m.fp_size, Mx)
+
+    def torch_way():
+        mc, ma = mixing_rows()
+        D, _ = ops.domain_grid(mc, ma, dom.rows)
+        z = mc[:, None, :] + ma[None, :, :]                       # materialised: N x N x Mx floats
+        picks, dist = [], []
+        for _ in range(K):
+            cand = D > 0 if live is None else live & (D > 0)
+            score = torch.where(cand, D, torch.full_like(D, -1.0))
+            at = int(torch.argmax(score))                         # the host round trip of a pick
+            top = float(score.view(-1)[at])
+            if not top > 0:
+                break
+            picks.append(at)
+            dist.append(top)
+            D = torch.minimum(D, (z - z[at // N, at % N]).square().sum(dim=2).sqrt())
+        return np.asarray(picks, np.int64), np.asarray(dist, np.float32)
+
+    new_way = lambda: m.screen_diverse(cat, an, dom, k=K, where=where)
+    (p_t, d_t), sel = wall(torch_way)[1], wall(new_way)[1]
+    t_torch, t_new = [], []
+    for _ in range(3):
+        t_torch.append(wall(torch_way)[0])
+        t_new.append(wall(new_way)[0])
+    mc, ma = mixing_rows()
+    words = None if where is None else where.words
+    REP = 3
+    runs = {"diverse_select": lambda: [ops.domain_diverse(mc, ma, dom.rows, K, where=words) for _ in range(REP)],
+            "diverse_select_k1": lambda: [ops.domain_diverse(mc, ma, dom.rows, 1, where=words) for _ in range(REP)],
+            "domain_grid": lambda: [ops.domain_grid(mc, ma, dom.rows) for _ in range(REP)]}
+    got = {n: [] for n in runs}
+    for fn in runs.values():
+        timed(fn)
+    for _ in range(3):
+        for n, fn in runs.items():
+            got[n].append(timed(fn)[0] / REP * 1e3)
+    p_k = sel.cation * N + sel.anion
+    shared = min(len(p_t), len(p_k))
+    step_us = (statistics.median(got["diverse_select"]) - statistics.median(got["diverse_select_k1"])) / max(K - 1, 1)
+    line = {"config": f"diverse {N}x{N} R={len(dom)} Mx={Mx} K={K}" + ("" if args.where is None else f" where={args.where}"),
+            "C": N, "A": N, "R": len(dom), "Mx": Mx, "K": K, "where": args.where, "picks": int(len(p_k)),
+            "competing": int(sel.competing), "torch_loop_ms": spread(t_torch), "screen_diverse_ms": spread(t_new),
+            "speedup": round(statistics.median(t_torch) / statistics.median(t_new), 2),
+            "launch_us": {n: spread(x) for n, x in got.items()}, "step_us": round(step_us, 2),
+            "step_state_GBps": round(8.0 * N * N / (step_us * 1e-6) / 1e9, 1) if step_us > 0 else None,
+            "torch_picks": int(len(p_t)), "same_leading_picks": int(np.argmin(np.append(p_t[:shared] == p_k[:shared], False))),
+            "same_picks_as_sets": int(len(set(p_t.tolist()) & set(p_k.tolist()))),
+            "last_distance": float(sel.distance[-1]) if len(p_k) else None,
+            "torch_last_distance": float(d_t[-1]) if len(p_t) else None}
+    print(json.dumps(line), flush=True)
+    lines.append(line)
+elif args.domain:
     N, R = args.size, args.domain
     m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
     m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
