@@ -13,6 +13,7 @@ import torch
 
 from ionic_mpnn_amd import _lib, data, model as MM, ops
 
+from footprint import FILL, GUARD, Guarded   # (test_gpu_pareto, _diverse, _rank, ... import them from here)
 from test_gpu_grid import DIMS, T5, bits, head_weights, make_model, pack, pooled_rows, species
 from test_transfer_grid_host import make_case
 from test_gpu_transfer_grid import dev, head_on_device
@@ -20,28 +21,12 @@ from test_gpu_transfer_grid import dev, head_on_device
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 KINDS = ("viscosity", "melting_point")
-GUARD = 256          # guard bytes on either side of every buffer the entries write
-FILL = 0xA5          # what they hold before the call: no float, index or entry the kernels write is 0xA5A5...
 MAX_T = ops.SELECT_MAX_T
 T_MAX = np.array([263.15, 298.15, 313.0, 390.0], np.float32)
 assert len(T_MAX) == MAX_T
 
 
 # ---------------------------------------------------------------- guarded calls of the two entries
-class Guarded:
-    def __init__(self, nbytes):
-        self.n = nbytes
-        self.whole = torch.full((GUARD + nbytes + GUARD,), FILL, dtype=torch.uint8, device=DEV)
-        assert self.whole.data_ptr() % 16 == 0
-        self.ptr = C.c_void_p(self.whole.data_ptr() + GUARD)
-
-    def body(self, dtype, what):
-        host = self.whole.cpu().numpy()
-        assert (host[:GUARD] == FILL).all(), f"write before {what}"
-        assert (host[GUARD + self.n:] == FILL).all(), f"write past {what}"
-        return host[GUARD:GUARD + self.n].view(dtype)
-
-
 def call_topk(family, launch, Cn, An, nT, k, workgroups):
     """Runs one entry on guarded outputs and a guarded workspace of exactly the queried size -> data.TopK of the
     meaningful slots, (rows, min(k, C*A)); checks that every slot was written and that the rest is NaN / -1."""
