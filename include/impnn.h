@@ -886,6 +886,59 @@ int impnn_transfer_mc_grid_topk_where(const float* u_cat, const float* u_an, con
                                       void* workspace, size_t workspace_bytes, int32_t C, int32_t A, int32_t workgroups,
                                       impnn_stream_t stream);
 
+/* ---- per-ion statistics of the grid, reduced on the GPU: for every cation over its anions, and for every anion over its
+ *      cations, the number of competing pairs, the sum, the sum of squares, the least and the greatest value - the
+ *      main-effects view of the cation x anion table, from ONE launch over the grid and without its (C,A[,nT]) output.
+ *      The sixth operation of the screening family and the one every grid family has: the ensemble grid and the transfer
+ *      MC grid summarise their score mean + kappa * std.
+ *      The summary kernels run the tile arithmetic of the family's materialising entry (a summarised value v has the bits
+ *      that entry writes for the pair), one tile (16 x 64 pairs; the transfer grids 8 x 32) per workgroup, and reduce the
+ *      tile on the chip; a second small launch, one thread per (plane, ion), adds the tiles' partial records.  No C x A
+ *      buffer, no atomics, no pre-zeroed memory.
+ *      A pair competes when its `where` bit is set (NULL: always) and v is not NaN.  The record of an ion and plane:
+ *        n: uint32, the competing pairs;  s = sum (double)v;  q = sum (double)v * (double)v (exact products);
+ *        lo, hi: the least and the greatest v under the order of impnn_head_grid_topk's key (-0.0 < +0.0);
+ *        n == 0: s = q = +0.0, lo = hi = the quiet NaN 0x7FC00000.
+ *      The sums run in double in one order, a pair that does not compete being +0.0; (bc, ba) = the tile, (16, 64) or
+ *      (8, 32).  Cation i: the anions in blocks of ba from anion 0, a block's partial the adjacent-pair tree
+ *      x[2k] + x[2k+1] level by level, the total +0.0 plus the blocks in ascending order.  Anion j: the cations in blocks
+ *      of bc from cation 0, a block's partial +0.0 plus its cations in ascending order, the total +0.0 (carry == 1: the
+ *      record the buffers hold) plus the blocks in ascending order.  A tile the mask lets a workgroup pass over gives the
+ *      partials computing it would give.  So the bits do not depend on the grid's size, on whether a masked-out tile was
+ *      skipped, or - when a caller cuts the cation axis at multiples of 16 and carries the anion records from one range's
+ *      call into the next - on that cut.
+ *      where: NULL, or a (C,W) pair mask, 4-byte aligned, the one mask for every plane.
+ *      carry: 0, the anion records are written without being read; 1, they continue from what they hold.
+ *      buffers: a HOST table of seven device pointers, planes = max(nT, 1): cat_count uint32 [planes][C], cat_sums double
+ *      [planes][C][2] (s, q; 8-byte aligned), cat_range float [planes][C][2] (lo, hi), an_count [planes][A], an_sums
+ *      [planes][A][2], an_range [planes][A][2], and the workspace (8-byte aligned): workspace_bytes >=
+ *      impnn_grid_summary_workspace_bytes(family, C, A, planes) = 32 * planes * (tiles_a * C + tiles_c * A) bytes, family
+ *      0 head, 1 transfer, 2 ensemble, 3 transfer MC grid; the query answers 0 for arguments no launch takes.  The
+ *      workspace is written before it is read and carries nothing from call to call.
+ *      Limits of one call: nT <= 4096 (kind 0); the widths, M, S and kappa of the family's other entries.
+ *      The ensemble grid's entry is impnn_deep_ensemble_grid_summary: the names that begin impnn_ensemble_grid are the
+ *      closed list of that family's materialising, mask-writing and selecting entries and their queries.
+ *      Checks in order, as impnn_head_grid_partners: kind and shape (with M or S and kappa, carry; IMPNN_E_BADARG, a
+ *      limit IMPNN_E_UNSUPPORTED); the widths; zero work (C == 0 or A == 0: IMPNN_OK, nothing touched); null pointers
+ *      (the table and each of its seven entries), then alignment and the image size; the workspace size
+ *      (IMPNN_E_WORKSPACE, nothing touched).  No allocation, no synchronisation, no state. */
+int64_t impnn_grid_summary_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t planes);
+int impnn_head_grid_summary(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                            const float* head_weights, const uint32_t* where, int32_t carry, size_t workspace_bytes,
+                            const void* const* buffers, int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F,
+                            int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_head_grid_summary(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                     const uint32_t* where, int32_t carry, size_t workspace_bytes,
+                                     const void* const* buffers, int32_t C, int32_t A, impnn_stream_t stream);
+int impnn_deep_ensemble_grid_summary(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                                const float* temperatures, const float* tails, float kappa, const uint32_t* where,
+                                int32_t carry, size_t workspace_bytes, const void* const* buffers, int32_t C, int32_t A,
+                                int32_t nT, int32_t F, int32_t Mx, impnn_stream_t stream);
+int impnn_transfer_mc_grid_summary(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                   const float* multipliers, int32_t S, float kappa, const uint32_t* where, int32_t carry,
+                                   size_t workspace_bytes, const void* const* buffers, int32_t C, int32_t A,
+                                   impnn_stream_t stream);
+
 /* ---- the Pareto front of two objectives over a cation x anion grid: a sound filter on the GPU, from two planes of
  *      values to a short candidate list that holds the whole front; the caller finishes the front of the candidates.
  *      A pair (i, j) has the float32 values v1, v2 and the keys k1, k2 of the selection's order (the order-preserving

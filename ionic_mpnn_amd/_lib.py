@@ -134,6 +134,11 @@ SIGNATURES = {
                                               vp]),
     "impnn_transfer_mc_grid_topk_where": (C.c_int, [vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp, vp, vp, vp, sz, i32,
                                                     i32, i32, vp]),
+    "impnn_grid_summary_workspace_bytes": (i64, [i32] * 4),
+    "impnn_head_grid_summary": (C.c_int, [i32, vp, vp, vp, vp, vp, i32, sz, PP] + [i32] * 6 + [vp]),
+    "impnn_transfer_head_grid_summary": (C.c_int, [vp, vp, vp, i64, vp, i32, sz, PP, i32, i32, vp]),
+    "impnn_deep_ensemble_grid_summary": (C.c_int, [i32, i32, vp, vp, vp, vp, f32, vp, i32, sz, PP] + [i32] * 5 + [vp]),
+    "impnn_transfer_mc_grid_summary": (C.c_int, [vp, vp, vp, i64, vp, i32, f32, vp, i32, sz, PP, i32, i32, vp]),
     "impnn_pareto_bucket_bits": (i32, []),
     "impnn_pareto_workspace_bytes": (C.c_int, [C.POINTER(sz)]),
     "impnn_pareto_begin": (C.c_int, [vp, sz, vp]),

@@ -1471,6 +1471,83 @@ int impnn_transfer_mc_grid_topk_where(const float* u_cat, const float* u_an, con
                            workspace_bytes);
 }
 
+// ---- per-ion statistics of the grid (include/impnn.h; grid_summary.hip): every family through the summary form.  The
+// partners entries' order: kind and shape (with M / S and kappa, carry and the plane limit), the widths, zero work, null
+// pointers (the table and its seven entries), alignment and the image size, the workspace size.
+namespace {
+int grid_summary_planes(const GridOperands& g) { return g.nT > 0 ? g.nT : 1; }
+
+int grid_summary_checked(const char* entry, const GridOperands& g, bool shape_ok, bool pointers_ok, int64_t image_floats,
+                         const uint32_t* where, int carry, size_t workspace_bytes, const void* const* buffers) {
+  if (int rc = grid_kind_rule(entry, g, shape_ok)) return rc;
+  if (g.family == 2)
+    if (int rc = grid_ensemble_rule(entry, g.M, g.kappa)) return rc;
+  if (g.family == 3)
+    if (int rc = grid_mc_rule(entry, g.M, g.kappa)) return rc;
+  if (g.C < 0 || g.A < 0 || g.nT < 0) return fail(IMPNN_E_BADARG, "%s: bad shape", entry);
+  if (carry != 0 && carry != 1) return fail(IMPNN_E_BADARG, "%s: carry must be 0 or 1", entry);
+  const int most = grid_summary_max_planes(g.family, g.M);
+  if (g.nT > most) return fail(IMPNN_E_UNSUPPORTED, "%s: nT=%d temperatures (<= %d per call)", entry, g.nT, most);
+  bool table_ok = buffers != nullptr;
+  for (int i = 0; table_ok && i < 7; ++i) table_ok = buffers[i] != nullptr;
+  bool launch;
+  if (int rc = grid_selecting_rules(entry, g, pointers_ok && table_ok, table_ok ? buffers[6] : nullptr, where, image_floats,
+                                    grid_summary_workspace_bytes(g.family, g.C, g.A, grid_summary_planes(g)),
+                                    workspace_bytes, &launch))
+    return rc;
+  if (!launch) return IMPNN_OK;
+  if (int rc = grid_aligned_rule(entry, buffers[1], buffers[4], 8, "the sums must be 8-byte aligned")) return rc;
+  for (int i : {0, 2, 3, 5})
+    if (int rc = grid_aligned_rule(entry, buffers[i], nullptr, 4, "the counts and the ranges must be 4-byte aligned")) return rc;
+  auto at = [&](int i) { return const_cast<void*>(buffers[i]); };
+  return launch_grid_summary(GridSummaryCall{g, where, carry, static_cast<uint32_t*>(at(0)), static_cast<double*>(at(1)),
+                                             static_cast<float*>(at(2)), static_cast<uint32_t*>(at(3)),
+                                             static_cast<double*>(at(4)), static_cast<float*>(at(5)), at(6)});
+}
+}  // namespace
+
+int64_t impnn_grid_summary_workspace_bytes(int32_t family, int32_t C, int32_t A, int32_t planes) {
+  if (family < 0 || family > 3 || C < 0 || A < 0 || planes < 1) return 0;
+  if (planes > grid_summary_max_planes(family, family == 2 ? ensemble_grid_max_members() : 1)) return 0;  // (the fullest ensemble)
+  return (int64_t)grid_summary_workspace_bytes(family, C, A, planes);
+}
+
+int impnn_head_grid_summary(int32_t kind, const float* mix_cat, const float* mix_an, const float* temperatures,
+                            const float* head_weights, const uint32_t* where, int32_t carry, size_t workspace_bytes,
+                            const void* const* buffers, int32_t C, int32_t A, int32_t nT, int32_t D, int32_t F,
+                            int32_t Mx, impnn_stream_t stream) {
+  return grid_summary_checked(__func__,
+                              head_grid_operands(kind, mix_cat, mix_an, temperatures, head_weights, C, A, nT, D, F, Mx, stream),
+                              D > 0 && F > 0 && Mx > 0, mix_cat && mix_an && head_weights && (kind == 1 || temperatures), 0,
+                              where, carry, workspace_bytes, buffers);
+}
+
+int impnn_transfer_head_grid_summary(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                     const uint32_t* where, int32_t carry, size_t workspace_bytes,
+                                     const void* const* buffers, int32_t C, int32_t A, impnn_stream_t stream) {
+  return grid_summary_checked(__func__, transfer_grid_operands(u_cat, u_an, image, C, A, stream), image_floats >= 0,
+                              u_cat && u_an && image, image_floats, where, carry, workspace_bytes, buffers);
+}
+
+int impnn_deep_ensemble_grid_summary(int32_t kind, int32_t M, const float* mix_cat, const float* mix_an,
+                                const float* temperatures, const float* tails, float kappa, const uint32_t* where,
+                                int32_t carry, size_t workspace_bytes, const void* const* buffers, int32_t C, int32_t A,
+                                int32_t nT, int32_t F, int32_t Mx, impnn_stream_t stream) {
+  return grid_summary_checked(__func__,
+                              ensemble_grid_operands(kind, M, mix_cat, mix_an, temperatures, tails, kappa, C, A, nT, F, Mx, stream),
+                              F > 0 && Mx > 0, mix_cat && mix_an && tails && (kind == 1 || temperatures), 0, where, carry,
+                              workspace_bytes, buffers);
+}
+
+int impnn_transfer_mc_grid_summary(const float* u_cat, const float* u_an, const float* image, int64_t image_floats,
+                                   const float* multipliers, int32_t S, float kappa, const uint32_t* where, int32_t carry,
+                                   size_t workspace_bytes, const void* const* buffers, int32_t C, int32_t A,
+                                   impnn_stream_t stream) {
+  return grid_summary_checked(__func__, transfer_mc_grid_operands(u_cat, u_an, image, multipliers, S, kappa, C, A, stream),
+                              image_floats >= 0, u_cat && u_an && image && multipliers, image_floats, where, carry,
+                              workspace_bytes, buffers);
+}
+
 // ---- the applicability domain (include/impnn.h; grid_domain.hip).  The three entries' order: shape (sizes, R >= 1,
 // Mx >= 1, exclude_self with Q != R, a NaN bound), the width limit, zero work, null pointers, then the launcher's tile count.
 namespace {

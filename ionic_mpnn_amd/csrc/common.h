@@ -448,6 +448,25 @@ int grid_rank_workgroups(int family, int C, int A, int workgroups);  // 0: the d
 size_t grid_rank_workspace_bytes(int family, int C, int A, int nT, int workgroups);
 int launch_grid_rank(const GridRankCall& c);
 
+// ---- per-ion statistics of a cation x anion grid (grid_summary.hip; include/impnn.h, impnn_*_grid_summary): every
+// family of GridOperands through the summary form, then the merge of the tiles' partial records.
+// One call: `where` may be null.  api.hip checks it.
+struct GridSummaryCall {
+  GridOperands g;
+  const uint32_t* where;  // (C, ceil(A / 32)) words, or null: every pair competes
+  int carry;              // 1: the anion records continue from what they hold
+  uint32_t* cat_count;    // [planes][C]
+  double* cat_sums;       // [planes][C][2]: s, q
+  float* cat_range;       // [planes][C][2]: lo, hi
+  uint32_t* an_count;     // [planes][A]
+  double* an_sums;
+  float* an_range;
+  void* workspace;
+};
+int grid_summary_max_planes(int family, int M);  // planes one launch takes (family 2: with M members)
+size_t grid_summary_workspace_bytes(int family, int C, int A, int planes);
+int launch_grid_summary(const GridSummaryCall& c);
+
 // ---- the typed-message family (message_typed.hip): edge sort by bond type, sorted forward, message adjoint
 int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)

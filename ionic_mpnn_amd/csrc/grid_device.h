@@ -3,7 +3,8 @@
 // impnn_transfer_head_grid_topk and their _where forms) and the mask-writing kernels (grid_mask.hip:
 // impnn_head_grid_mask, impnn_transfer_head_grid_mask) and the partner-selecting kernels (grid_partners.hip:
 // impnn_head_grid_partners, impnn_transfer_head_grid_partners) and the rank-cut kernels (grid_rank.hip:
-// impnn_head_grid_rank, impnn_transfer_head_grid_rank) all run, and the keys and the running top-k of the selection.
+// impnn_head_grid_rank, impnn_transfer_head_grid_rank) and the per-ion summary kernels (grid_summary.hip:
+// impnn_*_grid_summary) all run, and the keys and the running top-k of the selection.
 // One definition of a tile's arithmetic, so a selected or tested value has the bits the materialised grid holds for
 // that pair; and, at the end, the one host function that launches them (launch_grid_family).
 #pragma once
@@ -229,19 +230,41 @@ struct GridMaskRank {
   int W, largest;
 };
 
+// What the summary form adds (grid_summary.hip): where the materialising form stores a tile, this one reduces the tile's
+// values along every tile row (a cation's anions of this tile) and every tile column (an anion's cations of this tile)
+// to one record each and writes them to rows [planes][tiles_a][C] and cols [planes][tiles_c][A].  One tile per
+// workgroup and one writing workgroup per slot: no pre-zeroing, no atomics.  A pair competes when its `where` bit is
+// set (null: always) and its value is not NaN.  The record of the competing pairs: their number n, s = sum (double)v,
+// q = sum (double)v * (double)v (the product of two float32 values is exact in double), and lo / hi, the least keys of
+// select_key(v, false) / select_key(v, true), 0xFFFFFFFF where nothing competes.  The order of the sums is fixed: a tile
+// row is the adjacent-pair tree x[2k] + x[2k+1], level by level, over the row's lanes, a lane that does not compete
+// holding +0.0; a tile column starts at +0.0 and adds its rows in ascending order.
+struct SummaryRecord {
+  double s, q;
+  uint32_t n, lo, hi, pad;
+};
+static_assert(sizeof(SummaryRecord) == 32, "a summary record is 32 bytes");
+struct GridSummary {
+  SummaryRecord *rows, *cols;
+  const uint32_t* where;  // [C][W], or null
+  int W;
+};
+
 // which form of a grid kernel its trailing pack makes
-template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = false; };
-template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false, partners = false, rank_count = false, rank_mask = false; };
-template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false, partners = false, rank_count = false, rank_mask = false; };
-template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true, partners = false, rank_count = false, rank_mask = false; };
-template <> struct GridForm<GridPartners> { static constexpr bool select = false, where = false, mask = false, partners = true, rank_count = false, rank_mask = false; };
-template <> struct GridForm<GridPartnersWhere> { static constexpr bool select = false, where = true, mask = false, partners = true, rank_count = false, rank_mask = false; };
-template <> struct GridForm<GridRank> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = true, rank_mask = false; };
-template <> struct GridForm<GridMaskRank> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = true; };
+template <class... Sel> struct GridForm { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = false, summary = false; };
+template <> struct GridForm<GridSelect> { static constexpr bool select = true, where = false, mask = false, partners = false, rank_count = false, rank_mask = false, summary = false; };
+template <> struct GridForm<GridSelectWhere> { static constexpr bool select = true, where = true, mask = false, partners = false, rank_count = false, rank_mask = false, summary = false; };
+template <> struct GridForm<GridMask> { static constexpr bool select = false, where = false, mask = true, partners = false, rank_count = false, rank_mask = false, summary = false; };
+template <> struct GridForm<GridPartners> { static constexpr bool select = false, where = false, mask = false, partners = true, rank_count = false, rank_mask = false, summary = false; };
+template <> struct GridForm<GridPartnersWhere> { static constexpr bool select = false, where = true, mask = false, partners = true, rank_count = false, rank_mask = false, summary = false; };
+template <> struct GridForm<GridRank> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = true, rank_mask = false, summary = false; };
+template <> struct GridForm<GridSummary> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = false, summary = true; };
+template <> struct GridForm<GridMaskRank> { static constexpr bool select = false, where = false, mask = false, partners = false, rank_count = false, rank_mask = true, summary = false; };
 
 __device__ __forceinline__ bool select_next_tile(unsigned*, const GridMask&) { return false; }
 __device__ __forceinline__ bool select_next_tile(unsigned*, const GridPartners&) { return false; }
 __device__ __forceinline__ bool select_next_tile(unsigned*, const GridMaskRank&) { return false; }
+__device__ __forceinline__ bool select_next_tile(unsigned*, const GridSummary&) { return false; }
 __device__ __forceinline__ bool select_next_tile(unsigned* tile, const GridRank& g) {
   *tile += gridDim.x;
   return *tile < g.tiles;
@@ -258,6 +281,9 @@ __device__ __forceinline__ uint32_t* where_tile_words(const GridRank&, float* li
   return reinterpret_cast<uint32_t*>(lists) + (size_t)nT * kRankBins;
 }
 __device__ __forceinline__ uint32_t* where_tile_words(const GridMaskRank&, float* lists, int) {
+  return reinterpret_cast<uint32_t*>(lists);
+}
+__device__ __forceinline__ uint32_t* where_tile_words(const GridSummary&, float* lists, int) {
   return reinterpret_cast<uint32_t*>(lists);
 }
 
@@ -450,6 +476,96 @@ __device__ __forceinline__ void rank_skip_tile(const GridMaskRank& g, int C, int
   }
 }
 
+// ================================================================ per-ion summary (grid_summary.hip)
+// whether the launch has a mask (block-uniform: a kernel argument)
+__device__ __forceinline__ bool summary_masked(const GridSummary& g) { return g.where != nullptr; }
+
+constexpr uint32_t kSummaryNoKey = 0xFFFFFFFFu;  // lo / hi of a record without a competing pair
+
+// x + x of the lane a DPP control names: a double travels as its two halves (partners_dpp)
+template <int CTRL>
+__device__ __forceinline__ double summary_dpp_add(double x) {
+  return x + __longlong_as_double((long long)partners_dpp<CTRL>((unsigned long long)__double_as_longlong(x)));
+}
+// The sum over a row of WIDTH = 64 or 32 lanes, in every lane of the row, by partners_row_min's butterfly.  Every step
+// adds the two halves of a span that both hold their own sum, and a + b has the bits of b + a: the adjacent-pair tree
+// x[2k] + x[2k+1], level by level, with the same bits in every lane.
+template <int WIDTH>
+__device__ __forceinline__ double summary_row_sum(double x) {
+  x = summary_dpp_add<0xB1>(x);   // quad_perm [1,0,3,2]
+  x = summary_dpp_add<0x4E>(x);   // quad_perm [2,3,0,1]
+  x = summary_dpp_add<0x141>(x);  // row_half_mirror
+  x = summary_dpp_add<0x140>(x);  // row_mirror
+  x = x + __shfl_xor(x, 16);
+  if (WIDTH == 64) x = x + __shfl_xor(x, 32);
+  return x;
+}
+template <int CTRL>
+__device__ __forceinline__ uint32_t summary_dpp_min(uint32_t x) {
+  return min(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false));
+}
+template <int WIDTH>
+__device__ __forceinline__ uint32_t summary_row_min(uint32_t x) {
+  x = summary_dpp_min<0xB1>(x);
+  x = summary_dpp_min<0x4E>(x);
+  x = summary_dpp_min<0x141>(x);
+  x = summary_dpp_min<0x140>(x);
+  x = min(x, (uint32_t)__shfl_xor((int)x, 16));
+  if (WIDTH == 64) x = min(x, (uint32_t)__shfl_xor((int)x, 32));
+  return x;
+}
+
+// A tile row, one value per lane of a row of WIDTH lanes (`ok`: the lane's pair competes): the row's record, written by
+// the row's first lane to dst (null: the grid has no such row).  Wave-uniform control flow, every lane active.
+template <int WIDTH>
+__device__ __forceinline__ void summary_row(bool ok, float v, SummaryRecord* dst) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long b = __ballot(ok);
+  const uint32_t n = WIDTH == 64 ? (uint32_t)__popcll(b) : (uint32_t)__popc((uint32_t)(b >> (lane & 32)));
+  const double d = ok ? (double)v : 0.0;
+  const double s = summary_row_sum<WIDTH>(d), q = summary_row_sum<WIDTH>(d * d);
+  const uint32_t lo = summary_row_min<WIDTH>(ok ? select_key(v, false) : kSummaryNoKey);
+  const uint32_t hi = summary_row_min<WIDTH>(ok ? select_key(v, true) : kSummaryNoKey);
+  if (dst && (lane & (WIDTH - 1)) == 0) *dst = SummaryRecord{s, q, n, lo, hi, 0u};
+}
+
+// A record that grows one term, or one record, at a time in ascending order: a tile column (one thread walks the
+// tile's rows) and the merge of an ion's partial records.  It starts as the record of no pair: n 0, sums +0.0, no keys.
+struct SummarySum {
+  double s = 0.0, q = 0.0;
+  uint32_t n = 0u, lo = kSummaryNoKey, hi = kSummaryNoKey;
+  __device__ __forceinline__ void add(bool ok, float v) {
+    if (!ok) return;  // (s and q are never -0.0: adding the +0.0 of a pair that does not compete would change nothing)
+    const double d = (double)v;
+    s = s + d;
+    q = q + d * d;
+    n += 1u;
+    lo = min(lo, select_key(v, false));
+    hi = min(hi, select_key(v, true));
+  }
+  __device__ __forceinline__ void add(const SummaryRecord& r) {
+    s = s + r.s;
+    q = q + r.q;
+    n += r.n;
+    lo = min(lo, r.lo);
+    hi = min(hi, r.hi);
+  }
+  __device__ __forceinline__ SummaryRecord record() const { return SummaryRecord{s, q, n, lo, hi, 0u}; }
+};
+
+// The slots of a tile the mask lets the workgroup pass over: rows c0 .. c0 + nc of anion tile ta and columns a0 .. a0 + na
+// of cation tile tc, every plane, the record of no pair - what computing the tile would give.
+__device__ __forceinline__ void summary_skip_tile(const GridSummary& g, int C, int A, int c0, int a0, int nc, int na,
+                                                  int tiles_a, int ta, int tiles_c, int tc, int planes) {
+  const SummaryRecord none = SummarySum().record();
+  for (int t = 0; t < planes; ++t) {
+    SummaryRecord* rows = g.rows + ((size_t)t * tiles_a + ta) * C + c0;
+    SummaryRecord* cols = g.cols + ((size_t)t * tiles_c + tc) * A + a0;
+    for (int i = threadIdx.x; i < nc; i += blockDim.x) rows[i] = none;
+    for (int i = threadIdx.x; i < na; i += blockDim.x) cols[i] = none;
+  }
+}
+
 // ================================================================ the head grid (head_grid.hip; grid_select.hip; grid_mask.hip; grid_partners.hip)
 // One workgroup owns kTileC cations x kTileA anions; lane = anion, a wave walks the tile's cations.
 constexpr int kTileC = 16, kTileA = 64, kTilePairs = kTileC * kTileA;
@@ -492,6 +608,33 @@ __device__ __forceinline__ void partners_head_tile(const GridPartners& g, int C,
     for (int r = 0; r < nc; ++r)
       best.offer(partners_entry(g, live(r, a), value(r * kTileA + a, t), (uint32_t)(c0 + r) * (uint32_t)A + (uint32_t)(a0 + a)));
     best.store(g.cols + (((size_t)t * tiles_c + tc) * A + a0 + a) * g.m, g.m);
+  }
+}
+
+// The head grid's tile as summary records: value(e, t) is pair e = r * kTileA + a of the tile at plane t, live(r, a) its
+// mask bit.  A wave's 64 lanes are the 64 anions of one tile row; then one thread per (plane, tile column) walks the
+// column's rows in LDS in ascending order.
+template <class Fn, class Live>
+__device__ __forceinline__ void summary_head_tile(const GridSummary& g, int C, int A, int c0, int a0, int nc, int na,
+                                                  int tiles_a, int planes, Fn value, Live live) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ta = a0 / kTileA, tc = c0 / kTileC, tiles_c = (C + kTileC - 1) / kTileC;
+  for (int t = 0; t < planes; ++t)
+    for (int q = 0; q < kTilePairs / 256; ++q) {
+      const int e = q * 256 + tid, r = e >> 6;
+      const float v = value(e, t);
+      summary_row<kTileA>(r < nc && lane < na && live(r, lane) && v == v, v,
+                          r < nc ? g.rows + ((size_t)t * tiles_a + ta) * C + c0 + r : nullptr);
+    }
+  for (int item = tid; item < planes * kTileA; item += 256) {
+    const int t = item >> 6, a = item & 63;
+    if (a >= na) continue;
+    SummarySum sum;
+    for (int r = 0; r < nc; ++r) {
+      const float v = value(r * kTileA + a, t);
+      sum.add(live(r, a) && v == v, v);
+    }
+    g.cols[((size_t)t * tiles_c + tc) * A + a0 + a] = sum.record();
   }
 }
 
@@ -654,6 +797,14 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       continue;
     }
   }
+  if constexpr (Form::summary) {  // the summary form's mask may be null too
+    if (summary_masked(sel...) &&
+        !where_tile_any(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), KIND == 0 ? nT : 1, c0, nc, a0 >> 5, kTileA / 32)) {
+      summary_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTileA, (C + kTileC - 1) / kTileC, c0 / kTileC,
+                        KIND == 0 ? nT : 1);  // (its slots have no other writer)
+      continue;
+    }
+  }
 
   // the tile's mixing rows: contiguous in global memory, padded rows in LDS (the pads are never used)
   for (int idx = tid; idx < na * Mx; idx += blockDim.x) {
@@ -729,6 +880,12 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
                           [&](int r, int a) {
                             return !rank_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
                           });
+    } else if constexpr (Form::summary) {
+      summary_head_tile(sel..., C, A, c0, a0, nc, na, tiles_a, nT,
+                        [&](int e, int t) { return head_vft_eval(VftParams{resA[e], resB[e], resC[e]}, t100[t]); },
+                        [&](int r, int a) {
+                          return !summary_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), nT, r, a, kTileA / 32);
+                        });
     } else {
     store_rows(out, ((int64_t)c0 * A + a0) * nT, (int64_t)A * nT, nc, na * nT, nT, [&](int r, int a, int t) {
       return head_vft_eval(VftParams{resA[r * kTileA + a], resB[r * kTileA + a], resC[r * kTileA + a]}, t100[t]);
@@ -805,6 +962,10 @@ __global__ __launch_bounds__(256) void head_grid_kernel(const float* __restrict_
       rank_mask_head_tile(sel..., C, A, c0, a0, nc, na, 1, [&](int e, int) { return res[e]; }, [&](int r, int a) {
         return !rank_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
       });
+    } else if constexpr (Form::summary) {
+      summary_head_tile(sel..., C, A, c0, a0, nc, na, tiles_a, 1, [&](int e, int) { return res[e]; }, [&](int r, int a) {
+        return !summary_masked(sel...) || where_bit(sel..., sm + grid_lds_floats(KIND, nT, F, Mx), 1, r, a, kTileA / 32);
+      });
     } else {
     store_rows(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, 1, [&](int r, int a, int) { return res[r * kTileA + a]; });
     }
@@ -863,6 +1024,12 @@ inline int ensemble_max_temperatures(int M, int most) {
   const size_t room = (kEnsembleLdsCap - fixed) / sizeof(float) & ~(size_t)3;
   return room < (size_t)most ? (int)room : most;
 }
+// ... and a summary launch: the tile's mask words sit behind the tile's regions (at most `most`)
+inline int ensemble_summary_max_temperatures(int M, int most) {
+  const size_t fixed = sizeof(float) * ensemble_lds_floats(0, M, 0, kHeadMaxDim, kHeadMaxDim) + sizeof(uint32_t) * kWhereTileWords;
+  const size_t room = (kEnsembleLdsCap - fixed) / sizeof(float) & ~(size_t)3;
+  return room < (size_t)most ? (int)room : most;
+}
 inline int ensemble_select_max_temperatures(int M) {
   int nT = kSelectMaxT;
   while (nT > 1 && sizeof(float) * ensemble_lds_floats(0, M, nT, kHeadMaxDim, kHeadMaxDim) +
@@ -878,7 +1045,8 @@ struct EnsembleOut {
 };
 
 // mix_cat (M,C,Mx), mix_an (M,A,Mx), tails (M, ensemble_tail_floats).  The tile, its threads and its forms are
-// head_grid_kernel's (store, GridMask, GridSelect, GridSelectWhere); the mask and the selection use the score.
+// head_grid_kernel's (store, GridMask, GridSelect, GridSelectWhere, GridSummary); the mask, the selection and the summary
+// use the score.
 template <int KIND, int MXR, class... Sel>
 __global__ __launch_bounds__(256) void ensemble_grid_kernel(const float* __restrict__ mix_cat,
                                                             const float* __restrict__ mix_an,
@@ -909,6 +1077,12 @@ __global__ __launch_bounds__(256) void ensemble_grid_kernel(const float* __restr
   const int nc = min(kTileC, C - c0), na = min(kTileA, A - a0);
   if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
     if (!where_tile_any(sel..., lists, planes, c0, nc, a0 >> 5, kTileA / 32)) continue;
+  }
+  if constexpr (Form::summary) {  // the summary form's mask may be null: the same pass, when there is one
+    if (summary_masked(sel...) && !where_tile_any(sel..., lists, planes, c0, nc, a0 >> 5, kTileA / 32)) {
+      summary_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTileA, (C + kTileC - 1) / kTileC, c0 / kTileC, planes);
+      continue;
+    }
   }
 
   for (int m = 0; m < M; ++m) {
@@ -979,6 +1153,9 @@ __global__ __launch_bounds__(256) void ensemble_grid_kernel(const float* __restr
     });
   } else if constexpr (Form::mask) {
     mask_head_tile(sel..., C, c0, a0, nc, na, planes, [&](int e, int t) { return stat(e, t).score; });
+  } else if constexpr (Form::summary) {
+    summary_head_tile(sel..., C, A, c0, a0, nc, na, tiles_a, planes, [&](int e, int t) { return stat(e, t).score; },
+                      [&](int r, int a) { return !summary_masked(sel...) || where_bit(sel..., lists, planes, r, a, kTileA / 32); });
   } else {
     const int64_t first = ((int64_t)c0 * A + a0) * planes, pitch = (int64_t)A * planes;
     if (out.mean)
@@ -1033,6 +1210,25 @@ __device__ __forceinline__ void partners_transfer_tile(const GridPartners& g, co
     for (int rr = 0; rr < nc; ++rr)
       best.offer(partners_entry(g, live(rr, tid), res[rr * kTgTileA + tid], (uint32_t)(c0 + rr) * (uint32_t)A + (uint32_t)(a0 + tid)));
     best.store(g.cols + ((size_t)tc * A + a0 + tid) * g.m, g.m);
+  }
+}
+
+// The transfer grid's tile as summary records: a 32-lane half of a wave is one tile row of `res`; then one thread per
+// tile column walks its rows in ascending order.
+template <class Live>
+__device__ __forceinline__ void summary_transfer_tile(const GridSummary& g, const float* res, int C, int A, int c0, int a0,
+                                                      int nc, int na, int tiles_a, Live live) {
+  const int tid = threadIdx.x, r = tid >> 5, p = tid & 31;
+  const int ta = a0 / kTgTileA, tc = c0 / kTgTileC;
+  const float v = res[tid];
+  summary_row<kTgTileA>(r < nc && p < na && live(r, p) && v == v, v, r < nc ? g.rows + (size_t)ta * C + c0 + r : nullptr);
+  if (tid < na) {
+    SummarySum sum;
+    for (int rr = 0; rr < nc; ++rr) {
+      const float w = res[rr * kTgTileA + tid];
+      sum.add(live(rr, tid) && w == w, w);
+    }
+    g.cols[(size_t)tc * A + a0 + tid] = sum.record();
   }
 }
 
@@ -1147,6 +1343,12 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
   if constexpr (Form::rank_count || Form::rank_mask) {  // the rank forms' mask may be null: the same pass, when there is one
     if (rank_masked(sel...) && !where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) {
       rank_skip_tile(sel..., C, c0, nc, a0 >> 5, kTgTileA / 32, 1);  // (its words have no other writer)
+      continue;
+    }
+  }
+  if constexpr (Form::summary) {  // the summary form's mask may be null too
+    if (summary_masked(sel...) && !where_tile_any(sel..., sm + kTgLdsFloats, 1, c0, nc, a0 >> 5, kTgTileA / 32)) {
+      summary_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTgTileA, (C + kTgTileC - 1) / kTgTileC, c0 / kTgTileC, 1);
       continue;
     }
   }
@@ -1270,6 +1472,10 @@ __global__ __launch_bounds__(256) void transfer_grid_kernel(const float* __restr
     rank_transfer_tile(sel..., sm + kTgLdsFloats, res, C, A, c0, a0, nc, na, [&](int r, int a) {
       return !rank_masked(sel...) || where_bit(sel..., sm + kTgLdsFloats, 1, r, a, kTgTileA / 32);
     });
+  } else if constexpr (Form::summary) {
+    summary_transfer_tile(sel..., res, C, A, c0, a0, nc, na, tiles_a, [&](int r, int a) {
+      return !summary_masked(sel...) || where_bit(sel..., sm + kTgLdsFloats, 1, r, a, kTgTileA / 32);
+    });
   } else {
   store_spans(out, (int64_t)c0 * A + a0, (int64_t)A, nc, na, res, kTgTileA);
   }
@@ -1350,5 +1556,7 @@ void launch_grid_kernel(const GridOperands& g, unsigned groups, size_t extra_lds
   else
     launch_grid_family<1>(g, groups, extra_lds, GridOut{}, sel);
 }
+// the transfer MC grid's kernel lives in transfer_mc_grid.hip: the tile launch of its summary form
+void launch_transfer_mc_grid_summary_tiles(const GridOperands& g, unsigned groups, const GridSummary& sel);
 
 }  // namespace impnn

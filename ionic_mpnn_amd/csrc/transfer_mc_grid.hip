@@ -10,8 +10,8 @@
 // its multipliers, runs Dense 64 and Dense 1 exactly as transfer_grid_kernel does, and leaves its value for the tile's
 // 256 pairs in LDS [S][256].  After the last sample thread tid folds pair tid's S values, ascending, into ensemble_stat's
 // statistic generalised from 8 to S (mean, population deviation, score = fmaf(kappa, std, mean)) and hands one value
-// per pair to the form, as transfer_grid_kernel's res[] does: the stores, the mask words (GridMask) or the running top k
-// (GridSelect / GridSelectWhere), both on the score.  By MFMA count a wave spends 1024 + 256 S where the deterministic
+// per pair to the form, as transfer_grid_kernel's res[] does: the stores, the mask words (GridMask), the running top k
+// (GridSelect / GridSelectWhere) or the per-ion records (GridSummary), all on the score.  By MFMA count a wave spends 1024 + 256 S where the deterministic
 // grid spends 1280.
 //
 // The multipliers are an operand (S,128); no generator runs here.  They sit in LDS beside the sample array: a lane
@@ -82,6 +82,12 @@ __global__ __launch_bounds__(256) void transfer_mc_grid_kernel(const float* __re
   const int nc = min(kTgTileC, C - c0), na = min(kTgTileA, A - a0);
   if constexpr (Form::where) {  // a tile without a set bit: on to the next one, before any load
     if (!where_tile_any(sel..., lists, 1, c0, nc, a0 >> 5, kTgTileA / 32)) continue;
+  }
+  if constexpr (Form::summary) {  // the summary form's mask may be null: the same pass, when there is one
+    if (summary_masked(sel...) && !where_tile_any(sel..., lists, 1, c0, nc, a0 >> 5, kTgTileA / 32)) {
+      summary_skip_tile(sel..., C, A, c0, a0, nc, na, tiles_a, a0 / kTgTileA, (C + kTgTileC - 1) / kTgTileC, c0 / kTgTileC, 1);
+      continue;
+    }
   }
 
   // the tile's u rows; the rows of a ragged tile's padding pairs are zero (computed, not stored)
@@ -226,6 +232,12 @@ __global__ __launch_bounds__(256) void transfer_mc_grid_kernel(const float* __re
     const int r = tid >> 5;
     uint32_t* word = mask_word(sel..., c0 + r, a0 >> 5);
     mask_store_ballot(r < nc && p < na && mask_passes(sel..., score), r < nc ? word : nullptr, r < nc ? word : nullptr);
+  } else if constexpr (Form::summary) {
+    res[tid] = score;
+    __syncthreads();
+    summary_transfer_tile(sel..., res, C, A, c0, a0, nc, na, tiles_a, [&](int r, int a) {
+      return !summary_masked(sel...) || where_bit(sel..., lists, 1, r, a, kTgTileA / 32);
+    });
   } else {
     const int64_t first = (int64_t)c0 * A + a0;
     float* const outs[3] = {out.mean, out.std, out.score};
@@ -272,6 +284,11 @@ int launch_transfer_mc_grid_mask(const GridMaskCall& c) {
   if (int rc = grid_tiles_fit("transfer_mc_grid_mask", tiles)) return rc;
   launch_mc(c.g, (unsigned)tiles.count(), 0, McOut{}, GridMask{c.words, c.lo, c.hi, mask_row_words(c.g.A)});
   return check_launch("transfer_mc_grid_mask");
+}
+
+// the tile launch of a summary call (grid_summary.hip merges the partial records): the mask words behind the samples
+void launch_transfer_mc_grid_summary_tiles(const GridOperands& g, unsigned groups, const GridSummary& sel) {
+  launch_mc(g, groups, sizeof(uint32_t) * kWhereTileWords, McOut{}, sel);
 }
 
 int launch_transfer_mc_grid_topk(const GridTopkCall& c) {

@@ -138,6 +138,15 @@ class ModelEnsemble:
             raise ValueError("k must be >= 1")
         return _EnsembleScreen(self, cations, anions, T, where, batch_size, kp).top_k(k, largest, max_pairs_per_launch)
 
+    def screen_ion_summary(self, cations, anions, temperatures=None, where=None, kappa=0.0, max_pairs_per_launch=None,
+                           batch_size=4096):
+        """Per-ion statistics of the score, reduced on the GPU (impnn_deep_ensemble_grid_summary): what
+        ``data.grid_ion_summary(score, where)`` returns for the score of ``predict_grid(..., kappa=kappa)``, bit for
+        bit, without the grid -> ``data.IonSummary``.  Arguments, tiling and the carried anion records as
+        ``MPNNModel.screen_ion_summary``."""
+        T, kp = self._request("screen_ion_summary", cations, anions, temperatures, where, max_pairs_per_launch, kappa)
+        return _EnsembleScreen(self, cations, anions, T, where, batch_size, kp).ion_summary(max_pairs_per_launch)
+
     def _no_domain(self, *args, **kwargs):
         """The applicability domain is a distance in one model's latent space; the members' spaces differ."""
         raise ValueError("an ensemble has no latent space of its own: fit and screen the applicability domain with one "

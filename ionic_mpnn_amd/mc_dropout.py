@@ -10,7 +10,8 @@ grid - the "fixed set of masks" form of MC dropout - so a pair's statistic is a 
 the weights and the table: it does not depend on the tile, the launch, the host tiling or the grid's size, a screen's
 ranking is reproducible, and ``predict_pairs`` returns the grid's bits.
 
-Not built for this form: each ion's best partners, the rank cut, Pareto objectives; dropout inside the encoder's
+Not built for this form: each ion's best partners, the rank cut, Pareto objectives (per-ion statistics are:
+``screen_ion_summary``); dropout inside the encoder's
 GatedUpdates stays off (the samples share one encoding of every ion)."""
 from __future__ import annotations
 
@@ -132,6 +133,14 @@ class McDropout:
         if k < 1:
             raise ValueError("k must be >= 1")
         return _McScreen(self, cations, anions, where, batch_size, kp).top_k(k, largest, max_pairs_per_launch)
+
+    def screen_ion_summary(self, cations, anions, where=None, kappa=0.0, max_pairs_per_launch=None, batch_size=4096):
+        """Per-ion statistics of the score, reduced on the GPU (impnn_transfer_mc_grid_summary): what
+        ``data.grid_ion_summary(score, where, ops.SUMMARY_BLOCKS[3])`` returns for the score of ``predict_grid(...,
+        kappa=kappa)``, bit for bit, without the grid -> ``data.IonSummary``.  Arguments, tiling and the carried anion
+        records as ``MPNNModel.screen_ion_summary``."""
+        kp = self._request("screen_ion_summary", cations, anions, where, max_pairs_per_launch, kappa)
+        return _McScreen(self, cations, anions, where, batch_size, kp).ion_summary(max_pairs_per_launch)
 
     def predict_pairs(self, cations, anions, cation_index, anion_index, batch_size=4096):
         """Mean and population standard deviation of listed pairs - pair p is (cations[cation_index[p]],

@@ -41,6 +41,7 @@ GRID_MAX_TEMPERATURES = 4096   # temperatures per impnn_head_grid launch (includ
 GRID_GATHER_PAIRS = 1 << 18    # pairs per tile of the gathered path (widths above 64, the transfer head)
 SCREEN_MAX_K = ops.SELECT_MAX_K       # screen_top_k: the largest k the selecting kernels keep (above it: the fallback)
 SCREEN_MAX_PAIRS = (1 << 32) - 1      # pairs of one selecting launch: a pair's index has 32 bits
+SUMMARY_RANGE = 16                    # screen_ion_summary cuts the cation axis at its multiples: every summary block's size divides it
 
 
 def _ion_numpy(ion, what):
@@ -211,6 +212,44 @@ class _Screen:
         if not s.visc:
             values, cation, anion = values[0], cation[0], anion[0]
         return data.TopK(values, cation, anion)
+
+    def ion_summary(self, max_pairs_per_launch):
+        """The screen's per-ion statistics as a ``data.IonSummary`` (``MPNNModel.screen_ion_summary``): the summary
+        launches' records, or without a covering kernel those of the materialised tiles, over ranges of cations that end
+        at multiples of SUMMARY_RANGE, the anion records carried from one range into the next."""
+        s = self
+        family = s.operands.family if s.operands is not None else (1 if s.model.kind == "transfer" else 0)
+        blocks = ops.SUMMARY_BLOCKS[family]
+        t_step = s.grid_max_t
+        if max_pairs_per_launch is None and s.operands is None:
+            max_pairs_per_launch = s.default_pairs(False)
+        elif max_pairs_per_launch is None:  # a launch's workspace: one 32-byte record per plane, tile row and tile column
+            max_pairs_per_launch = s.default_pairs(True, 32 * min(s.planes, t_step) * (1.0 / blocks[0] + 1.0 / blocks[1]))
+        step = max(SUMMARY_RANGE, int(max_pairs_per_launch) // max(s.A, 1) // SUMMARY_RANGE * SUMMARY_RANGE)
+        parts = []  # per range of temperature rows: the records of all cations
+        for t0 in range(0, s.planes, t_step) if s.C > 0 and s.A > 0 else ():
+            t1 = min(s.planes, t0 + t_step)
+            cat, an = [], None
+            for lo in range(0, s.C, step):
+                hi = min(s.C, lo + step)
+                wh = s.where.rows(lo, hi) if s.where is not None else None
+                if s.operands is not None:
+                    got = ops.grid_summary(s.operands.rows(lo, hi).temperatures(t0, t1),
+                                           where=wh.words if wh is not None else None, carry=an)
+                else:
+                    tile = s.grid_tile(lo, hi, t0, t1, None).cpu().numpy()
+                    got = data.grid_ion_records(tile, wh, blocks, carry=an)
+                cat.append(got[:3])
+                an = got[3:]
+            host = lambda x: x.cpu().numpy() if isinstance(x, torch.Tensor) else x
+            parts.append([np.concatenate([host(c[f]) for c in cat], axis=1) for f in range(3)] + [host(x) for x in an])
+        if parts:
+            rec = [np.concatenate([p[f] for p in parts], axis=0) for f in range(6)]
+        else:  # an empty grid: no pair competes
+            rec = [x for n in (s.C, s.A) for x in (np.zeros((s.planes, n), np.uint32), np.zeros((s.planes, n, 2)),
+                                                   np.full((s.planes, n, 2), data.QUIET_NAN, np.float32))]
+        rec[0], rec[3] = rec[0].view(np.uint32), rec[3].view(np.uint32)  # (the device tensors are int32)
+        return data.IonSummary.from_records(rec, planes=s.visc)
 
     def grid_tile(self, lo, hi, t0, t1, operands):
         """The tile (lo, hi, t0, t1, operands) of ``tiles``, materialised on the device: (hi - lo, A[, t1 - t0])."""
@@ -1816,6 +1855,29 @@ class MPNNModel:
         if not s.visc:
             by_cation, by_anion = data.Partners(cat_v[0], cat_p[0]), data.Partners(an_v[0], an_p[0])
         return data.BestPartners(by_cation, by_anion)
+
+    def screen_ion_summary(self, cations, anions, temperatures=None, where=None, max_pairs_per_launch=None,
+                           batch_size=4096):
+        """The main-effects view of a screen, reduced on the GPU: for every cation over its anions, for every anion over
+        its cations and for the whole plane, how many pairs compete and the mean, the population standard deviation,
+        the least and the greatest prediction - what ``data.grid_ion_summary(self.predict_grid(...), where,
+        ops.SUMMARY_BLOCKS[family])`` returns, bit for bit, without the grid.  "What does this cation do on average over
+        the anions that may compete, how much does that depend on the partner, and what are its best and worst cases?"
+        ``encode_ions``, the per-ion halves and the argument rules are ``screen_best_partners``'s; the summary kernels
+        (impnn_head_grid_summary, impnn_transfer_head_grid_summary) evaluate every pair with the grid kernels'
+        arithmetic and reduce both axes in one launch, in double, in one stated order (``data.grid_ion_records``).
+        -> ``data.IonSummary(by_cation, by_anion, overall)`` of ``data.IonStats(count, mean, std, min, max)``: numpy
+        int64 / float32 of shape (nT,C), (nT,A), (nT,) for viscosity - a row per temperature - and (C,), (A,), scalars
+        otherwise; ``IonStats.order`` ranks the ions.  A pair competes when its ``where`` bit is set and its prediction
+        is not NaN; an ion without a competing pair has count 0 and NaN statistics.
+        The cation axis is tiled on the host at multiples of 16 only (``max_pairs_per_launch`` is rounded down to that,
+        the least range is 16 cations; the default bounds a launch's workspace) and the anion records are carried from
+        one range's launch into the next: the result's bits do not depend on the tiling.  Widths the head kernels do not
+        cover and the transfer model with ``grid_head_mode = "gathered"`` apply ``data.grid_ion_records`` to
+        ``predict_grid``'s tiles with the same blocks and the same carried records.
+        ``where``: a 2-D ``data.PairMask`` of shape (C,A), as in ``screen_top_k``; only its pairs compete."""
+        T = self._screen_request("screen_ion_summary", cations, anions, temperatures, where, max_pairs_per_launch)
+        return _Screen(self, cations, anions, T, where, batch_size).ion_summary(max_pairs_per_launch)
 
     def _screen_rank(self, what, cations, anions, temperatures, k, largest, where, batch_size, mask):
         """``screen_rank`` and ``screen_best_mask``: the rank cut of every plane and, with ``mask``, the best-k mask ->

@@ -902,8 +902,8 @@ def head_ion_mix(kind, ion, pooled, head_weights, fp_size, mixing_size):
     return mix
 
 
-# ---- the screening family over a cation x anion grid: the operands are validated once (GridOperands), the five
-# operations (grid_values, grid_topk, grid_partners, grid_rank, grid_mask) take any family's, and the named wrappers
+# ---- the screening family over a cation x anion grid: the operands are validated once (GridOperands), the six
+# operations (grid_values, grid_topk, grid_partners, grid_rank, grid_mask, grid_summary) take any family's, and the named wrappers
 # below them are "build the operands, call the operation"
 class GridOperands:
     """The validated operands of the screening family's launches over one cation x anion grid, built by
@@ -1097,6 +1097,8 @@ def grid_values(g, return_params=False):
 def _grid_entry(g, name):
     """The C entry ``name`` of g's family: impnn_head_grid_<name>, impnn_transfer_head_grid_<name>,
     impnn_ensemble_grid_<name> or impnn_transfer_mc_grid_<name>."""
+    if g.family == 2 and name == "summary":  # (named apart from impnn_ensemble_grid*, the list of that family's first entries)
+        return _lib.load().impnn_deep_ensemble_grid_summary
     return getattr(_lib.load(), ("impnn_head_grid_", "impnn_transfer_head_grid_", "impnn_ensemble_grid_",
                                  "impnn_transfer_mc_grid_")[g.family] + name)
 
@@ -1151,6 +1153,48 @@ def grid_rank(g, k, largest=False, where=None, mask=False, workgroups=0):
                                      *[ptr(o) if o is not None else None for o in out], ptr(ws), nbytes, *g.trail,
                                      workgroups, stream_ptr()))
     return out
+
+
+# (cations, anions) of the blocks the summary's sums run over: the kernel tile of each family (csrc/grid_device.h)
+SUMMARY_BLOCKS = {0: (16, 64), 1: (8, 32), 2: (16, 64), 3: (8, 32)}
+
+
+def grid_summary(g, where=None, carry=None):
+    """Per-ion records of ``g``'s grid without the grid (impnn_*_grid_summary; every family, the ensemble and MC grids
+    on their score) -> (cat_count int32 (P,C) - the uint32 counts' bits -, cat_sums float64 (P,C,2) = (s, q), cat_range
+    float32 (P,C,2) = (lo, hi), an_count (P,A), an_sums (P,A,2), an_range (P,A,2)) on the device, P = max(nT, 1): the
+    bits of ``data.grid_ion_records(grid_values(g), where, SUMMARY_BLOCKS[g.family])``.  ``where``: the (C,W) words of
+    a pair mask, only its pairs compete.  ``carry``: the three anion tensors an earlier range of cations returned (a
+    range ends at a multiple of 16 cations); the anion records continue from them, and the result has the bits of one
+    call over both ranges.  ``data.IonSummary.from_records`` finishes the records."""
+    require_gpu(g.cat, g.an, g.w)
+    if where is not None:
+        where = _mask_words(where, g.C, g.A, g.device)
+    C_, A_, planes, dev = g.C, g.A, max(g.nT, 1), g.device
+    shapes = ((torch.int32, ()), (torch.float64, (2,)), (torch.float32, (2,)))
+    if carry is not None:
+        carry = tuple(carry)
+        require_gpu(*carry)
+        if len(carry) != 3 or any(c.dtype != dt or tuple(c.shape) != (planes, A_, *tail) or c.device != dev
+                                  for c, (dt, tail) in zip(carry, shapes)):
+            raise ValueError(f"carry must be the three anion tensors of an earlier grid_summary over {planes} planes and "
+                             f"{A_} anions on {dev}")
+    with torch.cuda.device(dev):
+        cat = [torch.empty((planes, C_, *tail), dtype=dt, device=dev) for dt, tail in shapes]
+        an = [c.clone().contiguous() for c in carry] if carry is not None else \
+            [torch.empty((planes, A_, *tail), dtype=dt, device=dev) for dt, tail in shapes]
+        if C_ == 0 or A_ == 0:  # zero work touches nothing: no pair competes
+            for count, sums, rng in (cat, an) if carry is None else (cat,):
+                count.zero_(), sums.zero_(), rng.fill_(float("nan"))
+            return (*cat, *an)
+        need = int(_lib.load().impnn_grid_summary_workspace_bytes(g.family, C_, A_, planes))
+        if need == 0:
+            raise ValueError(f"grid_summary: {planes} temperature planes are more than one launch takes; split the sweep")
+        ws = _workspace(dev, need)
+        table = (C.c_void_p * 7)(*[t.data_ptr() for t in (*cat, *an)], ws.data_ptr())
+        check(_grid_entry(g, "summary")(*g.lead, ptr(where) if where is not None else None, int(carry is not None), need,
+                                        table, *g.trail, stream_ptr()))
+    return (*cat, *an)
 
 
 def grid_mask(g, lo, hi):

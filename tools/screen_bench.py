@@ -7,6 +7,7 @@ python tools/screen_bench.py [--quick] [--only viscosity|transfer]      -> one J
 python tools/screen_bench.py --select [--quick] [--only ...]            -> the top-k selection instead (see below)
 python tools/screen_bench.py --select --where FRACTION [--quick]        -> the constrained screen instead (see below)
 python tools/screen_bench.py --partners [--where FRACTION] [--quick]    -> each ion's best partners instead (see below)
+python tools/screen_bench.py --summary [--where FRACTION] [--size N] [--ensemble M | --mc S]  -> per-ion statistics (see below)
 python tools/screen_bench.py --rank [--where FRACTION] [--quick]        -> the best-k pair mask instead (see below)
 python tools/screen_bench.py --ensemble M [--select] [--where FRACTION] [--size N]  -> a deep ensemble instead (see below)
 python tools/screen_bench.py --mc S [--select] [--where FRACTION] [--size N]        -> Monte-Carlo dropout instead (see below)
@@ -39,6 +40,15 @@ two ways must return the same bits.  Plus the partner-selecting launches alone (
 impnn_transfer_head_grid_partners with their merge; a sweep above ops.SELECT_MAX_T temperatures takes several) against
 the materialising launch of the same C x A x nT, 10 calls between two HIP events, three rounds each in turn.  With
 --where F both ways run under one random pair mask of density F.
+
+--summary: the per-ion summary launches (ops.grid_summary: impnn_*_grid_summary's tile launch and merge) on resident
+operands over N x N pairs (--size, default 4096) at one temperature, against the materialised route in the same run:
+ops.grid_values on the same operands, then torch count / sum / sum of squares in float64 and amin / amax along both
+axes.  The head grid and the transfer grid, or with --ensemble M / --mc S that family on its score (kappa = 1).  Five
+alternating rounds after a warm-up of each, HIP events, median and spread; "ratio_exceeds_spread" says whether the
+difference of the medians is larger than the widest spread between rounds.  The counts of the two routes must be equal
+(the sums differ by rounding: torch's order of summation is its own).  Also the workspace per pair.  With --where F both
+run under one block-structured pair mask of density F.
 
 --rank: MPNNModel.screen_best_mask(k = 1 % of the grid, or of the mask's pairs) against predict_grid followed by
 data.grid_best_mask on the host, at the large configurations of --select (all of them with --all-configs): three
@@ -100,7 +110,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-from ionic_mpnn_amd import data, model as MM, ops, synthetic, weights  # noqa: E402
+from ionic_mpnn_amd import _lib, data, model as MM, ops, synthetic, weights  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="the first configuration only")
@@ -108,6 +118,8 @@ ap.add_argument("--only", choices=("viscosity", "transfer"), help="one family of
 ap.add_argument("--select", action="store_true", help="time screen_top_k against predict_grid + host selection")
 ap.add_argument("--partners", action="store_true", help="time screen_best_partners against predict_grid + host reference")
 ap.add_argument("--rank", action="store_true", help="time screen_best_mask against predict_grid + host reference")
+ap.add_argument("--summary", action="store_true", help="time the per-ion summary launches against the materialised grid + torch "
+                "reductions; with --ensemble M or --mc S that family, else the head grid and the transfer grid; --size, --where")
 ap.add_argument("--all-configs", action="store_true", help="with --rank: the small configurations of --select too")
 ap.add_argument("--where", type=float, metavar="FRACTION", help="with --select: the constrained screen at this mask density; "
                 "with --partners, --rank: a random mask of this density")
@@ -125,7 +137,7 @@ ap.add_argument("--reference", type=int, default=7700, metavar="R", help="with -
 ap.add_argument("--size", type=int, default=4096, help="with --ensemble, --mc, --pareto, --domain, --diverse: cations = anions = this many")
 ap.add_argument("--out", default=str(ROOT / "profiles" / "screen_bench.jsonl"))
 args = ap.parse_args()
-other = args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain or args.mc or args.diverse  # another table than the default one
+other = args.summary or args.select or args.partners or args.rank or args.ensemble or args.pareto or args.domain or args.mc or args.diverse  # another table than the default one
 dev = torch.device("cuda:0")
 Va, Vb = synthetic.DEFAULT_VA, synthetic.DEFAULT_VB
 # (name, atom_dim, steps, C, A, nT, predict batch)
@@ -294,7 +306,72 @@ RANK_CONFIGS = ("config2 2048x2048x4", "transfer 1024x1024", "transfer 4096x4096
 
 DOMAIN_TILE_FLOATS = 1 << 28  # the torch path's pairs x R distance tile: 1 GiB of float32
 
-if args.diverse:
+if args.summary:
+    # One temperature, cations = anions = --size.  The fused route: ops.grid_summary on resident operands (the tile
+    # launch and the merge).  The materialised route, in the same run: ops.grid_values on the same operands, then torch
+    # count / sum / sum of squares in float64 and amin / amax along both axes.  Medians of 5 alternating rounds.
+    N = args.size
+    cat, _ = species(N, 1)
+    _, an = species(N, 2)
+    rng = np.random.default_rng(0)
+    T1 = torch.tensor([298.15], dtype=torch.float32)
+    if args.ensemble:
+        from ionic_mpnn_amd import ModelEnsemble
+        from ionic_mpnn_amd.ensemble import _EnsembleScreen
+        members = []
+        for i in range(args.ensemble):
+            m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+            m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1 + i, perturb=True))
+            members.append(m)
+        families = [("ensemble M=%d" % args.ensemble, _EnsembleScreen(ModelEnsemble(members), cat, an, T1, None, 4096, 1.0).operands)]
+    elif args.mc:
+        from ionic_mpnn_amd.mc_dropout import _McScreen
+        families = [("mc S=%d" % args.mc, _McScreen(build_transfer(32, 3).mc_dropout(args.mc), cat, an, None, 4096, 1.0).operands)]
+    else:
+        m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
+        m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
+        families = [("head", MM._Screen(m, cat, an, T1, None, 4096).operands),
+                    ("transfer", MM._Screen(build_transfer(32, 3), cat, an, None, None, 4096).operands)]
+    for name, g in families:
+        blocks = ops.SUMMARY_BLOCKS[g.family]
+        where_b = block_mask(N, N, blocks, args.where, rng) if args.where is not None else None
+        where = data.PairMask.from_bool(where_b, device=dev) if where_b is not None else None
+        live_d = torch.from_numpy(where_b).to(dev) if where_b is not None else None
+        fused = lambda: ops.grid_summary(g, where=where.words if where is not None else None)
+
+        def materialised():
+            v = ops.grid_values(g)
+            v = (v[2] if g.family >= 2 else v).reshape(N, N).double()
+            live = ~torch.isnan(v) if live_d is None else live_d & ~torch.isnan(v)
+            x = torch.where(live, v, torch.zeros_like(v))
+            lo = torch.where(live, v, torch.full_like(v, float("inf")))
+            hi = torch.where(live, v, torch.full_like(v, float("-inf")))
+            return [f(axis) for axis in (1, 0) for f in (lambda a: live.sum(a), lambda a: x.sum(a), lambda a: (x * x).sum(a),
+                                                         lambda a: lo.amin(a), lambda a: hi.amax(a))]
+
+        timed(fused), timed(materialised)
+        t_f, t_m = [], []
+        for _ in range(5):
+            t_m.append(timed(materialised)[0])
+            t_f.append(timed(fused)[0])
+        rec, ref = fused(), materialised()
+        torch.cuda.synchronize()
+        count_ok = bool(torch.equal(rec[0][0].long(), ref[0]) and torch.equal(rec[3][0].long(), ref[5]))
+        mean_diff = float((rec[1][0, :, 0] - ref[1]).abs().max() / ref[1].abs().max().clamp_min(1e-300))
+        need = int(_lib.load().impnn_grid_summary_workspace_bytes(g.family, N, N, 1))
+        spread_ms = max(max(t_f) - min(t_f), max(t_m) - min(t_m))
+        line = {"config": "summary %s %dx%d" % (name, N, N) + ("" if args.where is None else " F=%g" % args.where),
+                "family": g.family, "C": N, "A": N, "nT": 1, "where": args.where,
+                "materialised_plus_torch_reductions_ms": spread(t_m), "grid_summary_ms": spread(t_f),
+                "ratio": round(statistics.median(t_m) / statistics.median(t_f), 2),
+                "ratio_exceeds_spread": bool(abs(statistics.median(t_m) - statistics.median(t_f)) > spread_ms),
+                "workspace_bytes": need, "workspace_bytes_per_pair": need / (N * N),
+                "expected_bytes_per_pair": 32 * (1 / blocks[0] + 1 / blocks[1]),
+                "counts_equal": count_ok, "sum_max_rel_diff": mean_diff}
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+
+elif args.diverse:
     N, R, K = args.size, args.reference, args.diverse
     m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
     m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
