@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib, data, ops
-from .model import MPNNModel, _Screen
+from .model import MPNNModel
+from .screening import _Screen, _screen_request, at_least_one, mask_bounds, score_kappa
 
 ENSEMBLE_KINDS = ("viscosity", "melting_point")
 
@@ -18,7 +19,10 @@ ENSEMBLE_KINDS = ("viscosity", "melting_point")
 class _EnsembleScreen(_Screen):
     """``_Screen`` over an ensemble: ``pc`` / ``pa`` are the members' pooled rows (lists), the operands are the ensemble
     grid's (always covered: ``ModelEnsemble`` refuses members the grid kernels do not cover), a launch takes the
-    temperatures the library reports for this many members, and a materialised tile is the score."""
+    temperatures the library reports for this many members, and a materialised tile is the score; ``values`` assembles
+    the three planes (mean, std, score)."""
+
+    n_values = 3
 
     def __init__(self, ensemble, cations, anions, T, where, batch_size, kappa):
         lib, M = _lib.load(), len(ensemble.models)
@@ -36,8 +40,8 @@ class _EnsembleScreen(_Screen):
     def _operands(self):
         return self.model._grid_operands(self.pc, self.pa, self.T, self.kappa)
 
-    def grid_tile(self, lo, hi, t0, t1, operands):
-        return ops.grid_values(operands)[2]
+    def tile_values(self, lo, hi, t0, t1, operands, extra):
+        return ops.grid_values(operands), None
 
 
 class ModelEnsemble:
@@ -92,10 +96,8 @@ class ModelEnsemble:
         return ops.ensemble_grid_operands(self.kind, torch.stack(cat), torch.stack(an), T, torch.stack(tails), fp, mx, kappa)
 
     def _request(self, what, cations, anions, temperatures, where, max_pairs_per_launch, kappa):
-        kappa = np.float32(kappa)
-        if not np.isfinite(kappa):
-            raise ValueError("kappa must be finite")
-        return self.models[0]._screen_request(what, cations, anions, temperatures, where, max_pairs_per_launch), float(kappa)
+        kappa = score_kappa(kappa)
+        return _screen_request(self.kind, what, cations, anions, temperatures, where, max_pairs_per_launch), kappa
 
     def predict_grid(self, cations, anions, temperatures=None, kappa=None, max_pairs_per_launch=None, batch_size=4096):
         """Mean and population standard deviation of the members' ``predict_grid`` over every cation x anion pair (x
@@ -105,23 +107,14 @@ class ModelEnsemble:
         bits do not depend on the host tiling.  Arguments as ``MPNNModel.predict_grid``."""
         T, kp = self._request("predict_grid", cations, anions, temperatures, None, max_pairs_per_launch,
                               0.0 if kappa is None else kappa)
-        s = _EnsembleScreen(self, cations, anions, T, None, batch_size, kp)
-        out = [np.empty((s.C, s.A, s.nT) if s.visc else (s.C, s.A), np.float32) for _ in range(3)]
-        for lo, hi, t0, t1, g, _ in s.tiles(max_pairs_per_launch, False):
-            for o, tile in zip(out, ops.grid_values(g)):
-                (o[lo:hi, :, t0:t1] if s.visc else o[lo:hi])[...] = tile.cpu().numpy()
-        return tuple(out) if kappa is not None else (out[0], out[1])
+        out = _EnsembleScreen(self, cations, anions, T, None, batch_size, kp).values(max_pairs_per_launch)
+        return out if kappa is not None else out[:2]
 
     def screen_mask(self, cations, anions, temperatures=None, at_least=None, at_most=None, kappa=0.0,
                     max_pairs_per_launch=None, batch_size=4096):
         """``at_least <= score <= at_most`` as a ``data.PairMask``, written on the GPU (impnn_ensemble_grid_mask), for
         the score ``predict_grid(..., kappa=kappa)`` gives.  Arguments as ``MPNNModel.screen_mask``."""
-        if at_least is None and at_most is None:
-            raise ValueError("screen_mask needs a bound: at_least, at_most or both")
-        lo_b = np.float32(-np.inf if at_least is None else at_least)
-        hi_b = np.float32(np.inf if at_most is None else at_most)
-        if np.isnan(lo_b) or np.isnan(hi_b):
-            raise ValueError("a screen_mask bound is NaN")
+        lo_b, hi_b = mask_bounds("screen_mask", at_least, at_most)
         T, kp = self._request("screen_mask", cations, anions, temperatures, None, max_pairs_per_launch, kappa)
         return _EnsembleScreen(self, cations, anions, T, None, batch_size, kp).pair_mask(lo_b, hi_b, max_pairs_per_launch)
 
@@ -133,9 +126,7 @@ class ModelEnsemble:
         (value, cation, anion, NaN last).  Arguments, tiling and the merge as ``MPNNModel.screen_top_k``; read the mean
         and spread of the selected pairs with ``predict_pairs``."""
         T, kp = self._request("screen_top_k", cations, anions, temperatures, where, max_pairs_per_launch, kappa)
-        k = int(k)
-        if k < 1:
-            raise ValueError("k must be >= 1")
+        k = at_least_one("k", k)
         return _EnsembleScreen(self, cations, anions, T, where, batch_size, kp).top_k(k, largest, max_pairs_per_launch)
 
     def screen_ion_summary(self, cations, anions, temperatures=None, where=None, kappa=0.0, max_pairs_per_launch=None,
@@ -159,7 +150,7 @@ class ModelEnsemble:
         anions[anion_index[p]]) - from the members' own ``head`` on gathered pooled rows -> numpy (mean, std) of shape
         (P,nT) for viscosity, (P,) for melting point.  How a caller reads the mean and spread behind the scores of
         ``screen_top_k``.  Not bitwise with the grid (another kernel evaluates the head): within 1e-5 of it."""
-        T = self.models[0]._screen_request("predict_pairs", cations, anions, temperatures, None, None)
+        T = _screen_request(self.kind, "predict_pairs", cations, anions, temperatures, None, None)
         ci = torch.as_tensor(np.asarray(cation_index, dtype=np.int64).reshape(-1), device=self.device)
         ai = torch.as_tensor(np.asarray(anion_index, dtype=np.int64).reshape(-1), device=self.device)
         P, nT = int(ci.numel()), int(T.numel()) if T is not None else 0

@@ -19,12 +19,16 @@ import numpy as np
 import torch
 
 from . import _lib, layers as L, ops
-from .model import MPNNModel, _Screen
+from .model import MPNNModel
+from .screening import _Screen, _screen_request, at_least_one, mask_bounds, score_kappa
 
 
 class _McScreen(_Screen):
     """``_Screen`` over the MC form: the operands are the transfer grid's with the multiplier table and ``kappa`` (always
-    the matrix-core grid: ``McDropout`` refuses a model it does not cover), and a materialised tile is the score."""
+    the matrix-core grid: ``McDropout`` refuses a model it does not cover), and a materialised tile is the score;
+    ``values`` assembles the three planes (mean, std, score) and, for its extra output, the sample planes (S,C,A)."""
+
+    n_values, extra_axis = 3, 1
 
     def __init__(self, mc, cations, anions, where, batch_size, kappa):
         self.mc, self.kappa = mc, kappa
@@ -37,8 +41,12 @@ class _McScreen(_Screen):
         g = self.model._grid_operands(self.pc, self.pa, None, True)
         return ops.transfer_mc_grid_operands(g.cat, g.an, g.w, self.mc.multipliers(), self.kappa)
 
-    def grid_tile(self, lo, hi, t0, t1, operands):
-        return ops.grid_values(operands)[2]
+    def tile_values(self, lo, hi, t0, t1, operands, extra):
+        got = ops.transfer_mc_grid(operands, extra)
+        return got[:3], got[3] if extra else None
+
+    def extra_out(self):
+        return np.empty((self.mc.samples, self.C, self.A), np.float32)
 
 
 class McDropout:
@@ -81,12 +89,9 @@ class McDropout:
         return self._table
 
     def _request(self, what, cations, anions, where, max_pairs_per_launch, kappa):
-        with np.errstate(over="ignore"):
-            kappa = np.float32(kappa)  # as the kernels see it
-        if not np.isfinite(kappa):
-            raise ValueError("kappa must be finite")
-        self.model._screen_request(what, cations, anions, None, where, max_pairs_per_launch)
-        return float(kappa)
+        kappa = score_kappa(kappa)
+        _screen_request(self.model.kind, what, cations, anions, None, where, max_pairs_per_launch)
+        return kappa
 
     def predict_grid(self, cations, anions, kappa=None, return_samples=False, max_pairs_per_launch=None, batch_size=4096):
         """Mean and population standard deviation of the S samples over every cation x anion pair, from one
@@ -96,28 +101,16 @@ class McDropout:
         size.  With dropout rate 0 every sample has the bits of ``MPNNModel.predict_grid``.  Arguments as
         ``MPNNModel.predict_grid``."""
         kp = self._request("predict_grid", cations, anions, None, max_pairs_per_launch, 0.0 if kappa is None else kappa)
-        s = _McScreen(self, cations, anions, None, batch_size, kp)
-        out = [np.empty((s.C, s.A), np.float32) for _ in range(3)]
-        planes = np.empty((self.samples, s.C, s.A), np.float32) if return_samples else None
-        for lo, hi, _, _, g, _ in s.tiles(max_pairs_per_launch, False):
-            got = ops.transfer_mc_grid(g, return_samples)
-            for o, tile in zip(out, got):
-                o[lo:hi] = tile.cpu().numpy()
-            if return_samples:
-                planes[:, lo:hi] = got[3].cpu().numpy()
-        res = tuple(out) if kappa is not None else (out[0], out[1])
-        return (*res, planes) if return_samples else res
+        res = _McScreen(self, cations, anions, None, batch_size, kp).values(max_pairs_per_launch, return_samples)
+        out, planes = res if return_samples else (res, None)
+        out = out if kappa is not None else out[:2]
+        return (*out, planes) if return_samples else out
 
     def screen_mask(self, cations, anions, at_least=None, at_most=None, kappa=0.0, max_pairs_per_launch=None,
                     batch_size=4096):
         """``at_least <= score <= at_most`` as a ``data.PairMask``, written on the GPU (impnn_transfer_mc_grid_mask),
         for the score ``predict_grid(..., kappa=kappa)`` gives.  Arguments as ``MPNNModel.screen_mask``."""
-        if at_least is None and at_most is None:
-            raise ValueError("screen_mask needs a bound: at_least, at_most or both")
-        lo_b = np.float32(-np.inf if at_least is None else at_least)
-        hi_b = np.float32(np.inf if at_most is None else at_most)
-        if np.isnan(lo_b) or np.isnan(hi_b):
-            raise ValueError("a screen_mask bound is NaN")
+        lo_b, hi_b = mask_bounds("screen_mask", at_least, at_most)
         kp = self._request("screen_mask", cations, anions, None, max_pairs_per_launch, kappa)
         return _McScreen(self, cations, anions, None, batch_size, kp).pair_mask(lo_b, hi_b, max_pairs_per_launch)
 
@@ -129,9 +122,7 @@ class McDropout:
         tiling and the merge as ``MPNNModel.screen_top_k``; read the mean and spread of the selected pairs with
         ``predict_pairs``."""
         kp = self._request("screen_top_k", cations, anions, where, max_pairs_per_launch, kappa)
-        k = int(k)
-        if k < 1:
-            raise ValueError("k must be >= 1")
+        k = at_least_one("k", k)
         return _McScreen(self, cations, anions, where, batch_size, kp).top_k(k, largest, max_pairs_per_launch)
 
     def screen_ion_summary(self, cations, anions, where=None, kappa=0.0, max_pairs_per_launch=None, batch_size=4096):

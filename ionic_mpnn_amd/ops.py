@@ -914,7 +914,7 @@ class GridOperands:
     fp_size, mixing_size) for the head family, (fp_size, mixing_size) for the ensemble family, whose rows are
     three-dimensional - (M,C,Mx) and (M,A,Mx), ``members`` = M - and which carries ``kappa`` of its score.  ``lead`` and
     ``trail`` are the arguments every C entry of the family opens and closes with; the operation's own go between.
-    ``rows`` and ``temperatures`` narrow it without validating again (the host tiling of model.py)."""
+    ``rows`` and ``temperatures`` narrow it without validating again (the host tiling of screening.py)."""
     __slots__ = ("family", "kind", "cat", "an", "T", "w", "widths", "kappa", "multipliers")
 
     def __init__(self, family, kind, cat, an, T, w, widths=(), kappa=0.0, multipliers=None):

@@ -13,7 +13,8 @@ import torch
 
 from . import data, ops
 from .ensemble import ModelEnsemble, _EnsembleScreen
-from .model import GRID_OUTPUT_BUDGET, MPNNModel, _Screen
+from .model import MPNNModel
+from .screening import GRID_OUTPUT_BUDGET, _Screen, _screen_request, cation_ranges, score_kappa
 
 MAX_BLOCK_PAIRS = (1 << 31) - 1   # pairs of one row-block of the filter (include/impnn.h)
 
@@ -39,14 +40,11 @@ class Objective:
             self.temperature = None
         if kappa is not None and not self.ensemble:
             raise ValueError("kappa applies to a ModelEnsemble objective only")
-        self.kappa = float(np.float32(0.0 if kappa is None else kappa))
-        if not np.isfinite(self.kappa):
-            raise ValueError("kappa must be finite")
+        self.kappa = score_kappa(0.0 if kappa is None else kappa)
 
     def _request(self, cations, anions, where, max_pairs_per_launch):
-        model = self.model.models[0] if self.ensemble else self.model
         T = None if self.temperature is None else [self.temperature]
-        return model._screen_request("screen_pareto", cations, anions, T, where, max_pairs_per_launch)
+        return _screen_request(self.model.kind, "screen_pareto", cations, anions, T, where, max_pairs_per_launch)
 
     def _screen(self, cations, anions, T, where, batch_size):
         if self.ensemble:
@@ -106,9 +104,8 @@ def screen_pareto(objectives, cations, anions, where=None, max_pairs_per_launch=
     C, A = s1.C, s1.A
     if C == 0 or A == 0:
         return data.ParetoFront(np.empty((0, 2), np.float32), np.empty(0, np.int64), np.empty(0, np.int64), 0)
-    pairs = min(s1.default_pairs(False), s2.default_pairs(False)) if max_pairs_per_launch is None else int(max_pairs_per_launch)
-    step = max(1, min(pairs, MAX_BLOCK_PAIRS) // A)
-    ranges = [(lo, min(C, lo + step)) for lo in range(0, C, step)]
+    pairs = min(s1.default_pairs(False), s2.default_pairs(False)) if max_pairs_per_launch is None else max_pairs_per_launch
+    ranges = list(cation_ranges(C, A, pairs, MAX_BLOCK_PAIRS))
 
     def evaluate():
         for lo, hi in ranges:

@@ -110,7 +110,7 @@ import torch
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-from ionic_mpnn_amd import _lib, data, model as MM, ops, synthetic, weights  # noqa: E402
+from ionic_mpnn_amd import _lib, data, model as MM, ops, screening, synthetic, weights  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--quick", action="store_true", help="the first configuration only")
@@ -330,8 +330,8 @@ if args.summary:
     else:
         m = MM.build_model(Va, Vb, atom_dim=32, num_steps=3, device=dev)
         m.load_weights(weights.init_weights("viscosity", Va, Vb, atom_dim=32, num_steps=3, seed=1, perturb=True))
-        families = [("head", MM._Screen(m, cat, an, T1, None, 4096).operands),
-                    ("transfer", MM._Screen(build_transfer(32, 3), cat, an, None, None, 4096).operands)]
+        families = [("head", screening._Screen(m, cat, an, T1, None, 4096).operands),
+                    ("transfer", screening._Screen(build_transfer(32, 3), cat, an, None, None, 4096).operands)]
     for name, g in families:
         blocks = ops.SUMMARY_BLOCKS[g.family]
         where_b = block_mask(N, N, blocks, args.where, rng) if args.where is not None else None
