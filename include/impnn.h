@@ -1106,6 +1106,25 @@ int impnn_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int32_t tgt_
                              int32_t N, int32_t E, int32_t D, impnn_stream_t stream);
 int impnn_global_sum_pool_bwd(const float* dpooled, const int32_t* atom_ids, float* dh, int32_t B, int32_t N,
                               int32_t D, impnn_stream_t stream);
+/*  The gradient of the LISTED rows of an embedding table, and of no other row (a frozen Embedding with trainable_rows;
+ *  csrc/embed_rows.hip).  For each listed token v = row_list[i], i < n_listed:
+ *      dtable[v,:] = (accumulate ? dtable[v,:] : +0.0) + sum over the r < rows with ids[r] == v of dout[r,:]
+ *  Rows of dtable that the list does not name are NOT written (nor read).  ids == NULL is the identity, rows == vocab
+ *  and row r holds token r: the listed rows of a full (vocab, dim) gradient are moved (or added) into dtable.
+ *  Indices are not trusted: a listed id outside [0, vocab) is skipped, an id the list holds twice counts once, an ids[r]
+ *  outside [0, vocab) is padding.
+ *  The sum has one order, a function of `rows` alone: the rows in chunks of 64, chunk c to wave c mod 8 of the token's
+ *  workgroup, a wave's rows in ascending order from +0.0, then the eight waves' partials in wave order, then the old
+ *  value.  No float atomics: the same call gives the same bits on every run (impnn_embed_gather_bwd does not).
+ *  buffers: a HOST table of one device pointer, [0] = dtable (vocab, dim) float32.  Any dim >= 1, any rows >= 0; ids,
+ *  dout, row_list and dtable 4-byte aligned.
+ *  Checks in order: shape (rows, n_listed, dim >= 0, vocab > 0, accumulate 0 or 1, ids == NULL only with rows == vocab;
+ *  IMPNN_E_BADARG); zero work (n_listed == 0, rows == 0 or dim == 0: IMPNN_OK, nothing touched); null pointers (the
+ *  table and its entry, dout, row_list); 4-byte alignment; n_listed * ceil(dim / 64) < 2^31 (IMPNN_E_UNSUPPORTED).  No
+ *  allocation, no synchronisation, no state. */
+int impnn_embed_rows_bwd(const int32_t* ids, const float* dout, const int32_t* row_list, int32_t n_listed,
+                         const void* const* buffers, int64_t rows, int32_t vocab, int32_t dim, int32_t accumulate,
+                         impnn_stream_t stream);
 int64_t impnn_bmm_message_typed_bwd_workspace_bytes(int32_t B, int32_t E, int32_t Vb);
 /*  impnn_bmm_message_typed (forward) over the same type-sorted edge segments, any D <= 128: A[type] staged in LDS,
  *  one workgroup per <= 64 edges of a type.  Same workspace (and size query) as the backward entry: a sort made here

@@ -154,6 +154,7 @@ SIGNATURES = {
     "impnn_diverse_workspace_bytes": (C.c_int, [i32, i32, i32, C.POINTER(sz)]),
     "impnn_diverse_select": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
     "impnn_embed_gather_bwd": (C.c_int, [vp, vp, vp, i64, i32, i32, vp]),
+    "impnn_embed_rows_bwd": (C.c_int, [vp, vp, vp, i32, PP, i64, i32, i32, i32, vp]),
     "impnn_reduce_scatter_bwd": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, vp]),
     "impnn_global_sum_pool_bwd": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
     "impnn_bmm_message_typed_bwd_workspace_bytes": (i64, [i32, i32, i32]),

@@ -33,6 +33,34 @@ def _lib_call(device, fn, *args):
         check(fn(*args, stream_ptr()))
 
 
+def restrict_rows(table, rows):
+    """Marks an embedding table (a leaf tensor) as row-restricted: its backward nodes then produce the gradient of the
+    listed rows only and +0.0 in every other row (impnn_embed_rows_bwd).  ``rows``: sorted, duplicate-free ids inside
+    the table (layers.Embedding.trainable_rows), or None to clear the mark.  The list becomes an int32 tensor on the
+    table's device that lives until the mark is cleared or replaced, so a captured step may read it on every replay;
+    MPNNModel.compile() sets and clears it.  A tensor without the mark behaves as it always did."""
+    table._impnn_rows = None if rows is None else torch.tensor(list(rows), dtype=torch.int32, device=table.device)
+
+
+def _listed_rows(table):
+    return getattr(table, "_impnn_rows", None)
+
+
+def _listed_rows_grad(table, rows, ids, dout, to_sink=True):
+    """The row-restricted gradient of ``table`` from ``dout`` (one row per id; ids None: dout is a full (V,dim) gradient
+    and row r belongs to token r): added into the table's sink, or (no sink, or ``to_sink`` false) returned as a dense
+    tensor that is +0.0 outside the list.  -> what the node returns for the table.
+    The kernel adds without atomics, so two calls that add into one sink must run in stream order: a model's nodes that
+    do so sit on one stream (MPNNModel._encode_two_streams looks both ions' atoms up ahead of the fork)."""
+    V, dim = table.shape
+    sink = _sink(table) if to_sink else None
+    dtable = sink if sink is not None else torch.zeros(V, dim, dtype=torch.float32, device=dout.device)
+    buffers = (C.c_void_p * 1)(dtable.data_ptr())
+    _lib_call(dout.device, _lib.load().impnn_embed_rows_bwd, None if ids is None else ptr(ids), ptr(dout), ptr(rows),
+              rows.numel(), buffers, V if ids is None else ids.numel(), V, dim, 1 if sink is not None else 0)
+    return None if sink is not None else dtable
+
+
 class EmbedGather(torch.autograd.Function):
     """Embedding lookup (train_viscosity.py:171-172)."""
 
@@ -46,6 +74,9 @@ class EmbedGather(torch.autograd.Function):
     def backward(ctx, dout):
         ids, table = ctx.saved_tensors
         V, dim = table.shape
+        rows = _listed_rows(table)
+        if rows is not None:
+            return None, _listed_rows_grad(table, rows, ids, f32c(dout))
         sink = _sink(table)  # the kernel accumulates (atomics): add straight into the gradient buffer
         dtable = sink if sink is not None else torch.zeros(V, dim, dtype=torch.float32, device=dout.device)
         dout = f32c(dout)
@@ -69,6 +100,18 @@ class BondTypeMatrices(torch.autograd.Function):
         D = W.shape[-1]
         dmats = f32c(dmats)
         sw, st = _sink(W), _sink(bond_table)
+        rows = _listed_rows(bond_table)
+        if rows is not None:
+            # a row-restricted table: the full table gradient goes to a scratch buffer, its listed rows from there
+            # into the sink where the layer's dW goes to its own (K < 64), else into a dense gradient that is +0.0
+            # elsewhere and that autograd adds up, as it does this node's unrestricted dtb: a model keeps one such node
+            # per layer and ion, on two streams, and the row kernel adds into a sink without atomics
+            direct = sw is not None and K < 64  # (the kernel then ADDS into both outputs: the scratch starts at zero)
+            dW = sw if direct else torch.empty_like(W)
+            dtb = torch.zeros_like(bond_table) if direct else torch.empty_like(bond_table)
+            _lib_call(W.device, _lib.load().impnn_bond_type_matrices_bwd, ptr(bond_table), ptr(W), ptr(dmats), ptr(dW),
+                      ptr(dtb), Vb, K, D, 1 if direct else 0)
+            return _listed_rows_grad(bond_table, rows, None, dtb, to_sink=direct), (None if direct else dW)
         if sw is not None and st is not None and K < 64:
             _lib_call(W.device, _lib.load().impnn_bond_type_matrices_bwd, ptr(bond_table), ptr(W), ptr(dmats), ptr(sw),
                       ptr(st), Vb, K, D, 1)
@@ -115,9 +158,19 @@ class BondTypeMatricesAll(torch.autograd.Function):
         # a frozen bond embedding (no gradient asked for): the kernel's table gradient goes to a scratch buffer and
         # the layers' dW still go straight into their sinks
         frozen_table = not ctx.needs_input_grad[0]
-        use_sinks = (st is not None or frozen_table) and all(sk is not None for sk in sinks)
-        dWs = sinks if use_sinks else [torch.empty_like(W) for W in Ws]
-        dtb = st if use_sinks and st is not None else torch.empty_like(bond_table)
+        # a row-restricted table takes the frozen table's path - its full gradient goes to a scratch buffer, which the
+        # adding form of the kernel needs zeroed - and its listed rows go from there to the sink or a dense gradient
+        rows = None if frozen_table else _listed_rows(bond_table)
+        if rows is not None:
+            # (the table's gradient needs every layer's matrices, frozen layers included: a frozen layer's dW goes to a
+            #  scratch buffer as a frozen table's gradient does, so the trained layers keep their sinks)
+            use_sinks = all(sk is not None or not ctx.needs_input_grad[1 + j] for j, sk in enumerate(sinks))
+            dWs = [sk if use_sinks and sk is not None else torch.empty_like(W) for sk, W in zip(sinks, Ws)]
+            dtb = torch.zeros_like(bond_table) if use_sinks else torch.empty_like(bond_table)
+        else:
+            use_sinks = (st is not None or frozen_table) and all(sk is not None for sk in sinks)
+            dWs = sinks if use_sinks else [torch.empty_like(W) for W in Ws]
+            dtb = st if use_sinks and st is not None else torch.empty_like(bond_table)
         n = len(Ws)
         wt = (C.c_void_p * n)(*[W.data_ptr() for W in Ws])
         dt = (C.c_void_p * n)(*[d.data_ptr() for d in dmats])
@@ -127,6 +180,8 @@ class BondTypeMatricesAll(torch.autograd.Function):
         ws = torch.empty(max(wsn, 1), dtype=torch.float32, device=bond_table.device)
         _lib_call(bond_table.device, lib.impnn_bond_type_matrices_multi_bwd_ws, ptr(bond_table), wt, dt, gt, ptr(dtb),
                   n, Vb, K, D, 1 if use_sinks else 0, ptr(ws), wsn)
+        if rows is not None:
+            return (_listed_rows_grad(bond_table, rows, None, dtb), *((None,) * n if use_sinks else dWs))
         if use_sinks:
             return (None,) * (n + 1)
         return (None if frozen_table else dtb, *dWs)

@@ -1713,6 +1713,20 @@ int impnn_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable,
   return launch_embed_gather_bwd(ids, dout, dtable, rows, vocab, dim, as_stream(stream));
 }
 
+int impnn_embed_rows_bwd(const int32_t* ids, const float* dout, const int32_t* row_list, int32_t n_listed,
+                         const void* const* buffers, int64_t rows, int32_t vocab, int32_t dim, int32_t accumulate,
+                         impnn_stream_t stream) {
+  REQUIRE(rows >= 0 && vocab > 0 && dim >= 0 && n_listed >= 0 && (accumulate == 0 || accumulate == 1), "bad shape");
+  REQUIRE(ids || rows == vocab, "ids == NULL is the identity: rows must equal vocab");
+  if (n_listed == 0 || rows == 0 || dim == 0) return IMPNN_OK;
+  REQUIRE(buffers && buffers[0] && dout && row_list, "null pointer");
+  float* dtable = static_cast<float*>(const_cast<void*>(buffers[0]));
+  const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+  REQUIRE(!(misaligned(ids) || misaligned(dout) || misaligned(row_list) || misaligned(dtable)),
+          "ids, dout, row_list and dtable must be 4-byte aligned");
+  return launch_embed_rows_bwd(ids, dout, row_list, n_listed, dtable, rows, vocab, dim, accumulate, as_stream(stream));
+}
+
 int impnn_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int32_t tgt_stride, float* dmessages, int32_t B,
                              int32_t N, int32_t E, int32_t D, impnn_stream_t stream) {
   REQUIRE(B >= 0 && N > 0 && E >= 0 && D > 0 && tgt_stride >= 1, "bad shape");

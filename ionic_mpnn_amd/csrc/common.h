@@ -476,6 +476,9 @@ int launch_bmm_message_typed_bwd(const TypedMessageCall& c);     // a checked ca
 // backward, dropout step, Adam
 int launch_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable, int64_t rows, int vocab, int dim,
                             hipStream_t s);
+// (embed_rows.hip) the listed rows' gradient, in one summation order and without float atomics
+int launch_embed_rows_bwd(const int32_t* ids, const float* dout, const int32_t* row_list, int n_listed, float* dtable,
+                          int64_t rows, int vocab, int dim, int accumulate, hipStream_t s);
 int launch_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int tgt_stride, float* dm, int B, int N, int E,
                               int D, hipStream_t s);
 int launch_global_sum_pool_bwd(const float* dp, const int32_t* ids, float* dh, int B, int N, int D, hipStream_t s);

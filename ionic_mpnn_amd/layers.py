@@ -173,13 +173,43 @@ class EmbeddedLookup:
 
 class Embedding(Layer):
     """keras.layers.Embedding(input_dim, output_dim, mask_zero=False) as used at
-    train_viscosity.py:163-164.  ``lazy=True`` returns an EmbeddedLookup handle."""
+    train_viscosity.py:163-164.  ``lazy=True`` returns an EmbeddedLookup handle.
 
-    def __init__(self, input_dim, output_dim, mask_zero=False, lazy=False, **kwargs):
+    ``trainable_rows``: None, or a sorted duplicate-free sequence of token ids in [0, input_dim).  A model's
+    ``compile()`` reads it like ``trainable``, and only while ``trainable`` is False: the listed rows train, every
+    other row of the table keeps its bits (a trainable layer trains all rows whatever the list says)."""
+
+    def __init__(self, input_dim, output_dim, mask_zero=False, lazy=False, trainable_rows=None, **kwargs):
         super().__init__(**kwargs)
         if mask_zero:
             raise ValueError("the reference uses mask_zero=False; masking is not implemented")
         self.input_dim, self.output_dim, self.mask_zero, self.lazy = int(input_dim), int(output_dim), False, lazy
+        self.trainable_rows = trainable_rows
+
+    @property
+    def trainable_rows(self):
+        return self._trainable_rows
+
+    @trainable_rows.setter
+    def trainable_rows(self, rows):
+        if rows is None:
+            self._trainable_rows = None
+            return
+        if isinstance(rows, (str, bytes)) or not hasattr(rows, "__iter__"):
+            raise ValueError("trainable_rows must be None or a sequence of token ids")
+        ids = []
+        for r in rows:
+            if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)):
+                raise ValueError(f"trainable_rows: {r!r} is not an integer token id")
+            if not 0 <= int(r) < self.input_dim:
+                raise ValueError(f"trainable_rows: id {int(r)} lies outside the vocabulary [0, {self.input_dim})")
+            if ids and int(r) <= ids[-1]:
+                raise ValueError("trainable_rows must be sorted and free of duplicates" if int(r) < ids[-1]
+                                 else f"trainable_rows: id {int(r)} is listed twice")
+            ids.append(int(r))
+        if not ids:
+            raise ValueError("trainable_rows is empty: use None for no rows")
+        self._trainable_rows = tuple(ids)
 
     def build(self, input_shape):
         self.embeddings = self.add_weight((self.input_dim, self.output_dim), "uniform", name="embeddings")
@@ -191,7 +221,8 @@ class Embedding(Layer):
 
     def get_config(self):
         cfg = super().get_config()
-        cfg.update({"input_dim": self.input_dim, "output_dim": self.output_dim, "mask_zero": False})
+        cfg.update({"input_dim": self.input_dim, "output_dim": self.output_dim, "mask_zero": False,
+                    "trainable_rows": None if self.trainable_rows is None else list(self.trainable_rows)})
         return cfg
 
 

@@ -226,6 +226,8 @@ class MPNNModel:
                 **({"head_dropout_rate": self.mp_dropout.rate, "head_dropout_seed": self.mp_dropout.seed}
                    if self.kind == "transfer" else {}),
                 "layer_trainable": {l.name: bool(l.trainable) for l in self.layers},
+                "embedding_trainable_rows": {l.name: (None if l.trainable_rows is None else list(l.trainable_rows))
+                                             for l in (self.atom_emb, self.bond_emb)},
                 "layers": [{"class_name": type(l).__name__, "config": l.get_config()} for l in self.layers]}
 
     @classmethod
@@ -240,6 +242,9 @@ class MPNNModel:
         flags = config.get("layer_trainable") or {}  # (absent in files written before layers could be frozen)
         for lyr in m.layers:
             lyr.trainable = bool(flags.get(lyr.name, True))
+        rows = config.get("embedding_trainable_rows") or {}  # (absent in files written before rows could be listed)
+        for lyr in (m.atom_emb, m.bond_emb):
+            lyr.trainable_rows = rows.get(lyr.name)
         return m
 
     def save_weights(self, path):
@@ -506,19 +511,20 @@ class MPNNModel:
         return ops.Dropout(self.dropout_rate, self.dropout_seed, ops.dropout_layer_word(lid, idist.dropout_rank()), step)
 
     def encode_layered(self, prefix, atom_ids, bond_ids, conn, trace=None, typed=True, type_mats=None,
-                       dropout_step=None, start=0, h0=None):
+                       dropout_step=None, start=0, h0=None, atoms=None):
         """encode() layer at a time (train_viscosity.py:171-187) -> pooled (B,D); type_mats: _all_type_matrices().
         dropout_step: the pass's dropout snapshot (a training pass of a model with dropout_rate > 0), else None.
         ``start=s, h0=h`` (cached frozen steps, data.FrozenStates): the pass resumes at step s from the atom states
         ``h0`` (B,N,D) as they stand after step s-1 - no atom embedding launch, no step below s; every row of ``h0``,
-        padding included, must be finite.  s may not lie above the ion's first trained step."""
+        padding included, must be finite.  s may not lie above the ion's first trained step.
+        ``atoms`` (a pass from step 0): the ion's embedded atoms (B,N,D), which the caller has looked up already."""
         br = self.branches[prefix]
         graph = ops.IonGraph(atom_ids, bond_ids, conn, self.bond_vocab_size)  # the message calls of all layers share it
         s0 = self._first_trained_step(prefix)
         if h0 is None:
             if start != 0:
                 raise ValueError("encode_layered: start > 0 needs the atom states h0 to start from")
-            h = self.atom_emb(atom_ids)
+            h = self.atom_emb(atom_ids) if atoms is None else atoms
         else:
             if not 0 < start < self.num_steps or trace is not None or not typed:
                 raise ValueError(f"encode_layered: a resumed pass starts at a step in 1..{self.num_steps - 1}, typed, "
@@ -682,6 +688,7 @@ class MPNNModel:
         the current stream and read by the side stream are recorded there, so the caching allocator does not reuse
         them before the side stream is done.  ``join_training_streams`` after backward() orders the gradient sinks
         written on the side stream before the optimizer step."""
+        from . import autograd
         cur = torch.cuda.current_stream(self.device)
         side = getattr(self, "_side_stream", None)
         if side is None:
@@ -704,6 +711,11 @@ class MPNNModel:
         kc, ka = ({} if resume is None else dict(zip(("start", "h0"), resume[p])) for p in ("cat", "an"))
         if ka.get("h0") is not None:
             ka["h0"].record_stream(side)
+        elif torch.is_grad_enabled() and autograd._listed_rows(self.atom_emb.embeddings) is not None:
+            # a row-restricted atom table: the row kernel adds into the gradient sink without atomics, so the two ions'
+            # lookups, and with them their backward nodes, stay on ONE stream - the anion's atoms are looked up here
+            ka["atoms"] = self.atom_emb(an[0])
+            ka["atoms"].record_stream(side)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
             pa = self.encode_layered("an", *an, None, type_mats=tm, dropout_step=dropout_step, **ka)
@@ -799,14 +811,29 @@ class MPNNModel:
     # ------------------------------------------------------------------ training (SURVEY.md 8 f4)
     def trainable_variables(self):
         """[(name, tensor)] of the weights whose layer is trainable (``layer.trainable``, all by default), in the
-        fixed order of ``variables()``."""
-        return [(n, w) for n, w, lyr in self._owned_tensors() if lyr.trainable]
+        fixed order of ``variables()``; an embedding whose layer is frozen but lists ``trainable_rows`` is among them
+        (its listed rows train)."""
+        return [(n, w) for n, w, lyr in self._owned_tensors()
+                if lyr.trainable or getattr(lyr, "trainable_rows", None) is not None]
+
+    def train_unseen_tokens(self, base_inputs, new_inputs):
+        """Lists, as both embeddings' ``trainable_rows``, the tokens ``new_inputs`` uses and ``base_inputs`` (what the
+        base model was trained on) never does: data.unseen_tokens, which is returned.  An empty list sets None.  Counts
+        from the next ``compile()``, and only for an embedding whose layer is frozen."""
+        from . import data
+        unseen = data.unseen_tokens(base_inputs, new_inputs, self.atom_vocab_size, self.bond_vocab_size)
+        self.atom_emb.trainable_rows = [int(v) for v in unseen.atom] or None
+        self.bond_emb.trainable_rows = [int(v) for v in unseen.bond] or None
+        return unseen
 
     def compile(self, optimizer=None, loss="mse", metrics=None, weighted_metrics=None):
         """model.compile(optimizer=Adam(1e-3, clipnorm=1.0), loss="mse") (train_viscosity.py:227-230) or
         loss=Huber(delta=1.0) / "huber" (train_melting_point_transfer.py:193-196).  Reads every ``layer.trainable``
         as Keras does: the optimizer (a fresh state per compile) holds the trainable variables only, the frozen ones
         ask for no gradient and no training step changes them; a flag changed later counts from the next compile.
+        A frozen Embedding's ``trainable_rows`` are read the same way: the table asks for a gradient, the backward
+        kernels hand the optimizer the listed rows' gradient and +0.0 everywhere else (autograd.restrict_rows), so
+        every other row keeps its bits; the table counts as training for ``frozen_prefix()`` and the caches.
         ``metrics`` / ``weighted_metrics``: names ("mae", "mse", "rmse", "bias", "max_error", "r2") or train.Metric
         objects.  ``metrics`` ignore ``sample_weight`` and are logged as ``<name>``, ``weighted_metrics`` use it and are
         logged as ``weighted_<name>`` (``val_`` in front for the validation set); fit and evaluate add them up on the
@@ -827,6 +854,9 @@ class MPNNModel:
             t.requires_grad_(n in names)
             if n not in names:
                 t.grad = None
+        from . import autograd
+        for lyr in (self.atom_emb, self.bond_emb):  # (ahead of optimizer.build: a restricted table does not decay)
+            autograd.restrict_rows(lyr.embeddings, None if lyr.trainable else lyr.trainable_rows)
         if self.frozen_prefix() != before:
             self._frozen_prefix_epoch += 1
         if self.kind == "transfer":

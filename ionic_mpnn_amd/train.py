@@ -261,7 +261,11 @@ class Adam:
         """variables: list of leaf tensors on one GPU.  Gradients live in ONE flat buffer (views become the
         variables' .grad), so the data-parallel average is a single collective and the kernel's pointer table
         stays valid for the whole run (also inside a captured hipGraph).  ``names``: the variables' names, which
-        ``exclude_from_weight_decay`` matches."""
+        ``exclude_from_weight_decay`` matches.
+        A row-restricted embedding table (autograd.restrict_rows: a frozen Embedding with ``trainable_rows``) never
+        decays, whatever ``exclude_from_weight_decay`` says: decay would move the rows that are to keep their bits.
+        Nothing else about it is special - its unlisted rows arrive with a gradient of +0.0, which leaves m, v and the
+        weight as they are."""
         variables = list(variables)
         if self._no_decay and self.weight_decay is not None and names is None:
             raise ValueError("exclude_from_weight_decay needs the variables' names: build(variables, names=[...])")
@@ -289,8 +293,9 @@ class Adam:
             names = [""] * len(variables) if names is None else list(names)
             if len(names) != len(variables):
                 raise ValueError("names must have one entry per variable")
-            self._decay_flags = torch.tensor([int(not any(s in n for s in self._no_decay)) for n in names],
-                                             dtype=torch.int32, device=dev)
+            self._decay_flags = torch.tensor([int(not any(s in n for s in self._no_decay)
+                                                  and getattr(var, "_impnn_rows", None) is None)
+                                              for n, var in zip(names, variables)], dtype=torch.int32, device=dev)
         if self.global_clipnorm is not None:
             need = int(_lib.load().impnn_adam_step_scheduled_workspace_floats(len(variables)))
             self._norm_ws = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)

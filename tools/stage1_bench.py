@@ -4,8 +4,13 @@ beside ``cache_frozen_encoder=True`` (every distinct ion encoded once, the head'
 in one process; medians of --rounds runs with the spread.  Synthetic explicit-hydrogen graphs at the reference's padded
 shape N = 160 / E = 640; --samples samples drawn from --cations + --anions distinct ions (default 2048 over 256 + 64:
 6.4 samples per distinct ion, the repeat rate of a melting-point set of a few thousand salts over a few hundred ions).
+--only embeddings (README.md, "Training the unseen tokens"): what it costs to train embedding rows in stage 1 - the
+captured step three ways, alternating: the head alone over cached encodings, both embeddings fully trainable (the
+whole layered step with an encoder backward), and both embeddings frozen with a sixth of the tokens the set uses listed
+as ``trainable_rows``.
 Reads nothing outside the repository.  One JSON line per measurement.
-    python tools/stage1_bench.py [--batch 32] [--rounds 5] [--iters 300] [--epochs 10] [--out FILE]"""
+    python tools/stage1_bench.py [--batch 32] [--rounds 5] [--iters 300] [--epochs 10] [--only all|stage1|embeddings]
+                                 [--out FILE]"""
 import argparse
 import json
 import sys
@@ -17,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from ionic_mpnn_amd import _lib, model, synthetic, train, weights  # noqa: E402
+from ionic_mpnn_amd import _lib, data, model, synthetic, train, weights  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=32)
@@ -31,6 +36,7 @@ ap.add_argument("--max-edges", type=int, default=640)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=300, help="captured steps per timed window")
 ap.add_argument("--epochs", type=int, default=10, help="timed epochs per fit (one more runs first and is reported apart)")
+ap.add_argument("--only", choices=("all", "stage1", "embeddings"), default="all")
 ap.add_argument("--out")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -46,7 +52,9 @@ if not torch.cuda.is_available():
     sys.exit(f"stage1_bench needs a GPU: a timing without one says nothing ({n} samples of shape {shape} were made)")
 
 
-def stage1_model():
+def stage1_model(embeddings=None):
+    """embeddings: None (frozen: stage 1 as the reference has it), "trainable" (both layers train every row) or "rows"
+    (both frozen, every sixth token the set uses listed as trainable_rows)."""
     with tempfile.TemporaryDirectory() as tmp:
         path = str(Path(tmp) / "viscosity_final.keras")
         v = model.build_model(synthetic.DEFAULT_VA, synthetic.DEFAULT_VB, atom_dim=D, num_steps=S, device=dev)
@@ -55,6 +63,12 @@ def stage1_model():
         m = model.build_transfer_model(path, device=dev, dropout_seed=7)
     for layer in m.layers:
         layer.trainable = layer.name.startswith("mp_") or layer.name == "melting_point"
+    if embeddings == "trainable":
+        m.atom_emb.trainable = m.bond_emb.trainable = True
+    elif embeddings == "rows":
+        use = data.token_usage(x, synthetic.DEFAULT_VA, synthetic.DEFAULT_VB)
+        sixth = lambda counts: [int(v) for v in np.flatnonzero(counts[1:] > 0)[::6] + 1]
+        m.atom_emb.trainable_rows, m.bond_emb.trainable_rows = sixth(use.atom), sixth(use.bond)
     return m.compile(train.Adam(1e-3), loss=train.Huber(delta=1.0))
 
 
@@ -74,6 +88,31 @@ def library_calls(fn):
     return names
 
 
+def timed_rounds(steps):
+    """{name: [ms per step, one value per round]} of {name: (GraphedTrainStep, its resident source)}, the contenders
+    alternating inside every round; round 0 warms up and is dropped."""
+    times = {name: [] for name in steps}
+    for r in range(a.rounds + 1):
+        for name, (step, src) in steps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(a.iters):
+                step.step_on_rows(src, y_dev, rows[i % len(rows)])
+            torch.cuda.synchronize()
+            if r:
+                times[name].append((time.perf_counter() - t0) / a.iters * 1e3)
+    return times
+
+
+def finish():
+    for ln in lines:
+        print(json.dumps(ln), flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            for ln in lines:
+                f.write(json.dumps(ln) + "\n")
+
+
 lines = []
 common = {"batch": B, "shape": shape, "atom_dim": D, "mp_steps": S, "samples": n, "distinct_cations": len(set(ci)),
           "distinct_anions": len(set(ai)), "samples_per_distinct_ion": round(n / (len(set(ci)) + len(set(ai))), 2)}
@@ -89,25 +128,37 @@ encode_ms = (time.perf_counter() - t0) * 1e3
 rows = [torch.from_numpy(rng.integers(0, n, B)).to(dev) for _ in range(16)]
 calls = {"plain": library_calls(lambda: plain.train_on_batch({k: v[rows[0]] for k, v in xd.items()}, y_dev[rows[0]])),
          "cached": library_calls(lambda: cached.train_on_encoded_batch(enc, rows[0], y_dev[rows[0]]))}
-steps = {"plain": (train.GraphedTrainStep(plain, {k: v[rows[0]] for k, v in xd.items()}, y[rows[0].cpu().numpy()],
-                                          resident=(xd, y_dev)), xd),
-         "cached": (train.GraphedTrainStep(cached, rows[0], y[rows[0].cpu().numpy()], resident=(enc, y_dev)), enc)}
-times = {name: [] for name in steps}
-for r in range(a.rounds + 1):                       # round 0 warms up and is dropped
-    for name, (step, src) in steps.items():         # alternating: every round times every contender once
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(a.iters):
-            step.step_on_rows(src, y_dev, rows[i % len(rows)])
-        torch.cuda.synchronize()
-        if r:
-            times[name].append((time.perf_counter() - t0) / a.iters * 1e3)
-for name, ts in times.items():
-    lines.append({"what": "captured step", "path": name, **common, "ms_median": float(np.median(ts)), "ms_min": min(ts),
-                  "ms_max": max(ts), "ms_all": [round(t, 4) for t in ts], "library_calls_per_eager_step": len(calls[name]),
-                  "library_calls": calls[name]})
-lines.append({"what": "encode every distinct ion once", "path": "cached", **common, "ms": round(encode_ms, 3)})
-del steps, plain, cached
+batch0 = ({k: v[rows[0]] for k, v in xd.items()}, y[rows[0].cpu().numpy()])
+if a.only != "embeddings":
+    steps = {"plain": (train.GraphedTrainStep(plain, *batch0, resident=(xd, y_dev)), xd),
+             "cached": (train.GraphedTrainStep(cached, rows[0], batch0[1], resident=(enc, y_dev)), enc)}
+    for name, ts in timed_rounds(steps).items():
+        lines.append({"what": "captured step", "path": name, **common, "ms_median": float(np.median(ts)), "ms_min": min(ts),
+                      "ms_max": max(ts), "ms_all": [round(t, 4) for t in ts],
+                      "library_calls_per_eager_step": len(calls[name]), "library_calls": calls[name]})
+    lines.append({"what": "encode every distinct ion once", "path": "cached", **common, "ms": round(encode_ms, 3)})
+    del steps
+
+# ---- training embedding rows in stage 1: the head over cached encodings, both embeddings trainable, listed rows only
+if a.only != "stage1":
+    full, listed = stage1_model("trainable"), stage1_model("rows")
+    n_rows = {"atom": len(listed.atom_emb.trainable_rows), "bond": len(listed.bond_emb.trainable_rows)}
+    step_of = lambda m: m.train_on_batch({k: v[rows[0]] for k, v in xd.items()}, y_dev[rows[0]])
+    calls = {"head only, cached encodings": calls["cached"], "embeddings trainable": library_calls(lambda: step_of(full)),
+             "rows restricted": library_calls(lambda: step_of(listed))}
+    steps = {"head only, cached encodings": (train.GraphedTrainStep(cached, rows[0], batch0[1], resident=(enc, y_dev)), enc),
+             "embeddings trainable": (train.GraphedTrainStep(full, *batch0, resident=(xd, y_dev)), xd),
+             "rows restricted": (train.GraphedTrainStep(listed, *batch0, resident=(xd, y_dev)), xd)}
+    for name, ts in timed_rounds(steps).items():
+        lines.append({"what": "captured step, embedding rows", "path": name, **common, "listed_rows": n_rows,
+                      "ms_median": float(np.median(ts)), "ms_min": min(ts), "ms_max": max(ts),
+                      "ms_all": [round(t, 4) for t in ts], "library_calls_per_eager_step": len(calls[name]),
+                      "library_calls": calls[name]})
+    del steps, full, listed
+del plain, cached
+if a.only == "embeddings":
+    finish()
+    sys.exit(0)
 
 
 # ---- a whole epoch of fit: n / batch steps and the host work around them
@@ -139,9 +190,4 @@ for name in models:
                   "ms_median": float(np.median(later[name])), "ms_min": min(later[name]), "ms_max": max(later[name]),
                   "first_epoch_ms_median": float(np.median(first[name])),
                   "note": "the first epoch holds the capture of the step and, cached, the encoding of every distinct ion"})
-for ln in lines:
-    print(json.dumps(ln), flush=True)
-if a.out:
-    with open(a.out, "a") as f:
-        for ln in lines:
-            f.write(json.dumps(ln) + "\n")
+finish()
