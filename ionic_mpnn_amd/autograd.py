@@ -1,6 +1,6 @@
 """Autograd nodes of the layer-at-a-time path: each forward is the libimpnn entry of
-the reference layer, each backward the matching ``impnn_*_bwd`` entry (csrc/train_kernels.hip; the message
-adjoint and its edge sort: csrc/message_typed.hip).
+the reference layer, each backward the matching ``impnn_*_bwd`` entry (csrc/layer_adjoints.hip,
+bond_matrices_train.hip, gated_update_bwd.hip; the message adjoint and its edge sort: csrc/message_typed.hip).
 ``ops.*`` routes through these nodes whenever an input requires grad and grad mode is on; with no grad
 the calls are the plain forward entries.  torch.autograd only keeps the graph - no torch op computes here.
 A model's training pass uses the larger nodes at the end of this file (a batch-32 step is bound by the number of

@@ -13,7 +13,7 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB = CSRC / "libimpnn.so"
-SOURCES = ["api.hip", "layer_kernels.hip", "loader_kernels.hip", "train_kernels.hip", "embed_rows.hip", "metrics.hip", "model_head.hip", "message_typed.hip", "transfer_head.hip", "head_grid.hip", "transfer_grid.hip", "grid_select.hip", "grid_mask.hip", "grid_partners.hip", "grid_rank.hip", "grid_summary.hip", "grid_pareto.hip", "grid_domain.hip", "grid_diverse.hip", "ensemble_grid.hip", "transfer_mc_grid.hip", "encoder_plan.hip", "encoder_fused.hip", "encoder_typed.hip", "encoder_wide.hip", "wide_plan.hip", "wide_message.hip", "wide_update.hip", "wide_update_x3.hip"]
+SOURCES = ["api.hip", "layer_kernels.hip", "loader_kernels.hip", "layer_adjoints.hip", "bond_matrices_train.hip", "gated_update_bwd.hip", "optimizer.hip", "dropout.hip", "embed_rows.hip", "metrics.hip", "model_head.hip", "message_typed.hip", "transfer_head.hip", "head_grid.hip", "transfer_grid.hip", "grid_select.hip", "grid_mask.hip", "grid_partners.hip", "grid_rank.hip", "grid_summary.hip", "grid_pareto.hip", "grid_domain.hip", "grid_diverse.hip", "ensemble_grid.hip", "transfer_mc_grid.hip", "encoder_plan.hip", "encoder_fused.hip", "encoder_typed.hip", "encoder_wide.hip", "wide_plan.hip", "wide_message.hip", "wide_update.hip", "wide_update_x3.hip"]
 ARCH = "gfx950"
 
 

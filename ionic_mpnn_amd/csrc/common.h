@@ -472,8 +472,7 @@ int64_t bmm_message_typed_bwd_workspace_ints(int B, int E, int Vb);
 int launch_bmm_message_typed_sorted(const TypedMessageCall& c);  // a checked call (api.hip)
 int launch_bmm_message_typed_bwd(const TypedMessageCall& c);     // a checked call (api.hip)
 
-// ---- backward + optimizer (train_kernels.hip): embedding / pool / Reduce adjoints, bond-table gradient, GatedUpdate
-// backward, dropout step, Adam
+// ---- the small adjoints (layer_adjoints.hip): embedding, Reduce, pool
 int launch_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable, int64_t rows, int vocab, int dim,
                             hipStream_t s);
 // (embed_rows.hip) the listed rows' gradient, in one summation order and without float atomics
@@ -482,23 +481,22 @@ int launch_embed_rows_bwd(const int32_t* ids, const float* dout, const int32_t* 
 int launch_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int tgt_stride, float* dm, int B, int N, int E,
                               int D, hipStream_t s);
 int launch_global_sum_pool_bwd(const float* dp, const int32_t* ids, float* dh, int B, int N, int D, hipStream_t s);
-int launch_strided_gemm(const float* A, const float* B, float* out, int64_t rows, int M, int N, int64_t a_rs,
-                        int64_t a_cs, int64_t b_rs, int64_t b_cs, hipStream_t s);
+// ---- bond-type matrices in training (bond_matrices_train.hip): the bond-table gradient, all layers in one launch
+int launch_bond_type_matrices_bwd(const float* tb, const float* W, const float* dA, float* dW, float* dtb, int Vb,
+                                  int K, int D, int accumulate, hipStream_t s);
 int launch_bond_type_matrices_multi(const float* tb, const float* const* W, float* const* out, int n, int Vb, int K,
                                     int D, hipStream_t s);
 int launch_bond_type_matrices_multi_bwd(const float* tb, const float* const* W, const float* const* dA,
                                         float* const* dW, float* dtb, int n, int Vb, int K, int D, int accumulate,
                                         hipStream_t s, float* workspace = nullptr);
 int64_t bond_type_matrices_multi_bwd_workspace(int n, int Vb, int K, int D);
-int launch_bond_type_matrices_bwd(const float* tb, const float* W, const float* dA, float* dW, float* dtb, int Vb,
-                                  int K, int D, int accumulate, hipStream_t s);
-int gated_update_bwd_blocks(int64_t rows, int D);
+// ---- GatedUpdate backward (gated_update_bwd.hip), and the one-pass GEMM the bond-table gradient borrows for K >= 64
+int launch_strided_gemm(const float* A, const float* B, float* out, int64_t rows, int M, int N, int64_t a_rs,
+                        int64_t a_cs, int64_t b_rs, int64_t b_cs, hipStream_t s);
 int64_t gated_update_param_floats(int D);
 int64_t gated_update_bwd_workspace(int64_t rows, int D, bool row_list = false);
 int launch_gated_update_bwd(const GatedUpdateCall& c);  // a checked call (api.hip)
-int launch_dropout_step(int64_t* counter, int64_t* snapshot, hipStream_t s);
-int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t* nrows_dev, int64_t max_rows, int D,
-                        float* out, hipStream_t s);
+// ---- optimizer (optimizer.hip): Adam, the learning-rate schedule
 int launch_adam_clipnorm(const void* table, const void* sizes, int n_vars, int64_t step, int64_t* step_dev, float lr,
                          float b1, float b2, float eps, float clipnorm, hipStream_t s);
 // The learning-rate record of impnn_adam_step_scheduled (include/impnn.h): word indices and schedule kinds.
@@ -512,6 +510,10 @@ int launch_adam_scheduled(const void* table, const void* sizes, int n_vars, int6
                           float b1, float b2, float eps, float clipnorm, float global_clipnorm, float weight_decay,
                           const int32_t* decay_flags, float* partials, hipStream_t s);
 int launch_lr_schedule_eval(const void* record, const int64_t* steps, float* out, int n, hipStream_t s);
+// ---- dropout counter and mask (dropout.hip)
+int launch_dropout_step(int64_t* counter, int64_t* snapshot, hipStream_t s);
+int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t* nrows_dev, int64_t max_rows, int D,
+                        float* out, hipStream_t s);
 
 // ---- batch assembly (loader_kernels.hip)
 int launch_batch_assemble(int n_ions, const int32_t* sample_idx, int B, int M, const int32_t* const* atom_flat,

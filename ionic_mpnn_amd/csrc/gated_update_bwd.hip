@@ -1,311 +1,16 @@
-// Backward kernels of the layer-at-a-time path and the optimizer step: what Keras
-// autodiff + Adam(1e-3, clipnorm=1.0) do for the reference's model.fit (train_viscosity.py:227-230,
-// 328-338; train_melting_point.py:205-208).  One kernel per reference layer, the adjoint of the forward
-// in layer_kernels.hip with the same masks (models/layers.py:114-115, :70 tgt > 0) and the same
-// "out-of-range index == padding" rule.  Written for any D (VALU, f32); the parameter-gradient sums run
-// over per-workgroup partial buffers that a second kernel adds in a fixed order, except where noted.
-// Holds the embedding, pool and Reduce adjoints, the bond-table gradient, the GatedUpdate backward and Adam; the message
-// adjoint (a4) and its edge sort are in message_typed.hip, the model head's backward in model_head.hip.
+// The GatedUpdate backward: what Keras autodiff does for the reference's GatedUpdate layer (a7,
+// models/layers.py:142-156), the adjoint of the forward in layer_kernels.hip with the same dropout mask.  A main kernel
+// per row tile (generic VALU for any D, one for atom_dim 32, a matrix-core one for 64 / 128), split-K GEMMs for the
+// three kernel gradients, and a reduction: the parameter-gradient sums run over per-workgroup and per-chunk partial
+// buffers that the reduction adds in a fixed order, so they are bitwise reproducible.  GuBwdPlan lays the workspace
+// out, choose_gu_bwd picks the main kernel.  The message adjoint (a4) is in message_typed.hip, the model head's
+// backward in model_head.hip.
 #include "kernel_device.h"
 
 namespace impnn {
 namespace {
 
 __device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// ---------------------------------------------------------------------------------------
-// a1/a2 backward: dtable[ids[r], :] += dout[r, :]   (float atomics: rows of one id meet in any order).
-// Vocabularies are small (~10^2 rows), so thousands of rows collide on the same table row: when the table
-// fits LDS every workgroup first sums its rows there (LDS atomics) and touches HBM once per entry.
-// ---------------------------------------------------------------------------------------
-__global__ void embed_gather_bwd_kernel(const int32_t* __restrict__ ids, const float* __restrict__ dout,
-                                        float* __restrict__ dtable, int64_t rows, int vocab, int dim, int use_lds) {
-  extern __shared__ __align__(16) float smem[];
-  const int64_t total = rows * dim;
-  if (use_lds) {
-    const int tsize = vocab * dim;
-    for (int t = threadIdx.x; t < tsize; t += blockDim.x) smem[t] = 0.f;
-    __syncthreads();
-    // contiguous slice of rows per workgroup
-    const int64_t per = (total + gridDim.x - 1) / gridDim.x;
-    const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < total ? lo + per : total;
-    constexpr int kU = 8;  // independent (id, value) loads in flight per thread
-    for (int64_t t0 = lo + threadIdx.x; t0 < hi; t0 += (int64_t)kU * blockDim.x) {
-      float v[kU];
-      int at[kU];
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const int64_t t = t0 + (int64_t)u * blockDim.x;
-        at[u] = -1;
-        v[u] = 0.f;
-        if (t < hi) {
-          const int64_t r = t / dim;
-          const int id = ids[r];
-          v[u] = dout[t];
-          if ((unsigned)id < (unsigned)vocab) at[u] = id * dim + (int)(t - r * dim);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kU; ++u)
-        if (at[u] >= 0 && v[u] != 0.f) atomicAdd(&smem[at[u]], v[u]);  // (padding atoms: half of the rows, all zeros)
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < tsize; t += blockDim.x) {
-      const float v = smem[t];
-      if (v != 0.f) atomicAdd(&dtable[t], v);
-    }
-    return;
-  }
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = t / dim;
-    const int c = (int)(t - r * dim);
-    const int id = ids[r];
-    if ((unsigned)id < (unsigned)vocab) atomicAdd(&dtable[(int64_t)id * dim + c], dout[t]);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// a5 backward (models/layers.py:57-83): dmessages[b,e,:] = tgt > 0 ? dagg[b,tgt,:] : 0
-// ---------------------------------------------------------------------------------------
-__global__ void reduce_scatter_bwd_kernel(const float* __restrict__ dagg, const int32_t* __restrict__ tgt,
-                                          int tgt_stride, float* __restrict__ dm, int64_t BE, int N, int E, int D) {
-  const int64_t total = BE * D;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t be = t / D;
-    const int c = (int)(t - be * D);
-    const int64_t b = be / E;
-    const int tg = tgt[be * tgt_stride];
-    dm[t] = (tg > 0 && tg < N) ? dagg[(b * N + tg) * D + c] : 0.f;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// a8 backward (models/layers.py:161-164): dh[b,n,:] = atom_ids[b,n] > 0 ? dpooled[b,:] : 0
-// ---------------------------------------------------------------------------------------
-__global__ void global_sum_pool_bwd_kernel(const float* __restrict__ dp, const int32_t* __restrict__ ids,
-                                           float* __restrict__ dh, int64_t BN, int N, int D) {
-  const int64_t total = BN * D;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t bn = t / D;
-    const int c = (int)(t - bn * D);
-    dh[t] = ids[bn] > 0 ? dp[(bn / N) * D + c] : 0.f;
-  }
-}
-
-__global__ void zero_floats_kernel(float* __restrict__ p, int64_t n) {
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) p[t] = 0.f;
-}
-
-// ---------------------------------------------------------------------------------------
-// schedule A backward: A[v] = sum_k Tb[v,k] W[k]  =>  dW[k] = sum_v Tb[v,k] dA[v];  dTb[v,k] = <dA[v], W[k]>
-// ---------------------------------------------------------------------------------------
-__global__ void bond_type_matrices_bwd_w_kernel(const float* __restrict__ tb, const float* __restrict__ dA,
-                                                float* __restrict__ dW, int Vb, int K, int DD, int accumulate) {
-  const int k = blockIdx.y;
-  for (int ij = blockIdx.x * blockDim.x + threadIdx.x; ij < DD; ij += gridDim.x * blockDim.x) {
-    float acc = 0.f;
-    int v = 0;
-    for (; v + 16 <= Vb; v += 16) {  // 16 independent rows in flight; the adds stay in vocabulary order
-      float x[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) x[u] = dA[(int64_t)(v + u) * DD + ij];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) acc = fmaf(tb[(int64_t)(v + u) * K + k], x[u], acc);
-    }
-    for (; v < Vb; ++v) acc = fmaf(tb[(int64_t)v * K + k], dA[(int64_t)v * DD + ij], acc);
-    dW[(int64_t)k * DD + ij] = accumulate ? dW[(int64_t)k * DD + ij] + acc : acc;
-  }
-}
-__global__ void bond_type_matrices_bwd_t_kernel(const float* __restrict__ W, const float* __restrict__ dA,
-                                                float* __restrict__ dtb, int Vb, int K, int DD, int accumulate) {
-  // one wave per (v,k)
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (wave >= Vb * K) return;
-  const int v = wave / K, k = wave - v * K;
-  float acc = 0.f;
-  const float* da = dA + (int64_t)v * DD;
-  const float* w = W + (int64_t)k * DD;
-  int ij = lane;
-  for (; ij + 7 * 64 < DD; ij += 8 * 64) {  // 16 independent loads in flight per lane
-    float x[8], y[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      x[u] = da[ij + 64 * u];
-      y[u] = w[ij + 64 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = fmaf(x[u], y[u], acc);
-  }
-  for (; ij < DD; ij += 64) acc = fmaf(da[ij], w[ij], acc);
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-  if (lane == 0) dtb[(int64_t)v * K + k] = accumulate ? dtb[(int64_t)v * K + k] + acc : acc;
-}
-
-// ---------------------------------------------------------------------------------------
-// The same for ALL message layers of a model in one launch each (training at the reference's batch 32 is bound by
-// the number of launches, and these depend on the weights only): problem p = (ion, step) has its own W_p, the bond
-// embedding table is shared, so dTb sums over the problems.
-// ---------------------------------------------------------------------------------------
-constexpr int kBtmMax = 16;
-struct BtmBatch {
-  const float* W[kBtmMax];
-  const float* dA[kBtmMax];
-  float* out[kBtmMax];  // forward: A_p (Vb x DD); backward: dW_p (K x DD)
-  int n;
-};
-// kernel-argument tables are indexed with constants only (a dynamic index is a dependent kernarg load per use)
-#define BTM_STAGE(bt)                                                       \
-  __shared__ const float* sW[kBtmMax];                                      \
-  __shared__ const float* sdA[kBtmMax];                                     \
-  __shared__ float* sout[kBtmMax];                                          \
-  _Pragma("unroll") for (int q = 0; q < kBtmMax; ++q) if ((int)threadIdx.x == q) {  \
-    sW[q] = bt.W[q];                                                        \
-    sdA[q] = bt.dA[q];                                                      \
-    sout[q] = bt.out[q];                                                    \
-  }                                                                         \
-  __syncthreads();
-
-__global__ void bond_type_matrices_multi_kernel(const float* __restrict__ tb, BtmBatch bt, int Vb, int K, int DD) {
-  BTM_STAGE(bt)
-  const int v = blockIdx.y;
-  const float* W = sW[blockIdx.z];
-  float* out = sout[blockIdx.z];
-  for (int ij = blockIdx.x * blockDim.x + threadIdx.x; ij < DD; ij += gridDim.x * blockDim.x) {
-    float acc = 0.f;
-    for (int k = 0; k < K; ++k) acc = fmaf(tb[(int64_t)v * K + k], W[(int64_t)k * DD + ij], acc);  // as the single kernel
-    out[(int64_t)v * DD + ij] = acc;
-  }
-}
-// bond_dim <= 8 (the reference's 8): the K values W[k][ij] of a thread's element stay in registers while it walks the
-// bond types, so W is read once instead of once per type (at atom_dim 128: 6 MB instead of 436 MB of L2 reads over the
-// 12 layers; 86 -> ~15 us).  Same fmaf chain per output element as the kernel above: identical bits.
-constexpr int kBtmSmallK = 8;
-constexpr int kBtmTbMax = 4096;  // bond_table floats staged in LDS (Vb * K)
-__global__ __launch_bounds__(kBlock) void bond_type_matrices_multi_smallk_kernel(const float* __restrict__ tb, BtmBatch bt,
-                                                                                 int Vb, int K, int DD) {
-  BTM_STAGE(bt)
-  __shared__ float tb_s[kBtmTbMax];
-  for (int t = threadIdx.x; t < Vb * K; t += kBlock) tb_s[t] = tb[t];
-  __syncthreads();
-  const float* W = sW[blockIdx.y];
-  float* out = sout[blockIdx.y];
-  const int ij = blockIdx.x * kBlock + threadIdx.x;
-  if (ij >= DD) return;
-  float w[kBtmSmallK];
-#pragma unroll
-  for (int k = 0; k < kBtmSmallK; ++k) w[k] = k < K ? W[(int64_t)k * DD + ij] : 0.f;
-  for (int v = 0; v < Vb; ++v) {
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < kBtmSmallK; ++k)
-      if (k < K) acc = fmaf(tb_s[v * K + k], w[k], acc);
-    out[(int64_t)v * DD + ij] = acc;
-  }
-}
-
-__global__ void bond_type_matrices_multi_bwd_w_kernel(const float* __restrict__ tb, BtmBatch bt, int Vb, int K, int DD,
-                                                      int accumulate) {
-  BTM_STAGE(bt)
-  const int k = blockIdx.y;
-  const float* dA = sdA[blockIdx.z];
-  float* dW = sout[blockIdx.z];
-  for (int ij = blockIdx.x * blockDim.x + threadIdx.x; ij < DD; ij += gridDim.x * blockDim.x) {
-    float acc = 0.f;
-    int v = 0;
-    for (; v + 16 <= Vb; v += 16) {
-      float x[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) x[u] = dA[(int64_t)(v + u) * DD + ij];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) acc = fmaf(tb[(int64_t)(v + u) * K + k], x[u], acc);
-    }
-    for (; v < Vb; ++v) acc = fmaf(tb[(int64_t)v * K + k], dA[(int64_t)v * DD + ij], acc);
-    dW[(int64_t)k * DD + ij] = accumulate ? dW[(int64_t)k * DD + ij] + acc : acc;
-  }
-}
-__global__ void bond_type_matrices_multi_bwd_t_kernel(BtmBatch bt, float* __restrict__ dtb, int Vb, int K, int DD,
-                                                      int accumulate) {
-  BTM_STAGE(bt)
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (wave >= Vb * K) return;
-  const int v = wave / K, k = wave - v * K;
-  float acc = 0.f;
-  for (int p = 0; p < bt.n; ++p) {  // problems in order, then the lanes: a fixed summation order
-    const float* da = sdA[p] + (int64_t)v * DD;
-    const float* w = sW[p] + (int64_t)k * DD;
-    int ij = lane;
-    for (; ij + 7 * 64 < DD; ij += 8 * 64) {
-      float x[8], y[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        x[u] = da[ij + 64 * u];
-        y[u] = w[ij + 64 * u];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc = fmaf(x[u], y[u], acc);
-    }
-    for (; ij < DD; ij += 64) acc = fmaf(da[ij], w[ij], acc);
-  }
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-  if (lane == 0) dtb[(int64_t)v * K + k] = accumulate ? dtb[(int64_t)v * K + k] + acc : acc;
-}
-
-
-// ---------------------------------------------------------------------------------------
-// dtb[v,k] = sum_p sum_ij dA_p[v,ij] W_p[k,ij] on the matrix cores (exact f32 products): bond types on M (VT tiles of
-// 16), k on N (K <= 16, padded with zeros), the contraction over (p, ij) cut into chunks of kBtC per WAVE - a lane loads
-// 16 bytes of a dA row and of a W row per 16 contraction indices (the MFMA's k = the lane's quarter q, component r of
-// the quad: any bijection serves as long as both operands use it).  The per-wave partials land in `part`
-// ([wave][v][k]) and bond_type_matrices_t_sum_kernel adds them in wave order: bitwise reproducible.
-// The one-wave-per-output kernel above walked 12 x 16 K products per lane with eight loads in flight: 116-170 us at
-// atom_dim 128 - alone on the stream at the end of every backward pass, so all of it on the critical path of a step.
-// ---------------------------------------------------------------------------------------
-constexpr int kBtC = 256;
-template <int VT>
-__global__ __launch_bounds__(256) void bond_type_matrices_multi_bwd_t_mfma_kernel(BtmBatch bt, float* __restrict__ part,
-                                                                                  int Vb, int K, int DD, int waves) {
-  BTM_STAGE(bt)
-  const int w = blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = threadIdx.x & 63, a = lane & 15, q = lane >> 4;
-  if (w >= waves) return;
-  const int cpp = DD / kBtC, p = w / cpp, c0 = (w - p * cpp) * kBtC + 4 * q;
-  const float* Wp = sW[p] + (int64_t)(a < K ? a : 0) * DD + c0;
-  const float* dAp = sdA[p] + c0;
-  const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4_t acc[VT];
-#pragma unroll
-  for (int t = 0; t < VT; ++t) acc[t] = zero;
-#pragma unroll 2
-  for (int st = 0; st < kBtC / 16; ++st) {
-    const f32x4_t wv = a < K ? ldv4(Wp + 16 * st) : zero;
-    f32x4_t x[VT];
-#pragma unroll
-    for (int t = 0; t < VT; ++t) {
-      const int v = 16 * t + a;
-      x[t] = v < Vb ? ldv4(dAp + (int64_t)v * DD + 16 * st) : zero;
-    }
-#pragma unroll
-    for (int t = 0; t < VT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[t] = mfma_f32(x[t][r], wv[r], acc[t]);
-  }
-  float* mine = part + (int64_t)w * Vb * K;
-#pragma unroll
-  for (int t = 0; t < VT; ++t)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int v = 16 * t + 4 * q + g;
-      if (v < Vb && a < K) mine[v * K + a] = acc[t][g];
-    }
-}
-__global__ void bond_type_matrices_t_sum_kernel(const float* __restrict__ part, float* __restrict__ dtb, int VK, int waves,
-                                                int accumulate) {
-  const int e = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-  if (e >= VK) return;
-  float acc = 0.f;
-  for (int w = lane; w < waves; w += 64) acc += part[(int64_t)w * VK + e];
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-  if (lane == 0) dtb[e] = accumulate ? dtb[e] + acc : acc;
-}
 
 // ---------------------------------------------------------------------------------------
 // a7 backward (models/layers.py:142-156).  Forward per row, c = [h|agg]:
@@ -1576,213 +1281,7 @@ __global__ void gated_update_reduce_kernel(const float* __restrict__ small, cons
   if (lane == 0) dparams[q] = accumulate ? dparams[q] + acc : acc;
 }
 
-// ---------------------------------------------------------------------------------------
-// Optimizer step: keras.optimizers.Adam(lr, clipnorm) as the trainers configure it
-// (train_viscosity.py:227-230).  kAdamSplit workgroups per variable: each forms the variable's gradient norm itself
-// (the same thread-strided sum in the same order in every workgroup, so all of them scale by the identical factor - no
-// partials buffer, no second launch) and updates its own 1/kAdamSplit of the elements; with one workgroup per variable
-// the step took as long as one workgroup needs for the largest variable (172 us at atom_dim 128: bond_transform, 131 K
-// floats through one workgroup's 20 GB/s):
-//   g <- g * clipnorm / max(||g||_2, clipnorm)          (tf.clip_by_norm, per variable; clipnorm <= 0: off)
-//   m <- b1 m + (1-b1) g;  v <- b2 v + (1-b2) g^2
-//   w <- w - lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
-// The variable table holds device pointers: 4 per variable (w, g, m, v) and the element count.
-// ---------------------------------------------------------------------------------------
-__global__ void incr_step_kernel(long long* step) { *step += 1; }
-constexpr int kAdamSplit = 16;
-
-// The learning rate of update number s (s updates already applied) from the 32-word record of impnn.h
-// (impnn_adam_step_scheduled); every value in it is uniform, so the loads are scalar.  An unknown kind gives NaN.
-__device__ __forceinline__ float lr_schedule_rate(const int* __restrict__ rec, long long s) {
-  const int kind = rec[kLrKind];
-  const float lr0 = __int_as_float(rec[kLrBase]);
-  if (kind == kLrConstant) return lr0;
-  if (kind == kLrExponential) {
-    float p = (float)s / (float)rec[kLrDecaySteps];
-    if (rec[kLrFlags] & 1) p = floorf(p);  // staircase
-    return lr0 * powf(__int_as_float(rec[kLrParam]), p);
-  }
-  if (kind == kLrCosine) {
-    const long long warm = rec[kLrWarmupSteps], dsteps = rec[kLrDecaySteps];
-    const float target = __int_as_float(rec[kLrTarget]), alpha = __int_as_float(rec[kLrParam]);
-    if (s < warm) return (target - lr0) * ((float)s / (float)warm) + lr0;
-    const long long sp = s - warm < dsteps ? s - warm : dsteps;
-    const float c = 0.5f * (1.0f + cosf(3.14159265358979323846f * ((float)sp / (float)dsteps)));
-    return target * ((1.0f - alpha) * c + alpha);
-  }
-  if (kind == kLrPiecewise) {
-    int nb = rec[kLrBoundaryCount];
-    nb = nb < 0 ? 0 : nb > kLrMaxBoundaries ? kLrMaxBoundaries : nb;
-    int i = 0;
-    while (i < nb && s > (long long)rec[kLrBoundaries + i]) ++i;
-    return __int_as_float(rec[kLrValues + i]);
-  }
-  return __int_as_float(0x7fc00000);
-}
-
-__global__ void lr_schedule_eval_kernel(const int* __restrict__ rec, const long long* __restrict__ steps,
-                                        float* __restrict__ out, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = lr_schedule_rate(rec, steps[i]);
-}
-
-// What impnn_adam_step_scheduled adds to the operands of the update kernel; the plain instantiation reads none of it.
-struct AdamExtras {
-  const int* rec;          // learning-rate record
-  const float* partials;   // kGlobal: n_vars * kAdamSplit sums of squares (adam_sumsq_kernel)
-  const int* decay_flags;  // kDecay: one word per variable, non-zero = the variable decays
-  float global_clipnorm, weight_decay;
-};
-
-// The [lo, hi) of workgroup y of a variable of n elements: the update kernel and the sum-of-squares kernel cut alike.
-__device__ __forceinline__ void adam_slice(long long n, long long& lo, long long& hi) {
-  long long per = (n + gridDim.y - 1) / gridDim.y;
-  if (per < 4096) per = 4096;  // small variables stay with their first workgroup(s)
-  lo = (long long)blockIdx.y * per;
-  hi = lo + per < n ? lo + per : n;
-}
-
-// global_clipnorm, first launch: partials[var * kAdamSplit + y] = sum of g^2 over slice y of variable var (0 for an
-// empty slice), thread-strided and reduced in a fixed order.
-__global__ __launch_bounds__(1024) void adam_sumsq_kernel(const unsigned long long* __restrict__ table,
-                                                          const long long* __restrict__ sizes,
-                                                          float* __restrict__ partials) {
-  __shared__ float red[16];
-  const int var = blockIdx.x;
-  const float* g = reinterpret_cast<const float*>(table[4 * var + 1]);
-  long long lo, hi;
-  adam_slice(sizes[var], lo, hi);
-  float ss = 0.f;
-  for (long long t = lo + threadIdx.x; t < hi; t += blockDim.x) ss = fmaf(g[t], g[t], ss);
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tot += red[i];
-    partials[(long long)var * gridDim.y + blockIdx.y] = tot;
-  }
-}
-
-// kSched: the rate comes from the record and the device counter.  kGlobal: tf.clip_by_global_norm - every workgroup adds
-// the partials itself, slices of a variable in slice order, then variables in variable order, so all of them hold the
-// same bits; a non-finite norm gives the scale NaN (every update of the step is NaN, as in TensorFlow).  kDecay: keras's
-// decoupled weight decay, w <- w - lr_t * wd * w ahead of the update, for the variables whose flag is set.
-template <bool kSched, bool kGlobal, bool kDecay>
-__global__ __launch_bounds__(1024) void adam_clipnorm_kernel(const unsigned long long* __restrict__ table,
-                                                             const long long* __restrict__ sizes, float lr,
-                                                             float b1, float b2, float eps, float clipnorm,
-                                                             float corr1, float corr2,
-                                                             const long long* __restrict__ step_dev, AdamExtras ex) {
-  if (step_dev) {  // step counter in device memory (a captured hipGraph replays with a new step every time)
-    const float t = (float)*step_dev;
-    corr1 = 1.0f - powf(b1, t);
-    corr2 = 1.0f - powf(b2, t);
-  }
-  if constexpr (kSched) lr = lr_schedule_rate(ex.rec, *step_dev - 1);  // keras: the schedule at `iterations` before the update
-  __shared__ float red[16];
-  __shared__ float scale_s;
-  const int var = blockIdx.x;
-  float* w = reinterpret_cast<float*>(table[4 * var + 0]);
-  const float* g = reinterpret_cast<const float*>(table[4 * var + 1]);
-  float* m = reinterpret_cast<float*>(table[4 * var + 2]);
-  float* v = reinterpret_cast<float*>(table[4 * var + 3]);
-  const long long n = sizes[var];
-  if ((long long)blockIdx.y * 4096 >= n && blockIdx.y > 0) return;  // no elements for this workgroup
-  if constexpr (kGlobal) {
-    __shared__ float var_s[1024];
-    const int nv = gridDim.x;
-    float tot = 0.f;  // (thread 0's is the sum)
-    for (int base = 0; base < nv; base += 1024) {
-      const int q = base + (int)threadIdx.x;
-      if (q < nv) {
-        float a = 0.f;
-        for (int k = 0; k < kAdamSplit; ++k) a += ex.partials[(long long)q * kAdamSplit + k];
-        var_s[threadIdx.x] = a;
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const int cnt = nv - base < 1024 ? nv - base : 1024;
-        for (int i = 0; i < cnt; ++i) tot += var_s[i];
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      const float norm = sqrtf(tot), c = ex.global_clipnorm;
-      scale_s = norm - norm == 0.f ? c / fmaxf(norm, c) : __int_as_float(0x7fc00000);  // (inf - inf, nan - nan: NaN)
-    }
-  } else {
-    float ss = 0.f;
-    if ((reinterpret_cast<uintptr_t>(g) & 15u) == 0) {  // 16-byte loads (every workgroup of the variable takes this path or none)
-      const long long n4 = n >> 2;
-      for (long long t = threadIdx.x; t < n4; t += blockDim.x) {
-        const f32x4_t x = ldv4(g + 4 * t);
-        ss = fmaf(x[0], x[0], ss);
-        ss = fmaf(x[1], x[1], ss);
-        ss = fmaf(x[2], x[2], ss);
-        ss = fmaf(x[3], x[3], ss);
-      }
-      for (long long t = 4 * n4 + threadIdx.x; t < n; t += blockDim.x) ss = fmaf(g[t], g[t], ss);
-    } else {
-      for (long long t = threadIdx.x; t < n; t += blockDim.x) ss = fmaf(g[t], g[t], ss);
-    }
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_down(ss, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float tot = 0.f;
-      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tot += red[i];
-      const float norm = sqrtf(tot);
-      scale_s = clipnorm > 0.f ? clipnorm / fmaxf(norm, clipnorm) : 1.0f;
-    }
-  }
-  __syncthreads();
-  const float sc = scale_s;
-  const float alpha = lr * sqrtf(corr2) / corr1;  // corr1 = 1 - b1^t, corr2 = 1 - b2^t
-  long long per = (n + gridDim.y - 1) / gridDim.y;
-  if (per < 4096) per = 4096;  // small variables stay with their first workgroup(s)
-  const long long lo = (long long)blockIdx.y * per, hi = lo + per < n ? lo + per : n;
-  float decay = 0.f;
-  if constexpr (kDecay) decay = ex.decay_flags[var] ? lr * ex.weight_decay : 0.f;
-  for (long long t = lo + threadIdx.x; t < hi; t += blockDim.x) {
-    const float gg = g[t] * sc;
-    const float mm = b1 * m[t] + (1.0f - b1) * gg;
-    const float vv = b2 * v[t] + (1.0f - b2) * gg * gg;
-    m[t] = mm;
-    v[t] = vv;
-    if constexpr (kDecay) {
-      const float ww = w[t];
-      w[t] = (decay != 0.f ? ww - ww * decay : ww) - alpha * mm / (sqrtf(vv) + eps);
-    } else {
-      w[t] -= alpha * mm / (sqrtf(vv) + eps);
-    }
-  }
-}
-
 }  // namespace
-
-int launch_embed_gather_bwd(const int32_t* ids, const float* dout, float* dtable, int64_t rows, int vocab, int dim,
-                            hipStream_t s) {
-  const size_t lds = sizeof(float) * (size_t)vocab * dim;
-  const int use_lds = lds <= 64 * 1024 && rows * dim >= 8 * (int64_t)vocab * dim;
-  if (use_lds && lds > 48 * 1024)
-    (void)hipFuncSetAttribute((const void*)embed_gather_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  embed_gather_bwd_kernel<<<grid_for(rows * dim, use_lds ? 512 : 256 * 8), kBlock, use_lds ? lds : 0, s>>>(
-      ids, dout, dtable, rows, vocab, dim, use_lds);
-  return check_launch("embed_gather_bwd");
-}
-
-int launch_reduce_scatter_bwd(const float* dagg, const int32_t* tgt, int tgt_stride, float* dm, int B, int N, int E,
-                              int D, hipStream_t s) {
-  reduce_scatter_bwd_kernel<<<grid_for((int64_t)B * E * D), kBlock, 0, s>>>(dagg, tgt, tgt_stride, dm,
-                                                                              (int64_t)B * E, N, E, D);
-  return check_launch("reduce_scatter_bwd");
-}
-
-int launch_global_sum_pool_bwd(const float* dp, const int32_t* ids, float* dh, int B, int N, int D, hipStream_t s) {
-  global_sum_pool_bwd_kernel<<<grid_for((int64_t)B * N * D), kBlock, 0, s>>>(dp, ids, dh, (int64_t)B * N, N, D);
-  return check_launch("global_sum_pool_bwd");
-}
 
 // out[M x N] = sum_r A(r,m) B(r,n) in one pass (no split: deterministic, no workspace)
 int launch_strided_gemm(const float* A, const float* B, float* out, int64_t rows, int M, int N, int64_t a_rs,
@@ -1795,342 +1294,153 @@ int launch_strided_gemm(const float* A, const float* B, float* out, int64_t rows
   return check_launch("strided_gemm");
 }
 
-int launch_bond_type_matrices_bwd(const float* tb, const float* W, const float* dA, float* dW, float* dtb, int Vb,
-                                  int K, int D, int accumulate, hipStream_t s) {
-  const int DD = D * D;
-  if (K >= 64) {
-    if (accumulate) return fail(IMPNN_E_UNSUPPORTED, "bond_type_matrices_bwd: accumulate needs K < 64");  // GEMM-shaped: dW (K x DD) = Tb^T dA over Vb rows; dTb (Vb x K) = dA W^T over DD rows
-    if (int rc = launch_strided_gemm(tb, dA, dW, Vb, K, DD, K, 1, DD, 1, s)) return rc;
-    return launch_strided_gemm(dA, W, dtb, DD, Vb, K, 1, DD, 1, DD, s);
-  }
-  bond_type_matrices_bwd_w_kernel<<<dim3((DD + kBlock - 1) / kBlock, K), kBlock, 0, s>>>(tb, dA, dW, Vb, K, DD, accumulate);
-  if (int rc = check_launch("bond_type_matrices_bwd_w")) return rc;
-  const int64_t waves = (int64_t)Vb * K;
-  bond_type_matrices_bwd_t_kernel<<<(int)((waves * 64 + kBlock - 1) / kBlock), kBlock, 0, s>>>(W, dA, dtb, Vb, K, DD,
-                                                                                               accumulate);
-  return check_launch("bond_type_matrices_bwd_t");
-}
-
-static int gu_main_blocks(int64_t rows, int D) {
-  // tiles of the main kernel: kBlock / D rows (generic kernels), 16 or 64 rows (the wide matrix-core kernel)
-  const int R = (D == 64 || D == 128) ? gu_wide_tile_rows(rows) : kBlock / D;
-  const int64_t ntile = (rows + R - 1) / R;
-  return (int)(ntile < 1024 ? (ntile < 1 ? 1 : ntile) : 1024);
-}
-// 128 x 64 output tiles: atom_dim 64 / 128 from 8 K rows (below that the 64 x 32 tiles give 4x the workgroups: 1.445
-// vs 1.478 ms per step at batch 32)
-static bool gu_big_tiles(int D, int64_t rows) { return D % kBN == 0 && (2 * D) % kBM == 0 && rows >= 8192; }
-static int gu_tiles(int D, int64_t rows, int* tiles_n) {
-  const int gn = gu_big_tiles(D, rows) ? kBN : kGN, gm = gu_big_tiles(D, rows) ? kBM : kGM;
-  const int tn = (D + gn - 1) / gn, tm = (2 * D + gm - 1) / gm;
-  if (tiles_n) *tiles_n = tn;
-  return tm * tn;
-}
-static int gu_chunks(int64_t rows, int D) {
-  const int tiles = gu_tiles(D, rows, nullptr);
-  // ~1024 workgroups of the 64 x 32 tiles, ~768 (three resident per CU) of the 128 x 64 ones
-  int64_t want = gu_big_tiles(D, rows) ? (768 + 3 * tiles - 1) / (3 * tiles) : (1024 + 3 * tiles - 1) / (3 * tiles);
-  const int64_t cap = (rows + 255) / 256;  // at least 256 contraction rows per chunk: fewer partials to write and add
-  if (want > cap) want = cap;
-  return (int)(want < 1 ? 1 : want);
-}
-
-int gated_update_bwd_blocks(int64_t rows, int D) { return gu_main_blocks(rows, D); }
-
 int64_t gated_update_param_floats(int D) { return 3 * ((int64_t)2 * D * D + D) + 2 * D; }
 
-// workspace (floats): dpre rows*3D | r*h rows*D | small nblk*5D | GEMM partials 3*nchunk*2D*D | W^T 3*2D*D
-// (row-list form: + compact copies of the rows' h and agg, rows*2D)
-int64_t gated_update_bwd_workspace(int64_t rows, int D, bool row_list) {
-  return rows * 4 * D + (int64_t)gu_main_blocks(rows, D) * 5 * D + (int64_t)3 * gu_chunks(rows, D) * 2 * D * D +
-         (int64_t)3 * 2 * D * D + (row_list ? rows * 2 * D : 0);
+// The launch sizes of a backward over `rows` rows and the workspace they fix, as float offsets:
+//   dpre rows*3D | rh (r*h) rows*D | small nblk*5D | gpart (GEMM partials) 3*nchunk*2D*D | wt (W^T) 3*2D*D
+//   | hc, aggc (compact copies of the listed rows' h and agg) rows*D each: row-list form only, -1 without
+struct GuBwdPlan {
+  int nblk, nchunk, tiles, tiles_n;  // main-kernel workgroups; row chunks, output tiles (and tiles along N) of the GEMMs
+  bool big_tiles;
+  int64_t dpre, rh, small, gpart, wt, hc, aggc, total;
+};
+static GuBwdPlan gu_bwd_plan(int64_t rows, int D, bool row_list) {
+  GuBwdPlan p;
+  // tiles of the main kernel: kBlock / D rows (generic kernels), 16 or 64 rows (the wide matrix-core kernel)
+  const int R = (D == 64 || D == 128) ? gu_wide_tile_rows(rows) : kBlock / D;
+  p.nblk = (int)std::min<int64_t>(std::max<int64_t>((rows + R - 1) / R, 1), 1024);
+  // 128 x 64 output tiles: atom_dim 64 / 128 from 8 K rows (below that the 64 x 32 tiles give 4x the workgroups: 1.445
+  // vs 1.478 ms per step at batch 32)
+  p.big_tiles = D % kBN == 0 && (2 * D) % kBM == 0 && rows >= 8192;
+  const int gn = p.big_tiles ? kBN : kGN, gm = p.big_tiles ? kBM : kGM;
+  p.tiles_n = (D + gn - 1) / gn;
+  p.tiles = (2 * D + gm - 1) / gm * p.tiles_n;
+  // ~1024 workgroups of the 64 x 32 tiles, ~768 (three resident per CU) of the 128 x 64 ones; at least 256 contraction
+  // rows per chunk: fewer partials to write and add
+  const int64_t want = ((p.big_tiles ? 768 : 1024) + 3 * p.tiles - 1) / (3 * p.tiles);
+  p.nchunk = (int)std::max<int64_t>(std::min<int64_t>(want, (rows + 255) / 256), 1);
+  const int64_t W3 = (int64_t)3 * 2 * D * D;
+  p.dpre = 0;
+  p.rh = p.dpre + rows * 3 * D;
+  p.small = p.rh + rows * D;
+  p.gpart = p.small + (int64_t)p.nblk * 5 * D;
+  p.wt = p.gpart + p.nchunk * W3;
+  p.hc = row_list ? p.wt + W3 : -1;
+  p.aggc = row_list ? p.hc + rows * D : -1;
+  p.total = row_list ? p.aggc + rows * D : p.wt + W3;
+  return p;
+}
+
+int64_t gated_update_bwd_workspace(int64_t rows, int D, bool row_list) { return gu_bwd_plan(rows, D, row_list).total; }
+
+// The main kernel of a backward.  al16: every tensor the kernel reads or writes is 16-byte aligned.
+enum class GuBwdRoute {
+  wide16,       // atom_dim 64 / 128 on the matrix cores
+  d32,          // atom_dim 32 on the matrix cores
+  generic_lds,  // any atom_dim, the gate kernels in LDS
+  generic_wt    // any atom_dim, 1024 threads, the transposed kernels in global memory
+};
+struct GuBwdChoice {
+  GuBwdRoute route;
+  int block, tile_rows;
+  size_t lds;      // dynamic LDS bytes
+  bool transpose;  // transpose3 fills wt first
+  int grid;        // workgroups, each of which writes its slice of `small`: the slices the reduction reads
+};
+static GuBwdChoice choose_gu_bwd(int D, int64_t rows, bool al16, bool saved) {
+  constexpr size_t F = sizeof(float);
+  const int nblk = gu_bwd_plan(rows, D, false).nblk;
+  if ((D == 64 || D == 128) && al16) {
+    const int tr = gu_wide_tile_rows(rows);  // (as the forward kernel: 16-row tiles below ~8 K rows)
+    const size_t lw = F * (64 * (2 * D + 4) + 64 * (D + 4) + 3 * 16 * 2 * D + 4 * 256) + 64 * sizeof(int32_t);
+    // (a workgroup whose tiles lie past the end of the row list writes zeros)
+    return {GuBwdRoute::wide16, 1024, tr, lw, true, (int)std::min<int64_t>((rows + tr - 1) / tr, nblk)};
+  }
+  if (D == 32 && al16)  // saved: no transposed kernels in LDS
+    return {GuBwdRoute::d32, kBlock, 16, F * ((saved ? 0 : 3 * 32 * kBwT) + 3 * 64 * kBwN + 4 * 32 + 4 * 5 * 32),
+            false, nblk};
+  // ten R x D tiles and 4 R row statistics, R = block / D; the closing column sums take 5 floats per thread
+  const auto tiles_lds = [D](int block) { return F * std::max(10 * (block / D) * D + 4 * (block / D), 5 * block); };
+  const size_t lds = tiles_lds(kBlock) + F * 3 * 2 * D * (D + 1);  // + the three gate kernels, row stride D + 1
+  if (lds <= 120 * 1024) return {GuBwdRoute::generic_lds, kBlock, kBlock / D, lds, false, nblk};
+  return {GuBwdRoute::generic_wt, 1024, 1024 / D, tiles_lds(1024), true, nblk};
 }
 
 // (api.hip has checked the call: atom_dim divides 256, and a row list or a `saved` buffer comes with an atom_dim and
 // alignment it covers)
 template <class... Drop>
 static int launch_gated_update_bwd_impl(const GatedUpdateCall& c, Drop... drop) {
-  const float *h = c.h, *agg = c.agg, *Wz = c.Wz, *bz = c.bz, *Wr = c.Wr, *br = c.br, *Wh = c.Wh, *bh = c.bh;
-  const float *gamma = c.gamma, *dout = c.dout;
-  const float eps = c.eps;
-  float *dh = c.dh, *dagg = c.dagg, *dparams = c.dparams, *workspace = c.workspace, *saved = c.saved;
-  const int32_t *ridx = c.row_index, *nrows_dev = c.n_rows;
   const int64_t rows = c.rows;
-  const int D = c.D, accumulate = c.accumulate;
+  const int D = c.D;
   const hipStream_t s = c.stream;
-  const int R = kBlock / D;
-  const int nblk = gu_main_blocks(rows, D), nchunk = gu_chunks(rows, D);
-  int nsmall = nblk;  // slices of `small` the reduction reads
+  const int32_t *ridx = c.row_index, *nrows_dev = c.n_rows;
+  const GuBwdPlan p = gu_bwd_plan(rows, D, ridx != nullptr);
   // saved (impnn_gated_update_rows_train's buffer, [z | r | tanh(t)] then r * h): used in place of the workspace's
   // first two regions and CONSUMED - it leaves holding the pre-activation gradients
-  float* dpre = saved ? saved : workspace;
-  float* rh = dpre + rows * 3 * D;
-  float* small = workspace + rows * 4 * D;
-  float* gpart = small + (int64_t)nblk * 5 * D;
-  float* wt = gpart + (int64_t)3 * nchunk * 2 * D * D;
-  float* hc = ridx ? wt + (int64_t)3 * 2 * D * D : nullptr;  // compact copies of the listed rows (row-list form)
-  float* aggc = ridx ? hc + rows * D : nullptr;
-  size_t lds = sizeof(float) * ((size_t)10 * R * D + 4 * R);
-  if (lds < sizeof(float) * 5 * kBlock) lds = sizeof(float) * 5 * kBlock;
-  const size_t wlds = sizeof(float) * (size_t)3 * 2 * D * (D + 1);
-  const bool al16 = ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(agg) | reinterpret_cast<uintptr_t>(dout) |
-                      reinterpret_cast<uintptr_t>(dh) | reinterpret_cast<uintptr_t>(dagg) |
-                      reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(dpre)) & 15u) == 0;
-  if ((D == 64 || D == 128) && al16) {
-    const size_t lw = sizeof(float) * ((size_t)64 * (2 * D + 4) + 64 * (D + 4) + 3 * 16 * 2 * D + 4 * 256) + 64 * sizeof(int32_t);
-    const int tile_rows = gu_wide_tile_rows(rows);  // (as the forward kernel: 16-row tiles below ~8 K rows)
-    transpose3_kernel<<<dim3((D + 31) / 32, (2 * D + 31) / 32, 3), dim3(32, 8), 0, s>>>(Wz, Wr, Wh, wt, D);
+  float *ws = c.workspace, *front = c.saved ? c.saved : ws;
+  float *dpre = front + p.dpre, *rh = front + p.rh, *small = ws + p.small, *gpart = ws + p.gpart, *wt = ws + p.wt;
+  float *hc = ridx ? ws + p.hc : nullptr, *aggc = ridx ? ws + p.aggc : nullptr;
+  const auto bits = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  const bool al16 =
+      ((bits(c.h) | bits(c.agg) | bits(c.dout) | bits(c.dh) | bits(c.dagg) | bits(ws) | bits(dpre)) & 15u) == 0;
+  const GuBwdChoice ch = choose_gu_bwd(D, rows, al16, c.saved != nullptr);
+  if (ch.transpose) {
+    transpose3_kernel<<<dim3((D + 31) / 32, (2 * D + 31) / 32, 3), dim3(32, 8), 0, s>>>(c.Wz, c.Wr, c.Wh, wt, D);
     if (int rc = check_launch("transpose3")) return rc;
-    const int64_t tiles64 = (rows + tile_rows - 1) / tile_rows;
-    const int nb = (int)(tiles64 < nblk ? tiles64 : nblk);  // every launched workgroup writes its slice of `small`
-    nsmall = nb;                                            // (zeros when the row list ends before its tiles)
-#define BWD16(NT_, SV_)                                                                                              \
-    do {                                                                                                              \
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_wide16_kernel<NT_, SV_, Drop...>,                       \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lw);                                 \
-      gated_update_bwd_wide16_kernel<NT_, SV_, Drop...><<<nb, 1024, lw, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, \
-                                                                            dout, dh, dagg, dpre, rh, small, rows,    \
-                                                                            ridx, nrows_dev, hc, aggc, tile_rows, wt, \
-                                                                            drop...);                                 \
-    } while (0)
-    if (D == 64) {
-      if (saved) BWD16(4, true); else BWD16(4, false);
-    } else {
-      if (saved) BWD16(8, true); else BWD16(8, false);
-    }
-#undef BWD16
-  } else if (D == 32 && al16) {
-    const size_t l32 = sizeof(float) * ((size_t)3 * 32 * kBwT + 3 * 64 * kBwN + 4 * 32 + 4 * 5 * 32);
-    if (l32 > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_d32_kernel<false, Drop...>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)l32);
-    if (saved) {
-      const size_t l32s = l32 - sizeof(float) * 3 * 32 * kBwT;  // no transposed kernels
-      gated_update_bwd_d32_kernel<true, Drop...><<<nblk, kBlock, l32s, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout,
-                                                                          dh, dagg, dpre, rh, small, rows, drop...);
-    } else {
-      gated_update_bwd_d32_kernel<false, Drop...><<<nblk, kBlock, l32, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout,
-                                                                           dh, dagg, dpre, rh, small, rows, drop...);
-    }
-  } else if (lds + wlds <= 120 * 1024) {
-    lds += wlds;
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_kernel<true, kBlock, Drop...>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gated_update_bwd_kernel<true, kBlock, Drop...><<<nblk, kBlock, lds, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout,
-                                                                             dh, dagg, dpre, rh, small, nullptr, rows, D, R,
-                                                                             drop...);
-  } else {
-    constexpr int kBig = 1024;
-    const int Rb = kBig / D;
-    size_t lb = sizeof(float) * ((size_t)10 * Rb * D + 4 * Rb);
-    if (lb < sizeof(float) * 5 * kBig) lb = sizeof(float) * 5 * kBig;
-    if (lb > 48 * 1024)
-      (void)hipFuncSetAttribute((const void*)gated_update_bwd_kernel<false, kBig, Drop...>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-    transpose3_kernel<<<dim3((D + 31) / 32, (2 * D + 31) / 32, 3), dim3(32, 8), 0, s>>>(Wz, Wr, Wh, wt, D);
-    if (int rc = check_launch("transpose3")) return rc;
-    gated_update_bwd_kernel<false, kBig, Drop...><<<nblk, kBig, lb, s>>>(h, agg, Wz, bz, Wr, br, Wh, bh, gamma, eps, dout, dh,
-                                                                         dagg, dpre, rh, small, wt, rows, D, Rb, drop...);
+  }
+  // every main kernel opens with the same sixteen operands and closes with the dropout pack
+  const auto run = [&](auto kernel, auto... tail) {
+    if (ch.lds > 48 * 1024)
+      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch.lds);
+    kernel<<<ch.grid, ch.block, ch.lds, s>>>(c.h, c.agg, c.Wz, c.bz, c.Wr, c.br, c.Wh, c.bh, c.gamma, c.eps, c.dout, c.dh,
+                                              c.dagg, dpre, rh, small, tail..., drop...);
+  };
+  const auto wide = [&](auto kernel) { run(kernel, rows, ridx, nrows_dev, hc, aggc, ch.tile_rows, (const float*)wt); };
+  switch (ch.route) {
+    case GuBwdRoute::wide16:
+      if (D == 64 && c.saved) wide(gated_update_bwd_wide16_kernel<4, true, Drop...>);
+      else if (D == 64) wide(gated_update_bwd_wide16_kernel<4, false, Drop...>);
+      else if (c.saved) wide(gated_update_bwd_wide16_kernel<8, true, Drop...>);
+      else wide(gated_update_bwd_wide16_kernel<8, false, Drop...>);
+      break;
+    case GuBwdRoute::d32:
+      if (c.saved) run(gated_update_bwd_d32_kernel<true, Drop...>, rows);
+      else run(gated_update_bwd_d32_kernel<false, Drop...>, rows);
+      break;
+    case GuBwdRoute::generic_lds:
+      run(gated_update_bwd_kernel<true, kBlock, Drop...>, (const float*)nullptr, rows, D, ch.tile_rows);
+      break;
+    case GuBwdRoute::generic_wt:
+      run(gated_update_bwd_kernel<false, 1024, Drop...>, (const float*)wt, rows, D, ch.tile_rows);
+      break;
   }
   if (int rc = check_launch("gated_update_bwd")) return rc;
-  int tiles_n = 1;
-  const int tiles = gu_tiles(D, rows, &tiles_n);
   GemmProblems ga;
-  const float* gh = ridx ? hc : h;      // the GEMMs contract over the listed rows: their compact copies
-  const float* ga_ = ridx ? aggc : agg;
+  const float* gh = ridx ? hc : c.h;      // the GEMMs contract over the listed rows: their compact copies
+  const float* ga_ = ridx ? aggc : c.agg;
   ga.A1[0] = gh; ga.A2[0] = ga_; ga.B[0] = dpre;
   ga.A1[1] = gh; ga.A2[1] = ga_; ga.B[1] = dpre + D;
   ga.A1[2] = rh; ga.A2[2] = ga_; ga.B[2] = dpre + 2 * D;
-  const bool al16g = ((reinterpret_cast<uintptr_t>(gh) | reinterpret_cast<uintptr_t>(ga_) | reinterpret_cast<uintptr_t>(rh) |
-                       reinterpret_cast<uintptr_t>(dpre)) & 15u) == 0;
-  if (gu_big_tiles(D, rows) && al16g)
-    strided_gemm_splitk_big_kernel<<<dim3(nchunk, tiles, 3), kBlock, 0, s>>>(ga, gpart, rows, 2 * D, D, D, D, 3 * D, nchunk,
-                                                                             tiles_n, ridx ? nrows_dev : nullptr);
-  else if (gu_big_tiles(D, rows))
+  const dim3 ggrid(p.nchunk, p.tiles, 3);
+  if (p.big_tiles && ((bits(gh) | bits(ga_) | bits(rh) | bits(dpre)) & 15u) != 0)
     return fail(IMPNN_E_BADARG, "gated_update_bwd: tensors must be 16B aligned at atom_dim %d", D);
+  if (p.big_tiles)
+    strided_gemm_splitk_big_kernel<<<ggrid, kBlock, 0, s>>>(ga, gpart, rows, 2 * D, D, D, D, 3 * D, p.nchunk, p.tiles_n,
+                                                            ridx ? nrows_dev : nullptr);
   else
-    strided_gemm_splitk_kernel<<<dim3(nchunk, tiles, 3), kBlock, 0, s>>>(ga, gpart, rows, 2 * D, D, D, D, 1, 3 * D, 1,
-                                                                         nchunk, tiles_n, ridx ? nrows_dev : nullptr);
+    strided_gemm_splitk_kernel<<<ggrid, kBlock, 0, s>>>(ga, gpart, rows, 2 * D, D, D, D, 1, 3 * D, 1, p.nchunk, p.tiles_n,
+                                                        ridx ? nrows_dev : nullptr);
   if (int rc = check_launch("strided_gemm_splitk")) return rc;
-  const int64_t welems = (int64_t)3 * 2 * D * D * (nchunk <= 64 ? 1 : 64);  // a thread or a wave per kernel element
+  const int64_t welems = (int64_t)3 * 2 * D * D * (p.nchunk <= 64 ? 1 : 64);  // a thread or a wave per kernel element
   const int wblocks = (int)((welems + kBlock - 1) / kBlock), vblocks = (5 * D * 64 + kBlock - 1) / kBlock;
-  gated_update_reduce_kernel<<<wblocks + vblocks, kBlock, 0, s>>>(small, gpart, dparams, nsmall, nchunk, D, accumulate,
-                                                                 wblocks);
+  gated_update_reduce_kernel<<<wblocks + vblocks, kBlock, 0, s>>>(small, gpart, c.dparams, ch.grid, p.nchunk, D,
+                                                                 c.accumulate, wblocks);
   return check_launch("gated_update_reduce");
 }
 
 int launch_gated_update_bwd(const GatedUpdateCall& c) {
   // the dropout instantiations of the main kernel; the GEMMs and the reduction behind it are the same
   return with_dropout_pack(c, [&](auto... drop) { return launch_gated_update_bwd_impl(c, drop...); });
-}
-
-// impnn_dropout_step: snapshot <- counter; counter += 1 (one thread; a captured step replays it)
-__global__ void dropout_step_kernel(long long* __restrict__ counter, long long* __restrict__ snapshot) {
-  const long long v = *counter;
-  *snapshot = v;
-  *counter = v + 1;
-}
-
-int launch_dropout_step(int64_t* counter, int64_t* snapshot, hipStream_t s) {
-  dropout_step_kernel<<<1, 1, 0, s>>>(reinterpret_cast<long long*>(counter), reinterpret_cast<long long*>(snapshot));
-  return check_launch("dropout_step");
-}
-
-// impnn_dropout_mask: out[row, c] = scale or 0, the mask the GatedUpdate kernels apply (one thread per column quad)
-__global__ void dropout_mask_kernel(DropoutArgs d, const int32_t* __restrict__ ridx, const int32_t* __restrict__ nrows_dev,
-                                    int64_t max_rows, int D, float* __restrict__ out) {
-  int64_t rows = max_rows;
-  if (nrows_dev) {
-    const int64_t n = *nrows_dev;
-    rows = n < 0 ? 0 : (n < max_rows ? n : max_rows);
-  }
-  const DropoutKey dk = dropout_key(d);
-  const int Q = (D + 3) / 4;
-  const int64_t n = rows * Q;
-  for (int64_t t4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t4 < n; t4 += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = t4 / Q;
-    const int c4 = (int)(t4 - i * Q);
-    int64_t row = ridx ? (int64_t)ridx[i] : i;
-    if (row < 0 || row >= max_rows) continue;  // (indices are never trusted)
-    const Philox4 bits = dropout_bits(dk, row, c4);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (4 * c4 + u < D) out[row * D + 4 * c4 + u] = dropout_apply(dk, bits.v[u], 1.0f);
-  }
-}
-
-int launch_dropout_mask(const DropoutArgs& d, const int32_t* ridx, const int32_t* nrows_dev, int64_t max_rows, int D,
-                        float* out, hipStream_t s) {
-  const int64_t n = max_rows * ((D + 3) / 4);
-  int64_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  dropout_mask_kernel<<<(unsigned)blocks, 256, 0, s>>>(d, ridx, nrows_dev, max_rows, D, out);
-  return check_launch("dropout_mask");
-}
-
-int launch_adam_clipnorm(const void* table, const void* sizes, int n_vars, int64_t step, int64_t* step_dev, float lr,
-                         float b1, float b2, float eps, float clipnorm, hipStream_t s) {
-  float corr1 = 1.0f, corr2 = 1.0f;
-  if (step_dev) {
-    incr_step_kernel<<<1, 1, 0, s>>>(reinterpret_cast<long long*>(step_dev));
-    if (int rc = check_launch("incr_step")) return rc;
-  } else {
-    corr1 = 1.0f - powf(b1, (float)step);
-    corr2 = 1.0f - powf(b2, (float)step);
-  }
-  adam_clipnorm_kernel<false, false, false><<<dim3(n_vars, kAdamSplit), 1024, 0, s>>>(
-      static_cast<const unsigned long long*>(table), static_cast<const long long*>(sizes), lr, b1, b2, eps, clipnorm,
-      corr1, corr2, reinterpret_cast<const long long*>(step_dev), AdamExtras{});
-  return check_launch("adam_clipnorm");
-}
-
-int64_t adam_scheduled_workspace(int n_vars) { return (int64_t)(n_vars > 0 ? n_vars : 0) * kAdamSplit; }
-
-int launch_adam_scheduled(const void* table, const void* sizes, int n_vars, int64_t* step_dev, const void* record,
-                          float b1, float b2, float eps, float clipnorm, float global_clipnorm, float weight_decay,
-                          const int32_t* decay_flags, float* partials, hipStream_t s) {
-  const auto* tb = static_cast<const unsigned long long*>(table);
-  const auto* sz = static_cast<const long long*>(sizes);
-  const auto* sd = reinterpret_cast<const long long*>(step_dev);
-  const bool global = global_clipnorm > 0.f, decay = decay_flags != nullptr;
-  incr_step_kernel<<<1, 1, 0, s>>>(reinterpret_cast<long long*>(step_dev));
-  if (int rc = check_launch("incr_step")) return rc;
-  if (global) {  // the one extra launch: per-(variable, slice) sums of squares
-    adam_sumsq_kernel<<<dim3(n_vars, kAdamSplit), 1024, 0, s>>>(tb, sz, partials);
-    if (int rc = check_launch("adam_sumsq")) return rc;
-  }
-  const AdamExtras ex{static_cast<const int*>(record), partials, decay_flags, global_clipnorm, weight_decay};
-  const dim3 grid(n_vars, kAdamSplit);
-#define ADAM_SCHEDULED(G, W) \
-  adam_clipnorm_kernel<true, G, W><<<grid, 1024, 0, s>>>(tb, sz, 0.f, b1, b2, eps, clipnorm, 1.0f, 1.0f, sd, ex)
-  if (global && decay) ADAM_SCHEDULED(true, true);
-  else if (global) ADAM_SCHEDULED(true, false);
-  else if (decay) ADAM_SCHEDULED(false, true);
-  else ADAM_SCHEDULED(false, false);
-#undef ADAM_SCHEDULED
-  return check_launch("adam_scheduled");
-}
-
-int launch_lr_schedule_eval(const void* record, const int64_t* steps, float* out, int n, hipStream_t s) {
-  lr_schedule_eval_kernel<<<(n + 255) / 256, 256, 0, s>>>(static_cast<const int*>(record),
-                                                         reinterpret_cast<const long long*>(steps), out, n);
-  return check_launch("lr_schedule_eval");
-}
-
-int launch_bond_type_matrices_multi(const float* tb, const float* const* W, float* const* out, int n, int Vb, int K,
-                                    int D, hipStream_t s) {
-  const int DD = D * D;
-  for (int p0 = 0; p0 < n; p0 += kBtmMax) {
-    BtmBatch bt{};
-    bt.n = n - p0 < kBtmMax ? n - p0 : kBtmMax;
-    for (int q = 0; q < bt.n; ++q) {
-      if (!W[p0 + q] || !out[p0 + q]) return fail(IMPNN_E_BADARG, "bond_type_matrices_multi: null tensor %d", p0 + q);
-      bt.W[q] = W[p0 + q];
-      bt.out[q] = out[p0 + q];
-    }
-    if (K <= kBtmSmallK && Vb * K <= kBtmTbMax && DD >= 4096)  // (small matrices: too few workgroups this way)
-      bond_type_matrices_multi_smallk_kernel<<<dim3((DD + kBlock - 1) / kBlock, bt.n), kBlock, 0, s>>>(tb, bt, Vb, K, DD);
-    else
-      bond_type_matrices_multi_kernel<<<dim3((DD + kBlock - 1) / kBlock, Vb, bt.n), kBlock, 0, s>>>(tb, bt, Vb, K, DD);
-    if (int rc = check_launch("bond_type_matrices_multi")) return rc;
-  }
-  return IMPNN_OK;
-}
-
-int64_t bond_type_matrices_multi_bwd_workspace(int n, int Vb, int K, int D) {
-  const int nb = n < kBtmMax ? n : kBtmMax;
-  return (int64_t)nb * ((int64_t)D * D / kBtC + 1) * Vb * K;
-}
-
-int launch_bond_type_matrices_multi_bwd(const float* tb, const float* const* W, const float* const* dA,
-                                        float* const* dW, float* dtb, int n, int Vb, int K, int D, int accumulate,
-                                        hipStream_t s, float* workspace) {
-  const int DD = D * D;
-  // with a workspace: the bond-table gradient on the matrix cores (partials per wave, summed in a fixed order)
-  const bool mfma_t = workspace && K <= 16 && Vb <= 128 && DD % kBtC == 0 && DD >= 4096 &&  // (small matrices: one launch less)
-                      (reinterpret_cast<uintptr_t>(workspace) & 15u) == 0;
-  for (int p0 = 0; p0 < n; p0 += kBtmMax) {
-    BtmBatch bt{};
-    bt.n = n - p0 < kBtmMax ? n - p0 : kBtmMax;
-    for (int q = 0; q < bt.n; ++q) {
-      if (!W[p0 + q] || !dA[p0 + q] || !dW[p0 + q])
-        return fail(IMPNN_E_BADARG, "bond_type_matrices_multi_bwd: null tensor %d", p0 + q);
-      bt.W[q] = W[p0 + q];
-      bt.dA[q] = dA[p0 + q];
-      bt.out[q] = dW[p0 + q];
-    }
-    bond_type_matrices_multi_bwd_w_kernel<<<dim3((DD + kBlock - 1) / kBlock, K, bt.n), kBlock, 0, s>>>(tb, bt, Vb, K, DD,
-                                                                                                     accumulate);
-    if (int rc = check_launch("bond_type_matrices_multi_bwd_w")) return rc;
-    bool al = mfma_t;
-    for (int q = 0; q < bt.n; ++q)
-      al = al && ((reinterpret_cast<uintptr_t>(bt.W[q]) | reinterpret_cast<uintptr_t>(bt.dA[q])) & 15u) == 0;
-    if (al) {
-      const int nw = bt.n * (DD / kBtC), nwg = (nw + 3) / 4, acc_t = (accumulate || p0 > 0) ? 1 : 0;
-      switch ((Vb + 15) / 16) {
-#define BTM_T(VT_)                                                                                                  \
-        case VT_:                                                                                                     \
-          bond_type_matrices_multi_bwd_t_mfma_kernel<VT_><<<nwg, 256, 0, s>>>(bt, workspace, Vb, K, DD, nw);          \
-          break;
-        BTM_T(1) BTM_T(2) BTM_T(3) BTM_T(4) BTM_T(5) BTM_T(6) BTM_T(7) BTM_T(8)
-#undef BTM_T
-      }
-      if (int rc = check_launch("bond_type_matrices_multi_bwd_t_mfma")) return rc;
-      bond_type_matrices_t_sum_kernel<<<(Vb * K * 64 + kBlock - 1) / kBlock, kBlock, 0, s>>>(workspace, dtb, Vb * K, nw,
-                                                                                           acc_t);
-      if (int rc = check_launch("bond_type_matrices_t_sum")) return rc;
-      continue;
-    }
-    const int64_t waves = (int64_t)Vb * K;
-    // (tried for bond_dim <= 8: one workgroup per bond type with the K partial dot products per thread, dA read once
-    //  instead of once per k - 71 workgroups are far too few: 116 us -> 1.3 ms at atom_dim 128)
-    bond_type_matrices_multi_bwd_t_kernel<<<(int)((waves * 64 + kBlock - 1) / kBlock), kBlock, 0, s>>>(
-        bt, dtb, Vb, K, DD, (accumulate || p0 > 0) ? 1 : 0);
-    if (int rc = check_launch("bond_type_matrices_multi_bwd_t")) return rc;
-  }
-  return IMPNN_OK;
 }
 
 }  // namespace impnn

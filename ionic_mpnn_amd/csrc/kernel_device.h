@@ -1,5 +1,6 @@
-// Device and launch helpers shared by train_kernels.hip, layer_kernels.hip, message_typed.hip, encoder_typed.hip and the
-// wide encoder (wide_device.h).
+// Device and launch helpers shared by layer_kernels.hip, the training files (layer_adjoints.hip, bond_matrices_train.hip,
+// gated_update_bwd.hip, optimizer.hip, dropout.hip), message_typed.hip, encoder_typed.hip and the wide encoder
+// (wide_device.h).
 #pragma once
 
 #include "common.h"

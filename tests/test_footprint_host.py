@@ -155,3 +155,31 @@ def test_the_size_queries_answer_without_a_device_positive_and_monotone():
     monotone(lambda b: lib.impnn_transfer_head_bwd_workspace_floats(b, 32, 20), "transfer head bwd workspace")
     assert lib.impnn_adam_step_scheduled_workspace_floats(3) > 0 and lib.impnn_transfer_grid_image_floats() > 0
     assert lib.impnn_regression_sums_words() == 8 and lib.impnn_model_head_floats(0, 32, 32, 20) > 0
+
+
+def gu_bwd_regions(rows, D, row_list=False):
+    """GuBwdPlan's regions (gated_update_bwd.hip), in floats and in workspace order."""
+    wide = D in (64, 128)
+    tile_rows = (16 if rows < 8192 else 64) if wide else 256 // D          # main-kernel tile
+    nblk = min(max(-(-rows // tile_rows), 1), 1024)                          # one slice of `small` per workgroup
+    big = D % 64 == 0 and (2 * D) % 128 == 0 and rows >= 8192                # 128 x 64 GEMM tiles, else 64 x 32
+    gm, gn = (128, 64) if big else (64, 32)
+    tiles = -(-2 * D // gm) * -(-D // gn)
+    nchunk = max(min(-(-(768 if big else 1024) // (3 * tiles)), -(-rows // 256)), 1)
+    regions = [("dpre", rows * 3 * D), ("rh", rows * D), ("small", nblk * 5 * D), ("gpart", 3 * nchunk * 2 * D * D),
+               ("wt", 3 * 2 * D * D)]
+    if row_list:
+        regions += [("hc", rows * D), ("aggc", rows * D)]
+    return regions
+
+
+def test_the_gated_update_backward_workspace_is_the_sum_of_its_regions():
+    lib = _lib.load()
+    total = lambda *a: sum(n for _, n in gu_bwd_regions(*a))
+    assert total(37, 32) == 17824 and dict(gu_bwd_regions(37, 32))["small"] == 5 * 5 * 32
+    assert total(9000, 128) == 8335488 and total(9000, 128, True) == 10639488
+    for D in (8, 16, 32, 64, 128, 256):
+        for rows in (0, 1, 255, 256, 257, 8191, 8192, 8193, 16384 * 4 + 1, 70001):
+            assert lib.impnn_gated_update_bwd_workspace_floats(rows, D) == total(rows, D), (rows, D)
+            if D in (64, 128):
+                assert lib.impnn_gated_update_rows_bwd_workspace_floats(rows, D) == total(rows, D, True), (rows, D)

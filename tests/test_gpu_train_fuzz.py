@@ -312,6 +312,32 @@ def test_gated_update_backward_into_the_flat_gradient_block(D, rows, kept):
     check_gated_update(f"D={D} rows={rows} kept={kept}", got, ref)
 
 
+# The main-kernel routes of the backward (choose_gu_bwd) that GU_CASES cannot reach: an atom_dim outside
+# {32, 64, 128}, or a tensor that starts one float into its allocation.  The id names the expected route.
+GuRoute = namedtuple("GuRoute", "name D rows misalign")
+GU_ROUTE_CASES = [
+    GuRoute("D=16 generic in-LDS", 16, 37, None),
+    GuRoute("D=256 generic 1024-thread transposed", 256, 21, None),
+    GuRoute("D=128 h off by one float: wide16 refused, 1024-thread transposed", 128, 75, "h"),
+    GuRoute("D=64 agg off by one float: wide16 refused, generic in-LDS at 110 KB", 64, 33, "agg"),
+    GuRoute("D=32 h off by one float: d32 refused, generic in-LDS", 32, 75, "h"),
+]
+
+
+@pytest.mark.parametrize("c", GU_ROUTE_CASES, ids=[c.name for c in GU_ROUTE_CASES])
+def test_gated_update_backward_routes(c):
+    """Plain backward (no row list, no kept activations), gradients handed back to the caller."""
+    inp = gated_update_inputs(c.D, c.rows, False)
+    ref = gated_update_reference(inp, torch.float64)
+    ps = [_dev(inp["p"][k]) for k in GU_NAMES]
+    h, agg = _dev(inp["h"], c.misalign == "h"), _dev(inp["agg"], c.misalign == "agg")
+    with torch.no_grad():
+        res = autograd._gated_update_backward((h, agg, *ps), 1e-3, _dev(inp["go"]))
+    torch.cuda.synchronize()
+    got = {"dh": res[0], "dagg": res[1], **dict(zip(GU_NAMES, res[2:10]))}
+    check_gated_update(c.name, got, ref)
+
+
 # =====================================================================================================================
 # Adam
 # =====================================================================================================================
